@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: moment-evals/s of one complete MLMC estimate on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--dump-outputs DIR] [--full]
 
 Defaults (no --config):
   N = 1  BASELINE.json configs[2], the largest single-GPU configuration: 5 levels x 1e7 synthetic samples, Legendre
          n_moments = 64, moment covariance mean + variance, level-variance regression and n_samples re-allocation
-         (reference: estimator.py:44-74,366-385).  The same JSON line carries three secondary blocks, each with its own
-         roofline: "moments_r64" (the stand-alone mean+var estimate on the same samples), "configs1" (BASELINE
+         (reference: estimator.py:44-74,366-385).  With --full the same JSON line carries three secondary blocks, each
+         with its own roofline: "moments_r64" (the stand-alone mean+var estimate on the same samples), "configs1" (BASELINE
          configs[1]: 3 x 1e7, R = 32, mean+var) and "north_star" (1e8 samples x 64 moments, moments + covariance).
   N > 1  BASELINE.json configs[3]: 5 levels x 1e8 samples sharded over the N ranks (strong scaling of the fixed 5e8
          samples; launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`),
@@ -18,6 +18,12 @@ transform + recurrence + mask + level-difference accumulation kernels), finalize
 N > 1, copy of the sums to the host) and the host formulas (level means / variances, MLMC totals; for the covariance
 configurations also the regression over the levels and the re-allocation, with the level variances of the moments
 read from row 0 of the covariance sums -- no second pass over the samples).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline of the timed steps).
+--full adds everything that takes runs of its own: the secondary blocks, the exchange block (N > 1), the PDF solve
+timing, the CPU baseline with its parity gate and the host-storage (h2d_inclusive) block.
+--dump-outputs DIR writes what the last timed step returned (sums, level statistics, MLMC totals, ...) as DIR/<name>.npy
+(float64); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -292,16 +298,20 @@ def estimate_block(cfg, data, fn, steps_h, ctx, steps, warmup, preroll_ms, confi
         # reset + push of every level + finalize: one call of the C ABI; with more than one rank the packed partial sums
         # stay on the device and go through ONE all-reduce before the host reads them
         n, n_rm, s, sp = acc.estimate(chunks)
-        _, _, mean, var = host_formulas(n, s, sp, level_stats)
+        l_means, l_vars, mean, var = host_formulas(n, s, sp, level_stats)
+        res = {"n_samples": n, "n_removed": n_rm, "sums": s, "sums_sq": sp, "level_means": l_means, "level_vars": l_vars,
+               "mean": mean, "var": var}
         if cfg["mode"] == "cov":
             s_m, sp_m = moments_from_covariance(s, sp, R)
             _, raw_vars = level_stats(n, s_m, sp_m)
             reg_vars = regress(raw_vars, np.array(steps_h))
-            extra["n_estimated"] = [int(v) for v in estimate_n_samples_for_target_variance(1e-6, reg_vars, n_ops, n_levels=L)]
-        return n, n_rm, mean, var
+            n_est = estimate_n_samples_for_target_variance(1e-6, reg_vars, n_ops, n_levels=L)
+            extra["n_estimated"] = [int(v) for v in n_est]
+            res.update(moments_level_vars=raw_vars, regressed_level_vars=reg_vars, n_estimated=n_est)
+        return res
 
     elapsed, pre, res, kt = timed_loop(one_estimate, acc, steps, warmup, preroll_ms, ctx)
-    n, n_rm, mean, var = res
+    n_rm, mean, var = res["n_removed"], res["mean"], res["var"]
     n_local = [int(data[l][0].shape[0]) for l in range(L)]
     samples_per_step = int(ctx.sum_over_ranks([float(sum(n_local))])[0])      # whole job: every rank's shard
     pairs, singles = sum(n_local[1:]), n_local[0]         # this rank's launches
@@ -312,6 +322,7 @@ def estimate_block(cfg, data, fn, steps_h, ctx, steps, warmup, preroll_ms, confi
         "result_check": {"mean0": float(np.ravel(mean)[0]), "var0": float(np.ravel(var)[0]), "n_removed": [int(v) for v in n_rm]},
     }
     out["result_check"].update(extra)
+    out["outputs"] = res
     acc.close()
     return out
 
@@ -401,17 +412,34 @@ def h2d_inclusive_block():
     return out
 
 
+def dump_outputs(directory, arrays, limit=64 << 20):
+    """--dump-outputs: the arrays the last timed step returned, one DIR/<name>.npy each, as float64 (counts included:
+    exact below 2^53)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise ValueError("--dump-outputs: {} bytes exceed the {} byte limit".format(total, limit))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=lambda v: int(v) if v.isdigit() else v, default=None, choices=[2, 3, 4, 5, 6, "sharded"],
-                    help="default: 3 (BASELINE configs[2]) + secondary blocks at N = 1, configs[3] sharded at N > 1; "
+                    help="default: 3 (BASELINE configs[2]; + secondary blocks with --full) at N = 1, configs[3] sharded at N > 1; "
                          "`--gpus 1 --config sharded` runs the WHOLE configs[3] job (5 x 1e8 samples, 8 GB) on one GPU: the "
                          "N = 1 point of the same strong-scaling workload the N > 1 default measures")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="N = 1 default line without the secondary blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: secondary blocks, exchange block (N > 1), PDF solve timing, "
+                         "CPU baseline + parity gate, host-storage block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity gate")
+    ap.add_argument("--no-secondary", action="store_true", help="--full N = 1 default line without the secondary blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--preroll-ms", type=float, default=250.0,
                     help="untimed load before the W warm-up steps: the shader clock of an idle MI355X needs ~70 ms of "
                          "continuous work to reach its steady state (0 = none)")
@@ -488,6 +516,8 @@ def main():
     data = synth_device(list(range(L)), lo, hi, steps_h, dev, seed=data_seed)
 
     head = estimate_block(cfg, data, fn, steps_h, ctx, args.steps, args.warmup, args.preroll_ms, key)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["outputs"])
     out = {
         "metric": "moment-evals/sec (samples x n_moments)", "value": head["value"], "unit": "moment-evals/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "preroll_steps": head["preroll_steps"],
@@ -500,6 +530,8 @@ def main():
     }
     if key == "sharded":
         out["config"]["samples_per_level_total"] = cfg["n_total_per_level"]
+    if not args.full:
+        return finish(out)
     if dist.is_initialized() and cfg["mode"] == "cov":
         out["exchange"] = exchange_block(fn, L, R, ctx)
 
@@ -508,6 +540,7 @@ def main():
         # the stand-alone mean + variance estimate on the same samples (R = 64): the fp64-VALU figure beside the MFMA one
         mcfg = dict(cfg, mode="moments", workload="configs[2] samples, stand-alone Legendre n_moments=64 mean+var estimate")
         blk = estimate_block(mcfg, data, fn, steps_h, ctx, 50, 10, 0.0, 3)
+        blk.pop("outputs")
         out["moments_r64"] = dict(blk, config={"workload": mcfg["workload"], "levels": L, "samples_per_level_per_gpu": n_l, "n_moments": R})
         if "aux_kernel" in head["roofline"]:
             # the same estimate with ALL THREE Gram matrices on the matrix cores (the headline's form before the mean was
@@ -550,6 +583,7 @@ def main():
             f2 = Legendre(c2["R"], DOMAIN)
             d2 = synth_device(list(range(c2["L"])), 0, c2["n_per_level"], sh, dev)
             blk = estimate_block(c2, d2, f2, sh, ctx, st, wu, 100.0, 3 if k2 == "north_star" else k2)
+            blk.pop("outputs")
             blk["config"] = {"workload": c2["workload"], "levels": c2["L"], "samples_per_level_per_gpu": c2["n_per_level"],
                              "n_moments": c2["R"], "estimate": c2["mode"]}
             if k2 == "north_star":
@@ -623,8 +657,9 @@ def tree_bench(args, cfg, world, rank, dev, dist):
             keep.append((f, c))
             acc.push(l, f[0], None if c is None else c[0])
         n, n_rm, s, sp = acc.finalize()
-        _, _, mean, var = host_formulas(n, s, sp, level_stats)
-        return n, n_rm, mean, var
+        l_means, l_vars, mean, var = host_formulas(n, s, sp, level_stats)
+        return {"n_samples": n, "n_removed": n_rm, "sums": s, "sums_sq": sp, "level_means": l_means, "level_vars": l_vars,
+                "mean": mean, "var": var}
 
     plan.kernel_time()
     steps_k, warm = args.steps, args.warmup
@@ -638,10 +673,13 @@ def tree_bench(args, cfg, world, rank, dev, dist):
     ctx.sync()
     t0 = time.perf_counter()
     for _ in range(steps_k):
-        n, n_rm, mean, var = one_step()
+        res = one_step()
     ctx.sync()
     elapsed = ctx.max_over_ranks([time.perf_counter() - t0])[0]
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    n_rm, mean, var = res["n_removed"], res["mean"], res["var"]
     x_ms, x_launches, x_bytes = plan.kernel_time()
     a_ms, a_launches, _ = acc.kernel_time()
     gbs = (x_bytes / 1e9) / (x_ms / 1e3) if x_ms > 0 else 0.0
@@ -661,7 +699,7 @@ def tree_bench(args, cfg, world, rank, dev, dist):
                      "moments_kernel_ms_per_step": round(a_ms / max(steps_k, 1), 5)},
         "result_check": {"mean0": float(mean[0]), "var0": float(var[0]), "n_removed": [int(v) for v in n_rm]},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # CPU leg: the same tree evaluated the way the reference does it (NumPy closures over [M, n, 2] chunks,
         # mlmc/quantity/quantity.py) on a bounded sample, and the parity of the device rows against it
         m = 2_000_000

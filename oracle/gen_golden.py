@@ -642,10 +642,38 @@ def g10_log_edges():
     np.savez_compressed(os.path.join(OUT, "G10_log_edges.npz"), **out)
 
 
+def g11_estimate_density_root():
+    """The outcome of the reference's root-finding variant ``Distribution.estimate_density`` (tool/distribution.py) on a
+    small, well-posed problem: the exception it raises, the frames it passes and the arguments of the frame that raises.
+    Data only (names and values), so that the test that explains why this method has no golden vector needs no reference
+    sources."""
+    import traceback
+    import mlmc.moments as mm
+    import mlmc.tool.distribution as dd
+    R, domain, tol = 5, (-3.0, 3.0), 1e-8
+    md = np.stack([np.eye(R)[0], np.full(R, 1e-6)], axis=1)
+    d = dd.Distribution(mm.Legendre(R, domain), md, domain=domain, force_decay=(True, True))
+    out = {"call": "Distribution(Legendre({}, {}), moment_data, force_decay=(True, True)).estimate_density(tol={!r})".format(R, domain, tol),
+           "tol": tol, "approx_size": R}
+    try:
+        d.estimate_density(tol=tol)
+        out["raised"] = None
+    except Exception as e:          # the recorded outcome
+        tb = e.__traceback__
+        out["raised"], out["message"] = type(e).__name__, str(e)
+        out["frames"] = [f.name for f in traceback.extract_tb(tb)][1:]
+        while tb.tb_next is not None:
+            tb = tb.tb_next
+        out["raising_frame_args"] = {k: v for k, v in tb.tb_frame.f_locals.items() if k in ("size", "tol")}
+    print("G11", out)
+    with open(os.path.join(OUT, "G11_estimate_density_root.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     _install_shims()
-    which = sys.argv[1:] or ["g1", "g2", "g5", "g7", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["g1", "g2", "g5", "g7", "g8", "g9", "g10", "g11"]
     if "g1" in which:
         g1_basis()
     if "g2" in which:
@@ -660,3 +688,5 @@ if __name__ == "__main__":
         g9_sampler_loop()
     if "g10" in which:
         g10_log_edges()
+    if "g11" in which:
+        g11_estimate_density_root()

@@ -207,7 +207,8 @@ def test_bench_multi_rank_default_is_config3_sharded(hip):
     total = 3_000_001
     env = dict(os.environ, MLMC_BENCH_BACKEND="gloo", MLMC_BENCH_DEVICE="0", MLMC_BENCH_TOTAL_PER_LEVEL=str(total))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+                          "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -235,15 +236,15 @@ def test_bench_multi_rank_default_is_config3_sharded(hip):
 
 
 def test_bench_default_line_carries_the_contract(hip):
-    """`python bench.py` (N = 1 defaults apart from K / W): ONE JSON line with the driver's keys, BASELINE configs[2] as the
+    """`python bench.py --full` (N = 1 defaults apart from K / W): ONE JSON line with the driver's keys, BASELINE configs[2] as the
     workload, `roofline` (bound / achieved / peak / unit / frac / traffic) of the dominant kernel with the auxiliary moments
     launch and the three-Gram form beside it, `cpu_baseline` on a bounded sample, the in-run parity gate green."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2"], capture_output=True, text=True,
-                         timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--full"], capture_output=True,
+                         text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -271,3 +272,48 @@ def test_bench_default_line_carries_the_contract(hip):
     assert d["result_check"]["mean0"] == 1.0 and d["result_check"]["var0"] == 0.0
     for k in ("moments_r64", "configs1", "north_star", "pdf_solve", "h2d_inclusive"):
         assert k in d, k
+
+
+def test_bench_plain_line_and_dumped_outputs(hip, tmp_path):
+    """`python bench.py` without --full: the headline line alone (none of the blocks that take runs of their own), and
+    --dump-outputs DIR: the arrays of the last timed step as float64 .npy files, consistent with the line and with each
+    other, the same counts and (to rounding) the same sums in a second run -- the inputs are seeded."""
+    import json
+    import subprocess
+    import sys
+    from mlmc_amd.engine import level_stats
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        d_out = str(tmp_path / "run{}".format(i))
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", d_out],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "result_check"):
+            assert k in d, k
+        for k in ("cpu_baseline", "parity", "pdf_solve", "moments_r64", "three_gram_form", "configs1", "north_star", "h2d_inclusive",
+                  "exchange"):
+            assert k not in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert abs(d["value"] - 5 * 10_000_000 * 64 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+        files = sorted(os.listdir(d_out))
+        assert files == sorted(k + ".npy" for k in ("n_samples", "n_removed", "sums", "sums_sq", "level_means", "level_vars", "mean",
+                                                     "var", "moments_level_vars", "regressed_level_vars", "n_estimated"))
+        arr = {f[:-4]: np.load(os.path.join(d_out, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arr.values()) and sum(a.nbytes for a in arr.values()) <= 64 << 20
+        assert arr["sums"].shape == (5, 64 * 64) and arr["sums_sq"].shape == (5, 64 * 64) and arr["mean"].shape == (64 * 64,)
+        rc = d["result_check"]
+        assert list(arr["n_removed"]) == rc["n_removed"] and list(arr["n_estimated"]) == rc["n_estimated"]
+        assert np.array_equal(arr["n_samples"] + arr["n_removed"], np.full(5, 10_000_000.0))
+        assert arr["mean"][0] == rc["mean0"] and arr["var"][0] == rc["var0"]
+        l_means, l_vars = level_stats(arr["n_samples"].astype(np.int64), arr["sums"], arr["sums_sq"])
+        assert np.array_equal(l_means, arr["level_means"]) and np.array_equal(l_vars, arr["level_vars"])
+        runs.append(arr)
+    a, b = runs
+    assert np.array_equal(a["n_samples"], b["n_samples"]) and np.array_equal(a["n_removed"], b["n_removed"])
+    scale = np.maximum(np.abs(a["sums"]), np.sqrt(np.abs(a["sums_sq"]) * a["n_samples"][:, None]) + 1e-300)
+    assert np.all(np.abs(a["sums"] - b["sums"]) <= 1e-10 * scale)
+    assert np.all(np.abs(a["sums_sq"] - b["sums_sq"]) <= 1e-10 * np.maximum(np.abs(a["sums_sq"]), 1e-300) + 1e-13)

@@ -520,8 +520,8 @@ def test_rccl_allreduce_path_single_rank(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MLMC_HIP_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     # the default N = 1 workload: BASELINE configs[2] (covariance R = 64 through mlmc_accum_estimate_packed + the all-reduce)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"],
-                         env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                          "--no-secondary"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

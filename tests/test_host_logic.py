@@ -319,15 +319,13 @@ def test_level_stats_beyond_two_to_the_53_equal_the_reference_formula():
 def test_reference_estimate_density_root_variant_cannot_run_as_written():
     """Why mlmc_amd.tool.distribution.Distribution.estimate_density has no golden vector: the reference's method
     (distribution.py:159-181) calls `self._initialize_params(tol)`, whose signature is `(self, size, tol=None)` and which
-    asserts `tol is not None` (:216-223).  Read from the reference's source when it is present (build container only)."""
-    path = "/root/reference/mlmc/tool/distribution.py"
-    if not os.path.exists(path):
-        pytest.skip("reference sources are not present on this machine")
-    src = open(path).read()
-    body = src[src.index("def estimate_density(self, tol=None):"):src.index("def density(self, value, moments_fn=None):")]
-    assert "self._initialize_params(tol)" in body
-    init = src[src.index("def _initialize_params(self, size, tol=None):"):src.index("def extend_size(self, new_size):")]
-    assert "assert tol is not None" in init
+    asserts `tol is not None` (:216-223).  The reference's own run of the method is recorded in G11 (oracle/gen_golden.py):
+    it stops with that assertion in `_initialize_params`, with `size` bound to the tolerance and `tol` left None."""
+    with open(os.path.join(GOLDEN, "G11_estimate_density_root.json")) as f:
+        g11 = json.load(f)
+    assert g11["raised"] == "AssertionError"
+    assert g11["frames"] == ["estimate_density", "_initialize_params"]
+    assert g11["raising_frame_args"] == {"size": g11["tol"], "tol": None}
 
 
 def test_orthogonal_moments_of_128_moments_with_the_mrrr_driver(monkeypatch):
