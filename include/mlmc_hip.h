@@ -29,9 +29,10 @@
 extern "C" {
 #endif
 
-#define MLMC_ABI_VERSION 6   /* 2: strides in mlmc_expr_eval, chaining flags, mlmc_accum_estimate_packed; 3: mlmc_wait_event;
+#define MLMC_ABI_VERSION 7   /* 2: strides in mlmc_expr_eval, chaining flags, mlmc_accum_estimate_packed; 3: mlmc_wait_event;
                               * 4: x_lo / x_hi in mlmc_basis_desc, mlmc_expr_state, mlmc_accum_kernel_flops;
-                              * 5: mlmc_accum_aux_kernel_time; 6: mlmc_linearization_table */
+                              * 5: mlmc_accum_aux_kernel_time; 6: mlmc_linearization_table;
+                              * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -174,6 +175,18 @@ int mlmc_accum_aux_kernel_time(mlmc_accum *a, double *ms, int64_t *launches, int
  * kind: MLMC_LEGENDRE or MLMC_MONOMIAL, 1 <= R <= 128 (squares: R <= 64). */
 int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *out, int64_t out_len);
 
+/* Mean-only level sums of a quantity of M components, each with ITS OWN moment functions (Estimate.construct_densities:
+ * construct_density of every scalar component, estimator.py:304-331): bases[m] (m < M) are plain Legendre, monomial or Fourier
+ * members of ONE family with size >= K, each with its own domain, log, x_lo / x_hi and safe_eval; component m of chunk c is row
+ * m of fine[c] / coarse[c] ([M][n] DEVICE buffers, coarse[c] NULL at level 0).  Each component is masked on its own, by the rule
+ * mlmc_accum_push applies to a one-component chunk (the fine AND the coarse value kept by the domain transform, no NaN), so
+ * n / n_rm are bit-identical to M scalar estimates.  One pass per chunk for all components (one launch per chunk, plus a
+ * fixed-order merge).  Outputs (host): n[l * M + m], n_rm[l * M + m], sums[(l * M + m) * K + k] = level sums of the
+ * differences phi_k(fine) - phi_k(coarse) of component m.  Synchronises. */
+int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
+                              const int32_t *levels, const double *const *fine, const double *const *coarse,
+                              const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *sums);
+
 /* ---- maximum-entropy density (mlmc/tool/simple_distribution.py:9-327) ------------------ */
 typedef struct {
     double tol;          /* gradient-norm tolerance (estimate_density_minimize tol, :50) */
@@ -209,6 +222,22 @@ int mlmc_density_eval(const mlmc_basis *b, const double *lambda, const double *s
 /* integral of the density over [lo_i, hi_i] by `degree`-point Gauss-Legendre per interval (cdf :108-125) */
 int mlmc_density_integrate(const mlmc_basis *b, const double *lambda, const double *sigma, int32_t R1, const double *lo,
                            const double *hi, int64_t n, int32_t degree, double *out);
+/* B independent problems of mlmc_maxent_solve's functional WITHOUT penalties (SimpleDistribution.estimate_density_minimize,
+ * one per scalar component of a vector quantity) in one launch: one workgroup owns one problem for the whole solve, so B may
+ * exceed the CU count and a problem's result is bit for bit the same alone, anywhere in any batch.  Problem i: basis bases[i]
+ * (its own transform and domain), R1[i] <= 128 moments, domain [a[i], b[i]].  mu, sigma, lambda_io, grad_out are [B][R1max],
+ * hess_out [B][R1max][R1max] (R1max = max R1[i]; entries beyond a problem's R1 are zero in the outputs, lambda_io keeps them);
+ * grad_out / hess_out may be NULL; info [B].  One opts for the batch (same quadrature for every problem); opts carrying
+ * stab_penalty or penalty_coef are rejected (the penalised Distribution stays on mlmc_maxent_solve).  Argument errors name the
+ * problem index; a problem that does not converge is no error (info[i].success = 0).  B = 0 is a no-op.  Same algorithm,
+ * constants and result fields as mlmc_maxent_solve. */
+int mlmc_maxent_solve_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *a, const double *b,
+                            const double *mu, const double *sigma, const mlmc_maxent_opts *opts, double *lambda_io,
+                            double *grad_out, double *hess_out, mlmc_maxent_info *info);
+/* mlmc_density_eval of B problems in one launch: lambda / sigma [B][R1max]; x / out host arrays holding the problems' points one
+ * after another (problem i: n[i] points at offset n[0] + ... + n[i - 1]).  Each value is bit for bit mlmc_density_eval's. */
+int mlmc_density_eval_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                            const double *x, const int64_t *n, double *out);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

@@ -718,7 +718,7 @@ __global__ void k_density_integrate(BasisParams bp, const double *__restrict__ c
 }
 
 // Gauss-Legendre nodes / weights on [-1, 1] (Newton on P_n, host, long double)
-static void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w) {
+void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w) {
     x.assign(n, 0.0);
     w.assign(n, 0.0);
     const long double pi = 3.14159265358979323846264338327950288L;
@@ -744,7 +744,7 @@ static void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w
 }
 
 // effective coefficients in the underlying scaled family: c_r = scale_c[r] * sum_j T[j][r] lambda_j / sigma_j
-static std::vector<double> effective_coeffs(const mlmc_basis *b, const double *lambda, const double *sigma, int R1) {
+std::vector<double> effective_coeffs(const mlmc_basis *b, const double *lambda, const double *sigma, int R1) {
     const int R = b->p.size;
     std::vector<double> c(R, 0.0);
     if (b->out_size > 0) {

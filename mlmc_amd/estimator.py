@@ -7,6 +7,7 @@ Every pass over the samples (moments, covariance, level variances) goes through
 import numpy as np
 
 from . import engine
+from . import linearize
 from .quantity import quantity_estimate as qe
 from .quantity.quantity_types import ScalarType
 
@@ -210,9 +211,87 @@ class Estimate:
         result = distr_obj.estimate_density_minimize(tol, reg_param)
         return distr_obj, info, result, moments_obj
 
+    def construct_densities(self, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None):
+        """Maximum-entropy density of EVERY scalar component of the quantity (any qtype, scalar included).
+
+        Entry m of the returned list is what `Estimate(q_m, storage, fn_m).construct_density(tol, reg_param,
+        orth_moments_tol)` returns for the scalar sub-quantity q_m = row m of `quantity.samples(chunk)` ([M, n, 2]): each
+        component is NaN-masked and domain-clipped on its own (a NaN in component 3 does not drop that sample from
+        component 0 -- unlike `mask_nan_samples` over the whole vector).  Row order: the qtype flattened from the outside in,
+        e.g. for the result format dict -> time series -> field -> array, m = ((time_index * n_locations + location_index)
+        * array_size + flat_array_index) inside the dict entry's block, dict entries one after another in their order.
+        For Legendre / monomial / Fourier moments (one family and size for all components) both estimates of every
+        component come from ONE device pass per stored chunk (mlmc_accum_estimate_multi); other moments (splines, transformed
+        moments, MLMC_HIP_LINEARIZE=0) take the scalar chain per component, with the same results.  The orthogonalisation
+        stays per component on the host; the max-entropy problems of all components are solved in ONE batched device call
+        (tool.simple_distribution.estimate_densities_minimize).  That solve gives one workgroup to each problem: it beats
+        M cooperative single solves from M ~ 16 components on, below that construct_density per component is faster.
+        :param moments_fns: optional list of M moments objects (component m uses moments_fns[m]); default: this
+            Estimate's moments_fn for every component
+        :return: list of M tuples (distr_obj, info, result, moments_obj)"""
+        from .tool import simple_distribution
+        n_comp = int(self._quantity.size())
+        if moments_fns is None:
+            moments_fns = [self._moments_fn] * n_comp
+        moments_fns = list(moments_fns)
+        if len(moments_fns) != n_comp:
+            raise ValueError("construct_densities: {} moments objects for {} components".format(len(moments_fns), n_comp))
+        exts = qe.linearized_bases(moments_fns)
+        if exts is not None:
+            # ONE device pass per stored chunk for all components: level sums of the extended moments of every component
+            # (its own mask) give both means -- the covariance by the product linearisation, the orthogonal moments as
+            # T_m times the first R sums -- as the scalar chain takes them from its first estimate (quantity_estimate.py)
+            n, _, sums = qe.multi_component_sums(self._quantity, exts)
+            if np.any(np.sum(n, axis=0) == 0):
+                raise Exception("All samples were masked")
+            nf = n.astype(np.float64)
+
+            def level_mean(m, s):                          # sum over levels of s_l / n_l (engine.level_stats)
+                return np.sum(s / nf[:, m, None], axis=0)
+            cov_means = [level_mean(m, linearize.covariance_sums_from_moment_sums(fn, sums[:, m, :])).reshape(fn.size, fn.size)
+                         for m, fn in enumerate(moments_fns)]
+        else:
+            comps = [self._quantity] if isinstance(self._quantity.qtype, ScalarType) else \
+                [scalar_component(self._quantity, m) for m in range(n_comp)]
+            cov_means = qe.component_means(comps, moments_fns, cov=True)
+        ortho = [simple_distribution.construct_ortogonal_moments(fn, cov, tol=orth_moments_tol)
+                 for fn, cov in zip(moments_fns, cov_means)]
+        if exts is not None:
+            mom_means = [level_mean(m, sums[:, m, :fn.size] @ mobj._base_matrix.T)
+                         for m, (fn, (mobj, _)) in enumerate(zip(moments_fns, ortho))]
+        else:
+            mom_means = qe.component_means(comps, [m for m, _ in ortho], cov=False)
+        distrs = []
+        for (moments_obj, _), est_moments in zip(ortho, mom_means):
+            moments_data = np.stack((est_moments, np.ones(moments_obj.size)), axis=1)   # variances discarded (:323)
+            distrs.append(simple_distribution.SimpleDistribution(moments_obj, moments_data, domain=moments_obj.domain))
+        results = simple_distribution.estimate_densities_minimize(distrs, tol, reg_param)
+        return [(d, info, r, m) for d, (m, info), r in zip(distrs, ortho, results)]
+
     def get_level_samples(self, level_id, n_samples=None):
         chunk_spec = next(self._sample_storage.chunks(level_id=level_id, n_samples=n_samples))
         return self._quantity.samples(chunk_spec=chunk_spec)
+
+
+def scalar_component(quantity, m):
+    """Scalar sub-quantity of row m of `quantity.samples(chunk)` ([M, n, 2] -> [1, n, 2]), lowerable to the device like
+    any item selection."""
+    from .quantity.quantity import Quantity
+    from .quantity import quantity_types as qt
+    qtype = quantity.qtype
+    if isinstance(qtype, qt.ArrayType) and isinstance(qtype._qtype, ScalarType):
+        key = tuple(int(i) for i in np.unravel_index(m, qtype._shape))     # ArrayType indexes its shaped rows
+    elif isinstance(qtype, qt.ArrayType):
+        key = None
+    else:
+        key = slice(m, m + 1)                                              # the other types index the flat rows
+    if key is None:
+        item = Quantity(quantity_type=ScalarType(), input_quantities=[quantity], operation=lambda y, m=m: y[m:m + 1])
+    else:
+        item = Quantity(quantity_type=ScalarType(), input_quantities=[quantity],
+                        operation=lambda y, key=key: qtype._make_getitem_op(y, key=key))
+        item._sym = ("getitem", key)
+    return item
 
 
 def estimate_domain(quantity, sample_storage, quantile=None):

@@ -886,6 +886,84 @@ def _sums_from_linearized_memo(fn, key, owner):
     return memo["n"].copy(), memo["n_rm"].copy(), (base @ fn._base_matrix.T).reshape(L, -1), n_comp
 
 
+def linearized_bases(moments_fns):
+    """The extended members (_linearized_basis) of M moments objects when ONE pass of mlmc_accum_estimate_multi can serve
+    them all -- every one has a linearisation, of the same family and size -- else None (the scalar chain per component)."""
+    exts = [_linearized_basis(fn) for fn in moments_fns]
+    if not exts or any(e is None for e in exts):
+        return None
+    if len({type(e) for e in exts}) != 1 or len({e.size for e in exts}) != 1:
+        return None
+    return exts
+
+
+def multi_component_sums(quantity, ext_fns):
+    """Level sums of the moments ext_fns[m] of row m of `quantity`'s chunks, every component masked on its own, in ONE
+    device pass per stored chunk for all components (mlmc_amd/csrc/moments_multi.hip).
+    -> n, n_rm [L, M] int64, sums [L, M, K] (K = size of the ext_fns, all equal)"""
+    with _estimate_lock:
+        return _multi_component_sums(quantity, ext_fns)
+
+
+def _multi_component_sums(quantity, ext_fns):
+    import ctypes as C
+    import torch
+    from .. import _lib
+    cache_clear()
+    storage_q = quantity.get_quantity_storage()
+    n_levels = int(np.max(storage_q.level_ids())) + 1
+    M, K = len(ext_fns), int(ext_fns[0].size)
+    if quantity.size() != M:
+        raise ValueError("multi_component_sums: {} moments objects for {} components".format(M, quantity.size()))
+    plan = lowering.plan_for(quantity) if _device_tree_enabled() else None
+    try:
+        n_collected = _level_stamps(storage_q)
+    except Exception:
+        n_collected = None
+    use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(quantity, "_volatile", False)
+    dev = torch.device("cuda", _lib_device())
+    levels, fines, coarses, ns, keep = [], [], [], [], []
+    for chunk_spec in storage_q.chunks():
+        fine, coarse = _chunk_for_device(quantity, plan, chunk_spec, n_collected, use_cache)
+        if fine.shape[-1] == 0:
+            continue
+        fine = torch.as_tensor(fine, dtype=torch.float64, device=dev).reshape(M, -1).contiguous()
+        if coarse is not None:
+            coarse = torch.as_tensor(coarse, dtype=torch.float64, device=dev).reshape(M, -1).contiguous()
+        keep.append((fine, coarse))
+        levels.append(int(chunk_spec.level_id))
+        fines.append(fine.data_ptr())
+        coarses.append(None if coarse is None else coarse.data_ptr())
+        ns.append(fine.shape[-1])
+    torch.cuda.current_stream(dev).synchronize()
+    n = np.zeros((n_levels, M), dtype=np.int64)
+    n_rm = np.zeros((n_levels, M), dtype=np.int64)
+    sums = np.zeros((n_levels, M, K))
+    nc = len(ns)
+    handles = (C.c_void_p * M)(*[fn._basis_handle().value for fn in ext_fns])
+    lv = np.array(levels, dtype=np.int32)
+    nn = np.array(ns, dtype=np.int64)
+    fp = (C.c_void_p * max(nc, 1))(*fines)
+    cp = (C.c_void_p * max(nc, 1))(*coarses)
+    _lib.check(_lib.lib().mlmc_accum_estimate_multi(M, C.cast(handles, C.c_void_p), K, n_levels, nc, _lib.ptr(lv),
+                                                    C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn), _lib.ptr(n),
+                                                    _lib.ptr(n_rm), _lib.ptr(sums)))
+    del keep
+    return n, n_rm, sums
+
+
+def component_means(components, moments_fns, cov=False):
+    """Means of the moments (cov=False: [R] each) or of the moment covariance (True: [R, R]) of several scalar
+    quantities, component m with moments_fns[m] -- entry m is estimate_mean(moments|covariance(components[m], fn_m),
+    variance=False).mean, each component masked on its own (Estimate.construct_densities)."""
+    node = covariance if cov else moments
+    out = []
+    for q, fn in zip(components, moments_fns):
+        mean = estimate_mean(node(q, fn), variance=False).mean
+        out.append(mean.reshape((fn.size, fn.size)) if cov else mean.reshape(fn.size))
+    return out
+
+
 def estimate_mean(quantity, group=None, variance=True):
     """MLMC mean estimator (reference: quantity_estimate.py:22-80).  Thread-safe: estimates of several host threads are
     serialised (one GPU stream, one sample cache, the memo of chunk evaluations shared by all quantities).

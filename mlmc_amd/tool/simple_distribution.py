@@ -70,6 +70,89 @@ def _solve_on_device(moments_fn, means, errs, domain, multipliers, tol, max_it, 
     return lam, grad, hess, info
 
 
+def _solve_batch_on_device(moments_fns, means, errs, domains, multipliers, tol, max_it, n_intervals=0, gauss_degree=21):
+    """B problems of _solve_on_device's functional (no penalties) in one mlmc_maxent_solve_batch call.
+    means / errs / multipliers: sequences of B vectors (problem b uses the first len(multipliers[b]) entries).
+    :return: list of (lam, grad, hess, info) per problem, as _solve_on_device returns them"""
+    B = len(moments_fns)
+    if B == 0:
+        return []
+    r1 = np.array([len(m) for m in multipliers], dtype=np.int32)
+    ldv = int(r1.max())
+    mu = np.zeros((B, ldv))
+    sig = np.ones((B, ldv))
+    lam = np.zeros((B, ldv))
+    for b in range(B):
+        r = r1[b]
+        mu[b, :r] = np.asarray(means[b], dtype=np.float64)[:r]
+        sig[b, :r] = np.asarray(errs[b], dtype=np.float64)[:r]
+        lam[b, :r] = np.asarray(multipliers[b], dtype=np.float64)
+    lo = np.ascontiguousarray([float(d[0]) for d in domains], dtype=np.float64)
+    hi = np.ascontiguousarray([float(d[1]) for d in domains], dtype=np.float64)
+    opts = _lib.MaxentOpts()
+    opts.tol = float(tol)
+    opts.max_it = int(max_it)
+    opts.n_intervals = int(n_intervals)
+    opts.gauss_degree = int(gauss_degree)
+    handles = (C.c_void_p * B)(*[fn._basis_handle().value for fn in moments_fns])
+    infos = (_lib.MaxentInfo * B)()
+    grad = np.empty((B, ldv))
+    hess = np.empty((B, ldv, ldv))
+    _lib.check(_lib.lib().mlmc_maxent_solve_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lo), _lib.ptr(hi),
+                                                  _lib.ptr(mu), _lib.ptr(sig), C.byref(opts), _lib.ptr(lam), _lib.ptr(grad),
+                                                  _lib.ptr(hess), C.cast(infos, C.c_void_p)))
+    return [(lam[b, :r1[b]].copy(), grad[b, :r1[b]].copy(), hess[b, :r1[b], :r1[b]].copy(), infos[b]) for b in range(B)]
+
+
+def densities(distrs, values):
+    """density() of many distributions in one device launch (mlmc_density_eval_batch).
+    values: one array of points for all (broadcast) or a sequence with one array per distribution.
+    :return: list of arrays, entry b = distrs[b].density(values[b]) bit for bit"""
+    B = len(distrs)
+    if B == 0:
+        return []
+    if isinstance(values, np.ndarray) or np.isscalar(values) or (len(values) > 0 and np.isscalar(values[0])):
+        values = [values] * B
+    shaped = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in values]
+    flat = np.ascontiguousarray(np.concatenate([v.reshape(-1) for v in shaped]))
+    n = np.array([v.size for v in shaped], dtype=np.int64)
+    r1 = np.array([len(d.multipliers) for d in distrs], dtype=np.int32)
+    ldv = int(r1.max())
+    lam = np.zeros((B, ldv))
+    sig = np.ones((B, ldv))
+    for b, d in enumerate(distrs):
+        lam[b, :r1[b]] = d.multipliers
+        sig[b, :r1[b]] = d._moment_errs[:r1[b]]
+    out = np.empty_like(flat)
+    handles = (C.c_void_p * B)(*[d.moments_fn._basis_handle().value for d in distrs])
+    _lib.check(_lib.lib().mlmc_density_eval_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig),
+                                                  _lib.ptr(flat), _lib.ptr(n), _lib.ptr(out)))
+    parts = np.split(out, np.cumsum(n)[:-1])
+    return [p.reshape(v.shape) for p, v in zip(parts, shaped)]
+
+
+def estimate_densities_minimize(distrs, tol=1e-5, reg_param=0.01):
+    """SimpleDistribution.estimate_density_minimize of every distribution in `distrs`, solved in ONE batched device call
+    (mlmc_maxent_solve_batch: one workgroup per problem).  Each distribution gets exactly what its own call would do:
+    initial multipliers, the normalisation fix, every OptimizeResult field.  All must share the quadrature
+    (n_intervals, gauss degree).
+    :return: list of OptimizeResult, one per distribution"""
+    distrs = list(distrs)
+    if not distrs:
+        return []
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError("estimate_densities_minimize: every distribution must use the same quadrature")
+    for d in distrs:
+        d._initialize_params(d.approx_size, tol)
+    solved = _solve_batch_on_device([d.moments_fn for d in distrs], [d.moment_means for d in distrs],
+                                    [d._moment_errs for d in distrs], [d.domain for d in distrs],
+                                    [d.multipliers for d in distrs], tol, max_it=100, n_intervals=n_int.pop(),
+                                    gauss_degree=degs.pop())
+    return [d._finish_minimize(lam, grad, hess, info, tol) for d, (lam, grad, hess, info) in zip(distrs, solved)]
+
+
 def _device_density(moments_fn, multipliers, errs, value):
     value = np.atleast_1d(np.asarray(value, dtype=np.float64))
     flat = np.ascontiguousarray(value.reshape(-1))
@@ -149,6 +232,10 @@ class SimpleDistribution:
         self._initialize_params(self.approx_size, tol)
         lam, grad, hess, info = _solve_on_device(self.moments_fn, self.moment_means, self._moment_errs, self.domain, self.multipliers,
                                            tol, max_it=100, n_intervals=self.n_intervals, gauss_degree=self._gauss_degree)
+        return self._finish_minimize(lam, grad, hess, info, tol)
+
+    def _finish_minimize(self, lam, grad, hess, info, tol):
+        """OptimizeResult and normalisation fix from a device solve (shared by the single and the batched solve)."""
         result = OptimizeResult()
         result.x = lam.copy()
         result.fun = info.fun
