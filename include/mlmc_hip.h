@@ -29,10 +29,11 @@
 extern "C" {
 #endif
 
-#define MLMC_ABI_VERSION 7   /* 2: strides in mlmc_expr_eval, chaining flags, mlmc_accum_estimate_packed; 3: mlmc_wait_event;
+#define MLMC_ABI_VERSION 8   /* 2: strides in mlmc_expr_eval, chaining flags, mlmc_accum_estimate_packed; 3: mlmc_wait_event;
                               * 4: x_lo / x_hi in mlmc_basis_desc, mlmc_expr_state, mlmc_accum_kernel_flops;
                               * 5: mlmc_accum_aux_kernel_time; 6: mlmc_linearization_table;
-                              * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi */
+                              * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi;
+                              * 8: mlmc_xcov_create, mlmc_xcov_set_shift */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -186,6 +187,23 @@ int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *o
 int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
                               const int32_t *levels, const double *const *fine, const double *const *coarse,
                               const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *sums);
+
+/* ---- covariance between the components of a vector quantity ---------------------------------------------------------
+ * An accumulator of the M x M level sums, per level l and kept sample k,
+ *     Y_k = (f_k - a)(f_k - a)^T - (c_k - a)(c_k - a)^T      (no coarse values -- level 0: Y_k = (f_k - a)(f_k - a)^T)
+ *     s[l] = sum_k Y_k,   sp[l] = sum_k Y_k o Y_k            (element-wise square)
+ * f_k / c_k: the M fine / coarse component values of sample k, a: the shift (the same for every level, fine and coarse).  A
+ * sample is dropped from the whole matrix if any of its M fine or M coarse values is NaN (quantity_estimate.py:6-14, over the
+ * [M, n, 2] chunk).  With a = 0, entry (i, j) is the reference's estimate_mean(q_i * q_j).  Both sums are bitwise symmetric.
+ * The result is an ordinary accumulator: mlmc_accum_push (chunks [M][n], component-major, coarse NULL at level 0), reset,
+ * finalize, estimate, estimate_packed, finalize_packed, kernel_time (the mask pass, the matrix-core launch and the reduction of
+ * every chunk), kernel_flops (executed v_mfma_f64_16x16x4_f64 flops) and destroy work on it; K = M * M, row i * M + j.
+ * M: 1 .. 1024.  flags: 0 or MLMC_MODE_MEAN_ONLY (sp comes back as NaN).  Deterministic: the same chunks pushed in the same
+ * order give the same bits. */
+int mlmc_xcov_create(int32_t M, int32_t n_levels, int32_t flags, mlmc_accum **out);
+/* The shift a (host array of M doubles, finite; NULL = zeros).  It takes effect at the next mlmc_accum_reset (mlmc_accum_estimate
+ * and mlmc_accum_estimate_packed reset first); an error while pushes since the last reset are pending. */
+int mlmc_xcov_set_shift(mlmc_accum *a, const double *shift_host);
 
 /* ---- maximum-entropy density (mlmc/tool/simple_distribution.py:9-327) ------------------ */
 typedef struct {

@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MLMC_HIP_LIB", os.path.join(_HERE, "libmlmc_hip.so"))   # env override: development builds
 
-ABI_VERSION = 7      # MLMC_ABI_VERSION of include/mlmc_hip.h
+ABI_VERSION = 8      # MLMC_ABI_VERSION of include/mlmc_hip.h
 LEGENDRE, MONOMIAL, FOURIER, IDENTITY, SPLINE = 0, 1, 2, 3, 4
 MODE_MOMENTS, MODE_COV = 0, 1
 MODE_MEAN_ONLY = 0x100
@@ -76,6 +76,8 @@ SIGNATURES = {
                                     C.c_int32, _vp, _vp, _vp, C.POINTER(MaxentInfo)]),
     "mlmc_density_eval": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int]),
     "mlmc_density_integrate": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int64, C.c_int32, _vp]),
+    "mlmc_xcov_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
+    "mlmc_xcov_set_shift": (C.c_int, [_vp, _vp]),
     "mlmc_accum_estimate_multi": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
     "mlmc_maxent_solve_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaxentOpts), _vp, _vp, _vp, _vp]),

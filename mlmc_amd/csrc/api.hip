@@ -605,6 +605,10 @@ int mlmc_accum_reset(mlmc_accum *a) {
     a->pending.clear();
     std::fill(a->level_flushed.begin(), a->level_flushed.end(), 0);
     MLMC_HIP_CHECK(hipMemsetAsync(a->d_state, 0, a->state_bytes, st));
+    if (a->xcov) {          // the shift set since the previous reset takes effect now (mlmc_xcov_set_shift)
+        MLMC_HIP_CHECK(hipMemcpyAsync(a->d_shift, a->shift_host.data(), sizeof(double) * a->shift_host.size(), hipMemcpyHostToDevice, st));
+        a->xcov_pushes = 0;
+    }
     a->lin_used = a->lin0_used = false;
     if (a->lin0)
         if (int rc = mlmc_accum_reset(a->lin0)) return rc;
@@ -620,7 +624,8 @@ void mlmc_accum_destroy(mlmc_accum *a) {
     if (a->lin_basis) mlmc_basis_destroy(a->lin_basis);
     if (a->lin0) mlmc_accum_destroy(a->lin0);
     if (a->lin0_basis) mlmc_basis_destroy(a->lin0_basis);         // (the coefficient tables are shared: lin_tables)
-    void *ptrs[] = {a->d_state, a->d_partials, a->d_pcounts, a->d_stage_f, a->d_stage_c, a->d_mask, a->d_out, a->d_vals_f, a->d_vals_c, a->d_vals_tmp};
+    void *ptrs[] = {a->d_state, a->d_partials, a->d_pcounts, a->d_stage_f, a->d_stage_c, a->d_mask, a->d_out, a->d_vals_f, a->d_vals_c, a->d_vals_tmp,
+                    a->d_shift};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a->h_out) (void)hipHostFree(a->h_out);
@@ -665,6 +670,10 @@ int mlmc_accum_push(mlmc_accum *a, int32_t level, const double *fine, const doub
         MLMC_HIP_CHECK(wait_stream(st));
     } else if (mem_kind != MLMC_DEVICE) {
         return fail("mlmc_accum_push: bad mem_kind");
+    }
+    if (a->xcov) {          // component covariance: the chunk is read in place, one launch for all output blocks (xcov.hip)
+        ++a->xcov_pushes;
+        return launch_xcov_push(a, level, d_f, d_c, n);
     }
     const uint8_t *d_mask = nullptr;
     bool count_in_kernel = true;
@@ -814,7 +823,7 @@ int mlmc_accum_finalize(mlmc_accum *a, int64_t *n, int64_t *n_rm, double *s, dou
         }
         return 0;
     }
-    int rc = (a->mode == MLMC_MODE_MOMENTS) ? launch_moments_finalize(a) : launch_cov_finalize(a);
+    int rc = a->xcov ? launch_xcov_finalize(a) : (a->mode == MLMC_MODE_MOMENTS) ? launch_moments_finalize(a) : launch_cov_finalize(a);
     if (rc) return rc;
     if (mem_kind == MLMC_DEVICE) {
         MLMC_HIP_CHECK(hipMemcpyAsync(n, a->d_out_n, sizeof(int64_t) * L, hipMemcpyDeviceToDevice, st));
@@ -864,7 +873,7 @@ int mlmc_accum_finalize_packed(mlmc_accum *a, double *packed, int mem_kind) {
     }
     if (a->mode == MLMC_MODE_MOMENTS)
         if (int rcf = flush_moments(a)) return rcf;
-    int rc = (a->mode == MLMC_MODE_MOMENTS) ? launch_moments_finalize(a) : launch_cov_finalize(a);
+    int rc = a->xcov ? launch_xcov_finalize(a) : (a->mode == MLMC_MODE_MOMENTS) ? launch_moments_finalize(a) : launch_cov_finalize(a);
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (2 * (size_t)a->n_levels + 2 * (size_t)a->n_levels * a->K);
     MLMC_HIP_CHECK(hipMemcpyAsync(packed, a->d_out_nd, bytes, mem_kind == MLMC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
@@ -925,6 +934,61 @@ int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *o
     if (squares) square_product_table(kind, R, t);
     else product_table(kind, R, t);
     std::memcpy(out, t.data(), sizeof(double) * t.size());
+    return 0;
+}
+
+// ---- component covariance (xcov.hip) ----------------------------------------------------------
+int mlmc_xcov_create(int32_t M, int32_t n_levels, int32_t flags, mlmc_accum **out) {
+    MLMC_API_GUARD;
+    if (need_runtime()) return 1;
+    if (!out) return fail("mlmc_xcov_create: null argument");
+    if (M < 1 || M > XCOV_MAX_M)
+        return fail("mlmc_xcov_create: M = " + std::to_string(M) + " components, supported are 1 .. " + std::to_string(XCOV_MAX_M));
+    if (n_levels <= 0) return fail("mlmc_xcov_create: n_levels must be > 0");
+    if (flags & ~MLMC_MODE_MEAN_ONLY) return fail("mlmc_xcov_create: unknown flags (only MLMC_MODE_MEAN_ONLY)");
+    mlmc_accum *a = new (std::nothrow) mlmc_accum();
+    if (!a) return fail("out of memory");
+    a->xcov = true;
+    a->mode = MODE_XCOV;
+    a->n_levels = n_levels;
+    a->n_comp = M;
+    a->mean_only = (flags & MLMC_MODE_MEAN_ONLY) != 0;
+    a->K = (int64_t)M * M;
+    a->int_width = 2 * a->K;                 // per level: s, sp
+    const size_t tot = (size_t)n_levels * a->int_width;
+    a->state_bytes = sizeof(double) * tot + sizeof(int64_t) * 2 * n_levels;
+    a->out_bytes = (sizeof(int64_t) + sizeof(double)) * 2 * n_levels + 2 * sizeof(double) * (size_t)n_levels * a->K;
+    a->shift_host.assign(M, 0.0);
+    if (hipMalloc(&a->d_state, a->state_bytes) != hipSuccess || hipMalloc(&a->d_out, a->out_bytes) != hipSuccess ||
+        hipMalloc(&a->d_shift, sizeof(double) * M) != hipSuccess ||
+        hipHostMalloc(&a->h_out, a->out_bytes, hipHostMallocDefault) != hipSuccess) {
+        mlmc_accum_destroy(a);
+        return fail("mlmc_xcov_create: device / pinned allocation failed");
+    }
+    a->d_totals = (double *)a->d_state;
+    a->d_counts = (int64_t *)(a->d_totals + tot);
+    a->level_flushed.assign(n_levels, 0);
+    a->d_out_n = (int64_t *)a->d_out;
+    a->d_out_nd = (double *)(a->d_out_n + 2 * (size_t)n_levels);
+    a->d_out_s = a->d_out_nd + 2 * (size_t)n_levels;
+    a->d_out_sp = a->d_out_s + (size_t)n_levels * a->K;
+    *out = a;
+    return mlmc_accum_reset(a);
+}
+
+int mlmc_xcov_set_shift(mlmc_accum *a, const double *shift_host) {
+    MLMC_API_GUARD;
+    if (need_runtime()) return 1;
+    if (!a) return fail("mlmc_xcov_set_shift: null argument");
+    if (!a->xcov) return fail("mlmc_xcov_set_shift: not a component-covariance accumulator (mlmc_xcov_create)");
+    if (a->xcov_pushes > 0) return fail("mlmc_xcov_set_shift: pushes are pending; reset the accumulator first");
+    const int M = a->n_comp;
+    if (shift_host)
+        for (int m = 0; m < M; ++m)
+            if (!std::isfinite(shift_host[m])) return fail("mlmc_xcov_set_shift: shift[" + std::to_string(m) + "] is not finite");
+    MLMC_HIP_CHECK(wait_stream(rt().stream));    // the previous reset's upload reads shift_host
+    if (shift_host) std::memcpy(a->shift_host.data(), shift_host, sizeof(double) * M);
+    else std::fill(a->shift_host.begin(), a->shift_host.end(), 0.0);
     return 0;
 }
 

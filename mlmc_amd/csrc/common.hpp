@@ -146,6 +146,11 @@ struct mlmc_accum {
                                           // extra launches of the auxiliary pass cost more than they save); sums are additive
     bool lin_used = false;                // a chunk of this estimate went the linearised way
     std::vector<PendingSeg> pending;   // MOMENTS: chunks gathered into one launch (flushed by finalize / conflicts)
+    // component covariance (mlmc_xcov_create, xcov.hip): no basis; totals [n_levels][2][M * M] (s, sp), K = M * M
+    bool xcov = false;
+    double *d_shift = nullptr;            // [M]: the shift in effect since the last reset
+    std::vector<double> shift_host;       // set by mlmc_xcov_set_shift, uploaded by mlmc_accum_reset
+    int64_t xcov_pushes = 0;              // non-empty pushes since the last reset
 };
 
 namespace mlmc {
@@ -161,6 +166,11 @@ int launch_moments_finalize(mlmc_accum *a);
 int launch_cov_accum(mlmc_accum *a, int level, int comp, const double *d_f, const double *d_c, const uint8_t *d_mask,
                      int64_t n, bool count, int gram_mode, int ncomp = 1);
 int launch_cov_finalize(mlmc_accum *a);
+// xcov.hip
+constexpr int XCOV_MAX_M = 1024;   // components of a component-covariance accumulator
+constexpr int MODE_XCOV = 2;   // internal mode of a component-covariance accumulator (not a mode of mlmc_accum_create)
+int launch_xcov_push(mlmc_accum *a, int level, const double *d_f, const double *d_c, int64_t n);
+int launch_xcov_finalize(mlmc_accum *a);
 // c_ijk of the product linearisation, k-major [2 R - 1][R * R]; false: the family has none here
 bool product_table(int kind, int R, std::vector<double> &out);
 // c2_ijk of (phi_i phi_j)^2 = sum_k c2_ijk phi_k, k-major [4 R - 3][R * R]

@@ -57,6 +57,7 @@ def _dist_group_active(group):
 class LevelAccumulator:
     MOMENTS = _lib.MODE_MOMENTS
     COV = _lib.MODE_COV
+    COMPONENT_COV = 2        # ComponentCovAccumulator (mlmc_xcov_create): no moment functions, K = M * M
 
     def __init__(self, moments_fn, n_levels, mode=_lib.MODE_MOMENTS, n_comp=1, mean_only=False):
         self._moments_fn = moments_fn if moments_fn is not None else _IdentityBasis()
@@ -193,6 +194,38 @@ class LevelAccumulator:
         fl = C.c_int64()
         _lib.check(_lib.lib().mlmc_accum_kernel_flops(self._h, C.byref(fl)))
         return fl.value
+
+
+class ComponentCovAccumulator(LevelAccumulator):
+    """Level sums of the covariance between the M components of a vector quantity (`mlmc_xcov_create`): per kept sample
+    Y = (f - a)(f - a)^T - (c - a)(c - a)^T (level 0: (f - a)(f - a)^T), s = sum Y, sp = sum Y o Y, K = M * M rows (row
+    i * M + j).  A sample with a NaN in any of its M fine or M coarse values is dropped from the whole matrix.  push / estimate /
+    finalize / kernel_time / kernel_flops are LevelAccumulator's; mean_only: sp comes back as NaN."""
+    MAX_COMPONENTS = 1024
+
+    def __init__(self, n_comp, n_levels, mean_only=False):
+        n_comp, n_levels = int(n_comp), int(n_levels)
+        if not 1 <= n_comp <= self.MAX_COMPONENTS:
+            raise ValueError("component covariance: {} components, supported are 1 .. {}".format(n_comp, self.MAX_COMPONENTS))
+        self._moments_fn = None
+        self.n_levels = n_levels
+        self.mode = self.COMPONENT_COV
+        self.n_comp = n_comp
+        self.rows_per_comp = n_comp
+        self.K = n_comp * n_comp
+        self._keepalive = []
+        h = C.c_void_p()
+        _lib.check(_lib.lib().mlmc_xcov_create(n_comp, n_levels, _lib.MODE_MEAN_ONLY if mean_only else 0, C.byref(h)))
+        self._h = h
+
+    def set_shift(self, shift=None):
+        """Shift a [M] (None: zeros) for the following pushes: set, then the accumulator is reset (pending pushes are an error)."""
+        if shift is not None:
+            shift = _lib.as_f64(shift)
+            if shift.shape != (self.n_comp,):
+                raise ValueError("component covariance: shift of shape {}, expected ({},)".format(shift.shape, self.n_comp))
+        _lib.check(_lib.lib().mlmc_xcov_set_shift(self._h, _lib.ptr(shift)))
+        self.reset()
 
 
 def allreduce_partials(packed, group=None):

@@ -48,6 +48,23 @@ class Estimate:
         self._cov_memo = (self._memo_key(moments_fn), r, moments_fn, self._quantity)
         return r.mean, r.var
 
+    def estimate_component_covariance(self, centered=True):
+        """-> (cov [M, M], cov_var [M, M]): the multilevel covariance between the M scalar components of the quantity (row order
+        as construct_densities documents) and the variance of each entry's estimate (sum over levels of l_vars / n_l).
+
+        centered=True: the shift a is the MLMC mean of the quantity (estimate_mean(quantity), a first pass), and cov is the
+        plug-in estimator E[(Q - mu^)(Q - mu^)^T] = sum_l mean_l((f - a)(f - a)^T - (c - a)(c - a)^T) with a = mu^; the shift
+        also spares the sums the cancellation of raw second moments when |mean| >> std.  It is the plug-in form: the
+        unbiased multilevel covariance with per-level sample covariances and n / (n - 1) corrections is not provided.
+        centered=False: raw second moments E[Q Q^T] (a = 0), entry (i, j) = estimate_mean(q_i * q_j).mean.
+        One pass of the component-covariance kernel per stored chunk (quantity_estimate.component_covariance)."""
+        M = int(self._quantity.size())
+        shift = None
+        if centered:
+            shift = np.asarray(qe.estimate_mean(self._quantity).mean, dtype=np.float64).reshape(M)
+        r = qe.estimate_mean(qe.component_covariance(self._quantity, shift))
+        return np.asarray(r.mean).reshape(M, M), np.asarray(r.var).reshape(M, M)
+
     def _memo_key(self, moments_fn):
         """What a kept covariance estimate is valid for: this quantity object, these moment functions, the stamps of the
         storage's levels (samples collected + modification counts, quantity_estimate._level_stamps)."""

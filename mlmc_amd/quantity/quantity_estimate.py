@@ -58,6 +58,53 @@ class _CovarianceNode(qmod.Quantity):
         raise NotImplementedError("samples of a covariance quantity are not materialised; use estimate_mean(covariance(...))")
 
 
+class _ComponentCovNode(qmod.Quantity):
+    """Quantity node 'covariance between the components of x' (component_covariance).  Like _CovarianceNode its samples are
+    never materialised: estimate_mean sends the raw component values to the component-covariance accumulator."""
+    _at_bottom = True
+
+    def __init__(self, quantity, shift, qtype):
+        self._shift = shift
+        self._moments_fn = None
+        super().__init__(quantity_type=qtype, input_quantities=[quantity], operation=self._eval)
+
+    def _eval(self, x):
+        raise NotImplementedError("samples of a component covariance are not materialised; use "
+                                  "estimate_mean(component_covariance(...))")
+
+
+def component_covariance(quantity, shift=None):
+    """Quantity of qtype ArrayType((M, M)) whose estimate_mean is the multilevel covariance between the M scalar components
+    of `quantity` (row order: as Estimate.construct_densities documents -- the qtype flattened from the outside in).
+
+    Per level l and kept sample k, with f_k / c_k the fine / coarse component vectors and a the shift (the same for every
+    level, fine and coarse, so the levels telescope):
+        Y_k = (f_k - a)(f_k - a)^T - (c_k - a)(c_k - a)^T          (level 0: Y_k = (f_k - a)(f_k - a)^T)
+    estimate_mean gives the level sums s_l = sum_k Y_k and sp_l = sum_k Y_k o Y_k, hence mean, var, l_means, l_vars,
+    n_samples and n_rm_samples with their usual meaning.  A sample is dropped from the whole matrix if any of its M fine or
+    M coarse values is NaN (mask_nan_samples over the [M, n, 2] chunk).  With a = 0 entry (i, j) is exactly
+    estimate_mean(q_i * q_j) (the reference's route: one derived quantity per pair).  Each stored chunk is read once by one
+    launch of the fp64 matrix-core kernel (mlmc_amd/csrc/xcov.hip) for all M (M + 1) / 2 pairs.
+
+    :param quantity: Quantity with M <= 1024 scalar components (not a moments / covariance node)
+    :param shift: None (zeros) or M finite values
+    """
+    if not isinstance(quantity, qmod.Quantity) or isinstance(quantity, (_MomentsNode, _CovarianceNode, _ComponentCovNode)):
+        raise TypeError("component_covariance: needs a Quantity whose samples are component values, got {}".format(
+            type(quantity).__name__))
+    M = int(quantity.size())
+    if M > engine.ComponentCovAccumulator.MAX_COMPONENTS:
+        raise ValueError("component_covariance: {} components, at most {} are supported".format(
+            M, engine.ComponentCovAccumulator.MAX_COMPONENTS))
+    if shift is not None:
+        shift = np.array(shift, dtype=np.float64)
+        if shift.shape != (M,):
+            raise ValueError("component_covariance: shift of shape {}, expected ({},)".format(shift.shape, M))
+        if not np.all(np.isfinite(shift)):
+            raise ValueError("component_covariance: the shift must be finite")
+    return _ComponentCovNode(quantity, shift, qt.ArrayType(shape=(M, M), qtype=qt.ScalarType()))
+
+
 def moment(quantity, moments_fn, i=0):
     """Quantity of the i-th moment function of `quantity` (reference: quantity_estimate.py:83-93)."""
     return qmod.Quantity(quantity_type=quantity.qtype, input_quantities=[quantity],
@@ -499,6 +546,8 @@ class _AccumulatorPool:
             acc = item[0]
             acc.reset()
             return acc
+        if mode == engine.LevelAccumulator.COMPONENT_COV:         # (fn is None: pooled by components, levels, mean_only)
+            return engine.ComponentCovAccumulator(n_comp, n_levels, mean_only=mean_only)
         return engine.LevelAccumulator(fn, n_levels, mode, n_comp=n_comp, mean_only=mean_only)
 
     def give(self, fn, n_levels, mode, n_comp, acc, mean_only=False):
@@ -991,6 +1040,10 @@ def _estimate_mean(quantity, group, variance):
         fn = quantity._moments_fn
         mode = engine.LevelAccumulator.MOMENTS if isinstance(quantity, _MomentsNode) else engine.LevelAccumulator.COV
         rows_per_comp = fn.size if mode == engine.LevelAccumulator.MOMENTS else fn.size * fn.size
+    elif isinstance(quantity, _ComponentCovNode):
+        # the raw component values go to the component-covariance accumulator: M x M rows, i.e. M "rows per component"
+        source, fn, mode = quantity._input_quantities[0], None, engine.LevelAccumulator.COMPONENT_COV
+        rows_per_comp = int(source.size())
     else:
         source, fn, mode, rows_per_comp = quantity, None, engine.LevelAccumulator.MOMENTS, 1
     rows_out = rows_per_comp                                      # rows per component the caller sees
@@ -1037,6 +1090,8 @@ def _estimate_mean(quantity, group, variance):
             if pair[0].shape[-1] > 0:
                 assert n_comp * rows_out == quantity_vec_size
             acc = _acc_pool.take(fn, n_levels, mode, n_comp, mean_only=not variance)
+            if mode == engine.LevelAccumulator.COMPONENT_COV:
+                acc.set_shift(quantity._shift)                  # this estimate's shift (the pooled one may carry another)
         if pair[0].shape[-1] == 0:                               # empty chunk / every sample deselected
             return
         fine, coarse = pair
