@@ -33,7 +33,8 @@ extern "C" {
                               * 4: x_lo / x_hi in mlmc_basis_desc, mlmc_expr_state, mlmc_accum_kernel_flops;
                               * 5: mlmc_accum_aux_kernel_time; 6: mlmc_linearization_table;
                               * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi;
-                              * 8: mlmc_xcov_create, mlmc_xcov_set_shift */
+                              * 8: mlmc_xcov_create, mlmc_xcov_set_shift; added within 8 (backwards compatible):
+                              *    mlmc_percentiles_rows */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -262,6 +263,15 @@ int mlmc_density_eval_batch(int32_t B, const mlmc_basis *const *bases, const int
  * a radix select on the device + NumPy's interpolation formula.  n_valid (may be NULL) = number of non-NaN values. */
 int mlmc_percentiles(const double *x, int64_t n, const double *q_percent, int32_t nq, double *out, int64_t *n_valid,
                      int mem_kind);
+/* mlmc_percentiles of every row of x, in one call: row m = x[m * ld, m * ld + n), out[m * nq + i] = np.percentile of the
+ * row's non-NaN values at q_percent[i], bit for bit what mlmc_percentiles gives for that row alone; n_valid [n_rows] (may be
+ * NULL): each row's number of non-NaN values.  x: host or device memory (mem_kind); q_percent, out and n_valid: host.  Rows
+ * up to 16384 values are sorted in LDS, longer ones go through a segmented radix select whose digits are chosen on the
+ * device (global scratch at most 64 MiB, more rows are processed in groups).  The number of launches and host waits does not
+ * depend on the data.  Errors: n_rows < 1, n < 1, ld < n, nq < 1, null x / q_percent / out, a percentile outside
+ * [0, 100], a row without a non-NaN value (the message names the row). */
+int mlmc_percentiles_rows(const double *x, int64_t n_rows, int64_t n, int64_t ld, const double *q_percent, int32_t nq,
+                          double *out /* [n_rows][nq] */, int64_t *n_valid /* [n_rows], may be NULL */, int mem_kind);
 
 /* ---- quantity expressions (mlmc/quantity/quantity.py:35-512: arithmetic, NumPy ufuncs, comparisons, select) ------
  * A lazily built Quantity tree over one storage is lowered by the host into a straight-line register program that a

@@ -59,6 +59,12 @@ Runtime &rt();
 // the completion interrupt, whose wake-up (20-60 us, more from a deep CPU idle state) would dominate a 0.2 ms estimate.
 hipError_t wait_stream(hipStream_t st);
 
+// ---- order statistics (select.hip, select_rows.hip) ----------------------------------------
+__device__ __forceinline__ unsigned long long order_key(double x) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // monotone in x for all non-NaN values (-0.0 < +0.0)
+}
+
 // ---- device-visible basis parameters (passed by value to kernels) -------------------------
 struct BasisParams {
     int kind;

@@ -18,11 +18,6 @@ namespace mlmc {
 constexpr int SEL_BITS = 11;
 constexpr int SEL_BINS = 1 << SEL_BITS;
 
-__device__ __forceinline__ unsigned long long order_key(double x) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // monotone in x for all non-NaN values (-0.0 < +0.0)
-}
-
 constexpr int SEL_MAX_PREFIX = 4;   // distinct key prefixes followed in one pass (LDS: 4 x 2048 counters = 32 KB)
 
 struct SelPrefixes {

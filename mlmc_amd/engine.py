@@ -323,3 +323,39 @@ def percentiles(values, q_percent, nan_policy="omit"):
     if nan_policy == "propagate" and n_valid.value < n:
         out[:] = np.nan
     return out
+
+
+def row_percentiles(values, q_percent, nan_policy="omit"):
+    """percentiles() of every row of a 2-D array in one device call (mlmc_percentiles_rows): -> [M, K], row m bit for bit
+    np.percentile(values[m][~isnan(values[m])], q_percent).  values: 2-D NumPy array or torch tensor (CUDA or host); rows
+    with a stride of their own (a view with ld > n) are read in place.  A row without a non-NaN value is an error.
+    nan_policy="propagate": NaN in every percentile of a row that holds a NaN, as percentiles(row, q, "propagate")."""
+    q = _lib.as_f64(np.atleast_1d(q_percent).reshape(-1))
+    if isinstance(values, np.ndarray):
+        if values.ndim != 2:
+            raise ValueError("row_percentiles: values must be 2-D [M, n], got shape {}".format(values.shape))
+        M, n = values.shape
+        st0, st1 = values.strides
+        if values.dtype != np.float64 or st1 != 8 or (M > 1 and (st0 % 8 or st0 < 8 * n)):
+            values = _lib.as_f64(values)
+            st0 = values.strides[0]
+        ld = st0 // 8 if M > 1 else n
+    else:
+        if values.dim() != 2:
+            raise ValueError("row_percentiles: values must be 2-D [M, n], got shape {}".format(tuple(values.shape)))
+        import torch
+        M, n = values.shape
+        if values.dtype != torch.float64:
+            values = values.to(torch.float64)
+        if values.stride(1) != 1 or (M > 1 and values.stride(0) < n):
+            values = values.contiguous()
+        ld = values.stride(0) if M > 1 else n
+        if values.is_cuda and not getattr(_lib, "_on_torch_stream", False):
+            torch.cuda.current_stream(values.device).synchronize()     # the library reads it on its own stream
+    out = np.empty((M, q.size), dtype=np.float64)
+    n_valid = np.empty(M, dtype=np.int64)
+    _lib.check(_lib.lib().mlmc_percentiles_rows(_lib.ptr(values), int(M), int(n), int(ld), _lib.ptr(q), int(q.size),
+                                                _lib.ptr(out), _lib.ptr(n_valid), _lib.mem_kind(values)))
+    if nan_policy == "propagate":
+        out[n_valid < n] = np.nan
+    return out

@@ -211,6 +211,22 @@ class Estimate:
         ranges = np.array(ranges)
         return np.min(ranges[:, 0]), np.max(ranges[:, 1])
 
+    @staticmethod
+    def estimate_domains(quantity, sample_storage, quantile=None):
+        """-> [M, 2]: row m is estimate_domain(scalar_component(quantity, m), sample_storage, quantile), bit for bit (row order
+        as construct_densities documents; a scalar quantity gives [[lo, hi]]).  The quantity is evaluated once per level for
+        all components and the percentiles of all of them come from one device call (engine.row_percentiles); NaNs are
+        removed per component.  Same chunks as estimate_domain."""
+        if quantile is None:
+            quantile = 0.01
+        n_comp = int(quantity.size())
+        ranges = []
+        for level_id in range(sample_storage.get_n_levels()):
+            chunk_spec = next(sample_storage.chunks(n_samples=sample_storage.get_n_collected()[level_id]))
+            fine = qe.fine_samples_for_device(quantity, chunk_spec)
+            ranges.append(engine.row_percentiles(fine.reshape(n_comp, -1), [100 * quantile, 100 * (1 - quantile)]))
+        return _domains_of(ranges)
+
     # ---- PDF ---------------------------------------------------------------------------------------------
     def construct_density(self, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, exact_pdf=None):
         """Maximum-entropy density from the estimated moments (reference: :304-331).
@@ -325,6 +341,30 @@ def estimate_domain(quantity, sample_storage, quantile=None):
         ranges.append(engine.percentiles(fine, [100 * quantile, 100 * (1 - quantile)], nan_policy="propagate"))
     ranges = np.array(ranges)
     return np.min(ranges[:, 0]), np.max(ranges[:, 1])
+
+
+def estimate_domains(quantity, sample_storage, quantile=None):
+    """-> [M, 2]: row m is estimate_domain(scalar_component(quantity, m), sample_storage, quantile), bit for bit: the same
+    chunks, one device call per level for all components, a NaN in a component's samples of some level gives that component
+    [nan, nan]."""
+    if quantile is None:
+        quantile = 0.01
+    n_comp = int(quantity.size())
+    ranges = []
+    for level_id in range(sample_storage.get_n_levels()):
+        n0 = sample_storage.get_n_collected()[0]
+        chunk_spec = next(sample_storage.chunks(level_id=level_id, n_samples=n0))
+        fine = qe.fine_samples_for_device(quantity, chunk_spec)
+        ranges.append(engine.row_percentiles(fine.reshape(n_comp, -1), [100 * quantile, 100 * (1 - quantile)],
+                                             nan_policy="propagate"))
+    return _domains_of(ranges)
+
+
+def _domains_of(ranges):
+    """[L] of [M, 2] per-level percentile pairs -> [M, 2]: min of the lower, max of the upper over the levels (np.min /
+    np.max as estimate_domain takes them: a NaN propagates)."""
+    ranges = np.array(ranges)                    # [L, M, 2]
+    return np.stack((np.min(ranges[:, :, 0], axis=0), np.max(ranges[:, :, 1], axis=0)), axis=1)
 
 
 def estimate_n_samples_for_target_variance(target_variance, prescribe_vars, n_ops, n_levels):
