@@ -34,7 +34,8 @@ extern "C" {
                               * 5: mlmc_accum_aux_kernel_time; 6: mlmc_linearization_table;
                               * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi;
                               * 8: mlmc_xcov_create, mlmc_xcov_set_shift; added within 8 (backwards compatible):
-                              *    mlmc_percentiles_rows */
+                              *    mlmc_percentiles_rows, mlmc_bootstrap_weights, mlmc_bootstrap_create / _destroy / _reset / _accum /
+                              *    _finalize / _kernel_time */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -347,6 +348,39 @@ int mlmc_expr_kernel_time(mlmc_expr *e, double *ms, int64_t *launches, int64_t *
  * fine_out / coarse_out [n_rows][k].  Asynchronous on the library's stream. */
 int mlmc_subsample_gather(const double *fine, const double *coarse, int32_t n_rows, int64_t n, int64_t k, uint64_t seed,
                           double *fine_out, double *coarse_out);
+
+/* ---- batched, seeded bootstrap of the moment estimates (Estimate.est_bootstrap, mlmc/estimator.py:171-205) -- added within 8 ----
+ * Replicate b of a chunk of n samples picks sizes[b] of them uniformly with replacement (RNG.choice(chunk, size, axis=1)): integer
+ * weights w[b][0 .. n) ~ Multinomial(sizes[b], uniform), sum_i w[b][i] = sizes[b].  They are drawn exactly as a multinomial over
+ * tiles of 4096 positions followed by uniform positions inside each tile, with Philox4x32-10 keyed by `seed` and a counter made of
+ * (draw, replicate index, tile, stream): the weights of replicate b depend on (seed, stream, n, b, sizes[b]) only -- not on the
+ * batch size or the range asked for.  `stream` tells chunks apart (mlmc_amd passes level << 20 | chunk index of the level).
+ * Chunks of up to 251658240 samples, 0 <= sizes[b] <= n. */
+/* The [nb][n] int32 weights of replicates b0 .. b0 + nb - 1 (sizes: host [nb]; w_out: DEVICE [nb][n]).  Synchronous. */
+int mlmc_bootstrap_weights(int64_t n, int64_t b0, int64_t nb, const int64_t *sizes, uint64_t seed, uint32_t stream,
+                           int32_t *w_out);
+typedef struct mlmc_bootstrap mlmc_bootstrap;
+/* Per-replicate level sums of the moments of a quantity with M components for B replicates and n_levels levels.  Basis: Legendre,
+ * monomial or Fourier (log / safe_eval included), no transform, M * R <= 2048.  Device state: the totals [n_levels][B][2 M R]
+ * doubles plus at most 64 MiB of scratch (tile counts, one weight slab, partial rows); larger B and n run in groups. */
+int mlmc_bootstrap_create(const mlmc_basis *b, int32_t M, int32_t n_levels, int64_t B, mlmc_bootstrap **out);
+void mlmc_bootstrap_destroy(mlmc_bootstrap *bs);
+/* Zero the totals (waits for the stream). */
+int mlmc_bootstrap_reset(mlmc_bootstrap *bs);
+/* Add one chunk of level `level` (fine / coarse: DEVICE [M][n], coarse NULL at level 0; sizes: host [B]) with exactly the weights
+ * mlmc_bootstrap_weights(n, 0, B, sizes, seed, stream) gives: per replicate b the kept count sum_i w_bi keep_i and the sums
+ * sum_i w_bi d_i, sum_i w_bi d_i o d_i over the moment differences d_i (fine - coarse; level 0: fine) of all M x R rows, row
+ * m * R + r.  keep_i: the sample's M fine and M coarse values all pass the basis transform (NaN / out of domain drop the whole
+ * sample, as mlmc_accum_push).  Asynchronous on the library's stream; no launch depends on device results.  The buffers must
+ * stay valid until mlmc_bootstrap_finalize.  Deterministic: a replicate's sums do not depend on B. */
+int mlmc_bootstrap_accum(mlmc_bootstrap *bs, int32_t level, const double *fine, const double *coarse, int64_t n,
+                         const int64_t *sizes, uint64_t seed, uint32_t stream);
+/* Wait for the stream and write (host) n_out [B][n_levels] kept counts, s_out / sp_out [B][n_levels][M * R] sums.  The totals
+ * stay (reset to start over). */
+int mlmc_bootstrap_finalize(mlmc_bootstrap *bs, int64_t *n_out, double *s_out, double *sp_out);
+/* With timing enabled (mlmc_init flags bit 0): HIP-event ms of the contraction launches (keep bytes, contraction, reduction) and of
+ * the RNG launches (tile counts, weights), and the executed v_mfma_f64_16x16x4_f64 flops, since create or the previous call. */
+int mlmc_bootstrap_kernel_time(mlmc_bootstrap *bs, double *ms_contract, double *ms_rng, int64_t *mfma_flops);
 
 /* ---- synthetic samples in HBM (mlmc/sim/synth_simulation.py:37-46,75-131; seeding mlmc/sampling_pool.py:75-84; sample
  * ids mlmc/sampler.py:120) -------------------------------------------------------------------------------------------

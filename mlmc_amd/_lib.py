@@ -92,6 +92,13 @@ SIGNATURES = {
                                       C.c_int32, _vp, _vp]),
     "mlmc_synth_seeds": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, _vp]),
     "mlmc_subsample_gather": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, _vp, _vp]),
+    "mlmc_bootstrap_weights": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _vp, C.c_uint64, C.c_uint32, _vp]),
+    "mlmc_bootstrap_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_vp)]),
+    "mlmc_bootstrap_destroy": (None, [_vp]),
+    "mlmc_bootstrap_reset": (C.c_int, [_vp]),
+    "mlmc_bootstrap_accum": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int64, _vp, C.c_uint64, C.c_uint32]),
+    "mlmc_bootstrap_finalize": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mlmc_bootstrap_kernel_time": (C.c_int, [_vp, _dp, _dp, _ip]),
 }
 
 _lock = threading.Lock()

@@ -1,0 +1,605 @@
+// Batched, seeded bootstrap of the moment estimates (Estimate.est_bootstrap_batch), gfx950.
+//
+// Replicate b of a stored chunk of n samples picks s_b of them uniformly with replacement (RNG.choice(chunk, s_b, axis=1)), i.e.
+// integer weights w_b ~ Multinomial(s_b, uniform over n).  Its level sums are sum_i w_bi [keep_i, d_i, d_i o d_i], d_i the row of
+// moment differences of sample i (fine - coarse, all M components x R moments), keep_i the mask of the moments kernels.  The
+// moments are evaluated once per stored sample and replicate group; the B-fold work is the contraction W [B x n] . Phi [n x 2 M R]
+// on the fp64 matrix cores (v_mfma_f64_16x16x4_f64: replicates on the M axis, samples on K, columns on N).
+//
+// Weights without a global scatter: a multinomial over n positions equals a multinomial over tiles of BS_TILE positions (the
+// tile numbers of s_b uniform positions) followed by uniform positions inside each tile.
+//   pass A (k_bs_tile_counts): s_b positions pos = hi64(r64 * n), two per Philox call; only pos / BS_TILE is kept, counted in an
+//     LDS histogram (segments of BS_SEG_TILES tiles) and added to counts[b][t] with integer atomics -- exact, order-free.
+//   pass B (k_bs_expand): one workgroup per (tile, replicate) draws counts[b][t] positions hi32(r32 * tile size) inside the tile,
+//     four per Philox call, into an LDS histogram, and writes the tile's weights.
+// Philox4x32-10 is keyed by the 64-bit seed; the counter is (draw index, replicate, tile | ~0 for pass A, stream), where the stream
+// names the (level, chunk) -- never the batch size, the grid or a position in a group.  mlmc_bootstrap_weights writes the weights
+// of a replicate range; mlmc_bootstrap_accum runs the same two kernels into a bounded scratch slab and contracts it, so both see
+// the same weights bit for bit.
+//
+// Accumulation of one chunk: replicates in groups of BG (multiples of 64), samples in ranges of nr (whole tiles, a function of n
+// and the column count only); per (group, range): keep bytes (k_bs_keep), the weight slab [BG][nr] (pass B), the contraction
+// (k_bs_contract: grid (512-sample slice, 64-replicate tile, 16 JT-column block), partial rows per workgroup) and a fixed-order
+// reduction into the level totals (k_bs_reduce).  A replicate's sums therefore do not depend on B, and runs are bit-identical.
+// Scratch (tile counts, slab, partials, keep bytes) stays below 64 MiB; the totals [L][B][2 M R] are the size of the result.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "device_basis.hpp"
+
+namespace mlmc {
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+
+constexpr int BS_TILE = 4096;              // positions per tile (pass A / pass B)
+constexpr int BS_SEG_TILES = 8192;         // tiles per LDS histogram of pass A (32 KiB)
+constexpr int BS_REPS = 64;                // replicates per contraction workgroup: 4 waves x 16 MFMA rows
+constexpr int BS_KB = 64;                  // samples per batch of the contraction
+constexpr int BS_SW = 512;                 // samples per contraction workgroup
+constexpr int BS_TPR_MAX = 8;              // tiles per sample range (nr <= 32768)
+constexpr int BS_NY_MAX = 4;               // 64-replicate tiles per group (BG <= 256)
+constexpr int64_t BS_MAX_N = (int64_t)61440 * BS_TILE;   // samples per chunk: tile counts of 64 replicates within 15 MiB
+constexpr int BS_MAX_COLS = 2048;          // M * R
+constexpr size_t BS_COUNTS_BYTES = (size_t)15 << 20;
+constexpr size_t BS_W_BYTES = (size_t)BS_NY_MAX * BS_REPS * BS_TPR_MAX * BS_TILE * 4;     // 32 MiB
+constexpr size_t BS_PART_BYTES = (size_t)16 << 20;
+
+__device__ __forceinline__ void bs_philox(uint32_t (&c)[4], uint64_t seed) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// pass A.  grid (workgroups per replicate, replicates, tile segments); sizes[b] picks of replicate b0 + b.
+__global__ __launch_bounds__(256) void k_bs_tile_counts(int64_t n, int64_t n_tiles, const int64_t *__restrict__ sizes, int64_t b0,
+                                                        int64_t pairs_per_wg, uint64_t seed, uint32_t stream,
+                                                        int32_t *__restrict__ counts) {
+    __shared__ int hist[BS_SEG_TILES];
+    const int64_t s = sizes[blockIdx.y];
+    const int64_t n_pairs = (s + 1) / 2;
+    const int64_t p0 = (int64_t)blockIdx.x * pairs_per_wg;
+    if (p0 >= n_pairs) return;                                   // (uniform over the workgroup)
+    const int64_t seg0 = (int64_t)blockIdx.z * BS_SEG_TILES;
+    const int nseg = (int)std::min((int64_t)BS_SEG_TILES, n_tiles - seg0);
+    for (int t = threadIdx.x; t < nseg; t += blockDim.x) hist[t] = 0;
+    __syncthreads();
+    const int64_t p1 = std::min(n_pairs, p0 + pairs_per_wg);
+    const uint32_t b = (uint32_t)(b0 + blockIdx.y);
+    for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
+        uint32_t c[4] = {(uint32_t)p, b, 0xFFFFFFFFu, stream};
+        bs_philox(c, seed);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (2 * p + h >= s) break;
+            const uint64_t r = ((uint64_t)c[2 * h + 1] << 32) | c[2 * h];
+            const int64_t t = (int64_t)(__umul64hi(r, (uint64_t)n) / BS_TILE) - seg0;
+            if (t >= 0 && t < nseg) atomicAdd(&hist[t], 1);
+        }
+    }
+    __syncthreads();
+    int32_t *__restrict__ row = counts + (int64_t)blockIdx.y * n_tiles + seg0;
+    for (int t = threadIdx.x; t < nseg; t += blockDim.x)
+        if (hist[t]) atomicAdd(&row[t], hist[t]);
+}
+
+// pass B.  grid (tiles t_first .. t_first + gridDim.x - 1, replicates); w[b][t * BS_TILE - col0 + i] = weight of sample i of tile t.
+__global__ __launch_bounds__(256) void k_bs_expand(int64_t n, int64_t n_tiles, int64_t t_first, const int32_t *__restrict__ counts,
+                                                   int64_t b0, uint64_t seed, uint32_t stream, int32_t *__restrict__ w, int64_t ldw,
+                                                   int64_t col0) {
+    __shared__ int hist[BS_TILE];
+    const int64_t t = t_first + blockIdx.x;
+    const int m = counts[(int64_t)blockIdx.y * n_tiles + t];
+    const int64_t first = t * BS_TILE;
+    const uint32_t size = (uint32_t)std::min((int64_t)BS_TILE, n - first);
+    for (int i = threadIdx.x; i < BS_TILE; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    const uint32_t b = (uint32_t)(b0 + blockIdx.y);
+    for (int q4 = threadIdx.x; q4 < (m + 3) / 4; q4 += blockDim.x) {
+        uint32_t c[4] = {(uint32_t)q4, b, (uint32_t)t, stream};
+        bs_philox(c, seed);
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+            if (4 * q4 + h < m) atomicAdd(&hist[__umulhi(c[h], size)], 1);
+    }
+    __syncthreads();
+    int32_t *__restrict__ row = w + (int64_t)blockIdx.y * ldw + (first - col0);
+    for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) row[i] = hist[i];
+}
+
+// keep byte of samples i0 .. i0 + nr - 1: every component of fine and coarse passes the basis transform (moments.hip, k_mask)
+__global__ __launch_bounds__(256) void k_bs_keep(BasisParams bp, const double *__restrict__ f, const double *__restrict__ c, int64_t n,
+                                                 int M, int64_t i0, int64_t nr, uint8_t *__restrict__ keep) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
+        bool k = true;
+        for (int m = 0; m < M; ++m) {
+            bool k1, k2 = true;
+            transform_value(bp, f[(int64_t)m * n + i0 + i], k1);
+            if (c) transform_value(bp, c[(int64_t)m * n + i0 + i], k2);
+            k = k && k1 && k2;
+        }
+        keep[i] = k ? 1 : 0;
+    }
+}
+
+// The contraction.  grid (slices of BS_SW samples of the range, 64-replicate tiles, column blocks of JB = 16 JT d-columns).
+// Per batch of BS_KB samples: the weights [64][KB] and keep bytes -> LDS, Phi [KB][JB] (d of the block's columns; 0 for dropped
+// samples) -> LDS, then each wave runs KB / 4 k-steps of 2 JT MFMAs: sum w d and sum w d^2 for its 16 replicates.  The kept
+// count sum w keep is an integer sum on the side (column block 0).  Partial rows: [64][2 JB] per workgroup, counts [64].
+template <int KIND, bool PAIR, int JT>
+__global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const double *__restrict__ fine, const double *__restrict__ coarse,
+                                                     int64_t n, int M, int R, int64_t i0, int64_t nr,
+                                                     const uint8_t *__restrict__ keep, const int32_t *__restrict__ W, int64_t ldw,
+                                                     int reps, double *__restrict__ partials, int32_t *__restrict__ pcnt) {
+    constexpr int JB = 16 * JT;
+    constexpr int KB = BS_KB;
+    constexpr int WS = KB + 4;                       // rows of 16 replicates x 4 samples hit 64 distinct banks
+    constexpr int PS = 32 * ((JB + 31) / 32) + 16;   // == 16 (mod 32): two k-rows of a fragment read in distinct bank halves
+    __shared__ int32_t wl[BS_REPS * WS];
+    __shared__ double ph[KB * PS];
+    __shared__ uint8_t kp[KB];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.z * JB;
+    const int m_lo = j0 / R, m_hi = std::min(M - 1, (j0 + JB - 1) / R);
+    const int ncomp = m_hi - m_lo + 1;
+    const int y0 = blockIdx.y * BS_REPS;
+    const int64_t s_begin = (int64_t)blockIdx.x * BS_SW, s_end = std::min(nr, s_begin + BS_SW);
+
+    v4f64 a1[JT], a2[JT];
+#pragma unroll
+    for (int J = 0; J < JT; ++J) {
+        a1[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
+        a2[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    }
+    int cnt = 0;
+    for (int64_t s0 = s_begin; s0 < s_end; s0 += KB) {
+        const int kb = (int)std::min((int64_t)KB, s_end - s0);
+        for (int e = threadIdx.x; e < BS_REPS * KB; e += 256) {
+            const int r = e / KB, k = e % KB;
+            wl[r * WS + k] = (y0 + r < reps && k < kb) ? W[(int64_t)(y0 + r) * ldw + s0 + k] : 0;
+        }
+        if (threadIdx.x < KB) kp[threadIdx.x] = (int)threadIdx.x < kb ? keep[s0 + threadIdx.x] : 0;
+        for (int e = threadIdx.x; e < KB * JB; e += 256) ph[(e / JB) * PS + e % JB] = 0.0;
+        __syncthreads();
+        for (int it = threadIdx.x; it < KB * ncomp; it += 256) {
+            const int k = it % KB, m = m_lo + it / KB;
+            if (k >= kb || !kp[k]) continue;
+            const int64_t idx = (int64_t)m * n + i0 + s0 + k;
+            bool kf, kc = true;
+            const double tf = transform_value(bp, fine[idx], kf);
+            const double tc = PAIR ? transform_value(bp, coarse[idx], kc) : 0.0;
+            TermGen<KIND> gf, gc;
+            gf.init(tf, 1.0, bp);
+            if (PAIR) gc.init(tc, 1.0, bp);
+            const int rb = j0 - m * R, re = std::min(R, j0 + JB - m * R);   // the block holds terms rb .. re - 1 of component m
+            for (int r = 0; r < re; ++r) {
+                double d = gf.next(r);
+                if (PAIR) d -= gc.next(r);
+                if (r >= rb) ph[k * PS + (r - rb)] = d;
+            }
+        }
+        __syncthreads();
+        const int arow = (16 * wave + (lane & 15)) * WS;
+#pragma unroll 4
+        for (int kk = 0; kk < KB / 4; ++kk) {
+            const int k = 4 * kk + (lane >> 4);
+            const int wv = wl[arow + k];
+            cnt += wv * (int)kp[k];
+            const double a = (double)wv;
+#pragma unroll
+            for (int J = 0; J < JT; ++J) {
+                const double bv = ph[k * PS + 16 * J + (lane & 15)];
+                a1[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, a1[J], 0, 0, 0);
+                a2[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv * bv, a2[J], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // f64 MFMA C/D layout: register r of lane l holds (row l / 16 + 4 r, column l % 16) of the tile
+    double *__restrict__ prow = partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (BS_REPS * 2 * JB);
+#pragma unroll
+    for (int J = 0; J < JT; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rep = 16 * wave + (lane >> 4) + 4 * r, col = 16 * J + (lane & 15);
+            prow[rep * 2 * JB + col] = a1[J][r];
+            prow[rep * 2 * JB + JB + col] = a2[J][r];
+        }
+    if (blockIdx.z == 0) {
+        cnt += __shfl_xor(cnt, 16, 64);
+        cnt += __shfl_xor(cnt, 32, 64);
+        if (lane < 16) pcnt[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * BS_REPS + 16 * wave + lane] = cnt;
+    }
+}
+
+// Level totals += the partial rows of one contraction launch, summed over the slices in a fixed order.
+// grid (ceil(64 * 2 JB / 256), 64-replicate tiles, column blocks).  tot: [B][2 MR] of the level (s | sp), cnt: [B].
+__global__ __launch_bounds__(256) void k_bs_reduce(const double *__restrict__ partials, const int32_t *__restrict__ pcnt, int nx, int JB,
+                                                   int MR, int64_t b_first, int reps, double *__restrict__ tot,
+                                                   int64_t *__restrict__ cnt) {
+    const int row = BS_REPS * 2 * JB;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < row) {
+        const int rep = e / (2 * JB), c = e % (2 * JB);
+        const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
+        double s = 0.0;
+        for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
+        const int b = blockIdx.y * BS_REPS + rep;
+        const int j = blockIdx.z * JB + (c % JB);
+        if (b < reps && j < MR) tot[(b_first + b) * 2 * MR + (c < JB ? j : MR + j)] += s;
+    }
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < BS_REPS) {
+        const int b = blockIdx.y * BS_REPS + threadIdx.x;
+        if (b < reps) {
+            int64_t s = 0;
+            for (int x = 0; x < nx; ++x) s += pcnt[((int64_t)blockIdx.y * nx + x) * BS_REPS + threadIdx.x];
+            cnt[b_first + b] += s;
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------
+struct BsScratch {              // one per accumulator / weights call: sized by the budgets above, never by B x n
+    int32_t *counts = nullptr;   // [rows][n_tiles]
+    int32_t *w = nullptr;        // [BG][nr]
+    double *part = nullptr;
+    int32_t *pcnt = nullptr;
+    uint8_t *keep = nullptr;
+};
+
+static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// pass A for replicates b0 .. b0 + nb - 1 (sizes: device-readable) into counts [nb][n_tiles] (zeroed here)
+static int launch_tile_counts(int64_t n, int64_t nb, const int64_t *d_sizes, int64_t max_size, int64_t b0, uint64_t seed,
+                              uint32_t stream, int32_t *counts) {
+    const int64_t n_tiles = cdiv(n, BS_TILE);
+    MLMC_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)(nb * n_tiles), rt().stream));
+    if (max_size <= 0) return 0;
+    const int64_t nseg = cdiv(n_tiles, BS_SEG_TILES);
+    // enough positions per workgroup that the flush of its histogram (<= BS_SEG_TILES integer atomics) stays a small part
+    const int64_t pairs_per_wg = std::max<int64_t>(4096, 4 * std::min<int64_t>(n_tiles, BS_SEG_TILES));
+    const int64_t gx = cdiv(cdiv(max_size, 2), pairs_per_wg);
+    hipLaunchKernelGGL(k_bs_tile_counts, dim3((unsigned)gx, (unsigned)nb, (unsigned)nseg), dim3(256), 0, rt().stream, n, n_tiles,
+                       d_sizes, b0, pairs_per_wg, seed, stream, counts);
+    MLMC_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int launch_expand(int64_t n, int64_t nb, int64_t t_first, int64_t nt, const int32_t *counts, int64_t b0, uint64_t seed,
+                         uint32_t stream, int32_t *w, int64_t ldw, int64_t col0) {
+    if (nt <= 0 || nb <= 0) return 0;
+    hipLaunchKernelGGL(k_bs_expand, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, rt().stream, n, cdiv(n, BS_TILE), t_first,
+                       counts, b0, seed, stream, w, ldw, col0);
+    MLMC_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static std::string check_sizes(const char *fn, const int64_t *sizes, int64_t nb, int64_t n) {
+    for (int64_t b = 0; b < nb; ++b)
+        if (sizes[b] < 0 || sizes[b] > n)
+            return std::string(fn) + ": sizes[" + std::to_string(b) + "] = " + std::to_string(sizes[b]) + " is outside [0, n = " +
+                   std::to_string(n) + "]";
+    return std::string();
+}
+
+}  // namespace mlmc
+
+struct mlmc_bootstrap {
+    const mlmc_basis *basis = nullptr;
+    int M = 0, L = 0, R = 0, MR = 0;
+    int64_t B = 0;
+    double *d_tot = nullptr;              // [L][B][2 MR]: sum w d | sum w d^2 (Legendre: scaled terms, finalize applies scale_c)
+    int64_t *d_cnt = nullptr;             // [L][B]
+    mlmc::BsScratch sc;
+    std::vector<int64_t *> h_sizes;       // pinned [B] blocks, one per accumulated chunk since the last finalize / reset
+    size_t sizes_used = 0;
+    std::vector<hipEvent_t> ev;           // timing pairs (FLAG_TIMING), with their kind: 0 = RNG, 1 = contraction
+    std::vector<int> ev_kind;
+    size_t ev_used = 0;
+    double ms_rng = 0, ms_contract = 0;
+    int64_t flops = 0;
+};
+
+namespace mlmc {
+
+static int bs_time(mlmc_bootstrap *a, int kind, bool end) {
+    if (!(rt().flags & 1)) return 0;
+    if (!end) {
+        if (a->ev_used + 2 > a->ev.size()) {
+            hipEvent_t e0, e1;
+            MLMC_HIP_CHECK(hipEventCreate(&e0));
+            MLMC_HIP_CHECK(hipEventCreate(&e1));
+            a->ev.push_back(e0);
+            a->ev.push_back(e1);
+            a->ev_kind.push_back(0);
+            a->ev_kind.push_back(0);
+        }
+        a->ev_kind[a->ev_used] = kind;
+        MLMC_HIP_CHECK(hipEventRecord(a->ev[a->ev_used], rt().stream));
+        return 0;
+    }
+    MLMC_HIP_CHECK(hipEventRecord(a->ev[a->ev_used + 1], rt().stream));
+    a->ev_used += 2;
+    return 0;
+}
+
+static int bs_time_collect(mlmc_bootstrap *a) {
+    for (size_t i = 0; i + 1 < a->ev_used; i += 2) {
+        float ms = 0.f;
+        MLMC_HIP_CHECK(hipEventElapsedTime(&ms, a->ev[i], a->ev[i + 1]));
+        (a->ev_kind[i] ? a->ms_contract : a->ms_rng) += ms;
+    }
+    a->ev_used = 0;
+    return 0;
+}
+
+static int bs_scratch_alloc(BsScratch &sc) {
+    MLMC_HIP_CHECK(hipMalloc((void **)&sc.counts, BS_COUNTS_BYTES));
+    MLMC_HIP_CHECK(hipMalloc((void **)&sc.w, BS_W_BYTES));
+    MLMC_HIP_CHECK(hipMalloc((void **)&sc.part, BS_PART_BYTES));
+    MLMC_HIP_CHECK(hipMalloc((void **)&sc.pcnt, (size_t)BS_NY_MAX * BS_TPR_MAX * (BS_TILE / BS_SW) * BS_REPS * 4));
+    MLMC_HIP_CHECK(hipMalloc((void **)&sc.keep, (size_t)BS_TPR_MAX * BS_TILE));
+    return 0;
+}
+
+static void bs_scratch_free(BsScratch &sc) {
+    if (sc.counts) (void)hipFree(sc.counts);
+    if (sc.w) (void)hipFree(sc.w);
+    if (sc.part) (void)hipFree(sc.part);
+    if (sc.pcnt) (void)hipFree(sc.pcnt);
+    if (sc.keep) (void)hipFree(sc.keep);
+    sc = BsScratch();
+}
+
+template <int KIND, bool PAIR>
+static void launch_contract_kind(int JT, dim3 grid, const BasisParams &bp, const double *f, const double *c, int64_t n, int M, int R,
+                                 int64_t i0, int64_t nr, const uint8_t *keep, const int32_t *W, int64_t ldw, int reps, double *part,
+                                 int32_t *pcnt) {
+    if (JT == 1)
+        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 1>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
+    else if (JT == 2)
+        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 2>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
+    else
+        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 4>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
+}
+
+static void launch_contract(int JT, dim3 grid, const BasisParams &bp, const double *f, const double *c, int64_t n, int M, int R,
+                            int64_t i0, int64_t nr, const uint8_t *keep, const int32_t *W, int64_t ldw, int reps, double *part,
+                            int32_t *pcnt) {
+#define MLMC_BS_KIND(K)                                                                                                    \
+    if (c) launch_contract_kind<K, true>(JT, grid, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);             \
+    else launch_contract_kind<K, false>(JT, grid, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
+    if (bp.kind == MLMC_LEGENDRE) { MLMC_BS_KIND(MLMC_LEGENDRE) }
+    else if (bp.kind == MLMC_MONOMIAL) { MLMC_BS_KIND(MLMC_MONOMIAL) }
+    else { MLMC_BS_KIND(MLMC_FOURIER) }
+#undef MLMC_BS_KIND
+}
+
+}  // namespace mlmc
+
+extern "C" int mlmc_bootstrap_weights(int64_t n, int64_t b0, int64_t nb, const int64_t *sizes, uint64_t seed, uint32_t stream,
+                                      int32_t *w_out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (!sizes || !w_out) return fail("mlmc_bootstrap_weights: null argument (sizes, w_out)");
+    if (n < 1 || n > BS_MAX_N)
+        return fail("mlmc_bootstrap_weights: n = " + std::to_string(n) + " (must be in 1 .. " + std::to_string(BS_MAX_N) + ")");
+    if (b0 < 0 || nb < 1 || b0 + nb > (int64_t)UINT32_MAX)
+        return fail("mlmc_bootstrap_weights: replicates b0 = " + std::to_string(b0) + ", nb = " + std::to_string(nb) +
+                    " (need b0 >= 0, nb >= 1, b0 + nb < 2^32)");
+    const std::string err = check_sizes("mlmc_bootstrap_weights", sizes, nb, n);
+    if (!err.empty()) return fail(err);
+    BsScratch sc;
+    struct Guard {
+        BsScratch &s;
+        ~Guard() { (void)wait_stream(rt().stream); bs_scratch_free(s); }
+    } guard{sc};
+    int64_t *d_sizes = nullptr;
+    if (int rc = bs_scratch_alloc(sc)) return rc;
+    const int64_t n_tiles = cdiv(n, BS_TILE);
+    const int64_t rows = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)65535, (int64_t)(BS_COUNTS_BYTES / 4) / n_tiles}));
+    MLMC_HIP_CHECK(hipMalloc((void **)&d_sizes, sizeof(int64_t) * (size_t)nb));
+    MLMC_HIP_CHECK(hipMemcpy(d_sizes, sizes, sizeof(int64_t) * (size_t)nb, hipMemcpyHostToDevice));
+    int rc = 0;
+    for (int64_t g = 0; g < nb && !rc; g += rows) {
+        const int64_t ng = std::min(rows, nb - g);
+        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
+        rc = launch_tile_counts(n, ng, d_sizes + g, mx, b0 + g, seed, stream, sc.counts);
+        if (!rc) rc = launch_expand(n, ng, 0, n_tiles, sc.counts, b0 + g, seed, stream, w_out + g * n, n, 0);
+    }
+    hipError_t e = wait_stream(rt().stream);
+    (void)hipFree(d_sizes);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("mlmc_bootstrap_weights: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_create(const mlmc_basis *b, int32_t M, int32_t n_levels, int64_t B, mlmc_bootstrap **out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (!b || !out) return fail("mlmc_bootstrap_create: null argument (basis, out)");
+    if (b->p.kind != MLMC_LEGENDRE && b->p.kind != MLMC_MONOMIAL && b->p.kind != MLMC_FOURIER)
+        return fail("mlmc_bootstrap_create: basis kind " + std::to_string(b->p.kind) +
+                    " is not supported (Legendre, monomial and Fourier moments only)");
+    if (b->out_size > 0) return fail("mlmc_bootstrap_create: transformed bases are not supported");
+    if (b->p.kind == MLMC_LEGENDRE && b->p.size > LEGENDRE_MAX_TERMS)
+        return fail("mlmc_bootstrap_create: Legendre size " + std::to_string(b->p.size) + " (at most " + std::to_string(LEGENDRE_MAX_TERMS) + ")");
+    if (M < 1) return fail("mlmc_bootstrap_create: M = " + std::to_string(M) + " (must be >= 1)");
+    if ((int64_t)M * b->p.size > BS_MAX_COLS)
+        return fail("mlmc_bootstrap_create: M * R = " + std::to_string((int64_t)M * b->p.size) + " columns, at most " +
+                    std::to_string(BS_MAX_COLS) + " are supported");
+    if (n_levels < 1 || n_levels > 2047) return fail("mlmc_bootstrap_create: n_levels = " + std::to_string(n_levels) + " (must be in 1 .. 2047)");
+    if (B < 1 || B > (int64_t)INT32_MAX) return fail("mlmc_bootstrap_create: B = " + std::to_string(B) + " (must be in 1 .. 2^31 - 1)");
+    mlmc_bootstrap *a = new mlmc_bootstrap();
+    a->basis = b;
+    a->M = M;
+    a->L = n_levels;
+    a->R = b->p.size;
+    a->MR = M * b->p.size;
+    a->B = B;
+    const size_t tot = sizeof(double) * (size_t)n_levels * (size_t)B * 2 * (size_t)a->MR;
+    if (hipMalloc((void **)&a->d_tot, tot) != hipSuccess || hipMalloc((void **)&a->d_cnt, sizeof(int64_t) * (size_t)n_levels * B) != hipSuccess ||
+        bs_scratch_alloc(a->sc) != 0) {
+        (void)hipGetLastError();
+        if (a->d_tot) (void)hipFree(a->d_tot);
+        if (a->d_cnt) (void)hipFree(a->d_cnt);
+        bs_scratch_free(a->sc);
+        delete a;
+        return fail("mlmc_bootstrap_create: out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch)");
+    }
+    MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, tot, rt().stream));
+    MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)n_levels * B, rt().stream));
+    *out = a;
+    return 0;
+}
+
+extern "C" void mlmc_bootstrap_destroy(mlmc_bootstrap *a) {
+    if (!a) return;
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    (void)wait_stream(rt().stream);
+    if (a->d_tot) (void)hipFree(a->d_tot);
+    if (a->d_cnt) (void)hipFree(a->d_cnt);
+    bs_scratch_free(a->sc);
+    for (int64_t *p : a->h_sizes) (void)hipHostFree(p);
+    for (hipEvent_t e : a->ev) (void)hipEventDestroy(e);
+    delete a;
+}
+
+extern "C" int mlmc_bootstrap_reset(mlmc_bootstrap *a) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_reset: null handle");
+    MLMC_HIP_CHECK(wait_stream(rt().stream));     // earlier chunks may still read the pinned sizes
+    a->sizes_used = 0;
+    a->ev_used = 0;
+    MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, sizeof(double) * (size_t)a->L * (size_t)a->B * 2 * (size_t)a->MR, rt().stream));
+    MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)a->L * (size_t)a->B, rt().stream));
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_accum(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n,
+                                    const int64_t *sizes, uint64_t seed, uint32_t stream) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (!a) return fail("mlmc_bootstrap_accum: null handle");
+    if (!fine || !sizes) return fail("mlmc_bootstrap_accum: null argument (fine, sizes)");
+    if (level < 0 || level >= a->L) return fail("mlmc_bootstrap_accum: level = " + std::to_string(level) + " (must be in 0 .. " + std::to_string(a->L - 1) + ")");
+    if (n < 1 || n > BS_MAX_N)
+        return fail("mlmc_bootstrap_accum: n = " + std::to_string(n) + " (must be in 1 .. " + std::to_string(BS_MAX_N) + ")");
+    const std::string err = check_sizes("mlmc_bootstrap_accum", sizes, a->B, n);
+    if (!err.empty()) return fail(err);
+    const int64_t B = a->B;
+    // the sizes go to a pinned block the kernels read in place: no copy to wait for, the block is reused after finalize / reset
+    if (a->sizes_used == a->h_sizes.size()) {
+        int64_t *p = nullptr;
+        MLMC_HIP_CHECK(hipHostMalloc((void **)&p, sizeof(int64_t) * (size_t)B, hipHostMallocDefault));
+        a->h_sizes.push_back(p);
+    }
+    int64_t *hs = a->h_sizes[a->sizes_used++];
+    std::memcpy(hs, sizes, sizeof(int64_t) * (size_t)B);
+    int64_t *ds = nullptr;
+    MLMC_HIP_CHECK(hipHostGetDevicePointer((void **)&ds, hs, 0));
+
+    const int MR = a->MR;
+    const int JT = MR <= 16 ? 1 : (MR <= 32 ? 2 : 4);
+    const int JB = 16 * JT;
+    const int ncb = (int)cdiv(MR, JB);
+    const int64_t n_tiles = cdiv(n, BS_TILE);
+    const size_t pwb = (size_t)BS_REPS * 2 * JB * sizeof(double);      // partial row block of one workgroup
+    constexpr int SPT = BS_TILE / BS_SW;                                 // slices per tile
+    // sample range: a function of n and the column blocks only (a replicate's summation order must not depend on B)
+    const int64_t tpr = std::max<int64_t>(1, std::min<int64_t>({n_tiles, (int64_t)BS_TPR_MAX, (int64_t)(BS_PART_BYTES / (pwb * SPT * ncb))}));
+    const int64_t nr = tpr * BS_TILE;
+    const int64_t nx_full = tpr * SPT;
+    int64_t ny = std::min<int64_t>({cdiv(B, BS_REPS), (int64_t)BS_NY_MAX, (int64_t)(BS_PART_BYTES / (pwb * nx_full * ncb)),
+                                    (int64_t)(BS_COUNTS_BYTES / (4 * (size_t)BS_REPS * n_tiles))});
+    ny = std::max<int64_t>(ny, 1);
+    const int64_t BG = ny * BS_REPS;
+    const BasisParams bp = a->basis->p;
+    double *tot = a->d_tot + (size_t)level * B * 2 * MR;
+    int64_t *cnt = a->d_cnt + (size_t)level * B;
+    const dim3 rgrid((unsigned)cdiv(BS_REPS * 2 * JB, 256), 0, (unsigned)ncb);
+    for (int64_t g = 0; g < B; g += BG) {
+        const int64_t ng = std::min(BG, B - g);
+        const int64_t nyg = cdiv(ng, BS_REPS);
+        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
+        if (int rc = bs_time(a, 0, false)) return rc;
+        if (int rc = launch_tile_counts(n, ng, ds + g, mx, g, seed, stream, a->sc.counts)) return rc;
+        if (int rc = bs_time(a, 0, true)) return rc;
+        for (int64_t i0 = 0; i0 < n; i0 += nr) {
+            const int64_t len = std::min(nr, n - i0);
+            const int64_t nt = cdiv(len, BS_TILE), nx = cdiv(len, BS_SW);
+            if (int rc = bs_time(a, 0, false)) return rc;
+            if (int rc = launch_expand(n, ng, i0 / BS_TILE, nt, a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
+            if (int rc = bs_time(a, 0, true)) return rc;
+            if (int rc = bs_time(a, 1, false)) return rc;
+            hipLaunchKernelGGL(k_bs_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, bp, fine, coarse, n, a->M, i0, len,
+                               a->sc.keep);
+            MLMC_HIP_CHECK(hipGetLastError());
+            const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
+            launch_contract(JT, grid, bp, fine, coarse, n, a->M, a->R, i0, len, a->sc.keep, a->sc.w, nr, (int)ng, a->sc.part, a->sc.pcnt);
+            MLMC_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_bs_reduce, dim3(rgrid.x, (unsigned)nyg, rgrid.z), dim3(256), 0, rt().stream, a->sc.part, a->sc.pcnt,
+                               (int)nx, JB, MR, g, (int)ng, tot, cnt);
+            MLMC_HIP_CHECK(hipGetLastError());
+            if (int rc = bs_time(a, 1, true)) return rc;
+            // executed matrix-core flops: every batch of every workgroup runs KB / 4 k-steps of 2 JT MFMAs per wave
+            const int64_t batches = (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
+            a->flops += batches * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
+        }
+    }
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_finalize(mlmc_bootstrap *a, int64_t *n_out, double *s_out, double *sp_out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_finalize: null handle");
+    if (!n_out || !s_out || !sp_out) return fail("mlmc_bootstrap_finalize: null argument (n_out, s_out, sp_out)");
+    const int64_t L = a->L, B = a->B, MR = a->MR;
+    std::vector<double> tot((size_t)L * B * 2 * MR);
+    std::vector<int64_t> cnt((size_t)L * B);
+    MLMC_HIP_CHECK(hipMemcpyAsync(tot.data(), a->d_tot, sizeof(double) * tot.size(), hipMemcpyDeviceToHost, rt().stream));
+    MLMC_HIP_CHECK(hipMemcpyAsync(cnt.data(), a->d_cnt, sizeof(int64_t) * cnt.size(), hipMemcpyDeviceToHost, rt().stream));
+    MLMC_HIP_CHECK(wait_stream(rt().stream));
+    a->sizes_used = 0;
+    if (int rc = bs_time_collect(a)) return rc;
+    const std::vector<double> &c = a->basis->scale_c;     // Legendre: P_r = c_r q_r of the scaled recurrence; else ones
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t l = 0; l < L; ++l) {
+            n_out[b * L + l] = cnt[l * B + b];
+            const double *t = tot.data() + (l * B + b) * 2 * MR;
+            double *s = s_out + (b * L + l) * MR, *sp = sp_out + (b * L + l) * MR;
+            for (int64_t j = 0; j < MR; ++j) {
+                const double cj = c[j % a->R];
+                s[j] = cj * t[j];
+                sp[j] = (cj * cj) * t[MR + j];
+            }
+        }
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_kernel_time(mlmc_bootstrap *a, double *ms_contract, double *ms_rng, int64_t *mfma_flops) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_kernel_time: null handle");
+    MLMC_HIP_CHECK(wait_stream(rt().stream));
+    if (int rc = bs_time_collect(a)) return rc;
+    if (ms_contract) *ms_contract = a->ms_contract;
+    if (ms_rng) *ms_rng = a->ms_rng;
+    if (mfma_flops) *mfma_flops = a->flops;
+    a->ms_contract = a->ms_rng = 0;
+    a->flops = 0;
+    return 0;
+}

@@ -65,6 +65,14 @@ __device__ __forceinline__ unsigned long long order_key(double x) {
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // monotone in x for all non-NaN values (-0.0 < +0.0)
 }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): one round (select.hip, bootstrap.hip) -----------------
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
 // ---- device-visible basis parameters (passed by value to kernels) -------------------------
 struct BasisParams {
     int kind;

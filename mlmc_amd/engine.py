@@ -359,3 +359,75 @@ def row_percentiles(values, q_percent, nan_policy="omit"):
     if nan_policy == "propagate":
         out[n_valid < n] = np.nan
     return out
+
+
+def bootstrap_weights(n, sizes, seed, stream=0, b0=0, device=False):
+    """The integer weights [nb, n] of bootstrap replicates b0 .. b0 + nb - 1 of one chunk of n samples (mlmc_bootstrap_weights):
+    row b picks sizes[b] of the n samples uniformly with replacement, a Multinomial(sizes[b], 1 / n) draw that depends on
+    (seed, stream, n, b0 + b, sizes[b]) only.  BootstrapAccumulator.accum uses exactly these weights.  -> int32 NumPy array, or
+    the torch CUDA tensor with device=True."""
+    import torch
+    sizes = np.ascontiguousarray(np.atleast_1d(sizes), dtype=np.int64)
+    if sizes.ndim != 1:
+        raise ValueError("bootstrap_weights: sizes must be one-dimensional, got shape {}".format(sizes.shape))
+    lib = _lib.lib()
+    w = torch.empty((sizes.size, max(int(n), 0)), dtype=torch.int32, device=torch.device("cuda", _lib._bound_device))
+    _lib.check(lib.mlmc_bootstrap_weights(int(n), int(b0), int(sizes.size), _lib.ptr(sizes), int(seed) & (2 ** 64 - 1),
+                                                 int(stream) & 0xFFFFFFFF, _lib.ptr(w)))
+    return w if device else w.cpu().numpy()
+
+
+class BootstrapAccumulator:
+    """Per-replicate level sums of the moments of a quantity with n_comp components for B bootstrap replicates (mlmc_bootstrap_*):
+    accum() adds one chunk with the weights of bootstrap_weights(n, sizes, seed, stream), finalize() returns n [B, L] kept counts
+    and s, sp [B, L, n_comp * R] (row m * R + r) -- what a LevelAccumulator in MOMENTS mode gives for the resampled chunks."""
+
+    def __init__(self, moments_fn, n_comp, n_levels, n_replicates):
+        self._moments_fn = moments_fn
+        self.n_comp, self.n_levels, self.B = int(n_comp), int(n_levels), int(n_replicates)
+        self.K = self.n_comp * int(moments_fn.size)
+        self._keepalive = []
+        h = C.c_void_p()
+        _lib.check(_lib.lib().mlmc_bootstrap_create(moments_fn._basis_handle(), self.n_comp, self.n_levels, self.B, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and _lib is not None and _lib._lib is not None:
+            _lib._lib.mlmc_bootstrap_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        _lib.check(_lib.lib().mlmc_bootstrap_reset(self._h))
+        self._keepalive = []
+
+    def accum(self, level, fine, coarse, sizes, seed, stream):
+        """fine / coarse: torch CUDA float64 tensors [n_comp, n] (coarse None at level 0); sizes: [B] picks of every replicate."""
+        if fine.dim() != 2 or fine.shape[0] != self.n_comp:
+            raise ValueError("bootstrap accum: expected fine of shape [{}, n], got {}".format(self.n_comp, tuple(fine.shape)))
+        if coarse is not None and tuple(coarse.shape) != tuple(fine.shape):
+            raise ValueError("bootstrap accum: fine and coarse shapes differ")
+        assert fine.is_cuda and fine.is_contiguous() and (coarse is None or (coarse.is_cuda and coarse.is_contiguous()))
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        if sizes.shape != (self.B,):
+            raise ValueError("bootstrap accum: sizes of shape {}, expected ({},)".format(sizes.shape, self.B))
+        self._keepalive.append((fine, coarse))             # launches are asynchronous
+        _lib.check(_lib.lib().mlmc_bootstrap_accum(self._h, int(level), _lib.ptr(fine), _lib.ptr(coarse), int(fine.shape[1]),
+                                                   _lib.ptr(sizes), int(seed) & (2 ** 64 - 1), int(stream) & 0xFFFFFFFF))
+
+    def finalize(self):
+        """-> n [B, L] int64, s [B, L, K], sp [B, L, K] float64 (one wait for the device)."""
+        n = np.empty((self.B, self.n_levels), dtype=np.int64)
+        s = np.empty((self.B, self.n_levels, self.K), dtype=np.float64)
+        sp = np.empty_like(s)
+        _lib.check(_lib.lib().mlmc_bootstrap_finalize(self._h, _lib.ptr(n), _lib.ptr(s), _lib.ptr(sp)))
+        self._keepalive = []
+        return n, s, sp
+
+    def kernel_time(self):
+        """(contraction ms, RNG ms, executed MFMA flops) since create or the previous call (needs FLAG_TIMING)."""
+        ms_c, ms_r = C.c_double(), C.c_double()
+        fl = C.c_int64()
+        _lib.check(_lib.lib().mlmc_bootstrap_kernel_time(self._h, C.byref(ms_c), C.byref(ms_r), C.byref(fl)))
+        return ms_c.value, ms_r.value, fl.value

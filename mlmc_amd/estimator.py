@@ -4,12 +4,17 @@ Every pass over the samples (moments, covariance, level variances) goes through
 `quantity_estimate.estimate_mean`, i.e. through the HIP accumulation kernels.  The O(L R) post-processing
 (variance regression over levels, n-samples allocation) is host arithmetic, as the numbers involved are tiny.
 """
+import collections
+
 import numpy as np
 
 from . import engine
 from . import linearize
 from .quantity import quantity_estimate as qe
 from .quantity.quantity_types import ScalarType
+
+
+BootstrapReplicates = collections.namedtuple("BootstrapReplicates", "n_samples l_means l_vars mean var seed")
 
 
 class Estimate:
@@ -187,10 +192,67 @@ class Estimate:
         # [L, R] for scalar quantities (reference: `[:, None]`); array-typed quantities carry extra trailing axes
         self._bs_level_mean_variance = self.var_bs_l_means * n_coll.reshape((-1,) + (1,) * (self.var_bs_l_means.ndim - 1))
 
-    def bs_target_var_n_estimated(self, target_var, sample_vec=None):
+    def est_bootstrap_batch(self, n_subsamples=100, sample_vector=None, moments_fn=None, seed=None):
+        """est_bootstrap with every replicate from one device pass per stored chunk, seeded.
+
+        Replicate b draws, in stored chunk c of level l (n_c samples, N_l collected, k_l = sample_vector[l] requested), a
+        Hypergeometric(k_l, N_l - k_l, min(n_c, N_l)) count s from a generator keyed by (seed, l, c), then s of the chunk's samples
+        uniformly with replacement (Philox, keyed by the seed) -- the distribution of est_bootstrap's sub-samples.  Its results are
+        those of estimate_mean(moments(q, fn, mom_at_bottom=False)) over that resample; the moments of each stored sample are
+        evaluated once, the replicates are an integer-weighted contraction on the matrix cores (mlmc_bootstrap_accum).  Results are
+        bit-identical from run to run, and the first B replicates do not depend on n_subsamples.  Sets the attributes of
+        est_bootstrap (mean_bs_* / var_bs_* over the replicates, _bs_level_mean_variance).
+        :param seed: None: one 63-bit seed drawn from quantity.RNG (seeding that RNG makes the call reproducible)
+        :return: BootstrapReplicates(n_samples [B, L], l_means, l_vars, mean, var -- leading axis B -- and the seed)
+        Legendre, monomial and Fourier moments only (log / safe_eval included); est_bootstrap serves the others."""
+        from .moments import Legendre, Monomial, Fourier
+        from .quantity import quantity as qmod
+        if moments_fn is None:
+            moments_fn = self._moments_fn
+        if type(moments_fn) not in (Legendre, Monomial, Fourier):
+            raise ValueError("est_bootstrap_batch: {} moments are not supported (Legendre, Monomial and Fourier are); use "
+                             "est_bootstrap for them".format(type(moments_fn).__name__))
+        if isinstance(n_subsamples, (bool, np.bool_)) or not isinstance(n_subsamples, (int, np.integer)) or n_subsamples < 1:
+            raise ValueError("est_bootstrap_batch: n_subsamples must be an integer >= 1, got {!r}".format(n_subsamples))
+        n_levels = self._sample_storage.get_n_levels()
+        n_coll = np.array(self._sample_storage.get_n_collected())[:n_levels]
+        k = determine_sample_vec(n_collected_samples=n_coll, n_levels=n_levels, sample_vector=sample_vector)
+        if k.shape != (n_levels,) or not np.all(np.isfinite(k.astype(np.float64))) or np.any(k != np.round(k)):
+            raise ValueError("est_bootstrap_batch: sample_vector must hold one integer per level, got {!r}".format(sample_vector))
+        k = k.astype(np.int64)
+        if np.any(k < 0) or np.any(k > n_coll):
+            raise ValueError("est_bootstrap_batch: sample_vector {} must lie in 0 .. n_collected {} on every level".format(
+                k.tolist(), n_coll.tolist()))
+        if int(self._quantity.size()) * moments_fn.size > 2048:
+            raise ValueError("est_bootstrap_batch: {} components x {} moments, at most 2048 columns are supported".format(
+                int(self._quantity.size()), moments_fn.size))
+        if seed is None:
+            seed = int(qmod.RNG.integers(0, 2 ** 63 - 1))
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("est_bootstrap_batch: seed must be an integer in [0, 2^64), got {!r}".format(seed))
+        seed = int(seed)
+        self._moments_fn = moments_fn
+        n, s, sp = qe.bootstrap_moments(self._quantity, moments_fn, int(n_subsamples), k, seed)
+        r = qe.bootstrap_statistics(self._quantity, moments_fn, n, s, sp)
+        self.mean_bs_mean = np.mean(r["mean"], axis=0)
+        self.mean_bs_var = np.mean(r["var"], axis=0)
+        self.mean_bs_l_means = np.mean(r["l_means"], axis=0)
+        self.mean_bs_l_vars = np.mean(r["l_vars"], axis=0)
+        self.var_bs_mean = np.var(r["mean"], axis=0, ddof=1)
+        self.var_bs_var = np.var(r["var"], axis=0, ddof=1)
+        self.var_bs_l_means = np.var(r["l_means"], axis=0, ddof=1)
+        self.var_bs_l_vars = np.var(r["l_vars"], axis=0, ddof=1)
+        self._bs_level_mean_variance = self.var_bs_l_means * n_coll.reshape((-1,) + (1,) * (self.var_bs_l_means.ndim - 1))
+        return BootstrapReplicates(r["n_samples"], r["l_means"], r["l_vars"], r["mean"], r["var"], seed)
+
+    def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
+        """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""
         sample_vec = determine_sample_vec(n_collected_samples=self._sample_storage.get_n_collected(),
                                           n_levels=self._sample_storage.get_n_levels(), sample_vector=sample_vec)
-        self.est_bootstrap(n_subsamples=300, sample_vector=sample_vec)
+        if batch:
+            self.est_bootstrap_batch(n_subsamples=300, sample_vector=sample_vec, seed=seed)
+        else:
+            self.est_bootstrap(n_subsamples=300, sample_vector=sample_vec)
         variances, n_ops = self.estimate_diff_vars_regression(sample_vec, raw_vars=self.mean_bs_l_vars)
         return estimate_n_samples_for_target_variance(target_var, variances, n_ops,
                                                       n_levels=self._sample_storage.get_n_levels())

@@ -1228,6 +1228,118 @@ def _estimate_mean(quantity, group, variance):
     return _finish_estimate(quantity, fn, n_levels, n_comp, rows_out, n_samples, n_rm_samples, sums, sums_sq)
 
 
+BOOTSTRAP_FAMILIES = ("Legendre", "Monomial", "Fourier")     # moments families of the batched bootstrap (mlmc_bootstrap_create)
+
+
+def bootstrap_sizes(seed, level, chunk, k, n_level, n_chunk, n_replicates):
+    """Sub-sample sizes of one stored chunk for replicates 0 .. n_replicates - 1, as the loop draws them per chunk
+    (_subsample_on_device): Hypergeometric(good = k, bad = N - k, draws = min(n_c, N)), here from a generator keyed by
+    (seed, level, chunk index of the level) alone -- replicate b's size does not depend on the number of replicates."""
+    rng = np.random.default_rng([int(seed), int(level), int(chunk)])
+    return rng.hypergeometric(int(k), int(n_level) - int(k), min(int(n_chunk), int(n_level)), size=int(n_replicates)).astype(np.int64)
+
+
+def bootstrap_stream(level, chunk):
+    """Philox stream of a stored chunk (mlmc_bootstrap_weights / mlmc_bootstrap_accum): level << 20 | chunk index of the level."""
+    return (int(level) << 20) | int(chunk)
+
+
+def bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
+    """Level sums of `moments(quantity, moments_fn, mom_at_bottom=False)` for n_replicates bootstrap sub-samples at once
+    (Estimate.est_bootstrap_batch).  Replicate b picks, in stored chunk c of level l (n_c samples, N_l collected, k_l requested),
+    s = bootstrap_sizes(seed, l, c, ...)[b] samples uniformly with replacement; its sums are those of estimate_mean over that
+    resample.  Walks the storage's own chunks (not the consolidated level tensors); ONE device wait, at the end.
+    -> n [B, L] kept counts, s, sp [B, L, M * R] (row m * R + r)"""
+    with _estimate_lock:
+        return _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed)
+
+
+def _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
+    import torch
+    cache_clear()
+    storage_q = quantity.get_quantity_storage()
+    n_levels = int(np.max(storage_q.level_ids())) + 1
+    n_level = [int(v) for v in storage_q.n_collected()]
+    plan = lowering.plan_for(quantity) if _device_tree_enabled() else None
+    try:
+        n_collected = _level_stamps(storage_q)
+    except Exception:
+        n_collected = None
+    use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(quantity, "_volatile", False)
+    dev = torch.device("cuda", _lib_device())
+    M = int(quantity.size())
+    key = (id(moments_fn), M, n_levels, int(n_replicates))
+    kept = _bootstrap_pool.pop("acc", None)                       # the last accumulator (64 MiB of scratch, pinned size blocks)
+    if kept is not None and kept[0] == key:
+        acc = kept[1]
+        acc.reset()
+    else:
+        if kept is not None:
+            kept[1].close()
+        acc = engine.BootstrapAccumulator(moments_fn, M, n_levels, n_replicates)
+    chunk_no = collections.Counter()
+    copied = False
+    pushed = 0
+    try:
+        for chunk_spec in storage_q.chunks():
+            level = int(chunk_spec.level_id)
+            c = chunk_no[level]
+            chunk_no[level] += 1
+            fine, coarse = _chunk_for_device(quantity, plan, chunk_spec, n_collected, use_cache)
+            n = fine.shape[-1]
+            if n == 0:
+                continue
+            pair = []
+            for t in (fine, coarse):
+                if t is None:
+                    pair.append(None)
+                    continue
+                if not isinstance(t, torch.Tensor):              # host chunk (over the cache budget): upload, as the gather path does
+                    t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
+                t2 = t.to(device=dev, dtype=torch.float64).reshape(M, n).contiguous()
+                copied = copied or t2.data_ptr() != t.data_ptr()
+                pair.append(t2)
+            if copied:
+                torch.cuda.current_stream(dev).synchronize()     # the library reads them on its own stream
+                copied = False
+            sizes = bootstrap_sizes(seed, level, c, sample_vector[level], n_level[level], n, n_replicates)
+            acc.accum(level, pair[0], pair[1], sizes, seed, bootstrap_stream(level, c))
+            pushed += 1
+        if pushed == 0:
+            raise Exception("All samples were masked")
+        out = acc.finalize()
+    except BaseException:
+        acc.close()
+        raise
+    _bootstrap_pool["acc"] = (key, acc, moments_fn)               # (moments_fn kept alive: its id stays unique)
+    return out
+
+
+_bootstrap_pool = {}
+
+
+def bootstrap_statistics(quantity, moments_fn, n, s, sp):
+    """Per-replicate l_means, l_vars, mean, var of bootstrap level sums (n [B, L], s / sp [B, L, M * R] in device row order) as
+    estimate_mean(moments(quantity, moments_fn, mom_at_bottom=False)) would return them for each replicate's resample
+    (engine.level_stats, QuantityMean, the 'on the surface' layout of _finish_estimate).  -> dict of arrays with a leading B axis."""
+    B, L, K = s.shape
+    if np.any(np.sum(n, axis=1) == 0):
+        raise Exception("All samples were masked")
+    node = moments(quantity, moments_fn, mom_at_bottom=False)
+    n_comp = K // int(moments_fn.size)
+    if n_comp > 1:
+        s = s.reshape(B, L, n_comp, -1).transpose(0, 1, 3, 2).reshape(B, L, K)
+        sp = sp.reshape(B, L, n_comp, -1).transpose(0, 1, 3, 2).reshape(B, L, K)
+    l_means, l_vars = engine.level_stats(n.reshape(B * L), s.reshape(B * L, K), sp.reshape(B * L, K))
+    l_means, l_vars = l_means.reshape(B, L, K), l_vars.reshape(B, L, K)
+    mean = np.sum(l_means, axis=1)
+    with np.errstate(all="ignore"):
+        var = np.sum(l_vars / n[:, :, None], axis=1)
+    shape = np.shape(node.qtype.reshape(np.zeros(K)))
+    return dict(n_samples=np.array(n), l_means=l_means.reshape((B, L) + shape), l_vars=l_vars.reshape((B, L) + shape),
+                mean=mean.reshape((B,) + shape), var=var.reshape((B,) + shape))
+
+
 def _finish_estimate(quantity, fn, n_levels, n_comp, rows_per_comp, n_samples, n_rm_samples, sums, sums_sq):
     if fn is not None and not quantity._at_bottom and n_comp > 1:
         # device rows are (component, moment...); 'on the surface' wants (moment..., component)
