@@ -35,7 +35,7 @@ extern "C" {
                               * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi;
                               * 8: mlmc_xcov_create, mlmc_xcov_set_shift; added within 8 (backwards compatible):
                               *    mlmc_percentiles_rows, mlmc_bootstrap_weights, mlmc_bootstrap_create / _destroy / _reset / _accum /
-                              *    _finalize / _kernel_time */
+                              *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -189,6 +189,15 @@ int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *o
 int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
                               const int32_t *levels, const double *const *fine, const double *const *coarse,
                               const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *sums);
+/* The same pass with the level variances (Estimate.estimate_component_moments / _diff_vars / _diff_vars_regression: the scalar
+ * estimate_moments / estimate_diff_vars of every component, estimator.py:32-93) -- added within 8.  Arguments, argument checks,
+ * masking rule and errors are those of mlmc_accum_estimate_multi (messages name this entry and the component); in addition
+ * sums_sq[(l * M + m) * K + k] = level sums of (phi_k(fine) - phi_k(coarse))^2 of component m.  Both sums of a (sample block,
+ * component, term window) stay in registers and are merged in a fixed order: the same chunks in the same order give the same
+ * bits.  Device scratch stays within 64 MiB (components run in groups when L * M * K exceeds about 3.5 M).  Synchronises once. */
+int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
+                                  const int32_t *levels, const double *const *fine, const double *const *coarse,
+                                  const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *sums, double *sums_sq);
 
 /* ---- covariance between the components of a vector quantity ---------------------------------------------------------
  * An accumulator of the M x M level sums, per level l and kept sample k,

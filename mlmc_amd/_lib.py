@@ -81,6 +81,8 @@ SIGNATURES = {
     "mlmc_xcov_set_shift": (C.c_int, [_vp, _vp]),
     "mlmc_accum_estimate_multi": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    "mlmc_accum_estimate_multi_var": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp]),
     "mlmc_maxent_solve_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaxentOpts), _vp, _vp, _vp, _vp]),
     "mlmc_density_eval_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mlmc_expr_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),

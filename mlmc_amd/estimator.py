@@ -120,6 +120,71 @@ class Estimate:
         sim_steps = np.squeeze(self._sample_storage.get_level_parameters())
         return self._all_moments_variance_regression(raw_vars, sim_steps), self._sample_storage.get_n_ops()
 
+    # ---- per-component estimates of a vector quantity -----------------------------------------------------------------
+    def _component_fns(self, moments_fns, what):
+        """moments_fns checked before any device work: M objects of one size (None: this Estimate's moments_fn for all)."""
+        n_comp = int(self._quantity.size())
+        if moments_fns is None:
+            if self._moments_fn is None:
+                raise ValueError("{}: no moments_fn given and none set on this Estimate".format(what))
+            moments_fns = [self._moments_fn] * n_comp
+        moments_fns = list(moments_fns)
+        if len(moments_fns) != n_comp:
+            raise ValueError("{}: {} moments objects for {} components".format(what, len(moments_fns), n_comp))
+        sizes = sorted({int(fn.size) for fn in moments_fns})
+        if len(sizes) != 1:
+            raise ValueError("{}: the moments objects must all have the same size, got sizes {}".format(what, sizes))
+        return moments_fns
+
+    def _component_estimate(self, moments_fns):
+        """-> n [L, M] int64, l_vars [L, M, R], mean [M, R], var [M, R]: row m is the scalar estimate_mean(moments(q_m, fn_m)).
+        Legendre / monomial / Fourier moments of one family: ONE device pass per stored chunk for all components
+        (quantity_estimate.component_level_sums); other moments: the per-component loop of scalar estimates."""
+        if qe.component_device_route(moments_fns):
+            n, _, s, sp = qe.component_level_sums(self._quantity, moments_fns)
+            _, l_vars, mean, var = qe.component_statistics(n, s, sp)
+            return n, l_vars, mean, var
+        comps = [self._quantity] if isinstance(self._quantity.qtype, ScalarType) else \
+            [scalar_component(self._quantity, m) for m in range(len(moments_fns))]
+        rs = qe.component_estimates(comps, moments_fns)
+        R = int(moments_fns[0].size)
+        n = np.stack([np.asarray(r.n_samples, dtype=np.int64) for r in rs], axis=1)
+        l_vars = np.stack([np.asarray(r.l_vars).reshape(-1, R) for r in rs], axis=1)
+        mean = np.stack([np.asarray(r.mean).reshape(R) for r in rs])
+        var = np.stack([np.asarray(r.var).reshape(R) for r in rs])
+        return n, l_vars, mean, var
+
+    def estimate_component_moments(self, moments_fns=None):
+        """-> (means [M, R], vars [M, R]): row m is Estimate(q_m, storage, fn_m).estimate_moments() for the scalar component
+        q_m = scalar_component(quantity, m) (row order as construct_densities documents), each component masked and clipped on
+        its own.  moments_fns: M moments objects of one size R (None: this Estimate's moments_fn for every component)."""
+        fns = self._component_fns(moments_fns, "estimate_component_moments")
+        _, _, mean, var = self._component_estimate(fns)
+        return mean, var
+
+    def estimate_component_diff_vars(self, moments_fns=None):
+        """-> (l_vars [L, M, R], n_samples [L, M] int64): column m is Estimate(q_m, storage, fn_m).estimate_diff_vars()."""
+        fns = self._component_fns(moments_fns, "estimate_component_diff_vars")
+        n, l_vars, _, _ = self._component_estimate(fns)
+        return l_vars, n
+
+    def estimate_component_diff_vars_regression(self, n_created_samples, moments_fns=None, raw_vars=None):
+        """-> (vars [L, M, R], n_ops [L]): estimate_diff_vars_regression of every component, the regression of
+        _all_moments_variance_regression over the [L, M * R] level variances (the columns of phi_0 are zero and left alone).
+        For the sample allocation: estimate_n_samples_for_target_variance(target, vars.reshape(L, -1), n_ops, L).
+        raw_vars: [L, M, R] level variances to regress instead of estimating them."""
+        self._n_created_samples = n_created_samples
+        if raw_vars is None:
+            raw_vars, _ = self.estimate_component_diff_vars(moments_fns)
+        raw_vars = np.asarray(raw_vars, dtype=np.float64)
+        if raw_vars.ndim != 3:
+            raise ValueError("estimate_component_diff_vars_regression: raw_vars must be [L, M, R], got shape {}".format(
+                raw_vars.shape))
+        n_levels = raw_vars.shape[0]
+        sim_steps = np.squeeze(self._sample_storage.get_level_parameters())
+        reg = self._all_moments_variance_regression(raw_vars.reshape(n_levels, -1), sim_steps).reshape(raw_vars.shape)
+        return reg, self._sample_storage.get_n_ops()
+
     def _all_moments_variance_regression(self, raw_vars, sim_steps):
         """Per-moment regression of the level variances (reference: :87-93), all moments in ONE least-squares solve with
         several right-hand sides (the design matrix [1, log h, log^2 h] is the same for every moment)."""

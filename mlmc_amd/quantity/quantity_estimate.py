@@ -955,15 +955,34 @@ def multi_component_sums(quantity, ext_fns):
 
 
 def _multi_component_sums(quantity, ext_fns):
+    from .. import _lib
+    M, K = len(ext_fns), int(ext_fns[0].size)
+    n_levels, keep, args = _component_chunks(quantity, M, "multi_component_sums")
+    n = np.zeros((n_levels, M), dtype=np.int64)
+    n_rm = np.zeros((n_levels, M), dtype=np.int64)
+    sums = np.zeros((n_levels, M, K))
+    _lib.check(_lib.lib().mlmc_accum_estimate_multi(M, _basis_handles(ext_fns), K, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm),
+                                                    _lib.ptr(sums)))
+    del keep
+    return n, n_rm, sums
+
+
+def _basis_handles(fns):
+    import ctypes as C
+    return C.cast((C.c_void_p * len(fns))(*[fn._basis_handle().value for fn in fns]), C.c_void_p)
+
+
+def _component_chunks(quantity, M, what):
+    """The stored chunks of `quantity` as [M, n] float64 device tensors for the per-component entries (mlmc_accum_estimate_multi,
+    _var).  -> (n_levels, tensors to keep alive until the call returns, (n_chunks, levels, fine, coarse, n_samples) arguments)"""
     import ctypes as C
     import torch
     from .. import _lib
     cache_clear()
     storage_q = quantity.get_quantity_storage()
     n_levels = int(np.max(storage_q.level_ids())) + 1
-    M, K = len(ext_fns), int(ext_fns[0].size)
     if quantity.size() != M:
-        raise ValueError("multi_component_sums: {} moments objects for {} components".format(M, quantity.size()))
+        raise ValueError("{}: {} moments objects for {} components".format(what, M, quantity.size()))
     plan = lowering.plan_for(quantity) if _device_tree_enabled() else None
     try:
         n_collected = _level_stamps(storage_q)
@@ -985,32 +1004,76 @@ def _multi_component_sums(quantity, ext_fns):
         coarses.append(None if coarse is None else coarse.data_ptr())
         ns.append(fine.shape[-1])
     torch.cuda.current_stream(dev).synchronize()
-    n = np.zeros((n_levels, M), dtype=np.int64)
-    n_rm = np.zeros((n_levels, M), dtype=np.int64)
-    sums = np.zeros((n_levels, M, K))
     nc = len(ns)
-    handles = (C.c_void_p * M)(*[fn._basis_handle().value for fn in ext_fns])
     lv = np.array(levels, dtype=np.int32)
     nn = np.array(ns, dtype=np.int64)
     fp = (C.c_void_p * max(nc, 1))(*fines)
     cp = (C.c_void_p * max(nc, 1))(*coarses)
-    _lib.check(_lib.lib().mlmc_accum_estimate_multi(M, C.cast(handles, C.c_void_p), K, n_levels, nc, _lib.ptr(lv),
-                                                    C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn), _lib.ptr(n),
-                                                    _lib.ptr(n_rm), _lib.ptr(sums)))
+    keep.append((lv, nn, fp, cp))
+    return n_levels, keep, (nc, _lib.ptr(lv), C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn))
+
+
+COMPONENT_FAMILIES = ("Legendre", "Monomial", "Fourier")     # moments of the device route of the per-component estimates
+
+
+def component_device_route(moments_fns):
+    """True when ONE pass of mlmc_accum_estimate_multi_var serves the moments objects of all components: plain Legendre,
+    monomial or Fourier moments (own domains, log, safe_eval), all of one family and one size."""
+    names = {type(fn).__name__ for fn in moments_fns}
+    return len(names) == 1 and names <= set(COMPONENT_FAMILIES) and len({int(fn.size) for fn in moments_fns}) == 1 \
+        and int(moments_fns[0].size) <= 512
+
+
+def component_level_sums(quantity, moments_fns):
+    """Level sums of the moments moments_fns[m] of component m (row m of `quantity`'s chunks, masked and clipped on its own) and of
+    their squares, ONE device pass per stored chunk for all components (mlmc_accum_estimate_multi_var).
+    -> n, n_rm [L, M] int64, s, sp [L, M, R] float64"""
+    with _estimate_lock:
+        return _component_level_sums(quantity, moments_fns)
+
+
+def _component_level_sums(quantity, moments_fns):
+    from .. import _lib
+    M, R = len(moments_fns), int(moments_fns[0].size)
+    n_levels, keep, args = _component_chunks(quantity, M, "component_level_sums")
+    n = np.zeros((n_levels, M), dtype=np.int64)
+    n_rm = np.zeros((n_levels, M), dtype=np.int64)
+    s = np.zeros((n_levels, M, R))
+    sp = np.zeros((n_levels, M, R))
+    _lib.check(_lib.lib().mlmc_accum_estimate_multi_var(M, _basis_handles(moments_fns), R, n_levels, *args, _lib.ptr(n),
+                                                        _lib.ptr(n_rm), _lib.ptr(s), _lib.ptr(sp)))
     del keep
-    return n, n_rm, sums
+    return n, n_rm, s, sp
+
+
+def component_statistics(n, s, sp):
+    """Per-level and total statistics of per-component level sums (n [L, M], s / sp [L, M, R]), as estimate_mean gives them for
+    each component alone: engine.level_stats per (level, component), mean = sum_l l_means, var = sum_l l_vars / n_l
+    (QuantityMean).  A component without a kept sample raises.  -> l_means, l_vars [L, M, R], mean, var [M, R]"""
+    L, M, R = s.shape
+    if np.any(np.sum(n, axis=0) == 0):
+        raise Exception("All samples were masked")
+    l_means, l_vars = engine.level_stats(n.reshape(L * M), s.reshape(L * M, R), sp.reshape(L * M, R))
+    l_means, l_vars = l_means.reshape(L, M, R), l_vars.reshape(L, M, R)
+    mean = np.sum(l_means, axis=0)
+    with np.errstate(all="ignore"):
+        var = np.sum(l_vars / n[:, :, None], axis=0)
+    return l_means, l_vars, mean, var
+
+
+def component_estimates(components, moments_fns, cov=False, variance=True):
+    """estimate_mean(moments|covariance(components[m], fn_m), variance) of several scalar quantities, component m with
+    moments_fns[m], each masked on its own: the per-component loop of the scalar chain.  -> list of QuantityMean"""
+    node = covariance if cov else moments
+    return [estimate_mean(node(q, fn), variance=variance) for q, fn in zip(components, moments_fns)]
 
 
 def component_means(components, moments_fns, cov=False):
     """Means of the moments (cov=False: [R] each) or of the moment covariance (True: [R, R]) of several scalar
     quantities, component m with moments_fns[m] -- entry m is estimate_mean(moments|covariance(components[m], fn_m),
     variance=False).mean, each component masked on its own (Estimate.construct_densities)."""
-    node = covariance if cov else moments
-    out = []
-    for q, fn in zip(components, moments_fns):
-        mean = estimate_mean(node(q, fn), variance=False).mean
-        out.append(mean.reshape((fn.size, fn.size)) if cov else mean.reshape(fn.size))
-    return out
+    return [r.mean.reshape((fn.size, fn.size)) if cov else r.mean.reshape(fn.size)
+            for r, fn in zip(component_estimates(components, moments_fns, cov=cov, variance=False), moments_fns)]
 
 
 def estimate_mean(quantity, group=None, variance=True):
