@@ -241,7 +241,10 @@ typedef struct {
 /* Minimise F(l) = sum_i mu_i l_i / sigma_i + int exp(-phi(x).l/sigma) dx (simple_distribution.py:259-327)
  * starting from lambda_io (size R1 = number of moments used, <= basis out size); on return lambda_io holds
  * the multipliers (normalisation fix of :86 NOT applied; see moment0), grad_out / hess_out (may be NULL) the final
- * gradient [R1] and Hessian [R1 * R1].  prev_lambda/n_prev: Distribution's stabilisation term (distribution.py:358-359), may be NULL/0. */
+ * gradient [R1] and Hessian [R1 * R1].  prev_lambda/n_prev: Distribution's stabilisation term (distribution.py:358-359), may be NULL/0.
+ * On EVERY exit (converged, iteration cap, regularisation limit) grad_out, hess_out, info->fun, info->grad_norm and
+ * info->moment0 are values AT THE RETURNED lambda_io, on the rule of n_intervals x gauss_degree points; without penalties
+ * hess_out is symmetric bit for bit.  success = 1 <=> grad_norm < tol. */
 int mlmc_maxent_solve(const mlmc_basis *b, const double *mu, const double *sigma, int32_t R1, double a, double bnd_b,
                       const mlmc_maxent_opts *opts, const double *prev_lambda, int32_t n_prev, double *lambda_io,
                       double *grad_out, double *hess_out, mlmc_maxent_info *info);

@@ -116,7 +116,9 @@ __global__ __launch_bounds__(256) void k_me_hessian(const double *__restrict__ P
             const int k = r * 64 + lane;
             const double v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
             const int row = 16 * ti + (lane >> 4) + 4 * r, col = 16 * tj + (lane & 15);
-            if (row < R1 && col < R1) {
+            // a diagonal tile holds both (row, col) and (col, row), rounded differently (a carries rho w, b does not): only
+            // its upper half is stored and mirrored, so that H is symmetric bit for bit and no entry is written twice
+            if (row < R1 && col < R1 && (ti != tj || row <= col)) {
                 H[(int64_t)row * R1 + col] = v;
                 H[(int64_t)col * R1 + row] = v;
             }
@@ -376,6 +378,7 @@ __global__ __launch_bounds__(COOP_THREADS) void k_me_coop(CoopArgs A) {
     // (the usual case near the solution) they ARE the next iterate's integral / gradient / Hessian, so an accepted
     // step costs no line-search round trip at all; otherwise the step lengths 1/2, 1/4, ... are tried four per barrier.
     bool spec = false;
+    bool give_up = false;       // the line search failed at the largest shift: leave after the next phase C (at lam)
     double alpha_try = 1.0, pen_ed0 = 0.0, pen_ed1 = 0.0, pen_fun_h = 0.0;     // penalised: step length of the trial point
     int ls_count = 0;
     for (int it = 0; it <= A.max_it && ok;) {
@@ -461,7 +464,9 @@ __global__ __launch_bounds__(COOP_THREADS) void k_me_coop(CoopArgs A) {
                 if (++ls_count < 40) continue;                               // the next round evaluates the shorter step
                 spec = false;
                 tau = (tau == 0.0) ? 1e-8 * (1.0 + fabs(F)) : tau * 100.0;
-                if (tau > 1e20) break;
+                // giving up: A.tot holds the sums of the rejected trial point -- one more round at lam, so that every output,
+                // the Hessian included, belongs to the returned multipliers; phase C then leaves the loop
+                if (tau > 1e20) give_up = true;
                 continue;                                                   // re-evaluate at lam with the larger shift
             }
             for (int i = tid; i < R1; i += COOP_THREADS) lam[i] = trial[i];
@@ -505,7 +510,9 @@ __global__ __launch_bounds__(COOP_THREADS) void k_me_coop(CoopArgs A) {
             }
             if (!accepted) {
                 tau = (tau == 0.0) ? 1e-8 * (1.0 + fabs(F)) : tau * 100.0;
-                if (tau > 1e20) break;
+                // giving up: A.tot holds the sums of the rejected trial point -- one more round at lam, so that every output,
+                // the Hessian included, belongs to the returned multipliers; phase C then leaves the loop
+                if (tau > 1e20) give_up = true;
                 continue;                                                   // re-evaluate at lam with the larger shift
             }
             __syncthreads();
@@ -639,7 +646,7 @@ __global__ __launch_bounds__(COOP_THREADS) void k_me_coop(CoopArgs A) {
         const bool not_spd = red[2] != 0.0;
         if (!(gnorm == gnorm) || !(F == F)) break;
         if (gnorm < A.tol) { success = 1; break; }
-        if (it == A.max_it) break;
+        if (it == A.max_it || give_up) break;
         ++it;
         if (not_spd || !(gp < 0.0)) {
             tau = (tau == 0.0) ? 1e-10 * (1.0 + fabs(F)) : tau * 100.0;

@@ -277,6 +277,7 @@ __global__ __launch_bounds__(MEB_THREADS) void k_meb_solve(MebArgs A) {
     int nit = 0, success = 0;
     double tau = 0.0, F = 0.0, gnorm = 0.0, moment0 = 0.0, gp = 0.0;
     bool spec = false;          // this round's full pass is at lam + pdir (the full Newton step), as in k_me_coop
+    bool give_up = false;       // the line search failed at the largest shift: leave after the next phase C (at lam)
     for (int it = 0; it <= A.max_it;) {
         pass_full(spec ? 1.0 : 0.0);
         if (spec) {
@@ -299,7 +300,9 @@ __global__ __launch_bounds__(MEB_THREADS) void k_meb_solve(MebArgs A) {
             }
             if (!accepted) {
                 tau = (tau == 0.0) ? 1e-8 * (1.0 + fabs(F)) : tau * 100.0;
-                if (tau > 1e20) break;
+                // giving up: the sums (hacc, gsum) are those of the rejected trial point -- one more round at lam, so that
+                // every output, the Hessian included, belongs to the returned multipliers; phase C then leaves the loop
+                if (tau > 1e20) give_up = true;
                 continue;                                                   // re-evaluate at lam with the larger shift
             }
             __syncthreads();
@@ -404,7 +407,7 @@ __global__ __launch_bounds__(MEB_THREADS) void k_meb_solve(MebArgs A) {
         const bool not_spd = red[2] != 0.0;
         if (!(gnorm == gnorm) || !(F == F)) break;
         if (gnorm < A.tol) { success = 1; break; }
-        if (it == A.max_it) break;
+        if (it == A.max_it || give_up) break;
         ++it;
         if (not_spd || !(gp < 0.0)) {
             tau = (tau == 0.0) ? 1e-10 * (1.0 + fabs(F)) : tau * 100.0;

@@ -195,9 +195,12 @@ def test_batch_larger_than_the_cu_count(hip):
     assert max(r.fun_norm for r in results) < tol
     # the moments of the solution (multipliers before the normalisation fix, result.x) are the prescribed ones: the density
     # evaluated independently of the device kernels under test, exp(clip(-phi . lambda / sigma)) in NumPy on the quadrature
+    # ... and of its basis kernel: phi from the plain-NumPy recurrence of tests/maxent_exact.py
+    from tests import maxent_exact as mx
+    phi_host = mx.basis(mx.Desc(mx.LEGENDRE, R, dom), pts, R, np.float64)[0]
     for m, r in zip(moms, results):
-        dv = np.exp(np.clip(-(phi @ r.x), -200, 200))
-        got = (dv * w) @ phi
+        dv = np.exp(np.clip(-(phi_host @ r.x), -200, 200))
+        got = (dv * w) @ phi_host
         assert np.max(np.abs(got - m)) < 50 * tol + 1e-7, np.max(np.abs(got - m))
 
 
