@@ -35,7 +35,9 @@ extern "C" {
                               * 7: mlmc_maxent_solve_batch, mlmc_density_eval_batch, mlmc_accum_estimate_multi;
                               * 8: mlmc_xcov_create, mlmc_xcov_set_shift; added within 8 (backwards compatible):
                               *    mlmc_percentiles_rows, mlmc_bootstrap_weights, mlmc_bootstrap_create / _destroy / _reset / _accum /
-                              *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var */
+                              *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var, mlmc_density_integrate_batch,
+                              *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
+                              *    mlmc_density_quantiles_kernel_time */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -270,6 +272,34 @@ int mlmc_maxent_solve_batch(int32_t B, const mlmc_basis *const *bases, const int
  * after another (problem i: n[i] points at offset n[0] + ... + n[i - 1]).  Each value is bit for bit mlmc_density_eval's. */
 int mlmc_density_eval_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
                             const double *x, const int64_t *n, double *out);
+/* mlmc_density_integrate of B problems in one launch: lambda / sigma [B][R1max]; lo / hi / out host arrays holding the problems'
+ * intervals one after another (problem i: n[i] intervals).  Each value is bit for bit mlmc_density_integrate's.  Argument errors
+ * name the problem index; B = 0 and n[i] = 0 are no-ops. */
+int mlmc_density_integrate_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *lo, const double *hi, const int64_t *n, int32_t degree,
+                                 double *out);
+/* CDF on the solver's rule, and its inverse, of B problems in one call.  For problem i with domain [a[i], b[i]] and the rule
+ * (n_intervals, gauss_degree; 0 = the solver's defaults 64 and 21) let e_j = a + j h (fp64, h = (b - a) / n_intervals, e_n = b)
+ * be the cell edges, C_j the gauss_degree-point Gauss-Legendre integral of the density over cell j (the arithmetic of
+ * mlmc_density_integrate), P_0 = 0, P_{j+1} = P_j + C_j in cell order and T = P_n the mass.  Then
+ *     Fhat(x) = (P_j + I(e_j, x)) / T for x in cell j (I: the same rule on the partial cell), 0 for x <= a, 1 for x >= b, NaN for NaN,
+ * is what mlmc_density_cdf_batch evaluates at x, and mlmc_density_quantiles_batch returns Q(p) = the x in [a, b] with
+ * Fhat(x) = p: Q(0) = a and Q(1) = b exactly, NaN for p outside [0, 1] or NaN.  Layout as mlmc_density_eval_batch: lambda / sigma
+ * [B][R1max], the problems' points one after another with counts n[i] (host, int64); a, b [B] host; mass_out [B] host (may be
+ * NULL) receives T; mem_kind (MLMC_HOST / MLMC_DEVICE) applies to x / p and out.  One thread owns one point and every sum has
+ * a fixed order: a value does not depend on the batch, on the problem's position in it or on the other points.  Argument errors
+ * of one problem name its index (null basis, R1 out of range, a >= b or non-finite, n < 0, unsupported basis kind = IDENTITY);
+ * errors of the call as a whole name none (a null array, B < 0, gauss_degree outside 0..64, n_intervals < 0, bad mem_kind); B = 0 and n[i] = 0 are no-ops; a problem whose mass is not finite and positive gives NaN for
+ * all its points and is no error. */
+int mlmc_density_cdf_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                           const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *x,
+                           const int64_t *n, double *out, double *mass_out, int mem_kind);
+int mlmc_density_quantiles_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                 const double *p, const int64_t *n, double *out, double *mass_out, int mem_kind);
+/* HIP-event time (ms) and number of the point kernels (quantile and CDF kernels, without the table kernels and copies) that
+ * mlmc_density_cdf_batch / mlmc_density_quantiles_batch have launched since the last call of this function; resets both. */
+int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

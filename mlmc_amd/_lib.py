@@ -85,6 +85,12 @@ SIGNATURES = {
                                                 _vp, _vp]),
     "mlmc_maxent_solve_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaxentOpts), _vp, _vp, _vp, _vp]),
     "mlmc_density_eval_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mlmc_density_integrate_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
+    "mlmc_density_cdf_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp,
+                                         C.c_int]),
+    "mlmc_density_quantiles_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp,
+                                               C.c_int]),
+    "mlmc_density_quantiles_kernel_time": (C.c_int, [_dp, _ip]),
     "mlmc_expr_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "mlmc_expr_destroy": (None, [_vp]),
     "mlmc_expr_eval": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _ip]),

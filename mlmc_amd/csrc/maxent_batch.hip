@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "device_basis.hpp"
+#include "maxent_batch.hpp"
 
 namespace mlmc {
 
@@ -485,52 +486,10 @@ __global__ __launch_bounds__(256) void k_meb_density(const MebDensity *__restric
     }
 }
 
-// grow-only device workspace and pinned staging buffer of the batched entry points (calls are serialised by the API lock)
-struct MebWorkspace {
-    char *dev = nullptr;
-    size_t dev_cap = 0;
-    char *host = nullptr;
-    size_t host_cap = 0;
-    int reserve(size_t dev_bytes, size_t host_bytes) {
-        hipStream_t st = rt().stream;
-        if (dev_bytes > dev_cap) {
-            MLMC_HIP_CHECK(wait_stream(st));
-            if (dev) (void)hipFree(dev);
-            dev = nullptr;
-            dev_cap = 0;
-            MLMC_HIP_CHECK(hipMalloc((void **)&dev, dev_bytes));
-            dev_cap = dev_bytes;
-        }
-        if (host_bytes > host_cap) {
-            MLMC_HIP_CHECK(wait_stream(st));
-            if (host) (void)hipHostFree(host);
-            host = nullptr;
-            host_cap = 0;
-            MLMC_HIP_CHECK(hipHostMalloc((void **)&host, host_bytes, hipHostMallocDefault));
-            host_cap = host_bytes;
-        }
-        return 0;
-    }
-    // a large device workspace (Phi of a big batch: B Q R1 doubles) is not kept beyond the call that needed it
-    void trim(size_t keep_bytes) {
-        if (dev_cap > keep_bytes) {
-            (void)wait_stream(rt().stream);
-            (void)hipFree(dev);
-            dev = nullptr;
-            dev_cap = 0;
-        }
-    }
-};
-constexpr size_t MEB_KEEP_BYTES = (size_t)256 << 20;
-static MebWorkspace &meb_ws() {
+// the workspace shared by the batched entry points (MebWorkspace: maxent_batch.hpp)
+MebWorkspace &meb_ws() {
     static MebWorkspace ws;
     return ws;
-}
-
-static size_t meb_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-static int meb_fail(const char *fn, int i, const std::string &what) {
-    return fail(std::string(fn) + ": problem " + std::to_string(i) + ": " + what);
 }
 
 }  // namespace mlmc

@@ -1,0 +1,439 @@
+// Batched CDFs and quantiles of the max-entropy densities on the device (gfx950).
+//
+// For a problem (basis, R1, lambda, sigma, [a, b]) and a rule (n_intervals, gauss_degree) the function that is tabulated
+// and inverted is
+//     Fhat(x) = (P_j + I(e_j, x)) / T,   x in cell j = [e_j, e_{j+1}],   e_j = a + j h, h = (b - a) / n_intervals, e_n = b,
+// with C_j = the gauss_degree-point Gauss-Legendre integral of the density over cell j (k_density_integrate's arithmetic,
+// maxent.hip), P_0 = 0, P_{j+1} = P_j + C_j summed in cell order, T = P_n, and I the same rule on the partial cell.
+//
+//   k_q_cells     : C_j of every problem, one thread per (problem, cell), into the table row [n_intervals + 1] of the problem
+//   k_q_prefix    : the in-order prefix P and the mass T, one thread per problem
+//   k_q_quantile  : one thread per (problem, p): binary search of p T in P, linear interpolate in the cell, then a bracketed
+//                   Newton iteration on g(x) = P_j + I(e_j, x) - p T with g' = density(x); bisection whenever the step leaves
+//                   the bracket or is not finite
+//   k_q_cdf       : Fhat at arbitrary values, one thread per value (cell lookup + one partial-cell rule)
+//   k_q_integrate : k_density_integrate for B problems in one launch, each value bit for bit the single entry's
+// One thread owns one point from start to end, every sum has a fixed order and every loop a constant bound: a result does not
+// depend on the batch, on the position of the problem in it or on the other points.  No atomics, no data-dependent launch.
+// A thread finds its problem by a binary search of its point index in the problems' offsets, so that the same launch geometry
+// serves thousands of problems with a few points each and a few problems with 10^7 points each.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "device_basis.hpp"
+#include "maxent_batch.hpp"
+
+namespace mlmc {
+
+constexpr int Q_THREADS = 256;
+constexpr int Q_MAX_IT = 64;                           // iteration cap of the bracketed Newton iteration
+constexpr int Q_MAX_INTERVALS = 1 << 20;
+constexpr size_t Q_TABLE_BYTES = (size_t)64 << 20;     // bound of the prefix tables; more problems are processed in groups
+
+struct QProb {
+    BasisParams bp;
+    int n_coef;
+    int64_t c_off;       // effective coefficients: coef + c_off, [n_coef]
+    int64_t x_off, n;    // the problem's points: [x_off, x_off + n) of the call's point arrays
+    double a, b;         // domain
+};
+
+// density(x) = exp(clip(-sum_r c_r Q_r(x), +-200)): the arithmetic of k_density
+template <int KIND>
+__device__ __forceinline__ double q_density(const BasisParams &bp, const double *__restrict__ c, int R, double x) {
+    bool keep;
+    const double t = transform_value(bp, x, keep);
+    TermGen<KIND> g;
+    g.init(keep ? t : 0.0, 1.0, bp);
+    double power = 0.0;
+    for (int r = 0; r < R; ++r) power = __builtin_fma(g.next(r), c[r], power);
+    power = fmin(fmax(-power, -200.0), 200.0);
+    return keep ? exp(power) : __builtin_nan("");
+}
+
+// integral of the density over [a, b] with a `deg`-point Gauss-Legendre rule: the arithmetic of k_density_integrate
+template <int KIND>
+__device__ __forceinline__ double q_integral(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b,
+                                             const double *__restrict__ nodes, const double *__restrict__ wts, int deg) {
+    const double half = 0.5 * (b - a), mid = 0.5 * (b + a);
+    double acc = 0.0;
+    for (int k = 0; k < deg; ++k) acc = __builtin_fma(wts[k], q_density<KIND>(bp, c, R, __builtin_fma(half, nodes[k], mid)), acc);
+    return acc * half;
+}
+
+__device__ __forceinline__ double q_integral_any(const QProb &P, const double *__restrict__ c, double a, double b,
+                                                 const double *__restrict__ nodes, const double *__restrict__ wts, int deg) {
+    switch (P.bp.kind) {
+        case MLMC_LEGENDRE: return q_integral<MLMC_LEGENDRE>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
+        case MLMC_MONOMIAL: return q_integral<MLMC_MONOMIAL>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
+        case MLMC_FOURIER: return q_integral<MLMC_FOURIER>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
+        default: return q_integral<MLMC_SPLINE>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
+    }
+}
+
+// cell edge j of the composite rule as an fp64 number: a + j h (two roundings, the file is compiled without contraction)
+__device__ __forceinline__ double q_edge(const QProb &P, double h, int nint, int j) {
+    return j >= nint ? P.b : P.a + (double)j * h;
+}
+
+// distance from |x| to the next larger double
+__device__ __forceinline__ double q_spacing(double x) {
+    const double ax = fabs(x);
+    return __longlong_as_double(__double_as_longlong(ax) + 1) - ax;
+}
+
+// the problem of point `idx`: the largest k with probs[k].x_off <= idx (problems without points share their successor's offset)
+__device__ __forceinline__ int q_find(const QProb *__restrict__ probs, int nprob, int64_t idx) {
+    int lo = 0, hi = nprob;
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (probs[mid].x_off <= idx) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(128) void k_q_cells(const QProb *__restrict__ probs, int nprob, int nint, const double *__restrict__ coef,
+                                                 const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                 double *__restrict__ tab) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)nprob * nint) return;
+    const int k = (int)(gid / nint), j = (int)(gid - (int64_t)k * nint);
+    const QProb P = probs[k];
+    const double h = (P.b - P.a) / (double)nint;
+    tab[(int64_t)k * (nint + 1) + j + 1] = q_integral_any(P, coef + P.c_off, q_edge(P, h, nint, j), q_edge(P, h, nint, j + 1), nodes, wts, deg);
+}
+
+__global__ __launch_bounds__(64) void k_q_prefix(int nprob, int nint, double *__restrict__ tab, double *__restrict__ mass) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nprob) return;
+    double *row = tab + (int64_t)k * (nint + 1);
+    double run = 0.0;
+    row[0] = 0.0;
+    for (int j = 0; j < nint; ++j) {
+        run += row[j + 1];
+        row[j + 1] = run;
+    }
+    mass[k] = run;
+}
+
+template <int KIND>
+__device__ double q_invert(const QProb &P, const double *__restrict__ c, const double *__restrict__ row, int nint,
+                           const double *__restrict__ nodes, const double *__restrict__ wts, int deg, double p) {
+    const double T = row[nint];
+    if (!(T > 0.0) || !(T < __builtin_inf())) return __builtin_nan("");
+    if (!(p >= 0.0 && p <= 1.0)) return __builtin_nan("");
+    if (p == 0.0) return P.a;
+    if (p == 1.0) return P.b;
+    const double target = p * T;
+    int lo = 0, hi = nint;                  // the largest j < n with P_j <= target
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] <= target) lo = mid; else hi = mid;
+    }
+    const int j = lo;
+    const double h = (P.b - P.a) / (double)nint;
+    const double ej = q_edge(P, h, nint, j), Pj = row[j];
+    double xl = ej, gl = Pj - target;                                  // g(xl) <= 0 <= g(xh)
+    double xh = q_edge(P, h, nint, j + 1), gh = row[j + 1] - target;
+    double x = xl + (xh - xl) * (-gl / (gh - gl));                     // linear interpolate inside the cell
+    if (!(x >= xl && x <= xh)) x = 0.5 * (xl + xh);
+    const double gstop = 0x1p-52 * target;                             // g is a difference of two sums near `target`: it is 0 or at least
+                                                                       // about one spacing of them, nothing in between can be resolved
+    for (int it = 0; it < Q_MAX_IT; ++it) {
+        const double gx = (Pj + q_integral<KIND>(P.bp, c, P.n_coef, ej, x, nodes, wts, deg)) - target;
+        if (gx <= 0.0) { xl = x; gl = gx; } else { xh = x; gh = gx; }
+        if (fabs(gx) <= gstop) break;
+        double xn = x - gx / q_density<KIND>(P.bp, c, P.n_coef, x);
+        if (!(xn > xl && xn < xh)) xn = 0.5 * (xl + xh);                // the step left the bracket or is not finite: bisection
+        if (fabs(xn - x) <= q_spacing(x)) break;
+        x = xn;
+    }
+    return fabs(gl) <= fabs(gh) ? xl : xh;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_quantile(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                          const double *__restrict__ coef, const double *__restrict__ tab,
+                                                          const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                          const double *__restrict__ p, double *__restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off, *row = tab + (int64_t)k * (nint + 1);
+    const double pv = p[idx];
+    double q;
+    switch (P.bp.kind) {
+        case MLMC_LEGENDRE: q = q_invert<MLMC_LEGENDRE>(P, c, row, nint, nodes, wts, deg, pv); break;
+        case MLMC_MONOMIAL: q = q_invert<MLMC_MONOMIAL>(P, c, row, nint, nodes, wts, deg, pv); break;
+        case MLMC_FOURIER: q = q_invert<MLMC_FOURIER>(P, c, row, nint, nodes, wts, deg, pv); break;
+        default: q = q_invert<MLMC_SPLINE>(P, c, row, nint, nodes, wts, deg, pv); break;
+    }
+    out[idx] = q;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_cdf(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                     const double *__restrict__ coef, const double *__restrict__ tab,
+                                                     const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                     const double *__restrict__ x, double *__restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *row = tab + (int64_t)k * (nint + 1);
+    const double T = row[nint], v = x[idx];
+    double f;
+    if (!(T > 0.0) || !(T < __builtin_inf()) || v != v) {
+        f = __builtin_nan("");
+    } else if (v <= P.a) {
+        f = 0.0;
+    } else if (v >= P.b) {
+        f = 1.0;
+    } else {
+        const double h = (P.b - P.a) / (double)nint;
+        int lo = 0, hi = nint;              // the largest j < n with e_j <= v
+        for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+            const int mid = (lo + hi) >> 1;
+            if (q_edge(P, h, nint, mid) <= v) lo = mid; else hi = mid;
+        }
+        f = (row[lo] + q_integral_any(P, coef + P.c_off, q_edge(P, h, nint, lo), v, nodes, wts, deg)) / T;
+    }
+    out[idx] = f;
+}
+
+__global__ __launch_bounds__(128) void k_q_integrate(const QProb *__restrict__ probs, int nprob, int64_t npts,
+                                                     const double *__restrict__ coef, const double *__restrict__ lo,
+                                                     const double *__restrict__ hi, const double *__restrict__ nodes,
+                                                     const double *__restrict__ wts, int deg, double *__restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npts) return;
+    const QProb P = probs[q_find(probs, nprob, idx)];
+    out[idx] = q_integral_any(P, coef + P.c_off, lo[idx], hi[idx], nodes, wts, deg);
+}
+
+// HIP-event time of the point kernels (k_q_quantile / k_q_cdf), for mlmc_density_quantiles_kernel_time: one event pair per group of
+// a call, read after the call's own wait
+struct QTiming {
+    std::vector<hipEvent_t> ev;
+    double ms = 0.0;
+    int64_t launches = 0;
+    // best effort: the timing never fails a call (false: this launch is not timed)
+    bool pair(size_t k, hipEvent_t &a, hipEvent_t &b) {
+        while (ev.size() < 2 * (k + 1)) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return false;
+            ev.push_back(e);
+        }
+        a = ev[2 * k];
+        b = ev[2 * k + 1];
+        return true;
+    }
+};
+static QTiming &q_timing() {
+    static QTiming t;
+    return t;
+}
+
+// validated problems of a call: table, effective coefficients (the same as mlmc_density_eval's), point offsets
+struct QSetup {
+    std::vector<QProb> probs;
+    std::vector<double> coef;
+    int64_t n_tot = 0;
+};
+
+static int q_prepare(const char *fn, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                     const double *sigma, const double *a, const double *b, const int64_t *n, QSetup &S) {
+    int ldv = 0;
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *bs = bases[i];
+        if (!bs) return meb_fail(fn, i, "null basis");
+        const int max_out = bs->out_size > 0 ? bs->out_size : bs->p.size;
+        if (R1[i] <= 0 || R1[i] > max_out) return meb_fail(fn, i, "R1 out of range");
+        if (bs->p.kind != MLMC_LEGENDRE && bs->p.kind != MLMC_MONOMIAL && bs->p.kind != MLMC_FOURIER && bs->p.kind != MLMC_SPLINE)
+            return meb_fail(fn, i, "unsupported basis kind");
+        if (n[i] < 0) return meb_fail(fn, i, "n < 0");
+        if (a && !(std::isfinite(a[i]) && std::isfinite(b[i]) && a[i] < b[i]))
+            return meb_fail(fn, i, "the domain must be finite with a < b");
+        ldv = std::max(ldv, (int)R1[i]);
+    }
+    S.probs.resize(B);
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *bs = bases[i];
+        const std::vector<double> c = effective_coeffs(bs, lambda + (size_t)i * ldv, sigma + (size_t)i * ldv, R1[i]);
+        const int Reff = bs->out_size > 0 ? bs->p.size : R1[i];
+        QProb &p = S.probs[i];
+        p.bp = bs->p;
+        p.n_coef = Reff;
+        p.c_off = (int64_t)S.coef.size();
+        p.x_off = S.n_tot;
+        p.n = n[i];
+        p.a = a ? a[i] : 0.0;
+        p.b = a ? b[i] : 0.0;
+        S.coef.insert(S.coef.end(), c.begin(), c.begin() + Reff);
+        S.n_tot += n[i];
+    }
+    return 0;
+}
+
+// mlmc_density_cdf_batch (inverse == false) and mlmc_density_quantiles_batch (inverse == true)
+static int q_on_rule(const char *fn, bool inverse, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                     const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b || !n) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    QSetup S;
+    if (q_prepare(fn, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
+    if (S.n_tot > 0 && (!x || !out)) return fail(std::string(fn) + ": null argument");
+    if (S.n_tot == 0 && !mass_out) return 0;
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    hipStream_t st = rt().stream;
+    std::vector<double> gx, gw;
+    gauss_legendre(deg, gx, gw);
+    const bool stage = mem_kind == MLMC_HOST && S.n_tot > 0;
+    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
+    const size_t b_probs = meb_align(sizeof(QProb) * B), b_coef = meb_align(sizeof(double) * S.coef.size());
+    const size_t b_g = meb_align(sizeof(double) * deg), b_in = b_probs + b_coef + 2 * b_g;
+    const size_t b_mass = meb_align(sizeof(double) * B), b_tab = meb_align(sizeof(double) * (size_t)G * ((size_t)nint + 1));
+    const size_t b_x = stage ? meb_align(sizeof(double) * (size_t)S.n_tot) : 0;
+    MebWorkspace &ws = meb_ws();
+    if (ws.reserve(b_in + b_mass + b_tab + 2 * b_x, b_in + b_mass + b_x)) return 1;
+    char *h = ws.host, *d = ws.dev;
+    std::memcpy(h, S.probs.data(), sizeof(QProb) * B);
+    std::memcpy(h + b_probs, S.coef.data(), sizeof(double) * S.coef.size());
+    std::memcpy(h + b_probs + b_coef, gx.data(), sizeof(double) * deg);
+    std::memcpy(h + b_probs + b_coef + b_g, gw.data(), sizeof(double) * deg);
+    MLMC_HIP_CHECK(hipMemcpyAsync(d, h, b_in, hipMemcpyHostToDevice, st));
+    const QProb *d_probs = (const QProb *)d;
+    const double *d_coef = (const double *)(d + b_probs);
+    const double *d_gx = (const double *)(d + b_probs + b_coef), *d_gw = (const double *)(d + b_probs + b_coef + b_g);
+    double *d_mass = (double *)(d + b_in), *d_tab = (double *)(d + b_in + b_mass);
+    const double *d_x = x;
+    double *d_out = out;
+    if (stage) {
+        std::memcpy(h + b_in + b_mass, x, sizeof(double) * (size_t)S.n_tot);
+        MLMC_HIP_CHECK(hipMemcpyAsync(d + b_in + b_mass + b_tab, h + b_in + b_mass, sizeof(double) * (size_t)S.n_tot, hipMemcpyHostToDevice, st));
+        d_x = (const double *)(d + b_in + b_mass + b_tab);
+        d_out = (double *)(d + b_in + b_mass + b_tab + b_x);
+    }
+    QTiming &tm = q_timing();
+    size_t timed = 0;
+    for (int g0 = 0; g0 < B; g0 += G) {
+        const int np = std::min(G, B - g0);
+        const int64_t cells = (int64_t)np * nint;
+        hipLaunchKernelGGL(k_q_cells, dim3((unsigned)((cells + 127) / 128)), dim3(128), 0, st, d_probs + g0, np, nint, d_coef, d_gx, d_gw,
+                           deg, d_tab);
+        hipLaunchKernelGGL(k_q_prefix, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st, np, nint, d_tab, d_mass + g0);
+        const int64_t pt0 = S.probs[g0].x_off;
+        const int64_t npts = (g0 + np < B ? S.probs[g0 + np].x_off : S.n_tot) - pt0;
+        if (npts > 0) {
+            const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));
+            hipEvent_t e0, e1;
+            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            if (inverse)
+                hipLaunchKernelGGL(k_q_quantile, grid, dim3(Q_THREADS), 0, st, d_probs + g0, np, nint, pt0, npts, d_coef, (const double *)d_tab,
+                                   d_gx, d_gw, deg, d_x, d_out);
+            else
+                hipLaunchKernelGGL(k_q_cdf, grid, dim3(Q_THREADS), 0, st, d_probs + g0, np, nint, pt0, npts, d_coef, (const double *)d_tab,
+                                   d_gx, d_gw, deg, d_x, d_out);
+            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+        }
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
+    if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)S.n_tot, hipMemcpyDeviceToHost, st));
+    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(h + b_in, d_mass, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    if (mass_out) std::memcpy(mass_out, h + b_in, sizeof(double) * B);
+    for (size_t k = 0; k < timed; ++k) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
+        tm.ms += ms;
+        ++tm.launches;
+    }
+    ws.trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+}  // namespace mlmc
+
+using namespace mlmc;
+
+extern "C" {
+
+int mlmc_density_integrate_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *lo, const double *hi, const int64_t *n, int32_t degree,
+                                 double *out) {
+    MLMC_API_GUARD;
+    static const char *fn = "mlmc_density_integrate_batch";
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail("mlmc_density_integrate_batch: B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !n) return fail("mlmc_density_integrate_batch: null argument");
+    if (degree <= 0 || degree > 64) return fail("mlmc_density_integrate_batch: degree must be in 1..64");
+    QSetup S;
+    if (q_prepare(fn, B, bases, R1, lambda, sigma, nullptr, nullptr, n, S)) return 1;
+    if (S.n_tot == 0) return 0;
+    if (!lo || !hi || !out) return fail("mlmc_density_integrate_batch: null argument");
+    hipStream_t st = rt().stream;
+    std::vector<double> gx, gw;
+    gauss_legendre(degree, gx, gw);
+    const size_t b_probs = meb_align(sizeof(QProb) * B), b_coef = meb_align(sizeof(double) * S.coef.size());
+    const size_t b_g = meb_align(sizeof(double) * degree), b_x = meb_align(sizeof(double) * (size_t)S.n_tot);
+    const size_t b_in = b_probs + b_coef + 2 * b_g + 2 * b_x;
+    MebWorkspace &ws = meb_ws();
+    if (ws.reserve(b_in + b_x, b_in)) return 1;
+    char *h = ws.host, *d = ws.dev;
+    std::memcpy(h, S.probs.data(), sizeof(QProb) * B);
+    std::memcpy(h + b_probs, S.coef.data(), sizeof(double) * S.coef.size());
+    std::memcpy(h + b_probs + b_coef, gx.data(), sizeof(double) * degree);
+    std::memcpy(h + b_probs + b_coef + b_g, gw.data(), sizeof(double) * degree);
+    std::memcpy(h + b_probs + b_coef + 2 * b_g, lo, sizeof(double) * (size_t)S.n_tot);
+    std::memcpy(h + b_probs + b_coef + 2 * b_g + b_x, hi, sizeof(double) * (size_t)S.n_tot);
+    MLMC_HIP_CHECK(hipMemcpyAsync(d, h, b_in, hipMemcpyHostToDevice, st));
+    double *d_out = (double *)(d + b_in);
+    hipLaunchKernelGGL(k_q_integrate, dim3((unsigned)((S.n_tot + 127) / 128)), dim3(128), 0, st, (const QProb *)d, (int)B, S.n_tot,
+                       (const double *)(d + b_probs), (const double *)(d + b_probs + b_coef + 2 * b_g),
+                       (const double *)(d + b_probs + b_coef + 2 * b_g + b_x), (const double *)(d + b_probs + b_coef),
+                       (const double *)(d + b_probs + b_coef + b_g), (int)degree, d_out);
+    MLMC_HIP_CHECK(hipGetLastError());
+    MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)S.n_tot, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    ws.trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+int mlmc_density_cdf_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                           const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *x,
+                           const int64_t *n, double *out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_cdf_batch", false, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, x, n, out, mass_out,
+                     mem_kind);
+}
+
+int mlmc_density_quantiles_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                 const double *p, const int64_t *n, double *out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_quantiles_batch", true, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, out,
+                     mass_out, mem_kind);
+}
+
+int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches) {
+    MLMC_API_GUARD;
+    QTiming &tm = q_timing();
+    if (ms) *ms = tm.ms;
+    if (launches) *launches = tm.launches;
+    tm.ms = 0.0;
+    tm.launches = 0;
+    return 0;
+}
+
+}  // extern "C"

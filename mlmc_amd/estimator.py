@@ -428,6 +428,25 @@ class Estimate:
         results = simple_distribution.estimate_densities_minimize(distrs, tol, reg_param)
         return [(d, info, r, m) for d, (m, info), r in zip(distrs, ortho, results)]
 
+    def estimate_component_quantiles(self, probs, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """Quantiles of the maximum-entropy density of EVERY scalar component of the quantity, in one batched device call
+        (tool.simple_distribution.quantiles: median, 5 % / 95 % bands, credible intervals of a field).
+
+        :param probs: probabilities, the same for every component
+        :param densities: the list `construct_densities` returned; without it the method calls
+            `construct_densities(tol, reg_param, orth_moments_tol, moments_fns)` itself
+        :return: (q, success): q [M, len(probs)], row m = the quantiles of component m (the row order of construct_densities),
+            equal to `construct_density` of `scalar_component(quantity, m)` followed by `.quantile(probs)` up to what
+            construct_densities promises against the scalar chain; success [M] bool, the solver's verdict per component (rows of
+            failed solves are still returned)"""
+        from .tool import simple_distribution
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+        q = simple_distribution.quantiles([d[0] for d in densities], probs)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return np.array(q, dtype=np.float64).reshape(len(densities), probs.size), success
+
     def get_level_samples(self, level_id, n_samples=None):
         chunk_spec = next(self._sample_storage.chunks(level_id=level_id, n_samples=n_samples))
         return self._quantity.samples(chunk_spec=chunk_spec)

@@ -8,7 +8,7 @@ import numpy as np
 import scipy.integrate as integrate
 from scipy.optimize import OptimizeResult
 
-from .simple_distribution import _cdf, _device_density, _solve_on_device
+from .simple_distribution import _cdf, _device_density, _quantile, _solve_on_device
 
 
 class Distribution:
@@ -132,6 +132,11 @@ class Distribution:
 
     def cdf(self, values):
         return _cdf(self, values)
+
+    def quantile(self, p):
+        """Q(p) of the stored multipliers on this distribution's quadrature (simple_distribution.quantiles with one
+        distribution; p may be a float64 torch device tensor)."""
+        return _quantile(self, p)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

@@ -131,6 +131,152 @@ def densities(distrs, values):
     return [p.reshape(v.shape) for p, v in zip(parts, shaped)]
 
 
+def _per_distribution(values, B):
+    """one entry per distribution from `values`: one 1-D array / scalar / flat sequence for all, or a sequence of B arrays.  An array
+    of more than one dimension is ambiguous ([B, n] rows per distribution, or one block for all?) and raises: pass list(array) for
+    rows, array.ravel() for one block."""
+    if (isinstance(values, np.ndarray) or hasattr(values, "data_ptr")) and values.ndim > 1:
+        raise ValueError("an array of {} dimensions is ambiguous: pass a list with one array per distribution, or one 1-D "
+                         "array for all".format(values.ndim))
+    if isinstance(values, np.ndarray) or hasattr(values, "data_ptr") or np.isscalar(values) \
+            or (len(values) > 0 and np.isscalar(values[0])):
+        return [values] * B
+    if len(values) != B:
+        raise ValueError("{} arrays for {} distributions".format(len(values), B))
+    return list(values)
+
+
+def _batch_problem_args(distrs):
+    """(handles, r1, lam, sig) of a list of distributions in the layout of the batched density entry points"""
+    B = len(distrs)
+    r1 = np.array([len(d.multipliers) for d in distrs], dtype=np.int32)
+    ldv = int(r1.max())
+    lam = np.zeros((B, ldv))
+    sig = np.ones((B, ldv))
+    for b, d in enumerate(distrs):
+        lam[b, :r1[b]] = d.multipliers
+        sig[b, :r1[b]] = d._moment_errs[:r1[b]]
+    handles = (C.c_void_p * B)(*[d.moments_fn._basis_handle().value for d in distrs])
+    return handles, r1, lam, sig
+
+
+def cdfs(distrs, values):
+    """cdf() of many distributions through ONE device call (mlmc_density_integrate_batch).
+    values: one array of points for all or a sequence with one array per distribution, as in `densities`.
+    :return: list of arrays, entry b = distrs[b].cdf(values[b]) bit for bit: the cumulative 10-point pieces between successive
+        in-domain values, prefix-summed on the host in the order of `_cdf` (values outside the domain and unsorted values behave
+        as there; like cdf() it takes no NaN values -- `cdfs_on_rule` does)"""
+    B = len(distrs)
+    if B == 0:
+        return []
+    vals = [np.atleast_1d(v) for v in _per_distribution(values, B)]
+    lo, hi = [], []
+    n = np.zeros(B, dtype=np.int64)
+    for b, (d, v) in enumerate(zip(distrs, vals)):
+        last_x = d.domain[0]
+        for val in v:
+            if d.domain[0] < val < d.domain[1]:
+                lo.append(last_x)
+                hi.append(val)
+                last_x = val
+                n[b] += 1
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    pieces = np.empty_like(lo)
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    _lib.check(_lib.lib().mlmc_density_integrate_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig),
+                                                       _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(n), 10, _lib.ptr(pieces)))
+    out, k = [], 0
+    for d, v in zip(distrs, vals):
+        cdf_y = np.empty(len(v))
+        last_y = 0
+        for i, val in enumerate(v):
+            if val <= d.domain[0]:
+                last_y = 0
+            elif val >= d.domain[1]:
+                last_y = 1
+            else:
+                last_y = last_y + pieces[k]
+                k += 1
+            cdf_y[i] = last_y
+        out.append(cdf_y)
+    return out
+
+
+def _on_rule(distrs, points, inverse, what):
+    """mlmc_density_quantiles_batch (inverse) / mlmc_density_cdf_batch of a list of distributions in ONE call.
+    points: per distribution a NumPy-convertible array, or torch device tensors for all of them (float64; the results are
+    device tensors then and nothing is copied to the host).
+    :return: (list of arrays shaped like the points, masses [B])"""
+    B = len(distrs)
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    on_device = [hasattr(p, "data_ptr") and p.is_cuda for p in points]
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    mass = np.empty(B)
+    if any(on_device):
+        import torch
+        if not all(on_device) or any(p.dtype != torch.float64 for p in points):
+            raise ValueError(what + ": device points must be float64 device tensors for every distribution")
+        shaped = list(points)
+        flat = shaped[0].contiguous().reshape(-1) if B == 1 else torch.cat([p.reshape(-1) for p in shaped])
+        out = torch.empty_like(flat)
+        n = np.array([p.numel() for p in shaped], dtype=np.int64)
+        torch.cuda.current_stream(flat.device).synchronize()         # the library reads it on its own stream
+        kind = _lib.DEVICE
+    else:
+        shaped = [np.atleast_1d(np.asarray(p, dtype=np.float64)) for p in points]
+        flat = np.ascontiguousarray(np.concatenate([p.reshape(-1) for p in shaped]))
+        out = np.empty_like(flat)
+        n = np.array([p.size for p in shaped], dtype=np.int64)
+        kind = _lib.HOST
+    fn = _lib.lib().mlmc_density_quantiles_batch if inverse else _lib.lib().mlmc_density_cdf_batch
+    _lib.check(fn(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
+                  int(n_int.pop()), int(degs.pop()), _lib.ptr(flat), _lib.ptr(n), _lib.ptr(out), _lib.ptr(mass), kind))
+    if kind == _lib.DEVICE:
+        import torch
+        parts = [out] if B == 1 else list(torch.split(out, [int(k) for k in n]))
+    else:
+        parts = np.split(out, np.cumsum(n)[:-1])
+    return [p.reshape(s.shape) for p, s in zip(parts, shaped)], mass
+
+
+def cdfs_on_rule(distrs, values):
+    """Fhat of many distributions through ONE device call (mlmc_density_cdf_batch): the normalised CDF on each distribution's
+    own quadrature (n_intervals cells of _gauss_degree points), the function that `quantiles` inverts.  With the cell edges
+    e_j, the cell integrals C_j, their in-order prefix P_j and the mass T = P_n (include/mlmc_hip.h),
+        Fhat(x) = (P_j + I(e_j, x)) / T for x in cell j, 0 for x <= a, 1 for x >= b, NaN for NaN.
+    Unlike `cdfs` every value is evaluated on its own: the result does not depend on the order of `values`, and it is
+    normalised by the mass of the rule (Fhat(b) = 1 exactly).
+    values: one array for all or one per distribution.  :return: list of arrays"""
+    distrs = list(distrs)
+    if not distrs:
+        return []
+    return _on_rule(distrs, _per_distribution(values, len(distrs)), False, "cdfs_on_rule")[0]
+
+
+def quantiles(distrs, probs):
+    """Quantiles of many distributions through ONE device call (mlmc_density_quantiles_batch): entry b = Q_b(probs[b]), the x in
+    the domain with Fhat_b(x) = p (`cdfs_on_rule`); Q(0) and Q(1) are the domain's end points exactly, p outside [0, 1] or NaN
+    gives NaN (SciPy's ppf convention).  A value is bit for bit the same for a distribution alone or in any batch.
+    probs: one array for all or one per distribution; every distribution uses its own n_intervals / _gauss_degree, which must
+    agree over the list (ValueError otherwise).  :return: list of arrays"""
+    distrs = list(distrs)
+    if not distrs:
+        return []
+    return _on_rule(distrs, _per_distribution(probs, len(distrs)), True, "quantiles")[0]
+
+
+def _quantile(dist, p):
+    """the B = 1 call of `quantiles`; a torch device tensor stays on the device"""
+    res = _on_rule([dist], [p], True, "quantile")[0][0]
+    return res
+
+
 def estimate_densities_minimize(distrs, tol=1e-5, reg_param=0.01):
     """SimpleDistribution.estimate_density_minimize of every distribution in `distrs`, solved in ONE batched device call
     (mlmc_maxent_solve_batch: one workgroup per problem).  Each distribution gets exactly what its own call would do:
@@ -267,6 +413,12 @@ class SimpleDistribution:
 
     def cdf(self, values):
         return _cdf(self, values)
+
+    def quantile(self, p):
+        """Q(p): the x in the domain with Fhat(x) = p on this distribution's quadrature (see `quantiles`, of which this is the
+        call with one distribution, hence bit for bit its value).  p: array-like, or a float64 torch device tensor (the result
+        is a device tensor then, e.g. for inverse-transform sampling with the caller's own uniforms)."""
+        return _quantile(self, p)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

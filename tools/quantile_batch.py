@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Batched CDFs and quantiles of max-entropy densities against what exists without them.
+
+few-points regime: M in {16, 64, 256, 1024} densities of R = 25 moments (Gaussian mixtures of varying shape, solved in one batch),
+probs = (0.05, 0.5, 0.95) and linspace(0.01, 0.99, 99):
+  quantiles_ms   simple_distribution.quantiles (one mlmc_density_quantiles_batch)
+  brentq_ms      scipy.optimize.brentq on d.cdf per (component, probability) at xtol = 4 spacing, TIMED ON A SUBSET of at most
+                 8 components x 3 probabilities AND SCALED to M x n_p
+  cdfs_ms        simple_distribution.cdfs at the quantiles (one mlmc_density_integrate_batch)
+  cdf_loop_ms    the loop [d.cdf(v) for d in distrs]
+many-points regime: B in {1, 8, 64} problems x n in {10^6, 10^7} device-resident uniforms, R1 in {9, 25, 64}:
+  kernel_ms      HIP-event time of the quantile kernel alone (mlmc_density_quantiles_kernel_time)
+  call_ms        wall time of one mlmc_density_quantiles_batch with p and out in device memory: host set-up, upload of the problem
+                 table, the two table kernels, the quantile kernel and the wait
+  steps          mean evaluations of g per point.  NOT counted on the device: counted by the plain-fp64 twin of the algorithm
+                 (tests/quantile_cases.py, same iteration and stopping rules) on 2000 of problem 0's uniforms
+  fp64_fraction  steps x gauss_degree x (2 R1 + EXP_FLOPS) x points / kernel_ms against the 78.6 TFLOP/s fp64 vector peak
+(--config B,R1,n runs one many-points configuration, e.g. under rocprofv3 --kernel-trace --stats.)
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n] [--reps K]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from scipy.optimize import brentq
+
+from mlmc_amd import _lib, Legendre
+from mlmc_amd.tool import simple_distribution as sd
+
+DOM = (-5.0, 5.0)
+PEAK_FP64 = 78.6e12
+EXP_FLOPS = 20            # fp64 operations counted for one exp (the library routine's polynomial and range reduction)
+
+
+def timed(fn, reps):
+    fn()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out = fn()
+    return (time.perf_counter() - t0) * 1e3 / reps, out
+
+
+def mixtures(M, R, seed=11):
+    """M solved SimpleDistributions of R moments: two-Gaussian mixtures of varying shape on DOM"""
+    fn = Legendre(R, DOM)
+    pts, w = sd._composite_gauss(DOM, 256, 21)
+    phi = fn.eval_all(pts)
+    rng = np.random.default_rng(seed)
+    norm = lambda x, m, s: np.exp(-0.5 * ((x - m) / s) ** 2) / (s * np.sqrt(2 * np.pi))
+    distrs = []
+    for _ in range(M):
+        m1, m2 = rng.uniform(-1.2, 1.2, size=2)
+        s1, s2 = rng.uniform(0.7, 1.3, size=2)
+        p = rng.uniform(0.2, 0.8)
+        mom = (p * norm(pts, m1, s1) + (1 - p) * norm(pts, m2, s2)) * w @ phi
+        distrs.append(sd.SimpleDistribution(fn, np.stack([mom, np.ones(R)], axis=1), domain=DOM))
+    res = sd.estimate_densities_minimize(distrs, tol=1e-8)
+    return distrs, all(r.success for r in res)
+
+
+def few_points(M, probs, reps):
+    distrs, ok = mixtures(M, 25)
+    q_ms, q = timed(lambda: sd.quantiles(distrs, probs), reps)
+    c_ms, _ = timed(lambda: sd.cdfs(distrs, q), reps)
+    loop_ms, _ = timed(lambda: [d.cdf(v) for d, v in zip(distrs, q)], 1)
+    sub_d, sub_p = distrs[:8], probs[np.linspace(0, len(probs) - 1, 3).astype(int)]
+    t0 = time.perf_counter()
+    worst = 0.0
+    for d, qd in zip(sub_d, q):
+        for p in sub_p:
+            x = brentq(lambda v: d.cdf(v)[0] - p, DOM[0], DOM[1], xtol=4 * np.spacing(DOM[1]))
+            worst = max(worst, abs(x - qd[np.argmin(np.abs(probs - p))]))
+    sub_ms = (time.perf_counter() - t0) * 1e3
+    brent_ms = sub_ms / (len(sub_d) * len(sub_p)) * M * len(probs)
+    return dict(M=M, n_p=len(probs), quantiles_ms=round(q_ms, 3), brentq_ms_scaled=round(brent_ms, 1),
+                brentq_subset=[len(sub_d), len(sub_p)], cdfs_ms=round(c_ms, 3), cdf_loop_ms=round(loop_ms, 3),
+                brentq_vs_quantiles_dx=float(worst), all_success=ok)
+
+
+def twin_steps(d, p):
+    """mean evaluations of g per point of the bracketed Newton iteration, counted on the fp64 twin of the kernel"""
+    from tests import maxent_exact as mx
+    from tests import maxent_cases as mc
+    from tests import quantile_cases as qc
+    desc = mx.Desc(mx.LEGENDRE, d.moments_fn.size, d.domain)
+    case = mc.Case("tool", desc, d.moment_means, d._moment_errs, d.multipliers, "tool")
+    stats = {}
+    qc.twin_quantiles(case, d.multipliers, (d.n_intervals, d._gauss_degree), p, stats)
+    return stats["evaluations"] / len(p)
+
+
+def many_points(B, R1, n, reps):
+    distrs, ok = mixtures(B, R1, seed=5)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(B * 131 + R1)
+    flat = torch.rand(B * n, dtype=torch.float64, device="cuda", generator=g)      # problem b: flat[b n : (b + 1) n]
+    out = torch.empty_like(flat)
+    torch.cuda.synchronize()
+    handles, r1, lam, sig = sd._batch_problem_args(distrs)
+    a, b = np.full(B, DOM[0]), np.full(B, DOM[1])
+    cnt = np.full(B, n, dtype=np.int64)
+    n_int, deg = distrs[0].n_intervals, distrs[0]._gauss_degree
+    lib, P = _lib.lib(), _lib.ptr
+
+    def call():
+        _lib.check(lib.mlmc_density_quantiles_batch(B, C.cast(handles, C.c_void_p), P(r1), P(lam), P(sig), P(a), P(b), n_int, deg,
+                                                    P(flat), P(cnt), P(out), None, _lib.DEVICE))
+    call()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))           # reset
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        call()
+    call_ms = (time.perf_counter() - t0) * 1e3 / reps
+    _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+    kernel_ms = k_ms.value / k_n.value
+    res = out[:n].cpu().numpy()
+    mono = bool(np.all(np.diff(res[np.argsort(flat[:n].cpu().numpy())]) >= 0))
+    steps = twin_steps(distrs[0], flat[:2000].cpu().numpy())
+    flops = steps * deg * (2 * R1 + EXP_FLOPS) * float(B) * n
+    return dict(B=B, R1=R1, n=n, kernel_ms=round(kernel_ms, 3), call_ms=round(call_ms, 3), ns_per_point=round(kernel_ms * 1e6 / (B * n), 3),
+                steps=round(steps, 2), fp64_fraction=round(flops / (kernel_ms * 1e-3) / PEAK_FP64, 4), monotone=mono, all_success=ok)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--config", help="one many-points configuration B,R1,n for a profiler run")
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    _lib.init(0)
+    out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
+    if a.config:
+        B, R1, n = (int(v) for v in a.config.split(","))
+        out["many"] = [many_points(B, R1, n, a.reps)]
+    else:
+        Ms = (16,) if a.quick else (16, 64, 256, 1024)
+        out["few"] = [few_points(M, probs, a.reps) for M in Ms for probs in (np.array([0.05, 0.5, 0.95]), np.linspace(0.01, 0.99, 99))]
+        cfgs = [(1, 25, 1_000_000)] if a.quick else [(B, R1, n) for n in (1_000_000, 10_000_000) for R1 in (9, 25, 64) for B in (1, 8, 64)]
+        out["many"] = [many_points(B, R1, n, a.reps) for B, R1, n in cfgs]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
