@@ -177,7 +177,11 @@ int mlmc_accum_aux_kernel_time(mlmc_accum *a, double *ms, int64_t *launches, int
 /* The coefficient tables of those linearisations, as the accumulators use them (host arithmetic only: needs no device, e.g.
  * for checking them against exact rational values): squares == 0: phi_i phi_j = sum_k c_ijk phi_k, K = 2 R - 1;
  * squares != 0: (phi_i phi_j)^2 = sum_k c2_ijk phi_k, K = 4 R - 3.  out [K][R * R] (k-major), out_len >= K * R * R.
- * kind: MLMC_LEGENDRE or MLMC_MONOMIAL, 1 <= R <= 128 (squares: R <= 64). */
+ * kind: MLMC_LEGENDRE or MLMC_MONOMIAL, 1 <= R <= 128 (squares: R <= 64).
+ * squares == 2 / 3 (MLMC_LEGENDRE only): the same two tables for level sums of CHEBYSHEV polynomials T_m of the transformed
+ * value, which the inner accumulators of a Legendre covariance sum where they have more than 64 terms (one FMA per term):
+ * phi_i phi_j = sum_m c'_ijm T_m, (phi_i phi_j)^2 = sum_m c2'_ijm T_m, with c'_ijm = sum_k c_ijk a_km and the exact connection
+ * P_k = sum_m a_km T_m folded in on the host in extended precision.  Same shapes and limits as 0 / 1; other values fail. */
 int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *out, int64_t out_len);
 
 /* Mean-only level sums of a quantity of M components, each with ITS OWN moment functions (Estimate.construct_densities:

@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include <algorithm>
 #include <map>
+#include <tuple>
 
 namespace mlmc {
 
@@ -124,16 +125,15 @@ static void log_keep_interval(const BasisParams &p, double *x_lo, double *x_hi) 
 //   c_ijk = (2k + 1) / (2s + 1) * A(s - i) A(s - j) A(s - k) / A(s),  2s = i + j + k,  |i - j| <= k <= i + j,  i + j + k even,
 // walked along k by ratio recurrences in extended precision (every factor is O(1), no factorial is formed) and rounded once;
 // max / min of (i, j) enter, so the table is bit for bit symmetric.  Monomials: t^i t^j = t^(i + j).
-bool product_table(int kind, int R, std::vector<double> &out) {
-    if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL) return false;
+typedef long double ld;
+// Legendre, before the single rounding: [2 R - 1][R * R]
+static void legendre_products_ld(int R, std::vector<ld> &out) {
     const int K = 2 * R - 1;
     const size_t RR = (size_t)R * R;
-    out.assign((size_t)K * RR, 0.0);
+    out.assign((size_t)K * RR, 0.0L);
     for (int i = 0; i < R; ++i)
         for (int j = 0; j < R; ++j) {
             const size_t ij = (size_t)i * R + j;
-            if (kind == MLMC_MONOMIAL) { out[(size_t)(i + j) * RR + ij] = 1.0; continue; }
-            typedef long double ld;
             const int hi = i > j ? i : j, lo = i > j ? j : i;
             const ld diff = (ld)(hi - lo);
             // first term k = |i - j| (s = hi):  (2 diff + 1) / (2 hi + 1) * A(diff) A(lo) / A(hi)
@@ -144,7 +144,7 @@ bool product_table(int kind, int R, std::vector<double> &out) {
             }
             for (int t = 0; t <= lo; ++t) {          // term t: k = diff + 2 t, s = hi + t
                 const int k = (hi - lo) + 2 * t;
-                out[(size_t)k * RR + ij] = (double)c;
+                out[(size_t)k * RR + ij] = c;
                 if (t == lo) break;
                 const ld s = (ld)hi + t, kk = (ld)k;
                 const ld si = s - hi, sj = s - lo, sk = s - kk;
@@ -155,6 +155,21 @@ bool product_table(int kind, int R, std::vector<double> &out) {
                 c = c * ratio;
             }
         }
+}
+
+bool product_table(int kind, int R, std::vector<double> &out) {
+    if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL) return false;
+    const int K = 2 * R - 1;
+    const size_t RR = (size_t)R * R;
+    out.assign((size_t)K * RR, 0.0);
+    if (kind == MLMC_MONOMIAL) {
+        for (int i = 0; i < R; ++i)
+            for (int j = 0; j < R; ++j) out[(size_t)(i + j) * RR + (size_t)i * R + j] = 1.0;
+        return true;
+    }
+    std::vector<ld> c;
+    legendre_products_ld(R, c);
+    for (size_t q = 0; q < c.size(); ++q) out[q] = (double)c[q];
     return true;
 }
 
@@ -162,17 +177,10 @@ bool product_table(int kind, int R, std::vector<double> &out) {
 // Legendre: the coefficients are (2k + 1) / 2 * int P_k (P_i P_j)^2, a polynomial of degree <= 8 R - 8 integrated exactly by a
 // Gauss-Legendre rule of 4 R points, nodes and weights by Newton's iteration, everything in extended precision and rounded
 // once; odd k and k > 2 (i + j) are exact zeros; non-negative, rows sum to one.  Monomials: t^(2 (i + j)).
-bool square_product_table(int kind, int R, std::vector<double> &out) {
-    if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL) return false;
+static void legendre_square_products_ld(int R, std::vector<ld> &out) {
     const int K = 4 * R - 3;
     const size_t RR = (size_t)R * R;
-    out.assign((size_t)K * RR, 0.0);
-    if (kind == MLMC_MONOMIAL) {
-        for (int i = 0; i < R; ++i)
-            for (int j = 0; j < R; ++j) out[(size_t)(2 * (i + j)) * RR + (size_t)i * R + j] = 1.0;
-        return true;
-    }
-    typedef long double ld;
+    out.assign((size_t)K * RR, 0.0L);
     const int Q = 4 * R;
     const ld pi = 3.14159265358979323846264338327950288L;
     std::vector<ld> x(Q), w(Q), P((size_t)K * Q);
@@ -222,26 +230,99 @@ bool square_product_table(int kind, int R, std::vector<double> &out) {
                 ld acc = 0.0L;
                 const ld *Pk = &P[(size_t)k * Q];
                 for (int q = 0; q < Q; ++q) acc += sq[q] * Pk[q];
-                const double c = (double)(acc * (2 * k + 1) / 2);
+                const ld c = acc * (2 * k + 1) / 2;
                 out[(size_t)k * RR + (size_t)i * R + j] = c;
                 out[(size_t)k * RR + (size_t)j * R + i] = c;
             }
         }
     // (P_0 P_j)^2 = P_j^2: these rows are the product table's own (Adams' formula) -- in particular c2_00k = delta_k0 EXACTLY,
     // which the exact sample counts in the P_0 P_0 entries (and vars[0] == 0) rest on, whatever the last bit of the quadrature
-    std::vector<double> t1;
-    product_table(kind, R, t1);
+    std::vector<ld> t1;
+    legendre_products_ld(R, t1);
     for (int j = 0; j < R; ++j)
         for (int k = 0; k < K; ++k) {
-            const double c = k < 2 * R - 1 ? t1[(size_t)k * RR + (size_t)j * R + j] : 0.0;
+            const ld c = k < 2 * R - 1 ? t1[(size_t)k * RR + (size_t)j * R + j] : 0.0L;
             out[(size_t)k * RR + (size_t)j] = c;
             out[(size_t)k * RR + (size_t)j * R] = c;
+        }
+}
+
+bool square_product_table(int kind, int R, std::vector<double> &out) {
+    if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL) return false;
+    const int K = 4 * R - 3;
+    const size_t RR = (size_t)R * R;
+    out.assign((size_t)K * RR, 0.0);
+    if (kind == MLMC_MONOMIAL) {
+        for (int i = 0; i < R; ++i)
+            for (int j = 0; j < R; ++j) out[(size_t)(2 * (i + j)) * RR + (size_t)i * R + j] = 1.0;
+        return true;
+    }
+    std::vector<ld> c;
+    legendre_square_products_ld(R, c);
+    for (size_t q = 0; q < c.size(); ++q) out[q] = (double)c[q];
+    return true;
+}
+
+// The same two tables for level sums of CHEBYSHEV polynomials (the inner accumulators of a Legendre covariance, ensure_lin):
+// P_k = sum_m a_km T_m with a_{k,|k - 2 j|} += g_j g_{k-j}, j = 0..k, g_j = (2j - 1)!! / (2j)!!  (P_k(cos th) = sum_j g_j g_{k-j}
+// cos((k - 2 j) th)), so sum_k c_ijk S[P_k] = sum_m c'_ijm S[T_m] with c'_ijm = sum_k c_ijk a_km.  All a_km >= 0, every row of a sums to
+// one (P_k(1) = T_m(1) = 1) and m has the parity of k, so the composed tables keep what the Legendre ones have: non-negative entries,
+// rows that sum to one, zeros for m > deg and for the wrong parity, c'_00m = delta_m0 exactly (a_00 = 1).  Composed in extended
+// precision from the unrounded Legendre coefficients and rounded once, for i <= j and mirrored: symmetric bit for bit.
+static void chebyshev_compose(const std::vector<ld> &c, int K, int R, std::vector<double> &out) {
+    const size_t RR = (size_t)R * R;
+    std::vector<ld> g(K), at((size_t)K * K, 0.0L), col(K);   // at[m][k] = a_km
+    g[0] = 1.0L;
+    for (int j = 1; j < K; ++j) g[j] = g[j - 1] * (ld)(2 * j - 1) / (ld)(2 * j);
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j <= k; ++j) at[(size_t)(k - 2 * j < 0 ? 2 * j - k : k - 2 * j) * K + k] += g[j] * g[k - j];
+    out.assign((size_t)K * RR, 0.0);
+    for (int i = 0; i < R; ++i)
+        for (int j = i; j < R; ++j) {
+            const size_t ij = (size_t)i * R + j, ji = (size_t)j * R + i;
+            for (int k = 0; k < K; ++k) col[k] = c[(size_t)k * RR + ij];
+            for (int m = 0; m < K; ++m) {
+                ld acc = 0.0L;
+                for (int k = m; k < K; k += 2) acc += col[k] * at[(size_t)m * K + k];
+                out[(size_t)m * RR + ij] = out[(size_t)m * RR + ji] = (double)acc;
+            }
+        }
+}
+
+bool product_table_chebyshev(int R, std::vector<double> &out) {
+    std::vector<ld> c;
+    legendre_products_ld(R, c);
+    chebyshev_compose(c, 2 * R - 1, R, out);
+    return true;
+}
+
+bool square_product_table_chebyshev(int R, std::vector<double> &out) {
+    std::vector<ld> c;
+    legendre_square_products_ld(R, c);
+    const int K = 4 * R - 3;
+    chebyshev_compose(c, K, R, out);
+    // rows with i = 0 (or j = 0): the product table's, bit for bit -- as in the Legendre table
+    std::vector<double> t1;
+    product_table_chebyshev(R, t1);
+    const size_t RR = (size_t)R * R;
+    for (int j = 0; j < R; ++j)
+        for (int m = 0; m < K; ++m) {
+            const double v = m < 2 * R - 1 ? t1[(size_t)m * RR + (size_t)j * R + j] : 0.0;
+            out[(size_t)m * RR + (size_t)j] = v;
+            out[(size_t)m * RR + (size_t)j * R] = v;
         }
     return true;
 }
 
 static bool linearize_enabled() {
     const char *e = std::getenv("MLMC_HIP_LINEARIZE");
+    return !(e && e[0] == '0');
+}
+
+// MLMC_HIP_LINEARIZE_CHEB=0: the inner accumulators of a Legendre covariance sum Legendre polynomials, as they did before the
+// Chebyshev sums (A/B runs, tests).  Read when an accumulator is created.
+static bool linearize_chebyshev_enabled() {
+    const char *e = std::getenv("MLMC_HIP_LINEARIZE_CHEB");
     return !(e && e[0] == '0');
 }
 
@@ -444,23 +525,25 @@ int mlmc_basis_eval(const mlmc_basis *b, const double *x, int64_t n, int32_t siz
     return rc;
 }
 
-// The coefficient tables of the linearisations live on the device once per (family, size) for the life of the process (4 MB +
-// 8 MB at R = 64): accumulators share them.
+// The coefficient tables of the linearisations live on the device once per (family of the sums, family, size) for the life of the
+// process (4 MB + 8 MB at R = 64): accumulators share them.  cheb: the tables for level sums of Chebyshev polynomials.
 struct LinTables {
     double *d_prod = nullptr, *d_prod2 = nullptr;
 };
-static int lin_tables(int kind, int R, bool squares, LinTables **out) {
-    static std::map<std::pair<int, int>, LinTables> cache;
-    LinTables &t = cache[std::make_pair(kind, R)];
+static int lin_tables(int kind, int R, bool cheb, bool squares, LinTables **out) {
+    static std::map<std::tuple<int, int, int>, LinTables> cache;
+    LinTables &t = cache[std::make_tuple(cheb ? 1 : 0, kind, R)];
     if (!t.d_prod) {
         std::vector<double> h;
-        product_table(kind, R, h);
+        if (cheb) product_table_chebyshev(R, h);
+        else product_table(kind, R, h);
         MLMC_HIP_CHECK(hipMalloc(&t.d_prod, sizeof(double) * h.size()));
         MLMC_HIP_CHECK(hipMemcpy(t.d_prod, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
     }
     if (squares && !t.d_prod2) {
         std::vector<double> h;                  // ~0.2 s of host time at R = 64
-        square_product_table(kind, R, h);
+        if (cheb) square_product_table_chebyshev(R, h);
+        else square_product_table(kind, R, h);
         MLMC_HIP_CHECK(hipMalloc(&t.d_prod2, sizeof(double) * h.size()));
         MLMC_HIP_CHECK(hipMemcpy(t.d_prod2, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
     }
@@ -468,39 +551,51 @@ static int lin_tables(int kind, int R, bool squares, LinTables **out) {
     return 0;
 }
 
-// Inner accumulators of a covariance accumulator that takes (part of) its sums from level sums of moments; called with the
-// first chunk that is large enough.
-static int ensure_lin(mlmc_accum *a) {
-    if (a->lin) return 0;
-    const mlmc_basis *b = a->basis;
-    LinTables *t = nullptr;
-    if (int rc = lin_tables(b->p.kind, a->R, a->lin0_eligible, &t)) return rc;
+// An inner basis of `size` terms over the transform and keep thresholds of the caller's basis `b`.  cheb: Chebyshev polynomials
+// (KIND_CHEBYSHEV, which mlmc_basis_create does not accept: created as monomials -- unit scales -- and re-labelled).
+static int inner_basis_create(const mlmc_basis *b, int size, bool cheb, mlmc_basis **out) {
     mlmc_basis_desc d;
     std::memset(&d, 0, sizeof(d));
-    d.kind = b->p.kind;
-    d.size = 2 * a->R - 1;
+    d.kind = cheb ? (int)MLMC_MONOMIAL : b->p.kind;
+    d.size = size;
     d.shift = b->p.shift; d.scale = b->p.scale; d.ref0 = b->p.ref0; d.ref1 = b->p.ref1;
     d.is_log = b->p.is_log; d.is_clip = b->p.is_clip;
     d.x_lo = b->p.x_lo; d.x_hi = b->p.x_hi;              // the very thresholds of the caller's basis: the same samples are kept
-    int rc = mlmc_basis_create(&d, &a->lin_basis);
+    if (int rc = mlmc_basis_create(&d, out)) return rc;
+    (*out)->p.x_lo = b->p.x_lo;                          // (a desc with x_lo == x_hi == 0 would have been bisected anew)
+    (*out)->p.x_hi = b->p.x_hi;
+    if (cheb) (*out)->p.kind = KIND_CHEBYSHEV;
+    return 0;
+}
+
+// Inner accumulators of a covariance accumulator that takes (part of) its sums from level sums of moments; called with the
+// first chunk that is large enough.  Legendre moments: the inner accumulators sum CHEBYSHEV polynomials of the same transformed
+// value wherever the mean-only term-split kernel runs them (more than 64 terms) -- one FMA per term instead of a multiply and an
+// FMA -- and the tables carry the change of basis (chebyshev_compose).
+static int ensure_lin(mlmc_accum *a) {
+    if (a->lin) return 0;
+    const mlmc_basis *b = a->basis;
+    const int K1 = 2 * a->R - 1, K2 = 4 * a->R - 3;
+    const bool cheb1 = a->lin_cheb && K1 > 64, cheb2 = a->lin_cheb && K2 > 64;
+    LinTables *t1 = nullptr, *t2 = nullptr;
+    if (int rc = lin_tables(b->p.kind, a->R, cheb1, false, &t1)) return rc;
+    if (a->lin0_eligible)
+        if (int rc = lin_tables(b->p.kind, a->R, cheb2, true, &t2)) return rc;
+    int rc = inner_basis_create(b, K1, cheb1, &a->lin_basis);
     if (!rc) rc = mlmc_accum_create(a->lin_basis, a->n_levels, MLMC_MODE_MOMENTS | MLMC_MODE_MEAN_ONLY, a->n_comp, &a->lin);
     if (!rc) {
-        a->lin_basis->p.x_lo = b->p.x_lo;                // (a desc with x_lo == x_hi == 0 would have been bisected anew)
-        a->lin_basis->p.x_hi = b->p.x_hi;
         a->lin->host_outputs = false;                    // its totals are read on the device (launch_cov_finalize)
-        a->lin_K = d.size;
-        a->d_lin_prod = t->d_prod;
+        a->lin_K = K1;
+        a->d_lin_prod = t1->d_prod;
     }
     if (!rc && a->lin0_eligible) {
-        d.size = 4 * a->R - 3;
-        rc = mlmc_basis_create(&d, &a->lin0_basis);
+        rc = inner_basis_create(b, K2, cheb2, &a->lin0_basis);
         if (!rc) rc = mlmc_accum_create(a->lin0_basis, a->n_levels, MLMC_MODE_MOMENTS | MLMC_MODE_MEAN_ONLY, a->n_comp, &a->lin0);
         if (!rc) {
-            a->lin0_basis->p.x_lo = b->p.x_lo;
-            a->lin0_basis->p.x_hi = b->p.x_hi;
             a->lin0->host_outputs = false;
-            a->lin0_K = d.size;
-            a->d_lin0_prod = t->d_prod2;
+            a->lin0_K = K2;
+            a->d_lin0_prod1 = t2->d_prod;                // products from the first 2 R - 1 sums of THIS accumulator's family
+            a->d_lin0_prod = t2->d_prod2;
         }
     }
     if (rc) {            // no half-built state: the accumulator goes on with all three Gram matrices
@@ -538,7 +633,8 @@ int mlmc_accum_create(const mlmc_basis *b, int32_t n_levels, int32_t mode, int32
     // plain polynomial moments with 64 < R <= 128: the mean-only form of the term-split kernel covers them in ONE pass
     // (moments.hip, k_moments_accum_split<..., SQ = false>); every other plain size keeps its free sums of squares
     a->mean_only_plain = mean_only && mode == MLMC_MODE_MOMENTS && b->out_size == 0 &&
-                         (b->p.kind == MLMC_LEGENDRE || b->p.kind == MLMC_MONOMIAL) && b->p.size > 64 && b->p.size <= 256;
+                         (b->p.kind == MLMC_LEGENDRE || b->p.kind == MLMC_MONOMIAL || b->p.kind == KIND_CHEBYSHEV) && b->p.size > 64 &&
+                         b->p.size <= 256;
     a->n_comp = n_comp;
     a->R = b->p.size;
     a->Rout = b->out_size > 0 ? b->out_size : b->p.size;
@@ -592,6 +688,9 @@ int mlmc_accum_create(const mlmc_basis *b, int32_t n_levels, int32_t mode, int32
         // level 0 without the matrix cores (<= 64 moments: the 4 R - 3 extended terms fit the two windows of the mean-only kernel)
         const char *lin0_env = std::getenv("MLMC_HIP_LINEARIZE_LEVEL0");
         a->lin0_eligible = a->R <= 64 && !(lin0_env && lin0_env[0] == '0');
+        // Legendre: the inner accumulators sum Chebyshev polynomials (ensure_lin); MLMC_HIP_NO_SPLIT=1 asks for the kernels without
+        // the term split, which exist for the public families only
+        a->lin_cheb = b->p.kind == MLMC_LEGENDRE && linearize_chebyshev_enabled() && std::getenv("MLMC_HIP_NO_SPLIT") == nullptr;
     }
     *out = a;
     return mlmc_accum_reset(a);
@@ -610,6 +709,8 @@ int mlmc_accum_reset(mlmc_accum *a) {
         a->xcov_pushes = 0;
     }
     a->lin_used = a->lin0_used = false;
+    a->lin_levels.assign(a->n_levels, 0);
+    a->lin0_levels.assign(a->n_levels, 0);
     if (a->lin0)
         if (int rc = mlmc_accum_reset(a->lin0)) return rc;
     if (a->lin) return mlmc_accum_reset(a->lin);
@@ -768,6 +869,7 @@ int mlmc_accum_push(mlmc_accum *a, int32_t level, const double *fine, const doub
             const bool use_lin0 = a->lin0 && !d_c && n >= a->lin_min_n;
             if (use_lin0) {
                 a->lin0_used = true;
+                a->lin0_levels[level] = 1;
                 rc = launch_moments_accum(a->lin0, level, m, f_m, nullptr, d_mask, n, count_in_kernel && m == 0,
                                           mem_kind == MLMC_DEVICE || a->n_comp > 1);
                 if (rc) return rc;
@@ -778,7 +880,7 @@ int mlmc_accum_push(mlmc_accum *a, int32_t level, const double *fine, const doub
             // the extended moments of the linearised mean over the same chunk (same mask; the covariance kernel counts);
             // device chunks wait for finalize and go out as ONE launch over all levels; staged host chunks and the components of a
             // vector quantity (shared mask scratch) are launched when the push ends
-            if (!rc && use_lin) a->lin_used = true;
+            if (!rc && use_lin) { a->lin_used = true; a->lin_levels[level] = 1; }
             if (!rc && use_lin)
                 rc = launch_moments_accum(a->lin, level, m, f_m, c_m, d_mask, n, false, mem_kind == MLMC_DEVICE || a->n_comp > 1);
         }
@@ -927,12 +1029,21 @@ int mlmc_accum_aux_kernel_time(mlmc_accum *a, double *ms, int64_t *launches, int
 int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *out, int64_t out_len) {
     if (!out) return fail("mlmc_linearization_table: null argument");
     if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL) return fail("mlmc_linearization_table: Legendre or monomial moments");
-    if (R < 1 || R > (squares ? 64 : 128)) return fail("mlmc_linearization_table: size out of range");
-    const int64_t K = squares ? 4 * (int64_t)R - 3 : 2 * (int64_t)R - 1;
+    if (squares < 0 || squares > 3) return fail("mlmc_linearization_table: squares is 0 .. 3");
+    const bool cheb = squares >= 2, sq = squares == 1 || squares == 3;
+    if (cheb && kind != MLMC_LEGENDRE) return fail("mlmc_linearization_table: the tables for Chebyshev sums belong to Legendre moments");
+    if (R < 1 || R > (sq ? 64 : 128)) return fail("mlmc_linearization_table: size out of range");
+    const int64_t K = sq ? 4 * (int64_t)R - 3 : 2 * (int64_t)R - 1;
     if (out_len < K * R * R) return fail("mlmc_linearization_table: output too small");
     std::vector<double> t;
-    if (squares) square_product_table(kind, R, t);
-    else product_table(kind, R, t);
+    if (cheb) {
+        if (sq) square_product_table_chebyshev(R, t);
+        else product_table_chebyshev(R, t);
+    } else if (sq) {
+        square_product_table(kind, R, t);
+    } else {
+        product_table(kind, R, t);
+    }
     std::memcpy(out, t.data(), sizeof(double) * t.size());
     return 0;
 }

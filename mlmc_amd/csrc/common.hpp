@@ -16,6 +16,14 @@ constexpr int ACC_THREADS = 256;   // 4 waves, one per SIMD of a CU
 #define MLMC_TERMS_PER_PASS 64
 #endif
 constexpr int MAX_TERMS_PER_PASS = MLMC_TERMS_PER_PASS;
+// Internal basis kind beside the public ones of mlmc_hip.h: Chebyshev polynomials T_k, the cheapest recurrence for the level sums the
+// linearised covariance contracts with a table (device_basis.hpp).  Not accepted by mlmc_basis_create; term-split mean-only kernels only.
+constexpr int KIND_CHEBYSHEV = 16;
+// The public kinds index per-kind caches by `kind & 7` (moments.hip, flush_moments): the internal value stays clear of every one of them,
+// and flush_moments refuses it before that cache is reached.
+static_assert(KIND_CHEBYSHEV > MLMC_SPLINE && KIND_CHEBYSHEV > MLMC_IDENTITY && KIND_CHEBYSHEV > MLMC_FOURIER && KIND_CHEBYSHEV > MLMC_MONOMIAL &&
+                  KIND_CHEBYSHEV > MLMC_LEGENDRE && KIND_CHEBYSHEV > 7,
+              "KIND_CHEBYSHEV must not collide with a public basis kind of mlmc_hip.h");
 constexpr int SPLINE_BAND_MAX_R = 256;   // banded mean-only covariance of spline moments (cov.hip): 4 x 5 x (R + 8) doubles of LDS
 
 // ---- error plumbing ---------------------------------------------------------------------
@@ -154,6 +162,11 @@ struct mlmc_accum {
     mlmc_accum *lin0 = nullptr;
     mlmc_basis *lin0_basis = nullptr;
     double *d_lin0_prod = nullptr;        // [lin0_K][R * R]: c2_ijk, k-major
+    double *d_lin0_prod1 = nullptr;       // [lin_K][R * R]: c_ijk for the first 2 R - 1 sums of lin0 (its own family: see lin_cheb)
+    // Legendre: the inner accumulators sum Chebyshev polynomials (KIND_CHEBYSHEV) where they have more than 64 terms, and the tables
+    // are composed with the connection P_k = sum_m a_km T_m (api.hip, ensure_lin); MLMC_HIP_LINEARIZE_CHEB=0: Legendre sums
+    bool lin_cheb = false;
+    std::vector<char> lin_levels, lin0_levels;   // levels with a chunk in lin / lin0 since the last reset (launch_cov_finalize)
     int lin0_K = 0;
     bool lin0_used = false;
     int64_t lin_min_n = 0;                // chunks with fewer samples keep all three Gram matrices on the matrix cores (the
@@ -189,6 +202,9 @@ int launch_xcov_finalize(mlmc_accum *a);
 bool product_table(int kind, int R, std::vector<double> &out);
 // c2_ijk of (phi_i phi_j)^2 = sum_k c2_ijk phi_k, k-major [4 R - 3][R * R]
 bool square_product_table(int kind, int R, std::vector<double> &out);
+// both for level sums of Chebyshev polynomials (Legendre moments): c'_ijm = sum_k c_ijk a_km
+bool product_table_chebyshev(int R, std::vector<double> &out);
+bool square_product_table_chebyshev(int R, std::vector<double> &out);
 int launch_cov_from_values(mlmc_accum *a, int level, int comp, const double *d_vf, const double *d_vc, const uint8_t *d_mask,
                            int64_t n, bool count, int gram_mode = 0);
 int ensure(void **p, size_t *cap, size_t bytes);

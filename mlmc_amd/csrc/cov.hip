@@ -15,6 +15,8 @@
 // values term-major into LDS (conflict-free: row stride 66 doubles).  Phase 2: every wave reads MFMA
 // fragments (A[i][k]: lane -> term i = lane & 15, sample k = lane >> 4) and issues 3 MFMAs per
 // (row tile, column tile, 4 samples).  Two workgroups per CU so one's phase 1 runs under the other's MFMAs.
+#include <cstring>
+
 #include "device_basis.hpp"
 
 namespace mlmc {
@@ -1251,36 +1253,63 @@ __global__ void k_cov_finalize(const double *__restrict__ totals, const double *
                                                   : 0.25 * (cc * cc) * ((G1[i * RP + j] + G1[j * RP + i]) + 2.0 * G2[i * RP + j]);
 }
 
-// Mean of the covariance through the product linearisation: out_s[lc][i][j] = sum_k c_ijk (scale_k S_k[lc]), S = level sums of
-// the 2 R - 1 (scaled) moments of the inner accumulator.  The table is k-major: consecutive threads read consecutive entries.
-// A thread owns one (i, j) for up to LIN_LC (level, component) rows: every table entry is read once per LIN_LC rows.  parity_step 2
-// (Legendre): c_ijk = 0 unless k = i + j (mod 2) (products), c2_ijk = 0 for odd k (squares: `squares` != 0) -- the other half of
-// the table is not even read.
+// Mean of the covariance through the product linearisation: out_s[lc][i][j] += sum_k c_ijk (scale_k S_k[lc]), S = level sums of
+// the 2 R - 1 (scaled) moments of an inner accumulator -- and, with the squares' table and the 4 R - 3 sums of the level-0
+// accumulator, the second moments out_sp likewise.  ONE launch per estimate: blockIdx.y selects a job = up to LIN_LC (level,
+// component) rows of one output array with up to two sources (table, totals), taken one after the other by the same thread so
+// that a row fed by both inner accumulators (chunks with and without coarse values in one level) is added to in a fixed order.
+// Only rows an inner accumulator has seen a chunk for are walked.  The tables are k-major: consecutive threads read consecutive
+// entries; a thread owns one (i, j) for the rows of its job: every table entry is read once per job.  parity_step 2 (Legendre moments,
+// sums of Legendre or Chebyshev polynomials alike): c_ijk = 0 unless k = i + j (mod 2) (products), c2_ijk = 0 for odd k (squares) -- the other
+// half of the table is not even read.
 constexpr int LIN_LC = 8;
-__global__ void k_cov_lin_mean(const double *__restrict__ prod, const double *__restrict__ lin_totals, const double *__restrict__ lin_scale,
-                               int R, int K, int64_t lin_width, double *__restrict__ out_s, int n_lc, int parity_step, int squares) {
-    extern __shared__ double m_s[];     // [LIN_LC][K] true-value sums of these (level, component) rows
-    const int lc0 = blockIdx.y * LIN_LC;
-    for (int q = threadIdx.x; q < LIN_LC * K; q += blockDim.x) {
-        const int l = q / K, k = q % K;
-        m_s[q] = lc0 + l < n_lc ? lin_scale[k] * lin_totals[(int64_t)(lc0 + l) * lin_width + k] : 0.0;
-    }
-    __syncthreads();
+constexpr int LIN_MAX_JOBS = 12;
+struct LinSrc {
+    const double *prod;      // [K][R * R]; nullptr: no such source
+    const double *totals;    // inner accumulator's totals, row stride `width`
+    const double *scale;     // [K]: true value of sum k = scale[k] * totals[k]
+    int64_t width;
+    int K, squares;
+};
+struct LinJob {
+    double *out;             // out_s or out_sp
+    int n_rows;
+    int row[LIN_LC];         // (level, component) rows
+    LinSrc src[2];
+};
+struct LinJobs {
+    LinJob job[LIN_MAX_JOBS];
+};
+__global__ void k_cov_lin_mean(LinJobs jobs, int R, int parity_step) {
+    extern __shared__ double m_s[];     // [LIN_LC][K] true-value sums of the job's rows
+    const LinJob &jb = jobs.job[blockIdx.y];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int RR = R * R;
-    if (idx >= RR) return;
-    double acc[LIN_LC];
+    for (int e = 0; e < 2; ++e) {
+        const LinSrc &sr = jb.src[e];
+        if (!sr.prod) continue;         // (uniform)
+        const int K = sr.K;
+        __syncthreads();                // the previous source's sums have been used
+        for (int q = threadIdx.x; q < LIN_LC * K; q += blockDim.x) {
+            const int l = q / K, k = q % K;
+            m_s[q] = l < jb.n_rows ? sr.scale[k] * sr.totals[(int64_t)jb.row[l] * sr.width + k] : 0.0;
+        }
+        __syncthreads();
+        if (idx < RR) {
+            double acc[LIN_LC];
 #pragma unroll
-    for (int l = 0; l < LIN_LC; ++l) acc[l] = 0.0;
-    const int k0 = (parity_step == 2 && !squares) ? ((idx / R + idx % R) & 1) : 0;
-    for (int k = k0; k < K; k += parity_step) {
-        const double c = prod[(int64_t)k * RR + idx];
+            for (int l = 0; l < LIN_LC; ++l) acc[l] = 0.0;
+            const int k0 = (parity_step == 2 && !sr.squares) ? ((idx / R + idx % R) & 1) : 0;
+            for (int k = k0; k < K; k += parity_step) {
+                const double c = sr.prod[(int64_t)k * RR + idx];
 #pragma unroll
-        for (int l = 0; l < LIN_LC; ++l) acc[l] = __builtin_fma(c, m_s[l * K + k], acc[l]);
+                for (int l = 0; l < LIN_LC; ++l) acc[l] = __builtin_fma(c, m_s[l * K + k], acc[l]);
+            }
+#pragma unroll
+            for (int l = 0; l < LIN_LC; ++l)
+                if (l < jb.n_rows) jb.out[(int64_t)jb.row[l] * RR + idx] += acc[l];     // (+ the sums of the chunks that went the direct way)
+        }
     }
-#pragma unroll
-    for (int l = 0; l < LIN_LC; ++l)
-        if (lc0 + l < n_lc) out_s[(int64_t)(lc0 + l) * RR + idx] += acc[l];     // (+ the sums of the chunks that went the direct way)
 }
 
 int launch_cov_finalize(mlmc_accum *a) {
@@ -1291,7 +1320,6 @@ int launch_cov_finalize(mlmc_accum *a) {
     if (lin0) {
         if (int rc = flush_moments(a->lin0)) return rc;
     }
-    const dim3 lin_grid((a->R * a->R + 255) / 256, (a->n_levels * a->n_comp + LIN_LC - 1) / LIN_LC);
     const int pstep = a->basis->p.kind == MLMC_LEGENDRE ? 2 : 1;
     const int n_lc = a->n_levels * a->n_comp;
     const bool vals = a->cov_from_values;              // TransformedMoments / more than 128 moments: accumulated from true values
@@ -1301,21 +1329,60 @@ int launch_cov_finalize(mlmc_accum *a) {
                        a->RP, a->int_width, a->d_out_s, a->d_out_sp, a->d_counts, a->n_levels, a->d_out_n, a->d_out_nd,
                        a->mean_only ? 1 : 0, lin0 ? a->lin0->d_counts : (const int64_t *)nullptr);
     MLMC_HIP_CHECK(hipGetLastError());
+    const bool lin = a->lin && a->lin_used;
+    if (!lin && !lin0) return 0;
+    // Level-0 chunks that went without a matrix pass (lin0): sum f_i f_j from the first 2 R - 1 extended sums, sum (f_i f_j)^2 from all
+    // 4 R - 3 (at level 0 the finalize formula 1/4 (G1 + G1^T + 2 G2) is this very sum: both kinds of chunk add up).  Chunks without G0
+    // (gram_mode 3, lin): their share of the means comes from the extended moments.  Jobs: the means of the rows only lin0 has fed, of
+    // the rows only lin has fed, of the rows both have fed (lin0 first); the second moments of lin0's rows.
+    LinSrc src0, src02, src1;
+    std::memset(&src0, 0, sizeof(src0));
+    std::memset(&src02, 0, sizeof(src02));
+    std::memset(&src1, 0, sizeof(src1));
+    int max_K = 0;
     if (lin0) {
-        // level-0 chunks that went without a matrix pass: sum f_i f_j from the first 2 R - 1 extended sums, sum (f_i f_j)^2 from all
-        // 4 R - 3 (at level 0 the finalize formula 1/4 (G1 + G1^T + 2 G2) is this very sum: both kinds of chunk add up)
-        hipLaunchKernelGGL(k_cov_lin_mean, lin_grid, dim3(256), sizeof(double) * LIN_LC * a->lin_K, rt().stream,
-                           a->d_lin_prod, a->lin0->d_totals, a->lin0_basis->d_scale, R, a->lin_K, a->lin0->int_width, a->d_out_s, n_lc, pstep, 0);
-        hipLaunchKernelGGL(k_cov_lin_mean, lin_grid, dim3(256), sizeof(double) * LIN_LC * a->lin0_K, rt().stream,
-                           a->d_lin0_prod, a->lin0->d_totals, a->lin0_basis->d_scale, R, a->lin0_K, a->lin0->int_width, a->d_out_sp, n_lc, pstep, 1);
-        MLMC_HIP_CHECK(hipGetLastError());
+        src0.prod = a->d_lin0_prod1; src0.totals = a->lin0->d_totals; src0.scale = a->lin0_basis->d_scale;
+        src0.width = a->lin0->int_width; src0.K = a->lin_K; src0.squares = 0;
+        src02 = src0;
+        src02.prod = a->d_lin0_prod; src02.K = a->lin0_K; src02.squares = 1;
+        max_K = a->lin0_K;
     }
-    if (a->lin && a->lin_used) {       // chunks without G0 (gram_mode 3): their share of the means comes from the extended moments
-        hipLaunchKernelGGL(k_cov_lin_mean, lin_grid, dim3(256), sizeof(double) * LIN_LC * a->lin_K, rt().stream,
-                           a->d_lin_prod, a->lin->d_totals, a->lin_basis->d_scale, R, a->lin_K, a->lin->int_width, a->d_out_s, n_lc, pstep, 0);
-        MLMC_HIP_CHECK(hipGetLastError());
+    if (lin) {
+        src1.prod = a->d_lin_prod; src1.totals = a->lin->d_totals; src1.scale = a->lin_basis->d_scale;
+        src1.width = a->lin->int_width; src1.K = a->lin_K; src1.squares = 0;
+        if (a->lin_K > max_K) max_K = a->lin_K;
     }
-    return 0;
+    LinJobs jobs;
+    std::memset(&jobs, 0, sizeof(jobs));
+    int n_jobs = 0;
+    const dim3 block(256);
+    auto launch = [&]() -> int {
+        if (n_jobs == 0) return 0;
+        hipLaunchKernelGGL(k_cov_lin_mean, dim3((R * R + 255) / 256, n_jobs), block, sizeof(double) * LIN_LC * max_K, rt().stream, jobs, R, pstep);
+        MLMC_HIP_CHECK(hipGetLastError());
+        std::memset(&jobs, 0, sizeof(jobs));
+        n_jobs = 0;
+        return 0;
+    };
+    // cls 1: lin0 only, 2: lin only, 3: both (means); 4: second moments of lin0's rows
+    for (int cls = 1; cls <= 4; ++cls) {
+        LinJob *jb = nullptr;
+        for (int lc = 0; lc < n_lc; ++lc) {
+            const int level = lc / a->n_comp;
+            const int fed = ((lin0 && a->lin0_levels[level]) ? 1 : 0) | ((lin && a->lin_levels[level]) ? 2 : 0);
+            if (cls <= 3 ? fed != cls : !(fed & 1)) continue;
+            if (!jb || jb->n_rows == LIN_LC) {
+                if (n_jobs == LIN_MAX_JOBS)
+                    if (int rc = launch()) return rc;
+                jb = &jobs.job[n_jobs++];
+                jb->out = cls == 4 ? a->d_out_sp : a->d_out_s;
+                jb->src[0] = cls == 4 ? src02 : (cls == 2 ? src1 : src0);
+                if (cls == 3) jb->src[1] = src1;
+            }
+            jb->row[jb->n_rows++] = lc;
+        }
+    }
+    return launch();
 }
 
 }  // namespace mlmc

@@ -66,11 +66,15 @@ __device__ constexpr LegendreG kLegendreG = LegendreG();
 // would leave the normal fp64 range near i = 480), the q_i stay O(1) up to the largest accepted size; powers of two
 // scale exactly, so every q_i is bit for bit 2^i times the unscaled value.  The true Legendre value is
 // P_i = c_i q_i with c_i = (leading coefficient of P_i) / 2^i ~ 1 / sqrt(pi i), applied once to the finished sums.
+//
+// KIND_CHEBYSHEV (internal: the inner accumulators of the linearised covariance, api.hip ensure_lin) is T_i = 2t T_{i-1} - T_{i-2}:
+// ONE FMA per term, no coefficient and no final scale.  Level sums of T_k serve the linearisation as well as sums of P_k, the
+// exact connection P_n = sum_m a_nm T_m being folded into the coefficient tables on the host (chebyshev_compose, api.hip).
 template <int KIND>
 struct TermGen {
     double x, p1, p2, c1, s1;
     __device__ __forceinline__ void init(double x_, double w, const BasisParams &) {
-        x = KIND == MLMC_LEGENDRE ? 2.0 * x_ : x_;
+        x = (KIND == MLMC_LEGENDRE || KIND == KIND_CHEBYSHEV) ? 2.0 * x_ : x_;
         p1 = w;   // term 0
         p2 = 0.0;
         if (KIND == MLMC_FOURIER) {
@@ -87,9 +91,30 @@ struct TermGen {
             p2 = p1;
             p1 = q;
             return q;
+        } else if (KIND == KIND_CHEBYSHEV) {
+            const double q = __builtin_fma(x, p1, -p2);
+            p2 = p1;
+            p1 = q;
+            return q;
         } else {
             return next(2 + (j & 1));
         }
+    }
+    // KIND_CHEBYSHEV, right after init: the state next(0) .. next(127) would leave, from the doubling identities
+    // T_2n = 2 T_n^2 - 1, T_2n+1 = 2 T_n T_n+1 - t: (T_1, T_2) -> (T_128, T_129) in seven doublings, two steps back to
+    // (T_127, T_126) -- 27 instructions instead of 128.  The keep weight is applied last (masked value: t = 0, exact zeros).
+    __device__ __forceinline__ void jump128() {
+        const double w = p1, t = 0.5 * x;
+        double a = t, b = __builtin_fma(x, t, -1.0);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const double a2 = 2.0 * a;
+            b = __builtin_fma(a2, b, -t);
+            a = __builtin_fma(a2, a, -1.0);
+        }
+        const double c = __builtin_fma(x, a, -b);
+        p2 = __builtin_fma(x, c, -a) * w;
+        p1 = c * w;
     }
     // must be called with i = 0, 1, 2, ... in order
     __device__ __forceinline__ double next(int i) {
@@ -98,6 +123,13 @@ struct TermGen {
             double q;
             if (i == 1) q = x * p1;
             else q = __builtin_fma(x, p1, -(kLegendreG.v[i] * p2));
+            p2 = p1;
+            p1 = q;
+            return q;
+        } else if (KIND == KIND_CHEBYSHEV) {
+            double q;
+            if (i == 1) q = (0.5 * x) * p1;   // t w, exactly
+            else q = __builtin_fma(x, p1, -p2);
             p2 = p1;
             p1 = q;
             return q;

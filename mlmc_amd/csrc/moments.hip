@@ -539,13 +539,13 @@ template <int KIND>
 __device__ __forceinline__ void split_export(const TermGen<KIND> &g, double *__restrict__ slot) {
     slot[0 * SPLIT_LANES] = g.x;
     slot[1 * SPLIT_LANES] = g.p1;
-    if (KIND == MLMC_LEGENDRE) slot[2 * SPLIT_LANES] = g.p2;
+    if (KIND == MLMC_LEGENDRE || KIND == KIND_CHEBYSHEV) slot[2 * SPLIT_LANES] = g.p2;
 }
 template <int KIND>
 __device__ __forceinline__ void split_import(TermGen<KIND> &g, const double *__restrict__ slot) {
     g.x = slot[0 * SPLIT_LANES];
     g.p1 = slot[1 * SPLIT_LANES];
-    g.p2 = KIND == MLMC_LEGENDRE ? slot[2 * SPLIT_LANES] : 0.0;
+    g.p2 = (KIND == MLMC_LEGENDRE || KIND == KIND_CHEBYSHEV) ? slot[2 * SPLIT_LANES] : 0.0;
     g.c1 = g.s1 = 0.0;
 }
 
@@ -604,7 +604,13 @@ __device__ __forceinline__ void split_head(const BasisParams &bp, const double *
             gf[q].init(keep ? tf : 0.0, w, bp);
             if (PAIR) gc[q].init(keep ? tc : 0.0, w, bp);
         }
-        if (T0 > 0) {      // second term window (terms [T0, T0 + HT + TT)): advance the recurrences without accumulating
+        if constexpr (KIND == KIND_CHEBYSHEV && T0 == 128) {   // second window: (T_127, T_126) by doubling, not by 128 steps
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+                gf[q].jump128();
+                if (PAIR) gc[q].jump128();
+            }
+        } else if (T0 > 0) {      // second term window (terms [T0, T0 + HT + TT)): advance the recurrences without accumulating
 #pragma unroll
             for (int i = 0; i < T0; ++i) {
 #pragma unroll
@@ -983,6 +989,12 @@ static int split_go(int op, const BasisParams &bp, const SegTable *tab, int tota
 constexpr int SPLIT_MEAN_HEAD_96 = 46, SPLIT_MEAN_HEAD_128 = 62;
 // second window (terms 128..255): the head walks 128 steps (4 instructions per pair and step) before its accumulating terms
 constexpr int SPLIT_MEAN_HEAD_W2 = 40;
+// The same for KIND_CHEBYSHEV, whose steps cost one FMA: per trip of two samples 8 instructions per accumulated term and pair (fma,
+// fma, sub, add; level 0: 4).  First window, balanced for pairs (the four pair levels are 5/6 of that launch's work):
+// 8 h + 50 = 8 (N - h) gives h = 60.9 of 128 and 44.9 of 96.  Second window, which only level 0 reaches (4 R - 3 terms): the
+// head starts from (T_127, T_126) by the doubling identities (TermGen::jump128, 27 instructions per value) instead of walking
+// 128 steps: 2 * 27 + 4 h + 50 = 4 (128 - h) gives h = 51.
+constexpr int SPLIT_CHEB_HEAD_96 = 45, SPLIT_CHEB_HEAD_128 = 61, SPLIT_CHEB_HEAD_W2 = 51;
 // n_split: terms of the instantiation -- 64 (mean + variance), 96 or 128 (mean only); t0 = 128: the second window (mean only)
 static int split_dispatch(int op, bool plain, const BasisParams &bp, int n_split, int t0, const SegTable *tab, int total_blocks, double *partials,
                           int64_t *pcounts, int *out) {
@@ -991,8 +1003,17 @@ static int split_dispatch(int op, bool plain, const BasisParams &bp, int n_split
      : n_split == 64 ? split_go<KIND, P, SPLIT_HEAD, 64 - SPLIT_HEAD, MLMC_SPLIT_WPS, true>(op, bp, tab, total_blocks, partials, pcounts, out)   \
      : n_split == 96 ? split_go<KIND, P, SPLIT_MEAN_HEAD_96, 96 - SPLIT_MEAN_HEAD_96, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out) \
                      : split_go<KIND, P, SPLIT_MEAN_HEAD_128, 128 - SPLIT_MEAN_HEAD_128, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out))
+#define MLMC_SPLIT_GO_CHEB(P)                                                                                                           \
+    (t0 == 128 ? split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_W2, 128 - SPLIT_CHEB_HEAD_W2, 2, false, 128>(op, bp, tab, total_blocks, partials, pcounts, out) \
+     : n_split == 96 ? split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_96, 96 - SPLIT_CHEB_HEAD_96, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out) \
+                     : split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_128, 128 - SPLIT_CHEB_HEAD_128, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out))
+    if (bp.kind == KIND_CHEBYSHEV) {
+        if (n_split == 64 && t0 == 0) return fail("moments: Chebyshev sums exist for the mean-only term-split kernels (65..256 terms)");
+        return plain ? MLMC_SPLIT_GO_CHEB(true) : MLMC_SPLIT_GO_CHEB(false);
+    }
     if (bp.kind == MLMC_LEGENDRE) return plain ? MLMC_SPLIT_GO(MLMC_LEGENDRE, true) : MLMC_SPLIT_GO(MLMC_LEGENDRE, false);
     return plain ? MLMC_SPLIT_GO(MLMC_MONOMIAL, true) : MLMC_SPLIT_GO(MLMC_MONOMIAL, false);
+#undef MLMC_SPLIT_GO_CHEB
 #undef MLMC_SPLIT_GO
 }
 
@@ -1012,12 +1033,14 @@ int flush_moments(mlmc_accum *a) {
     // instructions) -- for A/B runs.  Fourier, whose second pass would repeat the sincos, keeps one 64-term pass.
     // R <= 48 is one pass at two waves per SIMD; R > 64 uses 64-term passes.
     static const bool no_split = std::getenv("MLMC_HIP_NO_SPLIT") != nullptr;
-    const bool poly = bp.kind == MLMC_LEGENDRE || bp.kind == MLMC_MONOMIAL;
+    const bool cheb = bp.kind == KIND_CHEBYSHEV;      // inner accumulators of the linearised covariance only (api.hip, ensure_lin)
+    const bool poly = bp.kind == MLMC_LEGENDRE || bp.kind == MLMC_MONOMIAL || cheb;
     const bool poly64 = poly && R > 48 && R <= 64;
     // mean-only estimate of plain polynomial moments with 64 < R <= 128: ONE pass of the term-split kernel without the sums
     // of squares (k_moments_accum_split<..., SQ = false>)
-    const bool split_mean = poly && a->mean_only_plain && R > 64 && R <= 256 && !no_split;
+    const bool split_mean = poly && a->mean_only_plain && R > 64 && R <= 256 && (!no_split || cheb);
     const bool split = (poly64 && !no_split) || split_mean;
+    if (cheb && !split_mean) return fail("moments: Chebyshev sums exist for the mean-only term-split kernels (65..256 terms)");
     const int pass_terms = split_mean ? 128 : ((poly64 && !split) ? 32 : MAX_TERMS_PER_PASS);
     for (int t0 = 0; t0 < (sparse_spline ? 1 : R); t0 += pass_terms) {
         const int n_terms = (R - t0 < pass_terms) ? R - t0 : pass_terms;
@@ -1028,8 +1051,8 @@ int flush_moments(mlmc_accum *a) {
         bool plain = bp.kind != MLMC_IDENTITY && !bp.is_log && bp.is_clip;
         for (const PendingSeg &p : a->pending) plain = plain && p.mask == nullptr;
         if (split) {
-            static int occ_split[2][2][4];   // [Legendre | monomial][plain][64 | 96 | 128 terms | second window]; 0 = not asked yet
-            int &cached = occ_split[bp.kind == MLMC_LEGENDRE ? 0 : 1][plain ? 1 : 0][t0 ? 3 : (n_split == 64 ? 0 : (n_split == 96 ? 1 : 2))];
+            static int occ_split[3][2][4];   // [Legendre | monomial | Chebyshev][plain][64 | 96 | 128 terms | second window]; 0 = not asked yet
+            int &cached = occ_split[bp.kind == MLMC_LEGENDRE ? 0 : (cheb ? 2 : 1)][plain ? 1 : 0][t0 ? 3 : (n_split == 64 ? 0 : (n_split == 96 ? 1 : 2))];
             if (cached == 0)
                 if (int rc = split_dispatch(0, plain, bp, n_split, t0, nullptr, 0, nullptr, nullptr, &cached)) return rc;
             per_cu = cached;
@@ -1040,6 +1063,10 @@ int flush_moments(mlmc_accum *a) {
                 if (int rc = accum_dispatch(0, plain, bp, rt_sel, nullptr, 0, t0, nullptr, nullptr, &cached)) return rc;
             per_cu = cached;
         }
+        // the first-window Chebyshev kernels of unmasked clipped chunks hold 166 (61 + 67 terms) / 136 (45 + 51) VGPRs and would fit
+        // three workgroups per CU (masked 61 + 67: 189, second window: 182 -- two anyway); two, the occupancy the term split is built
+        // around, measured 2 % faster (three for the Legendre form: +3..5 %)
+        if (cheb && per_cu > 2) per_cu = 2;
         if (per_cu < 1) per_cu = 1;
         if (per_cu > 8) per_cu = 8;
         const int resident = rt().n_cu * per_cu;
