@@ -37,7 +37,7 @@ extern "C" {
                               *    mlmc_percentiles_rows, mlmc_bootstrap_weights, mlmc_bootstrap_create / _destroy / _reset / _accum /
                               *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var, mlmc_density_integrate_batch,
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
-                              *    mlmc_density_quantiles_kernel_time */
+                              *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -204,6 +204,33 @@ int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t
 int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
                                   const int32_t *levels, const double *const *fine, const double *const *coarse,
                                   const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *sums, double *sums_sq);
+
+/* ---- per-level convergence diagnostics of every component (level_diag.hip) -- added within 8 ----------------------------
+ * The statistics of the standard MLMC convergence tests (Giles' mlmc_test), per level l and component m.  A sample is kept when
+ * neither its fine nor (in a level with coarse samples) its coarse value is NaN -- each component on its own; +-inf is a value
+ * like any other.  With y = fl(f - c) (without coarse samples: y = f), M_k(x) = sum (x - mean x)^k over the kept samples and
+ * C_fc = sum (f - mean f)(c - mean c), the MLMC_DIAG_NSTAT statistics are, in this order,
+ *     mean_y, M2_y, M3_y, M4_y, mean_f, M2_f, mean_c, M2_c, C_fc
+ * Without coarse samples the last three are NaN; without a kept sample all nine are NaN; one kept sample gives the means as
+ * the values and every M as 0.
+ * A kept +-inf makes the means it enters +-inf (NaN where both signs, or inf - inf in y, meet), as estimate_mean gives them, and
+ * the central sums it enters NaN; the counts are not affected.
+ * Arguments and argument checks are those of mlmc_accum_estimate_multi_var without the bases ([M][n] DEVICE rows per chunk),
+ * except that M >= 1 is required; messages name this entry.  coarse[c] is NULL for a chunk without coarse samples and is not
+ * read at level 0; a level (above 0) whose non-empty chunks mix NULL and non-NULL coarse is an error.
+ * Outputs (host): n[l * M + m], n_rm[l * M + m], stats[(l * M + m) * MLMC_DIAG_NSTAT + s].  Two passes per chunk (means, then
+ * sums about them with the exact correction for the means' rounding: no cancellation at any offset of the data), fixed-order
+ * reductions, no floating-point atomics; the samples per workgroup depend on n alone, so a component's bits depend neither on
+ * M nor on its row, and the same chunks in the same order give the same bits.  The chunks of a level are merged in the order
+ * of the call with the arithmetic of mlmc_diag_merge.  Device scratch stays within 64 MiB plus 88 bytes per (chunk,
+ * component).  Synchronises once. */
+#define MLMC_DIAG_NSTAT 9
+int mlmc_level_diagnostics(int32_t M, int32_t n_levels, int32_t n_chunks, const int32_t *levels, const double *const *fine,
+                           const double *const *coarse, const int64_t *n_samples, int64_t *n, int64_t *n_rm, double *stats);
+/* The nine statistics of the union of two disjoint sample sets, a of na and b of nb samples, by the pairwise update formulas of
+ * Chan, Golub and LeVeque (mean, M2) and Pebay (M3, M4, co-moment).  Host arithmetic only: needs no device.  An empty side
+ * (count 0) returns the other side unchanged, bit for bit.  out may be a or b. */
+int mlmc_diag_merge(const double *a, int64_t na, const double *b, int64_t nb, double *out);
 
 /* ---- covariance between the components of a vector quantity ---------------------------------------------------------
  * An accumulator of the M x M level sums, per level l and kept sample k,

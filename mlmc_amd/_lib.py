@@ -83,6 +83,8 @@ SIGNATURES = {
                                             _vp]),
     "mlmc_accum_estimate_multi_var": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp]),
+    "mlmc_level_diagnostics": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mlmc_diag_merge": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp]),
     "mlmc_maxent_solve_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaxentOpts), _vp, _vp, _vp, _vp]),
     "mlmc_density_eval_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mlmc_density_integrate_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),

@@ -67,6 +67,24 @@ Runtime &rt();
 // the completion interrupt, whose wake-up (20-60 us, more from a deep CPU idle state) would dominate a 0.2 ms estimate.
 hipError_t wait_stream(hipStream_t st);
 
+// Device scratch of a one-call entry (moments_multi.hip, level_diag.hip): one allocation that grows only when a call needs more
+struct MultiWorkspace {
+    char *dev = nullptr;
+    size_t cap = 0;
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        MLMC_HIP_CHECK(wait_stream(rt().stream));
+        if (dev) (void)hipFree(dev);
+        dev = nullptr;
+        cap = 0;
+        MLMC_HIP_CHECK(hipMalloc((void **)&dev, bytes));
+        cap = bytes;
+        return 0;
+    }
+};
+
+inline size_t mm_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
 // ---- order statistics (select.hip, select_rows.hip) ----------------------------------------
 __device__ __forceinline__ unsigned long long order_key(double x) {
     unsigned long long u = (unsigned long long)__double_as_longlong(x);

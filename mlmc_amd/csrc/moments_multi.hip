@@ -273,23 +273,6 @@ static void launch_multi_var(dim3 grid, hipStream_t st, bool pair, int NWsel, co
     }
 }
 
-struct MultiWorkspace {
-    char *dev = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
-        MLMC_HIP_CHECK(wait_stream(rt().stream));
-        if (dev) (void)hipFree(dev);
-        dev = nullptr;
-        cap = 0;
-        MLMC_HIP_CHECK(hipMalloc((void **)&dev, bytes));
-        cap = bytes;
-        return 0;
-    }
-};
-
-static size_t mm_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
 // Argument checks of the per-component entries (`entry` names the entry in the messages).  On success bps holds the M
 // descriptors and n_max the longest chunk; `empty` is set when M == 0 (nothing to do).
 static int multi_args(const char *entry, int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,

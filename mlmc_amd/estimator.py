@@ -185,6 +185,22 @@ class Estimate:
         reg = self._all_moments_variance_regression(raw_vars.reshape(n_levels, -1), sim_steps).reshape(raw_vars.shape)
         return reg, self._sample_storage.get_n_ops()
 
+    def estimate_level_diagnostics(self):
+        """-> diagnostics.LevelDiagnostics: the MLMC convergence tests of the level hierarchy for EVERY scalar component of the
+        quantity (any qtype, scalar included; row order as construct_densities documents; no moments function needed), [L, M]
+        arrays: kurtosis and skewness of the level differences, mean and variance of the differences, of the fine and of the
+        coarse values, the fine / coarse correlation, the telescoping-consistency check between neighbouring levels, and
+        through `.rates()` / `.flags()` the decay rates alpha, beta, gamma and the levels that fail the checks.  Each
+        component is NaN-masked on its own.  Two device passes per stored chunk for all components
+        (quantity_estimate.level_diagnostics)."""
+        from . import diagnostics
+        n, _, stats = qe.level_diagnostics(self._quantity)
+        level_steps = np.squeeze(self._sample_storage.get_level_parameters())
+        n_ops = self._sample_storage.get_n_ops()
+        if n_ops is None or len(n_ops) != n.shape[0]:
+            n_ops = None                                   # the storage has no costs (for every level): gamma is NaN
+        return diagnostics.from_central_sums(n, stats, level_steps=level_steps, n_ops=n_ops)
+
     def _all_moments_variance_regression(self, raw_vars, sim_steps):
         """Per-moment regression of the level variances (reference: :87-93), all moments in ONE least-squares solve with
         several right-hand sides (the design matrix [1, log h, log^2 h] is the same for every moment)."""

@@ -1046,6 +1046,30 @@ def _component_level_sums(quantity, moments_fns):
     return n, n_rm, s, sp
 
 
+def level_diagnostics(quantity):
+    """Central sums of the MLMC convergence diagnostics of every scalar component of `quantity` (any qtype; no moments function):
+    per level and component the mean and the central sums of order 2..4 of the level differences, mean and second central sum of
+    the fine and of the coarse values and their co-moment (diagnostics.STAT_NAMES), each component NaN-masked on its own
+    (mask_nan_samples applied to the one component), two device passes per stored chunk for all components
+    (mlmc_level_diagnostics, mlmc_amd/csrc/level_diag.hip).
+    -> n, n_rm [L, M] int64, stats [L, M, 9] float64 (for diagnostics.from_central_sums)"""
+    with _estimate_lock:
+        return _level_diagnostics(quantity)
+
+
+def _level_diagnostics(quantity):
+    from .. import _lib
+    from .. import diagnostics
+    M = int(quantity.size())
+    n_levels, keep, args = _component_chunks(quantity, M, "level_diagnostics")
+    n = np.zeros((n_levels, M), dtype=np.int64)
+    n_rm = np.zeros((n_levels, M), dtype=np.int64)
+    stats = np.zeros((n_levels, M, diagnostics.N_STAT))
+    _lib.check(_lib.lib().mlmc_level_diagnostics(M, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm), _lib.ptr(stats)))
+    del keep
+    return n, n_rm, stats
+
+
 def component_statistics(n, s, sp):
     """Per-level and total statistics of per-component level sums (n [L, M], s / sp [L, M, R]), as estimate_mean gives them for
     each component alone: engine.level_stats per (level, component), mean = sum_l l_means, var = sum_l l_vars / n_l
