@@ -37,7 +37,8 @@ extern "C" {
                               *    mlmc_percentiles_rows, mlmc_bootstrap_weights, mlmc_bootstrap_create / _destroy / _reset / _accum /
                               *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var, mlmc_density_integrate_batch,
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
-                              *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge */
+                              *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
+                              *    mlmc_chebyshev_connection_table */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -183,6 +184,12 @@ int mlmc_accum_aux_kernel_time(mlmc_accum *a, double *ms, int64_t *launches, int
  * phi_i phi_j = sum_m c'_ijm T_m, (phi_i phi_j)^2 = sum_m c2'_ijm T_m, with c'_ijm = sum_k c_ijk a_km and the exact connection
  * P_k = sum_m a_km T_m folded in on the host in extended precision.  Same shapes and limits as 0 / 1; other values fail. */
 int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *out, int64_t out_len);
+
+/* The connection from Legendre to Chebyshev polynomials, T_m = sum_{k <= m} b_mk P_k for m, k < M <= 64: out[m * M + k], host
+ * arithmetic in extended precision, rounded once (no device needed).  b_00 = 1, b_0k = 0, b_mk = 0 unless k = m (mod 2), every row
+ * sums to one.  A covariance with variances of 49..64 Legendre moments takes the first 64 Chebyshev level sums of its pair levels from
+ * the Legendre difference sums its matrix kernel accumulates on the side (MLMC_HIP_LINEARIZE_ROWSUMS=0: from a full auxiliary pass). */
+int mlmc_chebyshev_connection_table(int32_t M, double *out, int64_t out_len);
 
 /* Mean-only level sums of a quantity of M components, each with ITS OWN moment functions (Estimate.construct_densities:
  * construct_density of every scalar component, estimator.py:304-331): bases[m] (m < M) are plain Legendre, monomial or Fourier

@@ -71,6 +71,7 @@ SIGNATURES = {
     "mlmc_accum_kernel_flops": (C.c_int, [_vp, _ip]),
     "mlmc_accum_aux_kernel_time": (C.c_int, [_vp, _dp, _ip, _ip]),
     "mlmc_linearization_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "mlmc_chebyshev_connection_table": (C.c_int, [C.c_int32, _vp, C.c_int64]),
     "mlmc_percentiles": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _ip, C.c_int]),
     "mlmc_percentiles_rows": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int]),
     "mlmc_maxent_solve": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_double, C.POINTER(MaxentOpts), _vp,

@@ -289,6 +289,27 @@ static void chebyshev_compose(const std::vector<ld> &c, int K, int R, std::vecto
         }
 }
 
+// The connection the other way, T_m = sum_{k <= m} b_mk P_k (k = m mod 2), in closed form from the same g_j = (2j - 1)!! / (2j)!!
+// (Alpert & Rokhlin 1991, the Chebyshev-to-Legendre matrix):  b_00 = 1,  b_mm = 1 / (2 g_m),
+//   b_mk = - m (k + 1/2) / ((m + k + 1) (m - k)) * g_((m - k - 2) / 2) / (n g_n),  n = (m + k) / 2,  k < m.
+// Diagonal positive, everything below it negative, every row sums to one, b_0k = delta_k0.  Every factor is O(1); extended
+// precision, rounded once.  out[m * M + k].
+static void chebyshev_connection(int M, std::vector<double> &out) {
+    std::vector<ld> g(M > 1 ? M : 1);
+    g[0] = 1.0L;
+    for (int j = 1; j < M; ++j) g[j] = g[j - 1] * (ld)(2 * j - 1) / (ld)(2 * j);
+    out.assign((size_t)M * M, 0.0);
+    out[0] = 1.0;
+    for (int m = 1; m < M; ++m) {
+        out[(size_t)m * M + m] = (double)(1.0L / (2.0L * g[m]));
+        for (int k = m - 2; k >= 0; k -= 2) {
+            const int n = (m + k) / 2;
+            const ld v = -((ld)m * ((ld)k + 0.5L)) / ((ld)(m + k + 1) * (ld)(m - k)) * g[(m - k - 2) / 2] / ((ld)n * g[n]);
+            out[(size_t)m * M + k] = (double)v;
+        }
+    }
+}
+
 bool product_table_chebyshev(int R, std::vector<double> &out) {
     std::vector<ld> c;
     legendre_products_ld(R, c);
@@ -323,6 +344,13 @@ static bool linearize_enabled() {
 // Chebyshev sums (A/B runs, tests).  Read when an accumulator is created.
 static bool linearize_chebyshev_enabled() {
     const char *e = std::getenv("MLMC_HIP_LINEARIZE_CHEB");
+    return !(e && e[0] == '0');
+}
+
+// MLMC_HIP_LINEARIZE_ROWSUMS=0: the pair levels' auxiliary pass walks all 2 R - 1 Chebyshev terms and the matrix kernel leaves no row
+// sums, as before they existed (A/B runs, tests).  Read when an accumulator is created.
+static bool linearize_rowsums_enabled() {
+    const char *e = std::getenv("MLMC_HIP_LINEARIZE_ROWSUMS");
     return !(e && e[0] == '0');
 }
 
@@ -551,6 +579,27 @@ static int lin_tables(int kind, int R, bool cheb, bool squares, LinTables **out)
     return 0;
 }
 
+// b_mk for M = 64 on the device, once per process; behind it the scales c_k, k < 64, of the matrix kernel's 64 Legendre terms
+// (P_k = c_k q_k as in mlmc_basis_create: the kernel evaluates all 64 terms whatever the size of the caller's basis)
+static int connection_table_device(double **out) {
+    static double *d_conn = nullptr;
+    if (!d_conn) {
+        std::vector<double> h;
+        chebyshev_connection(64, h);
+        ld c = 1.0L;
+        for (int i = 0; i < 64; ++i) {
+            if (i >= 1) c = c * (ld)(2 * i - 1) / (ld)(2 * i);
+            h.push_back((double)c);
+        }
+        double *d = nullptr;
+        MLMC_HIP_CHECK(hipMalloc(&d, sizeof(double) * h.size()));
+        MLMC_HIP_CHECK(hipMemcpy(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+        d_conn = d;
+    }
+    *out = d_conn;
+    return 0;
+}
+
 // An inner basis of `size` terms over the transform and keep thresholds of the caller's basis `b`.  cheb: Chebyshev polynomials
 // (KIND_CHEBYSHEV, which mlmc_basis_create does not accept: created as monomials -- unit scales -- and re-labelled).
 static int inner_basis_create(const mlmc_basis *b, int size, bool cheb, mlmc_basis **out) {
@@ -598,7 +647,18 @@ static int ensure_lin(mlmc_accum *a) {
             a->d_lin0_prod = t2->d_prod2;
         }
     }
+    if (!rc && a->cov_rows) {      // the first 64 sums of `lin` come from the matrix kernel's row sums
+        rc = connection_table_device(&a->d_conn);
+        if (!rc && hipMalloc(&a->d_rowsums, sizeof(double) * 64 * (size_t)a->n_levels * a->n_comp) != hipSuccess)
+            rc = fail("covariance: device allocation failed (row sums)");
+        if (!rc && hipMemsetAsync(a->d_rowsums, 0, sizeof(double) * 64 * (size_t)a->n_levels * a->n_comp, rt().stream) != hipSuccess)
+            rc = fail("covariance: memset failed (row sums)");
+        if (!rc) a->lin->first_term = 64;
+    }
     if (rc) {            // no half-built state: the accumulator goes on with all three Gram matrices
+        if (a->d_rowsums) (void)hipFree(a->d_rowsums);
+        a->d_rowsums = nullptr;
+        a->cov_rows = false;
         if (a->lin) mlmc_accum_destroy(a->lin);
         if (a->lin_basis) mlmc_basis_destroy(a->lin_basis);
         if (a->lin0) mlmc_accum_destroy(a->lin0);
@@ -691,6 +751,10 @@ int mlmc_accum_create(const mlmc_basis *b, int32_t n_levels, int32_t mode, int32
         // Legendre: the inner accumulators sum Chebyshev polynomials (ensure_lin); MLMC_HIP_NO_SPLIT=1 asks for the kernels without
         // the term split, which exist for the public families only
         a->lin_cheb = b->p.kind == MLMC_LEGENDRE && linearize_chebyshev_enabled() && std::getenv("MLMC_HIP_NO_SPLIT") == nullptr;
+        // 49..64 Legendre moments (the 64-term matrix kernel, 97..127 Chebyshev sums): the first 64 of them from the pair-level
+        // kernel's row sums.  With lin0 every chunk that reaches `lin` is a pair chunk of that kernel.
+        a->cov_rows = a->lin_cheb && a->lin0_eligible && a->R >= 49 && a->R <= 64 && a->RP == 64 && linearize_rowsums_enabled() &&
+                      cov_rows_available();
     }
     *out = a;
     return mlmc_accum_reset(a);
@@ -709,6 +773,7 @@ int mlmc_accum_reset(mlmc_accum *a) {
         a->xcov_pushes = 0;
     }
     a->lin_used = a->lin0_used = false;
+    if (a->d_rowsums) MLMC_HIP_CHECK(hipMemsetAsync(a->d_rowsums, 0, sizeof(double) * 64 * (size_t)a->n_levels * a->n_comp, st));
     a->lin_levels.assign(a->n_levels, 0);
     a->lin0_levels.assign(a->n_levels, 0);
     if (a->lin0)
@@ -726,7 +791,7 @@ void mlmc_accum_destroy(mlmc_accum *a) {
     if (a->lin0) mlmc_accum_destroy(a->lin0);
     if (a->lin0_basis) mlmc_basis_destroy(a->lin0_basis);         // (the coefficient tables are shared: lin_tables)
     void *ptrs[] = {a->d_state, a->d_partials, a->d_pcounts, a->d_stage_f, a->d_stage_c, a->d_mask, a->d_out, a->d_vals_f, a->d_vals_c, a->d_vals_tmp,
-                    a->d_shift};
+                    a->d_shift, a->d_rowparts, a->d_rowsums};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (a->h_out) (void)hipHostFree(a->h_out);
@@ -1044,6 +1109,16 @@ int mlmc_linearization_table(int32_t kind, int32_t R, int32_t squares, double *o
     } else {
         product_table(kind, R, t);
     }
+    std::memcpy(out, t.data(), sizeof(double) * t.size());
+    return 0;
+}
+
+int mlmc_chebyshev_connection_table(int32_t M, double *out, int64_t out_len) {
+    if (!out) return fail("mlmc_chebyshev_connection_table: null argument");
+    if (M < 1 || M > 64) return fail("mlmc_chebyshev_connection_table: size out of range (1 .. 64)");
+    if (out_len < (int64_t)M * M) return fail("mlmc_chebyshev_connection_table: output too small");
+    std::vector<double> t;
+    chebyshev_connection(M, t);
     std::memcpy(out, t.data(), sizeof(double) * t.size());
     return 0;
 }

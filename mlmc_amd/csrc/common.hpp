@@ -190,6 +190,15 @@ struct mlmc_accum {
     int64_t lin_min_n = 0;                // chunks with fewer samples keep all three Gram matrices on the matrix cores (the
                                           // extra launches of the auxiliary pass cost more than they save); sums are additive
     bool lin_used = false;                // a chunk of this estimate went the linearised way
+    // Legendre, 49..64 moments, Chebyshev sums: the pair-level variance kernel also leaves the row sums of its 64 Legendre
+    // differences (cov.hip, k_cov_accum_t4_rows); the inner accumulator `lin` then sums terms 64 .. 2 R - 2 only (first_term) and
+    // k_cov_lin_mean forms the first 64 Chebyshev sums from them with the connection T_m = sum_k b_mk P_k (MLMC_HIP_LINEARIZE_ROWSUMS=0:
+    // the full auxiliary pass)
+    bool cov_rows = false;
+    double *d_rowparts = nullptr; size_t rowparts_cap = 0;   // [n_comp][workgroups][64] of one launch
+    double *d_rowsums = nullptr;          // [n_levels][n_comp][64]: sum of q_k(f) - q_k(c), k < 64 (scaled like the basis: scale_c)
+    double *d_conn = nullptr;             // [64][64] b_mk, then [64] c_k: P_k = c_k q_k (shared, not owned)
+    int first_term = 0;                   // MOMENTS (inner accumulator): the terms below come from elsewhere, the passes start here
     std::vector<PendingSeg> pending;   // MOMENTS: chunks gathered into one launch (flushed by finalize / conflicts)
     // component covariance (mlmc_xcov_create, xcov.hip): no basis; totals [n_levels][2][M * M] (s, sp), K = M * M
     bool xcov = false;
@@ -211,6 +220,7 @@ int launch_moments_finalize(mlmc_accum *a);
 int launch_cov_accum(mlmc_accum *a, int level, int comp, const double *d_f, const double *d_c, const uint8_t *d_mask,
                      int64_t n, bool count, int gram_mode, int ncomp = 1);
 int launch_cov_finalize(mlmc_accum *a);
+bool cov_rows_available();             // this build's 64-term pair kernel can leave the row sums of its differences
 // xcov.hip
 constexpr int XCOV_MAX_M = 1024;   // components of a component-covariance accumulator
 constexpr int MODE_XCOV = 2;   // internal mode of a component-covariance accumulator (not a mode of mlmc_accum_create)

@@ -494,12 +494,25 @@ __host__ __device__ constexpr int xsym_n(int kind, int w) { return kind == 2 ? b
 __host__ __device__ constexpr int xsym_i(int kind, int w, int t) { return kind == 2 ? bsym_i(w, t) : (kind == 1 ? psym_i(w, t) : sym_i(w, t)); }
 __host__ __device__ constexpr int xsym_j(int kind, int w, int t) { return kind == 2 ? bsym_j(w, t) : (kind == 1 ? psym_j(w, t) : sym_j(w, t)); }
 
-template <int KIND, bool PAIR, int MODE, int BD, int W>
+// RS (2 x 2-block body of a pair level only): the waves on the diagonal also sum the differences d of the row blocks they hold --
+// wave 0 terms 0..31, wave 3 terms 32..63, one add per 16-term block and k-step -- and leave the 64 row sums
+// sum_pairs (q_k(f) - q_k(c)) of the workgroup in `rowparts`: the first 64 extended sums of the linearised mean (k_cov_lin_mean).
+// MLMC_COV_ROWS_WAVES (A/B): 1 = wave 1 block 0 and wave 2 blocks 1..3 (differences they form anyway for their d.s operands),
+// 2 = wave 2 all four blocks (block 0 costs it two more LDS reads and a subtraction).
+#ifndef MLMC_COV_ROWS_WAVES
+#define MLMC_COV_ROWS_WAVES 0
+#endif
+__host__ __device__ constexpr int cov_rows_mask(int w) {
+    return MLMC_COV_ROWS_WAVES == 0 ? (w == 0 ? 3 : (w == 3 ? 12 : 0))
+         : MLMC_COV_ROWS_WAVES == 1 ? (w == 1 ? 1 : (w == 2 ? 14 : 0))
+                                    : (w == 2 ? 15 : 0);
+}
+template <int KIND, bool PAIR, int MODE, int BD, int W, bool RS = false>
 __device__ __forceinline__ void cov_t4_body(const BasisParams &bp, 
                                             const double *__restrict__ fine, const double *__restrict__ coarse,
                                             const uint8_t *__restrict__ mask, int64_t n, double *__restrict__ partials,
                                             int64_t *__restrict__ pcounts, double *__restrict__ lds_f,
-                                            double *__restrict__ lds_c, int (*ldc)[2]) {
+                                            double *__restrict__ lds_c, int (*ldc)[2], double *__restrict__ rowparts = nullptr) {
     constexpr int NT = 64;
     constexpr int TA = 64 * BD;
     constexpr int N_EVAL = TA + NT;
@@ -515,7 +528,10 @@ __device__ __forceinline__ void cov_t4_body(const BasisParams &bp,
     constexpr int NFULL = (MODE == 0 && PAIR) ? 2 : (((MODE == 2 || MODE == 3) && PAIR) ? 1 : 0);     // G0 (and G1): full row W
     constexpr int GV = MODE == 3 ? 0 : 1;          // accumulator set of G1
     constexpr int NSYMM = (MODE == 0 && !PAIR) ? 2 : 1;    // symmetric matrices handled through the tile list
+    static_assert(!RS || BLK, "row sums: 2 x 2-block body of a pair level");
+    constexpr int RSM = RS ? cov_rows_mask(W) : 0;          // the 16-term blocks whose differences this wave sums
     const int lane = threadIdx.x & 63;
+    double rsum[4] = {0.0, 0.0, 0.0, 0.0};
 
     v4f64 accf[NFULL > 0 ? NFULL : 1][4];
     v4f64 accs[NSYMM][3];
@@ -650,6 +666,9 @@ __device__ __forceinline__ void cov_t4_body(const BasisParams &bp,
 #pragma unroll
                 for (int J = 0; J < 4; ++J) ds[J] = d[J] * sm[J];       // only the ones the tile list names survive
 #pragma unroll
+                for (int J = 0; J < 4; ++J)
+                    if ((RSM >> J) & 1) rsum[J] += d[J];
+#pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     const double dr2 = d[RA + r] * d[RA + r];
 #pragma unroll
@@ -724,6 +743,13 @@ __device__ __forceinline__ void cov_t4_body(const BasisParams &bp,
     }
 #endif
 
+    // the four lane groups hold the k-steps' samples 0..3 of every term: added in the order 0, 1, 2, 3
+#pragma unroll
+    for (int J = 0; J < 4; ++J)
+        if ((RSM >> J) & 1) {
+            const double v1 = __shfl(rsum[J], (lane & 15) + 16, 64), v2 = __shfl(rsum[J], (lane & 15) + 32, 64), v3 = __shfl(rsum[J], (lane & 15) + 48, 64);
+            if (lane < 16) rowparts[(int64_t)blockIdx.x * 64 + 16 * J + lane] = ((rsum[J] + v1) + v2) + v3;
+        }
     // ---- partial tiles: one row per block, columns [g][row][col]; symmetric tiles are mirrored here ----
     constexpr int NGOUT = cov_ng(MODE);
     double *__restrict__ prow = partials + (int64_t)blockIdx.x * (NGOUT * NT * NT);
@@ -830,16 +856,61 @@ __global__ __launch_bounds__(256, COV_T4_WGS) void k_cov_accum_t4(BasisParams bp
     }
 }
 
+// The pair-level variance kernel of 64 Legendre terms with the row sums of the differences (cov_t4_body: RS); a kernel of its
+// own, so that k_cov_accum_t4 stays the code it was.  rowparts: [component][workgroup][64].
+#if MLMC_COV_BLK22 && MLMC_COV_T4_BATCH == 32
+#define MLMC_COV_HAVE_ROWS 1
+template <int KIND>
+__global__ __launch_bounds__(256, COV_T4_WGS) void k_cov_accum_t4_rows(BasisParams bp, const double *__restrict__ fine,
+                                                              const double *__restrict__ coarse, const uint8_t *__restrict__ mask,
+                                                              int64_t n, double *__restrict__ partials,
+                                                              int64_t *__restrict__ pcounts, double *__restrict__ rowparts) {
+    __shared__ __attribute__((aligned(16))) double lds_f[64 * (COV_T4_BATCH + MLMC_COV_B128_PAD)];
+    __shared__ __attribute__((aligned(16))) double lds_c[64 * (COV_T4_BATCH + MLMC_COV_B128_PAD)];
+    __shared__ int ldc[2][2];
+    fine += (int64_t)blockIdx.y * n;
+    coarse += (int64_t)blockIdx.y * n;
+    partials += (int64_t)blockIdx.y * gridDim.x * (cov_ng(3) * 64 * 64);
+    rowparts += (int64_t)blockIdx.y * gridDim.x * 64;
+    if (blockIdx.y) pcounts = nullptr;
+    switch (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) {      // (scalar branch: see k_cov_accum_t4)
+        case 0: cov_t4_body<KIND, true, 3, 0, 0, true>(bp, fine, coarse, mask, n, partials, pcounts, lds_f, lds_c, ldc, rowparts); break;
+        case 1: cov_t4_body<KIND, true, 3, 0, 1, true>(bp, fine, coarse, mask, n, partials, pcounts, lds_f, lds_c, ldc, rowparts); break;
+        case 2: cov_t4_body<KIND, true, 3, 0, 2, true>(bp, fine, coarse, mask, n, partials, pcounts, lds_f, lds_c, ldc, rowparts); break;
+        default: cov_t4_body<KIND, true, 3, 0, 3, true>(bp, fine, coarse, mask, n, partials, pcounts, lds_f, lds_c, ldc, rowparts); break;
+    }
+}
+#endif
+
 // totals[g][row][col] (leading dimension RP) += sum over partial rows, fixed order.  16 columns per workgroup (one 128-byte
 // line of every partial row), 64 row groups: a three-Gram 16 x 16 tile set already gives 48 workgroups (64 columns per
 // workgroup left a 24-component quantity of small chunks waiting on 12 of them).
 __global__ __launch_bounds__(1024) void k_reduce_cov(const double *__restrict__ partials, int nrows, int NT, int NG, int RP,
                                                     int roff, int coff, double *__restrict__ totals, int64_t comp_stride,
                                                     int mirror, const int64_t *__restrict__ pcounts, int nblocks,
-                                                    int64_t *__restrict__ counts) {
+                                                    int64_t *__restrict__ counts, const double *__restrict__ rowparts = nullptr,
+                                                    double *__restrict__ rowsums = nullptr) {
     __shared__ double lds[64][17];
     const int c = threadIdx.x & 15, g = threadIdx.x >> 4;
     const int width = NG * NT * NT;
+    const int n_col_groups = (width + 15) / 16;
+    // four more workgroups behind the tiles' (rowparts): the launch's 64 row sums [component][workgroup][64], the same fixed order,
+    // added to the level's sums rowsums[component][64]
+    if (rowparts && (int)blockIdx.x >= n_col_groups && (int)blockIdx.x < n_col_groups + 4) {
+        const int col = ((int)blockIdx.x - n_col_groups) * 16 + c;
+        rowparts += (int64_t)blockIdx.y * nrows * 64;
+        double acc = 0.0;
+        for (int b = g; b < nrows; b += 64) acc += rowparts[(int64_t)b * 64 + col];
+        lds[g][c] = acc;
+        __syncthreads();
+        if (g == 0) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 64; ++k) v += lds[k][c];
+            rowsums[(int64_t)blockIdx.y * 64 + col] += v;
+        }
+        return;
+    }
     if (pcounts && blockIdx.x == gridDim.x - 1) {      // one more workgroup: the sample counts of the launch (exact integer sums)
         if (blockIdx.y == 0 && threadIdx.x < 64) {
             int64_t a = 0, b = 0;
@@ -1148,6 +1219,14 @@ static int cov_tiles_per_sample(int T, bool diagonal, bool pair, int gram_mode) 
     return full;
 }
 
+bool cov_rows_available() {
+#ifdef MLMC_COV_HAVE_ROWS
+    return true;
+#else
+    return false;
+#endif
+}
+
 int launch_cov_accum(mlmc_accum *a, int level, int comp, const double *d_f, const double *d_c, const uint8_t *d_mask,
                      int64_t n, bool count, int gram_mode, int ncomp) {
     // ncomp > 1: components comp .. comp + ncomp - 1 of a vector quantity ([M][n] arrays) in ONE launch (grid.y)
@@ -1200,6 +1279,18 @@ int launch_cov_accum(mlmc_accum *a, int level, int comp, const double *d_f, cons
                         : launch_cov_kind<KIND, 0>(bp, T, bi, bj, pair, blocks, ncomp, d_f, d_c, d_mask, n, R, a->d_partials, pc)
             if (gram_mode == 3 && bp.kind != MLMC_LEGENDRE && bp.kind != MLMC_MONOMIAL)
                 return fail("covariance: the variance-only pass exists for the polynomial families");
+            // the chunk's first 64 extended sums from the matrix kernel (api.hip, ensure_lin: Legendre, 49..64 moments)
+            const bool rows = a->cov_rows && gram_mode == 3 && pair;
+            if (rows) {
+#ifdef MLMC_COV_HAVE_ROWS
+                if (int rce = ensure((void **)&a->d_rowparts, &a->rowparts_cap, sizeof(double) * (size_t)blocks * 64 * ncomp)) return rce;
+                hipLaunchKernelGGL((k_cov_accum_t4_rows<MLMC_LEGENDRE>), dim3(blocks, ncomp), dim3(256), 0, st, bp, d_f, d_c, d_mask, n, a->d_partials, pc, a->d_rowparts);
+                MLMC_HIP_CHECK(hipGetLastError());
+                rc = 0;
+#else
+                return fail("covariance: this build has no row sums in the matrix kernel");
+#endif
+            } else
             switch (bp.kind) {
                 case MLMC_LEGENDRE: MLMC_COV_DISPATCH(MLMC_LEGENDRE); break;
                 case MLMC_MONOMIAL: MLMC_COV_DISPATCH(MLMC_MONOMIAL); break;
@@ -1216,9 +1307,11 @@ int launch_cov_accum(mlmc_accum *a, int level, int comp, const double *d_f, cons
                 a->alg_bytes += (int64_t)n * (pair ? 16 : 8) * ncomp;
                 a->mfma_flops += (int64_t)512 * cov_tiles_per_sample(T, bi == bj, pair, gram_mode) * n * ncomp;
             }
-            hipLaunchKernelGGL(k_reduce_cov, dim3((unsigned)((width + 15) / 16) + (do_count ? 1u : 0u), ncomp), dim3(1024), 0, st, a->d_partials,
+            hipLaunchKernelGGL(k_reduce_cov, dim3((unsigned)((width + 15) / 16) + (rows ? 4u : 0u) + (do_count ? 1u : 0u), ncomp), dim3(1024), 0, st, a->d_partials,
                                blocks * n_slices, NT, NG, a->RP, 64 * bi, 64 * bj, totals, a->int_width, (!pair && bi != bj) ? 1 : 0,
-                               do_count ? a->d_pcounts : (const int64_t *)nullptr, blocks, a->d_counts + 2 * (int64_t)level);
+                               do_count ? a->d_pcounts : (const int64_t *)nullptr, blocks, a->d_counts + 2 * (int64_t)level,
+                               rows ? a->d_rowparts : (const double *)nullptr,
+                               rows ? a->d_rowsums + ((int64_t)level * a->n_comp + comp) * 64 : (double *)nullptr);
             MLMC_HIP_CHECK(hipGetLastError());
         }
     return 0;
@@ -1270,6 +1363,9 @@ struct LinSrc {
     const double *scale;     // [K]: true value of sum k = scale[k] * totals[k]
     int64_t width;
     int K, squares;
+    // rowsums: sums k < 64 of this source are not in `totals` -- they follow from the matrix kernel's row sums of Legendre differences
+    // (row stride 64, scaled like the basis: pscale) through the connection T_m = sum_{k <= m} b_mk P_k, conn[m][k] (parity: k = m mod 2)
+    const double *rowsums, *conn, *pscale;
 };
 struct LinJob {
     double *out;             // out_s or out_sp
@@ -1292,7 +1388,16 @@ __global__ void k_cov_lin_mean(LinJobs jobs, int R, int parity_step) {
         __syncthreads();                // the previous source's sums have been used
         for (int q = threadIdx.x; q < LIN_LC * K; q += blockDim.x) {
             const int l = q / K, k = q % K;
-            m_s[q] = l < jb.n_rows ? sr.scale[k] * sr.totals[(int64_t)jb.row[l] * sr.width + k] : 0.0;
+            double v = 0.0;
+            if (l < jb.n_rows) {
+                if (sr.rowsums && k < 64) {          // fixed order: ascending Legendre degree
+                    const double *__restrict__ rs = sr.rowsums + (int64_t)jb.row[l] * 64;
+                    for (int j = k & 1; j <= k; j += 2) v = __builtin_fma(sr.conn[k * 64 + j], sr.pscale[j] * rs[j], v);
+                } else {
+                    v = sr.scale[k] * sr.totals[(int64_t)jb.row[l] * sr.width + k];
+                }
+            }
+            m_s[q] = v;
         }
         __syncthreads();
         if (idx < RR) {
@@ -1350,6 +1455,7 @@ int launch_cov_finalize(mlmc_accum *a) {
     if (lin) {
         src1.prod = a->d_lin_prod; src1.totals = a->lin->d_totals; src1.scale = a->lin_basis->d_scale;
         src1.width = a->lin->int_width; src1.K = a->lin_K; src1.squares = 0;
+        if (a->cov_rows) { src1.rowsums = a->d_rowsums; src1.conn = a->d_conn; src1.pscale = a->d_conn + 64 * 64; }
         if (a->lin_K > max_K) max_K = a->lin_K;
     }
     LinJobs jobs;

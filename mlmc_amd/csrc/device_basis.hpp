@@ -116,6 +116,20 @@ struct TermGen {
         p2 = __builtin_fma(x, c, -a) * w;
         p1 = c * w;
     }
+    // the same for next(0) .. next(63): six doublings to (T_64, T_65), two steps back to (T_63, T_62) -- 24 instructions
+    __device__ __forceinline__ void jump64() {
+        const double w = p1, t = 0.5 * x;
+        double a = t, b = __builtin_fma(x, t, -1.0);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double a2 = 2.0 * a;
+            b = __builtin_fma(a2, b, -t);
+            a = __builtin_fma(a2, a, -1.0);
+        }
+        const double c = __builtin_fma(x, a, -b);
+        p2 = __builtin_fma(x, c, -a) * w;
+        p1 = c * w;
+    }
     // must be called with i = 0, 1, 2, ... in order
     __device__ __forceinline__ double next(int i) {
         if (i == 0) return p1;

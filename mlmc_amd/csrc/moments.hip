@@ -610,6 +610,12 @@ __device__ __forceinline__ void split_head(const BasisParams &bp, const double *
                 gf[q].jump128();
                 if (PAIR) gc[q].jump128();
             }
+        } else if constexpr (KIND == KIND_CHEBYSHEV && T0 == 64) {    // terms from 64 on (the first 64 sums come from elsewhere)
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+                gf[q].jump64();
+                if (PAIR) gc[q].jump64();
+            }
         } else if (T0 > 0) {      // second term window (terms [T0, T0 + HT + TT)): advance the recurrences without accumulating
 #pragma unroll
             for (int i = 0; i < T0; ++i) {
@@ -995,6 +1001,13 @@ constexpr int SPLIT_MEAN_HEAD_W2 = 40;
 // head starts from (T_127, T_126) by the doubling identities (TermGen::jump128, 27 instructions per value) instead of walking
 // 128 steps: 2 * 27 + 4 h + 50 = 4 (128 - h) gives h = 51.
 constexpr int SPLIT_CHEB_HEAD_96 = 45, SPLIT_CHEB_HEAD_128 = 61, SPLIT_CHEB_HEAD_W2 = 51;
+// Terms 64..126 alone (mlmc_accum::first_term = 64: the pair levels of a covariance of 49..64 Legendre moments, whose first 64 sums
+// come from the matrix kernel's row sums): the head starts from (T_63, T_62) by TermGen::jump64, 24 instructions per value and four
+// values per trip of two pairs: 4 * 24 + 8 h + 50 = 8 (63 - h) gives h = 22.4.
+#ifndef MLMC_SPLIT_CHEB_HEAD_T64
+#define MLMC_SPLIT_CHEB_HEAD_T64 22
+#endif
+constexpr int SPLIT_CHEB_HEAD_T64 = MLMC_SPLIT_CHEB_HEAD_T64;
 // n_split: terms of the instantiation -- 64 (mean + variance), 96 or 128 (mean only); t0 = 128: the second window (mean only)
 static int split_dispatch(int op, bool plain, const BasisParams &bp, int n_split, int t0, const SegTable *tab, int total_blocks, double *partials,
                           int64_t *pcounts, int *out) {
@@ -1005,10 +1018,12 @@ static int split_dispatch(int op, bool plain, const BasisParams &bp, int n_split
                      : split_go<KIND, P, SPLIT_MEAN_HEAD_128, 128 - SPLIT_MEAN_HEAD_128, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out))
 #define MLMC_SPLIT_GO_CHEB(P)                                                                                                           \
     (t0 == 128 ? split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_W2, 128 - SPLIT_CHEB_HEAD_W2, 2, false, 128>(op, bp, tab, total_blocks, partials, pcounts, out) \
+     : t0 == 64 ? split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_T64, 63 - SPLIT_CHEB_HEAD_T64, 2, false, 64>(op, bp, tab, total_blocks, partials, pcounts, out) \
      : n_split == 96 ? split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_96, 96 - SPLIT_CHEB_HEAD_96, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out) \
                      : split_go<KIND_CHEBYSHEV, P, SPLIT_CHEB_HEAD_128, 128 - SPLIT_CHEB_HEAD_128, 2, false>(op, bp, tab, total_blocks, partials, pcounts, out))
     if (bp.kind == KIND_CHEBYSHEV) {
         if (n_split == 64 && t0 == 0) return fail("moments: Chebyshev sums exist for the mean-only term-split kernels (65..256 terms)");
+        if (t0 == 64 && n_split != 63) return fail("moments: the Chebyshev pass from term 64 on covers 63 terms");
         return plain ? MLMC_SPLIT_GO_CHEB(true) : MLMC_SPLIT_GO_CHEB(false);
     }
     if (bp.kind == MLMC_LEGENDRE) return plain ? MLMC_SPLIT_GO(MLMC_LEGENDRE, true) : MLMC_SPLIT_GO(MLMC_LEGENDRE, false);
@@ -1042,17 +1057,20 @@ int flush_moments(mlmc_accum *a) {
     const bool split = (poly64 && !no_split) || split_mean;
     if (cheb && !split_mean) return fail("moments: Chebyshev sums exist for the mean-only term-split kernels (65..256 terms)");
     const int pass_terms = split_mean ? 128 : ((poly64 && !split) ? 32 : MAX_TERMS_PER_PASS);
-    for (int t0 = 0; t0 < (sparse_spline ? 1 : R); t0 += pass_terms) {
+    // first_term = 64 (Chebyshev sums of 65..127 terms whose first 64 come from elsewhere): ONE pass over terms 64..126
+    if (a->first_term && !(a->first_term == 64 && cheb && split_mean && R > 64 && R <= 127))
+        return fail("moments: a first term of 64 exists for Chebyshev sums of 65..127 terms");
+    for (int t0 = a->first_term; t0 < (sparse_spline ? 1 : R); t0 += pass_terms) {
         const int n_terms = (R - t0 < pass_terms) ? R - t0 : pass_terms;
-        const int n_split = split_mean ? ((t0 == 0 && R <= 96) ? 96 : 128) : 64;
+        const int n_split = split_mean ? (t0 == 64 ? 63 : ((t0 == 0 && R <= 96) ? 96 : 128)) : 64;
         const int rt_sel = sparse_spline ? R : (split ? n_split : pick_rt(bp.kind, n_terms, t0));
         const int width = 2 * rt_sel;
         int per_cu = 4;
         bool plain = bp.kind != MLMC_IDENTITY && !bp.is_log && bp.is_clip;
         for (const PendingSeg &p : a->pending) plain = plain && p.mask == nullptr;
         if (split) {
-            static int occ_split[3][2][4];   // [Legendre | monomial | Chebyshev][plain][64 | 96 | 128 terms | second window]; 0 = not asked yet
-            int &cached = occ_split[bp.kind == MLMC_LEGENDRE ? 0 : (cheb ? 2 : 1)][plain ? 1 : 0][t0 ? 3 : (n_split == 64 ? 0 : (n_split == 96 ? 1 : 2))];
+            static int occ_split[3][2][5];   // [Legendre | monomial | Chebyshev][plain][64 | 96 | 128 terms | second window | from term 64]; 0 = not asked yet
+            int &cached = occ_split[bp.kind == MLMC_LEGENDRE ? 0 : (cheb ? 2 : 1)][plain ? 1 : 0][t0 == 64 ? 4 : (t0 ? 3 : (n_split == 64 ? 0 : (n_split == 96 ? 1 : 2)))];
             if (cached == 0)
                 if (int rc = split_dispatch(0, plain, bp, n_split, t0, nullptr, 0, nullptr, nullptr, &cached)) return rc;
             per_cu = cached;

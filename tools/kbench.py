@@ -6,6 +6,8 @@
 CASE = mode:R[:basis[:levels[:flags]]]   mode in {mom, cov};  basis in {leg, mono, four, spline};  levels = number of levels
        (level 0 has no coarse samples; "0" = one level-0 launch alone, "p" = one pair level alone);  flags: m = mean only
        e.g.  cov:64:leg:5   cov:64:leg:5:m   mom:127:leg:5   cov:128:spline:1:m
+       cov:64:leg:p --libs rows=mlmc_amd/libmlmc_hip.so,full=mlmc_amd/libmlmc_hip.so@MLMC_HIP_LINEARIZE_ROWSUMS=0
+             one pair level: "aux ms" is its auxiliary launch, terms 64..126 from the doubled start against all 127 terms
 Prints the HIP-event kernel time per estimate (mlmc_accum_kernel_time) and the wall time per estimate, best of `rounds`
 child processes per library.  Libraries alternate (MLMC_HIP_LIB) so that the variants see the same box in the same state;
 "path@VAR=VAL" runs the same library under an environment switch."""
