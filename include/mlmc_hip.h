@@ -38,7 +38,7 @@ extern "C" {
                               *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var, mlmc_density_integrate_batch,
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
-                              *    mlmc_chebyshev_connection_table */
+                              *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -461,6 +461,21 @@ int mlmc_bootstrap_finalize(mlmc_bootstrap *bs, int64_t *n_out, double *s_out, d
 /* With timing enabled (mlmc_init flags bit 0): HIP-event ms of the contraction launches (keep bytes, contraction, reduction) and of
  * the RNG launches (tile counts, weights), and the executed v_mfma_f64_16x16x4_f64 flops, since create or the previous call. */
 int mlmc_bootstrap_kernel_time(mlmc_bootstrap *bs, double *ms_contract, double *ms_rng, int64_t *mfma_flops);
+/* Per-component bootstrap -- added within 8.  A handle for M components with K moments each, component m under bases[m]: plain
+ * Legendre, monomial or Fourier members of ONE family, no transform, size >= K, each with its own domain, log, x_lo / x_hi and
+ * safe_eval (the rules and messages of mlmc_accum_estimate_multi; they name this entry and the component).  K in 1 .. 512,
+ * M in 1 .. 65535; there is no column cap, components run in groups of at most 2048 columns.  Device state: the totals
+ * [n_levels][B][M (2 K + 1)] doubles (refused above 2 GiB), the 64 MiB of scratch and at most max(8 MiB, 4096 M) keep bytes.
+ * The bases must outlive the handle.  mlmc_bootstrap_accum / _reset / _destroy / _kernel_time serve the handle unchanged
+ * (fine / coarse: DEVICE [M][n]; the weights are those of mlmc_bootstrap_weights); mlmc_bootstrap_finalize refuses it. */
+int mlmc_bootstrap_create_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int64_t B,
+                                mlmc_bootstrap **out);
+/* Wait for the stream and write (host) n_out [B][n_levels][M], s_out / sp_out [B][n_levels][M * K] (row m * K + k):
+ * n = sum_i w_bi keep_im, s = sum_i w_bi keep_im d_imk, sp = sum_i w_bi keep_im d_imk^2 with d_imk = phi_k(fine_im) - phi_k(coarse_im)
+ * (level 0: phi_k(fine_im)) under bases[m], and keep_im the mask mlmc_accum_push applies to a one-component chunk of row m: a
+ * NaN or an out-of-domain value of component m drops the sample for component m alone.  The counts are exact.  Refuses a handle
+ * of mlmc_bootstrap_create.  The totals stay (reset to start over). */
+int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *bs, int64_t *n_out, double *s_out, double *sp_out);
 
 /* ---- synthetic samples in HBM (mlmc/sim/synth_simulation.py:37-46,75-131; seeding mlmc/sampling_pool.py:75-84; sample
  * ids mlmc/sampler.py:120) -------------------------------------------------------------------------------------------

@@ -110,6 +110,8 @@ SIGNATURES = {
     "mlmc_bootstrap_accum": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int64, _vp, C.c_uint64, C.c_uint32]),
     "mlmc_bootstrap_finalize": (C.c_int, [_vp, _vp, _vp, _vp]),
     "mlmc_bootstrap_kernel_time": (C.c_int, [_vp, _dp, _dp, _ip]),
+    "mlmc_bootstrap_create_multi": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_vp)]),
+    "mlmc_bootstrap_finalize_multi": (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 _lock = threading.Lock()

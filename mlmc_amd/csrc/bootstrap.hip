@@ -22,6 +22,9 @@
 // (k_bs_contract: grid (512-sample slice, 64-replicate tile, 16 JT-column block), partial rows per workgroup) and a fixed-order
 // reduction into the level totals (k_bs_reduce).  A replicate's sums therefore do not depend on B, and runs are bit-identical.
 // Scratch (tile counts, slab, partials, keep bytes) stays below 64 MiB; the totals [L][B][2 M R] are the size of the result.
+//
+// Per-component route (mlmc_bootstrap_create_multi, Estimate.est_bootstrap_components): one basis and one mask per component, the
+// same weights; k_bs_keep_multi / k_bs_contract_multi / k_bs_reduce_multi below, components in groups of at most 2048 columns.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -245,6 +248,135 @@ __global__ __launch_bounds__(256) void k_bs_reduce(const double *__restrict__ pa
     }
 }
 
+// ---- per-component bootstrap (mlmc_bootstrap_create_multi): every component under its own basis and its own mask ------------
+// Column layout of a group of components: component m owns K + 1 columns, m (K + 1) = its keep flag (1 for a kept sample),
+// m (K + 1) + 1 + k = d_k.  The flag column rides through the same MFMAs: sum w keep is a sum of integers below 2^53, exact
+// in fp64 in any order, so the kept count of every (replicate, component) comes out as an exact integer with the sums.
+
+// keep byte of component m at samples i0 .. i0 + nr - 1, keep[m * ldk + i]: the fine and the coarse value pass component m's own
+// transform (moments_multi.hip: the rule of a one-component chunk).  grid (sample blocks, components)
+__global__ __launch_bounds__(256) void k_bs_keep_multi(const BasisParams *__restrict__ tab, const double *__restrict__ f,
+                                                       const double *__restrict__ c, int64_t n, int M, int64_t i0, int64_t nr,
+                                                       int64_t ldk, uint8_t *__restrict__ keep) {
+    for (int m = blockIdx.y; m < M; m += gridDim.y) {
+        const BasisParams bp = tab[m];
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
+            bool k1, k2 = true;
+            transform_value(bp, f[(int64_t)m * n + i0 + i], k1);
+            if (c) transform_value(bp, c[(int64_t)m * n + i0 + i], k2);
+            keep[(int64_t)m * ldk + i] = (k1 && k2) ? 1 : 0;
+        }
+    }
+}
+
+// k_bs_contract for a group of M components with K moments each (fine / coarse / tab / keep point at the group's first
+// component): same grid, same LDS plan and bank pattern.  The Phi phase takes the BasisParams of a column's component from the
+// table (a wave handles one component per trip: KB = 64 samples), and leaves the K + 1 columns of a component at 0 for the
+// samples that component drops.  A column block may straddle components.  Partial rows [64][2 JB] per workgroup; the sum of
+// squares of a flag column is not used.
+template <int KIND, bool PAIR, int JT>
+__global__ __launch_bounds__(256) void k_bs_contract_multi(const BasisParams *__restrict__ tab, const double *__restrict__ fine,
+                                                           const double *__restrict__ coarse, int64_t n, int M, int K, int64_t i0,
+                                                           int64_t nr, const uint8_t *__restrict__ keep, int64_t ldk,
+                                                           const int32_t *__restrict__ W, int64_t ldw, int reps,
+                                                           double *__restrict__ partials) {
+    constexpr int JB = 16 * JT;
+    constexpr int KB = BS_KB;
+    constexpr int WS = KB + 4;                       // as k_bs_contract: 16 replicates x 4 samples hit 64 distinct banks
+    constexpr int PS = 32 * ((JB + 31) / 32) + 16;   // == 16 (mod 32)
+    __shared__ int32_t wl[BS_REPS * WS];
+    __shared__ double ph[KB * PS];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K1 = K + 1;
+    const int j0 = blockIdx.z * JB;
+    const int m_lo = j0 / K1, m_hi = std::min(M - 1, (j0 + JB - 1) / K1);
+    const int ncomp = m_hi - m_lo + 1;
+    const int y0 = blockIdx.y * BS_REPS;
+    const int64_t s_begin = (int64_t)blockIdx.x * BS_SW, s_end = std::min(nr, s_begin + BS_SW);
+
+    v4f64 a1[JT], a2[JT];
+#pragma unroll
+    for (int J = 0; J < JT; ++J) {
+        a1[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
+        a2[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    }
+    for (int64_t s0 = s_begin; s0 < s_end; s0 += KB) {
+        const int kb = (int)std::min((int64_t)KB, s_end - s0);
+        for (int e = threadIdx.x; e < BS_REPS * KB; e += 256) {
+            const int r = e / KB, k = e % KB;
+            wl[r * WS + k] = (y0 + r < reps && k < kb) ? W[(int64_t)(y0 + r) * ldw + s0 + k] : 0;
+        }
+        for (int e = threadIdx.x; e < KB * JB; e += 256) ph[(e / JB) * PS + e % JB] = 0.0;
+        __syncthreads();
+        for (int it = threadIdx.x; it < KB * ncomp; it += 256) {
+            const int k = it % KB, m = m_lo + it / KB;
+            if (k >= kb || !keep[(int64_t)m * ldk + s0 + k]) continue;
+            const BasisParams bp = tab[m];
+            const int64_t idx = (int64_t)m * n + i0 + s0 + k;
+            bool kf, kc = true;
+            const double tf = transform_value(bp, fine[idx], kf);
+            const double tc = PAIR ? transform_value(bp, coarse[idx], kc) : 0.0;
+            TermGen<KIND> gf, gc;
+            gf.init(tf, 1.0, bp);
+            if (PAIR) gc.init(tc, 1.0, bp);
+            const int cb = m * K1 - j0;                                  // block column of the component's flag: < JB, may be < 0
+            if (cb >= 0) ph[k * PS + cb] = 1.0;
+            const int rb = -cb - 1, re = std::min(K, JB - cb - 1);       // the block holds terms max(rb, 0) .. re - 1 of component m
+            for (int r = 0; r < re; ++r) {
+                double d = gf.next(r);
+                if (PAIR) d -= gc.next(r);
+                if (r >= rb) ph[k * PS + cb + 1 + r] = d;
+            }
+        }
+        __syncthreads();
+        const int arow = (16 * wave + (lane & 15)) * WS;
+#pragma unroll 4
+        for (int kk = 0; kk < KB / 4; ++kk) {
+            const int k = 4 * kk + (lane >> 4);
+            const double a = (double)wl[arow + k];
+#pragma unroll
+            for (int J = 0; J < JT; ++J) {
+                const double bv = ph[k * PS + 16 * J + (lane & 15)];
+                a1[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, a1[J], 0, 0, 0);
+                a2[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv * bv, a2[J], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    double *__restrict__ prow = partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (BS_REPS * 2 * JB);
+#pragma unroll
+    for (int J = 0; J < JT; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rep = 16 * wave + (lane >> 4) + 4 * r, col = 16 * J + (lane & 15);
+            prow[rep * 2 * JB + col] = a1[J][r];
+            prow[rep * 2 * JB + JB + col] = a2[J][r];
+        }
+}
+
+// k_bs_reduce for a group of components starting at m0: `cols` = (components of the group) x (K + 1) group columns into the
+// level totals tot [B][M_all (2 K + 1)], per component (sum w d [K] | sum w d^2 [K] | kept count).  Slices in a fixed order.
+__global__ __launch_bounds__(256) void k_bs_reduce_multi(const double *__restrict__ partials, int nx, int JB, int cols, int K,
+                                                         int64_t m0, int64_t ld_tot, int64_t b_first, int reps,
+                                                         double *__restrict__ tot) {
+    const int row = BS_REPS * 2 * JB;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= row) return;
+    const int rep = e / (2 * JB), c = e % (2 * JB);
+    const int b = blockIdx.y * BS_REPS + rep;
+    const int j = blockIdx.z * JB + (c % JB);
+    if (b >= reps || j >= cols) return;
+    const int m = j / (K + 1), q = j % (K + 1);
+    if (c >= JB && q == 0) return;
+    const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
+    double s = 0.0;
+    for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
+    double *__restrict__ t = tot + (b_first + b) * ld_tot + (m0 + m) * (2 * K + 1);
+    if (c < JB) t[q ? q - 1 : 2 * K] += s;
+    else t[K + q - 1] += s;
+}
+
 // ---- host side ----------------------------------------------------------------------------
 struct BsScratch {              // one per accumulator / weights call: sized by the budgets above, never by B x n
     int32_t *counts = nullptr;   // [rows][n_tiles]
@@ -305,6 +437,13 @@ struct mlmc_bootstrap {
     size_t ev_used = 0;
     double ms_rng = 0, ms_contract = 0;
     int64_t flops = 0;
+    // per-component handle (mlmc_bootstrap_create_multi): R = K, totals [L][B][M (2 K + 1)], no d_cnt
+    bool multi = false;
+    std::vector<const mlmc_basis *> bases;
+    mlmc::BasisParams *d_tab = nullptr;   // [M]
+    uint8_t *d_keep_m = nullptr;          // [M][keep_tiles * BS_TILE]
+    int64_t keep_tiles = 0;               // tiles per sample range the keep bytes allow
+    size_t tot_bytes() const { return sizeof(double) * (size_t)L * (size_t)B * (multi ? (size_t)M * (2 * (size_t)R + 1) : 2 * (size_t)MR); }
 };
 
 namespace mlmc {
@@ -380,6 +519,96 @@ static void launch_contract(int JT, dim3 grid, const BasisParams &bp, const doub
     else if (bp.kind == MLMC_MONOMIAL) { MLMC_BS_KIND(MLMC_MONOMIAL) }
     else { MLMC_BS_KIND(MLMC_FOURIER) }
 #undef MLMC_BS_KIND
+}
+
+template <int KIND, bool PAIR>
+static void launch_contract_multi_kind(int JT, dim3 grid, const BasisParams *tab, const double *f, const double *c, int64_t n, int M,
+                                       int K, int64_t i0, int64_t nr, const uint8_t *keep, int64_t ldk, const int32_t *W, int64_t ldw,
+                                       int reps, double *part) {
+    if (JT == 1)
+        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 1>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
+    else if (JT == 2)
+        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 2>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
+    else
+        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 4>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
+}
+
+static void launch_contract_multi(int kind, int JT, dim3 grid, const BasisParams *tab, const double *f, const double *c, int64_t n,
+                                  int M, int K, int64_t i0, int64_t nr, const uint8_t *keep, int64_t ldk, const int32_t *W,
+                                  int64_t ldw, int reps, double *part) {
+#define MLMC_BS_KIND(KD)                                                                                                          \
+    if (c) launch_contract_multi_kind<KD, true>(JT, grid, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);             \
+    else launch_contract_multi_kind<KD, false>(JT, grid, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
+    if (kind == MLMC_LEGENDRE) { MLMC_BS_KIND(MLMC_LEGENDRE) }
+    else if (kind == MLMC_MONOMIAL) { MLMC_BS_KIND(MLMC_MONOMIAL) }
+    else { MLMC_BS_KIND(MLMC_FOURIER) }
+#undef MLMC_BS_KIND
+}
+
+// components per group of the per-component route: at most BS_MAX_COLS group columns of K + 1 each
+static int64_t bs_group_comps(int64_t M, int64_t K) { return std::min<int64_t>(M, std::max<int64_t>(1, BS_MAX_COLS / (K + 1))); }
+
+// One chunk of a per-component handle (mlmc_bootstrap_accum has checked the arguments; ds: the device view of the pinned sizes).
+// Per (replicate group, sample range): the weight slab and the keep bytes of all M components once, then per component group the
+// contraction and its fixed-order reduction.  The range and the column blocks are functions of n, M and K only.
+static int bs_accum_multi(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n, const int64_t *sizes,
+                          const int64_t *ds, uint64_t seed, uint32_t stream) {
+    const int64_t B = a->B, M = a->M, K = a->R, K1 = K + 1;
+    const int64_t mg = bs_group_comps(M, K);
+    const int64_t cg = mg * K1;                                          // columns of the largest group
+    const int JT = cg <= 16 ? 1 : (cg <= 32 ? 2 : 4);
+    const int JB = 16 * JT;
+    const int64_t ncb_max = cdiv(cg, JB);
+    const int64_t n_tiles = cdiv(n, BS_TILE);
+    const size_t pwb = (size_t)BS_REPS * 2 * JB * sizeof(double);
+    constexpr int SPT = BS_TILE / BS_SW;
+    const int64_t tpr = std::max<int64_t>(1, std::min<int64_t>({n_tiles, (int64_t)BS_TPR_MAX, a->keep_tiles,
+                                                                 (int64_t)(BS_PART_BYTES / (pwb * SPT * ncb_max))}));
+    const int64_t nr = tpr * BS_TILE;
+    const int64_t ldk = a->keep_tiles * BS_TILE;
+    const int64_t nx_full = tpr * SPT;
+    int64_t ny = std::min<int64_t>({cdiv(B, BS_REPS), (int64_t)BS_NY_MAX, (int64_t)(BS_PART_BYTES / (pwb * nx_full * ncb_max)),
+                                    (int64_t)(BS_COUNTS_BYTES / (4 * (size_t)BS_REPS * n_tiles))});
+    ny = std::max<int64_t>(ny, 1);
+    const int64_t BG = ny * BS_REPS;
+    const int kind = a->bases[0]->p.kind;
+    const int64_t ld_tot = M * (2 * K + 1);
+    double *tot = a->d_tot + (size_t)level * B * ld_tot;
+    for (int64_t g = 0; g < B; g += BG) {
+        const int64_t ng = std::min(BG, B - g);
+        const int64_t nyg = cdiv(ng, BS_REPS);
+        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
+        if (int rc = bs_time(a, 0, false)) return rc;
+        if (int rc = launch_tile_counts(n, ng, ds + g, mx, g, seed, stream, a->sc.counts)) return rc;
+        if (int rc = bs_time(a, 0, true)) return rc;
+        for (int64_t i0 = 0; i0 < n; i0 += nr) {
+            const int64_t len = std::min(nr, n - i0);
+            const int64_t nt = cdiv(len, BS_TILE), nx = cdiv(len, BS_SW);
+            if (int rc = bs_time(a, 0, false)) return rc;
+            if (int rc = launch_expand(n, ng, i0 / BS_TILE, nt, a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
+            if (int rc = bs_time(a, 0, true)) return rc;
+            if (int rc = bs_time(a, 1, false)) return rc;
+            hipLaunchKernelGGL(k_bs_keep_multi, dim3((unsigned)cdiv(len, 256), (unsigned)M), dim3(256), 0, rt().stream, a->d_tab, fine,
+                               coarse, n, (int)M, i0, len, ldk, a->d_keep_m);
+            MLMC_HIP_CHECK(hipGetLastError());
+            const int64_t batches = (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
+            for (int64_t m0 = 0; m0 < M; m0 += mg) {
+                const int64_t mc = std::min(mg, M - m0);
+                const int cols = (int)(mc * K1);
+                const int64_t ncb = cdiv(cols, JB);
+                const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
+                launch_contract_multi(kind, JT, grid, a->d_tab + m0, fine + m0 * n, coarse ? coarse + m0 * n : nullptr, n, (int)mc, (int)K,
+                                      i0, len, a->d_keep_m + m0 * ldk, ldk, a->sc.w, nr, (int)ng, a->sc.part);
+                MLMC_HIP_CHECK(hipGetLastError());
+                hipLaunchKernelGGL(k_bs_reduce_multi, dim3((unsigned)cdiv(BS_REPS * 2 * JB, 256), (unsigned)nyg, (unsigned)ncb), dim3(256), 0,
+                                   rt().stream, a->sc.part, (int)nx, JB, cols, (int)K, m0, ld_tot, g, (int)ng, tot);
+                MLMC_HIP_CHECK(hipGetLastError());
+                a->flops += batches * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
+            }
+            if (int rc = bs_time(a, 1, true)) return rc;
+        }
+    }
+    return 0;
 }
 
 }  // namespace mlmc
@@ -469,6 +698,8 @@ extern "C" void mlmc_bootstrap_destroy(mlmc_bootstrap *a) {
     (void)wait_stream(rt().stream);
     if (a->d_tot) (void)hipFree(a->d_tot);
     if (a->d_cnt) (void)hipFree(a->d_cnt);
+    if (a->d_tab) (void)hipFree(a->d_tab);
+    if (a->d_keep_m) (void)hipFree(a->d_keep_m);
     bs_scratch_free(a->sc);
     for (int64_t *p : a->h_sizes) (void)hipHostFree(p);
     for (hipEvent_t e : a->ev) (void)hipEventDestroy(e);
@@ -482,8 +713,8 @@ extern "C" int mlmc_bootstrap_reset(mlmc_bootstrap *a) {
     MLMC_HIP_CHECK(wait_stream(rt().stream));     // earlier chunks may still read the pinned sizes
     a->sizes_used = 0;
     a->ev_used = 0;
-    MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, sizeof(double) * (size_t)a->L * (size_t)a->B * 2 * (size_t)a->MR, rt().stream));
-    MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)a->L * (size_t)a->B, rt().stream));
+    MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, a->tot_bytes(), rt().stream));
+    if (a->d_cnt) MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)a->L * (size_t)a->B, rt().stream));
     return 0;
 }
 
@@ -510,6 +741,7 @@ extern "C" int mlmc_bootstrap_accum(mlmc_bootstrap *a, int32_t level, const doub
     std::memcpy(hs, sizes, sizeof(int64_t) * (size_t)B);
     int64_t *ds = nullptr;
     MLMC_HIP_CHECK(hipHostGetDevicePointer((void **)&ds, hs, 0));
+    if (a->multi) return bs_accum_multi(a, level, fine, coarse, n, sizes, ds, seed, stream);
 
     const int MR = a->MR;
     const int JT = MR <= 16 ? 1 : (MR <= 32 ? 2 : 4);
@@ -566,6 +798,7 @@ extern "C" int mlmc_bootstrap_finalize(mlmc_bootstrap *a, int64_t *n_out, double
     MLMC_API_GUARD;
     using namespace mlmc;
     if (!a) return fail("mlmc_bootstrap_finalize: null handle");
+    if (a->multi) return fail("mlmc_bootstrap_finalize: the handle comes from mlmc_bootstrap_create_multi (use mlmc_bootstrap_finalize_multi)");
     if (!n_out || !s_out || !sp_out) return fail("mlmc_bootstrap_finalize: null argument (n_out, s_out, sp_out)");
     const int64_t L = a->L, B = a->B, MR = a->MR;
     std::vector<double> tot((size_t)L * B * 2 * MR);
@@ -587,6 +820,95 @@ extern "C" int mlmc_bootstrap_finalize(mlmc_bootstrap *a, int64_t *n_out, double
                 sp[j] = (cj * cj) * t[MR + j];
             }
         }
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_create_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int64_t B,
+                                           mlmc_bootstrap **out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    const std::string e("mlmc_bootstrap_create_multi");
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (!bases || !out) return fail(e + ": null argument (bases, out)");
+    if (M < 1 || M > 65535) return fail(e + ": M = " + std::to_string(M) + " (must be in 1 .. 65535)");
+    if (K < 1 || K > 512) return fail(e + ": K must be in 1..512");
+    if (n_levels < 1 || n_levels > 2047) return fail(e + ": n_levels = " + std::to_string(n_levels) + " (must be in 1 .. 2047)");
+    if (B < 1 || B > (int64_t)INT32_MAX) return fail(e + ": B = " + std::to_string(B) + " (must be in 1 .. 2^31 - 1)");
+    std::vector<BasisParams> bps(M);
+    for (int m = 0; m < M; ++m) {
+        const mlmc_basis *b = bases[m];
+        const std::string where = e + ": component " + std::to_string(m) + ": ";
+        if (!b) return fail(where + "null basis");
+        if (b->out_size > 0) return fail(where + "transformed bases are not supported (pass the family member of size K)");
+        const int kind = b->p.kind;
+        if (kind != MLMC_LEGENDRE && kind != MLMC_MONOMIAL && kind != MLMC_FOURIER)
+            return fail(where + "only Legendre, monomial and Fourier moments");
+        if (kind != bases[0]->p.kind) return fail(where + "every component must use the same family");
+        if (b->p.size < K) return fail(where + "basis smaller than K");
+        bps[m] = b->p;
+    }
+    // [n_levels][B][M (2 K + 1)] doubles; every factor is small enough for the product to stay inside 64 bits
+    const uint64_t tot_elems = (uint64_t)n_levels * (uint64_t)B * (uint64_t)M * (uint64_t)(2 * K + 1);
+    if (tot_elems > ((uint64_t)2 << 30) / sizeof(double))
+        return fail(e + ": the totals [n_levels][B][M (2 K + 1)] = [" + std::to_string(n_levels) + "][" + std::to_string(B) + "][" +
+                    std::to_string((int64_t)M * (2 * K + 1)) + "] doubles take " + std::to_string((tot_elems * sizeof(double)) >> 20) +
+                    " MiB, at most 2048 MiB are supported (fewer replicates or components per call)");
+    mlmc_bootstrap *a = new mlmc_bootstrap();
+    a->multi = true;
+    a->basis = bases[0];
+    a->bases.assign(bases, bases + M);
+    a->M = M;
+    a->L = n_levels;
+    a->R = K;
+    a->MR = M * K;
+    a->B = B;
+    // keep bytes [M][range]: the range shrinks with M so that they stay within 8 MiB (one tile at least)
+    a->keep_tiles = std::max<int64_t>(1, std::min<int64_t>(BS_TPR_MAX, (int64_t)((size_t)8 << 20) / ((int64_t)M * BS_TILE)));
+    const size_t tot = a->tot_bytes();
+    if (hipMalloc((void **)&a->d_tot, tot) != hipSuccess || hipMalloc((void **)&a->d_tab, sizeof(BasisParams) * (size_t)M) != hipSuccess ||
+        hipMalloc((void **)&a->d_keep_m, (size_t)M * a->keep_tiles * BS_TILE) != hipSuccess || bs_scratch_alloc(a->sc) != 0) {
+        (void)hipGetLastError();
+        if (a->d_tot) (void)hipFree(a->d_tot);
+        if (a->d_tab) (void)hipFree(a->d_tab);
+        if (a->d_keep_m) (void)hipFree(a->d_keep_m);
+        bs_scratch_free(a->sc);
+        delete a;
+        return fail(e + ": out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch + keep bytes)");
+    }
+    hipError_t err = hipMemcpy(a->d_tab, bps.data(), sizeof(BasisParams) * (size_t)M, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemsetAsync(a->d_tot, 0, tot, rt().stream);
+    if (err != hipSuccess) {
+        mlmc_bootstrap_destroy(a);
+        return fail(e + ": " + hipGetErrorString(err));
+    }
+    *out = a;
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *a, int64_t *n_out, double *s_out, double *sp_out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_finalize_multi: null handle");
+    if (!a->multi) return fail("mlmc_bootstrap_finalize_multi: the handle comes from mlmc_bootstrap_create (use mlmc_bootstrap_finalize)");
+    if (!n_out || !s_out || !sp_out) return fail("mlmc_bootstrap_finalize_multi: null argument (n_out, s_out, sp_out)");
+    const int64_t L = a->L, B = a->B, M = a->M, K = a->R, C = 2 * K + 1;
+    std::vector<double> tot((size_t)L * B * M * C);
+    MLMC_HIP_CHECK(hipMemcpyAsync(tot.data(), a->d_tot, sizeof(double) * tot.size(), hipMemcpyDeviceToHost, rt().stream));
+    MLMC_HIP_CHECK(wait_stream(rt().stream));
+    a->sizes_used = 0;
+    if (int rc = bs_time_collect(a)) return rc;
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t l = 0; l < L; ++l)
+            for (int64_t m = 0; m < M; ++m) {
+                const double *t = tot.data() + ((l * B + b) * M + m) * C;
+                const std::vector<double> &c = a->bases[m]->scale_c;     // Legendre: P_k = c_k q_k; else ones
+                const int64_t o = (b * L + l) * M + m;
+                n_out[o] = (int64_t)t[2 * K];                            // an exact integer (k_bs_contract_multi)
+                for (int64_t k = 0; k < K; ++k) {
+                    s_out[o * K + k] = c[k] * t[k];
+                    sp_out[o * K + k] = (c[k] * c[k]) * t[K + k];
+                }
+            }
     return 0;
 }
 

@@ -431,3 +431,31 @@ class BootstrapAccumulator:
         fl = C.c_int64()
         _lib.check(_lib.lib().mlmc_bootstrap_kernel_time(self._h, C.byref(ms_c), C.byref(ms_r), C.byref(fl)))
         return ms_c.value, ms_r.value, fl.value
+
+
+class ComponentBootstrapAccumulator(BootstrapAccumulator):
+    """BootstrapAccumulator with one moments object per component (mlmc_bootstrap_create_multi): component m (row m of the chunks)
+    takes its first K moments from moments_fns[m] -- plain Legendre, Monomial or Fourier objects of one family, each with its own
+    domain -- and is masked on its own.  accum() is the base class's (the same weights); finalize() returns n [B, L, M] kept
+    counts and s, sp [B, L, M, K].  No column cap: components run in groups inside the library."""
+
+    def __init__(self, moments_fns, K, n_levels, n_replicates):
+        self._moments_fn = list(moments_fns)                   # the library reads the basis handles until destroy
+        self.n_comp, self.n_levels, self.B = len(self._moments_fn), int(n_levels), int(n_replicates)
+        self.n_moments = int(K)
+        self.K = self.n_comp * self.n_moments
+        self._keepalive = []
+        handles = (C.c_void_p * self.n_comp)(*[fn._basis_handle().value for fn in self._moments_fn])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().mlmc_bootstrap_create_multi(self.n_comp, C.cast(handles, C.c_void_p), self.n_moments, self.n_levels,
+                                                          self.B, C.byref(h)))
+        self._h = h
+
+    def finalize(self):
+        """-> n [B, L, M] int64, s [B, L, M, K], sp [B, L, M, K] float64 (one wait for the device)."""
+        n = np.empty((self.B, self.n_levels, self.n_comp), dtype=np.int64)
+        s = np.empty((self.B, self.n_levels, self.n_comp, self.n_moments), dtype=np.float64)
+        sp = np.empty_like(s)
+        _lib.check(_lib.lib().mlmc_bootstrap_finalize_multi(self._h, _lib.ptr(n), _lib.ptr(s), _lib.ptr(sp)))
+        self._keepalive = []
+        return n, s, sp

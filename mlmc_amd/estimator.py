@@ -15,6 +15,35 @@ from .quantity.quantity_types import ScalarType
 
 
 BootstrapReplicates = collections.namedtuple("BootstrapReplicates", "n_samples l_means l_vars mean var seed")
+ComponentBootstrapReplicates = collections.namedtuple("ComponentBootstrapReplicates", "n_samples l_means l_vars mean var seed")
+QuantileBands = collections.namedtuple("QuantileBands", "q lo hi replicates success n_ok seed")
+
+
+def quantile_bands(replicates, success, level):
+    """Percentile bands of bootstrap quantile replicates (host arithmetic): replicates [B, M, P], success [B, M] bool ->
+    (lo, hi) [M, P], the 100 (1 - level) / 2 and 100 (1 + level) / 2 percentiles (np.percentile, axis 0) of component m's
+    replicates over its successful rows alone; NaN for a component without a successful replicate."""
+    replicates = np.asarray(replicates, dtype=np.float64)
+    success = np.asarray(success, dtype=bool)
+    if replicates.ndim != 3 or success.shape != replicates.shape[:2]:
+        raise ValueError("quantile_bands: replicates [B, M, P] and success [B, M] expected, got shapes {} and {}".format(
+            replicates.shape, success.shape))
+    level = _check_level("quantile_bands", level)
+    _, M, P = replicates.shape
+    lo = np.full((M, P), np.nan)
+    hi = np.full((M, P), np.nan)
+    for m in range(M):
+        rows = replicates[success[:, m], m]
+        if rows.shape[0]:
+            lo[m] = np.percentile(rows, 100.0 * (1.0 - level) / 2.0, axis=0)
+            hi[m] = np.percentile(rows, 100.0 * (1.0 + level) / 2.0, axis=0)
+    return lo, hi
+
+
+def _check_level(what, level):
+    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < level < 1.0:
+        raise ValueError("{}: level must be a number in (0, 1), got {!r}".format(what, level))
+    return float(level)
 
 
 class Estimate:
@@ -325,6 +354,116 @@ class Estimate:
         self.var_bs_l_vars = np.var(r["l_vars"], axis=0, ddof=1)
         self._bs_level_mean_variance = self.var_bs_l_means * n_coll.reshape((-1,) + (1,) * (self.var_bs_l_means.ndim - 1))
         return BootstrapReplicates(r["n_samples"], r["l_means"], r["l_vars"], r["mean"], r["var"], seed)
+
+    def _component_bootstrap_args(self, what, n_subsamples, sample_vector, moments_fns, seed):
+        """The arguments of the per-component bootstrap, checked as est_bootstrap_batch checks its own, before any device work.
+        -> (moments objects [M], B, k [L] int64, seed)"""
+        from .quantity import quantity as qmod
+        fns = self._component_fns(moments_fns, what)
+        from .moments import Legendre, Monomial, Fourier
+        names = sorted({type(fn).__name__ for fn in fns})
+        if len(names) != 1 or type(fns[0]) not in (Legendre, Monomial, Fourier):
+            raise ValueError("{}: {} moments are not supported (Legendre, Monomial or Fourier objects of ONE family are); use "
+                             "est_bootstrap or est_bootstrap_batch on scalar_component(quantity, m) for them".format(
+                                 what, " / ".join(names)))
+        if int(fns[0].size) > 512:
+            raise ValueError("{}: {} moments per component, at most 512 are supported".format(what, int(fns[0].size)))
+        if isinstance(n_subsamples, (bool, np.bool_)) or not isinstance(n_subsamples, (int, np.integer)) or n_subsamples < 1:
+            raise ValueError("{}: n_subsamples must be an integer >= 1, got {!r}".format(what, n_subsamples))
+        n_levels = self._sample_storage.get_n_levels()
+        n_coll = np.array(self._sample_storage.get_n_collected())[:n_levels]
+        k = determine_sample_vec(n_collected_samples=n_coll, n_levels=n_levels, sample_vector=sample_vector)
+        if k.shape != (n_levels,) or k.dtype.kind not in "iuf" or not np.all(np.isfinite(k.astype(np.float64))) or \
+                np.any(k != np.round(k)):
+            raise ValueError("{}: sample_vector must hold one integer per level, got {!r}".format(what, sample_vector))
+        k = k.astype(np.int64)
+        if np.any(k < 0) or np.any(k > n_coll):
+            raise ValueError("{}: sample_vector {} must lie in 0 .. n_collected {} on every level".format(
+                what, k.tolist(), n_coll.tolist()))
+        if seed is None:
+            seed = int(qmod.RNG.integers(0, 2 ** 63 - 1))
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("{}: seed must be an integer in [0, 2^64), got {!r}".format(what, seed))
+        return fns, int(n_subsamples), k, int(seed)
+
+    def est_bootstrap_components(self, n_subsamples=100, sample_vector=None, moments_fns=None, seed=None):
+        """est_bootstrap_batch of EVERY scalar component of the quantity under its own moments object, from one device pass per
+        stored chunk for all components (mlmc_bootstrap_create_multi).
+
+        Slice [:, ..., m, :] of every result is what `Estimate(scalar_component(q, m), storage, moments_fns[m])
+        .est_bootstrap_batch(n_subsamples, sample_vector, seed=seed)` returns: component m has its own domain and is NaN-masked and
+        clipped on its own (a NaN in component 3 does not touch component 0 -- est_bootstrap_batch on the vector quantity drops
+        the sample for all), and replicate b is drawn with the very weights of the scalar call.  No column limit; Legendre,
+        Monomial and Fourier objects of one family and size.  Bit-identical from run to run, the first B replicates do not
+        depend on n_subsamples.  A level with sample_vector[l] = 0 gives NaN means and inf variances, as est_bootstrap_batch.
+        :param moments_fns: M moments objects (None: this Estimate's moments_fn for every component)
+        :param seed: None: one 63-bit seed drawn from quantity.RNG
+        :return: ComponentBootstrapReplicates(n_samples [B, L, M], l_means [B, L, M, R], l_vars [B, L, M, R], mean [B, M, R],
+            var [B, M, R], seed); a scalar quantity has M = 1"""
+        fns, B, k, seed = self._component_bootstrap_args("est_bootstrap_components", n_subsamples, sample_vector, moments_fns, seed)
+        n, s, sp = qe.bootstrap_component_moments(self._quantity, fns, B, k, seed)
+        if np.any(np.sum(n, axis=1) == 0):
+            raise Exception("All samples were masked")
+        _, L, M, R = s.shape
+        l_means, l_vars = engine.level_stats(n.reshape(-1), s.reshape(-1, R), sp.reshape(-1, R))
+        l_means, l_vars = l_means.reshape(B, L, M, R), l_vars.reshape(B, L, M, R)
+        mean = np.sum(l_means, axis=1)
+        with np.errstate(all="ignore"):
+            var = np.sum(l_vars / n[..., None], axis=1)
+        return ComponentBootstrapReplicates(n, l_means, l_vars, mean, var, seed)
+
+    def bootstrap_component_quantiles(self, probs, n_subsamples=100, sample_vector=None, seed=None, level=0.9, tol=1e-8,
+                                      reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """Bootstrap confidence bands of estimate_component_quantiles: how far the quantiles of every component's maximum-entropy
+        density move under resampling of the stored samples.
+
+        The orthogonal moments object of every component (matrix T_m, domain) is the one of `densities` (construct_densities,
+        computed here if not given) and stays fixed.  One est_bootstrap_components pass gives the level sums of the base moments of
+        every (replicate, component); replicate moments are mu_bm = sum_l (s[b, l, m] / n[b, l, m]) @ T_m^T over the levels with
+        sample_vector[l] > 0 (the arithmetic of construct_densities); the B * M max-entropy problems are solved in ONE batched
+        device call and their quantiles taken in ONE more.  A replicate equals the single solve of the same moments bit for bit
+        (tool.simple_distribution.quantiles).
+        :param probs: probabilities, the same for every component
+        :param level: coverage of the band, 0 < level < 1 (0.9: the 5 % .. 95 % percentiles over the replicates)
+        :param moments_fns: base moments objects of the bootstrap pass (None: those of `densities`)
+        :return: QuantileBands(q [M, P] = estimate_component_quantiles(probs, densities=densities)[0], lo [M, P], hi [M, P] =
+            quantile_bands(replicates, success, level), replicates [B, M, P], success [B, M] the solver's verdict per replicate,
+            n_ok [M] successful replicates per component, seed)"""
+        from .tool import simple_distribution
+        what = "bootstrap_component_quantiles"
+        level = _check_level(what, level)
+        try:
+            probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs))
+        if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):          # NaN fails both comparisons
+            raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs.tolist()))
+        if moments_fns is None and densities is not None:
+            moments_fns = [d[3]._base for d in densities]
+        fns, B, k, seed = self._component_bootstrap_args(what, n_subsamples, sample_vector, moments_fns, seed)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, fns)
+        if len(densities) != len(fns):
+            raise ValueError("{}: {} densities for {} components".format(what, len(densities), len(fns)))
+        q = self.estimate_component_quantiles(probs, densities=densities)[0]
+        n, s, _ = qe.bootstrap_component_moments(self._quantity, fns, B, k, seed)
+        if np.any(np.sum(n, axis=1) == 0):
+            raise Exception("All samples were masked")
+        M, R = len(fns), int(fns[0].size)
+        nf = n.astype(np.float64)
+        distrs = []
+        for b in range(B):
+            for m in range(M):
+                mobj = densities[m][3]
+                with np.errstate(all="ignore"):                     # (a level whose picks were all masked: NaN, a failed solve)
+                    mu = np.sum([(s[b, l, m, :R] / nf[b, l, m]) @ mobj._base_matrix.T for l in range(len(k)) if k[l] > 0], axis=0)
+                distrs.append(simple_distribution.SimpleDistribution(mobj, np.stack((mu, np.ones(mobj.size)), axis=1),
+                                                                     domain=mobj.domain))
+        results = simple_distribution.estimate_densities_minimize(distrs, tol, reg_param)
+        replicates = np.array(simple_distribution.quantiles(distrs, probs), dtype=np.float64).reshape(B, M, probs.size)
+        success = np.array([bool(r.success) for r in results], dtype=bool).reshape(B, M)
+        lo, hi = quantile_bands(replicates, success, level)
+        return QuantileBands(q, lo, hi, replicates, success, np.sum(success, axis=0), seed)
 
     def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
         """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""

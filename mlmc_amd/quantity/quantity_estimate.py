@@ -1342,6 +1342,31 @@ def bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
 
 
 def _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
+    M = int(quantity.size())
+    return _bootstrap_walk(quantity, "acc", lambda n_levels: (id(moments_fn), M, n_levels, int(n_replicates)),
+                           lambda n_levels: engine.BootstrapAccumulator(moments_fn, M, n_levels, n_replicates), moments_fn,
+                           n_replicates, sample_vector, seed)
+
+
+def bootstrap_component_moments(quantity, moments_fns, n_replicates, sample_vector, seed):
+    """bootstrap_moments for every scalar component of `quantity` under its own moments object (Estimate.est_bootstrap_components):
+    component m (row m of the chunks) uses moments_fns[m] -- its own domain, its own NaN / out-of-domain mask -- in ONE device pass
+    per stored chunk for all components (engine.ComponentBootstrapAccumulator).  The chunk walk, sizes and Philox streams are those
+    of bootstrap_moments, so replicate b of component m is drawn with exactly the weights of the scalar call on
+    scalar_component(quantity, m).  -> n [B, L, M] kept counts, s, sp [B, L, M, R]"""
+    with _estimate_lock:
+        fns = list(moments_fns)
+        M, R = len(fns), int(fns[0].size)
+        if int(quantity.size()) != M:
+            raise ValueError("bootstrap_component_moments: {} moments objects for {} components".format(M, quantity.size()))
+        return _bootstrap_walk(quantity, "acc_comp", lambda n_levels: (tuple(id(fn) for fn in fns), R, n_levels, int(n_replicates)),
+                               lambda n_levels: engine.ComponentBootstrapAccumulator(fns, R, n_levels, n_replicates), fns,
+                               n_replicates, sample_vector, seed)
+
+
+def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sample_vector, seed):
+    """One bootstrap pass over the stored chunks of `quantity` into the pooled accumulator of `slot` (reused when make_key(n_levels)
+    matches the last call's, else replaced by make_acc(n_levels)); `alive` is kept with it.  -> the accumulator's finalize()"""
     import torch
     cache_clear()
     storage_q = quantity.get_quantity_storage()
@@ -1355,15 +1380,15 @@ def _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
     use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(quantity, "_volatile", False)
     dev = torch.device("cuda", _lib_device())
     M = int(quantity.size())
-    key = (id(moments_fn), M, n_levels, int(n_replicates))
-    kept = _bootstrap_pool.pop("acc", None)                       # the last accumulator (64 MiB of scratch, pinned size blocks)
+    key = make_key(n_levels)
+    kept = _bootstrap_pool.pop(slot, None)                        # the last accumulator (64 MiB of scratch, pinned size blocks)
     if kept is not None and kept[0] == key:
         acc = kept[1]
         acc.reset()
     else:
         if kept is not None:
             kept[1].close()
-        acc = engine.BootstrapAccumulator(moments_fn, M, n_levels, n_replicates)
+        acc = make_acc(n_levels)
     chunk_no = collections.Counter()
     copied = False
     pushed = 0
@@ -1398,7 +1423,7 @@ def _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
     except BaseException:
         acc.close()
         raise
-    _bootstrap_pool["acc"] = (key, acc, moments_fn)               # (moments_fn kept alive: its id stays unique)
+    _bootstrap_pool[slot] = (key, acc, alive)                     # (the moments objects kept alive: their ids stay unique)
     return out
 
 
