@@ -24,7 +24,8 @@
 // Scratch (tile counts, slab, partials, keep bytes) stays below 64 MiB; the totals [L][B][2 M R] are the size of the result.
 //
 // Per-component route (mlmc_bootstrap_create_multi, Estimate.est_bootstrap_components): one basis and one mask per component, the
-// same weights; k_bs_keep_multi / k_bs_contract_multi / k_bs_reduce_multi below, components in groups of at most 2048 columns.
+// same weights, the same plan, the same k_bs_contract and k_bs_reduce under another column layout (BsPerComponent instead of
+// BsSharedBasis below), keep bytes from k_bs_keep_multi, components in groups of at most 2048 columns.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -131,26 +132,119 @@ __global__ __launch_bounds__(256) void k_bs_keep(BasisParams bp, const double *_
     }
 }
 
-// The contraction.  grid (slices of BS_SW samples of the range, 64-replicate tiles, column blocks of JB = 16 JT d-columns).
-// Per batch of BS_KB samples: the weights [64][KB] and keep bytes -> LDS, Phi [KB][JB] (d of the block's columns; 0 for dropped
-// samples) -> LDS, then each wave runs KB / 4 k-steps of 2 JT MFMAs: sum w d and sum w d^2 for its 16 replicates.  The kept
-// count sum w keep is an integer sum on the side (column block 0).  Partial rows: [64][2 JB] per workgroup, counts [64].
-template <int KIND, bool PAIR, int JT>
-__global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const double *__restrict__ fine, const double *__restrict__ coarse,
-                                                     int64_t n, int M, int R, int64_t i0, int64_t nr,
-                                                     const uint8_t *__restrict__ keep, const int32_t *__restrict__ W, int64_t ldw,
-                                                     int reps, double *__restrict__ partials, int32_t *__restrict__ pcnt) {
+// keep byte of component m at samples i0 .. i0 + nr - 1, keep[m * ldk + i]: the fine and the coarse value pass component m's own
+// transform (moments_multi.hip: the rule of a one-component chunk).  grid (sample blocks, components)
+__global__ __launch_bounds__(256) void k_bs_keep_multi(const BasisParams *__restrict__ tab, const double *__restrict__ f,
+                                                       const double *__restrict__ c, int64_t n, int M, int64_t i0, int64_t nr,
+                                                       int64_t ldk, uint8_t *__restrict__ keep) {
+    for (int m = blockIdx.y; m < M; m += gridDim.y) {
+        const BasisParams bp = tab[m];
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
+            bool k1, k2 = true;
+            transform_value(bp, f[(int64_t)m * n + i0 + i], k1);
+            if (c) transform_value(bp, c[(int64_t)m * n + i0 + i], k2);
+            keep[(int64_t)m * ldk + i] = (k1 && k2) ? 1 : 0;
+        }
+    }
+}
+
+// ---- column layouts: what the two routes do not share ---------------------------------------------------------------------------
+// k_bs_contract and k_bs_reduce work on the columns of the M components of one launch and ask a layout four things:
+//   basis(m)         the BasisParams of component m
+//   side_keep(s)     the byte the contraction stages in LDS for sample s of the range (the keep byte of the side count, if any)
+//   kept(m, s, side) whether component m keeps sample s; side: the staged byte of s
+//   width(), FLAG    columns per component; the first FLAG of them are a keep flag (1 for a kept sample), the others the terms d_r
+//   the kept count and the totals: Count / store_count in the contraction, total / reduce_count in the reduction
+// Both are passed by value and serve both kernels of a (range, component group).
+
+// One basis and one mask for all components (mlmc_bootstrap_create): component m owns R columns, the kept count sum w keep is an
+// integer sum on the side (workgroups of column block 0), totals [B][2 MR] (sum w d | sum w d^2) and counts [B].
+struct BsSharedBasis {
+    BasisParams bp;
+    const uint8_t *keep;   // [range]: the AND over the components (k_bs_keep)
+    int R, MR;
+    int32_t *pcnt;         // partial counts [64-replicate tile][slice][64]
+    double *tot;           // of the level
+    int64_t *cnt;
+    static constexpr int FLAG = 0;
+    __device__ const BasisParams &basis(int) const { return bp; }
+    __device__ int side_keep(int64_t s) const { return keep[s]; }
+    __device__ bool kept(int, int64_t, int side) const { return side != 0; }
+    __device__ int width() const { return R; }
+    struct Count {
+        int c = 0;
+        __device__ void add(int w, int k) { c += w * k; }
+    };
+    __device__ void store_count(Count n, int lane, int wave) const {        // lanes l, l + 16, l + 32, l + 48 hold one replicate
+        if (blockIdx.z != 0) return;
+        int c = n.c;
+        c += __shfl_xor(c, 16, 64);
+        c += __shfl_xor(c, 32, 64);
+        if (lane < 16) pcnt[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * BS_REPS + 16 * wave + lane] = c;
+    }
+    // where column j (its sum of squares: sq) of replicate b goes; null: nowhere
+    __device__ double *total(int64_t b, int j, bool sq) const { return j < MR ? tot + b * 2 * MR + (sq ? MR + j : j) : nullptr; }
+    __device__ void reduce_count(int nx, int64_t b_first, int reps) const {
+        if (blockIdx.x != 0 || blockIdx.z != 0 || threadIdx.x >= BS_REPS) return;
+        const int b = blockIdx.y * BS_REPS + threadIdx.x;
+        if (b >= reps) return;
+        int64_t s = 0;
+        for (int x = 0; x < nx; ++x) s += pcnt[((int64_t)blockIdx.y * nx + x) * BS_REPS + threadIdx.x];
+        cnt[b_first + b] += s;
+    }
+};
+
+// A basis and a mask per component (mlmc_bootstrap_create_multi), for a group of components: tab, keep and tot point at the group's
+// first one.  Component m owns K + 1 columns, m (K + 1) = its keep flag, m (K + 1) + 1 + k = d_k.  The flag column rides through
+// the same MFMAs: sum w keep is a sum of integers below 2^53, exact in fp64 in any order, so the kept count of every (replicate,
+// component) comes out as an exact integer with the sums.  Totals [B][ld_tot], per component (sum w d [K] | sum w d^2 [K] | kept
+// count); the sum of squares of a flag column is not used.
+struct BsPerComponent {
+    const BasisParams *tab;   // [M]
+    const uint8_t *keep;      // [M][ldk] (k_bs_keep_multi)
+    int64_t ldk;
+    int K, cols;              // cols = M (K + 1)
+    double *tot;              // of the level
+    int64_t ld_tot;
+    static constexpr int FLAG = 1;
+    __device__ const BasisParams &basis(int m) const { return tab[m]; }
+    __device__ int side_keep(int64_t) const { return 0; }
+    __device__ bool kept(int m, int64_t s, int) const { return keep[(int64_t)m * ldk + s] != 0; }
+    __device__ int width() const { return K + 1; }
+    struct Count {
+        __device__ void add(int, int) {}
+    };
+    __device__ void store_count(Count, int, int) const {}
+    __device__ double *total(int64_t b, int j, bool sq) const {
+        const int m = j / (K + 1), q = j % (K + 1);
+        if (j >= cols || (sq && q == 0)) return nullptr;
+        double *t = tot + b * ld_tot + (int64_t)m * (2 * K + 1);
+        return sq ? t + K + q - 1 : t + (q ? q - 1 : 2 * K);
+    }
+    __device__ void reduce_count(int, int64_t, int) const {}
+};
+
+// The contraction of M components (fine / coarse point at the first one).  grid (slices of BS_SW samples of the range, 64-replicate
+// tiles, column blocks of JB = 16 JT columns; a block may straddle components).
+// Per batch of BS_KB samples: the weights [64][KB] -> LDS, Phi [KB][JB] (flags and d of the block's columns; 0 where the column's
+// component drops the sample; a wave handles one component per trip: KB = 64 samples) -> LDS, then each wave runs KB / 4 k-steps of
+// 2 JT MFMAs: sum w d and sum w d^2 for its 16 replicates.  Partial rows: [64][2 JB] per workgroup.
+template <int KIND, bool PAIR, int JT, class Layout>
+__global__ __launch_bounds__(256) void k_bs_contract(Layout lay, const double *__restrict__ fine, const double *__restrict__ coarse,
+                                                     int64_t n, int M, int64_t i0, int64_t nr, const int32_t *__restrict__ W,
+                                                     int64_t ldw, int reps, double *__restrict__ partials) {
     constexpr int JB = 16 * JT;
     constexpr int KB = BS_KB;
     constexpr int WS = KB + 4;                       // rows of 16 replicates x 4 samples hit 64 distinct banks
     constexpr int PS = 32 * ((JB + 31) / 32) + 16;   // == 16 (mod 32): two k-rows of a fragment read in distinct bank halves
     __shared__ int32_t wl[BS_REPS * WS];
     __shared__ double ph[KB * PS];
-    __shared__ uint8_t kp[KB];
+    __shared__ uint8_t kp[KB];                       // Layout::side_keep of the batch
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cw = lay.width();
     const int j0 = blockIdx.z * JB;
-    const int m_lo = j0 / R, m_hi = std::min(M - 1, (j0 + JB - 1) / R);
+    const int m_lo = j0 / cw, m_hi = std::min(M - 1, (j0 + JB - 1) / cw);
     const int ncomp = m_hi - m_lo + 1;
     const int y0 = blockIdx.y * BS_REPS;
     const int64_t s_begin = (int64_t)blockIdx.x * BS_SW, s_end = std::min(nr, s_begin + BS_SW);
@@ -161,19 +255,20 @@ __global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const doubl
         a1[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
         a2[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
     }
-    int cnt = 0;
+    typename Layout::Count cnt;
     for (int64_t s0 = s_begin; s0 < s_end; s0 += KB) {
         const int kb = (int)std::min((int64_t)KB, s_end - s0);
         for (int e = threadIdx.x; e < BS_REPS * KB; e += 256) {
             const int r = e / KB, k = e % KB;
             wl[r * WS + k] = (y0 + r < reps && k < kb) ? W[(int64_t)(y0 + r) * ldw + s0 + k] : 0;
         }
-        if (threadIdx.x < KB) kp[threadIdx.x] = (int)threadIdx.x < kb ? keep[s0 + threadIdx.x] : 0;
+        if (threadIdx.x < KB) kp[threadIdx.x] = (int)threadIdx.x < kb ? lay.side_keep(s0 + threadIdx.x) : 0;
         for (int e = threadIdx.x; e < KB * JB; e += 256) ph[(e / JB) * PS + e % JB] = 0.0;
         __syncthreads();
         for (int it = threadIdx.x; it < KB * ncomp; it += 256) {
             const int k = it % KB, m = m_lo + it / KB;
-            if (k >= kb || !kp[k]) continue;
+            if (k >= kb || !lay.kept(m, s0 + k, kp[k])) continue;
+            const BasisParams bp = lay.basis(m);
             const int64_t idx = (int64_t)m * n + i0 + s0 + k;
             bool kf, kc = true;
             const double tf = transform_value(bp, fine[idx], kf);
@@ -181,11 +276,14 @@ __global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const doubl
             TermGen<KIND> gf, gc;
             gf.init(tf, 1.0, bp);
             if (PAIR) gc.init(tc, 1.0, bp);
-            const int rb = j0 - m * R, re = std::min(R, j0 + JB - m * R);   // the block holds terms rb .. re - 1 of component m
+            const int c0 = m * cw - j0;                                  // block column of the component's first column: < JB, may be < 0
+            if (Layout::FLAG && c0 >= 0) ph[k * PS + c0] = 1.0;
+            const int t0 = c0 + Layout::FLAG;                            // ... of its term 0
+            const int rb = -t0, re = std::min(cw - Layout::FLAG, JB - t0);   // the block holds terms max(rb, 0) .. re - 1 of component m
             for (int r = 0; r < re; ++r) {
                 double d = gf.next(r);
                 if (PAIR) d -= gc.next(r);
-                if (r >= rb) ph[k * PS + (r - rb)] = d;
+                if (r >= rb) ph[k * PS + t0 + r] = d;
             }
         }
         __syncthreads();
@@ -194,7 +292,7 @@ __global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const doubl
         for (int kk = 0; kk < KB / 4; ++kk) {
             const int k = 4 * kk + (lane >> 4);
             const int wv = wl[arow + k];
-            cnt += wv * (int)kp[k];
+            cnt.add(wv, kp[k]);
             const double a = (double)wv;
 #pragma unroll
             for (int J = 0; J < JT; ++J) {
@@ -215,166 +313,28 @@ __global__ __launch_bounds__(256) void k_bs_contract(BasisParams bp, const doubl
             prow[rep * 2 * JB + col] = a1[J][r];
             prow[rep * 2 * JB + JB + col] = a2[J][r];
         }
-    if (blockIdx.z == 0) {
-        cnt += __shfl_xor(cnt, 16, 64);
-        cnt += __shfl_xor(cnt, 32, 64);
-        if (lane < 16) pcnt[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * BS_REPS + 16 * wave + lane] = cnt;
-    }
+    lay.store_count(cnt, lane, wave);
 }
 
 // Level totals += the partial rows of one contraction launch, summed over the slices in a fixed order.
-// grid (ceil(64 * 2 JB / 256), 64-replicate tiles, column blocks).  tot: [B][2 MR] of the level (s | sp), cnt: [B].
-__global__ __launch_bounds__(256) void k_bs_reduce(const double *__restrict__ partials, const int32_t *__restrict__ pcnt, int nx, int JB,
-                                                   int MR, int64_t b_first, int reps, double *__restrict__ tot,
-                                                   int64_t *__restrict__ cnt) {
+// grid (ceil(64 * 2 JB / 256), 64-replicate tiles, column blocks)
+template <class Layout>
+__global__ __launch_bounds__(256) void k_bs_reduce(Layout lay, const double *__restrict__ partials, int nx, int JB, int64_t b_first,
+                                                   int reps) {
     const int row = BS_REPS * 2 * JB;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < row) {
         const int rep = e / (2 * JB), c = e % (2 * JB);
-        const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
-        double s = 0.0;
-        for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
         const int b = blockIdx.y * BS_REPS + rep;
-        const int j = blockIdx.z * JB + (c % JB);
-        if (b < reps && j < MR) tot[(b_first + b) * 2 * MR + (c < JB ? j : MR + j)] += s;
-    }
-    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < BS_REPS) {
-        const int b = blockIdx.y * BS_REPS + threadIdx.x;
-        if (b < reps) {
-            int64_t s = 0;
-            for (int x = 0; x < nx; ++x) s += pcnt[((int64_t)blockIdx.y * nx + x) * BS_REPS + threadIdx.x];
-            cnt[b_first + b] += s;
+        double *dst = b < reps ? lay.total(b_first + b, blockIdx.z * JB + c % JB, c >= JB) : nullptr;
+        if (dst) {
+            const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
+            double s = 0.0;
+            for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
+            *dst += s;
         }
     }
-}
-
-// ---- per-component bootstrap (mlmc_bootstrap_create_multi): every component under its own basis and its own mask ------------
-// Column layout of a group of components: component m owns K + 1 columns, m (K + 1) = its keep flag (1 for a kept sample),
-// m (K + 1) + 1 + k = d_k.  The flag column rides through the same MFMAs: sum w keep is a sum of integers below 2^53, exact
-// in fp64 in any order, so the kept count of every (replicate, component) comes out as an exact integer with the sums.
-
-// keep byte of component m at samples i0 .. i0 + nr - 1, keep[m * ldk + i]: the fine and the coarse value pass component m's own
-// transform (moments_multi.hip: the rule of a one-component chunk).  grid (sample blocks, components)
-__global__ __launch_bounds__(256) void k_bs_keep_multi(const BasisParams *__restrict__ tab, const double *__restrict__ f,
-                                                       const double *__restrict__ c, int64_t n, int M, int64_t i0, int64_t nr,
-                                                       int64_t ldk, uint8_t *__restrict__ keep) {
-    for (int m = blockIdx.y; m < M; m += gridDim.y) {
-        const BasisParams bp = tab[m];
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
-            bool k1, k2 = true;
-            transform_value(bp, f[(int64_t)m * n + i0 + i], k1);
-            if (c) transform_value(bp, c[(int64_t)m * n + i0 + i], k2);
-            keep[(int64_t)m * ldk + i] = (k1 && k2) ? 1 : 0;
-        }
-    }
-}
-
-// k_bs_contract for a group of M components with K moments each (fine / coarse / tab / keep point at the group's first
-// component): same grid, same LDS plan and bank pattern.  The Phi phase takes the BasisParams of a column's component from the
-// table (a wave handles one component per trip: KB = 64 samples), and leaves the K + 1 columns of a component at 0 for the
-// samples that component drops.  A column block may straddle components.  Partial rows [64][2 JB] per workgroup; the sum of
-// squares of a flag column is not used.
-template <int KIND, bool PAIR, int JT>
-__global__ __launch_bounds__(256) void k_bs_contract_multi(const BasisParams *__restrict__ tab, const double *__restrict__ fine,
-                                                           const double *__restrict__ coarse, int64_t n, int M, int K, int64_t i0,
-                                                           int64_t nr, const uint8_t *__restrict__ keep, int64_t ldk,
-                                                           const int32_t *__restrict__ W, int64_t ldw, int reps,
-                                                           double *__restrict__ partials) {
-    constexpr int JB = 16 * JT;
-    constexpr int KB = BS_KB;
-    constexpr int WS = KB + 4;                       // as k_bs_contract: 16 replicates x 4 samples hit 64 distinct banks
-    constexpr int PS = 32 * ((JB + 31) / 32) + 16;   // == 16 (mod 32)
-    __shared__ int32_t wl[BS_REPS * WS];
-    __shared__ double ph[KB * PS];
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int K1 = K + 1;
-    const int j0 = blockIdx.z * JB;
-    const int m_lo = j0 / K1, m_hi = std::min(M - 1, (j0 + JB - 1) / K1);
-    const int ncomp = m_hi - m_lo + 1;
-    const int y0 = blockIdx.y * BS_REPS;
-    const int64_t s_begin = (int64_t)blockIdx.x * BS_SW, s_end = std::min(nr, s_begin + BS_SW);
-
-    v4f64 a1[JT], a2[JT];
-#pragma unroll
-    for (int J = 0; J < JT; ++J) {
-        a1[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
-        a2[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
-    }
-    for (int64_t s0 = s_begin; s0 < s_end; s0 += KB) {
-        const int kb = (int)std::min((int64_t)KB, s_end - s0);
-        for (int e = threadIdx.x; e < BS_REPS * KB; e += 256) {
-            const int r = e / KB, k = e % KB;
-            wl[r * WS + k] = (y0 + r < reps && k < kb) ? W[(int64_t)(y0 + r) * ldw + s0 + k] : 0;
-        }
-        for (int e = threadIdx.x; e < KB * JB; e += 256) ph[(e / JB) * PS + e % JB] = 0.0;
-        __syncthreads();
-        for (int it = threadIdx.x; it < KB * ncomp; it += 256) {
-            const int k = it % KB, m = m_lo + it / KB;
-            if (k >= kb || !keep[(int64_t)m * ldk + s0 + k]) continue;
-            const BasisParams bp = tab[m];
-            const int64_t idx = (int64_t)m * n + i0 + s0 + k;
-            bool kf, kc = true;
-            const double tf = transform_value(bp, fine[idx], kf);
-            const double tc = PAIR ? transform_value(bp, coarse[idx], kc) : 0.0;
-            TermGen<KIND> gf, gc;
-            gf.init(tf, 1.0, bp);
-            if (PAIR) gc.init(tc, 1.0, bp);
-            const int cb = m * K1 - j0;                                  // block column of the component's flag: < JB, may be < 0
-            if (cb >= 0) ph[k * PS + cb] = 1.0;
-            const int rb = -cb - 1, re = std::min(K, JB - cb - 1);       // the block holds terms max(rb, 0) .. re - 1 of component m
-            for (int r = 0; r < re; ++r) {
-                double d = gf.next(r);
-                if (PAIR) d -= gc.next(r);
-                if (r >= rb) ph[k * PS + cb + 1 + r] = d;
-            }
-        }
-        __syncthreads();
-        const int arow = (16 * wave + (lane & 15)) * WS;
-#pragma unroll 4
-        for (int kk = 0; kk < KB / 4; ++kk) {
-            const int k = 4 * kk + (lane >> 4);
-            const double a = (double)wl[arow + k];
-#pragma unroll
-            for (int J = 0; J < JT; ++J) {
-                const double bv = ph[k * PS + 16 * J + (lane & 15)];
-                a1[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, a1[J], 0, 0, 0);
-                a2[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv * bv, a2[J], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    double *__restrict__ prow = partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (BS_REPS * 2 * JB);
-#pragma unroll
-    for (int J = 0; J < JT; ++J)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int rep = 16 * wave + (lane >> 4) + 4 * r, col = 16 * J + (lane & 15);
-            prow[rep * 2 * JB + col] = a1[J][r];
-            prow[rep * 2 * JB + JB + col] = a2[J][r];
-        }
-}
-
-// k_bs_reduce for a group of components starting at m0: `cols` = (components of the group) x (K + 1) group columns into the
-// level totals tot [B][M_all (2 K + 1)], per component (sum w d [K] | sum w d^2 [K] | kept count).  Slices in a fixed order.
-__global__ __launch_bounds__(256) void k_bs_reduce_multi(const double *__restrict__ partials, int nx, int JB, int cols, int K,
-                                                         int64_t m0, int64_t ld_tot, int64_t b_first, int reps,
-                                                         double *__restrict__ tot) {
-    const int row = BS_REPS * 2 * JB;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= row) return;
-    const int rep = e / (2 * JB), c = e % (2 * JB);
-    const int b = blockIdx.y * BS_REPS + rep;
-    const int j = blockIdx.z * JB + (c % JB);
-    if (b >= reps || j >= cols) return;
-    const int m = j / (K + 1), q = j % (K + 1);
-    if (c >= JB && q == 0) return;
-    const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
-    double s = 0.0;
-    for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
-    double *__restrict__ t = tot + (b_first + b) * ld_tot + (m0 + m) * (2 * K + 1);
-    if (c < JB) t[q ? q - 1 : 2 * K] += s;
-    else t[K + q - 1] += s;
+    lay.reduce_count(nx, b_first, reps);
 }
 
 // ---- host side ----------------------------------------------------------------------------
@@ -437,12 +397,12 @@ struct mlmc_bootstrap {
     size_t ev_used = 0;
     double ms_rng = 0, ms_contract = 0;
     int64_t flops = 0;
+    int64_t keep_tiles = 0;               // tiles per sample range the keep bytes allow
     // per-component handle (mlmc_bootstrap_create_multi): R = K, totals [L][B][M (2 K + 1)], no d_cnt
     bool multi = false;
     std::vector<const mlmc_basis *> bases;
     mlmc::BasisParams *d_tab = nullptr;   // [M]
     uint8_t *d_keep_m = nullptr;          // [M][keep_tiles * BS_TILE]
-    int64_t keep_tiles = 0;               // tiles per sample range the keep bytes allow
     size_t tot_bytes() const { return sizeof(double) * (size_t)L * (size_t)B * (multi ? (size_t)M * (2 * (size_t)R + 1) : 2 * (size_t)MR); }
 };
 
@@ -497,82 +457,78 @@ static void bs_scratch_free(BsScratch &sc) {
     sc = BsScratch();
 }
 
-template <int KIND, bool PAIR>
-static void launch_contract_kind(int JT, dim3 grid, const BasisParams &bp, const double *f, const double *c, int64_t n, int M, int R,
-                                 int64_t i0, int64_t nr, const uint8_t *keep, const int32_t *W, int64_t ldw, int reps, double *part,
-                                 int32_t *pcnt) {
-    if (JT == 1)
-        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 1>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
-    else if (JT == 2)
-        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 2>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
-    else
-        hipLaunchKernelGGL((k_bs_contract<KIND, PAIR, 4>), grid, dim3(256), 0, rt().stream, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
+// (kind, pair, JT) -> the instantiation of k_bs_contract for a layout
+template <class Layout>
+using BsContractFn = void (*)(Layout, const double *, const double *, int64_t, int, int64_t, int64_t, const int32_t *, int64_t, int,
+                              double *);
+
+template <class L>
+static BsContractFn<L> bs_contract_kernel(int kind, bool pair, int JT) {
+    static const BsContractFn<L> fn[3][2][3] = {
+        {{k_bs_contract<MLMC_LEGENDRE, false, 1, L>, k_bs_contract<MLMC_LEGENDRE, false, 2, L>, k_bs_contract<MLMC_LEGENDRE, false, 4, L>},
+         {k_bs_contract<MLMC_LEGENDRE, true, 1, L>, k_bs_contract<MLMC_LEGENDRE, true, 2, L>, k_bs_contract<MLMC_LEGENDRE, true, 4, L>}},
+        {{k_bs_contract<MLMC_MONOMIAL, false, 1, L>, k_bs_contract<MLMC_MONOMIAL, false, 2, L>, k_bs_contract<MLMC_MONOMIAL, false, 4, L>},
+         {k_bs_contract<MLMC_MONOMIAL, true, 1, L>, k_bs_contract<MLMC_MONOMIAL, true, 2, L>, k_bs_contract<MLMC_MONOMIAL, true, 4, L>}},
+        {{k_bs_contract<MLMC_FOURIER, false, 1, L>, k_bs_contract<MLMC_FOURIER, false, 2, L>, k_bs_contract<MLMC_FOURIER, false, 4, L>},
+         {k_bs_contract<MLMC_FOURIER, true, 1, L>, k_bs_contract<MLMC_FOURIER, true, 2, L>, k_bs_contract<MLMC_FOURIER, true, 4, L>}}};
+    return fn[kind == MLMC_LEGENDRE ? 0 : (kind == MLMC_MONOMIAL ? 1 : 2)][pair][JT / 2];
 }
 
-static void launch_contract(int JT, dim3 grid, const BasisParams &bp, const double *f, const double *c, int64_t n, int M, int R,
-                            int64_t i0, int64_t nr, const uint8_t *keep, const int32_t *W, int64_t ldw, int reps, double *part,
-                            int32_t *pcnt) {
-#define MLMC_BS_KIND(K)                                                                                                    \
-    if (c) launch_contract_kind<K, true>(JT, grid, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);             \
-    else launch_contract_kind<K, false>(JT, grid, bp, f, c, n, M, R, i0, nr, keep, W, ldw, reps, part, pcnt);
-    if (bp.kind == MLMC_LEGENDRE) { MLMC_BS_KIND(MLMC_LEGENDRE) }
-    else if (bp.kind == MLMC_MONOMIAL) { MLMC_BS_KIND(MLMC_MONOMIAL) }
-    else { MLMC_BS_KIND(MLMC_FOURIER) }
-#undef MLMC_BS_KIND
-}
-
-template <int KIND, bool PAIR>
-static void launch_contract_multi_kind(int JT, dim3 grid, const BasisParams *tab, const double *f, const double *c, int64_t n, int M,
-                                       int K, int64_t i0, int64_t nr, const uint8_t *keep, int64_t ldk, const int32_t *W, int64_t ldw,
-                                       int reps, double *part) {
-    if (JT == 1)
-        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 1>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
-    else if (JT == 2)
-        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 2>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
-    else
-        hipLaunchKernelGGL((k_bs_contract_multi<KIND, PAIR, 4>), grid, dim3(256), 0, rt().stream, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
-}
-
-static void launch_contract_multi(int kind, int JT, dim3 grid, const BasisParams *tab, const double *f, const double *c, int64_t n,
-                                  int M, int K, int64_t i0, int64_t nr, const uint8_t *keep, int64_t ldk, const int32_t *W,
-                                  int64_t ldw, int reps, double *part) {
-#define MLMC_BS_KIND(KD)                                                                                                          \
-    if (c) launch_contract_multi_kind<KD, true>(JT, grid, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);             \
-    else launch_contract_multi_kind<KD, false>(JT, grid, tab, f, c, n, M, K, i0, nr, keep, ldk, W, ldw, reps, part);
-    if (kind == MLMC_LEGENDRE) { MLMC_BS_KIND(MLMC_LEGENDRE) }
-    else if (kind == MLMC_MONOMIAL) { MLMC_BS_KIND(MLMC_MONOMIAL) }
-    else { MLMC_BS_KIND(MLMC_FOURIER) }
-#undef MLMC_BS_KIND
+// the contraction of one (replicate group, sample range, component group) and its reduction into the totals the layout names
+template <class Layout>
+static int bs_contract_reduce(const Layout &lay, int kind, int JT, dim3 grid, const double *f, const double *c, int64_t n, int M,
+                              int64_t i0, int64_t len, const BsScratch &sc, int64_t ldw, int64_t g, int ng) {
+    const int JB = 16 * JT;
+    hipLaunchKernelGGL(bs_contract_kernel<Layout>(kind, c != nullptr, JT), grid, dim3(256), 0, rt().stream, lay, f, c, n, M, i0, len,
+                       sc.w, ldw, ng, sc.part);
+    MLMC_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_bs_reduce<Layout>, dim3((unsigned)cdiv(BS_REPS * 2 * JB, 256), grid.y, grid.z), dim3(256), 0, rt().stream, lay,
+                       sc.part, (int)grid.x, JB, g, ng);
+    MLMC_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // components per group of the per-component route: at most BS_MAX_COLS group columns of K + 1 each
 static int64_t bs_group_comps(int64_t M, int64_t K) { return std::min<int64_t>(M, std::max<int64_t>(1, BS_MAX_COLS / (K + 1))); }
 
-// One chunk of a per-component handle (mlmc_bootstrap_accum has checked the arguments; ds: the device view of the pinned sizes).
-// Per (replicate group, sample range): the weight slab and the keep bytes of all M components once, then per component group the
-// contraction and its fixed-order reduction.  The range and the column blocks are functions of n, M and K only.
-static int bs_accum_multi(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n, const int64_t *sizes,
-                          const int64_t *ds, uint64_t seed, uint32_t stream) {
-    const int64_t B = a->B, M = a->M, K = a->R, K1 = K + 1;
-    const int64_t mg = bs_group_comps(M, K);
-    const int64_t cg = mg * K1;                                          // columns of the largest group
-    const int JT = cg <= 16 ? 1 : (cg <= 32 ? 2 : 4);
+// How a chunk of n samples is cut: column blocks of 16 JT, sample ranges of nr, replicate groups of BG.  JT and nr are functions
+// of n, the columns of the largest component group and the tiles the keep bytes allow -- never of B: a replicate's summation
+// order must not depend on it.
+struct BsPlan {
+    int JT;
+    int64_t nr, BG;
+};
+
+static BsPlan bs_plan(int64_t n, int64_t B, int64_t cols, int64_t keep_tiles) {
+    const int JT = cols <= 16 ? 1 : (cols <= 32 ? 2 : 4);
     const int JB = 16 * JT;
-    const int64_t ncb_max = cdiv(cg, JB);
+    const int64_t ncb = cdiv(cols, JB);
     const int64_t n_tiles = cdiv(n, BS_TILE);
-    const size_t pwb = (size_t)BS_REPS * 2 * JB * sizeof(double);
-    constexpr int SPT = BS_TILE / BS_SW;
-    const int64_t tpr = std::max<int64_t>(1, std::min<int64_t>({n_tiles, (int64_t)BS_TPR_MAX, a->keep_tiles,
-                                                                 (int64_t)(BS_PART_BYTES / (pwb * SPT * ncb_max))}));
-    const int64_t nr = tpr * BS_TILE;
-    const int64_t ldk = a->keep_tiles * BS_TILE;
+    const size_t pwb = (size_t)BS_REPS * 2 * JB * sizeof(double);      // partial row block of one workgroup
+    constexpr int SPT = BS_TILE / BS_SW;                                 // slices per tile
+    const int64_t tpr = std::max<int64_t>(1, std::min<int64_t>({n_tiles, (int64_t)BS_TPR_MAX, keep_tiles,
+                                                                 (int64_t)(BS_PART_BYTES / (pwb * SPT * ncb))}));
     const int64_t nx_full = tpr * SPT;
-    int64_t ny = std::min<int64_t>({cdiv(B, BS_REPS), (int64_t)BS_NY_MAX, (int64_t)(BS_PART_BYTES / (pwb * nx_full * ncb_max)),
+    int64_t ny = std::min<int64_t>({cdiv(B, BS_REPS), (int64_t)BS_NY_MAX, (int64_t)(BS_PART_BYTES / (pwb * nx_full * ncb)),
                                     (int64_t)(BS_COUNTS_BYTES / (4 * (size_t)BS_REPS * n_tiles))});
     ny = std::max<int64_t>(ny, 1);
-    const int64_t BG = ny * BS_REPS;
-    const int kind = a->bases[0]->p.kind;
-    const int64_t ld_tot = M * (2 * K + 1);
+    return BsPlan{JT, tpr * BS_TILE, ny * BS_REPS};
+}
+
+// One chunk (mlmc_bootstrap_accum has checked the arguments; ds: the device view of the pinned sizes).  Per (replicate group,
+// sample range): the weight slab and the keep bytes once, then per component group the contraction and its fixed-order reduction.
+// The shared-basis handle has one group of all M components.
+static int bs_accum(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n, const int64_t *sizes,
+                    const int64_t *ds, uint64_t seed, uint32_t stream) {
+    const int64_t B = a->B, M = a->M, R = a->R;
+    const int64_t cw = a->multi ? R + 1 : R;                             // columns per component
+    const int64_t mg = a->multi ? bs_group_comps(M, R) : M;
+    const BsPlan p = bs_plan(n, B, mg * cw, a->keep_tiles);
+    const int JT = p.JT, JB = 16 * JT;
+    const int64_t nr = p.nr, BG = p.BG;
+    const int64_t ldk = a->keep_tiles * BS_TILE;
+    const int64_t ld_tot = a->multi ? M * (2 * R + 1) : 2 * M * R;
+    const BasisParams bp = a->basis->p;
     double *tot = a->d_tot + (size_t)level * B * ld_tot;
     for (int64_t g = 0; g < B; g += BG) {
         const int64_t ng = std::min(BG, B - g);
@@ -588,26 +544,40 @@ static int bs_accum_multi(mlmc_bootstrap *a, int32_t level, const double *fine, 
             if (int rc = launch_expand(n, ng, i0 / BS_TILE, nt, a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
             if (int rc = bs_time(a, 0, true)) return rc;
             if (int rc = bs_time(a, 1, false)) return rc;
-            hipLaunchKernelGGL(k_bs_keep_multi, dim3((unsigned)cdiv(len, 256), (unsigned)M), dim3(256), 0, rt().stream, a->d_tab, fine,
-                               coarse, n, (int)M, i0, len, ldk, a->d_keep_m);
+            if (a->multi)
+                hipLaunchKernelGGL(k_bs_keep_multi, dim3((unsigned)cdiv(len, 256), (unsigned)M), dim3(256), 0, rt().stream, a->d_tab, fine,
+                                   coarse, n, (int)M, i0, len, ldk, a->d_keep_m);
+            else
+                hipLaunchKernelGGL(k_bs_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, bp, fine, coarse, n, (int)M, i0,
+                                   len, a->sc.keep);
             MLMC_HIP_CHECK(hipGetLastError());
+            // executed matrix-core flops: every batch of every workgroup runs KB / 4 k-steps of 2 JT MFMAs per wave
             const int64_t batches = (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
             for (int64_t m0 = 0; m0 < M; m0 += mg) {
                 const int64_t mc = std::min(mg, M - m0);
-                const int cols = (int)(mc * K1);
+                const int cols = (int)(mc * cw);
                 const int64_t ncb = cdiv(cols, JB);
                 const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
-                launch_contract_multi(kind, JT, grid, a->d_tab + m0, fine + m0 * n, coarse ? coarse + m0 * n : nullptr, n, (int)mc, (int)K,
-                                      i0, len, a->d_keep_m + m0 * ldk, ldk, a->sc.w, nr, (int)ng, a->sc.part);
-                MLMC_HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_bs_reduce_multi, dim3((unsigned)cdiv(BS_REPS * 2 * JB, 256), (unsigned)nyg, (unsigned)ncb), dim3(256), 0,
-                                   rt().stream, a->sc.part, (int)nx, JB, cols, (int)K, m0, ld_tot, g, (int)ng, tot);
-                MLMC_HIP_CHECK(hipGetLastError());
+                const double *f = fine + m0 * n, *c = coarse ? coarse + m0 * n : nullptr;
+                const int rc = a->multi
+                    ? bs_contract_reduce(BsPerComponent{a->d_tab + m0, a->d_keep_m + m0 * ldk, ldk, (int)R, cols, tot + m0 * (2 * R + 1), ld_tot},
+                                         bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng)
+                    : bs_contract_reduce(BsSharedBasis{bp, a->sc.keep, (int)R, cols, a->sc.pcnt, tot, a->d_cnt + (size_t)level * B},
+                                         bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng);
+                if (rc) return rc;
                 a->flops += batches * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
             }
             if (int rc = bs_time(a, 1, true)) return rc;
         }
     }
+    return 0;
+}
+
+// what both create functions check first (e: the entry point's name)
+static int bs_create_check(const std::string &e, int32_t n_levels, int64_t B) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (n_levels < 1 || n_levels > 2047) return fail(e + ": n_levels = " + std::to_string(n_levels) + " (must be in 1 .. 2047)");
+    if (B < 1 || B > (int64_t)INT32_MAX) return fail(e + ": B = " + std::to_string(B) + " (must be in 1 .. 2^31 - 1)");
     return 0;
 }
 
@@ -654,20 +624,18 @@ extern "C" int mlmc_bootstrap_weights(int64_t n, int64_t b0, int64_t nb, const i
 extern "C" int mlmc_bootstrap_create(const mlmc_basis *b, int32_t M, int32_t n_levels, int64_t B, mlmc_bootstrap **out) {
     MLMC_API_GUARD;
     using namespace mlmc;
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (!b || !out) return fail("mlmc_bootstrap_create: null argument (basis, out)");
+    const std::string e("mlmc_bootstrap_create");
+    if (int rc = bs_create_check(e, n_levels, B)) return rc;
+    if (!b || !out) return fail(e + ": null argument (basis, out)");
     if (b->p.kind != MLMC_LEGENDRE && b->p.kind != MLMC_MONOMIAL && b->p.kind != MLMC_FOURIER)
-        return fail("mlmc_bootstrap_create: basis kind " + std::to_string(b->p.kind) +
-                    " is not supported (Legendre, monomial and Fourier moments only)");
-    if (b->out_size > 0) return fail("mlmc_bootstrap_create: transformed bases are not supported");
+        return fail(e + ": basis kind " + std::to_string(b->p.kind) + " is not supported (Legendre, monomial and Fourier moments only)");
+    if (b->out_size > 0) return fail(e + ": transformed bases are not supported");
     if (b->p.kind == MLMC_LEGENDRE && b->p.size > LEGENDRE_MAX_TERMS)
-        return fail("mlmc_bootstrap_create: Legendre size " + std::to_string(b->p.size) + " (at most " + std::to_string(LEGENDRE_MAX_TERMS) + ")");
-    if (M < 1) return fail("mlmc_bootstrap_create: M = " + std::to_string(M) + " (must be >= 1)");
+        return fail(e + ": Legendre size " + std::to_string(b->p.size) + " (at most " + std::to_string(LEGENDRE_MAX_TERMS) + ")");
+    if (M < 1) return fail(e + ": M = " + std::to_string(M) + " (must be >= 1)");
     if ((int64_t)M * b->p.size > BS_MAX_COLS)
-        return fail("mlmc_bootstrap_create: M * R = " + std::to_string((int64_t)M * b->p.size) + " columns, at most " +
-                    std::to_string(BS_MAX_COLS) + " are supported");
-    if (n_levels < 1 || n_levels > 2047) return fail("mlmc_bootstrap_create: n_levels = " + std::to_string(n_levels) + " (must be in 1 .. 2047)");
-    if (B < 1 || B > (int64_t)INT32_MAX) return fail("mlmc_bootstrap_create: B = " + std::to_string(B) + " (must be in 1 .. 2^31 - 1)");
+        return fail(e + ": M * R = " + std::to_string((int64_t)M * b->p.size) + " columns, at most " + std::to_string(BS_MAX_COLS) +
+                    " are supported");
     mlmc_bootstrap *a = new mlmc_bootstrap();
     a->basis = b;
     a->M = M;
@@ -675,15 +643,13 @@ extern "C" int mlmc_bootstrap_create(const mlmc_basis *b, int32_t M, int32_t n_l
     a->R = b->p.size;
     a->MR = M * b->p.size;
     a->B = B;
-    const size_t tot = sizeof(double) * (size_t)n_levels * (size_t)B * 2 * (size_t)a->MR;
+    a->keep_tiles = BS_TPR_MAX;
+    const size_t tot = a->tot_bytes();
     if (hipMalloc((void **)&a->d_tot, tot) != hipSuccess || hipMalloc((void **)&a->d_cnt, sizeof(int64_t) * (size_t)n_levels * B) != hipSuccess ||
         bs_scratch_alloc(a->sc) != 0) {
         (void)hipGetLastError();
-        if (a->d_tot) (void)hipFree(a->d_tot);
-        if (a->d_cnt) (void)hipFree(a->d_cnt);
-        bs_scratch_free(a->sc);
-        delete a;
-        return fail("mlmc_bootstrap_create: out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch)");
+        mlmc_bootstrap_destroy(a);
+        return fail(e + ": out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch)");
     }
     MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, tot, rt().stream));
     MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)n_levels * B, rt().stream));
@@ -741,57 +707,7 @@ extern "C" int mlmc_bootstrap_accum(mlmc_bootstrap *a, int32_t level, const doub
     std::memcpy(hs, sizes, sizeof(int64_t) * (size_t)B);
     int64_t *ds = nullptr;
     MLMC_HIP_CHECK(hipHostGetDevicePointer((void **)&ds, hs, 0));
-    if (a->multi) return bs_accum_multi(a, level, fine, coarse, n, sizes, ds, seed, stream);
-
-    const int MR = a->MR;
-    const int JT = MR <= 16 ? 1 : (MR <= 32 ? 2 : 4);
-    const int JB = 16 * JT;
-    const int ncb = (int)cdiv(MR, JB);
-    const int64_t n_tiles = cdiv(n, BS_TILE);
-    const size_t pwb = (size_t)BS_REPS * 2 * JB * sizeof(double);      // partial row block of one workgroup
-    constexpr int SPT = BS_TILE / BS_SW;                                 // slices per tile
-    // sample range: a function of n and the column blocks only (a replicate's summation order must not depend on B)
-    const int64_t tpr = std::max<int64_t>(1, std::min<int64_t>({n_tiles, (int64_t)BS_TPR_MAX, (int64_t)(BS_PART_BYTES / (pwb * SPT * ncb))}));
-    const int64_t nr = tpr * BS_TILE;
-    const int64_t nx_full = tpr * SPT;
-    int64_t ny = std::min<int64_t>({cdiv(B, BS_REPS), (int64_t)BS_NY_MAX, (int64_t)(BS_PART_BYTES / (pwb * nx_full * ncb)),
-                                    (int64_t)(BS_COUNTS_BYTES / (4 * (size_t)BS_REPS * n_tiles))});
-    ny = std::max<int64_t>(ny, 1);
-    const int64_t BG = ny * BS_REPS;
-    const BasisParams bp = a->basis->p;
-    double *tot = a->d_tot + (size_t)level * B * 2 * MR;
-    int64_t *cnt = a->d_cnt + (size_t)level * B;
-    const dim3 rgrid((unsigned)cdiv(BS_REPS * 2 * JB, 256), 0, (unsigned)ncb);
-    for (int64_t g = 0; g < B; g += BG) {
-        const int64_t ng = std::min(BG, B - g);
-        const int64_t nyg = cdiv(ng, BS_REPS);
-        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
-        if (int rc = bs_time(a, 0, false)) return rc;
-        if (int rc = launch_tile_counts(n, ng, ds + g, mx, g, seed, stream, a->sc.counts)) return rc;
-        if (int rc = bs_time(a, 0, true)) return rc;
-        for (int64_t i0 = 0; i0 < n; i0 += nr) {
-            const int64_t len = std::min(nr, n - i0);
-            const int64_t nt = cdiv(len, BS_TILE), nx = cdiv(len, BS_SW);
-            if (int rc = bs_time(a, 0, false)) return rc;
-            if (int rc = launch_expand(n, ng, i0 / BS_TILE, nt, a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
-            if (int rc = bs_time(a, 0, true)) return rc;
-            if (int rc = bs_time(a, 1, false)) return rc;
-            hipLaunchKernelGGL(k_bs_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, bp, fine, coarse, n, a->M, i0, len,
-                               a->sc.keep);
-            MLMC_HIP_CHECK(hipGetLastError());
-            const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
-            launch_contract(JT, grid, bp, fine, coarse, n, a->M, a->R, i0, len, a->sc.keep, a->sc.w, nr, (int)ng, a->sc.part, a->sc.pcnt);
-            MLMC_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_bs_reduce, dim3(rgrid.x, (unsigned)nyg, rgrid.z), dim3(256), 0, rt().stream, a->sc.part, a->sc.pcnt,
-                               (int)nx, JB, MR, g, (int)ng, tot, cnt);
-            MLMC_HIP_CHECK(hipGetLastError());
-            if (int rc = bs_time(a, 1, true)) return rc;
-            // executed matrix-core flops: every batch of every workgroup runs KB / 4 k-steps of 2 JT MFMAs per wave
-            const int64_t batches = (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
-            a->flops += batches * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
-        }
-    }
-    return 0;
+    return bs_accum(a, level, fine, coarse, n, sizes, ds, seed, stream);
 }
 
 extern "C" int mlmc_bootstrap_finalize(mlmc_bootstrap *a, int64_t *n_out, double *s_out, double *sp_out) {
@@ -828,12 +744,10 @@ extern "C" int mlmc_bootstrap_create_multi(int32_t M, const mlmc_basis *const *b
     MLMC_API_GUARD;
     using namespace mlmc;
     const std::string e("mlmc_bootstrap_create_multi");
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (int rc = bs_create_check(e, n_levels, B)) return rc;
     if (!bases || !out) return fail(e + ": null argument (bases, out)");
     if (M < 1 || M > 65535) return fail(e + ": M = " + std::to_string(M) + " (must be in 1 .. 65535)");
     if (K < 1 || K > 512) return fail(e + ": K must be in 1..512");
-    if (n_levels < 1 || n_levels > 2047) return fail(e + ": n_levels = " + std::to_string(n_levels) + " (must be in 1 .. 2047)");
-    if (B < 1 || B > (int64_t)INT32_MAX) return fail(e + ": B = " + std::to_string(B) + " (must be in 1 .. 2^31 - 1)");
     std::vector<BasisParams> bps(M);
     for (int m = 0; m < M; ++m) {
         const mlmc_basis *b = bases[m];
@@ -868,11 +782,7 @@ extern "C" int mlmc_bootstrap_create_multi(int32_t M, const mlmc_basis *const *b
     if (hipMalloc((void **)&a->d_tot, tot) != hipSuccess || hipMalloc((void **)&a->d_tab, sizeof(BasisParams) * (size_t)M) != hipSuccess ||
         hipMalloc((void **)&a->d_keep_m, (size_t)M * a->keep_tiles * BS_TILE) != hipSuccess || bs_scratch_alloc(a->sc) != 0) {
         (void)hipGetLastError();
-        if (a->d_tot) (void)hipFree(a->d_tot);
-        if (a->d_tab) (void)hipFree(a->d_tab);
-        if (a->d_keep_m) (void)hipFree(a->d_keep_m);
-        bs_scratch_free(a->sc);
-        delete a;
+        mlmc_bootstrap_destroy(a);
         return fail(e + ": out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch + keep bytes)");
     }
     hipError_t err = hipMemcpy(a->d_tab, bps.data(), sizeof(BasisParams) * (size_t)M, hipMemcpyHostToDevice);
@@ -903,7 +813,7 @@ extern "C" int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *a, int64_t *n_out, 
                 const double *t = tot.data() + ((l * B + b) * M + m) * C;
                 const std::vector<double> &c = a->bases[m]->scale_c;     // Legendre: P_k = c_k q_k; else ones
                 const int64_t o = (b * L + l) * M + m;
-                n_out[o] = (int64_t)t[2 * K];                            // an exact integer (k_bs_contract_multi)
+                n_out[o] = (int64_t)t[2 * K];                            // an exact integer (BsPerComponent)     
                 for (int64_t k = 0; k < K; ++k) {
                     s_out[o * K + k] = c[k] * t[k];
                     sp_out[o * K + k] = (c[k] * c[k]) * t[K + k];

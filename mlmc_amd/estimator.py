@@ -316,33 +316,18 @@ class Estimate:
         :return: BootstrapReplicates(n_samples [B, L], l_means, l_vars, mean, var -- leading axis B -- and the seed)
         Legendre, monomial and Fourier moments only (log / safe_eval included); est_bootstrap serves the others."""
         from .moments import Legendre, Monomial, Fourier
-        from .quantity import quantity as qmod
         if moments_fn is None:
             moments_fn = self._moments_fn
         if type(moments_fn) not in (Legendre, Monomial, Fourier):
             raise ValueError("est_bootstrap_batch: {} moments are not supported (Legendre, Monomial and Fourier are); use "
                              "est_bootstrap for them".format(type(moments_fn).__name__))
-        if isinstance(n_subsamples, (bool, np.bool_)) or not isinstance(n_subsamples, (int, np.integer)) or n_subsamples < 1:
-            raise ValueError("est_bootstrap_batch: n_subsamples must be an integer >= 1, got {!r}".format(n_subsamples))
-        n_levels = self._sample_storage.get_n_levels()
-        n_coll = np.array(self._sample_storage.get_n_collected())[:n_levels]
-        k = determine_sample_vec(n_collected_samples=n_coll, n_levels=n_levels, sample_vector=sample_vector)
-        if k.shape != (n_levels,) or not np.all(np.isfinite(k.astype(np.float64))) or np.any(k != np.round(k)):
-            raise ValueError("est_bootstrap_batch: sample_vector must hold one integer per level, got {!r}".format(sample_vector))
-        k = k.astype(np.int64)
-        if np.any(k < 0) or np.any(k > n_coll):
-            raise ValueError("est_bootstrap_batch: sample_vector {} must lie in 0 .. n_collected {} on every level".format(
-                k.tolist(), n_coll.tolist()))
         if int(self._quantity.size()) * moments_fn.size > 2048:
             raise ValueError("est_bootstrap_batch: {} components x {} moments, at most 2048 columns are supported".format(
                 int(self._quantity.size()), moments_fn.size))
-        if seed is None:
-            seed = int(qmod.RNG.integers(0, 2 ** 63 - 1))
-        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError("est_bootstrap_batch: seed must be an integer in [0, 2^64), got {!r}".format(seed))
-        seed = int(seed)
+        n_subsamples, k, seed = self._bootstrap_args("est_bootstrap_batch", n_subsamples, sample_vector, seed)
+        n_coll = np.array(self._sample_storage.get_n_collected())[:len(k)]
         self._moments_fn = moments_fn
-        n, s, sp = qe.bootstrap_moments(self._quantity, moments_fn, int(n_subsamples), k, seed)
+        n, s, sp = qe.bootstrap_moments(self._quantity, moments_fn, n_subsamples, k, seed)
         r = qe.bootstrap_statistics(self._quantity, moments_fn, n, s, sp)
         self.mean_bs_mean = np.mean(r["mean"], axis=0)
         self.mean_bs_var = np.mean(r["var"], axis=0)
@@ -355,19 +340,10 @@ class Estimate:
         self._bs_level_mean_variance = self.var_bs_l_means * n_coll.reshape((-1,) + (1,) * (self.var_bs_l_means.ndim - 1))
         return BootstrapReplicates(r["n_samples"], r["l_means"], r["l_vars"], r["mean"], r["var"], seed)
 
-    def _component_bootstrap_args(self, what, n_subsamples, sample_vector, moments_fns, seed):
-        """The arguments of the per-component bootstrap, checked as est_bootstrap_batch checks its own, before any device work.
-        -> (moments objects [M], B, k [L] int64, seed)"""
+    def _bootstrap_args(self, what, n_subsamples, sample_vector, seed):
+        """The replicate count, the requested samples per level and the seed of a batched bootstrap (`what`: the caller's name),
+        checked before any device work.  -> (B, k [L] int64, seed)"""
         from .quantity import quantity as qmod
-        fns = self._component_fns(moments_fns, what)
-        from .moments import Legendre, Monomial, Fourier
-        names = sorted({type(fn).__name__ for fn in fns})
-        if len(names) != 1 or type(fns[0]) not in (Legendre, Monomial, Fourier):
-            raise ValueError("{}: {} moments are not supported (Legendre, Monomial or Fourier objects of ONE family are); use "
-                             "est_bootstrap or est_bootstrap_batch on scalar_component(quantity, m) for them".format(
-                                 what, " / ".join(names)))
-        if int(fns[0].size) > 512:
-            raise ValueError("{}: {} moments per component, at most 512 are supported".format(what, int(fns[0].size)))
         if isinstance(n_subsamples, (bool, np.bool_)) or not isinstance(n_subsamples, (int, np.integer)) or n_subsamples < 1:
             raise ValueError("{}: n_subsamples must be an integer >= 1, got {!r}".format(what, n_subsamples))
         n_levels = self._sample_storage.get_n_levels()
@@ -384,7 +360,21 @@ class Estimate:
             seed = int(qmod.RNG.integers(0, 2 ** 63 - 1))
         if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
             raise ValueError("{}: seed must be an integer in [0, 2^64), got {!r}".format(what, seed))
-        return fns, int(n_subsamples), k, int(seed)
+        return int(n_subsamples), k, int(seed)
+
+    def _component_bootstrap_args(self, what, n_subsamples, sample_vector, moments_fns, seed):
+        """The arguments of the per-component bootstrap, checked before any device work.
+        -> (moments objects [M], B, k [L] int64, seed)"""
+        fns = self._component_fns(moments_fns, what)
+        from .moments import Legendre, Monomial, Fourier
+        names = sorted({type(fn).__name__ for fn in fns})
+        if len(names) != 1 or type(fns[0]) not in (Legendre, Monomial, Fourier):
+            raise ValueError("{}: {} moments are not supported (Legendre, Monomial or Fourier objects of ONE family are); use "
+                             "est_bootstrap or est_bootstrap_batch on scalar_component(quantity, m) for them".format(
+                                 what, " / ".join(names)))
+        if int(fns[0].size) > 512:
+            raise ValueError("{}: {} moments per component, at most 512 are supported".format(what, int(fns[0].size)))
+        return (fns,) + self._bootstrap_args(what, n_subsamples, sample_vector, seed)
 
     def est_bootstrap_components(self, n_subsamples=100, sample_vector=None, moments_fns=None, seed=None):
         """est_bootstrap_batch of EVERY scalar component of the quantity under its own moments object, from one device pass per

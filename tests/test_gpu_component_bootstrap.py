@@ -23,9 +23,9 @@ def hip():
     return _lib
 
 
-def _component_levels(M, seed=7, positive=False):
+def _component_levels(M, seed=7, positive=False, n_samples=N):
     """_levels plus NaNs at other samples of the inner components: every component has a mask of its own"""
-    levels = _levels(N, M, seed=seed, positive=positive)
+    levels = _levels(n_samples, M, seed=seed, positive=positive)
     for l, (f, c) in enumerate(levels):
         for m in range(1, M - 1):
             f[m, (3 + m)::(50 + 7 * m)] = np.nan
@@ -115,6 +115,44 @@ def test_default_moments_fn_serves_every_component(hip):
     b = Estimate(q, st).est_bootstrap_components(20, sample_vector=K_REQ, moments_fns=[fn] * 3, seed=5)
     for name in ("n_samples", "l_means", "l_vars", "mean", "var"):
         assert np.array_equal(getattr(a, name), getattr(b, name)), name
+
+
+# ---- 1b. the two routes of the library agree bit for bit ------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [9001, 40000])
+@pytest.mark.parametrize("family", ["legendre", "monomial"])
+def test_component_route_equals_one_component_route_bit_for_bit(hip, family, n):
+    """mlmc_bootstrap_create_multi against mlmc_bootstrap_create on one row at a time, at the engine level: both routes evaluate the
+    same term sequence, feed the same MFMA k-steps in the same order and add slices and ranges in the same fixed order, and a sample
+    component m drops contributes exact zeros in both, so n, s and sp of component m are EQUAL whenever both cut the same sample
+    ranges (M (K + 1) <= 256 and M <= 256).  M = 5, K = 7: 40 columns, JT = 4 and column blocks that straddle components against
+    the 7 columns (JT = 1) of a single component; B = 70: a full and a partial 64-replicate tile; n = 9001: three tiles, partial
+    last tile, 512-sample slice and 64-sample batch; n = 40000: two sample ranges in both routes.  A level-0 chunk and a pair."""
+    import torch
+    from mlmc_amd import Legendre, Monomial, engine
+    from mlmc_amd.quantity import quantity_estimate as qe
+    M, K, seed = 5, 7, 4711
+    fns = [{"legendre": Legendre, "monomial": Monomial}[family](K, d) for d in _domains(M)]
+    levels = [(torch.from_numpy(f).cuda(), None if c is None else torch.from_numpy(c).cuda())
+              for f, c in _component_levels(M, seed=23, n_samples=[n, n])]
+    rng = np.random.default_rng(n)
+    sizes = [np.concatenate(([0, n, 1], rng.integers(0, n + 1, size=B - 3))) for _ in levels]
+
+    def run(acc, rows):
+        for l, (f, c) in enumerate(levels):
+            acc.accum(l, f[rows].contiguous(), None if c is None else c[rows].contiguous(), sizes[l], seed, qe.bootstrap_stream(l, 0))
+        out = acc.finalize()
+        acc.close()
+        return out
+    n_all, s_all, sp_all = run(engine.ComponentBootstrapAccumulator(fns, K, 2, B), slice(0, M))
+    assert np.all(n_all[0] == 0) and n_all[1].min() > 0                                # replicates 0 and 1 pick 0 and n samples
+    assert len({tuple(n_all[1, :, m]) for m in range(M)}) > 1                          # the masks do differ
+    for m in range(M):
+        n_one, s_one, sp_one = run(engine.BootstrapAccumulator(fns[m], 1, 2, B), slice(m, m + 1))
+        for name, got, want in (("n", n_all[:, :, m], n_one), ("s", s_all[:, :, m], s_one), ("sp", sp_all[:, :, m], sp_one)):
+            diff = np.argwhere(got != want)
+            print(family, n, "component", m, name, "differing elements", len(diff),
+                  "first", None if not len(diff) else (tuple(diff[0]), got[tuple(diff[0])], want[tuple(diff[0])]))
+            assert np.array_equal(got, want), (m, name)
 
 
 # ---- 2. a planted mask ----------------------------------------------------------------------------------------------------------------

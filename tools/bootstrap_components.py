@@ -6,9 +6,9 @@ its own per component, B replicates, half of every level requested:
   loop_ms      host wall time of the M calls Estimate(scalar_component(q, m), st, fns[m]).est_bootstrap_batch(B, k, seed)
   comp_ms      host wall time of Estimate(q, st).est_bootstrap_components(B, k, fns, seed)
                (both: median of the repetitions, the two alternating on the same device; `reps` says how many were taken)
-  contract_ms  HIP-event time of the contraction launches (keep bytes, k_bs_contract_multi, k_bs_reduce_multi) of one accumulation
-               of the same chunks and sizes (engine.ComponentBootstrapAccumulator), mfma_frac = executed MFMA flops / contract
-               time / 78.6 TFLOP/s
+  contract_ms  HIP-event time of the contraction launches (keep bytes, k_bs_contract and k_bs_reduce under the per-component layout) of one
+               accumulation of the same chunks and sizes (engine.ComponentBootstrapAccumulator), mfma_frac = executed MFMA flops /
+               contract time / 78.6 TFLOP/s
   rng_ms       HIP-event time of the weight passes (tile counts, expansion)
 
 at M = 16, 64, 256, R = 16, 25, B = 300 and n = 10^4, 10^5, 10^6.  With --bands: Estimate.bootstrap_component_quantiles at M = 64,
