@@ -1,12 +1,13 @@
-// Per-component moment sums of a vector quantity (gfx950): M basis descriptors, ONE pass over each stored chunk.  Mean-only
-// (k_moments_multi, below) and with the sums of squares (k_moments_multi_var, further down: the level variances).
+// Per-component moment sums of a vector quantity (gfx950): M basis descriptors, ONE pass over each stored chunk, with or
+// without the sums of squares (SQ: the level variances).
 //
 // Estimate.construct_densities needs, per scalar component m, the level sums of K = linearize.extended_size(fn_m) moments of
 // fn_m's family (the covariance mean by the product linearisation, the orthogonal-moments mean as T_m times the first R of
-// them) -- each component masked and clipped ON ITS OWN.  The scalar chain runs two estimates per component; here one launch
-// per (level, chunk) covers every component: grid (sample block, component, 32-term window), the component's BasisParams
-// from a device table, the window's sums in registers, fixed-order wave / block reductions, and a fixed-order merge of the
-// block partials into the level totals (k_multi_reduce), so the sums are the same bits run to run.
+// them) -- each component masked and clipped ON ITS OWN; the per-component moment estimates need the sums of squares too.  The
+// scalar chain runs its estimates per component; here one launch per (level, chunk) -- two with K > 32 -- covers every
+// component: grid (sample block, component, 32-term window), the component's BasisParams from a device table, the window's
+// sums in registers, fixed-order wave / block reductions, and a fixed-order merge of the block partials into the level totals
+// (k_multi_reduce), so the sums are the same bits run to run, and Σd is the same bits with and without Σd².
 // Keep rule per component = the scalar path's for a one-component chunk: transform_value keeps the fine value AND (above
 // level 0) the coarse value; a NaN is never kept.  The counts are therefore bit-identical to the scalar chain's.
 #include <algorithm>
@@ -19,104 +20,25 @@
 namespace mlmc {
 
 constexpr int MM_THREADS = 256;
-constexpr int MM_WIN = 32;            // terms per window (registers of one thread)
 constexpr int MM_MAX_K = 512;
-
-template <int KIND>
-__device__ __forceinline__ void mm_accumulate(const BasisParams &bp, const double *__restrict__ f, const double *__restrict__ c,
-                                              int64_t s0, int64_t s1, int k0, int K, double (&acc)[MM_WIN], int &kept,
-                                              int &removed) {
-    for (int64_t i = s0 + threadIdx.x; i < s1; i += MM_THREADS) {
-        bool kf, kc = true;
-        const double tf = transform_value(bp, f[i], kf);
-        const double tc = c ? transform_value(bp, c[i], kc) : 0.0;
-        const bool keep = kf && kc;
-        kept += keep;
-        removed += !keep;
-        const double w = keep ? 1.0 : 0.0;      // a dropped sample yields exactly 0 in every term
-        TermGen<KIND> gf, gc;
-        gf.init(keep ? tf : 0.0, w, bp);
-        gc.init(keep ? tc : 0.0, w, bp);
-        for (int k = 0; k < k0; ++k) {          // terms before the window (the recurrences run in order)
-            gf.next(k);
-            if (c) gc.next(k);
-        }
-#pragma unroll
-        for (int j = 0; j < MM_WIN; ++j) {
-            const int k = k0 + j;
-            if (k < K) {
-                const double vf = gf.next(k);
-                const double vc = c ? gc.next(k) : 0.0;
-                acc[j] += vf - vc;
-            }
-        }
-    }
-}
-
-// part[(m * nb + b) * K + k] = block b's sum of term k of component m; pcount[(m * nb + b) * 2 + {0, 1}] = kept / dropped
-__global__ __launch_bounds__(MM_THREADS) void k_moments_multi(const BasisParams *__restrict__ bps, const double *__restrict__ fine,
-                                                              const double *__restrict__ coarse, int64_t n, int K, int nb,
-                                                              double *__restrict__ part, int64_t *__restrict__ pcount) {
-    const int b = blockIdx.x, m = blockIdx.y, k0 = blockIdx.z * MM_WIN;
-    const BasisParams bp = bps[m];
-    const int64_t per = (n + nb - 1) / nb, s0 = std::min<int64_t>(n, (int64_t)b * per), s1 = std::min<int64_t>(n, s0 + per);
-    const double *f = fine + (int64_t)m * n;
-    const double *c = coarse ? coarse + (int64_t)m * n : nullptr;
-    double acc[MM_WIN];
-#pragma unroll
-    for (int j = 0; j < MM_WIN; ++j) acc[j] = 0.0;
-    int kept = 0, removed = 0;
-    switch (bp.kind) {
-        case MLMC_LEGENDRE: mm_accumulate<MLMC_LEGENDRE>(bp, f, c, s0, s1, k0, K, acc, kept, removed); break;
-        case MLMC_MONOMIAL: mm_accumulate<MLMC_MONOMIAL>(bp, f, c, s0, s1, k0, K, acc, kept, removed); break;
-        default: mm_accumulate<MLMC_FOURIER>(bp, f, c, s0, s1, k0, K, acc, kept, removed); break;
-    }
-    __shared__ double red[4][MM_WIN];
-    __shared__ int cred[4][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < MM_WIN; ++j) {
-        const double v = wave_sum(acc[j]);
-        if (lane == 0) red[wave][j] = v;
-    }
-    kept = wave_sum_i(kept);
-    removed = wave_sum_i(removed);
-    if (lane == 0) { cred[wave][0] = kept; cred[wave][1] = removed; }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < MM_WIN && k0 + t < K) part[((int64_t)m * nb + b) * K + k0 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-    if (blockIdx.z == 0 && t < 2) pcount[((int64_t)m * nb + b) * 2 + t] = ((int64_t)cred[0][t] + cred[1][t]) + ((int64_t)cred[2][t] + cred[3][t]);
-}
-
-// tot[(m) * K + k] += sum_b part[(m * nb + b) * K + k] in block order (one workgroup per component), counts likewise
-__global__ __launch_bounds__(MM_THREADS) void k_multi_reduce(const double *__restrict__ part, const int64_t *__restrict__ pcount,
-                                                             int K, int nb, double *__restrict__ tot, int64_t *__restrict__ tcount) {
-    const int m = blockIdx.x;
-    for (int k = threadIdx.x; k < K; k += MM_THREADS) {
-        double s = 0.0;
-        for (int b = 0; b < nb; ++b) s += part[((int64_t)m * nb + b) * K + k];
-        tot[(int64_t)m * K + k] += s;
-    }
-    if (threadIdx.x < 2) {
-        int64_t s = 0;
-        for (int b = 0; b < nb; ++b) s += pcount[((int64_t)m * nb + b) * 2 + threadIdx.x];
-        tcount[(int64_t)m * 2 + threadIdx.x] += s;
-    }
-}
-
-// ---- mean + variance: k_moments_multi_var ------------------------------------------------------------------------------
-// Σd and Σd² of up to NW terms of one component per workgroup, grid (sample block, component, term window).  Each lane takes
-// two samples per trip (four independent recurrences for a fine / coarse pair) and issues the next trip's loads before the
-// current trip's arithmetic, as the scalar kernel does (moments.hip, accum_samples).  The tile is computed whole: terms >= K
-// of the last window are evaluated and discarded (no run-time guard inside the unrolled loop).  A window at k0 > 0 first
-// walks the k0 terms before it -- the first 32 with compile-time coefficients, the rest in blocks of 32 whose Legendre
-// coefficients are fetched ahead of the dependent steps -- and accumulates its own terms the same way.
 constexpr int MV_WIN = 32;            // terms per window with K > 16 (Σd and Σd²: 128 VGPRs)
 
-template <int KIND, int NW, bool PAIR, bool FIRST>
+// Σd (and with SQ Σd²) of up to NW terms of one component per workgroup, grid (sample block, component, term window).  Each
+// lane takes two samples per trip (four independent recurrences for a fine / coarse pair) and issues the next trip's loads
+// before the current trip's arithmetic, as the scalar kernel does (moments.hip, accum_samples).  The tile is computed whole:
+// terms >= K of the last window are evaluated and discarded (no run-time guard inside the unrolled loop).  A window at k0 > 0
+// first walks the k0 terms before it -- the first 32 with compile-time coefficients, the rest in blocks of 32 whose Legendre
+// coefficients are fetched ahead of the dependent steps -- and accumulates its own terms the same way.
+template <bool SQ>
+__device__ __forceinline__ void mv_add(double d, double &s, double &sp) {
+    s += d;
+    if constexpr (SQ) sp = __builtin_fma(d, d, sp);
+}
+
+template <int KIND, int NW, bool PAIR, bool FIRST, bool SQ>
 __device__ __forceinline__ void mv_accumulate(const BasisParams &bp, const double *__restrict__ f, const double *__restrict__ c,
-                                              int64_t s0, int64_t s1, int k0, double (&s)[NW], double (&sp)[NW], int &kept,
-                                              int &removed) {
+                                              int64_t s0, int64_t s1, int k0, double (&s)[NW], double (&sp)[SQ ? NW : 1],
+                                              int &kept, int &removed) {
     constexpr int64_t T = MM_THREADS;
     int64_t i0 = s0 + threadIdx.x, i1 = i0 + T;
     double f0 = 0.0, f1 = 0.0, c0 = 0.0, c1 = 0.0;
@@ -153,10 +75,8 @@ __device__ __forceinline__ void mv_accumulate(const BasisParams &bp, const doubl
             for (int i = 0; i < NW; ++i) {
                 double d0 = gf0.next(i), d1 = gf1.next(i);
                 if (PAIR) { d0 -= gc0.next(i); d1 -= gc1.next(i); }
-                s[i] += d0;
-                sp[i] = __builtin_fma(d0, d0, sp[i]);
-                s[i] += d1;
-                sp[i] = __builtin_fma(d1, d1, sp[i]);
+                mv_add<SQ>(d0, s[i], sp[SQ ? i : 0]);
+                mv_add<SQ>(d1, s[i], sp[SQ ? i : 0]);
             }
         } else {
 #pragma unroll
@@ -181,10 +101,8 @@ __device__ __forceinline__ void mv_accumulate(const BasisParams &bp, const doubl
             for (int i = 0; i < NW; ++i) {                  // the window's terms [k0, k0 + NW), k0 a multiple of 32
                 double d0 = gf0.skip(i, ga[i]), d1 = gf1.skip(i, ga[i]);
                 if (PAIR) { d0 -= gc0.skip(i, ga[i]); d1 -= gc1.skip(i, ga[i]); }
-                s[i] += d0;
-                sp[i] = __builtin_fma(d0, d0, sp[i]);
-                s[i] += d1;
-                sp[i] = __builtin_fma(d1, d1, sp[i]);
+                mv_add<SQ>(d0, s[i], sp[SQ ? i : 0]);
+                mv_add<SQ>(d1, s[i], sp[SQ ? i : 0]);
             }
         }
         i0 = j0;
@@ -192,61 +110,69 @@ __device__ __forceinline__ void mv_accumulate(const BasisParams &bp, const doubl
     }
 }
 
-// part / part_sq[(m * nb + b) * K + k] = block b's Σd / Σd² of term k of component m; pcount[(m * nb + b) * 2 + {0, 1}] =
-// kept / dropped.  Component m of the chunk is row m of fine / coarse ([M][n], n samples per row).
-template <int KIND, int NW, bool PAIR, bool FIRST>
+// part / part_sq[(m * nb + b) * K + k] = block b's Σd / Σd² of term k of component m (part_sq with SQ only);
+// pcount[(m * nb + b) * 2 + {0, 1}] = kept / dropped.  Component m of the chunk is row m of fine / coarse ([M][n], n samples
+// per row).
+template <int KIND, int NW, bool PAIR, bool FIRST, bool SQ>
 __global__ __launch_bounds__(MM_THREADS) void k_moments_multi_var(const BasisParams *__restrict__ bps, const double *__restrict__ fine,
                                                                   const double *__restrict__ coarse, int64_t n, int K, int nb,
                                                                   double *__restrict__ part, double *__restrict__ part_sq,
                                                                   int64_t *__restrict__ pcount) {
+    constexpr int NC = SQ ? 2 * NW : NW;        // columns of the block reduction
     const int b = blockIdx.x, m = blockIdx.y, k0 = (blockIdx.z + (FIRST ? 0 : 1)) * MV_WIN;
     const BasisParams bp = bps[m];
     const int64_t per = (n + nb - 1) / nb, s0 = std::min<int64_t>(n, (int64_t)b * per), s1 = std::min<int64_t>(n, s0 + per);
     const double *f = fine + (int64_t)m * n;
     const double *c = PAIR ? coarse + (int64_t)m * n : nullptr;
-    double s[NW], sp[NW];
+    double s[NW], sp[SQ ? NW : 1];
 #pragma unroll
-    for (int j = 0; j < NW; ++j) { s[j] = 0.0; sp[j] = 0.0; }
+    for (int j = 0; j < NW; ++j) s[j] = sp[SQ ? j : 0] = 0.0;
     int kept = 0, removed = 0;
-    mv_accumulate<KIND, NW, PAIR, FIRST>(bp, f, c, s0, s1, k0, s, sp, kept, removed);
+    mv_accumulate<KIND, NW, PAIR, FIRST, SQ>(bp, f, c, s0, s1, k0, s, sp, kept, removed);
     // block partial: wave sums (fixed butterfly), then the four waves in order
-    __shared__ double red[4][2 * NW];
+    __shared__ double red[4][NC];
     __shared__ int cred[4][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
-        const double v = wave_sum(s[j]), vq = wave_sum(sp[j]);
-        if (lane == 0) { red[wave][j] = v; red[wave][NW + j] = vq; }
+        double v = wave_sum(s[j]), vq = 0.0;
+        if constexpr (SQ) vq = wave_sum(sp[j]);
+        if (lane == 0) {
+            red[wave][j] = v;
+            if constexpr (SQ) red[wave][NW + j] = vq;
+        }
     }
     kept = wave_sum_i(kept);
     removed = wave_sum_i(removed);
     if (lane == 0) { cred[wave][0] = kept; cred[wave][1] = removed; }
     __syncthreads();
     const int t = threadIdx.x;
-    if (t < 2 * NW) {
+    if (t < NC) {
         const int j = t < NW ? t : t - NW;
         if (k0 + j < K) {
             const double v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-            (t < NW ? part : part_sq)[((int64_t)m * nb + b) * K + k0 + j] = v;
+            (!SQ || t < NW ? part : part_sq)[((int64_t)m * nb + b) * K + k0 + j] = v;
         }
     }
     if (FIRST && t < 2)
         pcount[((int64_t)m * nb + b) * 2 + t] = ((int64_t)cred[0][t] + cred[1][t]) + ((int64_t)cred[2][t] + cred[3][t]);
 }
 
-// tot / tot_sq[m * K + k] += Σ_b part / part_sq[(m * nb + b) * K + k] in block order (one workgroup per component), counts
-// likewise
-__global__ __launch_bounds__(MM_THREADS) void k_multi_reduce_var(const double *__restrict__ part, const double *__restrict__ part_sq,
-                                                                 const int64_t *__restrict__ pcount, int K, int nb,
-                                                                 double *__restrict__ tot, double *__restrict__ tot_sq,
-                                                                 int64_t *__restrict__ tcount) {
+// tot / tot_sq[m * K + k] += Σ_b part / part_sq[(m * nb + b) * K + k] in block order (one workgroup per component; the
+// squares with SQ only, as values K .. 2K - 1 of the thread loop), counts likewise
+template <bool SQ>
+__global__ __launch_bounds__(MM_THREADS) void k_multi_reduce(const double *__restrict__ part, const double *__restrict__ part_sq,
+                                                             const int64_t *__restrict__ pcount, int K, int nb,
+                                                             double *__restrict__ tot, double *__restrict__ tot_sq,
+                                                             int64_t *__restrict__ tcount) {
     const int m = blockIdx.x;
-    for (int k = threadIdx.x; k < 2 * K; k += MM_THREADS) {
-        const double *src = k < K ? part : part_sq;
-        const int kk = k < K ? k : k - K;
+    for (int k = threadIdx.x; k < (SQ ? 2 : 1) * K; k += MM_THREADS) {
+        const bool sq = SQ && k >= K;
+        const double *src = sq ? part_sq : part;
+        const int kk = sq ? k - K : k;
         double s = 0.0;
         for (int b = 0; b < nb; ++b) s += src[((int64_t)m * nb + b) * K + kk];
-        (k < K ? tot : tot_sq)[(int64_t)m * K + kk] += s;
+        (sq ? tot_sq : tot)[(int64_t)m * K + kk] += s;
     }
     if (threadIdx.x < 2) {
         int64_t s = 0;
@@ -255,22 +181,19 @@ __global__ __launch_bounds__(MM_THREADS) void k_multi_reduce_var(const double *_
     }
 }
 
-template <int KIND>
-static void launch_multi_var(dim3 grid, hipStream_t st, bool pair, int NWsel, const BasisParams *d_tab, const double *fine,
-                             const double *coarse, int64_t n, int K, int nb, double *part, double *part_sq, int64_t *pcount) {
-    // NWsel: 16 (K <= 16, one window) or 32; windows after the first (blockIdx.z > 0) run in a launch of their own
-    const dim3 g0(grid.x, grid.y, 1), g1(grid.x, grid.y, grid.z - 1);
-    if (NWsel == 16) {
-        if (pair) hipLaunchKernelGGL((k_moments_multi_var<KIND, 16, true, true>), g0, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-        else hipLaunchKernelGGL((k_moments_multi_var<KIND, 16, false, true>), g0, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-        return;
-    }
-    if (pair) hipLaunchKernelGGL((k_moments_multi_var<KIND, MV_WIN, true, true>), g0, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-    else hipLaunchKernelGGL((k_moments_multi_var<KIND, MV_WIN, false, true>), g0, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-    if (grid.z > 1) {
-        if (pair) hipLaunchKernelGGL((k_moments_multi_var<KIND, MV_WIN, true, false>), g1, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-        else hipLaunchKernelGGL((k_moments_multi_var<KIND, MV_WIN, false, false>), g1, dim3(MM_THREADS), 0, st, d_tab, fine, coarse, n, K, nb, part, part_sq, pcount);
-    }
+// (kind, tile, pair, sq) -> the instantiation of k_moments_multi_var; tile 0: the 16-term tile of K <= 16, 1: the first
+// 32-term window, 2: the windows after the first (FIRST = false)
+using MultiFn = void (*)(const BasisParams *, const double *, const double *, int64_t, int, int, double *, double *, int64_t *);
+
+static MultiFn multi_kernel(int kind, int tile, bool pair, bool sq) {
+#define MV_CELL(KIND, NW, FIRST)                                                                                         \
+    {{k_moments_multi_var<KIND, NW, false, FIRST, false>, k_moments_multi_var<KIND, NW, false, FIRST, true>},            \
+     {k_moments_multi_var<KIND, NW, true, FIRST, false>, k_moments_multi_var<KIND, NW, true, FIRST, true>}}
+#define MV_KIND(KIND) {MV_CELL(KIND, 16, true), MV_CELL(KIND, MV_WIN, true), MV_CELL(KIND, MV_WIN, false)}
+    static const MultiFn fn[3][3][2][2] = {MV_KIND(MLMC_LEGENDRE), MV_KIND(MLMC_MONOMIAL), MV_KIND(MLMC_FOURIER)};
+#undef MV_KIND
+#undef MV_CELL
+    return fn[kind == MLMC_LEGENDRE ? 0 : (kind == MLMC_MONOMIAL ? 1 : 2)][tile][pair][sq];
 }
 
 // Argument checks of the per-component entries (`entry` names the entry in the messages).  On success bps holds the M
@@ -318,80 +241,21 @@ static int multi_blocks(int64_t n, int64_t M, int W) {
     return (int)std::min(want, room);
 }
 
-}  // namespace mlmc
-
-using namespace mlmc;
-
-extern "C" {
-
-int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
-                              const int32_t *levels, const double *const *fine, const double *const *coarse,
-                              const int64_t *n_samples, int64_t *n_out, int64_t *n_rm_out, double *sums_out) {
-    MLMC_API_GUARD;
+// Both entries: the level sums (with `sq` also the sums of squares, else sums_sq_out is null and nothing of them exists) and
+// the counts of every component over all chunks.
+static int accum_multi(const char *entry, bool sq, int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels,
+                       int32_t n_chunks, const int32_t *levels, const double *const *fine, const double *const *coarse,
+                       const int64_t *n_samples, int64_t *n_out, int64_t *n_rm_out, double *sums_out, double *sums_sq_out) {
     std::vector<BasisParams> bps;
     int64_t n_max = 0;
     bool empty = false;
-    if (multi_args("mlmc_accum_estimate_multi", M, bases, K, n_levels, n_chunks, levels, fine, coarse, n_samples,
-                   n_out && n_rm_out && sums_out, bps, n_max, empty))
-        return 1;
-    if (empty) return 0;
-    hipStream_t st = rt().stream;
-    const int W = (K + MM_WIN - 1) / MM_WIN;
-    auto blocks_for = [&](int64_t n) { return multi_blocks(n, M, W); };
-    const int nb_max = blocks_for(n_max);
-    const size_t b_tab = mm_align(sizeof(BasisParams) * M), b_part = mm_align(sizeof(double) * (size_t)nb_max * M * K);
-    const size_t b_pc = mm_align(sizeof(int64_t) * (size_t)nb_max * M * 2), b_tot = mm_align(sizeof(double) * (size_t)n_levels * M * K);
-    const size_t b_tc = mm_align(sizeof(int64_t) * (size_t)n_levels * M * 2);
-    static MultiWorkspace ws;
-    if (ws.reserve(b_tab + b_part + b_pc + b_tot + b_tc)) return 1;
-    BasisParams *d_tab = (BasisParams *)ws.dev;
-    double *d_part = (double *)(ws.dev + b_tab);
-    int64_t *d_pc = (int64_t *)(ws.dev + b_tab + b_part);
-    double *d_tot = (double *)(ws.dev + b_tab + b_part + b_pc);
-    int64_t *d_tc = (int64_t *)(ws.dev + b_tab + b_part + b_pc + b_tot);
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_tab, bps.data(), sizeof(BasisParams) * M, hipMemcpyHostToDevice, st));
-    MLMC_HIP_CHECK(hipMemsetAsync(d_tot, 0, b_tot + b_tc, st));
-    for (int c = 0; c < n_chunks; ++c) {
-        const int64_t n = n_samples[c];
-        if (n == 0) continue;
-        const int nb = blocks_for(n);
-        const int lv = levels[c];
-        hipLaunchKernelGGL(k_moments_multi, dim3((unsigned)nb, (unsigned)M, (unsigned)W), dim3(MM_THREADS), 0, st, d_tab, fine[c],
-                           coarse[c], n, K, nb, d_part, d_pc);
-        hipLaunchKernelGGL(k_multi_reduce, dim3((unsigned)M), dim3(MM_THREADS), 0, st, d_part, d_pc, K, nb,
-                           d_tot + (size_t)lv * M * K, d_tc + (size_t)lv * M * 2);
-        MLMC_HIP_CHECK(hipGetLastError());
-    }
-    std::vector<int64_t> counts((size_t)n_levels * M * 2);
-    MLMC_HIP_CHECK(hipMemcpyAsync(sums_out, d_tot, sizeof(double) * (size_t)n_levels * M * K, hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(hipMemcpyAsync(counts.data(), d_tc, sizeof(int64_t) * counts.size(), hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(wait_stream(st));
-    for (int l = 0; l < n_levels; ++l)
-        for (int m = 0; m < M; ++m) {
-            const size_t lm = (size_t)l * M + m;
-            n_out[lm] = counts[lm * 2];
-            n_rm_out[lm] = counts[lm * 2 + 1];
-            const std::vector<double> &sc = bases[m]->scale_c;      // Legendre: P_k = scale_c[k] q_k (the sums are of q_k)
-            for (int k = 0; k < K; ++k) sums_out[lm * K + k] *= sc[k];
-        }
-    return 0;
-}
-
-int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
-                                  const int32_t *levels, const double *const *fine, const double *const *coarse,
-                                  const int64_t *n_samples, int64_t *n_out, int64_t *n_rm_out, double *sums_out,
-                                  double *sums_sq_out) {
-    MLMC_API_GUARD;
-    std::vector<BasisParams> bps;
-    int64_t n_max = 0;
-    bool empty = false;
-    if (multi_args("mlmc_accum_estimate_multi_var", M, bases, K, n_levels, n_chunks, levels, fine, coarse, n_samples,
-                   n_out && n_rm_out && sums_out && sums_sq_out, bps, n_max, empty))
+    if (multi_args(entry, M, bases, K, n_levels, n_chunks, levels, fine, coarse, n_samples,
+                   n_out && n_rm_out && sums_out && (sums_sq_out || !sq), bps, n_max, empty))
         return 1;
     if (empty) return 0;
     hipStream_t st = rt().stream;
     const int kind = bps[0].kind;
-    const int nw = K <= 16 ? 16 : MV_WIN;
+    const int tile = K <= 16 ? 0 : 1;
     const int W = (K + MV_WIN - 1) / MV_WIN;
     const int64_t L = n_levels;
     // scratch of groups of mg components (the last group may be smaller and take more sample blocks per component): table,
@@ -405,15 +269,18 @@ int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int
     auto sizes_for = [&](int64_t mg, size_t (&b)[7]) {
         const int64_t pr = part_rows(mg);
         b[0] = mm_align(sizeof(BasisParams) * mg);
-        b[1] = b[2] = mm_align(sizeof(double) * (size_t)(pr * K));
+        b[1] = mm_align(sizeof(double) * (size_t)(pr * K));
+        b[2] = sq ? b[1] : 0;
         b[3] = mm_align(sizeof(int64_t) * (size_t)(pr * 2));
-        b[4] = b[5] = mm_align(sizeof(double) * (size_t)(L * mg * K));
+        b[4] = mm_align(sizeof(double) * (size_t)(L * mg * K));
+        b[5] = sq ? b[4] : 0;
         b[6] = mm_align(sizeof(int64_t) * (size_t)(L * mg * 2));
         size_t t = 0;
         for (size_t v : b) t += v;
         return t;
     };
-    // components in groups whose scratch stays within 64 MiB (one group up to L * M * K of about 3.5 M)
+    // components in groups whose scratch stays within 64 MiB (one group up to L * M * K of about 3.5 M with the squares,
+    // 7 M without)
     constexpr size_t MV_SCRATCH = size_t(64) << 20;
     size_t bsz[7];
     int64_t Mg = M;
@@ -428,6 +295,7 @@ int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int
     double *d_tot = (double *)(p += bsz[3]);
     double *d_tot_sq = (double *)(p += bsz[4]);
     int64_t *d_tc = (int64_t *)(p += bsz[5]);
+    if (!sq) d_part_sq = d_tot_sq = nullptr;
     std::vector<int64_t> counts((size_t)L * M * 2);
     for (int64_t g0 = 0; g0 < M; g0 += Mg) {
         const int64_t mg = std::min<int64_t>(Mg, M - g0);
@@ -440,18 +308,21 @@ int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int
             const int lv = levels[c];
             const double *f = fine[c] + g0 * n;
             const double *co = coarse[c] ? coarse[c] + g0 * n : nullptr;
-            const dim3 grid((unsigned)nb, (unsigned)mg, (unsigned)W);
-            if (kind == MLMC_LEGENDRE) launch_multi_var<MLMC_LEGENDRE>(grid, st, co != nullptr, nw, d_tab, f, co, n, K, nb, d_part, d_part_sq, d_pc);
-            else if (kind == MLMC_MONOMIAL) launch_multi_var<MLMC_MONOMIAL>(grid, st, co != nullptr, nw, d_tab, f, co, n, K, nb, d_part, d_part_sq, d_pc);
-            else launch_multi_var<MLMC_FOURIER>(grid, st, co != nullptr, nw, d_tab, f, co, n, K, nb, d_part, d_part_sq, d_pc);
-            hipLaunchKernelGGL(k_multi_reduce_var, dim3((unsigned)mg), dim3(MM_THREADS), 0, st, d_part, d_part_sq, d_pc, K, nb,
-                               d_tot + (size_t)lv * mg * K, d_tot_sq + (size_t)lv * mg * K, d_tc + (size_t)lv * mg * 2);
+            // the first window (or the 16-term tile), then the windows after it in a launch of their own
+            hipLaunchKernelGGL(multi_kernel(kind, tile, co != nullptr, sq), dim3((unsigned)nb, (unsigned)mg, 1), dim3(MM_THREADS), 0,
+                               st, d_tab, f, co, n, K, nb, d_part, d_part_sq, d_pc);
+            if (W > 1)
+                hipLaunchKernelGGL(multi_kernel(kind, 2, co != nullptr, sq), dim3((unsigned)nb, (unsigned)mg, (unsigned)(W - 1)),
+                                   dim3(MM_THREADS), 0, st, d_tab, f, co, n, K, nb, d_part, d_part_sq, d_pc);
+            hipLaunchKernelGGL(sq ? k_multi_reduce<true> : k_multi_reduce<false>, dim3((unsigned)mg), dim3(MM_THREADS), 0, st, d_part,
+                               d_part_sq, d_pc, K, nb, d_tot + (size_t)lv * mg * K, sq ? d_tot_sq + (size_t)lv * mg * K : nullptr,
+                               d_tc + (size_t)lv * mg * 2);
             MLMC_HIP_CHECK(hipGetLastError());
         }
         // the group's rows [L][mg] into the [L][M] outputs (stream-ordered before the next group reuses the scratch)
         const size_t row = sizeof(double) * (size_t)(mg * K), ld = sizeof(double) * (size_t)M * K;
         MLMC_HIP_CHECK(hipMemcpy2DAsync(sums_out + g0 * K, ld, d_tot, row, row, (size_t)L, hipMemcpyDeviceToHost, st));
-        MLMC_HIP_CHECK(hipMemcpy2DAsync(sums_sq_out + g0 * K, ld, d_tot_sq, row, row, (size_t)L, hipMemcpyDeviceToHost, st));
+        if (sq) MLMC_HIP_CHECK(hipMemcpy2DAsync(sums_sq_out + g0 * K, ld, d_tot_sq, row, row, (size_t)L, hipMemcpyDeviceToHost, st));
         MLMC_HIP_CHECK(hipMemcpy2DAsync(counts.data() + g0 * 2, sizeof(int64_t) * (size_t)M * 2, d_tc, sizeof(int64_t) * (size_t)(mg * 2),
                                         sizeof(int64_t) * (size_t)(mg * 2), (size_t)L, hipMemcpyDeviceToHost, st));
     }
@@ -464,10 +335,33 @@ int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int
             const std::vector<double> &sc = bases[m]->scale_c;      // Legendre: P_k = scale_c[k] q_k, P_k² = scale_c[k]² q_k²
             for (int k = 0; k < K; ++k) {
                 sums_out[lm * K + k] *= sc[k];
-                sums_sq_out[lm * K + k] *= sc[k] * sc[k];
+                if (sq) sums_sq_out[lm * K + k] *= sc[k] * sc[k];
             }
         }
     return 0;
+}
+
+}  // namespace mlmc
+
+using namespace mlmc;
+
+extern "C" {
+
+int mlmc_accum_estimate_multi(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
+                              const int32_t *levels, const double *const *fine, const double *const *coarse,
+                              const int64_t *n_samples, int64_t *n_out, int64_t *n_rm_out, double *sums_out) {
+    MLMC_API_GUARD;
+    return accum_multi("mlmc_accum_estimate_multi", false, M, bases, K, n_levels, n_chunks, levels, fine, coarse, n_samples, n_out,
+                       n_rm_out, sums_out, nullptr);
+}
+
+int mlmc_accum_estimate_multi_var(int32_t M, const mlmc_basis *const *bases, int32_t K, int32_t n_levels, int32_t n_chunks,
+                                  const int32_t *levels, const double *const *fine, const double *const *coarse,
+                                  const int64_t *n_samples, int64_t *n_out, int64_t *n_rm_out, double *sums_out,
+                                  double *sums_sq_out) {
+    MLMC_API_GUARD;
+    return accum_multi("mlmc_accum_estimate_multi_var", true, M, bases, K, n_levels, n_chunks, levels, fine, coarse, n_samples,
+                       n_out, n_rm_out, sums_out, sums_sq_out);
 }
 
 }  // extern "C"

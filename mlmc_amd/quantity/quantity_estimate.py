@@ -955,16 +955,8 @@ def multi_component_sums(quantity, ext_fns):
 
 
 def _multi_component_sums(quantity, ext_fns):
-    from .. import _lib
     M, K = len(ext_fns), int(ext_fns[0].size)
-    n_levels, keep, args = _component_chunks(quantity, M, "multi_component_sums")
-    n = np.zeros((n_levels, M), dtype=np.int64)
-    n_rm = np.zeros((n_levels, M), dtype=np.int64)
-    sums = np.zeros((n_levels, M, K))
-    _lib.check(_lib.lib().mlmc_accum_estimate_multi(M, _basis_handles(ext_fns), K, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm),
-                                                    _lib.ptr(sums)))
-    del keep
-    return n, n_rm, sums
+    return _component_entry(quantity, M, "multi_component_sums", "mlmc_accum_estimate_multi", (M, _basis_handles(ext_fns), K), [(K,)])
 
 
 def _basis_handles(fns):
@@ -974,7 +966,8 @@ def _basis_handles(fns):
 
 def _component_chunks(quantity, M, what):
     """The stored chunks of `quantity` as [M, n] float64 device tensors for the per-component entries (mlmc_accum_estimate_multi,
-    _var).  -> (n_levels, tensors to keep alive until the call returns, (n_chunks, levels, fine, coarse, n_samples) arguments)"""
+    _var, mlmc_level_diagnostics: _component_entry).
+    -> (n_levels, tensors to keep alive until the call returns, (n_chunks, levels, fine, coarse, n_samples) arguments)"""
     import ctypes as C
     import torch
     from .. import _lib
@@ -1013,6 +1006,19 @@ def _component_chunks(quantity, M, what):
     return n_levels, keep, (nc, _lib.ptr(lv), C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn))
 
 
+def _component_entry(quantity, M, what, entry, lead, shapes):
+    """One call of the per-component C entry `entry` over the stored chunks of `quantity`: entry(*lead, n_levels, the chunk
+    arguments, n, n_rm, one float64 output [L, M, *shape] per shape).  -> n, n_rm [L, M] int64, then the float outputs"""
+    from .. import _lib
+    n_levels, keep, args = _component_chunks(quantity, M, what)
+    n = np.zeros((n_levels, M), dtype=np.int64)
+    n_rm = np.zeros((n_levels, M), dtype=np.int64)
+    outs = [np.zeros((n_levels, M) + shape) for shape in shapes]
+    _lib.check(getattr(_lib.lib(), entry)(*lead, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm), *[_lib.ptr(o) for o in outs]))
+    del keep
+    return (n, n_rm, *outs)
+
+
 COMPONENT_FAMILIES = ("Legendre", "Monomial", "Fourier")     # moments of the device route of the per-component estimates
 
 
@@ -1033,17 +1039,9 @@ def component_level_sums(quantity, moments_fns):
 
 
 def _component_level_sums(quantity, moments_fns):
-    from .. import _lib
     M, R = len(moments_fns), int(moments_fns[0].size)
-    n_levels, keep, args = _component_chunks(quantity, M, "component_level_sums")
-    n = np.zeros((n_levels, M), dtype=np.int64)
-    n_rm = np.zeros((n_levels, M), dtype=np.int64)
-    s = np.zeros((n_levels, M, R))
-    sp = np.zeros((n_levels, M, R))
-    _lib.check(_lib.lib().mlmc_accum_estimate_multi_var(M, _basis_handles(moments_fns), R, n_levels, *args, _lib.ptr(n),
-                                                        _lib.ptr(n_rm), _lib.ptr(s), _lib.ptr(sp)))
-    del keep
-    return n, n_rm, s, sp
+    return _component_entry(quantity, M, "component_level_sums", "mlmc_accum_estimate_multi_var",
+                            (M, _basis_handles(moments_fns), R), [(R,), (R,)])
 
 
 def level_diagnostics(quantity):
@@ -1058,16 +1056,9 @@ def level_diagnostics(quantity):
 
 
 def _level_diagnostics(quantity):
-    from .. import _lib
     from .. import diagnostics
     M = int(quantity.size())
-    n_levels, keep, args = _component_chunks(quantity, M, "level_diagnostics")
-    n = np.zeros((n_levels, M), dtype=np.int64)
-    n_rm = np.zeros((n_levels, M), dtype=np.int64)
-    stats = np.zeros((n_levels, M, diagnostics.N_STAT))
-    _lib.check(_lib.lib().mlmc_level_diagnostics(M, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm), _lib.ptr(stats)))
-    del keep
-    return n, n_rm, stats
+    return _component_entry(quantity, M, "level_diagnostics", "mlmc_level_diagnostics", (M,), [(diagnostics.N_STAT,)])
 
 
 def component_statistics(n, s, sp):

@@ -1,6 +1,7 @@
 """GPU tests of the per-component moment estimates of a vector quantity: mlmc_accum_estimate_multi_var level sums against the
 scalar estimates and the NumPy oracle, Estimate.estimate_component_moments / _diff_vars / _diff_vars_regression against the loop
-of scalar estimates, a chunk of several sample blocks, the adaptive sample-allocation loop end to end, ABI errors."""
+of scalar estimates, a chunk of several sample blocks, the adaptive sample-allocation loop end to end, ABI errors; the mean-only entry (mlmc_accum_estimate_multi) against the variance
+entry bit for bit."""
 import ctypes as C
 
 import numpy as np
@@ -241,6 +242,85 @@ def test_adaptive_sample_allocation_loop_end_to_end(hip):
     for a, b in zip(sched_a, sched_b):
         assert np.array_equal(a, b)
     assert np.array_equal(n_a, n_b)
+
+
+def _both_entries(hip, fns, K, chunks):
+    """mlmc_accum_estimate_multi and mlmc_accum_estimate_multi_var on the same bases and chunks [(level, fine [M, n], coarse [M, n]
+    | None)], two levels -> (n, n_rm, sums), (n, n_rm, s, sp)"""
+    lib, M, L = hip.lib(), len(fns), 2
+    arr = (C.c_void_p * M)(*[fn._basis_handle().value for fn in fns])
+    lv = np.array([c[0] for c in chunks], dtype=np.int32)
+    nn = np.array([c[1].shape[1] for c in chunks], dtype=np.int64)
+    fp = (C.c_void_p * len(chunks))(*[c[1].data_ptr() for c in chunks])
+    cp = (C.c_void_p * len(chunks))(*[None if c[2] is None else c[2].data_ptr() for c in chunks])
+    out = []
+    for entry, n_float in ((lib.mlmc_accum_estimate_multi, 1), (lib.mlmc_accum_estimate_multi_var, 2)):
+        n, n_rm = np.zeros((L, M), dtype=np.int64), np.zeros((L, M), dtype=np.int64)
+        sums = [np.zeros((L, M, K)) for _ in range(n_float)]
+        hip.check(entry(M, C.cast(arr, C.c_void_p), K, L, len(chunks), hip.ptr(lv), C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p),
+                        hip.ptr(nn), hip.ptr(n), hip.ptr(n_rm), *[hip.ptr(v) for v in sums]))
+        out.append((n, n_rm, *sums))
+    return out
+
+
+MEAN_ONLY_N = (1, 511, 512, 513, 4097)       # a single sample; the last trip of 2 x 256 lanes with and without its second
+                                             # sample; two sample blocks
+
+
+def _mean_only_data():
+    """Per chunk length n: level 0 without coarse rows, level 1 in two chunks of n and 300 samples, M = 3.  Component 0: NaNs in
+    its fine rows and values outside its domain (-2, 2); component 1: NaNs in its coarse rows, and not one value of its 300-sample
+    chunk inside its domain; component 2: positive data (log=True)."""
+    import torch
+    rng = np.random.default_rng(2024)
+    out = {}
+    for n in MEAN_ONLY_N:
+        chunks = []
+        for level, length in ((0, n), (1, n), (1, 300)):
+            f = rng.normal(size=(3, length))
+            f[2] = np.exp(0.5 * f[2])
+            c = f + 0.1 * rng.normal(size=f.shape)
+            c[2] = f[2] * np.exp(0.05 * rng.normal(size=length))
+            f[0, 3::7] = np.nan
+            c[1, 2::5] = np.nan
+            if length == 300:
+                f[1] = 1e9
+            chunks.append((level, torch.from_numpy(f).cuda(), None if level == 0 else torch.from_numpy(c).cuda()))
+        out[n] = chunks
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.fixture(scope="module")
+def mean_only_chunks(hip):
+    return _mean_only_data()
+
+
+def _mean_only_fns(kind, K):
+    from mlmc_amd import Legendre, Monomial, Fourier
+    cls = {"legendre": Legendre, "monomial": Monomial, "fourier": Fourier}[kind]
+    return [cls(K, (-2.0, 2.0)), cls(K, (-3.0, 3.5)), cls(K, (0.2, 6.0), log=True)]
+
+
+MEAN_ONLY_CASES = [("legendre", 13), ("legendre", 25), ("legendre", 49), ("legendre", 97), ("monomial", 25), ("monomial", 49),
+                   ("fourier", 25), ("fourier", 49)]
+
+
+@pytest.mark.parametrize("kind,K", MEAN_ONLY_CASES)
+def test_mean_only_entry_equals_the_variance_entry_bit_for_bit(hip, mean_only_chunks, kind, K):
+    """Both C entries on the same bases and device chunks: equal counts, and the sums of the mean-only entry are the Σd of the
+    variance entry, no tolerance.  K = 13: the 16-term tile; 25: one 32-term window with terms >= K discarded; 49: one window
+    after the first; 97: windows that walk one and two 32-term blocks before their own."""
+    fns = _mean_only_fns(kind, K)
+    for n, chunks in mean_only_chunks.items():
+        (n0, rm0, sums), (n1, rm1, s, sp) = _both_entries(hip, fns, K, chunks)
+        assert np.array_equal(n0, n1) and np.array_equal(rm0, rm1), (kind, K, n)
+        assert np.array_equal(sums, s), (kind, K, n, np.max(np.abs(sums - s)))
+        # the cases are what they claim: every sample counted once, the 300-sample chunk of component 1 dropped whole, of
+        # component 0 more than its NaNs dropped (the values outside its domain), finite sums
+        assert np.array_equal(n1 + rm1, np.array([[n] * 3, [n + 300] * 3]))
+        assert rm1[1, 1] >= 300 and rm1[1, 0] > len(range(3, n, 7)) + len(range(3, 300, 7))
+        assert np.all(np.isfinite(s)) and np.all(np.isfinite(sp))
 
 
 def test_abi_errors_name_the_component(hip):

@@ -6,10 +6,12 @@ samples per level of synthetic per-component samples resident in HBM (DeviceMemo
   loop_ms       the loop of Estimate(q_m, storage, fn).estimate_diff_vars_regression over the components
   entry_ms      one mlmc_accum_estimate_multi_var call on the gathered chunks (launches + one wait: an upper bound of the
                 kernel time; rocprofv3 --kernel-trace gives the kernels alone)
+  mean_only_ms  with --mean-only: one mlmc_accum_estimate_multi call (no squares) on the same chunks, K = linearize.extended_size
+                of the moments (2 R - 1 for Legendre), the pass behind Estimate.construct_densities; mean_only_K names K
   evals_per_s   moment evaluations (fine and coarse values x R) per second of entry_ms
   fp64_frac     flops by the count of DESIGN 3.1 (14 R per pair, 8 R at level 0) per entry_ms against 78.6 TFLOP/s
 
-Prints one JSON line.  Usage: python tools/component_moments.py [--quick | --config M,R,n] [--reps K] [--no-loop]"""
+Prints one JSON line.  Usage: python tools/component_moments.py [--quick | --config M,R,n] [--reps K] [--no-loop] [--mean-only]"""
 import argparse
 import json
 import os
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from mlmc_amd import _lib, Legendre
+from mlmc_amd import _lib, Legendre, linearize
 from mlmc_amd.estimator import Estimate, scalar_component
 from mlmc_amd.quantity.quantity import make_root_quantity
 from mlmc_amd.quantity.quantity_spec import QuantitySpec
@@ -60,25 +62,26 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) * 1e3 / reps, out
 
 
-def entry_call(q, fns):
-    """The C entry alone on the quantity's gathered chunks (what component_level_sums times beyond the gathering)."""
+def entry_call(q, fns, mean_only=False):
+    """The C entry alone on the quantity's gathered chunks (what component_level_sums times beyond the gathering); mean_only:
+    mlmc_accum_estimate_multi on the extended members of the moments instead."""
+    if mean_only:
+        fns = [fn.change_size(linearize.extended_size(fn)) for fn in fns]
     M, R = len(fns), fns[0].size
     n_levels, keep, args = qe._component_chunks(q, M, "component_moments")
     n = np.zeros((n_levels, M), dtype=np.int64)
     n_rm = np.zeros_like(n)
-    s = np.zeros((n_levels, M, R))
-    sp = np.zeros_like(s)
+    outs = [np.zeros((n_levels, M, R)) for _ in range(1 if mean_only else 2)]
     handles = qe._basis_handles(fns)
-    lib = _lib.lib()
+    entry = getattr(_lib.lib(), "mlmc_accum_estimate_multi" if mean_only else "mlmc_accum_estimate_multi_var")
 
     def call():
-        _lib.check(lib.mlmc_accum_estimate_multi_var(M, handles, R, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm), _lib.ptr(s),
-                                                     _lib.ptr(sp)))
-        return keep
+        _lib.check(entry(M, handles, R, n_levels, *args, _lib.ptr(n), _lib.ptr(n_rm), *[_lib.ptr(o) for o in outs]))
+        return keep, fns
     return call
 
 
-def run_config(M, R, n, reps, loop):
+def run_config(M, R, n, reps, loop, mean_only=False):
     st, q = storage(M, n)
     fns = [Legendre(R, (-3.5 + 0.3 * m / max(M - 1, 1), 3.5 + 0.3 * m / max(M - 1, 1))) for m in range(M)]
     est = Estimate(q, st, fns[0])
@@ -90,13 +93,17 @@ def run_config(M, R, n, reps, loop):
         loop_ms, _ = timed(lambda: [Estimate(c, st, f).estimate_diff_vars_regression(n_created) for c, f in zip(comps, fns)],
                            max(1, reps // 2))
     entry_ms, _ = timed(entry_call(q, fns), reps)
+    mean = {}
+    if mean_only:
+        mean_ms, _ = timed(entry_call(q, fns, mean_only=True), reps)
+        mean = dict(mean_only_ms=round(mean_ms, 4), mean_only_K=linearize.extended_size(fns[0]))
     L = len(STEPS)
     evals = M * n * R * (1 + 2 * (L - 1))                         # fine values at level 0, fine and coarse above
     flops = M * n * R * (8 + 14 * (L - 1))
     row = dict(M=M, R=R, n=n, L=L, batched_ms=round(batched_ms, 3), loop_ms=None if loop_ms is None else round(loop_ms, 3),
                speedup=None if loop_ms is None else round(loop_ms / batched_ms, 2), entry_ms=round(entry_ms, 4),
                evals_per_s=float("%.4g" % (evals / (entry_ms * 1e-3))),
-               fp64_frac=round(flops / (entry_ms * 1e-3) / FP64_PEAK, 3), finite=bool(np.all(np.isfinite(reg))))
+               fp64_frac=round(flops / (entry_ms * 1e-3) / FP64_PEAK, 3), finite=bool(np.all(np.isfinite(reg))), **mean)
     del st, q, est
     torch.cuda.empty_cache()
     return row
@@ -108,6 +115,7 @@ def main():
     ap.add_argument("--config", help="one configuration M,R,n (e.g. 64,32,1000000), for a profiler run")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-loop", action="store_true", help="do not time the per-component loop")
+    ap.add_argument("--mean-only", action="store_true", help="also time mlmc_accum_estimate_multi (mean-only, K = 2 R - 1)")
     a = ap.parse_args()
     _lib.init(0)
     Ms, Rs, ns = ((1, 8), (25,), (10_000,)) if a.quick else ((1, 8, 64, 256), (13, 25, 64), (10_000, 1_000_000))
@@ -118,7 +126,7 @@ def main():
     for n in ns:
         for R in Rs:
             for M in Ms:
-                rows.append(run_config(M, R, n, a.reps, not a.no_loop))
+                rows.append(run_config(M, R, n, a.reps, not a.no_loop, a.mean_only))
                 print(json.dumps(rows[-1]), file=sys.stderr, flush=True)       # progress
     print(json.dumps(dict(tool="component_moments", device=_lib.device_info()["name"], rows=rows)))
 
