@@ -38,7 +38,8 @@ extern "C" {
                               *    _finalize / _kernel_time, mlmc_accum_estimate_multi_var, mlmc_density_integrate_batch,
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
-                              *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi */
+                              *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
+                              *    mlmc_density_tail_means_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -335,8 +336,31 @@ int mlmc_density_cdf_batch(int32_t B, const mlmc_basis *const *bases, const int3
 int mlmc_density_quantiles_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                                  const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                  const double *p, const int64_t *n, double *out, double *mass_out, int mem_kind);
+/* Tail means (expected shortfall, CVaR) of B problems in one call -- added within 8.  Edges e_j, cell integrals C_j, prefix P and
+ * mass T = P_n are those of mlmc_density_cdf_batch, bit for bit the table of the quantile entry.  On the nodes t_k and weights
+ * w_k of C_j let
+ *     A_j = sum_k w_k (t_k - a) rho(t_k),   B_j = sum_k w_k (b - t_k) rho(t_k)
+ * (the anchors are the domain ends in full and partial cells alike: every term is non-negative and nothing cancels, whatever the
+ * sign of the domain), V_0 = 0, V_{j+1} = V_j + A_j in cell order, S_n = W_n = 0, S_j = S_{j+1} + C_j, W_j = W_{j+1} + B_j from the
+ * last cell down.  For x in [a, b], j the largest index below n with e_j <= x and I, A(.,.), B(.,.) the same rule on a partial cell,
+ *     m_lo(x) = P_j + I(e_j, x)           lower(x) = a + (V_j + A(e_j, x)) / m_lo(x)            = E[X | X <= x]
+ *     m_hi(x) = S_{j+1} + I(x, e_{j+1})   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / m_hi(x)    = E[X | X >= x]
+ * and a tail without mass (m_lo == 0 or m_hi == 0) returns x itself, so lower(a) = a and upper(b) = b.  For every probability p the
+ * entry writes q_out = Q(p), bit for bit the value of mlmc_density_quantiles_batch for the same problem and p, lower_out =
+ * lower(Q(p)) (the lower expected shortfall at level p) and upper_out = upper(Q(p)) (the upper one).  All three are NaN for p
+ * outside [0, 1] or NaN, and for every point of a problem whose mass T is not finite and positive (no error).  mean_out [B] host
+ * (may be NULL) receives a + V_n / T, mass_out [B] host (may be NULL) T.  p lower + (1 - p) upper = mean holds only up to the
+ * resolution of the rule: the two partial-cell rules of a point do not add up to the cell's rule exactly.  Layout, conventions,
+ * argument errors and no-ops as mlmc_density_quantiles_batch; mem_kind applies to p, q_out, lower_out and upper_out.  One thread
+ * owns one point and every sum has a fixed order: a value does not depend on the batch, on the problem's position in it or on the
+ * other points.  One host wait. */
+int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                  const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                  int32_t gauss_degree, const double *p, const int64_t *n, double *q_out, double *lower_out,
+                                  double *upper_out, double *mass_out, double *mean_out, int mem_kind);
 /* HIP-event time (ms) and number of the point kernels (quantile and CDF kernels, without the table kernels and copies) that
- * mlmc_density_cdf_batch / mlmc_density_quantiles_batch have launched since the last call of this function; resets both. */
+ * mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch have launched since the last call of this
+ * function; resets both.  A tail-means call counts its quantile kernel and its tail kernel together as one launch per group. */
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */

@@ -13,6 +13,13 @@
 //                   the bracket or is not finite
 //   k_q_cdf       : Fhat at arbitrary values, one thread per value (cell lookup + one partial-cell rule)
 //   k_q_integrate : k_density_integrate for B problems in one launch, each value bit for bit the single entry's
+// Tail means (expected shortfall, mlmc_density_tail_means_batch): with A_j / B_j the cell sums of (t - a) rho / (b - t) rho on the
+// nodes of C_j, V the forward prefix of the A_j, S and W the backward suffixes of the C_j and B_j,
+//     lower(x) = a + (V_j + A(e_j, x)) / (P_j + I(e_j, x)),   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / (S_{j+1} + I(x, e_{j+1})).
+//   k_q_tail_cells  : C_j (the bits of k_q_cells), A_j, B_j in one walk over the nodes, one thread per (problem, cell)
+//   k_q_tail_prefix : P, V forwards and S, W backwards, one thread per problem
+//   k_q_tails       : one thread per (problem, x): cell lookup of k_q_cdf, then the two partial-cell rules [e_j, x] and
+//                     [x, e_{j+1}] in ONE loop over the nodes, their two density evaluations interleaved term by term
 // One thread owns one point from start to end, every sum has a fixed order and every loop a constant bound: a result does not
 // depend on the batch, on the position of the problem in it or on the other points.  No atomics, no data-dependent launch.
 // A thread finds its problem by a binary search of its point index in the problems' offsets, so that the same launch geometry
@@ -72,6 +79,70 @@ __device__ __forceinline__ double q_integral_any(const QProb &P, const double *_
         case MLMC_FOURIER: return q_integral<MLMC_FOURIER>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
         default: return q_integral<MLMC_SPLINE>(P.bp, c, P.n_coef, a, b, nodes, wts, deg);
     }
+}
+
+// q_density at two points at once: the arithmetic of q_density per point (hence its bits), the two term chains interleaved so that
+// one coefficient load serves both and one chain's FMAs overlap the other's
+template <int KIND>
+__device__ __forceinline__ void q_density2(const BasisParams &bp, const double *__restrict__ c, int R, double x0, double x1, double &d0,
+                                           double &d1) {
+    bool keep0, keep1;
+    const double t0 = transform_value(bp, x0, keep0), t1 = transform_value(bp, x1, keep1);
+    TermGen<KIND> g0, g1;
+    g0.init(keep0 ? t0 : 0.0, 1.0, bp);
+    g1.init(keep1 ? t1 : 0.0, 1.0, bp);
+    double pw0 = 0.0, pw1 = 0.0;
+    for (int r = 0; r < R; ++r) {
+        const double cr = c[r];
+        pw0 = __builtin_fma(g0.next(r), cr, pw0);
+        pw1 = __builtin_fma(g1.next(r), cr, pw1);
+    }
+    pw0 = fmin(fmax(-pw0, -200.0), 200.0);
+    pw1 = fmin(fmax(-pw1, -200.0), 200.0);
+    d0 = keep0 ? exp(pw0) : __builtin_nan("");
+    d1 = keep1 ? exp(pw1) : __builtin_nan("");
+}
+
+// sums of one cell [lo, hi] of the domain [a, b] in one walk over the nodes: C = the value (and the bits) of q_integral,
+// A = sum w (t - a) rho, B = sum w (b - t) rho on the same nodes t and weights w
+template <int KIND>
+__device__ __forceinline__ void q_cell_sums(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b, double lo,
+                                            double hi, const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                            double &C, double &A, double &B) {
+    const double half = 0.5 * (hi - lo), mid = 0.5 * (hi + lo);
+    double acc = 0.0, acc_a = 0.0, acc_b = 0.0;
+    for (int k = 0; k < deg; ++k) {
+        const double t = __builtin_fma(half, nodes[k], mid), w = wts[k];
+        const double rho = q_density<KIND>(bp, c, R, t);
+        acc = __builtin_fma(w, rho, acc);
+        acc_a = __builtin_fma(w, (t - a) * rho, acc_a);
+        acc_b = __builtin_fma(w, (b - t) * rho, acc_b);
+    }
+    C = acc * half;
+    A = acc_a * half;
+    B = acc_b * half;
+}
+
+// the partial-cell rules of a point x in the cell [lo, hi]: I and A on [lo, x], I and B on [x, hi], node k of both in one step
+template <int KIND>
+__device__ __forceinline__ void q_tail_sums(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b, double lo,
+                                            double x, double hi, const double *__restrict__ nodes, const double *__restrict__ wts,
+                                            int deg, double &I_lo, double &A_lo, double &I_hi, double &B_hi) {
+    const double half0 = 0.5 * (x - lo), mid0 = 0.5 * (x + lo), half1 = 0.5 * (hi - x), mid1 = 0.5 * (hi + x);
+    double i0 = 0.0, a0 = 0.0, i1 = 0.0, b1 = 0.0;
+    for (int k = 0; k < deg; ++k) {
+        const double t0 = __builtin_fma(half0, nodes[k], mid0), t1 = __builtin_fma(half1, nodes[k], mid1), w = wts[k];
+        double rho0, rho1;
+        q_density2<KIND>(bp, c, R, t0, t1, rho0, rho1);
+        i0 = __builtin_fma(w, rho0, i0);
+        a0 = __builtin_fma(w, (t0 - a) * rho0, a0);
+        i1 = __builtin_fma(w, rho1, i1);
+        b1 = __builtin_fma(w, (b - t1) * rho1, b1);
+    }
+    I_lo = i0 * half0;
+    A_lo = a0 * half0;
+    I_hi = i1 * half1;
+    B_hi = b1 * half1;
 }
 
 // cell edge j of the composite rule as an fp64 number: a + j h (two roundings, the file is compiled without contraction)
@@ -205,6 +276,99 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_cdf(const QProb *__restrict__ p
     out[idx] = f;
 }
 
+// the four table rows of a problem, [n + 1] doubles each, row r of problem k at tab + r * plane + k * (n + 1): the P rows alone are
+// the table of k_q_quantile / k_q_cdf
+enum { Q_ROW_P = 0, Q_ROW_V = 1, Q_ROW_S = 2, Q_ROW_W = 3, Q_TAIL_ROWS = 4 };
+
+__global__ __launch_bounds__(128) void k_q_tail_cells(const QProb *__restrict__ probs, int nprob, int nint, const double *__restrict__ coef,
+                                                      const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                      double *__restrict__ tab, int64_t plane) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)nprob * nint) return;
+    const int k = (int)(gid / nint), j = (int)(gid - (int64_t)k * nint);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off;
+    const double h = (P.b - P.a) / (double)nint;
+    const double lo = q_edge(P, h, nint, j), hi = q_edge(P, h, nint, j + 1);
+    double C, A, B;
+    switch (P.bp.kind) {
+        case MLMC_LEGENDRE: q_cell_sums<MLMC_LEGENDRE>(P.bp, c, P.n_coef, P.a, P.b, lo, hi, nodes, wts, deg, C, A, B); break;
+        case MLMC_MONOMIAL: q_cell_sums<MLMC_MONOMIAL>(P.bp, c, P.n_coef, P.a, P.b, lo, hi, nodes, wts, deg, C, A, B); break;
+        case MLMC_FOURIER: q_cell_sums<MLMC_FOURIER>(P.bp, c, P.n_coef, P.a, P.b, lo, hi, nodes, wts, deg, C, A, B); break;
+        default: q_cell_sums<MLMC_SPLINE>(P.bp, c, P.n_coef, P.a, P.b, lo, hi, nodes, wts, deg, C, A, B); break;
+    }
+    double *row = tab + (int64_t)k * (nint + 1);
+    row[Q_ROW_P * plane + j + 1] = C;            // summed forwards into P_{j+1}, backwards into S_j
+    row[Q_ROW_V * plane + j + 1] = A;            // summed forwards into V_{j+1}
+    row[Q_ROW_W * plane + j] = B;                // summed backwards into W_j
+}
+
+__global__ __launch_bounds__(64) void k_q_tail_prefix(int nprob, int nint, double *__restrict__ tab, int64_t plane, const QProb *__restrict__ probs,
+                                                      double *__restrict__ mass, double *__restrict__ mean) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nprob) return;
+    double *row = tab + (int64_t)k * (nint + 1);
+    double *__restrict__ rp = row + Q_ROW_P * plane, *__restrict__ rv = row + Q_ROW_V * plane;      // four disjoint rows
+    double *__restrict__ rs = row + Q_ROW_S * plane, *__restrict__ rw = row + Q_ROW_W * plane;
+    double run = 0.0, run2 = 0.0;
+    rs[nint] = 0.0;
+    rw[nint] = 0.0;
+    for (int j = nint - 1; j >= 0; --j) {        // from the last cell down, before the forward pass overwrites the C_j
+        run += rp[j + 1];
+        rs[j] = run;
+        run2 += rw[j];
+        rw[j] = run2;
+    }
+    run = 0.0;
+    run2 = 0.0;
+    rp[0] = 0.0;
+    rv[0] = 0.0;
+    for (int j = 0; j < nint; ++j) {             // k_q_prefix's sum: the same P and T
+        run += rp[j + 1];
+        rp[j + 1] = run;
+        run2 += rv[j + 1];
+        rv[j + 1] = run2;
+    }
+    mass[k] = run;
+    mean[k] = probs[k].a + run2 / run;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_tails(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                       const double *__restrict__ coef, const double *__restrict__ tab, int64_t plane,
+                                                       const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                       const double *__restrict__ x, double *__restrict__ lower, double *__restrict__ upper) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off, *row = tab + (int64_t)k * (nint + 1);
+    const double T = row[Q_ROW_P * plane + nint], v = x[idx];
+    double lw = __builtin_nan(""), up = __builtin_nan("");
+    if (T > 0.0 && T < __builtin_inf() && v == v) {
+        const double h = (P.b - P.a) / (double)nint;
+        int lo = 0, hi = nint;                  // the largest j < n with e_j <= v (k_q_cdf's lookup)
+        for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+            const int mid = (lo + hi) >> 1;
+            if (q_edge(P, h, nint, mid) <= v) lo = mid; else hi = mid;
+        }
+        const double ej = q_edge(P, h, nint, lo), ej1 = q_edge(P, h, nint, lo + 1);
+        double I_lo, A_lo, I_hi, B_hi;
+        switch (P.bp.kind) {
+            case MLMC_LEGENDRE: q_tail_sums<MLMC_LEGENDRE>(P.bp, c, P.n_coef, P.a, P.b, ej, v, ej1, nodes, wts, deg, I_lo, A_lo, I_hi, B_hi); break;
+            case MLMC_MONOMIAL: q_tail_sums<MLMC_MONOMIAL>(P.bp, c, P.n_coef, P.a, P.b, ej, v, ej1, nodes, wts, deg, I_lo, A_lo, I_hi, B_hi); break;
+            case MLMC_FOURIER: q_tail_sums<MLMC_FOURIER>(P.bp, c, P.n_coef, P.a, P.b, ej, v, ej1, nodes, wts, deg, I_lo, A_lo, I_hi, B_hi); break;
+            default: q_tail_sums<MLMC_SPLINE>(P.bp, c, P.n_coef, P.a, P.b, ej, v, ej1, nodes, wts, deg, I_lo, A_lo, I_hi, B_hi); break;
+        }
+        const double m_lo = row[Q_ROW_P * plane + lo] + I_lo, m_hi = row[Q_ROW_S * plane + lo + 1] + I_hi;
+        // a tail without mass returns the point itself: lower(a) = a, upper(b) = b
+        lw = m_lo == 0.0 ? v : P.a + (row[Q_ROW_V * plane + lo] + A_lo) / m_lo;
+        up = m_hi == 0.0 ? v : P.b - (row[Q_ROW_W * plane + lo + 1] + B_hi) / m_hi;
+    }
+    lower[idx] = lw;
+    upper[idx] = up;
+}
+
 __global__ __launch_bounds__(128) void k_q_integrate(const QProb *__restrict__ probs, int nprob, int64_t npts,
                                                      const double *__restrict__ coef, const double *__restrict__ lo,
                                                      const double *__restrict__ hi, const double *__restrict__ nodes,
@@ -215,8 +379,8 @@ __global__ __launch_bounds__(128) void k_q_integrate(const QProb *__restrict__ p
     out[idx] = q_integral_any(P, coef + P.c_off, lo[idx], hi[idx], nodes, wts, deg);
 }
 
-// HIP-event time of the point kernels (k_q_quantile / k_q_cdf), for mlmc_density_quantiles_kernel_time: one event pair per group of
-// a call, read after the call's own wait
+// HIP-event time of the point kernels (k_q_quantile / k_q_cdf; k_q_quantile + k_q_tails of a tail-means call as one), for
+// mlmc_density_quantiles_kernel_time: one event pair per group of a call, read after the call's own wait
 struct QTiming {
     std::vector<hipEvent_t> ev;
     double ms = 0.0;
@@ -279,10 +443,14 @@ static int q_prepare(const char *fn, int32_t B, const mlmc_basis *const *bases, 
     return 0;
 }
 
-// mlmc_density_cdf_batch (inverse == false) and mlmc_density_quantiles_batch (inverse == true)
-static int q_on_rule(const char *fn, bool inverse, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+enum QMode { Q_CDF, Q_QUANTILES, Q_TAILS };
+
+// mlmc_density_cdf_batch (Q_CDF), mlmc_density_quantiles_batch (Q_QUANTILES) and mlmc_density_tail_means_batch (Q_TAILS: `out`
+// receives the quantiles, lower_out / upper_out the tail means at them, mean_out the problems' means; all NULL otherwise)
+static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
-                     const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind) {
+                     const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind, double *lower_out = nullptr,
+                     double *upper_out = nullptr, double *mean_out = nullptr) {
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (B < 0) return fail(std::string(fn) + ": B < 0");
     if (B == 0) return 0;
@@ -292,20 +460,24 @@ static int q_on_rule(const char *fn, bool inverse, int32_t B, const mlmc_basis *
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
     QSetup S;
     if (q_prepare(fn, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
-    if (S.n_tot > 0 && (!x || !out)) return fail(std::string(fn) + ": null argument");
-    if (S.n_tot == 0 && !mass_out) return 0;
+    const bool tails = mode == Q_TAILS;
+    if (S.n_tot > 0 && (!x || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
+    if (S.n_tot == 0 && !mass_out && !mean_out) return 0;
     const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     hipStream_t st = rt().stream;
     std::vector<double> gx, gw;
     gauss_legendre(deg, gx, gw);
     const bool stage = mem_kind == MLMC_HOST && S.n_tot > 0;
-    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
+    const size_t rows = tails ? Q_TAIL_ROWS : 1, n_out = tails ? 3 : 1;      // table rows per problem, point arrays written
+    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * rows * ((size_t)nint + 1))));
+    const int64_t plane = (int64_t)G * (nint + 1);
     const size_t b_probs = meb_align(sizeof(QProb) * B), b_coef = meb_align(sizeof(double) * S.coef.size());
     const size_t b_g = meb_align(sizeof(double) * deg), b_in = b_probs + b_coef + 2 * b_g;
-    const size_t b_mass = meb_align(sizeof(double) * B), b_tab = meb_align(sizeof(double) * (size_t)G * ((size_t)nint + 1));
+    const size_t b_mass = meb_align(sizeof(double) * B) * (tails ? 2 : 1);   // masses, then means
+    const size_t b_tab = meb_align(sizeof(double) * rows * (size_t)plane);
     const size_t b_x = stage ? meb_align(sizeof(double) * (size_t)S.n_tot) : 0;
     MebWorkspace &ws = meb_ws();
-    if (ws.reserve(b_in + b_mass + b_tab + 2 * b_x, b_in + b_mass + b_x)) return 1;
+    if (ws.reserve(b_in + b_mass + b_tab + (1 + n_out) * b_x, b_in + b_mass + b_x)) return 1;
     char *h = ws.host, *d = ws.dev;
     std::memcpy(h, S.probs.data(), sizeof(QProb) * B);
     std::memcpy(h + b_probs, S.coef.data(), sizeof(double) * S.coef.size());
@@ -315,43 +487,60 @@ static int q_on_rule(const char *fn, bool inverse, int32_t B, const mlmc_basis *
     const QProb *d_probs = (const QProb *)d;
     const double *d_coef = (const double *)(d + b_probs);
     const double *d_gx = (const double *)(d + b_probs + b_coef), *d_gw = (const double *)(d + b_probs + b_coef + b_g);
-    double *d_mass = (double *)(d + b_in), *d_tab = (double *)(d + b_in + b_mass);
+    double *d_mass = (double *)(d + b_in), *d_mean = (double *)(d + b_in + b_mass / 2), *d_tab = (double *)(d + b_in + b_mass);
     const double *d_x = x;
-    double *d_out = out;
+    double *d_out = out, *d_lower = lower_out, *d_upper = upper_out;
     if (stage) {
         std::memcpy(h + b_in + b_mass, x, sizeof(double) * (size_t)S.n_tot);
         MLMC_HIP_CHECK(hipMemcpyAsync(d + b_in + b_mass + b_tab, h + b_in + b_mass, sizeof(double) * (size_t)S.n_tot, hipMemcpyHostToDevice, st));
         d_x = (const double *)(d + b_in + b_mass + b_tab);
         d_out = (double *)(d + b_in + b_mass + b_tab + b_x);
+        d_lower = (double *)(d + b_in + b_mass + b_tab + 2 * b_x);
+        d_upper = (double *)(d + b_in + b_mass + b_tab + 3 * b_x);
     }
     QTiming &tm = q_timing();
     size_t timed = 0;
     for (int g0 = 0; g0 < B; g0 += G) {
         const int np = std::min(G, B - g0);
         const int64_t cells = (int64_t)np * nint;
-        hipLaunchKernelGGL(k_q_cells, dim3((unsigned)((cells + 127) / 128)), dim3(128), 0, st, d_probs + g0, np, nint, d_coef, d_gx, d_gw,
-                           deg, d_tab);
-        hipLaunchKernelGGL(k_q_prefix, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st, np, nint, d_tab, d_mass + g0);
+        if (tails) {
+            hipLaunchKernelGGL(k_q_tail_cells, dim3((unsigned)((cells + 127) / 128)), dim3(128), 0, st, d_probs + g0, np, nint, d_coef, d_gx,
+                               d_gw, deg, d_tab, plane);
+            hipLaunchKernelGGL(k_q_tail_prefix, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st, np, nint, d_tab, plane, d_probs + g0,
+                               d_mass + g0, d_mean + g0);
+        } else {
+            hipLaunchKernelGGL(k_q_cells, dim3((unsigned)((cells + 127) / 128)), dim3(128), 0, st, d_probs + g0, np, nint, d_coef, d_gx, d_gw,
+                               deg, d_tab);
+            hipLaunchKernelGGL(k_q_prefix, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st, np, nint, d_tab, d_mass + g0);
+        }
         const int64_t pt0 = S.probs[g0].x_off;
         const int64_t npts = (g0 + np < B ? S.probs[g0 + np].x_off : S.n_tot) - pt0;
         if (npts > 0) {
             const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));
             hipEvent_t e0, e1;
             const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
-            if (inverse)
+            if (mode != Q_CDF)
                 hipLaunchKernelGGL(k_q_quantile, grid, dim3(Q_THREADS), 0, st, d_probs + g0, np, nint, pt0, npts, d_coef, (const double *)d_tab,
                                    d_gx, d_gw, deg, d_x, d_out);
             else
                 hipLaunchKernelGGL(k_q_cdf, grid, dim3(Q_THREADS), 0, st, d_probs + g0, np, nint, pt0, npts, d_coef, (const double *)d_tab,
                                    d_gx, d_gw, deg, d_x, d_out);
+            if (tails)                           // the quantiles, as k_q_quantile has just written them, are the points
+                hipLaunchKernelGGL(k_q_tails, grid, dim3(Q_THREADS), 0, st, d_probs + g0, np, nint, pt0, npts, d_coef, (const double *)d_tab,
+                                   plane, d_gx, d_gw, deg, (const double *)d_out, d_lower, d_upper);
             if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
         }
         MLMC_HIP_CHECK(hipGetLastError());
     }
     if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)S.n_tot, hipMemcpyDeviceToHost, st));
-    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(h + b_in, d_mass, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    if (stage && tails) {
+        MLMC_HIP_CHECK(hipMemcpyAsync(lower_out, d_lower, sizeof(double) * (size_t)S.n_tot, hipMemcpyDeviceToHost, st));
+        MLMC_HIP_CHECK(hipMemcpyAsync(upper_out, d_upper, sizeof(double) * (size_t)S.n_tot, hipMemcpyDeviceToHost, st));
+    }
+    if (mass_out || mean_out) MLMC_HIP_CHECK(hipMemcpyAsync(h + b_in, d_mass, b_mass, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, h + b_in, sizeof(double) * B);
+    if (mean_out) std::memcpy(mean_out, h + b_in + b_mass / 2, sizeof(double) * B);
     for (size_t k = 0; k < timed; ++k) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
@@ -414,7 +603,7 @@ int mlmc_density_cdf_batch(int32_t B, const mlmc_basis *const *bases, const int3
                            const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *x,
                            const int64_t *n, double *out, double *mass_out, int mem_kind) {
     MLMC_API_GUARD;
-    return q_on_rule("mlmc_density_cdf_batch", false, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, x, n, out, mass_out,
+    return q_on_rule("mlmc_density_cdf_batch", Q_CDF, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, x, n, out, mass_out,
                      mem_kind);
 }
 
@@ -422,8 +611,17 @@ int mlmc_density_quantiles_batch(int32_t B, const mlmc_basis *const *bases, cons
                                  const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                  const double *p, const int64_t *n, double *out, double *mass_out, int mem_kind) {
     MLMC_API_GUARD;
-    return q_on_rule("mlmc_density_quantiles_batch", true, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, out,
+    return q_on_rule("mlmc_density_quantiles_batch", Q_QUANTILES, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, out,
                      mass_out, mem_kind);
+}
+
+int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                  const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                  const double *p, const int64_t *n, double *q_out, double *lower_out, double *upper_out, double *mass_out,
+                                  double *mean_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_tail_means_batch", Q_TAILS, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, q_out,
+                     mass_out, mem_kind, lower_out, upper_out, mean_out);
 }
 
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches) {

@@ -46,6 +46,11 @@ def _check_level(what, level):
     return float(level)
 
 
+def _check_tail(what, tail):
+    if tail not in ("upper", "lower"):
+        raise ValueError("{}: tail must be 'upper' or 'lower', got {!r}".format(what, tail))
+
+
 class Estimate:
     """Wrapper methods for moment estimation, sample allocation and PDF reconstruction (reference: estimator.py:11-341)."""
 
@@ -420,7 +425,39 @@ class Estimate:
             quantile_bands(replicates, success, level), replicates [B, M, P], success [B, M] the solver's verdict per replicate,
             n_ok [M] successful replicates per component, seed)"""
         from .tool import simple_distribution
-        what = "bootstrap_component_quantiles"
+        probs, densities, distrs, success, seed, level = self._bootstrap_replicate_densities(
+            "bootstrap_component_quantiles", probs, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
+            moments_fns, densities)
+        q = self.estimate_component_quantiles(probs, densities=densities)[0]
+        replicates = np.array(simple_distribution.quantiles(distrs, probs), dtype=np.float64).reshape(success.shape + (probs.size,))
+        lo, hi = quantile_bands(replicates, success, level)
+        return QuantileBands(q, lo, hi, replicates, success, np.sum(success, axis=0), seed)
+
+    def bootstrap_component_shortfall(self, probs, n_subsamples=100, sample_vector=None, seed=None, level=0.9, tail="upper", tol=1e-8,
+                                      reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """Bootstrap confidence bands of estimate_component_shortfall: bootstrap_component_quantiles with the expected shortfall
+        (tool.simple_distribution.tail_means) of every replicate density in place of its quantiles.  Same arguments, the same
+        replicate densities for the same seed, and
+        :param tail: "upper" (E[X | X >= Q(p)]) or "lower" (E[X | X <= Q(p)])
+        :return: QuantileBands whose q [M, P] = estimate_component_shortfall(probs, tail, densities=densities)[0], lo, hi [M, P]
+            and replicates [B, M, P] hold the shortfall values; success, n_ok, seed as in bootstrap_component_quantiles"""
+        from .tool import simple_distribution
+        what = "bootstrap_component_shortfall"
+        _check_tail(what, tail)
+        probs, densities, distrs, success, seed, level = self._bootstrap_replicate_densities(
+            what, probs, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol, moments_fns, densities)
+        es = self.estimate_component_shortfall(probs, tail, densities=densities)[0]
+        _, lower, upper, _ = simple_distribution.tail_means(distrs, probs)
+        replicates = np.array(upper if tail == "upper" else lower, dtype=np.float64).reshape(success.shape + (probs.size,))
+        lo, hi = quantile_bands(replicates, success, level)
+        return QuantileBands(es, lo, hi, replicates, success, np.sum(success, axis=0), seed)
+
+    def _bootstrap_replicate_densities(self, what, probs, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
+                                       moments_fns, densities):
+        """The part bootstrap_component_quantiles and bootstrap_component_shortfall share: argument checks, the densities of the
+        estimate, one est_bootstrap_components pass and the B * M replicate max-entropy problems solved in one batched call.
+        :return: (probs [P], densities, distrs [B * M] solved replicate distributions (replicate-major), success [B, M], seed, level)"""
+        from .tool import simple_distribution
         level = _check_level(what, level)
         try:
             probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
@@ -435,7 +472,6 @@ class Estimate:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, fns)
         if len(densities) != len(fns):
             raise ValueError("{}: {} densities for {} components".format(what, len(densities), len(fns)))
-        q = self.estimate_component_quantiles(probs, densities=densities)[0]
         n, s, _ = qe.bootstrap_component_moments(self._quantity, fns, B, k, seed)
         if np.any(np.sum(n, axis=1) == 0):
             raise Exception("All samples were masked")
@@ -450,10 +486,8 @@ class Estimate:
                 distrs.append(simple_distribution.SimpleDistribution(mobj, np.stack((mu, np.ones(mobj.size)), axis=1),
                                                                      domain=mobj.domain))
         results = simple_distribution.estimate_densities_minimize(distrs, tol, reg_param)
-        replicates = np.array(simple_distribution.quantiles(distrs, probs), dtype=np.float64).reshape(B, M, probs.size)
         success = np.array([bool(r.success) for r in results], dtype=bool).reshape(B, M)
-        lo, hi = quantile_bands(replicates, success, level)
-        return QuantileBands(q, lo, hi, replicates, success, np.sum(success, axis=0), seed)
+        return probs, densities, distrs, success, seed, level
 
     def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
         """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""
@@ -591,6 +625,26 @@ class Estimate:
         q = simple_distribution.quantiles([d[0] for d in densities], probs)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return np.array(q, dtype=np.float64).reshape(len(densities), probs.size), success
+
+    def estimate_component_shortfall(self, probs, tail="upper", tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
+                                     densities=None):
+        """Expected shortfall (CVaR) of the maximum-entropy density of EVERY scalar component of the quantity, in one batched
+        device call (tool.simple_distribution.tail_means): E[X | X >= Q(p)] for tail = "upper", E[X | X <= Q(p)] for "lower".
+
+        :param probs: probabilities, the same for every component
+        :param densities: as in estimate_component_quantiles
+        :return: (es, q, success): es [M, len(probs)] the shortfall of component m at every level, q [M, len(probs)] the
+            quantiles they start from (bit for bit estimate_component_quantiles'), success [M] bool the solver's verdict"""
+        from .tool import simple_distribution
+        _check_tail("estimate_component_shortfall", tail)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+        q, lower, upper, _ = simple_distribution.tail_means([d[0] for d in densities], probs)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        shape = (len(densities), probs.size)
+        es = np.array(upper if tail == "upper" else lower, dtype=np.float64).reshape(shape)
+        return es, np.array(q, dtype=np.float64).reshape(shape), success
 
     def get_level_samples(self, level_id, n_samples=None):
         chunk_spec = next(self._sample_storage.chunks(level_id=level_id, n_samples=n_samples))

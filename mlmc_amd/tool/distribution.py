@@ -8,7 +8,7 @@ import numpy as np
 import scipy.integrate as integrate
 from scipy.optimize import OptimizeResult
 
-from .simple_distribution import _cdf, _device_density, _quantile, _solve_on_device
+from .simple_distribution import _cdf, _device_density, _expected_shortfall, _quantile, _solve_on_device
 
 
 class Distribution:
@@ -137,6 +137,11 @@ class Distribution:
         """Q(p) of the stored multipliers on this distribution's quadrature (simple_distribution.quantiles with one
         distribution; p may be a float64 torch device tensor)."""
         return _quantile(self, p)
+
+    def expected_shortfall(self, p, tail="upper"):
+        """Expected shortfall (CVaR) at level p of the stored multipliers on this distribution's quadrature: E[X | X >= Q(p)]
+        for tail = "upper", E[X | X <= Q(p)] for "lower" (simple_distribution.tail_means with one distribution)."""
+        return _expected_shortfall(self, p, tail)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

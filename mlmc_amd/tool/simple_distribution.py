@@ -203,11 +203,13 @@ def cdfs(distrs, values):
     return out
 
 
-def _on_rule(distrs, points, inverse, what):
-    """mlmc_density_quantiles_batch (inverse) / mlmc_density_cdf_batch of a list of distributions in ONE call.
+def _on_rule(distrs, points, inverse, what, tails=False):
+    """mlmc_density_quantiles_batch (inverse) / mlmc_density_cdf_batch / mlmc_density_tail_means_batch (tails) of a list of
+    distributions in ONE call.
     points: per distribution a NumPy-convertible array, or torch device tensors for all of them (float64; the results are
     device tensors then and nothing is copied to the host).
-    :return: (list of arrays shaped like the points, masses [B])"""
+    :return: (list of arrays shaped like the points, masses [B]); with tails ((q, lower, upper, means [B]), masses [B]), q, lower
+        and upper each such a list"""
     B = len(distrs)
     n_int = {d.n_intervals for d in distrs}
     degs = {d._gauss_degree for d in distrs}
@@ -224,25 +226,36 @@ def _on_rule(distrs, points, inverse, what):
             raise ValueError(what + ": device points must be float64 device tensors for every distribution")
         shaped = list(points)
         flat = shaped[0].contiguous().reshape(-1) if B == 1 else torch.cat([p.reshape(-1) for p in shaped])
-        out = torch.empty_like(flat)
+        outs = [torch.empty_like(flat) for _ in range(3 if tails else 1)]
         n = np.array([p.numel() for p in shaped], dtype=np.int64)
         torch.cuda.current_stream(flat.device).synchronize()         # the library reads it on its own stream
         kind = _lib.DEVICE
     else:
         shaped = [np.atleast_1d(np.asarray(p, dtype=np.float64)) for p in points]
         flat = np.ascontiguousarray(np.concatenate([p.reshape(-1) for p in shaped]))
-        out = np.empty_like(flat)
+        outs = [np.empty_like(flat) for _ in range(3 if tails else 1)]
         n = np.array([p.size for p in shaped], dtype=np.int64)
         kind = _lib.HOST
-    fn = _lib.lib().mlmc_density_quantiles_batch if inverse else _lib.lib().mlmc_density_cdf_batch
-    _lib.check(fn(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
-                  int(n_int.pop()), int(degs.pop()), _lib.ptr(flat), _lib.ptr(n), _lib.ptr(out), _lib.ptr(mass), kind))
-    if kind == _lib.DEVICE:
-        import torch
-        parts = [out] if B == 1 else list(torch.split(out, [int(k) for k in n]))
+    head = (B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
+            int(n_int.pop()), int(degs.pop()), _lib.ptr(flat), _lib.ptr(n))
+    if tails:
+        mean = np.empty(B)
+        _lib.check(_lib.lib().mlmc_density_tail_means_batch(*head, _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
+                                                            _lib.ptr(mass), _lib.ptr(mean), kind))
     else:
-        parts = np.split(out, np.cumsum(n)[:-1])
-    return [p.reshape(s.shape) for p, s in zip(parts, shaped)], mass
+        fn = _lib.lib().mlmc_density_quantiles_batch if inverse else _lib.lib().mlmc_density_cdf_batch
+        _lib.check(fn(*head, _lib.ptr(outs[0]), _lib.ptr(mass), kind))
+
+    def per_distribution(out):
+        if kind == _lib.DEVICE:
+            import torch
+            parts = [out] if B == 1 else list(torch.split(out, [int(k) for k in n]))
+        else:
+            parts = np.split(out, np.cumsum(n)[:-1])
+        return [p.reshape(s.shape) for p, s in zip(parts, shaped)]
+    if tails:
+        return (per_distribution(outs[0]), per_distribution(outs[1]), per_distribution(outs[2]), mean), mass
+    return per_distribution(outs[0]), mass
 
 
 def cdfs_on_rule(distrs, values):
@@ -269,6 +282,31 @@ def quantiles(distrs, probs):
     if not distrs:
         return []
     return _on_rule(distrs, _per_distribution(probs, len(distrs)), True, "quantiles")[0]
+
+
+def tail_means(distrs, probs):
+    """Quantiles and tail means (expected shortfall, CVaR) of many distributions through ONE device call
+    (mlmc_density_tail_means_batch).  With Q = `quantiles` and the rule of `cdfs_on_rule`, entry b of
+        q     = Q_b(probs[b]), bit for bit the value of `quantiles`,
+        lower = E[X | X <= q], the lower expected shortfall at level p,
+        upper = E[X | X >= q], the upper one,
+    each a mean of the density on the distribution's own quadrature, normalised by the mass of the tail on the same rule
+    (include/mlmc_hip.h); lower(Q(0)) = a, upper(Q(1)) = b, NaN for p outside [0, 1] or NaN; mean [B] is the mean of every
+    distribution on its rule.  p lower + (1 - p) upper equals the mean only up to the resolution of the rule.
+    probs: as in `quantiles` (one array for all or one per distribution, a common quadrature or ValueError; float64 device
+    tensors stay on the device).  :return: (q, lower, upper, mean): three lists of arrays shaped like the probabilities, mean [B]"""
+    distrs = list(distrs)
+    if not distrs:
+        return [], [], [], np.empty(0)
+    return _on_rule(distrs, _per_distribution(probs, len(distrs)), True, "tail_means", tails=True)[0]
+
+
+def _expected_shortfall(dist, p, tail):
+    """the B = 1 call of `tail_means`: upper(Q(p)) or lower(Q(p)); a torch device tensor stays on the device"""
+    if tail not in ("upper", "lower"):
+        raise ValueError("expected_shortfall: tail must be 'upper' or 'lower', got {!r}".format(tail))
+    _, lower, upper, _ = _on_rule([dist], [p], True, "expected_shortfall", tails=True)[0]
+    return upper[0] if tail == "upper" else lower[0]
 
 
 def _quantile(dist, p):
@@ -419,6 +457,12 @@ class SimpleDistribution:
         call with one distribution, hence bit for bit its value).  p: array-like, or a float64 torch device tensor (the result
         is a device tensor then, e.g. for inverse-transform sampling with the caller's own uniforms)."""
         return _quantile(self, p)
+
+    def expected_shortfall(self, p, tail="upper"):
+        """Expected shortfall (CVaR) at level p on this distribution's quadrature: E[X | X >= Q(p)] for tail = "upper",
+        E[X | X <= Q(p)] for "lower" (see `tail_means`, of which this is the call with one distribution, hence bit for bit its
+        value).  p: as in `quantile`."""
+        return _expected_shortfall(self, p, tail)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

@@ -16,7 +16,16 @@ many-points regime: B in {1, 8, 64} problems x n in {10^6, 10^7} device-resident
                  (tests/quantile_cases.py, same iteration and stopping rules) on 2000 of problem 0's uniforms
   fp64_fraction  steps x gauss_degree x (2 R1 + EXP_FLOPS) x points / kernel_ms against the 78.6 TFLOP/s fp64 vector peak
 (--config B,R1,n runs one many-points configuration, e.g. under rocprofv3 --kernel-trace --stats.)
-Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n] [--reps K]"""
+--tails: simple_distribution.tail_means against simple_distribution.quantiles, alternating in one process,
+on the same M in {16, 256, 1024} solved densities at 3 and 99 probabilities:
+  tail_means_ms / quantiles_ms   wall time of the one device call each
+  quad_ms_scaled                 what exists without the entry: scipy.integrate.quad of x density(x) and of density(x) from
+                                 d.quantile(p) to the domain end per (component, probability), TIMED ON A SUBSET of at most
+                                 4 components x 3 probabilities AND SCALED to M x n_p
+and on B = 1, R1 = 25, n = 10^6 device-resident probabilities (--config B,R1,n with --tails: that configuration alone):
+  tails_kernel_ms / quantile_kernel_ms   HIP-event time of the point kernels of one call (mlmc_density_quantiles_kernel_time)
+  tails_call_ms / quantile_call_ms       wall time of the C entry
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n] [--tails] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -27,6 +36,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+from scipy.integrate import quad
 from scipy.optimize import brentq
 
 from mlmc_amd import _lib, Legendre
@@ -127,15 +137,88 @@ def many_points(B, R1, n, reps):
                 steps=round(steps, 2), fp64_fraction=round(flops / (kernel_ms * 1e-3) / PEAK_FP64, 4), monotone=mono, all_success=ok)
 
 
+def alternating(fns, reps):
+    """wall ms per call of every function after one warm-up call each, the functions taking turns inside every repetition"""
+    for fn in fns:
+        fn()
+    total = [0.0] * len(fns)
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            total[k] += time.perf_counter() - t0
+    return [t * 1e3 / reps for t in total]
+
+
+def tails_few_points(M, probs, reps):
+    distrs, ok = mixtures(M, 25)
+    t_ms, q_ms = alternating([lambda: sd.tail_means(distrs, probs), lambda: sd.quantiles(distrs, probs)], reps)
+    q, lower, upper, _ = sd.tail_means(distrs, probs)
+    sub_d, sub_k = distrs[:4], np.linspace(0, len(probs) - 1, 3).astype(int)
+    t0 = time.perf_counter()
+    worst = 0.0
+    for d, qd, ud in zip(sub_d, q, upper):
+        for k in sub_k:
+            x = d.quantile(probs[k])[0]
+            num = quad(lambda v: v * d.density(v)[0], x, DOM[1], epsabs=1e-12, epsrel=1e-12)[0]
+            den = quad(lambda v: d.density(v)[0], x, DOM[1], epsabs=1e-12, epsrel=1e-12)[0]
+            worst = max(worst, abs(num / den - ud[k]))
+    sub_ms = (time.perf_counter() - t0) * 1e3
+    quad_ms = sub_ms / (len(sub_d) * len(sub_k)) * M * len(probs)
+    return dict(M=M, n_p=len(probs), tail_means_ms=round(t_ms, 3), quantiles_ms=round(q_ms, 3), quad_ms_scaled=round(quad_ms, 1),
+                quad_subset=[len(sub_d), len(sub_k)], quad_vs_tail_means=float(worst), all_success=ok)
+
+
+def tails_many_points(B, R1, n, reps):
+    distrs, ok = mixtures(B, R1, seed=5)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(B * 131 + R1)
+    flat = torch.rand(B * n, dtype=torch.float64, device="cuda", generator=g)
+    q, lower, upper = torch.empty_like(flat), torch.empty_like(flat), torch.empty_like(flat)
+    torch.cuda.synchronize()
+    handles, r1, lam, sig = sd._batch_problem_args(distrs)
+    a, b = np.full(B, DOM[0]), np.full(B, DOM[1])
+    cnt = np.full(B, n, dtype=np.int64)
+    n_int, deg = distrs[0].n_intervals, distrs[0]._gauss_degree
+    lib, P = _lib.lib(), _lib.ptr
+    head = (B, C.cast(handles, C.c_void_p), P(r1), P(lam), P(sig), P(a), P(b), n_int, deg, P(flat), P(cnt))
+    calls = [lambda: _lib.check(lib.mlmc_density_tail_means_batch(*head, P(q), P(lower), P(upper), None, None, _lib.DEVICE)),
+             lambda: _lib.check(lib.mlmc_density_quantiles_batch(*head, P(q), None, _lib.DEVICE))]
+    k_ms, k_n = C.c_double(), C.c_int64()
+    for fn in calls:
+        fn()
+    wall, kern = [0.0, 0.0], [0.0, 0.0]
+    for _ in range(reps):
+        for k, fn in enumerate(calls):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k] += (time.perf_counter() - t0) * 1e3 / reps
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k] += k_ms.value / reps
+    calls[0]()
+    ordered = bool(torch.all((lower <= q) & (q <= upper)).item())
+    return dict(B=B, R1=R1, n=n, tails_kernel_ms=round(kern[0], 3), quantile_kernel_ms=round(kern[1], 3), tails_call_ms=round(wall[0], 3),
+                quantile_call_ms=round(wall[1], 3), ordered=ordered, all_success=ok)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--config", help="one many-points configuration B,R1,n for a profiler run")
+    ap.add_argument("--tails", action="store_true", help="tail_means against quantiles (DESIGN.md section 3.5.9)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
-    if a.config:
+    if a.tails:
+        cfg = tuple(int(v) for v in a.config.split(",")) if a.config else (1, 25, 1_000_000)
+        if not a.config:
+            Ms = (16,) if a.quick else (16, 256, 1024)
+            out["tails_few"] = [tails_few_points(M, probs, a.reps) for M in Ms
+                                for probs in (np.array([0.05, 0.5, 0.95]), np.linspace(0.01, 0.99, 99))]
+        out["tails_many"] = [tails_many_points(*cfg, a.reps)]
+    elif a.config:
         B, R1, n = (int(v) for v in a.config.split(","))
         out["many"] = [many_points(B, R1, n, a.reps)]
     else:
