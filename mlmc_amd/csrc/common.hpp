@@ -236,7 +236,7 @@ bool square_product_table_chebyshev(int R, std::vector<double> &out);
 int launch_cov_from_values(mlmc_accum *a, int level, int comp, const double *d_vf, const double *d_vc, const uint8_t *d_mask,
                            int64_t n, bool count, int gram_mode = 0);
 int ensure(void **p, size_t *cap, size_t bytes);
-// maxent.hip (shared with the batched solver, maxent_batch.hip)
+// maxent.hip (shared with the batched solver, maxent_batch.hip, and the density entries, density.hip)
 void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w);   // nodes / weights on [-1, 1]
 std::vector<double> effective_coeffs(const mlmc_basis *b, const double *lambda, const double *sigma, int R1);
 int timing_begin(mlmc_accum *a);

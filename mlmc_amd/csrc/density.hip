@@ -1,0 +1,653 @@
+// The max-entropy densities at points, on the device (gfx950): values, integrals, CDFs, quantiles and tail means of one problem or
+// of a batch.  The arithmetic of the density is density.hpp's; this file has the kernels and the host entries.  A single entry
+// (mlmc_density_eval, mlmc_density_integrate) is its batched twin at B = 1.
+//
+//   k_q_density   : density at the points of every problem: grid (problem, y-blocks), grid-stride over the problem's points
+//   k_q_integrate : the Gauss-Legendre integral over [lo_i, hi_i], one thread per interval of the call
+//
+// CDFs and quantiles.  For a problem (basis, R1, lambda, sigma, [a, b]) and a rule (n_intervals, gauss_degree) the function that is
+// tabulated and inverted is
+//     Fhat(x) = (P_j + I(e_j, x)) / T,   x in cell j = [e_j, e_{j+1}],   e_j = a + j h, h = (b - a) / n_intervals, e_n = b,
+// with C_j = the gauss_degree-point Gauss-Legendre integral of the density over cell j (density_integral), P_0 = 0,
+// P_{j+1} = P_j + C_j summed in cell order, T = P_n, and I the same rule on the partial cell.
+//
+//   k_q_cells     : C_j of every problem, one thread per (problem, cell), into the table row [n_intervals + 1] of the problem
+//   k_q_prefix    : the in-order prefix P and the mass T, one thread per problem
+//   k_q_quantile  : one thread per (problem, p): binary search of p T in P, linear interpolate in the cell, then a bracketed
+//                   Newton iteration on g(x) = P_j + I(e_j, x) - p T with g' = density(x); bisection whenever the step leaves
+//                   the bracket or is not finite
+//   k_q_cdf       : Fhat at arbitrary values, one thread per value (cell lookup + one partial-cell rule)
+// Tail means (expected shortfall, mlmc_density_tail_means_batch): with A_j / B_j the cell sums of (t - a) rho / (b - t) rho on the
+// nodes of C_j, V the forward prefix of the A_j, S and W the backward suffixes of the C_j and B_j,
+//     lower(x) = a + (V_j + A(e_j, x)) / (P_j + I(e_j, x)),   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / (S_{j+1} + I(x, e_{j+1})).
+//   k_q_cells<true>  : C_j (the same bits), A_j, B_j in one walk over the nodes
+//   k_q_prefix<true> : P, V forwards and S, W backwards
+//   k_q_tails        : one thread per (problem, x): cell lookup of k_q_cdf, then the two partial-cell rules [e_j, x] and
+//                      [x, e_{j+1}] in ONE loop over the nodes, their two density evaluations interleaved term by term
+// One thread owns one point from start to end, every sum has a fixed order and every loop a constant bound: a result does not
+// depend on the batch, on the position of the problem in it or on the other points.  No atomics, no data-dependent launch.
+// A thread of the flat-index kernels finds its problem by a binary search of its point index in the problems' offsets, so that the
+// same launch geometry serves thousands of problems with a few points each and a few problems with 10^7 points each.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "density.hpp"
+#include "maxent_batch.hpp"
+
+namespace mlmc {
+
+constexpr int Q_THREADS = 256;
+constexpr int Q_MAX_IT = 64;                           // iteration cap of the bracketed Newton iteration
+constexpr int Q_MAX_INTERVALS = 1 << 20;
+constexpr size_t Q_TABLE_BYTES = (size_t)64 << 20;     // bound of the prefix tables; more problems are processed in groups
+constexpr size_t Q_DIRECT_BYTES = (size_t)1 << 20;     // host point arrays beyond this are copied to the device straight from the caller's
+                                                       // memory (faster from 8 MB on, measured); smaller ones ride in the block's one copy
+
+__device__ __forceinline__ double q_integral(const QProb &P, const double *__restrict__ c, double a, double b,
+                                             const double *__restrict__ nodes, const double *__restrict__ wts, int deg) {
+    return with_kind(P.bp.kind, [&](auto K) { return density_integral<decltype(K)::value>(P.bp, c, P.n_coef, a, b, nodes, wts, deg); });
+}
+
+// sums of one cell [lo, hi] of the domain [a, b] in one walk over the nodes: C = the value (and the bits) of density_integral,
+// A = sum w (t - a) rho, B = sum w (b - t) rho on the same nodes t and weights w
+template <int KIND>
+__device__ __forceinline__ void q_cell_sums(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b, double lo,
+                                            double hi, const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                            double &C, double &A, double &B) {
+    const double half = 0.5 * (hi - lo), mid = 0.5 * (hi + lo);
+    double acc = 0.0, acc_a = 0.0, acc_b = 0.0;
+    for (int k = 0; k < deg; ++k) {
+        const double t = __builtin_fma(half, nodes[k], mid), w = wts[k];
+        const double rho = density_value<KIND>(bp, c, R, t);
+        acc = __builtin_fma(w, rho, acc);
+        acc_a = __builtin_fma(w, (t - a) * rho, acc_a);
+        acc_b = __builtin_fma(w, (b - t) * rho, acc_b);
+    }
+    C = acc * half;
+    A = acc_a * half;
+    B = acc_b * half;
+}
+
+// the partial-cell rules of a point x in the cell [lo, hi]: I and A on [lo, x], I and B on [x, hi], node k of both in one step
+template <int KIND>
+__device__ __forceinline__ void q_tail_sums(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b, double lo,
+                                            double x, double hi, const double *__restrict__ nodes, const double *__restrict__ wts,
+                                            int deg, double &I_lo, double &A_lo, double &I_hi, double &B_hi) {
+    const double half0 = 0.5 * (x - lo), mid0 = 0.5 * (x + lo), half1 = 0.5 * (hi - x), mid1 = 0.5 * (hi + x);
+    double i0 = 0.0, a0 = 0.0, i1 = 0.0, b1 = 0.0;
+    for (int k = 0; k < deg; ++k) {
+        const double t0 = __builtin_fma(half0, nodes[k], mid0), t1 = __builtin_fma(half1, nodes[k], mid1), w = wts[k];
+        double rho0, rho1;
+        density_value2<KIND>(bp, c, R, t0, t1, rho0, rho1);
+        i0 = __builtin_fma(w, rho0, i0);
+        a0 = __builtin_fma(w, (t0 - a) * rho0, a0);
+        i1 = __builtin_fma(w, rho1, i1);
+        b1 = __builtin_fma(w, (b - t1) * rho1, b1);
+    }
+    I_lo = i0 * half0;
+    A_lo = a0 * half0;
+    I_hi = i1 * half1;
+    B_hi = b1 * half1;
+}
+
+// cell edge j of the composite rule as an fp64 number: a + j h (two roundings, the file is compiled without contraction)
+__device__ __forceinline__ double q_edge(const QProb &P, double h, int nint, int j) {
+    return j >= nint ? P.b : P.a + (double)j * h;
+}
+
+// the cell of a value: the largest j < n with e_j <= v
+__device__ __forceinline__ int q_cell_of(const QProb &P, double h, int nint, double v) {
+    int lo = 0, hi = nint;
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (q_edge(P, h, nint, mid) <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// distance from |x| to the next larger double
+__device__ __forceinline__ double q_spacing(double x) {
+    const double ax = fabs(x);
+    return __longlong_as_double(__double_as_longlong(ax) + 1) - ax;
+}
+
+// the problem of point `idx`: the largest k with probs[k].x_off <= idx (problems without points share their successor's offset)
+__device__ __forceinline__ int q_find(const QProb *__restrict__ probs, int nprob, int64_t idx) {
+    int lo = 0, hi = nprob;
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (probs[mid].x_off <= idx) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_q_density(const QProb *__restrict__ probs, const double *__restrict__ coef,
+                                                   const double *__restrict__ x, double *__restrict__ out) {
+    const QProb P = probs[blockIdx.x];
+    const double *c = coef + P.c_off;
+    for (int64_t i = (int64_t)blockIdx.y * blockDim.x + threadIdx.x; i < P.n; i += (int64_t)gridDim.y * blockDim.x) {
+        const double v = x[P.x_off + i];
+        out[P.x_off + i] = with_kind(P.bp.kind, [&](auto K) { return density_value<decltype(K)::value>(P.bp, c, P.n_coef, v); });
+    }
+}
+
+__global__ __launch_bounds__(128) void k_q_integrate(const QProb *__restrict__ probs, int nprob, int64_t npts,
+                                                     const double *__restrict__ coef, const double *__restrict__ lo,
+                                                     const double *__restrict__ hi, const double *__restrict__ nodes,
+                                                     const double *__restrict__ wts, int deg, double *__restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npts) return;
+    const QProb P = probs[q_find(probs, nprob, idx)];
+    out[idx] = q_integral(P, coef + P.c_off, lo[idx], hi[idx], nodes, wts, deg);
+}
+
+// the table rows of a problem, [n + 1] doubles each, row r of problem k at tab + r * plane + k * (n + 1): the P row alone is the
+// table of CDFs and quantiles, tail means have all four
+enum { Q_ROW_P = 0, Q_ROW_V = 1, Q_ROW_S = 2, Q_ROW_W = 3, Q_TAIL_ROWS = 4 };
+
+template <bool TAILS>
+__global__ __launch_bounds__(128) void k_q_cells(const QProb *__restrict__ probs, int nprob, int nint, const double *__restrict__ coef,
+                                                 const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                 double *__restrict__ tab, int64_t plane) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)nprob * nint) return;
+    const int k = (int)(gid / nint), j = (int)(gid - (int64_t)k * nint);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off;
+    const double h = (P.b - P.a) / (double)nint;
+    const double lo = q_edge(P, h, nint, j), hi = q_edge(P, h, nint, j + 1);
+    double *row = tab + (int64_t)k * (nint + 1);
+    if constexpr (TAILS) {
+        double C, A, B;
+        with_kind(P.bp.kind, [&](auto K) { q_cell_sums<decltype(K)::value>(P.bp, c, P.n_coef, P.a, P.b, lo, hi, nodes, wts, deg, C, A, B); });
+        row[Q_ROW_P * plane + j + 1] = C;            // summed forwards into P_{j+1}, backwards into S_j
+        row[Q_ROW_V * plane + j + 1] = A;            // summed forwards into V_{j+1}
+        row[Q_ROW_W * plane + j] = B;                // summed backwards into W_j
+    } else {
+        row[j + 1] = q_integral(P, c, lo, hi, nodes, wts, deg);
+    }
+}
+
+template <bool TAILS>
+__global__ __launch_bounds__(64) void k_q_prefix(int nprob, int nint, double *__restrict__ tab, int64_t plane, const QProb *__restrict__ probs,
+                                                 double *__restrict__ mass, double *__restrict__ mean) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nprob) return;
+    double *row = tab + (int64_t)k * (nint + 1);
+    double *__restrict__ rp = row + Q_ROW_P * plane, *__restrict__ rv = row + Q_ROW_V * plane;      // disjoint rows
+    double run = 0.0, run2 = 0.0;
+    if constexpr (TAILS) {
+        double *__restrict__ rs = row + Q_ROW_S * plane, *__restrict__ rw = row + Q_ROW_W * plane;
+        rs[nint] = 0.0;
+        rw[nint] = 0.0;
+        for (int j = nint - 1; j >= 0; --j) {        // from the last cell down, before the forward pass overwrites the C_j
+            run += rp[j + 1];
+            rs[j] = run;
+            run2 += rw[j];
+            rw[j] = run2;
+        }
+        run = 0.0;
+        run2 = 0.0;
+        rv[0] = 0.0;
+    }
+    rp[0] = 0.0;
+    for (int j = 0; j < nint; ++j) {                 // P and T are the same sums with and without the tail rows
+        run += rp[j + 1];
+        rp[j + 1] = run;
+        if constexpr (TAILS) {
+            run2 += rv[j + 1];
+            rv[j + 1] = run2;
+        }
+    }
+    mass[k] = run;
+    if constexpr (TAILS) mean[k] = probs[k].a + run2 / run;
+}
+
+template <int KIND>
+__device__ double q_invert(const QProb &P, const double *__restrict__ c, const double *__restrict__ row, int nint,
+                           const double *__restrict__ nodes, const double *__restrict__ wts, int deg, double p) {
+    const double T = row[nint];
+    if (!(T > 0.0) || !(T < __builtin_inf())) return __builtin_nan("");
+    if (!(p >= 0.0 && p <= 1.0)) return __builtin_nan("");
+    if (p == 0.0) return P.a;
+    if (p == 1.0) return P.b;
+    const double target = p * T;
+    int lo = 0, hi = nint;                  // the largest j < n with P_j <= target
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] <= target) lo = mid; else hi = mid;
+    }
+    const int j = lo;
+    const double h = (P.b - P.a) / (double)nint;
+    const double ej = q_edge(P, h, nint, j), Pj = row[j];
+    double xl = ej, gl = Pj - target;                                  // g(xl) <= 0 <= g(xh)
+    double xh = q_edge(P, h, nint, j + 1), gh = row[j + 1] - target;
+    double x = xl + (xh - xl) * (-gl / (gh - gl));                     // linear interpolate inside the cell
+    if (!(x >= xl && x <= xh)) x = 0.5 * (xl + xh);
+    const double gstop = 0x1p-52 * target;                             // g is a difference of two sums near `target`: it is 0 or at least
+                                                                       // about one spacing of them, nothing in between can be resolved
+    for (int it = 0; it < Q_MAX_IT; ++it) {
+        const double gx = (Pj + density_integral<KIND>(P.bp, c, P.n_coef, ej, x, nodes, wts, deg)) - target;
+        if (gx <= 0.0) { xl = x; gl = gx; } else { xh = x; gh = gx; }
+        if (fabs(gx) <= gstop) break;
+        double xn = x - gx / density_value<KIND>(P.bp, c, P.n_coef, x);
+        if (!(xn > xl && xn < xh)) xn = 0.5 * (xl + xh);                // the step left the bracket or is not finite: bisection
+        if (fabs(xn - x) <= q_spacing(x)) break;
+        x = xn;
+    }
+    return fabs(gl) <= fabs(gh) ? xl : xh;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_quantile(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                          const double *__restrict__ coef, const double *__restrict__ tab,
+                                                          const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                          const double *__restrict__ p, double *__restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off, *row = tab + (int64_t)k * (nint + 1);
+    const double pv = p[idx];
+    out[idx] = with_kind(P.bp.kind, [&](auto K) { return q_invert<decltype(K)::value>(P, c, row, nint, nodes, wts, deg, pv); });
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_cdf(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                     const double *__restrict__ coef, const double *__restrict__ tab,
+                                                     const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                     const double *__restrict__ x, double *__restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *row = tab + (int64_t)k * (nint + 1);
+    const double T = row[nint], v = x[idx];
+    double f;
+    if (!(T > 0.0) || !(T < __builtin_inf()) || v != v) {
+        f = __builtin_nan("");
+    } else if (v <= P.a) {
+        f = 0.0;
+    } else if (v >= P.b) {
+        f = 1.0;
+    } else {
+        const double h = (P.b - P.a) / (double)nint;
+        const int j = q_cell_of(P, h, nint, v);
+        f = (row[j] + q_integral(P, coef + P.c_off, q_edge(P, h, nint, j), v, nodes, wts, deg)) / T;
+    }
+    out[idx] = f;
+}
+
+__global__ __launch_bounds__(Q_THREADS) void k_q_tails(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
+                                                       const double *__restrict__ coef, const double *__restrict__ tab, int64_t plane,
+                                                       const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                       const double *__restrict__ x, double *__restrict__ lower, double *__restrict__ upper) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npts) return;
+    const int64_t idx = pt0 + gid;
+    const int k = q_find(probs, nprob, idx);
+    const QProb P = probs[k];
+    const double *c = coef + P.c_off, *row = tab + (int64_t)k * (nint + 1);
+    const double T = row[Q_ROW_P * plane + nint], v = x[idx];
+    double lw = __builtin_nan(""), up = __builtin_nan("");
+    if (T > 0.0 && T < __builtin_inf() && v == v) {
+        const double h = (P.b - P.a) / (double)nint;
+        const int j = q_cell_of(P, h, nint, v);
+        const double ej = q_edge(P, h, nint, j), ej1 = q_edge(P, h, nint, j + 1);
+        double I_lo, A_lo, I_hi, B_hi;
+        with_kind(P.bp.kind, [&](auto K) {
+            q_tail_sums<decltype(K)::value>(P.bp, c, P.n_coef, P.a, P.b, ej, v, ej1, nodes, wts, deg, I_lo, A_lo, I_hi, B_hi);
+        });
+        const double m_lo = row[Q_ROW_P * plane + j] + I_lo, m_hi = row[Q_ROW_S * plane + j + 1] + I_hi;
+        // a tail without mass returns the point itself: lower(a) = a, upper(b) = b
+        lw = m_lo == 0.0 ? v : P.a + (row[Q_ROW_V * plane + j] + A_lo) / m_lo;
+        up = m_hi == 0.0 ? v : P.b - (row[Q_ROW_W * plane + j + 1] + B_hi) / m_hi;
+    }
+    lower[idx] = lw;
+    upper[idx] = up;
+}
+
+// HIP-event time of the point kernels (k_q_quantile / k_q_cdf; k_q_quantile + k_q_tails of a tail-means call as one), for
+// mlmc_density_quantiles_kernel_time: one event pair per group of a call, read after the call's own wait
+struct QTiming {
+    std::vector<hipEvent_t> ev;
+    double ms = 0.0;
+    int64_t launches = 0;
+    // best effort: the timing never fails a call (false: this launch is not timed)
+    bool pair(size_t k, hipEvent_t &a, hipEvent_t &b) {
+        while (ev.size() < 2 * (k + 1)) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return false;
+            ev.push_back(e);
+        }
+        a = ev[2 * k];
+        b = ev[2 * k + 1];
+        return true;
+    }
+};
+static QTiming &q_timing() {
+    static QTiming t;
+    return t;
+}
+
+// validated problems of a call: table, effective coefficients, point offsets
+struct QSetup {
+    std::vector<QProb> probs;
+    std::vector<double> coef;
+    int64_t n_tot = 0;
+};
+
+// the message of problem i; a single entry has one problem and does not name it
+static int q_fail(const char *fn, bool single, int i, const std::string &what) {
+    return single ? fail(std::string(fn) + ": " + what) : meb_fail(fn, i, what);
+}
+
+// a and b: the domains, or both NULL for an entry that takes none
+static int q_prepare(const char *fn, bool single, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                     const double *sigma, const double *a, const double *b, const int64_t *n, QSetup &S) {
+    int ldv = 0;
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *bs = bases[i];
+        if (!bs) return q_fail(fn, single, i, "null basis");
+        const int max_out = bs->out_size > 0 ? bs->out_size : bs->p.size;
+        if (R1[i] <= 0 || R1[i] > max_out) return q_fail(fn, single, i, "R1 out of range");
+        if (bs->p.kind != MLMC_LEGENDRE && bs->p.kind != MLMC_MONOMIAL && bs->p.kind != MLMC_FOURIER && bs->p.kind != MLMC_SPLINE)
+            return q_fail(fn, single, i, "unsupported basis kind");
+        if (n[i] < 0) return q_fail(fn, single, i, "n < 0");
+        if (a && !(std::isfinite(a[i]) && std::isfinite(b[i]) && a[i] < b[i]))
+            return q_fail(fn, single, i, "the domain must be finite with a < b");
+        ldv = std::max(ldv, (int)R1[i]);
+    }
+    S.probs.resize(B);
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *bs = bases[i];
+        const std::vector<double> c = effective_coeffs(bs, lambda + (size_t)i * ldv, sigma + (size_t)i * ldv, R1[i]);
+        const int Reff = bs->out_size > 0 ? bs->p.size : R1[i];
+        QProb &p = S.probs[i];
+        p.bp = bs->p;
+        p.n_coef = Reff;
+        p.c_off = (int64_t)S.coef.size();
+        p.x_off = S.n_tot;
+        p.n = n[i];
+        p.a = a ? a[i] : 0.0;
+        p.b = a ? b[i] : 0.0;
+        S.coef.insert(S.coef.end(), c.begin(), c.begin() + Reff);
+        S.n_tot += n[i];
+    }
+    return 0;
+}
+
+// One call's block in the shared workspace (meb_ws), every part 256-byte aligned:
+//   pinned buffer and device, at the same offsets:  problem table | coefficients | Gauss nodes | Gauss weights | staged point arrays
+//   behind them, device only:  the call's further arrays (outputs, tables);   pinned buffer only:  results on their way back
+// q_stage lays the block out, reserves it and fills in table, coefficients and rule; upload() sends it with the caller's host
+// points: in the block's one copy, or (`direct`: no pinned room for them) each array straight from the caller's memory.
+struct QBlock {
+    const QProb *probs;               // device
+    const double *coef, *gx, *gw;     // device
+    double *h_in[2], *d_in[2];        // staged point arrays: pinned and device side
+    double *d[5];                     // device only
+    double *h[1];                     // pinned only
+    size_t head_bytes, in_bytes;      // up to the end of the Gauss rule / of the staged arrays
+    bool direct;
+    int upload(std::initializer_list<const double *> points, size_t len) const {
+        hipStream_t st = rt().stream;
+        int i = 0;
+        for (const double *src : points) {
+            if (len > 0 && direct) MLMC_HIP_CHECK(hipMemcpyAsync(d_in[i], src, sizeof(double) * len, hipMemcpyHostToDevice, st));
+            if (len > 0 && !direct) std::memcpy(h_in[i], src, sizeof(double) * len);
+            ++i;
+        }
+        MLMC_HIP_CHECK(hipMemcpyAsync(meb_ws().dev, meb_ws().host, direct ? head_bytes : in_bytes, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
+
+// array lengths in doubles (0: an array the call does not need); deg = 0: no Gauss rule
+static int q_stage(const QSetup &S, int deg, std::initializer_list<size_t> staged, std::initializer_list<size_t> dev_only,
+                   std::initializer_list<size_t> host_only, QBlock &K) {
+    std::vector<double> gx, gw;
+    gauss_legendre(deg, gx, gw);
+    const void *src[4] = {S.probs.data(), S.coef.data(), gx.data(), gw.data()};
+    const size_t bytes[4] = {sizeof(QProb) * S.probs.size(), sizeof(double) * S.coef.size(), sizeof(double) * deg, sizeof(double) * deg};
+    size_t at[4], head = 0;
+    for (int k = 0; k < 4; ++k) {
+        at[k] = head;
+        head += meb_align(bytes[k]);
+    }
+    const auto span = [](std::initializer_list<size_t> lens) {
+        size_t sum = 0;
+        for (size_t len : lens) sum += meb_align(sizeof(double) * len);
+        return sum;
+    };
+    K.head_bytes = head;
+    K.in_bytes = head + span(staged);
+    K.direct = K.in_bytes - head > Q_DIRECT_BYTES;
+    const size_t host_in = K.direct ? head : K.in_bytes;
+    MebWorkspace &ws = meb_ws();
+    if (ws.reserve(K.in_bytes + span(dev_only), host_in + span(host_only))) return 1;
+    for (int k = 0; k < 4; ++k)
+        if (bytes[k]) std::memcpy(ws.host + at[k], src[k], bytes[k]);
+    K.probs = (const QProb *)(ws.dev + at[0]);
+    K.coef = (const double *)(ws.dev + at[1]);
+    K.gx = (const double *)(ws.dev + at[2]);
+    K.gw = (const double *)(ws.dev + at[3]);
+    const auto carve = [](char *base, size_t from, std::initializer_list<size_t> lens, double **ptr) {
+        for (size_t len : lens) {
+            *ptr++ = (double *)(base + from);
+            from += meb_align(sizeof(double) * len);
+        }
+    };
+    carve(ws.host, head, staged, K.h_in);
+    carve(ws.dev, head, staged, K.d_in);
+    carve(ws.dev, K.in_bytes, dev_only, K.d);
+    carve(ws.host, host_in, host_only, K.h);
+    return 0;
+}
+
+// mlmc_density_eval (single; x and out in host or device memory) and mlmc_density_eval_batch
+static int q_eval(const char *fn, bool single, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                  const double *sigma, const double *x, const int64_t *n, double *out, int mem_kind) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !n) return fail(std::string(fn) + ": null argument");
+    QSetup S;
+    if (q_prepare(fn, single, B, bases, R1, lambda, sigma, nullptr, nullptr, n, S)) return 1;
+    if (S.n_tot == 0) return 0;
+    if (!x || !out) return fail(std::string(fn) + ": null argument");
+    hipStream_t st = rt().stream;
+    const bool stage = mem_kind == MLMC_HOST;            // device arrays are used in place
+    const size_t np = stage ? (size_t)S.n_tot : 0;
+    QBlock K;
+    if (q_stage(S, 0, {np}, {np}, {}, K)) return 1;
+    if (K.upload({x}, np)) return 1;
+    double *d_out = stage ? K.d[0] : out;
+    int64_t n_max = 0;
+    for (const QProb &p : S.probs) n_max = std::max(n_max, p.n);
+    const unsigned gy = (unsigned)std::min<int64_t>((n_max + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_q_density, dim3((unsigned)B, gy), dim3(256), 0, st, K.probs, K.coef, stage ? (const double *)K.d_in[0] : x, d_out);
+    MLMC_HIP_CHECK(hipGetLastError());
+    if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+// mlmc_density_integrate (single) and mlmc_density_integrate_batch
+static int q_integrate(const char *fn, bool single, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                       const double *sigma, const double *lo, const double *hi, const int64_t *n, int32_t degree, double *out) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !n) return fail(std::string(fn) + ": null argument");
+    if (degree <= 0 || degree > 64) return fail(std::string(fn) + ": degree must be in 1..64");
+    QSetup S;
+    if (q_prepare(fn, single, B, bases, R1, lambda, sigma, nullptr, nullptr, n, S)) return 1;
+    if (S.n_tot == 0) return 0;
+    if (!lo || !hi || !out) return fail(std::string(fn) + ": null argument");
+    hipStream_t st = rt().stream;
+    const size_t np = (size_t)S.n_tot;
+    QBlock K;
+    if (q_stage(S, degree, {np, np}, {np}, {}, K)) return 1;
+    if (K.upload({lo, hi}, np)) return 1;
+    hipLaunchKernelGGL(k_q_integrate, dim3((unsigned)((S.n_tot + 127) / 128)), dim3(128), 0, st, K.probs, (int)B, S.n_tot, K.coef,
+                       (const double *)K.d_in[0], (const double *)K.d_in[1], K.gx, K.gw, (int)degree, K.d[0]);
+    MLMC_HIP_CHECK(hipGetLastError());
+    MLMC_HIP_CHECK(hipMemcpyAsync(out, K.d[0], sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+enum QMode { Q_CDF, Q_QUANTILES, Q_TAILS };
+
+// mlmc_density_cdf_batch (Q_CDF), mlmc_density_quantiles_batch (Q_QUANTILES) and mlmc_density_tail_means_batch (Q_TAILS: `out`
+// receives the quantiles, lower_out / upper_out the tail means at them, mean_out the problems' means; all NULL otherwise)
+static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                     const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind, double *lower_out = nullptr,
+                     double *upper_out = nullptr, double *mean_out = nullptr) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b || !n) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    QSetup S;
+    if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
+    const bool tails = mode == Q_TAILS;
+    if (S.n_tot > 0 && (!x || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
+    if (S.n_tot == 0 && !mass_out && !mean_out) return 0;
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    hipStream_t st = rt().stream;
+    const bool stage = mem_kind == MLMC_HOST && S.n_tot > 0;
+    const size_t rows = tails ? Q_TAIL_ROWS : 1;                             // table rows per problem
+    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * rows * ((size_t)nint + 1))));
+    const int64_t plane = (int64_t)G * (nint + 1);
+    const size_t np = stage ? (size_t)S.n_tot : 0, nm = (size_t)B * (tails ? 2 : 1);      // staged points; masses, then means
+    QBlock K;
+    if (q_stage(S, deg, {np}, {nm, rows * (size_t)plane, np, tails ? np : 0, tails ? np : 0}, {nm}, K)) return 1;
+    if (K.upload({x}, np)) return 1;
+    double *d_mass = K.d[0], *d_mean = d_mass + B, *d_tab = K.d[1];
+    const double *d_x = stage ? K.d_in[0] : x;
+    double *d_out = stage ? K.d[2] : out, *d_lower = stage ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
+    const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
+    const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
+    QTiming &tm = q_timing();
+    size_t timed = 0;
+    for (int g0 = 0; g0 < B; g0 += G) {
+        const int np_g = std::min(G, B - g0);
+        const int64_t n_cells = (int64_t)np_g * nint;
+        hipLaunchKernelGGL(cells, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx, K.gw, deg,
+                           d_tab, plane);
+        hipLaunchKernelGGL(prefix, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0, d_mass + g0,
+                           d_mean + g0);
+        const int64_t pt0 = S.probs[g0].x_off;
+        const int64_t npts = (g0 + np_g < B ? S.probs[g0 + np_g].x_off : S.n_tot) - pt0;
+        if (npts > 0) {
+            const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));
+            hipEvent_t e0, e1;
+            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts, K.coef,
+                               (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
+            if (tails)                           // the quantiles, as k_q_quantile has just written them, are the points
+                hipLaunchKernelGGL(k_q_tails, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts, K.coef, (const double *)d_tab,
+                                   plane, K.gx, K.gw, deg, (const double *)d_out, d_lower, d_upper);
+            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+        }
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
+    if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    if (stage && tails) {
+        MLMC_HIP_CHECK(hipMemcpyAsync(lower_out, d_lower, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+        MLMC_HIP_CHECK(hipMemcpyAsync(upper_out, d_upper, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    }
+    if (mass_out || mean_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * nm, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * B);
+    if (mean_out) std::memcpy(mean_out, K.h[0] + B, sizeof(double) * B);
+    for (size_t k = 0; k < timed; ++k) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
+        tm.ms += ms;
+        ++tm.launches;
+    }
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+}  // namespace mlmc
+
+using namespace mlmc;
+
+extern "C" {
+
+int mlmc_density_eval(const mlmc_basis *b, const double *lambda, const double *sigma, int32_t R1, const double *x, int64_t n,
+                      double *out, int mem_kind) {
+    MLMC_API_GUARD;
+    if (!b) return fail("mlmc_density_eval: null argument");
+    return q_eval("mlmc_density_eval", true, 1, &b, &R1, lambda, sigma, x, &n, out, mem_kind);
+}
+
+int mlmc_density_eval_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                            const double *x, const int64_t *n, double *out) {
+    MLMC_API_GUARD;
+    return q_eval("mlmc_density_eval_batch", false, B, bases, R1, lambda, sigma, x, n, out, MLMC_HOST);
+}
+
+int mlmc_density_integrate(const mlmc_basis *b, const double *lambda, const double *sigma, int32_t R1, const double *lo,
+                           const double *hi, int64_t n, int32_t degree, double *out) {
+    MLMC_API_GUARD;
+    if (!b) return fail("mlmc_density_integrate: null argument");
+    return q_integrate("mlmc_density_integrate", true, 1, &b, &R1, lambda, sigma, lo, hi, &n, degree, out);
+}
+
+int mlmc_density_integrate_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *lo, const double *hi, const int64_t *n, int32_t degree,
+                                 double *out) {
+    MLMC_API_GUARD;
+    return q_integrate("mlmc_density_integrate_batch", false, B, bases, R1, lambda, sigma, lo, hi, n, degree, out);
+}
+
+int mlmc_density_cdf_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                           const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *x,
+                           const int64_t *n, double *out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_cdf_batch", Q_CDF, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, x, n, out, mass_out,
+                     mem_kind);
+}
+
+int mlmc_density_quantiles_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                 const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                 const double *p, const int64_t *n, double *out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_quantiles_batch", Q_QUANTILES, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, out,
+                     mass_out, mem_kind);
+}
+
+int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                  const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                  const double *p, const int64_t *n, double *q_out, double *lower_out, double *upper_out, double *mass_out,
+                                  double *mean_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_on_rule("mlmc_density_tail_means_batch", Q_TAILS, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, q_out,
+                     mass_out, mem_kind, lower_out, upper_out, mean_out);
+}
+
+int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches) {
+    MLMC_API_GUARD;
+    QTiming &tm = q_timing();
+    if (ms) *ms = tm.ms;
+    if (launches) *launches = tm.launches;
+    tm.ms = 0.0;
+    tm.launches = 0;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,86 @@
+// The max-entropy density on the device: the one place where its arithmetic is written (the kernels are in density.hip).
+//
+//     density(x) = exp(clip(-sum_r c_r Q_r(x), +-200)),   c = effective coefficients in the underlying (scaled) family
+//
+// A value outside the basis' domain (transform_value's keep flag) gives NaN.  Every sum has a fixed order, so a value depends
+// on (basis, c, x) alone: not on the kernel that asks for it, not on the batch.
+#pragma once
+#include <type_traits>
+
+#include "device_basis.hpp"
+
+namespace mlmc {
+
+// one density problem of a call
+struct QProb {
+    BasisParams bp;
+    int n_coef;
+    int64_t c_off;       // effective coefficients: coef + c_off, [n_coef]
+    int64_t x_off, n;    // the problem's points: [x_off, x_off + n) of the call's point arrays
+    double a, b;         // domain (0, 0 in the entries that take none: they do not read it)
+};
+
+// the run-time basis kind as a compile-time one: f(std::integral_constant<int, KIND>()), `decltype(K)::value` in a generic lambda
+template <class F>
+__device__ __forceinline__ auto with_kind(int kind, F &&f) {
+    switch (kind) {
+        case MLMC_LEGENDRE: return f(std::integral_constant<int, MLMC_LEGENDRE>());
+        case MLMC_MONOMIAL: return f(std::integral_constant<int, MLMC_MONOMIAL>());
+        case MLMC_FOURIER: return f(std::integral_constant<int, MLMC_FOURIER>());
+        default: return f(std::integral_constant<int, MLMC_SPLINE>());
+    }
+}
+
+// the chain of operations behind one density value: begin, term(r, c_r) for r = 0, 1, 2, ... in order, value
+template <int KIND>
+struct DensityChain {
+    TermGen<KIND> g;
+    double power;
+    bool keep;
+    __device__ __forceinline__ void begin(const BasisParams &bp, double x) {
+        const double t = transform_value(bp, x, keep);
+        g.init(keep ? t : 0.0, 1.0, bp);
+        power = 0.0;
+    }
+    __device__ __forceinline__ void term(int r, double cr) { power = __builtin_fma(g.next(r), cr, power); }
+    __device__ __forceinline__ double value() const {
+        return keep ? exp(fmin(fmax(-power, -200.0), 200.0)) : __builtin_nan("");
+    }
+};
+
+template <int KIND>
+__device__ __forceinline__ double density_value(const BasisParams &bp, const double *__restrict__ c, int R, double x) {
+    DensityChain<KIND> d;
+    d.begin(bp, x);
+    for (int r = 0; r < R; ++r) d.term(r, c[r]);
+    return d.value();
+}
+
+// density_value at two points at once: two chains interleaved term by term, so that one coefficient load serves both and one
+// chain's FMAs overlap the other's.  Each chain is density_value's, hence so are its bits.
+template <int KIND>
+__device__ __forceinline__ void density_value2(const BasisParams &bp, const double *__restrict__ c, int R, double x0, double x1,
+                                               double &d0, double &d1) {
+    DensityChain<KIND> c0, c1;
+    c0.begin(bp, x0);
+    c1.begin(bp, x1);
+    for (int r = 0; r < R; ++r) {
+        const double cr = c[r];
+        c0.term(r, cr);
+        c1.term(r, cr);
+    }
+    d0 = c0.value();
+    d1 = c1.value();
+}
+
+// integral of the density over [a, b] with a `deg`-point Gauss-Legendre rule (nodes / weights on [-1, 1])
+template <int KIND>
+__device__ __forceinline__ double density_integral(const BasisParams &bp, const double *__restrict__ c, int R, double a, double b,
+                                                   const double *__restrict__ nodes, const double *__restrict__ wts, int deg) {
+    const double half = 0.5 * (b - a), mid = 0.5 * (b + a);
+    double acc = 0.0;
+    for (int k = 0; k < deg; ++k) acc = __builtin_fma(wts[k], density_value<KIND>(bp, c, R, __builtin_fma(half, nodes[k], mid)), acc);
+    return acc * half;
+}
+
+}  // namespace mlmc

@@ -684,46 +684,6 @@ __global__ __launch_bounds__(COOP_THREADS) void k_me_coop(CoopArgs A) {
     }
 }
 
-// density(x) = exp(clip(-sum_r c_r Q_r(x), +-200)), c = effective coefficients in the underlying (scaled) family
-template <int KIND>
-__global__ void k_density(BasisParams bp, const double *__restrict__ c, int R,
-                          const double *__restrict__ x, int64_t n, double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    bool keep;
-    const double t = transform_value(bp, x[i], keep);
-    TermGen<KIND> g;
-    g.init(keep ? t : 0.0, 1.0, bp);
-    double power = 0.0;
-    for (int r = 0; r < R; ++r) power = __builtin_fma(g.next(r), c[r], power);
-    power = fmin(fmax(-power, -200.0), 200.0);
-    out[i] = keep ? exp(power) : __builtin_nan("");
-}
-
-// integral of the density over [lo_i, hi_i] with a `deg`-point Gauss-Legendre rule (nodes/weights on [-1, 1])
-template <int KIND>
-__global__ void k_density_integrate(BasisParams bp, const double *__restrict__ c, int R,
-                                    const double *__restrict__ lo, const double *__restrict__ hi, int64_t n,
-                                    const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
-                                    double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double a = lo[i], b = hi[i];
-    const double half = 0.5 * (b - a), mid = 0.5 * (b + a);
-    double acc = 0.0;
-    for (int k = 0; k < deg; ++k) {
-        bool keep;
-        const double t = transform_value(bp, __builtin_fma(half, nodes[k], mid), keep);
-        TermGen<KIND> g;
-        g.init(keep ? t : 0.0, 1.0, bp);
-        double power = 0.0;
-        for (int r = 0; r < R; ++r) power = __builtin_fma(g.next(r), c[r], power);
-        power = fmin(fmax(-power, -200.0), 200.0);
-        acc = __builtin_fma(wts[k], keep ? exp(power) : __builtin_nan(""), acc);
-    }
-    out[i] = acc * half;
-}
-
 // Gauss-Legendre nodes / weights on [-1, 1] (Newton on P_n, host, long double)
 void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w) {
     x.assign(n, 0.0);
@@ -766,13 +726,10 @@ std::vector<double> effective_coeffs(const mlmc_basis *b, const double *lambda, 
     return c;
 }
 
-// One device allocation per call, carved into 256-byte aligned sub-buffers.
+// The solver's device workspace, carved into 256-byte aligned sub-buffers.
 struct DevPool {
     char *base = nullptr;
     size_t used = 0, cap = 0;
-    bool owner = true;
-    ~DevPool() { if (base && owner) (void)hipFree(base); }
-    int reserve(size_t bytes) { MLMC_HIP_CHECK(hipMalloc((void **)&base, bytes)); cap = bytes; return 0; }
     // view of the process-wide workspace of the max-entropy solver (grow-only; solves are serialised on the stream)
     int reserve_shared(size_t bytes) {
         static char *g_base = nullptr;
@@ -787,7 +744,6 @@ struct DevPool {
         }
         base = g_base;
         cap = g_cap;
-        owner = false;
         return 0;
     }
     static size_t pad(size_t n_doubles) { return ((n_doubles * sizeof(double) + 255) / 256) * 256 + 256; }
@@ -1047,89 +1003,6 @@ int mlmc_maxent_solve(const mlmc_basis *b, const double *mu, const double *sigma
     info->moment0 = scal[1];
     info->n_quad = Q;
     info->reserved = 0;
-    return 0;
-}
-
-int mlmc_density_eval(const mlmc_basis *b, const double *lambda, const double *sigma, int32_t R1, const double *x, int64_t n,
-                      double *out, int mem_kind) {
-    MLMC_API_GUARD;
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (!b || !lambda || !sigma || (n > 0 && (!x || !out))) return fail("mlmc_density_eval: null argument");
-    const int max_out = b->out_size > 0 ? b->out_size : b->p.size;
-    if (R1 <= 0 || R1 > max_out) return fail("mlmc_density_eval: R1 out of range");
-    if (n == 0) return 0;
-    hipStream_t st = rt().stream;
-    const int R = b->p.size;
-    std::vector<double> c = effective_coeffs(b, lambda, sigma, R1);
-    const int Reff = b->out_size > 0 ? R : R1;
-    DevPool pool;
-    if (pool.reserve(DevPool::pad(R) + 2 * DevPool::pad((size_t)n))) return 1;
-    DevBuf d_c, d_x, d_o;
-    d_c.p = pool.take(R);
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_c.p, c.data(), sizeof(double) * R, hipMemcpyHostToDevice, st));
-    const double *xd = x;
-    double *od = out;
-    if (mem_kind == MLMC_HOST) {
-        d_x.p = pool.take((size_t)n);
-        d_o.p = pool.take((size_t)n);
-        MLMC_HIP_CHECK(hipMemcpyAsync(d_x.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-        xd = d_x.d();
-        od = d_o.d();
-    }
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    switch (b->p.kind) {
-        case MLMC_LEGENDRE: hipLaunchKernelGGL(k_density<MLMC_LEGENDRE>, grid, block, 0, st, b->p, d_c.d(), Reff, xd, n, od); break;
-        case MLMC_MONOMIAL: hipLaunchKernelGGL(k_density<MLMC_MONOMIAL>, grid, block, 0, st, b->p, d_c.d(), Reff, xd, n, od); break;
-        case MLMC_FOURIER: hipLaunchKernelGGL(k_density<MLMC_FOURIER>, grid, block, 0, st, b->p, d_c.d(), Reff, xd, n, od); break;
-        case MLMC_SPLINE: hipLaunchKernelGGL(k_density<MLMC_SPLINE>, grid, block, 0, st, b->p, d_c.d(), Reff, xd, n, od); break;
-        default: return fail("mlmc_density_eval: unsupported basis kind");
-    }
-    MLMC_HIP_CHECK(hipGetLastError());
-    if (mem_kind == MLMC_HOST) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_o.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(wait_stream(st));
-    return 0;
-}
-
-int mlmc_density_integrate(const mlmc_basis *b, const double *lambda, const double *sigma, int32_t R1, const double *lo,
-                           const double *hi, int64_t n, int32_t degree, double *out) {
-    MLMC_API_GUARD;
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (!b || !lambda || !sigma || (n > 0 && (!lo || !hi || !out))) return fail("mlmc_density_integrate: null argument");
-    const int max_out = b->out_size > 0 ? b->out_size : b->p.size;
-    if (R1 <= 0 || R1 > max_out) return fail("mlmc_density_integrate: R1 out of range");
-    if (degree <= 0 || degree > 64) return fail("mlmc_density_integrate: degree must be in 1..64");
-    if (n == 0) return 0;
-    hipStream_t st = rt().stream;
-    const int R = b->p.size;
-    std::vector<double> c = effective_coeffs(b, lambda, sigma, R1);
-    const int Reff = b->out_size > 0 ? R : R1;
-    std::vector<double> gx, gw;
-    gauss_legendre(degree, gx, gw);
-    DevPool pool;
-    if (pool.reserve(DevPool::pad(R) + 3 * DevPool::pad((size_t)n) + 2 * DevPool::pad(degree))) return 1;
-    DevBuf d_c, d_lo, d_hi, d_o, d_gx, d_gw;
-    d_c.p = pool.take(R);
-    d_lo.p = pool.take((size_t)n);
-    d_hi.p = pool.take((size_t)n);
-    d_o.p = pool.take((size_t)n);
-    d_gx.p = pool.take(degree);
-    d_gw.p = pool.take(degree);
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_c.p, c.data(), sizeof(double) * R, hipMemcpyHostToDevice, st));
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_lo.p, lo, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_hi.p, hi, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_gx.p, gx.data(), sizeof(double) * degree, hipMemcpyHostToDevice, st));
-    MLMC_HIP_CHECK(hipMemcpyAsync(d_gw.p, gw.data(), sizeof(double) * degree, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n + 127) / 128)), block(128);
-    switch (b->p.kind) {
-        case MLMC_LEGENDRE: hipLaunchKernelGGL(k_density_integrate<MLMC_LEGENDRE>, grid, block, 0, st, b->p, d_c.d(), Reff, d_lo.d(), d_hi.d(), n, d_gx.d(), d_gw.d(), degree, d_o.d()); break;
-        case MLMC_MONOMIAL: hipLaunchKernelGGL(k_density_integrate<MLMC_MONOMIAL>, grid, block, 0, st, b->p, d_c.d(), Reff, d_lo.d(), d_hi.d(), n, d_gx.d(), d_gw.d(), degree, d_o.d()); break;
-        case MLMC_FOURIER: hipLaunchKernelGGL(k_density_integrate<MLMC_FOURIER>, grid, block, 0, st, b->p, d_c.d(), Reff, d_lo.d(), d_hi.d(), n, d_gx.d(), d_gw.d(), degree, d_o.d()); break;
-        case MLMC_SPLINE: hipLaunchKernelGGL(k_density_integrate<MLMC_SPLINE>, grid, block, 0, st, b->p, d_c.d(), Reff, d_lo.d(), d_hi.d(), n, d_gx.d(), d_gw.d(), degree, d_o.d()); break;
-        default: return fail("mlmc_density_integrate: unsupported basis kind");
-    }
-    MLMC_HIP_CHECK(hipGetLastError());
-    MLMC_HIP_CHECK(hipMemcpyAsync(out, d_o.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(wait_stream(st));
     return 0;
 }
 

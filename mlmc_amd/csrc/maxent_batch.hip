@@ -450,43 +450,7 @@ __global__ __launch_bounds__(MEB_THREADS) void k_meb_solve(MebArgs A) {
     }
 }
 
-// density of many problems on their own points: grid (B, y-blocks), grid-stride over each problem's points
-struct MebDensity {
-    BasisParams bp;
-    int n_coef;
-    int64_t c_off, x_off, n;
-};
-
-template <int KIND>
-__device__ __forceinline__ double meb_density_value(const BasisParams &bp, const double *c, int R, double x) {
-    bool keep;
-    const double t = transform_value(bp, x, keep);
-    TermGen<KIND> g;
-    g.init(keep ? t : 0.0, 1.0, bp);
-    double power = 0.0;
-    for (int r = 0; r < R; ++r) power = __builtin_fma(g.next(r), c[r], power);
-    power = fmin(fmax(-power, -200.0), 200.0);
-    return keep ? exp(power) : __builtin_nan("");
-}
-
-__global__ __launch_bounds__(256) void k_meb_density(const MebDensity *__restrict__ probs, const double *__restrict__ coef,
-                                                     const double *__restrict__ x, double *__restrict__ out) {
-    const MebDensity P = probs[blockIdx.x];
-    const double *c = coef + P.c_off;
-    for (int64_t i = (int64_t)blockIdx.y * blockDim.x + threadIdx.x; i < P.n; i += (int64_t)gridDim.y * blockDim.x) {
-        const double v = x[P.x_off + i];
-        double d;
-        switch (P.bp.kind) {
-            case MLMC_LEGENDRE: d = meb_density_value<MLMC_LEGENDRE>(P.bp, c, P.n_coef, v); break;
-            case MLMC_MONOMIAL: d = meb_density_value<MLMC_MONOMIAL>(P.bp, c, P.n_coef, v); break;
-            case MLMC_FOURIER: d = meb_density_value<MLMC_FOURIER>(P.bp, c, P.n_coef, v); break;
-            default: d = meb_density_value<MLMC_SPLINE>(P.bp, c, P.n_coef, v); break;
-        }
-        out[P.x_off + i] = d;
-    }
-}
-
-// the workspace shared by the batched entry points (MebWorkspace: maxent_batch.hpp)
+// the workspace shared by the batched solver and the density entries (MebWorkspace: maxent_batch.hpp)
 MebWorkspace &meb_ws() {
     static MebWorkspace ws;
     return ws;
@@ -628,69 +592,6 @@ int mlmc_maxent_solve_batch(int32_t B, const mlmc_basis *const *bases, const int
         info[i].n_quad = Q;
         info[i].reserved = 0;
     }
-    ws.trim(MEB_KEEP_BYTES);
-    return 0;
-}
-
-int mlmc_density_eval_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
-                            const double *x, const int64_t *n, double *out) {
-    MLMC_API_GUARD;
-    static const char *fn = "mlmc_density_eval_batch";
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (B < 0) return fail("mlmc_density_eval_batch: B < 0");
-    if (B == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !n) return fail("mlmc_density_eval_batch: null argument");
-    int ldv = 0;
-    int64_t n_tot = 0, n_max = 0;
-    size_t n_coef = 0;
-    for (int i = 0; i < B; ++i) {
-        const mlmc_basis *bs = bases[i];
-        if (!bs) return meb_fail(fn, i, "null basis");
-        const int max_out = bs->out_size > 0 ? bs->out_size : bs->p.size;
-        if (R1[i] <= 0 || R1[i] > max_out) return meb_fail(fn, i, "R1 out of range");
-        if (bs->p.kind == MLMC_IDENTITY) return meb_fail(fn, i, "IDENTITY basis");
-        if (n[i] < 0) return meb_fail(fn, i, "n < 0");
-        ldv = std::max(ldv, (int)R1[i]);
-        n_tot += n[i];
-        n_max = std::max(n_max, (int64_t)n[i]);
-        n_coef += bs->out_size > 0 ? bs->p.size : R1[i];
-    }
-    if (n_tot == 0) return 0;
-    if (!x || !out) return fail("mlmc_density_eval_batch: null argument");
-    hipStream_t st = rt().stream;
-    std::vector<MebDensity> probs(B);
-    const size_t b_probs = meb_align(sizeof(MebDensity) * B), b_coef = meb_align(sizeof(double) * n_coef);
-    const size_t b_x = meb_align(sizeof(double) * (size_t)n_tot);
-    MebWorkspace &ws = meb_ws();
-    if (ws.reserve(b_probs + b_coef + 2 * b_x, b_probs + b_coef + b_x)) return 1;
-    char *h = ws.host, *d = ws.dev;
-    double *h_coef = (double *)(h + b_probs);
-    size_t c_off = 0;
-    int64_t x_off = 0;
-    for (int i = 0; i < B; ++i) {
-        const mlmc_basis *bs = bases[i];
-        // the same coefficients as mlmc_density_eval: one value per point is bit for bit the single entry's
-        std::vector<double> c = effective_coeffs(bs, lambda + (size_t)i * ldv, sigma + (size_t)i * ldv, R1[i]);
-        const int Reff = bs->out_size > 0 ? bs->p.size : R1[i];
-        std::memcpy(h_coef + c_off, c.data(), sizeof(double) * Reff);
-        probs[i].bp = bs->p;
-        probs[i].n_coef = Reff;
-        probs[i].c_off = (int64_t)c_off;
-        probs[i].x_off = x_off;
-        probs[i].n = n[i];
-        c_off += Reff;
-        x_off += n[i];
-    }
-    std::memcpy(h, probs.data(), sizeof(MebDensity) * B);
-    std::memcpy(h + b_probs + b_coef, x, sizeof(double) * (size_t)n_tot);
-    MLMC_HIP_CHECK(hipMemcpyAsync(d, h, b_probs + b_coef + b_x, hipMemcpyHostToDevice, st));
-    double *d_out = (double *)(d + b_probs + b_coef + b_x);
-    const unsigned gy = (unsigned)std::min<int64_t>((n_max + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_meb_density, dim3((unsigned)B, gy), dim3(256), 0, st, (const MebDensity *)d, (const double *)(d + b_probs),
-                       (const double *)(d + b_probs + b_coef), d_out);
-    MLMC_HIP_CHECK(hipGetLastError());
-    MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_tot, hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(wait_stream(st));
     ws.trim(MEB_KEEP_BYTES);
     return 0;
 }

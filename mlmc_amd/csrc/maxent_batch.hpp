@@ -1,4 +1,4 @@
-// Host-side helpers shared by the batched max-entropy entry points (maxent_batch.hip, quantile.hip).
+// Host-side helpers shared by the batched max-entropy solver (maxent_batch.hip) and the density entries (density.hip).
 #pragma once
 #include <string>
 
@@ -6,7 +6,7 @@
 
 namespace mlmc {
 
-// grow-only device workspace and pinned staging buffer of the batched entry points (calls are serialised by the API lock)
+// grow-only device workspace and pinned staging buffer of these entry points (calls are serialised by the API lock)
 struct MebWorkspace {
     char *dev = nullptr;
     size_t dev_cap = 0;
@@ -50,7 +50,7 @@ struct MebWorkspace {
     }
 };
 constexpr size_t MEB_KEEP_BYTES = (size_t)256 << 20;
-MebWorkspace &meb_ws();   // maxent_batch.hip: one workspace for all batched entry points
+MebWorkspace &meb_ws();   // maxent_batch.hip: one workspace for all of them
 
 inline size_t meb_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
 

@@ -14,7 +14,7 @@ from tests import maxent_exact as mx
 LD = np.longdouble
 U = 2.0 ** -53
 RULES = ((64, 21), (200, 21))
-MAX_IT = 64                                     # iteration cap of the bracketed Newton iteration (quantile.hip)
+MAX_IT = 64                                     # iteration cap of the bracketed Newton iteration (density.hip)
 
 GRID_INNER = np.linspace(0.001, 0.999, 201)
 GRID = np.concatenate([[1e-12, 1e-6], GRID_INNER, [1 - 1e-6, 1 - 1e-12]])

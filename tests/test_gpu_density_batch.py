@@ -242,6 +242,134 @@ def test_batch_argument_errors(hip):
     assert sd.estimate_densities_minimize([]) == []
 
 
+def test_density_entries_share_one_workspace(hip):
+    """The single entries (mlmc_density_eval, mlmc_density_integrate) use the workspace of the batched ones: whatever ran before,
+    at whatever size, leaves nothing behind that a later call sees.  The smallest and the largest R1 of tests/maxent_cases.py
+    (R1 = 1 and 128, plain Legendre) and the largest transformed basis (R1 = 41, orthogonalised Legendre); n = 1 and n = 257 points (grid points, both ends, points
+    outside, NaN, +-inf), 257 intervals, probabilities (0.05, 0.5, 0.95).  eval with host x, eval with device x (out prefilled
+    with a sentinel), eval_batch, integrate, integrate_batch, quantiles_batch and tail_means_batch, each followed by its own
+    n = 0 call, run in that order and in the reverse order: every output has the same bits in both, and a device `out` is
+    untouched beyond n."""
+    import torch
+    from mlmc_amd.tool import simple_distribution as sd
+    from mlmc_amd import Legendre, TransformedMoments
+    from tests import maxent_cases as mc
+
+    class _D:
+        n_intervals, _gauss_degree = 64, 21
+    by_r1 = sorted(mc.cases().values(), key=lambda c: c.R1)
+    picked = [by_r1[0], by_r1[-1], [c for c in by_r1 if c.desc.matrix is not None][-1]]
+    assert [c.R1 for c in picked[:2]] == [1, 128] and picked[2].R1 == 41
+    distrs = []
+    for c in picked:
+        d = _D()
+        base = Legendre(c.desc.size, c.domain)
+        d.moments_fn = base if c.desc.matrix is None else TransformedMoments(base, c.desc.matrix)
+        d.multipliers, d._moment_errs, d.domain = mc.perturbed(c.lam0), c.sigma, c.domain
+        distrs.append(d)
+    probs = np.array([0.05, 0.5, 0.95])
+    SENTINEL, PAD = 7.25, 64
+
+    def eval_device(d, x):
+        xd = torch.as_tensor(np.ascontiguousarray(x), device="cuda")
+        od = torch.full((x.size + PAD,), SENTINEL, dtype=torch.float64, device="cuda")
+        lam, sig = np.ascontiguousarray(d.multipliers), np.ascontiguousarray(d._moment_errs[:len(d.multipliers)])
+        torch.cuda.synchronize()
+        hip.check(hip.lib().mlmc_density_eval(d.moments_fn._basis_handle(), hip.ptr(lam), hip.ptr(sig), len(lam),
+                                              hip.ptr(xd) if x.size else None, x.size, hip.ptr(od), hip.DEVICE))
+        hip.check(hip.lib().mlmc_synchronize())
+        got = od.cpu().numpy()
+        assert np.all(got[x.size:] == SENTINEL)
+        return got[:x.size]
+
+    def integrate_batch(ivs):
+        lo, hi = (np.ascontiguousarray(np.concatenate([v[k] for v in ivs])) for k in (0, 1))
+        n, out = np.array([v[0].size for v in ivs], dtype=np.int64), np.empty_like(lo)
+        handles, r1, lam, sig = sd._batch_problem_args(distrs)
+        hip.check(hip.lib().mlmc_density_integrate_batch(len(distrs), C.cast(handles, C.c_void_p), hip.ptr(r1), hip.ptr(lam), hip.ptr(sig),
+                                                         hip.ptr(lo), hip.ptr(hi), hip.ptr(n), 21, hip.ptr(out)))
+        return np.split(out, np.cumsum(n)[:-1])
+
+    def entries(n):
+        """name -> call(empty): the entry on n points / intervals per problem, or on none"""
+        xs = [mc.density_points(d.domain)[-n:] for d in distrs]
+        iv = [tuple(v[:n] for v in mc.integrate_intervals(d.domain)) for d in distrs]
+        cut = lambda arrs, empty: [a[:0] if empty else a for a in arrs]
+        return {
+            "eval host": lambda e: [sd._device_density(d.moments_fn, d.multipliers, d._moment_errs, x) for d, x in zip(distrs, cut(xs, e))],
+            "eval device": lambda e: [eval_device(d, x) for d, x in zip(distrs, cut(xs, e))],
+            "eval_batch": lambda e: sd.densities(distrs, cut(xs, e)),
+            "integrate": lambda e: [sd._device_integrals(d.moments_fn, d.multipliers, d._moment_errs, *cut(v, e), 21) for d, v in zip(distrs, iv)],
+            "integrate_batch": lambda e: integrate_batch([cut(v, e) for v in iv]),
+            "quantiles_batch": lambda e: sd.quantiles(distrs, cut([probs] * 3, e)),
+            "tail_means_batch": lambda e: [v for part in sd.tail_means(distrs, cut([probs] * 3, e)) for v in part],
+        }
+
+    def run(order):
+        out = {}
+        for n in order[0]:
+            calls = entries(n)
+            for name in (list(calls) if order[1] else list(calls)[::-1]):
+                out[(name, n)] = calls[name](False)
+                for v in calls[name](True)[:3]:
+                    assert np.size(v) == 0, name
+        return out
+    first, second = run(((1, 257), True)), run(((257, 1), False))
+    assert set(first) == set(second) and len(first) == 14
+    for key, vals in first.items():
+        assert len(vals) == len(second[key]) >= 3, key
+        for a, b in zip(vals, second[key]):
+            assert np.array_equal(a, b, equal_nan=True), key
+    assert np.isnan(first[("eval host", 257)][0]).sum() >= 5 and np.isfinite(first[("eval host", 257)][0]).sum() >= 200
+    for single, others in (("eval host", ("eval device", "eval_batch")), ("integrate", ("integrate_batch",))):
+        for key in others:
+            for a, b in zip(first[(single, 257)], first[(key, 257)]):
+                assert a.size == 257 and np.array_equal(a, b, equal_nan=True), key
+
+
+def test_host_points_beyond_the_direct_copy_threshold(hip):
+    """Host point arrays of more than 1 MiB per call (Q_DIRECT_BYTES, density.hip) go to the device straight from the caller's
+    memory instead of through the pinned block.  140 001 points (1.07 MiB) of a plain and a transformed basis: eval, eval_batch,
+    integrate and quantiles on the whole array give the bits of the same entries on chunks of 50 000 (below the threshold), and
+    eval those of device-resident points."""
+    import torch
+    from mlmc_amd import Legendre, TransformedMoments
+    from mlmc_amd.tool import simple_distribution as sd
+    from tests import maxent_cases as mc
+
+    class _D:
+        n_intervals, _gauss_degree = 64, 21
+    N, CHUNK = 140001, 50000
+    assert 8 * CHUNK < (1 << 20) < 8 * N
+    distrs = []
+    for name in ("mix_R26", "norm12_R21"):
+        c, d = mc.cases()[name], _D()
+        base = Legendre(c.desc.size, c.domain)
+        d.moments_fn = base if c.desc.matrix is None else TransformedMoments(base, c.desc.matrix)
+        d.multipliers, d._moment_errs, d.domain = mc.perturbed(c.lam0), c.sigma, c.domain
+        distrs.append(d)
+    chunks = lambda f, *arrs: np.concatenate([f(*[a[k:k + CHUNK] for a in arrs]) for k in range(0, N, CHUNK)])
+    xs = [np.linspace(d.domain[0], d.domain[1], N) for d in distrs]
+    probs = np.linspace(0.0, 1.0, N)
+    for d, x, whole in zip(distrs, xs, sd.densities(distrs, xs)):
+        dens = lambda v: sd._device_density(d.moments_fn, d.multipliers, d._moment_errs, v)
+        want = chunks(dens, x)
+        assert np.all(np.isfinite(want)) and np.array_equal(dens(x), want) and np.array_equal(whole, want)
+        assert np.array_equal(sd.densities([d], [x])[0], want)
+        xd = torch.as_tensor(x, device="cuda")
+        od = torch.empty_like(xd)
+        lam, sig = np.ascontiguousarray(d.multipliers), np.ascontiguousarray(d._moment_errs[:len(d.multipliers)])
+        torch.cuda.synchronize()
+        hip.check(hip.lib().mlmc_density_eval(d.moments_fn._basis_handle(), hip.ptr(lam), hip.ptr(sig), len(lam), hip.ptr(xd), N,
+                                              hip.ptr(od), hip.DEVICE))
+        hip.check(hip.lib().mlmc_synchronize())
+        assert np.array_equal(od.cpu().numpy(), want)
+        integ = lambda lo, hi: sd._device_integrals(d.moments_fn, d.multipliers, d._moment_errs, lo, hi, 21)
+        lo = np.full(N, d.domain[0])
+        assert np.array_equal(integ(lo, x), chunks(integ, lo, x))
+        assert np.array_equal(sd.quantiles([d], [probs])[0], chunks(lambda p: sd.quantiles([d], [p])[0], probs))
+
+
 # ---- Estimate.construct_densities -----------------------------------------------------------------------------------
 M_TIMES, M_ARR = 2, 3          # result format: times [1, 2], one location, array (3, 1) -> M = 6 components
 LOG_COMP = 4

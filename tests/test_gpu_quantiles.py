@@ -1,4 +1,4 @@
-"""GPU tests of the batched CDFs and quantiles of the max-entropy densities (mlmc_amd/csrc/quantile.hip) through the public
+"""GPU tests of the batched CDFs and quantiles of the max-entropy densities (mlmc_amd/csrc/density.hip) through the public
 entries: simple_distribution.quantiles / cdfs_on_rule / cdfs, SimpleDistribution.quantile, Distribution.quantile,
 Estimate.estimate_component_quantiles and the three C entries.
 

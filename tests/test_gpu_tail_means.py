@@ -1,5 +1,5 @@
-"""GPU tests of the batched tail means (expected shortfall) of the max-entropy densities (k_q_tail_cells, k_q_tail_prefix, k_q_tails
-in mlmc_amd/csrc/quantile.hip) through the public entries: simple_distribution.tail_means, SimpleDistribution / Distribution
+"""GPU tests of the batched tail means (expected shortfall) of the max-entropy densities (k_q_cells<true>, k_q_prefix<true>, k_q_tails
+in mlmc_amd/csrc/density.hip) through the public entries: simple_distribution.tail_means, SimpleDistribution / Distribution
 .expected_shortfall, Estimate.estimate_component_shortfall / bootstrap_component_shortfall and mlmc_density_tail_means_batch.
 
 lower(x) and upper(x) (include/mlmc_hip.h) are finite sums; tests/tail_cases.py evaluates them in 80-bit long double AT THE

@@ -25,7 +25,10 @@ on the same M in {16, 256, 1024} solved densities at 3 and 99 probabilities:
 and on B = 1, R1 = 25, n = 10^6 device-resident probabilities (--config B,R1,n with --tails: that configuration alone):
   tails_kernel_ms / quantile_kernel_ms   HIP-event time of the point kernels of one call (mlmc_density_quantiles_kernel_time)
   tails_call_ms / quantile_call_ms       wall time of the C entry
-Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n] [--tails] [--reps K]"""
+--single: the single entries through the C ABI on one solved density of R1 = 25, wall ms of one call up to and including its own wait:
+  eval_host_ms / eval_device_ms   mlmc_density_eval at n = 10^3, 10^6, 10^7 host points / n = 10^6 device-resident points
+  integrate_ms                    mlmc_density_integrate at n = 10^3, 10^6 host intervals, degree 21
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -202,16 +205,41 @@ def tails_many_points(B, R1, n, reps):
                 quantile_call_ms=round(wall[1], 3), ordered=ordered, all_success=ok)
 
 
+def single_entries(reps):
+    distrs, ok = mixtures(1, 25, seed=5)
+    d = distrs[0]
+    lam = np.ascontiguousarray(d.multipliers, dtype=np.float64)
+    sig = np.ascontiguousarray(d._moment_errs[:len(lam)], dtype=np.float64)
+    handle, lib, P = d.moments_fn._basis_handle(), _lib.lib(), _lib.ptr
+    x = np.random.default_rng(3).uniform(DOM[0], DOM[1], 10_000_000)
+    lo, out = np.full(1_000_000, DOM[0]), np.empty_like(x)
+    xd = torch.as_tensor(x[:1_000_000], device="cuda")
+    od = torch.empty_like(xd)
+    torch.cuda.synchronize()
+    ev = lambda xs, os, n, kind: lambda: _lib.check(lib.mlmc_density_eval(handle, P(lam), P(sig), len(lam), P(xs), n, P(os), kind))
+    ig = lambda n: lambda: _lib.check(lib.mlmc_density_integrate(handle, P(lam), P(sig), len(lam), P(lo), P(x), n, 21, P(out)))
+    res = dict(R1=len(lam), all_success=ok, eval_host_ms={}, eval_device_ms={}, integrate_ms={})
+    for n in (1_000, 1_000_000, 10_000_000):
+        res["eval_host_ms"][n] = round(timed(ev(x, out, n, _lib.HOST), reps)[0], 4)
+    res["eval_device_ms"][1_000_000] = round(timed(ev(xd, od, 1_000_000, _lib.DEVICE), reps)[0], 4)
+    for n in (1_000, 1_000_000):
+        res["integrate_ms"][n] = round(timed(ig(n), reps)[0], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--config", help="one many-points configuration B,R1,n for a profiler run")
     ap.add_argument("--tails", action="store_true", help="tail_means against quantiles (DESIGN.md section 3.5.9)")
+    ap.add_argument("--single", action="store_true", help="the single entries mlmc_density_eval / mlmc_density_integrate")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
-    if a.tails:
+    if a.single:
+        out["single"] = single_entries(a.reps)
+    elif a.tails:
         cfg = tuple(int(v) for v in a.config.split(",")) if a.config else (1, 25, 1_000_000)
         if not a.config:
             Ms = (16,) if a.quick else (16, 256, 1024)
