@@ -39,7 +39,7 @@ extern "C" {
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
-                              *    mlmc_density_tail_means_batch */
+                              *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -358,6 +358,38 @@ int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, con
                                   const double *sigma, const double *a, const double *b, int32_t n_intervals,
                                   int32_t gauss_degree, const double *p, const int64_t *n, double *q_out, double *lower_out,
                                   double *upper_out, double *mass_out, double *mean_out, int mem_kind);
+/* Divergences between pairs of the B problems in one call -- added within 8.  Problems as in mlmc_density_cdf_batch (basis, R1,
+ * lambda, sigma, domain [a[i], b[i]]).  Pair k compares problem first[k], the prior p, with problem second[k], the posterior q (the
+ * roles of KL_divergence(prior_density, posterior_density, a, b), simple_distribution.py:443-464) on [lo[k], hi[k]]; a problem may
+ * appear in any number of pairs.  lo == hi == NULL: the intersection [max(a_p, a_q), min(b_p, b_q)] of the two domains.  The rule
+ * (n_intervals, gauss_degree; 0 = 64 and 21) has the cell edges e_j = lo + j h (fp64, h = (hi - lo) / n_intervals, e_n = hi) and
+ * on every cell the nodes t and weights w of mlmc_density_integrate.  At a node let e_p, e_q be the clipped exponents
+ * clip(-sum_r c_r Q_r(t), +-200) of the two problems, rho_p = exp(e_p), rho_q = exp(e_q) (bit for bit the values of
+ * mlmc_density_eval), d = e_q - e_p, x = expm1(d), y = expm1(d / 2).  out[k][c] is the rule's sum of the integrand of column c: */
+enum {
+    MLMC_DIV_KL = 0,     /* rho_p (x - d)            int p log(p / q) - p + q: the positivity-preserving form, no log, no division */
+    MLMC_DIV_L2SQ = 1,   /* (rho_p rho_p) (x x)      int (q - p)^2 */
+    MLMC_DIV_TV = 2,     /* (rho_p / 2) |x|          1/2 int |q - p| */
+    MLMC_DIV_H2 = 3,     /* (rho_p / 2) (y y)        1/2 int (sqrt q - sqrt p)^2 */
+    MLMC_DIV_MASS_P = 4, /* rho_p                    mass of p on the interval */
+    MLMC_DIV_MASS_Q = 5, /* rho_q                    mass of q on the interval */
+    MLMC_DIV_COUNT = 6
+};
+/* The densities enter as they are, without normalisation; the two masses let the caller normalise.  Every integrand is formed
+ * from rho_p and d, so a pair of a problem with itself gives exactly 0 in the first four columns and equal masses.  Order of the
+ * sums: per cell one FMA per node in node order, then times half the cell width (the arithmetic of mlmc_density_integrate); the
+ * cells are added in cell order.  Hence with [lo, hi] = [a, b] of the prior MASS_P is bit for bit the mass_out of
+ * mlmc_density_cdf_batch for that problem and rule, and a pair's values depend neither on the batch nor on the pair's position
+ * nor on how often its problems are used.  A node outside the domain of either basis (density NaN), or NaN multipliers, make
+ * all six values of the pair NaN and are no error; oppositely clipped exponents (d > 354.89) overflow x x, and with it L2SQ, to
+ * inf, which is no error either.  first / second [P] host int32, lo / hi [P] host (both or neither NULL), out [P][6] host.  Errors
+ * of one problem name the problem as in mlmc_density_cdf_batch; errors of one pair name the pair (an index outside 0..B-1, lo or
+ * hi not finite or lo >= hi, an interval not inside both domains, an empty intersection); errors of the call as a whole name
+ * nothing.  B = 0 or P = 0 is a no-op.  One workgroup per pair, no atomics; one host wait. */
+int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                   const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                   int32_t gauss_degree, int64_t P, const int32_t *first, const int32_t *second, const double *lo,
+                                   const double *hi, double *out);
 /* HIP-event time (ms) and number of the point kernels (quantile and CDF kernels, without the table kernels and copies) that
  * mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch have launched since the last call of this
  * function; resets both.  A tail-means call counts its quantile kernel and its tail kernel together as one launch per group. */

@@ -24,6 +24,10 @@
 //   k_q_prefix<true> : P, V forwards and S, W backwards
 //   k_q_tails        : one thread per (problem, x): cell lookup of k_q_cdf, then the two partial-cell rules [e_j, x] and
 //                      [x, e_{j+1}] in ONE loop over the nodes, their two density evaluations interleaved term by term
+// Divergences between pairs of problems (mlmc_density_divergences_batch): the rule's sums of six integrands of the two densities.
+//   k_q_divergences  : one workgroup per pair; the effective coefficients of both problems go to LDS once (every lane reads the
+//                      same address: a broadcast), the threads stride over the cells, two Gauss nodes advance together through
+//                      the terms of p and then of q; cell sums to the pair's table row, six threads add one column each in cell order
 // One thread owns one point from start to end, every sum has a fixed order and every loop a constant bound: a result does not
 // depend on the batch, on the position of the problem in it or on the other points.  No atomics, no data-dependent launch.
 // A thread of the flat-index kernels finds its problem by a binary search of its point index in the problems' offsets, so that the
@@ -95,9 +99,8 @@ __device__ __forceinline__ void q_tail_sums(const BasisParams &bp, const double 
 }
 
 // cell edge j of the composite rule as an fp64 number: a + j h (two roundings, the file is compiled without contraction)
-__device__ __forceinline__ double q_edge(const QProb &P, double h, int nint, int j) {
-    return j >= nint ? P.b : P.a + (double)j * h;
-}
+__device__ __forceinline__ double q_edge(double a, double b, double h, int nint, int j) { return j >= nint ? b : a + (double)j * h; }
+__device__ __forceinline__ double q_edge(const QProb &P, double h, int nint, int j) { return q_edge(P.a, P.b, h, nint, j); }
 
 // the cell of a value: the largest j < n with e_j <= v
 __device__ __forceinline__ int q_cell_of(const QProb &P, double h, int nint, double v) {
@@ -309,6 +312,75 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_tails(const QProb *__restrict__
     }
     lower[idx] = lw;
     upper[idx] = up;
+}
+
+// one pair of a divergences call: problems `first` (p) and `second` (q) on [lo, hi]; three doubles wide, staged as such
+struct QPair {
+    double lo, hi;
+    int32_t first, second;
+};
+static_assert(sizeof(QPair) == 3 * sizeof(double), "QPair is staged as three doubles");
+
+constexpr int Q_DIV_THREADS = 256;                     // at most; a launch has as many waves as the rule has cells to fill
+
+// node (t, w) of a pair into the six sums, each one FMA: every integrand from rho_p and d = e_q - e_p alone
+__device__ __forceinline__ void q_div_node(double w, double ep, double rp, double eq, double rq, double (&acc)[MLMC_DIV_COUNT]) {
+    const double d = eq - ep, x = expm1(d), y = expm1(0.5 * d);
+    acc[MLMC_DIV_KL] = __builtin_fma(w, rp * (x - d), acc[MLMC_DIV_KL]);
+    acc[MLMC_DIV_L2SQ] = __builtin_fma(w, (rp * rp) * (x * x), acc[MLMC_DIV_L2SQ]);
+    acc[MLMC_DIV_TV] = __builtin_fma(w, (0.5 * rp) * fabs(x), acc[MLMC_DIV_TV]);
+    acc[MLMC_DIV_H2] = __builtin_fma(w, (0.5 * rp) * (y * y), acc[MLMC_DIV_H2]);
+    acc[MLMC_DIV_MASS_P] = __builtin_fma(w, rp, acc[MLMC_DIV_MASS_P]);
+    acc[MLMC_DIV_MASS_Q] = __builtin_fma(w, rq, acc[MLMC_DIV_MASS_Q]);
+}
+
+// nodes k .. k + N - 1 of a cell: N chains through the terms of p, then N through those of q (the two may be of different families)
+template <int N>
+__device__ __forceinline__ void q_div_nodes(const QProb &Pp, const double *__restrict__ cp, const QProb &Pq, const double *__restrict__ cq,
+                                            double half, double mid, const double *__restrict__ nodes, const double *__restrict__ wts, int k,
+                                            double (&acc)[MLMC_DIV_COUNT], bool &ok) {
+    double t[N], ep[N], rp[N], eq[N], rq[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[i] = __builtin_fma(half, nodes[k + i], mid);
+    with_kind(Pp.bp.kind, [&](auto K) { density_exponents<decltype(K)::value, N>(Pp.bp, cp, Pp.n_coef, t, ep, rp, ok); });
+    with_kind(Pq.bp.kind, [&](auto K) { density_exponents<decltype(K)::value, N>(Pq.bp, cq, Pq.n_coef, t, eq, rq, ok); });
+#pragma unroll
+    for (int i = 0; i < N; ++i) q_div_node(wts[k + i], ep[i], rp[i], eq[i], rq[i], acc);
+}
+
+// tab: row of pair g of the launch at tab + g * MLMC_DIV_COUNT * nint, column c of cell j at [c * nint + j]; LDS: the coefficients
+// of p, then those of q
+__global__ __launch_bounds__(Q_DIV_THREADS) void k_q_divergences(const QProb *__restrict__ probs, const QPair *__restrict__ pairs, int nint,
+                                                                 const double *__restrict__ coef, const double *__restrict__ nodes,
+                                                                 const double *__restrict__ wts, int deg, double *__restrict__ tab,
+                                                                 double *__restrict__ out) {
+    extern __shared__ double q_div_coef[];
+    const QPair pr = pairs[blockIdx.x];
+    const QProb Pp = probs[pr.first], Pq = probs[pr.second];
+    double *cp = q_div_coef, *cq = q_div_coef + Pp.n_coef;
+    for (int r = threadIdx.x; r < Pp.n_coef; r += blockDim.x) cp[r] = coef[Pp.c_off + r];
+    for (int r = threadIdx.x; r < Pq.n_coef; r += blockDim.x) cq[r] = coef[Pq.c_off + r];
+    __syncthreads();
+    double *row = tab + (int64_t)blockIdx.x * MLMC_DIV_COUNT * nint;
+    const double h = (pr.hi - pr.lo) / (double)nint;
+    for (int j = threadIdx.x; j < nint; j += blockDim.x) {
+        const double lo = q_edge(pr.lo, pr.hi, h, nint, j), hi = q_edge(pr.lo, pr.hi, h, nint, j + 1);
+        const double half = 0.5 * (hi - lo), mid = 0.5 * (hi + lo);              // density_integral's
+        double acc[MLMC_DIV_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool ok = true;
+        int k = 0;
+        for (; k + 1 < deg; k += 2) q_div_nodes<2>(Pp, cp, Pq, cq, half, mid, nodes, wts, k, acc, ok);
+        if (k < deg) q_div_nodes<1>(Pp, cp, Pq, cq, half, mid, nodes, wts, k, acc, ok);
+#pragma unroll
+        for (int c = 0; c < MLMC_DIV_COUNT; ++c) row[(int64_t)c * nint + j] = ok ? acc[c] * half : __builtin_nan("");
+    }
+    __syncthreads();
+    if (threadIdx.x < MLMC_DIV_COUNT) {
+        const double *col = row + (int64_t)threadIdx.x * nint;
+        double run = 0.0;
+        for (int j = 0; j < nint; ++j) run += col[j];
+        out[(int64_t)blockIdx.x * MLMC_DIV_COUNT + threadIdx.x] = run;
+    }
 }
 
 // HIP-event time of the point kernels (k_q_quantile / k_q_cdf; k_q_quantile + k_q_tails of a tail-means call as one), for
@@ -582,6 +654,63 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     return 0;
 }
 
+// mlmc_density_divergences_batch
+static int q_divergences(const char *fn, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                         const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int64_t P,
+                         const int32_t *first, const int32_t *second, const double *lo, const double *hi, double *out) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (P < 0) return fail(std::string(fn) + ": P < 0");
+    if (B == 0 || P == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b || !first || !second || !out) return fail(std::string(fn) + ": null argument");
+    if (!lo != !hi) return fail(std::string(fn) + ": lo and hi must both be given or both be NULL");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    QSetup S;
+    const std::vector<int64_t> no_points(B, 0);
+    if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, no_points.data(), S)) return 1;
+    const auto pair_fail = [fn](int64_t k, const std::string &what) {
+        return fail(std::string(fn) + ": pair " + std::to_string(k) + ": " + what);
+    };
+    std::vector<QPair> pairs((size_t)P);
+    int max_coef = 0;
+    for (int64_t k = 0; k < P; ++k) {
+        QPair &pr = pairs[(size_t)k];
+        pr.first = first[k];
+        pr.second = second[k];
+        if (pr.first < 0 || pr.first >= B || pr.second < 0 || pr.second >= B) return pair_fail(k, "problem index outside 0..B-1");
+        const QProb &p = S.probs[pr.first], &q = S.probs[pr.second];
+        const double in_lo = std::max(p.a, q.a), in_hi = std::min(p.b, q.b);
+        if (!lo && !(in_lo < in_hi)) return pair_fail(k, "the two domains do not intersect");
+        pr.lo = lo ? lo[k] : in_lo;
+        pr.hi = lo ? hi[k] : in_hi;
+        if (!(std::isfinite(pr.lo) && std::isfinite(pr.hi) && pr.lo < pr.hi)) return pair_fail(k, "the interval must be finite with lo < hi");
+        if (pr.lo < in_lo || pr.hi > in_hi) return pair_fail(k, "the interval is not inside both domains");
+        max_coef = std::max(max_coef, p.n_coef + q.n_coef);
+    }
+    const size_t lds = sizeof(double) * (size_t)max_coef;
+    if (lds > 65536) return fail(std::string(fn) + ": more than 8192 terms in the two bases of a pair");
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    const size_t row = (size_t)MLMC_DIV_COUNT * nint, n_out = (size_t)MLMC_DIV_COUNT * (size_t)P;
+    const int64_t G = (int64_t)std::min<size_t>((size_t)P, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * row)));
+    hipStream_t st = rt().stream;
+    QBlock K;
+    if (q_stage(S, deg, {3 * (size_t)P}, {n_out, row * (size_t)G}, {n_out}, K)) return 1;
+    if (K.upload({(const double *)pairs.data()}, 3 * (size_t)P)) return 1;
+    const unsigned threads = (unsigned)std::min(Q_DIV_THREADS, (nint + 63) / 64 * 64);
+    for (int64_t g0 = 0; g0 < P; g0 += G) {              // groups share the table, in stream order
+        const int64_t np_g = std::min(G, P - g0);
+        hipLaunchKernelGGL(k_q_divergences, dim3((unsigned)np_g), dim3(threads), lds, st, K.probs, (const QPair *)K.d_in[0] + g0, nint, K.coef,
+                           K.gx, K.gw, deg, K.d[1], K.d[0] + g0 * MLMC_DIV_COUNT);
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
+    MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], K.d[0], sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    std::memcpy(out, K.h[0], sizeof(double) * n_out);
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
 }  // namespace mlmc
 
 using namespace mlmc;
@@ -638,6 +767,15 @@ int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, con
     MLMC_API_GUARD;
     return q_on_rule("mlmc_density_tail_means_batch", Q_TAILS, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, q_out,
                      mass_out, mem_kind, lower_out, upper_out, mean_out);
+}
+
+int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                   const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                   int64_t P, const int32_t *first, const int32_t *second, const double *lo, const double *hi,
+                                   double *out) {
+    MLMC_API_GUARD;
+    return q_divergences("mlmc_density_divergences_batch", B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, P, first, second,
+                         lo, hi, out);
 }
 
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches) {

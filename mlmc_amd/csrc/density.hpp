@@ -43,9 +43,11 @@ struct DensityChain {
         power = 0.0;
     }
     __device__ __forceinline__ void term(int r, double cr) { power = __builtin_fma(g.next(r), cr, power); }
-    __device__ __forceinline__ double value() const {
-        return keep ? exp(fmin(fmax(-power, -200.0), 200.0)) : __builtin_nan("");
-    }
+    // the clipped exponent: what value() is the exp of
+    __device__ __forceinline__ double exponent() const { return fmin(fmax(-power, -200.0), 200.0); }
+    __device__ __forceinline__ double value() const { return keep ? exp(exponent()) : __builtin_nan(""); }
+    // inside the basis' domain, and the sum is a number (NaN coefficients pass the clip as -200)
+    __device__ __forceinline__ bool valid() const { return keep && power == power; }
 };
 
 template <int KIND>
@@ -71,6 +73,27 @@ __device__ __forceinline__ void density_value2(const BasisParams &bp, const doub
     }
     d0 = c0.value();
     d1 = c1.value();
+}
+
+// clipped exponents e and densities rho = exp(e) (the bits of density_value) at N points at once: density_value2's interleaving of
+// N chains; ok is cleared where a chain is not valid()
+template <int KIND, int N>
+__device__ __forceinline__ void density_exponents(const BasisParams &bp, const double *__restrict__ c, int R, const double (&x)[N],
+                                                  double (&e)[N], double (&rho)[N], bool &ok) {
+    DensityChain<KIND> ch[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) ch[i].begin(bp, x[i]);
+    for (int r = 0; r < R; ++r) {
+        const double cr = c[r];
+#pragma unroll
+        for (int i = 0; i < N; ++i) ch[i].term(r, cr);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        e[i] = ch[i].exponent();
+        rho[i] = ch[i].value();
+        ok = ok && ch[i].valid();
+    }
 }
 
 // integral of the density over [a, b] with a `deg`-point Gauss-Legendre rule (nodes / weights on [-1, 1])

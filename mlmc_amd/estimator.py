@@ -40,6 +40,29 @@ def quantile_bands(replicates, success, level):
     return lo, hi
 
 
+DivergenceSpread = collections.namedtuple("DivergenceSpread", "kl l2 tv hellinger upper success n_ok seed")
+
+
+def divergence_upper(measures, success, level):
+    """One-sided percentile of bootstrap divergence replicates (host arithmetic): measures = four [B, M] arrays (kl, l2, tv,
+    hellinger), success [B, M] bool -> upper [M, 4], the 100 level percentile (np.percentile) of each measure over component m's
+    successful replicates alone, in that column order; NaN for a component without a successful replicate.  One-sided because
+    the measures are non-negative: their spread has 0 as its natural lower end."""
+    stack = np.stack([np.asarray(v, dtype=np.float64) for v in measures], axis=-1)
+    success = np.asarray(success, dtype=bool)
+    if stack.ndim != 3 or stack.shape[2] != 4 or success.shape != stack.shape[:2]:
+        raise ValueError("divergence_upper: four measures [B, M] and success [B, M] expected, got shapes {} and {}".format(
+            stack.shape, success.shape))
+    level = _check_level("divergence_upper", level)
+    M = stack.shape[1]
+    upper = np.full((M, 4), np.nan)
+    for m in range(M):
+        rows = stack[success[:, m], m]
+        if rows.shape[0]:
+            upper[m] = np.percentile(rows, 100.0 * level, axis=0)
+    return upper
+
+
 def _check_level(what, level):
     if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < level < 1.0:
         raise ValueError("{}: level must be a number in (0, 1), got {!r}".format(what, level))
@@ -452,6 +475,24 @@ class Estimate:
         lo, hi = quantile_bands(replicates, success, level)
         return QuantileBands(es, lo, hi, replicates, success, np.sum(success, axis=0), seed)
 
+    def bootstrap_component_divergences(self, n_subsamples=100, sample_vector=None, seed=None, level=0.9, tol=1e-8, reg_param=0.0,
+                                        orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """How far the maximum-entropy density of every component itself moves under resampling of the stored samples: the
+        divergences (tool.simple_distribution.divergences) of every bootstrap replicate density (the posterior) from the
+        component's estimated density (the prior) on the component's domain, all B * M pairs in ONE device call.  Same arguments
+        and, for the same seed, the same replicate densities as bootstrap_component_quantiles.
+        :param level: 0 < level < 1, the percentile of `upper`
+        :return: DivergenceSpread(kl, l2, tv, hellinger [B, M], upper [M, 4] = divergence_upper((kl, l2, tv, hellinger), success,
+            level), success [B, M] the solver's verdict per replicate, n_ok [M], seed)"""
+        from .tool import simple_distribution
+        _, densities, distrs, success, seed, level = self._bootstrap_replicate_densities(
+            "bootstrap_component_divergences", None, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
+            moments_fns, densities)
+        B, M = success.shape
+        res = simple_distribution.divergences([densities[m][0] for _ in range(B) for m in range(M)], distrs)
+        measures = [np.asarray(v, dtype=np.float64).reshape(B, M) for v in (res.kl, res.l2, res.tv, res.hellinger)]
+        return DivergenceSpread(*measures, divergence_upper(measures, success, level), success, np.sum(success, axis=0), seed)
+
     def _bootstrap_replicate_densities(self, what, probs, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
                                        moments_fns, densities):
         """The part bootstrap_component_quantiles and bootstrap_component_shortfall share: argument checks, the densities of the
@@ -459,12 +500,13 @@ class Estimate:
         :return: (probs [P], densities, distrs [B * M] solved replicate distributions (replicate-major), success [B, M], seed, level)"""
         from .tool import simple_distribution
         level = _check_level(what, level)
-        try:
-            probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
-        except (TypeError, ValueError):
-            raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs))
-        if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):          # NaN fails both comparisons
-            raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs.tolist()))
+        if probs is not None:                                   # None: a caller without probabilities
+            try:
+                probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs))
+            if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):          # NaN fails both comparisons
+                raise ValueError("{}: probs must be numbers in [0, 1], got {!r}".format(what, probs.tolist()))
         if moments_fns is None and densities is not None:
             moments_fns = [d[3]._base for d in densities]
         fns, B, k, seed = self._component_bootstrap_args(what, n_subsamples, sample_vector, moments_fns, seed)

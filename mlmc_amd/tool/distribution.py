@@ -8,7 +8,7 @@ import numpy as np
 import scipy.integrate as integrate
 from scipy.optimize import OptimizeResult
 
-from .simple_distribution import _cdf, _device_density, _expected_shortfall, _quantile, _solve_on_device
+from .simple_distribution import _cdf, _device_density, _divergence, _expected_shortfall, _quantile, _solve_on_device
 
 
 class Distribution:
@@ -142,6 +142,11 @@ class Distribution:
         """Expected shortfall (CVaR) at level p of the stored multipliers on this distribution's quadrature: E[X | X >= Q(p)]
         for tail = "upper", E[X | X <= Q(p)] for "lower" (simple_distribution.tail_means with one distribution)."""
         return _expected_shortfall(self, p, tail)
+
+    def divergence(self, prior, interval=None):
+        """KL, L2, total-variation and Hellinger distance of the stored multipliers' density (the posterior) from `prior` on this
+        distribution's quadrature (simple_distribution.divergences with one pair).  :return: Divergences of floats"""
+        return _divergence(self, prior, interval)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

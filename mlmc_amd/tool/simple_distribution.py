@@ -7,6 +7,7 @@ kernels as well.  The reference's SciPy trust-ncg iterates and QUADPACK sub-inte
 (they are pinned by no reference test); the converged multipliers are, because the functional is
 strictly convex.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -315,6 +316,66 @@ def _quantile(dist, p):
     return res
 
 
+Divergences = collections.namedtuple("Divergences", "kl l2 tv hellinger mass_prior mass_posterior")
+
+
+def divergences(priors, posteriors, intervals=None):
+    """Distances between pairs of max-entropy densities through ONE device call (mlmc_density_divergences_batch): pair k compares
+    the prior p = priors[k] with the posterior q = posteriors[k] (the roles of `KL_divergence(prior_density, posterior_density, a,
+    b)`) on intervals[k] = (lo, hi), by default the intersection of the two domains.  On the distributions' common quadrature
+    (n_intervals cells of _gauss_degree points over the interval)
+        kl = int p log(p / q) - p + q,  l2 = sqrt(int (q - p)^2),  tv = 1/2 int |q - p|,  hellinger = sqrt(1/2 int (sqrt q - sqrt p)^2),
+    with the densities as they are (not normalised; mass_prior and mass_posterior are their integrals over the interval).  The
+    integrands are formed from p and the difference of the two exponents (include/mlmc_hip.h): no logarithm, no division, and a
+    density against itself gives exactly 0.  A value is bit for bit the same for a pair alone or in any batch; an object that
+    appears in many pairs is sent to the device once.  A density that is NaN on the interval gives NaN for the pair.
+    :param priors, posteriors: equally long sequences of SimpleDistribution / Distribution objects with multipliers
+    :param intervals: None, one (lo, hi) for all pairs, or one per pair; each inside both domains
+    :return: Divergences(kl, l2, tv, hellinger, mass_prior, mass_posterior) of [P] arrays"""
+    priors, posteriors = list(priors), list(posteriors)
+    P = len(priors)
+    if len(posteriors) != P:
+        raise ValueError("divergences: {} priors for {} posteriors".format(P, len(posteriors)))
+    if P == 0:
+        return Divergences(*(np.empty(0) for _ in range(6)))
+    index, distrs = {}, []
+    for d in priors + posteriors:
+        if id(d) not in index:
+            index[id(d)] = len(distrs)
+            distrs.append(d)
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError("divergences: every distribution must use the same quadrature")
+    first = np.array([index[id(d)] for d in priors], dtype=np.int32)
+    second = np.array([index[id(d)] for d in posteriors], dtype=np.int32)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    lo = hi = None                                                   # the library takes the intersections
+    if intervals is None:
+        empty = np.flatnonzero(~(np.maximum(a[first], a[second]) < np.minimum(b[first], b[second])))
+        if empty.size:
+            raise ValueError("divergences: pair {}: the two domains do not intersect".format(int(empty[0])))
+    else:
+        iv = np.asarray(intervals, dtype=np.float64)
+        if iv.shape not in ((2,), (P, 2)):
+            raise ValueError("divergences: intervals must be one (lo, hi) or one per pair, got shape {}".format(iv.shape))
+        iv = np.broadcast_to(iv, (P, 2))
+        lo, hi = np.ascontiguousarray(iv[:, 0]), np.ascontiguousarray(iv[:, 1])
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    out = np.empty((P, 6))
+    _lib.check(_lib.lib().mlmc_density_divergences_batch(len(distrs), C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam),
+                                                         _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()), int(degs.pop()),
+                                                         P, _lib.ptr(first), _lib.ptr(second), _lib.ptr(lo), _lib.ptr(hi),
+                                                         _lib.ptr(out)))
+    return Divergences(out[:, 0].copy(), np.sqrt(out[:, 1]), out[:, 2].copy(), np.sqrt(out[:, 3]), out[:, 4].copy(), out[:, 5].copy())
+
+
+def _divergence(dist, prior, interval):
+    """the P = 1 call of `divergences` with `dist` as the posterior: a Divergences of floats"""
+    return Divergences(*(float(v[0]) for v in divergences([prior], [dist], None if interval is None else [tuple(interval)])))
+
+
 def estimate_densities_minimize(distrs, tol=1e-5, reg_param=0.01):
     """SimpleDistribution.estimate_density_minimize of every distribution in `distrs`, solved in ONE batched device call
     (mlmc_maxent_solve_batch: one workgroup per problem).  Each distribution gets exactly what its own call would do:
@@ -463,6 +524,12 @@ class SimpleDistribution:
         E[X | X <= Q(p)] for "lower" (see `tail_means`, of which this is the call with one distribution, hence bit for bit its
         value).  p: as in `quantile`."""
         return _expected_shortfall(self, p, tail)
+
+    def divergence(self, prior, interval=None):
+        """KL, L2, total-variation and Hellinger distance of this density (the posterior) from `prior`, another distribution
+        object on the same quadrature, over `interval` (default: the intersection of the two domains): `divergences` with one
+        pair, hence bit for bit its values.  :return: Divergences of floats"""
+        return _divergence(self, prior, interval)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

@@ -28,7 +28,15 @@ and on B = 1, R1 = 25, n = 10^6 device-resident probabilities (--config B,R1,n w
 --single: the single entries through the C ABI on one solved density of R1 = 25, wall ms of one call up to and including its own wait:
   eval_host_ms / eval_device_ms   mlmc_density_eval at n = 10^3, 10^6, 10^7 host points / n = 10^6 device-resident points
   integrate_ms                    mlmc_density_integrate at n = 10^3, 10^6 host intervals, degree 21
-Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails] [--reps K]"""
+--divergences: simple_distribution.divergences at R1 = 25 on the 64 x 21 rule for P = 16 (16 x 1), 3600
+(300 x 12) and 19200 (300 x 64) pairs of n_rep solved replicate densities against n_comp solved priors, the three taking turns:
+  divergences_ms      wall time of the one call (problem table of n_comp + P distributions, one mlmc_density_divergences_batch)
+  host_sums_ms        (a) the best host alternative of the same definition: ONE simple_distribution.densities call for the
+                      n_comp + P distributions at the rule's nodes, then the six sums in NumPy (d from the logarithms)
+  quad_ms_scaled      (b) what the public API offers without the entry: KL_divergence and L2_distance with scipy.integrate.quad
+                      on d.density, TIMED ON 4 PAIRS AND SCALED to P
+  host_vs_entry / quad_vs_entry   largest difference between the alternatives' kl / l2 and the entry's, relative to the value
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails | --divergences] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -205,6 +213,40 @@ def tails_many_points(B, R1, n, reps):
                 quantile_call_ms=round(wall[1], 3), ordered=ordered, all_success=ok)
 
 
+def divergence_pairs(n_rep, n_comp, reps):
+    distrs, ok = mixtures(n_comp + n_rep * n_comp, 25)
+    priors = [distrs[m] for _ in range(n_rep) for m in range(n_comp)]
+    posteriors = distrs[n_comp:]
+    P = len(priors)
+    d0 = distrs[0]
+    pts, w = sd._composite_gauss(DOM, d0.n_intervals, d0._gauss_degree)
+    first = np.tile(np.arange(n_comp), n_rep)
+
+    def host_sums():
+        rho = np.array(sd.densities(distrs, pts))
+        rp, rq = rho[first], rho[n_comp:]
+        d = np.log(rq) - np.log(rp)
+        x = np.expm1(d)
+        return ((rp * (x - d)) @ w, np.sqrt((rp * rp * x * x) @ w), 0.5 * (rp * np.abs(x)) @ w,
+                np.sqrt(0.5 * (rp * np.expm1(0.5 * d) ** 2) @ w), rp @ w, rq @ w)
+    big = P > 4000                                                   # the host alternative holds 5 arrays of P x 1344 doubles
+    d_ms, h_ms = alternating([lambda: sd.divergences(priors, posteriors), host_sums], 1 if big else reps)
+    res, host = sd.divergences(priors, posteriors), host_sums()
+    rel = lambda got, want: float(np.max(np.abs(got - want) / np.abs(want)))
+    sub = range(0, P, max(1, P // 4))[:4]
+    t0 = time.perf_counter()
+    worst = 0.0
+    for k in sub:
+        p, q = priors[k], posteriors[k]
+        kl = sd.KL_divergence(lambda v: p.density(v)[0], lambda v: q.density(v)[0], DOM[0], DOM[1])
+        l2 = sd.L2_distance(lambda v: p.density(v)[0], lambda v: q.density(v)[0], DOM[0], DOM[1])
+        worst = max(worst, abs(kl - res.kl[k]) / res.kl[k], abs(l2 - res.l2[k]) / res.l2[k])
+    quad_ms = (time.perf_counter() - t0) * 1e3 / len(sub) * P
+    return dict(P=P, n_rep=n_rep, n_comp=n_comp, R1=25, rule=[d0.n_intervals, d0._gauss_degree], divergences_ms=round(d_ms, 3),
+                host_sums_ms=round(h_ms, 3), quad_ms_scaled=round(quad_ms, 1), quad_pairs=len(sub),
+                host_vs_entry=max(rel(host[0], res.kl), rel(host[1], res.l2)), quad_vs_entry=float(worst), all_success=ok)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -233,12 +275,16 @@ def main():
     ap.add_argument("--config", help="one many-points configuration B,R1,n for a profiler run")
     ap.add_argument("--tails", action="store_true", help="tail_means against quantiles (DESIGN.md section 3.5.9)")
     ap.add_argument("--single", action="store_true", help="the single entries mlmc_density_eval / mlmc_density_integrate")
+    ap.add_argument("--divergences", action="store_true", help="divergences against host sums and quad (DESIGN.md section 3.5.10)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.divergences:
+        shapes = ((16, 1),) if a.quick else ((16, 1), (300, 12), (300, 64))
+        out["divergences"] = [divergence_pairs(n_rep, n_comp, a.reps) for n_rep, n_comp in shapes]
     elif a.tails:
         cfg = tuple(int(v) for v in a.config.split(",")) if a.config else (1, 25, 1_000_000)
         if not a.config:
