@@ -39,7 +39,7 @@ extern "C" {
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
-                              *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch */
+                              *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -390,6 +390,30 @@ int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, co
                                    const double *sigma, const double *a, const double *b, int32_t n_intervals,
                                    int32_t gauss_degree, int64_t P, const int32_t *first, const int32_t *second, const double *lo,
                                    const double *hi, double *out);
+/* Expectations under the densities of B problems in one call -- added within 8: moments in a basis of the caller's choice, mass
+ * and entropy.  Problems and rule as in mlmc_density_cdf_batch (basis, R1, lambda / sigma [B][R1max], domain [a[i], b[i]],
+ * n_intervals, gauss_degree; 0 = 64 and 21).  Problem i has in addition a test basis test[i] of any of the four kinds, plain or
+ * with a matrix, with its own domain, transform, log and clip flags (unrelated to the density's basis), and a count K[i] of its
+ * outputs, 1 <= K[i] <= out_size (size for a plain basis).  Its underlying terms are S = size if it has a matrix, else K[i];
+ * S <= 512.  The rule: edges e_j = a + j h (fp64, h = (b - a) / n_intervals, e_n = b), per cell half = (e_{j+1} - e_j) / 2,
+ * mid = (e_{j+1} + e_j) / 2, nodes t_k = fma(half, g_k, mid) and weights w_k of mlmc_density_integrate.  At a node rho = exp(e)
+ * and the clipped exponent e = clip(-sum_r c_r Q_r(t), +-200) are those of mlmc_density_eval (bit for bit), and q_r(t), r < S,
+ * are the underlying terms of the test basis at its own transform of t (Legendre: the scaled monic polynomials, P_r = c_r q_r).
+ * For every column f in {q_0 .. q_{S-1}, 1, -e}
+ *     C_j[f] = (sum over k in node order of acc = fma(w_k, rho f, acc)) * half,     s[f] = sum over j in cell order of C_j[f],
+ * then on the host m_r = c_r s[q_r] and, for a basis with a matrix, psi_j = sum_r matrix[j][r] m_r in r order in plain fp64.
+ * out [B][Kmax] host, Kmax = max K[i]: the K[i] raw moments int psi_j rho of the density as it is (not normalised), zeros beyond
+ * K[i].  mass_out [B] host (may be NULL): the column 1, bit for bit the mass_out of mlmc_density_cdf_batch for the problem and
+ * rule.  entropy_out [B] host (may be NULL): the column -e, -int rho log rho with the clipped exponent; the differential entropy
+ * of the normalised density is entropy / T + log T.  A node where the density is outside its basis' domain, or NaN multipliers,
+ * make every output of the problem NaN; a node the test basis does not keep makes the problem's moments NaN and leaves mass and
+ * entropy alone; neither is an error.  Argument errors and no-ops as mlmc_density_cdf_batch; a null test basis, an IDENTITY test
+ * basis, K[i] out of range or S > 512 is an error that names the problem.  A problem's values depend neither on the batch nor on
+ * its position in it nor on the other problems' bases.  One workgroup per problem, no atomics; one host wait. */
+int mlmc_density_moments_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                               const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                               const mlmc_basis *const *test, const int32_t *K, double *out, double *mass_out,
+                               double *entropy_out);
 /* HIP-event time (ms) and number of the point kernels (quantile and CDF kernels, without the table kernels and copies) that
  * mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch have launched since the last call of this
  * function; resets both.  A tail-means call counts its quantile kernel and its tail kernel together as one launch per group. */

@@ -28,6 +28,10 @@
 //   k_q_divergences  : one workgroup per pair; the effective coefficients of both problems go to LDS once (every lane reads the
 //                      same address: a broadcast), the threads stride over the cells, two Gauss nodes advance together through
 //                      the terms of p and then of q; cell sums to the pair's table row, six threads add one column each in cell order
+// Expectations under a density (mlmc_density_moments_batch): the rule's sums of rho f for the terms f of a test basis, 1 and -e.
+//   k_q_moments      : one workgroup per problem; steps of whole cells, lane = node fills an LDS tile [node][column] with rho f,
+//                      thread = (cell, column) sums the nodes of a cell in node order, thread = column adds the cells in cell order
+//                      onto a sum that stays in its register; columns beyond the tile's width follow in further chunks
 // One thread owns one point from start to end, every sum has a fixed order and every loop a constant bound: a result does not
 // depend on the batch, on the position of the problem in it or on the other points.  No atomics, no data-dependent launch.
 // A thread of the flat-index kernels finds its problem by a binary search of its point index in the problems' offsets, so that the
@@ -383,6 +387,122 @@ __global__ __launch_bounds__(Q_DIV_THREADS) void k_q_divergences(const QProb *__
     }
 }
 
+// the test basis of one problem of a moments call; nine doubles wide, staged as such
+struct QTest {
+    BasisParams bp;
+    int32_t S;          // underlying terms q_0 .. q_{S-1}; the columns of the problem are these, then 1, then -e
+    int32_t reserved;
+};
+static_assert(sizeof(QTest) == 9 * sizeof(double), "QTest is staged as nine doubles");
+
+constexpr int Q_MOM_THREADS = 256;
+constexpr int Q_MOM_MAX_TERMS = 512;
+constexpr int Q_MOM_SUMS = (Q_MOM_MAX_TERMS + 2 + Q_MOM_THREADS - 1) / Q_MOM_THREADS;      // running column sums of a thread
+constexpr size_t Q_MOM_LDS_BYTES = 65536;
+
+// LDS of a moments launch, in doubles: coefficients [coef_cap] | tile [cps * deg][stride] | cell sums [cps][chunk].  A step takes
+// `cps` whole cells, wave w the cells w * cpw .. of the step (cpw = max(1, 64 / deg) cells, lane = node); the columns go through
+// the tile `chunk` at a time (stride = chunk | 1: odd, so that the lanes of a wave writing one column hit different banks)
+struct QMomLayout {
+    int coef_cap, cpw, cps, chunk, stride;
+};
+
+// Expectations under the density of one problem (mlmc_density_moments_batch): column sums of rho f over the rule.
+//   phase 1, thread = node : the density chain, then the test generator in term order; rho f into the tile
+//   phase 2a, thread = (cell, column) : C_j[f] = (sum_k fma(w_k, tile, acc)) * half in node order, into the cell sums
+//   phase 2b, thread = column : the cells of the step in cell order onto the running sum in the thread's register
+// The generator of a node stays in its thread's registers from one chunk of columns to the next.
+template <int TKIND>
+__device__ __forceinline__ void q_mom_problem(const QProb &P, const QTest &T, const double *__restrict__ c, double *__restrict__ tile,
+                                              double *__restrict__ cell_sums, int *__restrict__ flags, int nint,
+                                              const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                              const QMomLayout &L, double (&sum)[Q_MOM_SUMS]) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int cw = lane / deg, k = lane - cw * deg;                 // cell within the wave, node within the cell
+    const int cs = wave * L.cpw + cw;                               // cell within the step
+    const int n_col = T.S + 2;
+    const double h = (P.b - P.a) / (double)nint;
+    for (int j0 = 0; j0 < nint; j0 += L.cps) {
+        const int nc = min(L.cps, nint - j0);
+        const bool active = cw < L.cpw && cs < nc;
+        TermGen<TKIND> g;
+        double rho = 0.0, neg_e = 0.0;
+        if (active) {
+            const double lo = q_edge(P, h, nint, j0 + cs), hi = q_edge(P, h, nint, j0 + cs + 1);
+            const double half = 0.5 * (hi - lo), mid = 0.5 * (hi + lo);          // density_integral's
+            const double t = __builtin_fma(half, nodes[k], mid);
+            bool ok = true;
+            with_kind(P.bp.kind, [&](auto K) {
+                DensityChain<decltype(K)::value> ch;
+                ch.begin(P.bp, t);
+                for (int r = 0; r < P.n_coef; ++r) ch.term(r, c[r]);
+                rho = ch.value();
+                neg_e = -ch.exponent();
+                ok = ch.valid();
+            });
+            if (!ok) flags[0] = 1;
+            bool keep;
+            const double tt = transform_value(T.bp, t, keep);
+            if (!keep) flags[1] = 1;
+            g.init(keep ? tt : 0.0, 1.0, T.bp);
+        }
+        for (int c0 = 0; c0 < n_col; c0 += L.chunk) {
+            const int ncc = min(L.chunk, n_col - c0);
+            if (active) {
+                double *row = tile + (size_t)(cs * deg + k) * L.stride;
+                for (int i = 0; i < ncc; ++i) {
+                    const int r = c0 + i;
+                    row[i] = r < T.S ? rho * g.next(r) : (r == T.S ? rho : rho * neg_e);
+                }
+            }
+            __syncthreads();
+            for (int p = tid; p < nc * ncc; p += blockDim.x) {
+                const int cell = p / ncc, i = p - cell * ncc;
+                const double lo = q_edge(P, h, nint, j0 + cell), hi = q_edge(P, h, nint, j0 + cell + 1);
+                const double half = 0.5 * (hi - lo);
+                const double *col = tile + (size_t)cell * deg * L.stride + i;
+                double acc = 0.0;
+                for (int kk = 0; kk < deg; ++kk) acc = __builtin_fma(wts[kk], col[(size_t)kk * L.stride], acc);
+                cell_sums[cell * L.chunk + i] = acc * half;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < Q_MOM_SUMS; ++s) {
+                const int i = tid + s * Q_MOM_THREADS - c0;
+                if (i >= 0 && i < ncc)
+                    for (int cell = 0; cell < nc; ++cell) sum[s] += cell_sums[cell * L.chunk + i];
+            }
+            // the next writes of the cell sums come after the next barrier, those of the tile after the one above
+        }
+    }
+}
+
+// out: row of problem g of the launch at out + g * ldo: the sums of the columns q_0 .. q_{S-1}, 1, -e
+__global__ __launch_bounds__(Q_MOM_THREADS) void k_q_moments(const QProb *__restrict__ probs, const QTest *__restrict__ tests, int nint,
+                                                             const double *__restrict__ coef, const double *__restrict__ nodes,
+                                                             const double *__restrict__ wts, int deg, QMomLayout L, int ldo,
+                                                             double *__restrict__ out) {
+    extern __shared__ double q_mom_lds[];
+    __shared__ int flags[2];                 // a node where the density chain is not valid / that the test basis does not keep
+    const QProb P = probs[blockIdx.x];
+    const QTest T = tests[blockIdx.x];
+    double *c = q_mom_lds, *tile = c + L.coef_cap, *cell_sums = tile + (size_t)L.cps * deg * L.stride;
+    for (int r = threadIdx.x; r < P.n_coef; r += blockDim.x) c[r] = coef[P.c_off + r];
+    if (threadIdx.x < 2) flags[threadIdx.x] = 0;
+    __syncthreads();
+    double sum[Q_MOM_SUMS];
+#pragma unroll
+    for (int s = 0; s < Q_MOM_SUMS; ++s) sum[s] = 0.0;
+    with_kind(T.bp.kind, [&](auto K) { q_mom_problem<decltype(K)::value>(P, T, c, tile, cell_sums, flags, nint, nodes, wts, deg, L, sum); });
+    __syncthreads();
+    const bool bad_density = flags[0] != 0, bad_test = flags[1] != 0;
+#pragma unroll
+    for (int s = 0; s < Q_MOM_SUMS; ++s) {
+        const int col = threadIdx.x + s * Q_MOM_THREADS;
+        if (col < T.S + 2) out[(int64_t)blockIdx.x * ldo + col] = (bad_density || (bad_test && col < T.S)) ? __builtin_nan("") : sum[s];
+    }
+}
+
 // HIP-event time of the point kernels (k_q_quantile / k_q_cdf; k_q_quantile + k_q_tails of a tail-means call as one), for
 // mlmc_density_quantiles_kernel_time: one event pair per group of a call, read after the call's own wait
 struct QTiming {
@@ -711,6 +831,94 @@ static int q_divergences(const char *fn, int32_t B, const mlmc_basis *const *bas
     return 0;
 }
 
+// the LDS layout of a moments launch from the call's largest column count and coefficient count: as many whole cells per step as
+// the four waves can take (at most the rule's), the columns in as few chunks as leave room for them, never fewer than one cell.
+// No sum depends on it.
+static QMomLayout q_mom_layout(int n_col_max, int max_coef, int nint, int deg) {
+    QMomLayout L;
+    L.coef_cap = max_coef;
+    L.cpw = std::max(1, 64 / deg);
+    const int want = std::min(4 * L.cpw, nint);
+    const size_t room = Q_MOM_LDS_BYTES / sizeof(double) - (size_t)max_coef;
+    const auto cells = [&](int chunk) { return (int)(room / ((size_t)deg * (chunk | 1) + chunk)); };
+    L.chunk = n_col_max;
+    while (cells(L.chunk) < want && L.chunk > 16) L.chunk = (L.chunk + 1) / 2;
+    L.stride = L.chunk | 1;
+    L.cps = std::min(want, cells(L.chunk));
+    return L;
+}
+
+// mlmc_density_moments_batch
+static int q_moments(const char *fn, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                     const mlmc_basis *const *test, const int32_t *K, double *out, double *mass_out, double *entropy_out) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": B < 0");
+    if (B == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b || !test || !K || !out) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    QSetup S;
+    const std::vector<int64_t> no_points(B, 0);
+    if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, no_points.data(), S)) return 1;
+    std::vector<QTest> tests((size_t)B);
+    int k_max = 0, n_col_max = 0, max_coef = 0;
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *tb = test[i];
+        if (!tb) return meb_fail(fn, i, "null test basis");
+        if (tb->p.kind != MLMC_LEGENDRE && tb->p.kind != MLMC_MONOMIAL && tb->p.kind != MLMC_FOURIER && tb->p.kind != MLMC_SPLINE)
+            return meb_fail(fn, i, "unsupported test basis kind");
+        const int max_out = tb->out_size > 0 ? tb->out_size : tb->p.size;
+        if (K[i] < 1 || K[i] > max_out) return meb_fail(fn, i, "K out of range");
+        QTest &t = tests[(size_t)i];
+        t.bp = tb->p;
+        t.S = tb->out_size > 0 ? tb->p.size : K[i];
+        t.reserved = 0;
+        if (t.S > Q_MOM_MAX_TERMS) return meb_fail(fn, i, "more than 512 terms in the test basis");
+        k_max = std::max(k_max, (int)K[i]);
+        n_col_max = std::max(n_col_max, t.S + 2);
+        max_coef = std::max(max_coef, S.probs[(size_t)i].n_coef);
+    }
+    if (max_coef > 4096) return fail(std::string(fn) + ": more than 4096 terms in the basis of a density");
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    const QMomLayout L = q_mom_layout(n_col_max, max_coef, nint, deg);
+    const size_t lds = sizeof(double) * ((size_t)L.coef_cap + (size_t)L.cps * ((size_t)deg * L.stride + L.chunk));
+    if (L.cps < 1 || lds > Q_MOM_LDS_BYTES) return fail(std::string(fn) + ": internal error: the tile does not fit");
+    const size_t n_out = (size_t)B * n_col_max, n_test = (size_t)B * (sizeof(QTest) / sizeof(double));
+    hipStream_t st = rt().stream;
+    QBlock Kb;
+    if (q_stage(S, deg, {n_test}, {n_out}, {n_out}, Kb)) return 1;
+    if (Kb.upload({(const double *)tests.data()}, n_test)) return 1;
+    hipLaunchKernelGGL(k_q_moments, dim3((unsigned)B), dim3(Q_MOM_THREADS), lds, st, Kb.probs, (const QTest *)Kb.d_in[0], nint, Kb.coef, Kb.gx,
+                       Kb.gw, deg, L, n_col_max, Kb.d[0]);
+    MLMC_HIP_CHECK(hipGetLastError());
+    MLMC_HIP_CHECK(hipMemcpyAsync(Kb.h[0], Kb.d[0], sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    std::vector<double> m;
+    for (int i = 0; i < B; ++i) {
+        const mlmc_basis *tb = test[i];
+        const int terms = tests[(size_t)i].S;
+        const double *row = Kb.h[0] + (size_t)i * n_col_max;
+        double *o = out + (size_t)i * k_max;
+        m.resize((size_t)terms);
+        for (int r = 0; r < terms; ++r) m[(size_t)r] = tb->scale_c[(size_t)r] * row[r];
+        for (int j = 0; j < k_max; ++j) {
+            double v = 0.0;
+            if (j < K[i] && tb->out_size > 0) {
+                const double *mr = tb->matrix.data() + (size_t)j * tb->p.size;
+                for (int r = 0; r < terms; ++r) v += mr[r] * m[(size_t)r];         // in r order, plain fp64 (no contraction in this file)
+            } else if (j < K[i]) {
+                v = m[(size_t)j];
+            }
+            o[j] = v;
+        }
+        if (mass_out) mass_out[i] = row[terms];
+        if (entropy_out) entropy_out[i] = row[terms + 1];
+    }
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
 }  // namespace mlmc
 
 using namespace mlmc;
@@ -776,6 +984,14 @@ int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, co
     MLMC_API_GUARD;
     return q_divergences("mlmc_density_divergences_batch", B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, P, first, second,
                          lo, hi, out);
+}
+
+int mlmc_density_moments_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                               const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                               const mlmc_basis *const *test, const int32_t *K, double *out, double *mass_out, double *entropy_out) {
+    MLMC_API_GUARD;
+    return q_moments("mlmc_density_moments_batch", B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, test, K, out, mass_out,
+                     entropy_out);
 }
 
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches) {

@@ -493,6 +493,23 @@ class Estimate:
         measures = [np.asarray(v, dtype=np.float64).reshape(B, M) for v in (res.kl, res.l2, res.tv, res.hellinger)]
         return DivergenceSpread(*measures, divergence_upper(measures, success, level), success, np.sum(success, axis=0), seed)
 
+    def bootstrap_component_summaries(self, n_subsamples=100, sample_vector=None, seed=None, level=0.9, tol=1e-8, reg_param=0.0,
+                                      orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """Bootstrap confidence bands of estimate_component_summaries: bootstrap_component_quantiles with the statistics of every
+        replicate density (tool.simple_distribution.summaries) in place of its quantiles.  Same arguments and, for the same seed,
+        the same replicate densities.
+        :return: QuantileBands whose five columns are mean, var, skewness, kurtosis and entropy: q [M, 5] = the statistics of
+            estimate_component_summaries(densities=densities), lo, hi [M, 5] = quantile_bands(replicates, success, level),
+            replicates [B, M, 5]; success, n_ok, seed as in bootstrap_component_quantiles"""
+        from .tool import simple_distribution
+        _, densities, distrs, success, seed, level = self._bootstrap_replicate_densities(
+            "bootstrap_component_summaries", None, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
+            moments_fns, densities)
+        q = np.stack(self.estimate_component_summaries(densities=densities)[:5], axis=1)
+        replicates = np.stack(simple_distribution.summaries(distrs)[:5], axis=1).reshape(success.shape + (5,))
+        lo, hi = quantile_bands(replicates, success, level)
+        return QuantileBands(q, lo, hi, replicates, success, np.sum(success, axis=0), seed)
+
     def _bootstrap_replicate_densities(self, what, probs, n_subsamples, sample_vector, seed, level, tol, reg_param, orth_moments_tol,
                                        moments_fns, densities):
         """The part bootstrap_component_quantiles and bootstrap_component_shortfall share: argument checks, the densities of the
@@ -687,6 +704,17 @@ class Estimate:
         shape = (len(densities), probs.size)
         es = np.array(upper if tail == "upper" else lower, dtype=np.float64).reshape(shape)
         return es, np.array(q, dtype=np.float64).reshape(shape), success
+
+    def estimate_component_summaries(self, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None):
+        """Mean, variance, skewness, kurtosis, differential entropy and mass of the maximum-entropy density of EVERY scalar
+        component of the quantity, from two batched device calls (tool.simple_distribution.summaries).
+        :param densities: as in estimate_component_quantiles
+        :return: DensitySummary(mean, var, skewness, kurtosis, entropy, mass) of [M] arrays, entry m = `.summary()` of component
+            m's distribution (the row order of construct_densities); components of failed solves are still returned"""
+        from .tool import simple_distribution
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        return simple_distribution.summaries([d[0] for d in densities])
 
     def get_level_samples(self, level_id, n_samples=None):
         chunk_spec = next(self._sample_storage.chunks(level_id=level_id, n_samples=n_samples))

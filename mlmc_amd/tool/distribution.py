@@ -8,7 +8,8 @@ import numpy as np
 import scipy.integrate as integrate
 from scipy.optimize import OptimizeResult
 
-from .simple_distribution import _cdf, _device_density, _divergence, _expected_shortfall, _quantile, _solve_on_device
+from .simple_distribution import (_cdf, _device_density, _divergence, _entropy, _expected_shortfall, _fitted_moments, _quantile,
+                                  _solve_on_device, _summary)
 
 
 class Distribution:
@@ -147,6 +148,20 @@ class Distribution:
         """KL, L2, total-variation and Hellinger distance of the stored multipliers' density (the posterior) from `prior` on this
         distribution's quadrature (simple_distribution.divergences with one pair).  :return: Divergences of floats"""
         return _divergence(self, prior, interval)
+
+    def fitted_moments(self):
+        """int phi_i rho / int rho, i < len(multipliers), of the stored multipliers' density in this distribution's moments object
+        (simple_distribution.density_moments with one distribution)."""
+        return _fitted_moments(self)
+
+    def summary(self):
+        """Mean, variance, skewness, kurtosis, differential entropy and mass of the stored multipliers' density on this
+        distribution's quadrature (simple_distribution.summaries with one distribution).  :return: DensitySummary of floats"""
+        return _summary(self)
+
+    def entropy(self):
+        """Differential entropy of the normalised density of the stored multipliers on this distribution's quadrature."""
+        return _entropy(self)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

@@ -376,6 +376,154 @@ def _divergence(dist, prior, interval):
     return Divergences(*(float(v[0]) for v in divergences([prior], [dist], None if interval is None else [tuple(interval)])))
 
 
+DensityMoments = collections.namedtuple("DensityMoments", "moments entropy mass")
+DensitySummary = collections.namedtuple("DensitySummary", "mean var skewness kurtosis entropy mass")
+
+
+def _moment_problems(what, distrs, moments_fns, sizes):
+    """(test moments objects [B], output counts [B]) of a `density_moments` call, checked before any device call"""
+    B = len(distrs)
+    if moments_fns is None:
+        fns = [d.moments_fn for d in distrs]
+        if sizes is None:
+            sizes = [len(d.multipliers) for d in distrs]
+    elif isinstance(moments_fns, moments_mod.Moments):
+        fns = [moments_fns] * B
+    else:
+        fns = list(moments_fns)
+        if len(fns) != B:
+            raise ValueError("{}: {} moments objects for {} distributions".format(what, len(fns), B))
+        if not all(isinstance(fn, moments_mod.Moments) for fn in fns):
+            raise ValueError("{}: moments_fns must hold Moments objects".format(what))
+    if sizes is None:
+        sizes = [fn.size for fn in fns]
+    elif np.isscalar(sizes):
+        sizes = [sizes] * B
+    sizes = list(sizes)
+    if len(sizes) != B:
+        raise ValueError("{}: {} sizes for {} distributions".format(what, len(sizes), B))
+    seen = set()                                               # thousands of distributions usually share a few (object, size) pairs
+    for i, (fn, k) in enumerate(zip(fns, sizes)):
+        if (id(fn), id(k)) in seen:
+            continue
+        seen.add((id(fn), id(k)))
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= fn.size:
+            raise ValueError("{}: distribution {}: size must be an integer in 1..{}, got {!r}".format(what, i, fn.size, k))
+        if getattr(fn, "_kind", None) not in (_lib.LEGENDRE, _lib.MONOMIAL, _lib.FOURIER, _lib.SPLINE):
+            raise ValueError("{}: distribution {}: {} moments are not supported".format(what, i, type(fn).__name__))
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) > 1 or len(degs) > 1:
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    return fns, np.array(sizes, dtype=np.int32)
+
+
+def _raw_density_moments(what, distrs, moments_fns, sizes):
+    """mlmc_density_moments_batch of a list of distributions: (raw moments [B, Kmax], counts [B], raw entropy column [B], mass [B])"""
+    fns, k = _moment_problems(what, distrs, moments_fns, sizes)
+    B = len(distrs)
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    tests = (C.c_void_p * B)(*[fn._basis_handle().value for fn in fns])
+    out = np.empty((B, int(k.max())))
+    mass, ent = np.empty(B), np.empty(B)
+    _lib.check(_lib.lib().mlmc_density_moments_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig),
+                                                     _lib.ptr(a), _lib.ptr(b), int(distrs[0].n_intervals), int(distrs[0]._gauss_degree),
+                                                     C.cast(tests, C.c_void_p), _lib.ptr(k), _lib.ptr(out), _lib.ptr(mass),
+                                                     _lib.ptr(ent)))
+    return out, k, ent, mass
+
+
+def _normalized_entropy(ent, mass):
+    """differential entropy of rho / T from the raw column -int rho log rho and the mass T"""
+    with np.errstate(all="ignore"):
+        return ent / mass + np.log(mass)
+
+
+def density_moments(distrs, moments_fns=None, sizes=None, normalize=True):
+    """Moments, differential entropy and mass of many max-entropy densities through ONE device call (mlmc_density_moments_batch):
+    entry b of `moments` is int psi_j(x) rho_b(x) dx, j < sizes[b], for the moments object psi = moments_fns[b] -- any Legendre,
+    Monomial, Fourier or Spline object or a TransformedMoments of one, with its own domain, unrelated to the basis of the density.
+    A node of the quadrature outside a safe_eval object's domain makes that distribution's moments NaN.  On the distributions'
+    common quadrature (include/mlmc_hip.h); a value is bit for bit the same for a distribution alone or in any batch.
+    :param moments_fns: None: every distribution's own moments_fn at len(multipliers) -- the moments the solver has fitted, to
+        compare with moment_means; one object for all; or one per distribution
+    :param sizes: None: the full size of every object; one count for all; or one per distribution
+    :param normalize: True: moments of rho / T and the entropy -int (rho / T) log(rho / T), T the mass; False: the raw
+        int psi_j rho and -int rho log rho of the density as it is (the exponent clipped to +-200, as in `density`)
+    :return: DensityMoments(moments: list of B arrays, entropy [B], mass [B])"""
+    distrs = list(distrs)
+    if not distrs:
+        _moment_problems("density_moments", distrs, moments_fns, sizes)
+        return DensityMoments([], np.empty(0), np.empty(0))
+    out, k, ent, mass = _raw_density_moments("density_moments", distrs, moments_fns, sizes)
+    if normalize:
+        with np.errstate(all="ignore"):
+            out = out / mass[:, None]
+        ent = _normalized_entropy(ent, mass)
+    return DensityMoments([row[:n] for row, n in zip(out, k.tolist())], ent, mass)        # rows of one array owned by the result
+
+
+def _central_summary(r, scale, ref0, shift):
+    """mean, variance, skewness and kurtosis (not excess) of x from the normalised raw moments r [B, 5] = E[t^k], k = 0 .. 4, of
+    t = (x - shift) * scale + ref0: the exact raw-to-central formulas about t = 0, then x - shift = (t - ref0) / scale"""
+    r = np.asarray(r, dtype=np.float64)
+    r1, r2, r3, r4 = r[:, 1], r[:, 2], r[:, 3], r[:, 4]
+    with np.errstate(all="ignore"):
+        c2 = r2 - r1 * r1
+        c3 = r3 - 3 * r1 * r2 + 2 * r1 ** 3
+        c4 = r4 - 4 * r1 * r3 + 6 * r1 * r1 * r2 - 3 * r1 ** 4
+        return (r1 - ref0) / scale + shift, c2 / scale ** 2, c3 / c2 ** 1.5, c4 / (c2 * c2)
+
+
+def summaries(distrs):
+    """Mean, variance, skewness, kurtosis (3 for a Gaussian), differential entropy and mass of many max-entropy densities from two
+    device calls of `density_moments`' entry.  The first, with Monomial(2, domain), gives the mass and the centre m = a + W m_1 /
+    m_0, W = b - a; the second takes the moments of t = (x - m) / W up to t^4 (a Monomial object whose reference domain is the
+    domain shifted to the centre), so that the raw-to-central formulas subtract nothing of size: mu_1 ~ 0.  All on the
+    distributions' common quadrature, of the normalised density rho / mass.
+    :return: DensitySummary(mean, var, skewness, kurtosis, entropy, mass) of [B] arrays"""
+    distrs = list(distrs)
+    if not distrs:
+        return DensitySummary(*(np.empty(0) for _ in range(6)))
+    by_domain = {}                                             # one object (one device handle) per distinct domain
+    first = [by_domain.setdefault(dom, moments_mod.Monomial(2, dom)) for dom in ((float(d.domain[0]), float(d.domain[1])) for d in distrs)]
+    out, _, _, mass = _raw_density_moments("summaries", distrs, first, None)
+    second = []
+    for d, row in zip(distrs, out):
+        a, b = float(d.domain[0]), float(d.domain[1])
+        W = b - a
+        with np.errstate(all="ignore"):
+            m = a + W * (row[1] / row[0])
+        if not a <= m <= b:                                    # a density without a mean (NaN multipliers): NaN statistics below
+            m = 0.5 * (a + b)
+        second.append(moments_mod.Monomial(5, (a, b), ref_domain=((a - m) / W, (b - m) / W), safe_eval=False))
+    out, _, ent, mass = _raw_density_moments("summaries", distrs, second, None)
+    with np.errstate(all="ignore"):
+        r = out / mass[:, None]
+    scale = np.array([fn._linear_scale for fn in second], dtype=np.float64)
+    ref0 = np.array([fn.ref_domain[0] for fn in second], dtype=np.float64)
+    shift = np.array([fn._linear_shift for fn in second], dtype=np.float64)
+    mean, var, skew, kurt = _central_summary(r, scale, ref0, shift)
+    return DensitySummary(mean, var, skew, kurt, _normalized_entropy(ent, mass), mass)
+
+
+def _fitted_moments(dist):
+    """the B = 1 call of `density_moments` with the distribution's own moments object"""
+    return density_moments([dist]).moments[0]
+
+
+def _summary(dist):
+    """the B = 1 call of `summaries`: a DensitySummary of floats"""
+    return DensitySummary(*(float(v[0]) for v in summaries([dist])))
+
+
+def _entropy(dist):
+    """the B = 1 call of `density_moments`: the differential entropy of the normalised density"""
+    return float(density_moments([dist], sizes=1).entropy[0])
+
+
 def estimate_densities_minimize(distrs, tol=1e-5, reg_param=0.01):
     """SimpleDistribution.estimate_density_minimize of every distribution in `distrs`, solved in ONE batched device call
     (mlmc_maxent_solve_batch: one workgroup per problem).  Each distribution gets exactly what its own call would do:
@@ -530,6 +678,21 @@ class SimpleDistribution:
         object on the same quadrature, over `interval` (default: the intersection of the two domains): `divergences` with one
         pair, hence bit for bit its values.  :return: Divergences of floats"""
         return _divergence(self, prior, interval)
+
+    def fitted_moments(self):
+        """The moments of the normalised density in this distribution's own moments object, int phi_i rho / int rho for
+        i < len(multipliers): what the solver has fitted to moment_means (`density_moments` with one distribution, hence bit for
+        bit its values)."""
+        return _fitted_moments(self)
+
+    def summary(self):
+        """Mean, variance, skewness, kurtosis, differential entropy and mass of this density on its quadrature (`summaries` with
+        one distribution, hence bit for bit its values).  :return: DensitySummary of floats"""
+        return _summary(self)
+
+    def entropy(self):
+        """Differential entropy -int p log p of the normalised density p = rho / int rho on this distribution's quadrature."""
+        return _entropy(self)
 
     def _initialize_params(self, size, tol=None):
         assert self.domain is not None

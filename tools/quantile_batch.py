@@ -36,7 +36,16 @@ and on B = 1, R1 = 25, n = 10^6 device-resident probabilities (--config B,R1,n w
   quad_ms_scaled      (b) what the public API offers without the entry: KL_divergence and L2_distance with scipy.integrate.quad
                       on d.density, TIMED ON 4 PAIRS AND SCALED to P
   host_vs_entry / quad_vs_entry   largest difference between the alternatives' kl / l2 and the entry's, relative to the value
-Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails | --divergences] [--reps K]"""
+--moments: simple_distribution.density_moments at R1 = 25, K = 25 (every density's own Legendre basis) on the
+64 x 21 rule for B = 16, 3600 and 19200 solved densities, against the host route of the same definition, the two taking turns after
+a warm-up call each:
+  moments_ms          wall time of the one call (one mlmc_density_moments_batch), [min, mean, max] over the repetitions
+  host_sums_ms        ONE simple_distribution.densities call for the B distributions at the rule's nodes, then NumPy: the Legendre
+                      functions at the nodes (once: the densities share their basis), the moment sums as one matrix product, the
+                      mass and the entropy from the logarithm of the density; [min, mean, max]
+  summaries_ms        wall time of simple_distribution.summaries (two calls of the entry and 2 B moments objects), [min, mean, max]
+  host_vs_entry       largest difference between the host route's normalised moments and the entry's, absolute
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails | --divergences | --moments] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -247,6 +256,34 @@ def divergence_pairs(n_rep, n_comp, reps):
                 host_vs_entry=max(rel(host[0], res.kl), rel(host[1], res.l2)), quad_vs_entry=float(worst), all_success=ok)
 
 
+def moments_batch(B, reps):
+    distrs, ok = mixtures(B, 25)
+    d0 = distrs[0]
+    pts, w = sd._composite_gauss(DOM, d0.n_intervals, d0._gauss_degree)
+    fn = d0.moments_fn
+
+    def host_sums():
+        rho = np.array(sd.densities(distrs, pts))
+        phi = np.polynomial.legendre.legvander(fn.linear(pts), fn.size - 1)
+        wr = rho * w
+        mass = wr.sum(axis=1)
+        return (wr @ phi) / mass[:, None], -(wr * np.log(rho)).sum(axis=1) / mass + np.log(mass), mass
+    fns = [lambda: sd.density_moments(distrs), host_sums, lambda: sd.summaries(distrs)]
+    for f in fns:
+        f()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for k, f in enumerate(fns):
+            t0 = time.perf_counter()
+            f()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    res, host = sd.density_moments(distrs), host_sums()
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    return dict(B=B, R1=25, K=25, rule=[d0.n_intervals, d0._gauss_degree], moments_ms=span(times[0]), host_sums_ms=span(times[1]),
+                summaries_ms=span(times[2]), host_vs_entry=float(np.max(np.abs(np.array(res.moments) - host[0]))),
+                entropy_host_vs_entry=float(np.max(np.abs(res.entropy - host[1]))), all_success=ok)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -276,12 +313,15 @@ def main():
     ap.add_argument("--tails", action="store_true", help="tail_means against quantiles (DESIGN.md section 3.5.9)")
     ap.add_argument("--single", action="store_true", help="the single entries mlmc_density_eval / mlmc_density_integrate")
     ap.add_argument("--divergences", action="store_true", help="divergences against host sums and quad (DESIGN.md section 3.5.10)")
+    ap.add_argument("--moments", action="store_true", help="density_moments against host sums (DESIGN.md section 3.5.11)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.moments:
+        out["moments"] = [moments_batch(B, a.reps) for B in ((16,) if a.quick else (16, 3600, 19200))]
     elif a.divergences:
         shapes = ((16, 1),) if a.quick else ((16, 1), (300, 12), (300, 64))
         out["divergences"] = [divergence_pairs(n_rep, n_comp, a.reps) for n_rep, n_comp in shapes]
