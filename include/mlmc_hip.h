@@ -39,7 +39,8 @@ extern "C" {
                               *    mlmc_density_cdf_batch, mlmc_density_quantiles_batch,
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
-                              *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch */
+                              *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
+                              *    mlmc_density_sample_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -414,9 +415,37 @@ int mlmc_density_moments_batch(int32_t B, const mlmc_basis *const *bases, const 
                                const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                const mlmc_basis *const *test, const int32_t *K, double *out, double *mass_out,
                                double *entropy_out);
-/* HIP-event time (ms) and number of the point kernels (quantile and CDF kernels, without the table kernels and copies) that
- * mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch have launched since the last call of this
- * function; resets both.  A tail-means call counts its quantile kernel and its tail kernel together as one launch per group. */
+/* Seeded draws from the densities of B problems in one call (inverse-transform sampling) -- added within 8.  Problems, rule, table
+ * and Q are those of mlmc_density_quantiles_batch.  Draw j (0 <= j < 2^63) of stream s (uint32) under `seed` is x_j = Q(u_j), bit
+ * for bit the value of mlmc_density_quantiles_batch for the same problem, rule and p = u_j, where u_j is defined as follows.
+ *   Uniform k of the stream: Philox4x32-10 (Salmon et al., SC'11; key = (low word of seed, high word of seed), key bumps
+ *     0x9E3779B9 / 0xBB67AE85 per round) of the counter (i_lo, i_hi, s, 0x53414D50), i = k >> 1, gives r0 .. r3;
+ *     (hi, lo) = (r0, r1) for even k, (r2, r3) for odd k; m = (hi << 20) | (lo >> 12) (52 bits); u = (2 m + 1) 2^-53.
+ *     u is an odd multiple of 2^-53: 0 < u < 1 always, u is exact in fp64, and 1 - u is exact and of the same form.
+ *   Without MLMC_SAMPLE_ANTITHETIC in `flags` u_j = uniform j.  With it u_j = uniform j >> 1 for even j and 1 - (uniform j >> 1)
+ *     for odd j: draws 2k and 2k + 1 are an antithetic pair.
+ * Problem i writes its draws first[i] .. first[i] + n[i] - 1 of stream streams[i], one problem after another in out (and their
+ * u_j in u_out, which may be NULL), the layout of the points of mlmc_density_quantiles_batch.  streams [B] host uint32 (NULL:
+ * stream i = i), first [B] host int64 (NULL: zeros), n [B] host int64; mem_kind applies to out and u_out.  A draw depends on
+ * (seed, stream, j, flag, problem, rule) alone: not on n, on first, on the batch, on the problem's position in it or on the launch
+ * geometry; first = 50, n = 100 gives elements [50, 150) of first = 0, n = 150, so a run can be continued, and split across ranks
+ * by j or by stream.  Distinct streams, and distinct seeds, give independent uniforms; the draws of different problems are
+ * independent unless the caller gives them one stream (then they share their u_j: comonotone draws).  Layout, conventions,
+ * argument errors and no-ops as mlmc_density_quantiles_batch; in addition first[i] < 0 and first[i] + n[i] beyond int64 are errors
+ * that name the problem, unknown bits in flags an error of the call.  A problem whose mass is not finite and positive gives NaN
+ * for all its draws, its u_out are still the uniforms, and it is no error.  So does a problem with a NaN among its effective
+ * coefficients (NaN multipliers): the clip of the exponent hides them from the mass, and this entry does not draw from what
+ * is left (the one case where a draw is not the quantile entry's value).  One workgroup per (problem, share of its draws), no
+ * atomics; one host wait. */
+#define MLMC_SAMPLE_ANTITHETIC 1
+int mlmc_density_sample_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                              const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                              uint64_t seed, const uint32_t *streams, const int64_t *first, const int64_t *n, int32_t flags,
+                              double *out, double *u_out, double *mass_out, int mem_kind);
+/* HIP-event time (ms) and number of the point kernels (quantile, CDF and sampling kernels, without the table kernels and copies)
+ * that mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch / mlmc_density_sample_batch have
+ * launched since the last call of this function; resets both.  A tail-means call counts its quantile kernel and its tail kernel
+ * together as one launch per group; a sampling call counts its sampling kernel, one launch per group. */
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */

@@ -17,6 +17,10 @@
 //                   Newton iteration on g(x) = P_j + I(e_j, x) - p T with g' = density(x); bisection whenever the step leaves
 //                   the bracket or is not finite
 //   k_q_cdf       : Fhat at arbitrary values, one thread per value (cell lookup + one partial-cell rule)
+//   k_q_sample    : seeded draws x_j = Q(u_j) (mlmc_density_sample_batch): one workgroup per (problem, share of its draws); rule,
+//                   coefficients and P row staged in LDS once, the uniform of a draw made in registers by Philox4x32-10 from
+//                   (seed, stream, j), then k_q_quantile's inversion reading LDS; a lane walks its own list of draws and starts
+//                   the next when its current one has ended (QInversion), so a slow draw holds up one lane, not its wave
 // Tail means (expected shortfall, mlmc_density_tail_means_batch): with A_j / B_j the cell sums of (t - a) rho / (b - t) rho on the
 // nodes of C_j, V the forward prefix of the A_j, S and W the backward suffixes of the C_j and B_j,
 //     lower(x) = a + (V_j + A(e_j, x)) / (P_j + I(e_j, x)),   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / (S_{j+1} + I(x, e_{j+1})).
@@ -214,39 +218,69 @@ __global__ __launch_bounds__(64) void k_q_prefix(int nprob, int nint, double *__
     if constexpr (TAILS) mean[k] = probs[k].a + run2 / run;
 }
 
+// The inversion of one probability p as a resumable iteration, so that a lane can take its next point while its neighbours still
+// iterate on theirs: begin() is the table look-up and the start in the cell, step() one evaluation of g with the bracketed Newton
+// update.  The operations of a point and their order do not depend on how its steps interleave with those of other points.
+template <int KIND>
+struct QInversion {
+    double value;                            // Q(p), once begin() or step() has returned false
+    double target, ej, Pj, xl, gl, xh, gh, x, gstop;
+    int it;
+    // false: the value is known without iterating
+    __device__ __forceinline__ bool begin(const QProb &P, const double *__restrict__ row, int nint, double p) {
+        const double T = row[nint];
+        value = __builtin_nan("");
+        if (!(T > 0.0) || !(T < __builtin_inf())) return false;
+        if (!(p >= 0.0 && p <= 1.0)) return false;
+        if (p == 0.0) value = P.a;
+        if (p == 1.0) value = P.b;
+        if (p == 0.0 || p == 1.0) return false;
+        target = p * T;
+        int lo = 0, hi = nint;                  // the largest j < n with P_j <= target
+        for (int k = 0; k < 32 && hi - lo > 1; ++k) {
+            const int mid = (lo + hi) >> 1;
+            if (row[mid] <= target) lo = mid; else hi = mid;
+        }
+        const int j = lo;
+        const double h = (P.b - P.a) / (double)nint;
+        ej = q_edge(P, h, nint, j);
+        Pj = row[j];
+        xl = ej;                                                           // g(xl) <= 0 <= g(xh)
+        gl = Pj - target;
+        xh = q_edge(P, h, nint, j + 1);
+        gh = row[j + 1] - target;
+        x = xl + (xh - xl) * (-gl / (gh - gl));                            // linear interpolate inside the cell
+        if (!(x >= xl && x <= xh)) x = 0.5 * (xl + xh);
+        gstop = 0x1p-52 * target;                                          // g is a difference of two sums near `target`: it is 0 or at least
+                                                                           // about one spacing of them, nothing in between can be resolved
+        it = 0;
+        return true;
+    }
+    // false: the iteration has ended
+    __device__ __forceinline__ bool step(const QProb &P, const double *__restrict__ c, const double *__restrict__ nodes,
+                                         const double *__restrict__ wts, int deg) {
+        const double gx = (Pj + density_integral<KIND>(P.bp, c, P.n_coef, ej, x, nodes, wts, deg)) - target;
+        if (gx <= 0.0) { xl = x; gl = gx; } else { xh = x; gh = gx; }
+        bool more = !(fabs(gx) <= gstop);
+        if (more) {
+            double xn = x - gx / density_value<KIND>(P.bp, c, P.n_coef, x);
+            if (!(xn > xl && xn < xh)) xn = 0.5 * (xl + xh);                // the step left the bracket or is not finite: bisection
+            more = !(fabs(xn - x) <= q_spacing(x));
+            if (more) x = xn;
+        }
+        more = more && ++it < Q_MAX_IT;
+        if (!more) value = fabs(gl) <= fabs(gh) ? xl : xh;
+        return more;
+    }
+};
+
 template <int KIND>
 __device__ double q_invert(const QProb &P, const double *__restrict__ c, const double *__restrict__ row, int nint,
                            const double *__restrict__ nodes, const double *__restrict__ wts, int deg, double p) {
-    const double T = row[nint];
-    if (!(T > 0.0) || !(T < __builtin_inf())) return __builtin_nan("");
-    if (!(p >= 0.0 && p <= 1.0)) return __builtin_nan("");
-    if (p == 0.0) return P.a;
-    if (p == 1.0) return P.b;
-    const double target = p * T;
-    int lo = 0, hi = nint;                  // the largest j < n with P_j <= target
-    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-        const int mid = (lo + hi) >> 1;
-        if (row[mid] <= target) lo = mid; else hi = mid;
-    }
-    const int j = lo;
-    const double h = (P.b - P.a) / (double)nint;
-    const double ej = q_edge(P, h, nint, j), Pj = row[j];
-    double xl = ej, gl = Pj - target;                                  // g(xl) <= 0 <= g(xh)
-    double xh = q_edge(P, h, nint, j + 1), gh = row[j + 1] - target;
-    double x = xl + (xh - xl) * (-gl / (gh - gl));                     // linear interpolate inside the cell
-    if (!(x >= xl && x <= xh)) x = 0.5 * (xl + xh);
-    const double gstop = 0x1p-52 * target;                             // g is a difference of two sums near `target`: it is 0 or at least
-                                                                       // about one spacing of them, nothing in between can be resolved
-    for (int it = 0; it < Q_MAX_IT; ++it) {
-        const double gx = (Pj + density_integral<KIND>(P.bp, c, P.n_coef, ej, x, nodes, wts, deg)) - target;
-        if (gx <= 0.0) { xl = x; gl = gx; } else { xh = x; gh = gx; }
-        if (fabs(gx) <= gstop) break;
-        double xn = x - gx / density_value<KIND>(P.bp, c, P.n_coef, x);
-        if (!(xn > xl && xn < xh)) xn = 0.5 * (xl + xh);                // the step left the bracket or is not finite: bisection
-        if (fabs(xn - x) <= q_spacing(x)) break;
-        x = xn;
-    }
-    return fabs(gl) <= fabs(gh) ? xl : xh;
+    QInversion<KIND> s;
+    if (s.begin(P, row, nint, p))
+        while (s.step(P, c, nodes, wts, deg)) {}
+    return s.value;
 }
 
 __global__ __launch_bounds__(Q_THREADS) void k_q_quantile(const QProb *__restrict__ probs, int nprob, int nint, int64_t pt0, int64_t npts,
@@ -316,6 +350,94 @@ __global__ __launch_bounds__(Q_THREADS) void k_q_tails(const QProb *__restrict__
     }
     lower[idx] = lw;
     upper[idx] = up;
+}
+
+// the draws of one problem of a sampling call: draws first .. first + n - 1 of stream `stream`; two doubles wide, staged as such
+struct QDraw {
+    int64_t first;
+    uint32_t stream;
+    uint32_t nan_coef;   // a coefficient of the problem is NaN: the clip of the exponent hides it from the mass, the draws are NaN
+};
+static_assert(sizeof(QDraw) == 2 * sizeof(double), "QDraw is staged as two doubles");
+
+constexpr int Q_SAMPLE_THREADS = 256;                  // at most; problems with few draws get fewer waves with longer lists
+constexpr int Q_SAMPLE_MAX_COEF = 512;                 // coefficients of a problem that are staged in LDS; more stay in global memory
+constexpr size_t Q_SAMPLE_LDS_BYTES = 32768;           // of a workgroup: at this size the registers still bound the occupancy, not the LDS
+constexpr int Q_SAMPLE_DRAWS = 32;                     // draws per lane a launch aims at: long lists even out the step counts
+constexpr int Q_SAMPLE_WAVES_PER_CU = 16;              // resident waves per CU where the runtime does not tell (4 per SIMD at 123 VGPRs)
+
+// uniform `idx` of stream `stream` under `seed` (include/mlmc_hip.h): Philox counter (idx >> 1, stream, "SAMP"), words (r0, r1) for
+// an even idx and (r2, r3) for an odd one, their top 52 bits m, u = (2 m + 1) 2^-53: exact, 0 < u < 1, and 1 - u is exact
+__device__ __forceinline__ double q_uniform(uint64_t seed, uint32_t stream, uint64_t idx) {
+    const uint64_t i = idx >> 1;
+    uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), stream, 0x53414D50u};
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);         // keyed as bs_philox (bootstrap.hip) and philox_u64 (select.hip)
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    const uint32_t hi = (idx & 1) ? c[2] : c[0], lo = (idx & 1) ? c[3] : c[1];
+    const uint64_t m = ((uint64_t)hi << 20) | (uint64_t)(lo >> 12);
+    return (double)(int64_t)(2 * m + 1) * 0x1p-53;
+}
+
+// Draws of a problem = blockIdx.x, grid-stride in y over its draws as in k_q_density.  What every draw of the problem reads is
+// staged once per workgroup in LDS, Gauss nodes | weights | coefficients (COEF_LDS) | P row (ROW_LDS), and read from there by
+// the inversion: every lane reads the same address in the density chain (a broadcast).  A lane walks its own list of draws and
+// starts the next one as soon as its current one has ended (QInversion), whatever its neighbours are doing: a wave then takes as
+// long as the lane with the largest SUM of steps, not the sum over draws of the largest step count among 64 lanes (3.5 steps
+// on average, but 0.3-1.3 % of the draws take 10-50).  Neither where the values live nor how the steps interleave enters the
+// arithmetic of a draw, so out is bit for bit k_q_quantile's value at the same u.
+template <bool COEF_LDS, bool ROW_LDS>
+__global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__restrict__ probs, const QDraw *__restrict__ draws, int nint,
+                                                               const double *__restrict__ coef, const double *__restrict__ tab,
+                                                               const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                               uint64_t seed, int antithetic, double *__restrict__ out,
+                                                               double *__restrict__ u_out) {
+    extern __shared__ double q_sample_lds[];
+    const QProb P = probs[blockIdx.x];
+    const int64_t t0 = (int64_t)blockIdx.y * blockDim.x;
+    if (t0 >= P.n) return;                                 // the whole workgroup: no draw of this problem is left for it
+    const QDraw D = draws[blockIdx.x];
+    double *gx = q_sample_lds, *gw = gx + deg, *cl = gw + deg, *rl = cl + (COEF_LDS ? P.n_coef : 0);
+    for (int k = threadIdx.x; k < deg; k += blockDim.x) {
+        gx[k] = nodes[k];
+        gw[k] = wts[k];
+    }
+    const double *c = coef + P.c_off, *row = tab + (int64_t)blockIdx.x * (nint + 1);
+    if constexpr (COEF_LDS) {
+        for (int r = threadIdx.x; r < P.n_coef; r += blockDim.x) cl[r] = c[r];
+        c = cl;
+    }
+    if constexpr (ROW_LDS) {
+        for (int j = threadIdx.x; j <= nint; j += blockDim.x) rl[j] = row[j];
+        row = rl;
+    }
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.y * blockDim.x;
+    with_kind(P.bp.kind, [&](auto K) {
+        QInversion<decltype(K)::value> s;
+        bool busy = false;
+        int64_t cur = 0;                                    // the draw `s` iterates on
+        for (int64_t t = t0 + threadIdx.x; busy || t < P.n;) {
+            if (!busy) {                                    // this lane's next draw, while other lanes go on with theirs
+                const uint64_t j = (uint64_t)(D.first + t);
+                double u = q_uniform(seed, D.stream, antithetic ? j >> 1 : j);
+                if (antithetic && (j & 1)) u = 1.0 - u;
+                if (u_out) u_out[P.x_off + t] = u;
+                busy = !D.nan_coef && s.begin(P, row, nint, u);
+                if (!busy) out[P.x_off + t] = D.nan_coef ? __builtin_nan("") : s.value;
+                cur = t;
+                t += stride;
+            }
+            if (busy && !s.step(P, c, gx, gw, deg)) {
+                out[P.x_off + cur] = s.value;
+                busy = false;
+            }
+        }
+    });
 }
 
 // one pair of a divergences call: problems `first` (p) and `second` (q) on [lo, hi]; three doubles wide, staged as such
@@ -503,7 +625,7 @@ __global__ __launch_bounds__(Q_MOM_THREADS) void k_q_moments(const QProb *__rest
     }
 }
 
-// HIP-event time of the point kernels (k_q_quantile / k_q_cdf; k_q_quantile + k_q_tails of a tail-means call as one), for
+// HIP-event time of the point kernels (k_q_quantile / k_q_cdf / k_q_sample; k_q_quantile + k_q_tails of a tail-means call as one), for
 // mlmc_density_quantiles_kernel_time: one event pair per group of a call, read after the call's own wait
 struct QTiming {
     std::vector<hipEvent_t> ev;
@@ -696,14 +818,39 @@ static int q_integrate(const char *fn, bool single, int32_t B, const mlmc_basis 
     return 0;
 }
 
-enum QMode { Q_CDF, Q_QUANTILES, Q_TAILS };
+enum QMode { Q_CDF, Q_QUANTILES, Q_TAILS, Q_SAMPLE };
 
-// mlmc_density_cdf_batch (Q_CDF), mlmc_density_quantiles_batch (Q_QUANTILES) and mlmc_density_tail_means_batch (Q_TAILS: `out`
-// receives the quantiles, lower_out / upper_out the tail means at them, mean_out the problems' means; all NULL otherwise)
+// what a sampling call has instead of points
+struct QSampling {
+    uint64_t seed;
+    const uint32_t *streams;          // [B] host or NULL
+    const int64_t *first;             // [B] host or NULL
+    int32_t flags;
+    double *u_out;                    // may be NULL
+};
+
+// the draws table of a sampling call
+static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::vector<QDraw> &draws) {
+    draws.resize(S.probs.size());
+    for (size_t i = 0; i < S.probs.size(); ++i) {
+        const QProb &p = S.probs[i];
+        const int64_t first = smp.first ? smp.first[i] : 0;
+        if (first < 0) return meb_fail(fn, (int)i, "first < 0");
+        if (first > INT64_MAX - p.n) return meb_fail(fn, (int)i, "first + n overflows int64");
+        const double *c = S.coef.data() + p.c_off;
+        const bool nan_coef = std::any_of(c, c + p.n_coef, [](double v) { return v != v; });
+        draws[i] = QDraw{first, smp.streams ? smp.streams[i] : (uint32_t)i, nan_coef ? 1u : 0u};
+    }
+    return 0;
+}
+
+// mlmc_density_cdf_batch (Q_CDF), mlmc_density_quantiles_batch (Q_QUANTILES), mlmc_density_tail_means_batch (Q_TAILS: `out`
+// receives the quantiles, lower_out / upper_out the tail means at them, mean_out the problems' means; all NULL otherwise) and
+// mlmc_density_sample_batch (Q_SAMPLE: no points x, `smp` instead; `out` receives the draws, smp->u_out their uniforms)
 static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                      const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind, double *lower_out = nullptr,
-                     double *upper_out = nullptr, double *mean_out = nullptr) {
+                     double *upper_out = nullptr, double *mean_out = nullptr, const QSampling *smp = nullptr) {
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (B < 0) return fail(std::string(fn) + ": B < 0");
     if (B == 0) return 0;
@@ -711,10 +858,13 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
     if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    const bool tails = mode == Q_TAILS, sample = mode == Q_SAMPLE;
+    if (sample && (smp->flags & ~MLMC_SAMPLE_ANTITHETIC)) return fail(std::string(fn) + ": unknown flag bits");
     QSetup S;
     if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
-    const bool tails = mode == Q_TAILS;
-    if (S.n_tot > 0 && (!x || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
+    std::vector<QDraw> draws;
+    if (sample && q_draws(fn, S, *smp, draws)) return 1;
+    if (S.n_tot > 0 && ((!sample && !x) || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
     if (S.n_tot == 0 && !mass_out && !mean_out) return 0;
     const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     hipStream_t st = rt().stream;
@@ -723,12 +873,29 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * rows * ((size_t)nint + 1))));
     const int64_t plane = (int64_t)G * (nint + 1);
     const size_t np = stage ? (size_t)S.n_tot : 0, nm = (size_t)B * (tails ? 2 : 1);      // staged points; masses, then means
+    // what goes up with the block: the points, or the draws table of a sampling call; a sampling call returns the uniforms in
+    // the place of the lower tail means
+    const size_t n_in = sample ? draws.size() * (sizeof(QDraw) / sizeof(double)) : np;
+    if (sample) lower_out = smp->u_out;
     QBlock K;
-    if (q_stage(S, deg, {np}, {nm, rows * (size_t)plane, np, tails ? np : 0, tails ? np : 0}, {nm}, K)) return 1;
-    if (K.upload({x}, np)) return 1;
+    if (q_stage(S, deg, {n_in}, {nm, rows * (size_t)plane, np, lower_out ? np : 0, tails ? np : 0}, {nm}, K)) return 1;
+    if (K.upload({sample ? (const double *)draws.data() : x}, n_in)) return 1;
     double *d_mass = K.d[0], *d_mean = d_mass + B, *d_tab = K.d[1];
     const double *d_x = stage ? K.d_in[0] : x;
-    double *d_out = stage ? K.d[2] : out, *d_lower = stage ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
+    double *d_out = stage ? K.d[2] : out, *d_lower = stage && lower_out ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
+    // a sampling launch: LDS for the rule, the coefficients and the P row, each as far as it fits
+    int max_coef = 0;
+    for (const QProb &p : S.probs) max_coef = std::max(max_coef, p.n_coef);
+    const bool coef_lds = max_coef <= Q_SAMPLE_MAX_COEF;
+    const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)), lds_row = sizeof(double) * ((size_t)nint + 1);
+    const bool row_lds = coef_lds && lds_head + lds_row <= Q_SAMPLE_LDS_BYTES;
+    const auto sampler = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
+    const size_t lds_bytes = lds_head + (row_lds ? lds_row : 0);
+    // resident waves per CU of the sampling kernel as the runtime reports them for its registers and this LDS size
+    int64_t sample_waves_per_cu = Q_SAMPLE_WAVES_PER_CU;
+    int resident = 0;
+    if (sample && hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, sampler, Q_SAMPLE_THREADS, lds_bytes) == hipSuccess && resident > 0)
+        sample_waves_per_cu = (int64_t)resident * (Q_SAMPLE_THREADS / 64);
     const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
     const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
     QTiming &tm = q_timing();
@@ -743,11 +910,27 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
         const int64_t pt0 = S.probs[g0].x_off;
         const int64_t npts = (g0 + np_g < B ? S.probs[g0 + np_g].x_off : S.n_tot) - pt0;
         if (npts > 0) {
-            const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));
             hipEvent_t e0, e1;
             const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
-            hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts, K.coef,
-                               (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
+            const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));           // of the one-thread-per-point kernels
+            if (sample) {
+                int64_t n_max = 0;
+                for (int i = g0; i < g0 + np_g; ++i) n_max = std::max(n_max, S.probs[i].n);
+                // Launch geometry (no draw depends on it).  The group's draws are dealt to the chip's wave slots in k rounds, k such
+                // that a lane's list has about Q_SAMPLE_DRAWS draws, or one round of shorter lists when there are too few draws for
+                // that: a problem gets as many waves (first within a workgroup, then workgroups) as its lists of that length need.
+                const int64_t lanes = 64 * sample_waves_per_cu * std::max(1, rt().n_cu);
+                const int64_t rounds = std::max<int64_t>(1, (npts + lanes * Q_SAMPLE_DRAWS / 2) / (lanes * Q_SAMPLE_DRAWS));
+                const int64_t list = std::max<int64_t>(1, npts / (lanes * rounds));
+                const int64_t threads = 64 * std::clamp<int64_t>(n_max / (64 * list), 1, Q_SAMPLE_THREADS / 64);
+                const int64_t gy = std::clamp<int64_t>((n_max + threads * list / 2) / (threads * list), 1, 65535);
+                hipLaunchKernelGGL(sampler, dim3((unsigned)np_g, (unsigned)gy), dim3((unsigned)threads), lds_bytes, st, K.probs + g0,
+                                   (const QDraw *)K.d_in[0] + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, smp->seed,
+                                   (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower);
+            } else {
+                hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts,
+                                   K.coef, (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
+            }
             if (tails)                           // the quantiles, as k_q_quantile has just written them, are the points
                 hipLaunchKernelGGL(k_q_tails, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts, K.coef, (const double *)d_tab,
                                    plane, K.gx, K.gw, deg, (const double *)d_out, d_lower, d_upper);
@@ -756,10 +939,8 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
         MLMC_HIP_CHECK(hipGetLastError());
     }
     if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    if (stage && tails) {
-        MLMC_HIP_CHECK(hipMemcpyAsync(lower_out, d_lower, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-        MLMC_HIP_CHECK(hipMemcpyAsync(upper_out, d_upper, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    }
+    if (stage && lower_out) MLMC_HIP_CHECK(hipMemcpyAsync(lower_out, d_lower, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    if (stage && tails) MLMC_HIP_CHECK(hipMemcpyAsync(upper_out, d_upper, sizeof(double) * np, hipMemcpyDeviceToHost, st));
     if (mass_out || mean_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * nm, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * B);
@@ -975,6 +1156,16 @@ int mlmc_density_tail_means_batch(int32_t B, const mlmc_basis *const *bases, con
     MLMC_API_GUARD;
     return q_on_rule("mlmc_density_tail_means_batch", Q_TAILS, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, p, n, q_out,
                      mass_out, mem_kind, lower_out, upper_out, mean_out);
+}
+
+int mlmc_density_sample_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                              const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, uint64_t seed,
+                              const uint32_t *streams, const int64_t *first, const int64_t *n, int32_t flags, double *out, double *u_out,
+                              double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    const QSampling smp = {seed, streams, first, flags, u_out};
+    return q_on_rule("mlmc_density_sample_batch", Q_SAMPLE, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, nullptr, n, out,
+                     mass_out, mem_kind, nullptr, nullptr, nullptr, &smp);
 }
 
 int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,

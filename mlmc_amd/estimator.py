@@ -685,6 +685,30 @@ class Estimate:
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return np.array(q, dtype=np.float64).reshape(len(densities), probs.size), success
 
+    def sample_components(self, n, seed, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
+                          antithetic=False, device=False):
+        """Seeded draws from the maximum-entropy density of EVERY scalar component of the quantity, in one batched device call
+        (tool.simple_distribution.samples): draws first .. first + n - 1 of component m come from stream m under `seed`.
+
+        The marginals are drawn INDEPENDENTLY: dependence between the components is out of scope here.  For dependent draws
+        make the uniforms yourself (for example from a copula fitted to the stored samples) and pass row m of them to
+        `tool.simple_distribution.quantiles`, which is the same inverse transform.
+        :param n: draws per component
+        :param seed: required, 0 <= seed < 2^64; there is no global generator
+        :param densities: as in estimate_component_quantiles
+        :param device: return the draws as a float64 torch device tensor
+        :return: (samples, success): samples [M, n], row m = `.rvs(n, seed, stream=m, first=first, antithetic=antithetic)` of
+            component m's distribution (the row order of construct_densities); success [M] bool, the solver's verdict per
+            component (rows of failed solves are still returned)"""
+        from .tool import simple_distribution
+        if isinstance(n, bool) or int(n) != n or n < 0:
+            raise ValueError("sample_components: n must be a non-negative integer")
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        flat, _, _ = simple_distribution._samples_flat([d[0] for d in densities], int(n), seed, None, first, antithetic, device, False)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return flat.reshape(len(densities), int(n)), success           # the call's one array, viewed as [M, n]
+
     def estimate_component_shortfall(self, probs, tail="upper", tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                      densities=None):
         """Expected shortfall (CVaR) of the maximum-entropy density of EVERY scalar component of the quantity, in one batched

@@ -9,7 +9,7 @@ import scipy.integrate as integrate
 from scipy.optimize import OptimizeResult
 
 from .simple_distribution import (_cdf, _device_density, _divergence, _entropy, _expected_shortfall, _fitted_moments, _quantile,
-                                  _solve_on_device, _summary)
+                                  _rvs, _solve_on_device, _summary)
 
 
 class Distribution:
@@ -138,6 +138,11 @@ class Distribution:
         """Q(p) of the stored multipliers on this distribution's quadrature (simple_distribution.quantiles with one
         distribution; p may be a float64 torch device tensor)."""
         return _quantile(self, p)
+
+    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False):
+        """n seeded draws from the density of the stored multipliers: draws first .. first + n - 1 of stream `stream` under `seed`
+        (simple_distribution.samples with one distribution)."""
+        return _rvs(self, n, seed, stream, first, antithetic, device)
 
     def expected_shortfall(self, p, tail="upper"):
         """Expected shortfall (CVaR) at level p of the stored multipliers on this distribution's quadrature: E[X | X >= Q(p)]

@@ -316,6 +316,93 @@ def _quantile(dist, p):
     return res
 
 
+def _per_distribution_int(what, name, value, B):
+    """[B] int64 from one integer for all or one per distribution"""
+    arr = np.asarray(value)
+    if arr.ndim > 1 or (arr.ndim == 1 and arr.size != B):
+        raise ValueError("{}: {} must be one integer or one per distribution".format(what, name))
+    if arr.dtype.kind not in "iu" or np.any(arr < 0) or np.any(arr.astype(np.uint64) > np.uint64(2 ** 63 - 1)):
+        raise ValueError("{}: {} must be non-negative integers below 2^63".format(what, name))
+    return np.ascontiguousarray(np.broadcast_to(arr.astype(np.int64), (B,)))
+
+
+def samples(distrs, n, seed, streams=None, first=0, antithetic=False, device=False, return_uniforms=False):
+    """Seeded draws from many distributions through ONE device call (mlmc_density_sample_batch): inverse-transform sampling on
+    each distribution's quadrature.  Draw j of stream s under `seed` is Q(u_j) with Q of `quantiles` (bit for bit its value at
+    p = u_j) and u_j the Philox4x32-10 uniform that include/mlmc_hip.h defines, an odd multiple of 2^-53 in (0, 1).  Entry b holds
+    the draws first[b] .. first[b] + n[b] - 1 of stream streams[b].  A draw depends on (seed, stream, j, antithetic, distribution,
+    quadrature) alone: not on n, on first or on the other distributions, so `first` continues a run and streams (or ranges of
+    j) split it across ranks.  The draws of different distributions are independent unless they are given one stream.
+    :param n: draws per distribution, one int for all or one per distribution
+    :param seed: required, 0 <= seed < 2^64; there is no global generator
+    :param streams: one uint32 stream per distribution; default: stream b = b
+    :param first: index of the first draw, one int for all or one per distribution
+    :param antithetic: draws 2k and 2k + 1 come from u and 1 - u
+    :param device: return float64 torch device tensors; nothing but the problem table touches the host then
+    :param return_uniforms: also return the list of the u_j
+    :return: list of arrays [n[b]] (and the same list of uniforms); every distribution must use the same quadrature"""
+    out, u, n = _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms)
+
+    def per_distribution(flat):
+        if device:
+            import torch
+            return list(torch.split(flat, [int(k) for k in n]))
+        return np.split(flat, np.cumsum(n)[:-1])
+    if out is None:
+        return ([], []) if return_uniforms else []
+    return (per_distribution(out), per_distribution(u)) if return_uniforms else per_distribution(out)
+
+
+def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms):
+    """the call behind `samples`: (draws, uniforms or None, counts [B]) with the distributions' draws one after another in one
+    array or device tensor; (None, None, counts) for an empty list"""
+    distrs = list(distrs)
+    B = len(distrs)
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("samples: seed must be an integer in 0 .. 2^64 - 1")
+    if B == 0:
+        return None, None, np.zeros(0, dtype=np.int64)
+    n = _per_distribution_int("samples", "n", n, B)
+    first = _per_distribution_int("samples", "first", first, B)
+    if streams is None:
+        streams = np.arange(B, dtype=np.uint32)
+    else:
+        st = np.asarray(streams)
+        if st.shape != (B,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
+            raise ValueError("samples: streams must be one integer in 0 .. 2^32 - 1 per distribution")
+        streams = np.ascontiguousarray(st.astype(np.uint32))
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError("samples: every distribution must use the same quadrature")
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    total = int(n.sum())
+    lib = _lib.lib()
+    if device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty(total, dtype=torch.float64, device=dev)
+        u = torch.empty(total, dtype=torch.float64, device=dev) if return_uniforms else None
+        torch.cuda.current_stream(dev).synchronize()         # the library writes them on its own stream
+        kind = _lib.DEVICE
+    else:
+        out = np.empty(total)
+        u = np.empty(total) if return_uniforms else None
+        kind = _lib.HOST
+    _lib.check(lib.mlmc_density_sample_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a),
+                                             _lib.ptr(b), int(n_int.pop()), int(degs.pop()), int(seed), _lib.ptr(streams),
+                                             _lib.ptr(first), _lib.ptr(n), _lib.SAMPLE_ANTITHETIC if antithetic else 0,
+                                             _lib.ptr(out), _lib.ptr(u), None, kind))
+    return out, u, n
+
+
+def _rvs(dist, n, seed, stream, first, antithetic, device):
+    """the B = 1 call of `samples`"""
+    return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device)[0]
+
+
 Divergences = collections.namedtuple("Divergences", "kl l2 tv hellinger mass_prior mass_posterior")
 
 
@@ -666,6 +753,11 @@ class SimpleDistribution:
         call with one distribution, hence bit for bit its value).  p: array-like, or a float64 torch device tensor (the result
         is a device tensor then, e.g. for inverse-transform sampling with the caller's own uniforms)."""
         return _quantile(self, p)
+
+    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False):
+        """n seeded draws from this density: draws first .. first + n - 1 of stream `stream` under `seed` (see `samples`, of which
+        this is the call with one distribution, hence bit for bit its values; `seed` is required)."""
+        return _rvs(self, n, seed, stream, first, antithetic, device)
 
     def expected_shortfall(self, p, tail="upper"):
         """Expected shortfall (CVaR) at level p on this distribution's quadrature: E[X | X >= Q(p)] for tail = "upper",

@@ -45,7 +45,17 @@ a warm-up call each:
                       mass and the entropy from the logarithm of the density; [min, mean, max]
   summaries_ms        wall time of simple_distribution.summaries (two calls of the entry and 2 B moments objects), [min, mean, max]
   host_vs_entry       largest difference between the host route's normalised moments and the entry's, absolute
-Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single] [--tails | --divergences | --moments] [--reps K]"""
+--samples: simple_distribution.samples(..., device=True) against the route that exists without it,
+torch.rand on the device + simple_distribution.quantiles, on the same solved densities, the two taking turns after a warm-up call
+each; B x R1 x n = 1 x {9, 25, 64} x 10^7, 64 x 25 x 10^6 and 3600 x 25 x 10^3 draws (--config B,R1,n with --samples: that shape alone):
+  samples_ms / rand_quantiles_ms                wall time of the whole route up to a device synchronise, [min, mean, max]
+  samples_kernel_ms / quantiles_kernel_ms       HIP-event time of the point kernel of one call (mlmc_density_quantiles_kernel_time):
+                                                k_q_sample, which makes its uniforms, and k_q_quantile, which reads torch's
+  speedup_wall / speedup_kernel                 the route without the entry over the entry, from the means
+  ks_samples / ks_rand_quantiles                Kolmogorov distance of the first 10^5 draws of problem 0 (or all its draws) from
+                                                cdfs_on_rule, a sanity check of both routes
+Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
+                                                             [--tails | --divergences | --moments | --samples] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -284,6 +294,48 @@ def moments_batch(B, reps):
                 entropy_host_vs_entry=float(np.max(np.abs(res.entropy - host[1]))), all_success=ok)
 
 
+def samples_shape(B, R1, n, reps):
+    distrs, ok = mixtures(B, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    seed = [1000 * B + R1]
+
+    def new_route():
+        seed[0] += 1                                                 # fresh draws in every call, as torch.rand gives the other route
+        x = sd.samples(distrs, n, seed[0], device=True)
+        torch.cuda.synchronize()
+        return x
+
+    def parent_route():
+        u = torch.rand(B * n, dtype=torch.float64, device="cuda")
+        x = sd.quantiles(distrs, list(torch.split(u, n)))
+        torch.cuda.synchronize()
+        return x
+    routes = (new_route, parent_route)
+    for fn in routes:
+        fn()
+    wall, kern = [[], []], [[], []]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+
+    def ks(x):
+        f = np.sort(sd.cdfs_on_rule([distrs[0]], x[0][:100_000].cpu().numpy())[0])
+        k = np.arange(1, f.size + 1)
+        return float(max(np.max(k / f.size - f), np.max(f - (k - 1) / f.size)))
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    mean = lambda t: sum(t) / len(t)
+    return dict(B=B, R1=R1, n=n, samples_ms=span(wall[0]), rand_quantiles_ms=span(wall[1]), samples_kernel_ms=span(kern[0]),
+                quantiles_kernel_ms=span(kern[1]), speedup_wall=round(mean(wall[1]) / mean(wall[0]), 3),
+                speedup_kernel=round(mean(kern[1]) / mean(kern[0]), 3), ks_samples=round(ks(new_route()), 5),
+                ks_rand_quantiles=round(ks(parent_route()), 5), all_success=ok)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -314,12 +366,20 @@ def main():
     ap.add_argument("--single", action="store_true", help="the single entries mlmc_density_eval / mlmc_density_integrate")
     ap.add_argument("--divergences", action="store_true", help="divergences against host sums and quad (DESIGN.md section 3.5.10)")
     ap.add_argument("--moments", action="store_true", help="density_moments against host sums (DESIGN.md section 3.5.11)")
+    ap.add_argument("--samples", action="store_true", help="samples against torch.rand + quantiles (DESIGN.md section 3.5.12)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.samples:
+        shapes = [(1, 9, 10_000_000), (1, 25, 10_000_000), (1, 64, 10_000_000), (64, 25, 1_000_000), (3600, 25, 1_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 10_000)]
+        out["samples"] = [samples_shape(B, R1, n, a.reps) for B, R1, n in shapes]
     elif a.moments:
         out["moments"] = [moments_batch(B, a.reps) for B in ((16,) if a.quick else (16, 3600, 19200))]
     elif a.divergences:
