@@ -40,7 +40,7 @@ extern "C" {
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
-                              *    mlmc_density_sample_batch */
+                              *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -442,10 +442,43 @@ int mlmc_density_sample_batch(int32_t B, const mlmc_basis *const *bases, const i
                               const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                               uint64_t seed, const uint32_t *streams, const int64_t *first, const int64_t *n, int32_t flags,
                               double *out, double *u_out, double *mass_out, int mem_kind);
+/* Seeded JOINT draws of M problems through a Gaussian copula -- added within 8.  Problems, rule, table and the quantile function
+ * Q_m are those of mlmc_density_quantiles_batch (lambda / sigma [M][R1max]).  With K >= 1 latent normals and a factor F [M][K] of
+ * the correlation matrix of the normal scores (host, row-major; K = M and the lower Cholesky factor is the usual case, K < M a
+ * low-rank factor model, K = 1 with ones gives comonotone draws), draw j (first <= j < first + n) of component m is
+ *     x[m][j] = Q_m(u[m][j]),   u[m][j] = min(max(normcdf(y[m][j]), 2^-53), 1 - 2^-53),   y[m][j] = sum_k F[m][k] z[k][j].
+ *   Latent normal k of draw j: u0 = uniform i of stream streams[k] (uint32 [K] host, NULL: stream k = k) under `seed`, exactly the
+ *     uniform of mlmc_density_sample_batch (same Philox keying, tag word and 52-bit construction).  Without
+ *     MLMC_SAMPLE_ANTITHETIC in `flags` i = j and z = normcdfinv(u0); with it i = j >> 1 and z is negated for odd j (exact: draws
+ *     2k and 2k + 1 are an exact antithetic pair of normals).  u0 is an odd multiple of 2^-53, so z is always finite.
+ *   The sum y runs over k ascending in the groups of four that v_mfma_f64_16x16x4_f64 consumes, from 0; padding of M, K and n to
+ *     tile sizes adds exact zeros.
+ *   x[m][j] is bit for bit the value of mlmc_density_quantiles_batch for problem m, the rule and p = u[m][j].
+ * Every entry of F must be finite and every row must satisfy |sum_k F[m][k]^2 - 1| <= 1e-6 (otherwise the marginals would silently
+ * be wrong); a violation is an error that names the row.  One n (int64 >= 0) and one first (int64 >= 0, first + n within int64) for
+ * all components.  out [M][n] and u_out [M][n] (may be NULL) and z_out [K][n] (may be NULL) are host or device arrays by mem_kind,
+ * column j - first of a row holds draw j; mass_out [M] (may be NULL) is host and receives the masses of the quantile entry.
+ * u[m][j] depends on (seed, streams, j, flag, row m of F) alone and x[m][j] in addition on problem m and the rule: neither depends on
+ * M, on the row's position, on the other rows or problems, on n, on first, on the blocks the draws are processed in or on the launch
+ * geometry; first = 50, n = 100 gives columns [50, 150) of first = 0, n = 150.  With F = I the latent normals come from the same
+ * uniforms as mlmc_density_sample_batch with the same seed and streams, and the joint draws equal the independent ones up to the
+ * rounding of normcdf(normcdfinv(.)): a caller who wants joint and independent draws that are independent of each other gives them
+ * different seeds or streams.  Argument errors and no-ops as mlmc_density_sample_batch (null arrays, M < 0, bad rule, bad mem_kind,
+ * unknown flag bits; M = 0 is a no-op); K < 1, a null factor, n < 0, first < 0 and first + n beyond int64 are errors of the call;
+ * n = 0 is a no-op that still returns the masses when asked.  A problem whose mass is not finite and positive, or with NaN
+ * coefficients, gives a row of NaN draws, is no error, its rows of u_out / z_out are still written and the other rows are
+ * unaffected.  The draws are processed in blocks of columns so that the normals and uniforms in the workspace stay within 192 MiB
+ * (MLMC_JOINT_BLOCK_DRAWS in the environment, read per call, sets the block length: a test aid, no value depends on it).  No
+ * atomics; one host wait. */
+int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                    const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                    int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
+                                    int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
 /* HIP-event time (ms) and number of the point kernels (quantile, CDF and sampling kernels, without the table kernels and copies)
- * that mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch / mlmc_density_sample_batch have
- * launched since the last call of this function; resets both.  A tail-means call counts its quantile kernel and its tail kernel
- * together as one launch per group; a sampling call counts its sampling kernel, one launch per group. */
+ * that mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch / mlmc_density_sample_batch /
+ * mlmc_density_sample_joint_batch have launched since the last call of this function; resets both.  A tail-means call counts its
+ * quantile kernel and its tail kernel together as one launch per group; a sampling call counts its sampling kernel, one launch per
+ * group; a joint sampling call counts its normals, uniforms and sampling kernels together as one launch per block and group. */
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */

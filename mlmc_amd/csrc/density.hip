@@ -20,7 +20,9 @@
 //   k_q_sample    : seeded draws x_j = Q(u_j) (mlmc_density_sample_batch): one workgroup per (problem, share of its draws); rule,
 //                   coefficients and P row staged in LDS once, the uniform of a draw made in registers by Philox4x32-10 from
 //                   (seed, stream, j), then k_q_quantile's inversion reading LDS; a lane walks its own list of draws and starts
-//                   the next when its current one has ended (QInversion), so a slow draw holds up one lane, not its wave
+//                   the next when its current one has ended (QInversion), so a slow draw holds up one lane, not its wave;
+//                   the instances with U_IN (mlmc_density_sample_joint_batch) read the uniforms that copula.hip's kernels have
+//                   made (u = clamp(normcdf(F z)), a Gaussian copula over the problems) instead of making them
 // Tail means (expected shortfall, mlmc_density_tail_means_batch): with A_j / B_j the cell sums of (t - a) rho / (b - t) rho on the
 // nodes of C_j, V the forward prefix of the A_j, S and W the backward suffixes of the C_j and B_j,
 //     lower(x) = a + (V_j + A(e_j, x)) / (P_j + I(e_j, x)),   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / (S_{j+1} + I(x, e_{j+1})).
@@ -42,11 +44,13 @@
 // same launch geometry serves thousands of problems with a few points each and a few problems with 10^7 points each.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
 
+#include "copula.hpp"
 #include "density.hpp"
 #include "maxent_batch.hpp"
 
@@ -56,6 +60,9 @@ constexpr int Q_THREADS = 256;
 constexpr int Q_MAX_IT = 64;                           // iteration cap of the bracketed Newton iteration
 constexpr int Q_MAX_INTERVALS = 1 << 20;
 constexpr size_t Q_TABLE_BYTES = (size_t)64 << 20;     // bound of the prefix tables; more problems are processed in groups
+constexpr size_t Q_JOINT_BYTES = (size_t)192 << 20;    // bound of the latent normals and copula uniforms of a joint sampling call that
+                                                       // live in the workspace; more draws are processed in blocks of columns (with
+                                                       // the table the workspace stays below MEB_KEEP_BYTES: it is kept between calls)
 constexpr size_t Q_DIRECT_BYTES = (size_t)1 << 20;     // host point arrays beyond this are copied to the device straight from the caller's
                                                        // memory (faster from 8 MB on, measured); smaller ones ride in the block's one copy
 
@@ -366,23 +373,6 @@ constexpr size_t Q_SAMPLE_LDS_BYTES = 32768;           // of a workgroup: at thi
 constexpr int Q_SAMPLE_DRAWS = 32;                     // draws per lane a launch aims at: long lists even out the step counts
 constexpr int Q_SAMPLE_WAVES_PER_CU = 16;              // resident waves per CU where the runtime does not tell (4 per SIMD at 123 VGPRs)
 
-// uniform `idx` of stream `stream` under `seed` (include/mlmc_hip.h): Philox counter (idx >> 1, stream, "SAMP"), words (r0, r1) for
-// an even idx and (r2, r3) for an odd one, their top 52 bits m, u = (2 m + 1) 2^-53: exact, 0 < u < 1, and 1 - u is exact
-__device__ __forceinline__ double q_uniform(uint64_t seed, uint32_t stream, uint64_t idx) {
-    const uint64_t i = idx >> 1;
-    uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), stream, 0x53414D50u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);         // keyed as bs_philox (bootstrap.hip) and philox_u64 (select.hip)
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint32_t hi = (idx & 1) ? c[2] : c[0], lo = (idx & 1) ? c[3] : c[1];
-    const uint64_t m = ((uint64_t)hi << 20) | (uint64_t)(lo >> 12);
-    return (double)(int64_t)(2 * m + 1) * 0x1p-53;
-}
-
 // Draws of a problem = blockIdx.x, grid-stride in y over its draws as in k_q_density.  What every draw of the problem reads is
 // staged once per workgroup in LDS, Gauss nodes | weights | coefficients (COEF_LDS) | P row (ROW_LDS), and read from there by
 // the inversion: every lane reads the same address in the density chain (a broadcast).  A lane walks its own list of draws and
@@ -390,16 +380,21 @@ __device__ __forceinline__ double q_uniform(uint64_t seed, uint32_t stream, uint
 // long as the lane with the largest SUM of steps, not the sum over draws of the largest step count among 64 lanes (3.5 steps
 // on average, but 0.3-1.3 % of the draws take 10-50).  Neither where the values live nor how the steps interleave enters the
 // arithmetic of a draw, so out is bit for bit k_q_quantile's value at the same u.
-template <bool COEF_LDS, bool ROW_LDS>
+// U_IN (mlmc_density_sample_joint_batch): the uniforms are not made here but read, draw t of problem blockIdx.x from
+// u_in[blockIdx.x * u_ld + t], t < u_n (a block of the call's draws, the same count for every problem); `out` points at the
+// block's first draw.  seed, antithetic, u_out and the draws' first / stream are not used then.
+template <bool COEF_LDS, bool ROW_LDS, bool U_IN = false>
 __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__restrict__ probs, const QDraw *__restrict__ draws, int nint,
                                                                const double *__restrict__ coef, const double *__restrict__ tab,
                                                                const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
                                                                uint64_t seed, int antithetic, double *__restrict__ out,
-                                                               double *__restrict__ u_out) {
+                                                               double *__restrict__ u_out, const double *__restrict__ u_in, int64_t u_ld,
+                                                               int64_t u_n) {
     extern __shared__ double q_sample_lds[];
     const QProb P = probs[blockIdx.x];
+    const int64_t n_draws = U_IN ? u_n : P.n;
     const int64_t t0 = (int64_t)blockIdx.y * blockDim.x;
-    if (t0 >= P.n) return;                                 // the whole workgroup: no draw of this problem is left for it
+    if (t0 >= n_draws) return;                             // the whole workgroup: no draw of this problem is left for it
     const QDraw D = draws[blockIdx.x];
     double *gx = q_sample_lds, *gw = gx + deg, *cl = gw + deg, *rl = cl + (COEF_LDS ? P.n_coef : 0);
     for (int k = threadIdx.x; k < deg; k += blockDim.x) {
@@ -421,12 +416,27 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
         QInversion<decltype(K)::value> s;
         bool busy = false;
         int64_t cur = 0;                                    // the draw `s` iterates on
-        for (int64_t t = t0 + threadIdx.x; busy || t < P.n;) {
+        int64_t t = t0 + threadIdx.x;
+        // U_IN: the uniform of the lane's next draw is loaded while it inverts the one before, so that no wave waits for memory
+        // at the start of a draw
+        [[maybe_unused]] const double *ur = nullptr;
+        [[maybe_unused]] double u_next = 0.0;
+        if constexpr (U_IN) {
+            ur = u_in + (int64_t)blockIdx.x * u_ld;
+            if (t < n_draws) u_next = ur[t];
+        }
+        while (busy || t < n_draws) {
             if (!busy) {                                    // this lane's next draw, while other lanes go on with theirs
-                const uint64_t j = (uint64_t)(D.first + t);
-                double u = q_uniform(seed, D.stream, antithetic ? j >> 1 : j);
-                if (antithetic && (j & 1)) u = 1.0 - u;
-                if (u_out) u_out[P.x_off + t] = u;
+                double u;
+                if constexpr (U_IN) {
+                    u = u_next;
+                    if (t + stride < n_draws) u_next = ur[t + stride];
+                } else {
+                    const uint64_t j = (uint64_t)(D.first + t);
+                    u = q_uniform(seed, D.stream, antithetic ? j >> 1 : j);
+                    if (antithetic && (j & 1)) u = 1.0 - u;
+                    if (u_out) u_out[P.x_off + t] = u;
+                }
                 busy = !D.nan_coef && s.begin(P, row, nint, u);
                 if (!busy) out[P.x_off + t] = D.nan_coef ? __builtin_nan("") : s.value;
                 cur = t;
@@ -844,6 +854,43 @@ static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::v
     return 0;
 }
 
+// A sampling launch: the kernel's instance and its LDS (the rule, the coefficients and the P row, each as far as it fits), and
+// the resident waves per CU of that instance as the runtime reports them for its registers and this LDS size.
+using QSampler = decltype(&k_q_sample<true, true, false>);
+struct QSampleLaunch {
+    QSampler kernel = nullptr;
+    size_t lds_bytes = 0;
+    int64_t waves_per_cu = Q_SAMPLE_WAVES_PER_CU;
+    // Launch geometry (no draw depends on it) of npts draws in all, at most n_max of one problem.  The draws are dealt to the chip's
+    // wave slots in k rounds, k such that a lane's list has about Q_SAMPLE_DRAWS draws, or one round of shorter lists when there
+    // are too few draws for that: a problem gets as many waves (first within a workgroup, then workgroups) as its lists of that
+    // length need.
+    void geometry(int64_t npts, int64_t n_max, unsigned &threads, unsigned &gy) const {
+        const int64_t lanes = 64 * waves_per_cu * std::max(1, rt().n_cu);
+        const int64_t rounds = std::max<int64_t>(1, (npts + lanes * Q_SAMPLE_DRAWS / 2) / (lanes * Q_SAMPLE_DRAWS));
+        const int64_t list = std::max<int64_t>(1, npts / (lanes * rounds));
+        const int64_t th = 64 * std::clamp<int64_t>(n_max / (64 * list), 1, Q_SAMPLE_THREADS / 64);
+        threads = (unsigned)th;
+        gy = (unsigned)std::clamp<int64_t>((n_max + th * list / 2) / (th * list), 1, 65535);
+    }
+};
+// u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch)
+static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in) {
+    int max_coef = 0;
+    for (const QProb &p : S.probs) max_coef = std::max(max_coef, p.n_coef);
+    const bool coef_lds = max_coef <= Q_SAMPLE_MAX_COEF;
+    const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)), lds_row = sizeof(double) * ((size_t)nint + 1);
+    const bool row_lds = coef_lds && lds_head + lds_row <= Q_SAMPLE_LDS_BYTES;
+    QSampleLaunch L;
+    if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
+    else L.kernel = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
+    L.lds_bytes = lds_head + (row_lds ? lds_row : 0);
+    int resident = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, L.kernel, Q_SAMPLE_THREADS, L.lds_bytes) == hipSuccess && resident > 0)
+        L.waves_per_cu = (int64_t)resident * (Q_SAMPLE_THREADS / 64);
+    return L;
+}
+
 // mlmc_density_cdf_batch (Q_CDF), mlmc_density_quantiles_batch (Q_QUANTILES), mlmc_density_tail_means_batch (Q_TAILS: `out`
 // receives the quantiles, lower_out / upper_out the tail means at them, mean_out the problems' means; all NULL otherwise) and
 // mlmc_density_sample_batch (Q_SAMPLE: no points x, `smp` instead; `out` receives the draws, smp->u_out their uniforms)
@@ -883,19 +930,8 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     double *d_mass = K.d[0], *d_mean = d_mass + B, *d_tab = K.d[1];
     const double *d_x = stage ? K.d_in[0] : x;
     double *d_out = stage ? K.d[2] : out, *d_lower = stage && lower_out ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
-    // a sampling launch: LDS for the rule, the coefficients and the P row, each as far as it fits
-    int max_coef = 0;
-    for (const QProb &p : S.probs) max_coef = std::max(max_coef, p.n_coef);
-    const bool coef_lds = max_coef <= Q_SAMPLE_MAX_COEF;
-    const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)), lds_row = sizeof(double) * ((size_t)nint + 1);
-    const bool row_lds = coef_lds && lds_head + lds_row <= Q_SAMPLE_LDS_BYTES;
-    const auto sampler = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
-    const size_t lds_bytes = lds_head + (row_lds ? lds_row : 0);
-    // resident waves per CU of the sampling kernel as the runtime reports them for its registers and this LDS size
-    int64_t sample_waves_per_cu = Q_SAMPLE_WAVES_PER_CU;
-    int resident = 0;
-    if (sample && hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, sampler, Q_SAMPLE_THREADS, lds_bytes) == hipSuccess && resident > 0)
-        sample_waves_per_cu = (int64_t)resident * (Q_SAMPLE_THREADS / 64);
+    QSampleLaunch L;
+    if (sample) L = q_sample_launch(S, nint, deg, false);
     const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
     const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
     QTiming &tm = q_timing();
@@ -916,17 +952,12 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
             if (sample) {
                 int64_t n_max = 0;
                 for (int i = g0; i < g0 + np_g; ++i) n_max = std::max(n_max, S.probs[i].n);
-                // Launch geometry (no draw depends on it).  The group's draws are dealt to the chip's wave slots in k rounds, k such
-                // that a lane's list has about Q_SAMPLE_DRAWS draws, or one round of shorter lists when there are too few draws for
-                // that: a problem gets as many waves (first within a workgroup, then workgroups) as its lists of that length need.
-                const int64_t lanes = 64 * sample_waves_per_cu * std::max(1, rt().n_cu);
-                const int64_t rounds = std::max<int64_t>(1, (npts + lanes * Q_SAMPLE_DRAWS / 2) / (lanes * Q_SAMPLE_DRAWS));
-                const int64_t list = std::max<int64_t>(1, npts / (lanes * rounds));
-                const int64_t threads = 64 * std::clamp<int64_t>(n_max / (64 * list), 1, Q_SAMPLE_THREADS / 64);
-                const int64_t gy = std::clamp<int64_t>((n_max + threads * list / 2) / (threads * list), 1, 65535);
-                hipLaunchKernelGGL(sampler, dim3((unsigned)np_g, (unsigned)gy), dim3((unsigned)threads), lds_bytes, st, K.probs + g0,
+                unsigned threads, gy;
+                L.geometry(npts, n_max, threads, gy);
+                hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0,
                                    (const QDraw *)K.d_in[0] + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, smp->seed,
-                                   (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower);
+                                   (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower, (const double *)nullptr, (int64_t)0,
+                                   (int64_t)0);
             } else {
                 hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts,
                                    K.coef, (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
@@ -945,6 +976,125 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * B);
     if (mean_out) std::memcpy(mean_out, K.h[0] + B, sizeof(double) * B);
+    for (size_t k = 0; k < timed; ++k) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
+        tm.ms += ms;
+        ++tm.launches;
+    }
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+// mlmc_density_sample_joint_batch: draws of M problems joined by a Gaussian copula.  Table, masses and inversion are those of
+// q_on_rule's sampling branch; the uniforms come from copula.hip instead of q_uniform.  The draws are processed in blocks of nb
+// columns: latent normals Z [K][nb], copula uniforms U [M][nb], inversion of the block.  Z and U live in the workspace unless the
+// caller's device arrays take them in place.  No value depends on nb.
+static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                   const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf, const double *factor,
+                   uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *out, double *u_out,
+                   double *z_out, double *mass_out, int mem_kind) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (M < 0) return fail(std::string(fn) + ": M < 0");
+    if (M == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    if (flags & ~MLMC_SAMPLE_ANTITHETIC) return fail(std::string(fn) + ": unknown flag bits");
+    if (Kf < 1) return fail(std::string(fn) + ": K < 1");
+    if (!factor) return fail(std::string(fn) + ": null factor");
+    if (n < 0) return fail(std::string(fn) + ": n < 0");
+    if (first < 0) return fail(std::string(fn) + ": first < 0");
+    if (first > INT64_MAX - n) return fail(std::string(fn) + ": first + n overflows int64");
+    for (int m = 0; m < M; ++m) {
+        const double *row = factor + (size_t)m * Kf;
+        double ss = 0.0;
+        for (int k = 0; k < Kf; ++k) ss += row[k] * row[k];          // a value that is not finite makes the sum not finite
+        if (!std::isfinite(ss)) return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": an entry is not finite");
+        if (!(std::fabs(ss - 1.0) <= 1e-6))
+            return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": the sum of squares must be 1 within 1e-6");
+    }
+    QSetup S;
+    const std::vector<int64_t> counts((size_t)M, n);
+    if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
+    std::vector<QDraw> draws;
+    const QSampling no_streams = {seed, nullptr, nullptr, flags, nullptr};        // of the table, the joint entry reads nan_coef alone
+    if (q_draws(fn, S, no_streams, draws)) return 1;
+    if (n > 0 && !out) return fail(std::string(fn) + ": null argument");
+    if (n == 0 && !mass_out) return 0;
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    hipStream_t st = rt().stream;
+    const bool stage = mem_kind == MLMC_HOST && n > 0;
+    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
+    const int64_t plane = (int64_t)G * (nint + 1);
+    // the draws of a block: Z and U of a block within Q_JOINT_BYTES, whole tiles of the matrix kernel
+    int64_t nb = std::max<int64_t>(64, (int64_t)(Q_JOINT_BYTES / (sizeof(double) * ((size_t)M + (size_t)Kf))) / 64 * 64);
+    if (const char *env = std::getenv("MLMC_JOINT_BLOCK_DRAWS")) {
+        const long long v = std::atoll(env);
+        if (v > 0) nb = v;
+    }
+    nb = std::min(nb, std::max<int64_t>(n, 1));
+    const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && !(mem_kind == MLMC_DEVICE && u_out);
+    // what goes up with the block: the draws table | the streams (uint32) | the factor
+    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
+    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_in = n_draw + n_str + n_fac;
+    std::vector<double> packed(n_in);
+    std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
+    if (n > 0) {
+        uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
+        for (int k = 0; k < Kf; ++k) sv[k] = streams ? streams[k] : (uint32_t)k;
+        std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
+    }
+    QBlock K;
+    if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, stage ? (size_t)M * (size_t)n : 0, u_ws ? (size_t)M * (size_t)nb : 0,
+                                z_ws ? (size_t)Kf * (size_t)nb : 0}, {(size_t)M}, K))
+        return 1;
+    if (K.upload({packed.data()}, n_in)) return 1;
+    const QDraw *d_draws = (const QDraw *)K.d_in[0];
+    const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
+    const double *d_factor = K.d_in[0] + n_draw + n_str;
+    double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
+    const QSampleLaunch L = q_sample_launch(S, nint, deg, true);
+    QTiming &tm = q_timing();
+    size_t timed = 0;
+    for (int g0 = 0; g0 < M; g0 += G) {
+        const int np_g = std::min(G, M - g0);
+        const int64_t n_cells = (int64_t)np_g * nint;
+        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
+                           K.gw, deg, d_tab, plane);
+        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
+                           d_mass + g0, (double *)nullptr);
+        for (int64_t c0 = 0; c0 < n; c0 += nb) {
+            const int64_t nc = std::min(nb, n - c0);
+            // the block's Z and U: in the caller's device arrays at column c0 (row length n), or in the workspace (row length nb)
+            double *Z = z_ws ? K.d[4] : z_out + c0, *U = u_ws ? K.d[3] : u_out + c0;
+            const int64_t ldz = z_ws ? nb : n, ldu = u_ws ? nb : n;
+            hipEvent_t e0, e1;
+            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            if (g0 == 0 || z_ws)               // a later group finds the normals of the block in the caller's array
+                cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
+            cop_launch_uniforms(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu);
+            unsigned threads, gy;
+            L.geometry((int64_t)np_g * nc, nc, threads, gy);
+            hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0, d_draws + g0, nint, K.coef,
+                               (const double *)d_tab, K.gx, K.gw, deg, seed, 0, d_out + c0, (double *)nullptr,
+                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc);
+            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+            MLMC_HIP_CHECK(hipGetLastError());
+            if (stage && z_out && g0 == 0)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c0, sizeof(double) * n, Z, sizeof(double) * ldz, sizeof(double) * nc, (size_t)Kf,
+                                                hipMemcpyDeviceToHost, st));
+            if (stage && u_out)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + (int64_t)g0 * n + c0, sizeof(double) * n, U + (int64_t)g0 * ldu, sizeof(double) * ldu,
+                                                sizeof(double) * nc, (size_t)np_g, hipMemcpyDeviceToHost, st));
+        }
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
+    if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)M * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
     for (size_t k = 0; k < timed; ++k) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
@@ -1166,6 +1316,15 @@ int mlmc_density_sample_batch(int32_t B, const mlmc_basis *const *bases, const i
     const QSampling smp = {seed, streams, first, flags, u_out};
     return q_on_rule("mlmc_density_sample_batch", Q_SAMPLE, B, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, nullptr, n, out,
                      mass_out, mem_kind, nullptr, nullptr, nullptr, &smp);
+}
+
+int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                    const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                    int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
+                                    int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_joint("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
+                   streams, first, n, flags, out, u_out, z_out, mass_out, mem_kind);
 }
 
 int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,

@@ -690,9 +690,8 @@ class Estimate:
         """Seeded draws from the maximum-entropy density of EVERY scalar component of the quantity, in one batched device call
         (tool.simple_distribution.samples): draws first .. first + n - 1 of component m come from stream m under `seed`.
 
-        The marginals are drawn INDEPENDENTLY: dependence between the components is out of scope here.  For dependent draws
-        make the uniforms yourself (for example from a copula fitted to the stored samples) and pass row m of them to
-        `tool.simple_distribution.quantiles`, which is the same inverse transform.
+        The marginals are drawn INDEPENDENTLY; `sample_joint` draws them jointly, through a Gaussian copula with the
+        correlation of `estimate_component_covariance`.
         :param n: draws per component
         :param seed: required, 0 <= seed < 2^64; there is no global generator
         :param densities: as in estimate_component_quantiles
@@ -708,6 +707,49 @@ class Estimate:
         flat, _, _ = simple_distribution._samples_flat([d[0] for d in densities], int(n), seed, None, first, antithetic, device, False)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return flat.reshape(len(densities), int(n)), success           # the call's one array, viewed as [M, n]
+
+    def sample_joint(self, n, seed, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
+                     antithetic=False, device=False):
+        """Seeded JOINT draws of all scalar components of the quantity, in one batched device call
+        (tool.simple_distribution.joint_samples): the maximum-entropy marginals of `construct_densities` joined by a Gaussian
+        copula.  Column j of the result is one scenario of the whole vector: use it for the sum of the components, the CVaR of a
+        portfolio of outputs or joint exceedance.
+
+        What the dependence is: the PEARSON correlation of the components (corr_ij = cov_ij / sqrt(cov_ii cov_jj) of
+        `estimate_component_covariance()`) used as the correlation of the normal scores.  This is the uncorrected Nataf / NORTA
+        approximation: it is exact for Gaussian marginals, and the marginal transforms preserve the rank correlation of the
+        normal scores; for other marginals the Pearson correlation of the draws differs somewhat from the one put in.
+        Estimating the normal-score correlation itself, by a multilevel pass over Phi^-1(Fhat_m(X_m)), is the follow-up and not
+        provided.  A covariance estimate that is not positive definite (a telescoping sum need not be) is repaired by
+        `tool.simple_distribution.correlation_factor`.
+        :param n: draws per component, indices first .. first + n - 1
+        :param seed: required, 0 <= seed < 2^64; there is no global generator.  With corr = identity the draws equal those of
+            `sample_components` with the same seed up to rounding: use another seed where the two must be independent
+        :param corr: correlation matrix [M, M] of the normal scores; default: from estimate_component_covariance() as above
+        :param densities: as in estimate_component_quantiles
+        :param device: return the draws as a float64 torch device tensor
+        :return: (samples [M, n], success [M], corr_used [M, M]): row m = component m (the row order of construct_densities);
+            the solver's verdict per component; F F^T of the factor that was used"""
+        from .tool import simple_distribution
+        if isinstance(n, bool) or int(n) != n or n < 0:
+            raise ValueError("sample_joint: n must be a non-negative integer")
+        if corr is None:
+            cov, _ = self.estimate_component_covariance()
+            var = np.diag(cov)
+            bad = np.flatnonzero(~(np.isfinite(var) & (var > 0)))
+            if bad.size:
+                raise ValueError("sample_joint: component {} has no positive finite variance estimate ({})".format(int(bad[0]),
+                                                                                                                  var[bad[0]]))
+            sd = np.sqrt(var)
+            corr = cov / sd[:, None] / sd[None, :]
+            np.fill_diagonal(corr, 1.0)
+        factor, _ = simple_distribution.correlation_factor(corr)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        draws = simple_distribution.joint_samples([d[0] for d in densities], int(n), seed, factor=factor, first=first,
+                                                  antithetic=antithetic, device=device)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return draws, success, factor @ factor.T
 
     def estimate_component_shortfall(self, probs, tail="upper", tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                      densities=None):

@@ -398,6 +398,108 @@ def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_un
     return out, u, n
 
 
+CorrelationFactorInfo = collections.namedtuple("CorrelationFactorInfo", "min_eig_in repaired max_change")
+
+
+def correlation_factor(corr, min_eig=1e-10):
+    """Lower-triangular factor F of a correlation matrix, F F^T = corr, for `joint_samples`; on the host in NumPy.  The matrix is
+    symmetrised; it must be square and finite with a unit diagonal within 1e-8.  A multilevel covariance estimate is a telescoping
+    sum and need not be positive definite: if the smallest eigenvalue is below `min_eig`, the eigenvalues are clipped to
+    `min_eig`, the matrix is rebuilt and rescaled to a unit diagonal.  The rows of the Cholesky factor are renormalised to unit
+    norm, so that every marginal of F z is a standard normal.
+    :return: (factor [M, M], CorrelationFactorInfo(min_eig_in, repaired, max_change)): the smallest eigenvalue of the input,
+        whether it was repaired, and the largest absolute change of an entry (F F^T against the symmetrised input)"""
+    c = np.array(corr, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 1:
+        raise ValueError("correlation_factor: corr must be a square matrix, got shape {}".format(c.shape))
+    if not np.all(np.isfinite(c)):
+        raise ValueError("correlation_factor: corr must be finite")
+    c = 0.5 * (c + c.T)
+    if np.max(np.abs(np.diag(c) - 1.0)) > 1e-8:
+        raise ValueError("correlation_factor: corr must have a unit diagonal (within 1e-8)")
+    w, v = np.linalg.eigh(c)
+    min_eig_in = float(w[0])
+    repaired = bool(min_eig_in < min_eig)
+    fixed = c
+    if repaired:
+        fixed = (v * np.maximum(w, min_eig)) @ v.T
+        d = 1.0 / np.sqrt(np.diag(fixed))
+        fixed = fixed * d[:, None] * d[None, :]
+        fixed = 0.5 * (fixed + fixed.T)
+    factor = np.linalg.cholesky(fixed)
+    factor = np.ascontiguousarray(factor / np.sqrt(np.sum(factor * factor, axis=1))[:, None])
+    return factor, CorrelationFactorInfo(min_eig_in, repaired, float(np.max(np.abs(factor @ factor.T - c))))
+
+
+def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0, antithetic=False, device=False,
+                  return_uniforms=False, return_normals=False):
+    """Seeded JOINT draws from many distributions through ONE device call (mlmc_density_sample_joint_batch): a Gaussian copula
+    over the marginals.  With K latent standard normals z and a factor F [M, K] of the correlation matrix of the normal scores,
+        x[m, j] = Q_m(u[m, j]),   u = clamp(Phi(F z)),
+    Q_m of `quantiles` (bit for bit its value at p = u).  Latent normal k of draw j is Phi^-1 of the uniform j of stream streams[k]
+    under `seed` that `samples` uses (include/mlmc_hip.h), so a draw depends on (seed, streams, j, antithetic, row m of F,
+    distribution m, quadrature) alone: not on n, on first, on the other rows or on the batch.  With F = I the draws equal those of
+    `samples` with the same seed and streams up to the rounding of Phi(Phi^-1(.)): give the two different seeds or streams where
+    they must be independent of each other.
+    :param n: draws per distribution (one integer); draw indices first .. first + n - 1
+    :param seed: required, 0 <= seed < 2^64; there is no global generator
+    :param corr: correlation matrix [M, M] of the normal scores; goes through `correlation_factor`
+    :param factor: or the factor itself, [M, K] with rows of unit norm: K = M lower triangular, K < M a low-rank factor model,
+        ones [M, 1] comonotone draws.  Exactly one of corr / factor must be given
+    :param streams: one uint32 stream per latent normal; default: stream k = k
+    :param antithetic: draws 2k and 2k + 1 come from z and -z
+    :param device: return float64 torch device tensors
+    :param return_uniforms, return_normals: also return u [M, n] and / or z [K, n], in this order
+    :return: draws [M, n]; every distribution must use the same quadrature"""
+    distrs = list(distrs)
+    M = len(distrs)
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("joint_samples: seed must be an integer in 0 .. 2^64 - 1")
+    if (corr is None) == (factor is None):
+        raise ValueError("joint_samples: exactly one of corr and factor must be given")
+    if M == 0:
+        raise ValueError("joint_samples: no distributions")
+    n = int(_per_distribution_int("joint_samples", "n", n, 1)[0])
+    first = int(_per_distribution_int("joint_samples", "first", first, 1)[0])
+    if corr is not None:
+        factor = correlation_factor(corr)[0]
+    factor = np.ascontiguousarray(factor, dtype=np.float64)
+    if factor.ndim != 2 or factor.shape[0] != M or factor.shape[1] < 1:
+        raise ValueError("joint_samples: the factor must be [M, K] with M = {} distributions, got shape {}".format(M, factor.shape))
+    K = factor.shape[1]
+    if streams is not None:
+        st = np.asarray(streams)
+        if st.shape != (K,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
+            raise ValueError("joint_samples: streams must be one integer in 0 .. 2^32 - 1 per latent normal")
+        streams = np.ascontiguousarray(st.astype(np.uint32))
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError("joint_samples: every distribution must use the same quadrature")
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    if device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((M, n), dtype=torch.float64, device=dev)
+        u = torch.empty((M, n), dtype=torch.float64, device=dev) if return_uniforms else None
+        z = torch.empty((K, n), dtype=torch.float64, device=dev) if return_normals else None
+        torch.cuda.current_stream(dev).synchronize()         # the library writes them on its own stream
+        kind = _lib.DEVICE
+    else:
+        out = np.empty((M, n))
+        u = np.empty((M, n)) if return_uniforms else None
+        z = np.empty((K, n)) if return_normals else None
+        kind = _lib.HOST
+    _lib.check(_lib.lib().mlmc_density_sample_joint_batch(
+        M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()),
+        int(degs.pop()), K, _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, _lib.SAMPLE_ANTITHETIC if antithetic else 0,
+        _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
+    extra = tuple(v for v, want in ((u, return_uniforms), (z, return_normals)) if want)
+    return (out,) + extra if extra else out
+
+
 def _rvs(dist, n, seed, stream, first, antithetic, device):
     """the B = 1 call of `samples`"""
     return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device)[0]

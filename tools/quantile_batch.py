@@ -54,8 +54,16 @@ each; B x R1 x n = 1 x {9, 25, 64} x 10^7, 64 x 25 x 10^6 and 3600 x 25 x 10^3 d
   speedup_wall / speedup_kernel                 the route without the entry over the entry, from the means
   ks_samples / ks_rand_quantiles                Kolmogorov distance of the first 10^5 draws of problem 0 (or all its draws) from
                                                 cdfs_on_rule, a sanity check of both routes
+--joint: simple_distribution.joint_samples(..., device=True) against (a) samples (independent draws) at
+the same shape and (b) the route without the entry: torch.randn, torch.matmul with the factor, torch.special.ndtr and
+simple_distribution.quantiles on the device uniforms; the three take turns after a warm-up call each; M x R1 x n = 12 x 25 x 10^6,
+64 x 25 x 10^6, 256 x 25 x 10^5 with K = M, and 12 x 25 x 10^6 with K = 3 (--config M,R1,n,K with --joint: that shape alone):
+  joint_ms / samples_ms / torch_quantiles_ms    wall time of the whole route up to a device synchronise, [min, mean, max]
+  joint_kernel_ms / samples_kernel_ms / quantiles_kernel_ms   HIP-event time of one call's point kernels (the joint entry's normals,
+                                                uniforms and sampling kernels together; torch's kernels are not in the third)
+  joint_over_samples_wall / torch_over_joint_wall   ratios of the mean wall times
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
-                                                             [--tails | --divergences | --moments | --samples] [--reps K]"""
+                                                             [--tails | --divergences | --moments | --samples | --joint] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -336,6 +344,62 @@ def samples_shape(B, R1, n, reps):
                 ks_rand_quantiles=round(ks(parent_route()), 5), all_success=ok)
 
 
+def joint_shape(M, R1, n, K, reps):
+    """joint_samples(device=True) against (a) samples (independent draws) and (b) the route without the joint entry: torch.randn,
+    torch.matmul with the factor, torch.special.ndtr, quantiles on the device uniforms; the routes take turns in one process"""
+    distrs, ok = mixtures(M, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    rng = np.random.default_rng(7)
+    if K == M:
+        A = rng.standard_normal((M, M + 3))
+        c = A @ A.T
+        d = 1.0 / np.sqrt(np.diag(c))
+        factor = sd.correlation_factor(c * d[:, None] * d[None, :])[0]
+    else:
+        factor = rng.standard_normal((M, K))
+        factor = np.ascontiguousarray(factor / np.sqrt(np.sum(factor * factor, axis=1))[:, None])
+    factor_dev = torch.as_tensor(factor, device="cuda")
+    seed = [1000 * M + R1]
+
+    def joint_route():
+        seed[0] += 1
+        x = sd.joint_samples(distrs, n, seed[0], factor=factor, device=True)
+        torch.cuda.synchronize()
+        return x
+
+    def independent_route():
+        seed[0] += 1
+        x = sd.samples(distrs, n, seed[0], device=True)
+        torch.cuda.synchronize()
+        return x
+
+    def torch_route():
+        z = torch.randn(K, n, dtype=torch.float64, device="cuda")
+        u = torch.special.ndtr(torch.matmul(factor_dev, z)).clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+        x = sd.quantiles(distrs, list(u))
+        torch.cuda.synchronize()
+        return x
+    routes = (joint_route, independent_route, torch_route)
+    for fn in routes:
+        fn()
+    wall, kern = [[] for _ in routes], [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    mean = lambda t: sum(t) / len(t)
+    return dict(M=M, R1=R1, n=n, K=K, joint_ms=span(wall[0]), samples_ms=span(wall[1]), torch_quantiles_ms=span(wall[2]),
+                joint_kernel_ms=span(kern[0]), samples_kernel_ms=span(kern[1]), quantiles_kernel_ms=span(kern[2]),
+                joint_over_samples_wall=round(mean(wall[0]) / mean(wall[1]), 3), torch_over_joint_wall=round(mean(wall[2]) / mean(wall[0]), 3),
+                all_success=ok)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -367,12 +431,21 @@ def main():
     ap.add_argument("--divergences", action="store_true", help="divergences against host sums and quad (DESIGN.md section 3.5.10)")
     ap.add_argument("--moments", action="store_true", help="density_moments against host sums (DESIGN.md section 3.5.11)")
     ap.add_argument("--samples", action="store_true", help="samples against torch.rand + quantiles (DESIGN.md section 3.5.12)")
+    ap.add_argument("--joint", action="store_true", help="joint_samples against samples and torch.randn + matmul + ndtr + quantiles "
+                                                         "(DESIGN.md section 3.5.13)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.joint:
+        shapes = [(12, 25, 1_000_000, 12), (64, 25, 1_000_000, 64), (256, 25, 100_000, 256), (12, 25, 1_000_000, 3)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 10_000, 4)]
+        out["joint"] = [joint_shape(M, R1, n, K, a.reps) for M, R1, n, K in shapes]
     elif a.samples:
         shapes = [(1, 9, 10_000_000), (1, 25, 10_000_000), (1, 64, 10_000_000), (64, 25, 1_000_000), (3600, 25, 1_000)]
         if a.config:
