@@ -40,7 +40,7 @@ extern "C" {
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
-                              *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch */
+                              *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -474,11 +474,37 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
                                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                     int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
                                     int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
+/* Normal scores of stored samples under the densities of M problems in one call -- added within 8: the probability-integral
+ * transform followed by normcdfinv, the step between the fitted marginals and a correlation of the Gaussian copula
+ * (mlmc_density_sample_joint_batch).  Problems, rule, table, masses and Fhat_m are those of mlmc_density_cdf_batch (lambda / sigma
+ * [M][R1max], domain [a[m], b[m]], n_intervals, gauss_degree; 0 = 64 and 21).  fine and coarse are DEVICE arrays [M][ld_in] of
+ * which n columns are used, the component-major chunk layout of mlmc_accum_push; coarse may be NULL (level 0), then z_coarse and
+ * u_coarse are ignored.  z_fine / z_coarse are DEVICE arrays [M][ld_out]; u_fine / u_coarse (may be NULL) have the same layout;
+ * mass_out [M] host (may be NULL) receives the masses.  For component m and a value x of its row:
+ *   z = u = NaN if x is NaN, if the problem's mass is not finite and positive, if one of its effective coefficients is NaN (the
+ *     rule of mlmc_density_sample_batch), or if x lies outside the OPEN interval (a[m], b[m]): the end points themselves drop;
+ *   otherwise u = Fhat_m(x), bit for bit the value of mlmc_density_cdf_batch for the same problem, rule and x, and
+ *     z = normcdfinv(min(max(u, 2^-53), 1 - 2^-53)), the clamp of mlmc_density_sample_joint_batch (|z| <= 8.21); a u that is NaN
+ *     because the density left its basis' domain inside (a, b) gives z = NaN.
+ * Values outside the domain drop and are not clamped: the densities were fitted to the in-domain samples alone (the moment
+ * functions mask the rest), so u is uniform on exactly those, and a NaN in any row of a column drops the sample pair in the
+ * component-covariance accumulator.  The test compares the raw value with a and b; the mask of the moment functions compares the
+ * transformed value with the reference domain, so at a boundary ulp the two may count a sample differently.  A value depends on
+ * (problem m, rule, x) alone: not on M, on the row's position, on n, on ld_in / ld_out, on whether coarse is present or on the
+ * launch geometry.  An output array may overlap neither an input array nor another output array (an error of the call, as are
+ * a null array, M < 0, n < 0, ld_in < n, ld_out < n and a bad rule); errors of one problem name it as in mlmc_density_cdf_batch.
+ * M = 0 is a no-op, n = 0 a no-op that still returns the masses when asked.  One thread owns the fine and the coarse value of a
+ * column (without coarse: two columns), no atomics; one host wait. */
+int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                              const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *fine,
+                              const double *coarse, int64_t n, int64_t ld_in, double *z_fine, double *z_coarse, int64_t ld_out,
+                              double *u_fine, double *u_coarse, double *mass_out);
 /* HIP-event time (ms) and number of the point kernels (quantile, CDF and sampling kernels, without the table kernels and copies)
  * that mlmc_density_cdf_batch / mlmc_density_quantiles_batch / mlmc_density_tail_means_batch / mlmc_density_sample_batch /
- * mlmc_density_sample_joint_batch have launched since the last call of this function; resets both.  A tail-means call counts its
- * quantile kernel and its tail kernel together as one launch per group; a sampling call counts its sampling kernel, one launch per
- * group; a joint sampling call counts its normals, uniforms and sampling kernels together as one launch per block and group. */
+ * mlmc_density_sample_joint_batch / mlmc_density_scores_batch have launched since the last call of this function; resets both.  A
+ * tail-means call counts its quantile kernel and its tail kernel together as one launch per group; a sampling call counts its
+ * sampling kernel, one launch per group; a joint sampling call counts its normals, uniforms and sampling kernels together as one
+ * launch per block and group; a scores call counts its scores kernels, one launch per group. */
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */

@@ -23,6 +23,9 @@
 //                   the next when its current one has ended (QInversion), so a slow draw holds up one lane, not its wave;
 //                   the instances with U_IN (mlmc_density_sample_joint_batch) read the uniforms that copula.hip's kernels have
 //                   made (u = clamp(normcdf(F z)), a Gaussian copula over the problems) instead of making them
+//   k_q_scores    : normal scores normcdfinv(clamp(Fhat(x))) of stored samples (mlmc_density_scores_batch): one workgroup per
+//                   (problem, run of columns) of the component-major arrays, LDS staging as k_q_sample, a lane owns the fine and
+//                   the coarse value of a column as two interleaved chains of k_q_cdf's partial-cell rule
 // Tail means (expected shortfall, mlmc_density_tail_means_batch): with A_j / B_j the cell sums of (t - a) rho / (b - t) rho on the
 // nodes of C_j, V the forward prefix of the A_j, S and W the backward suffixes of the C_j and B_j,
 //     lower(x) = a + (V_j + A(e_j, x)) / (P_j + I(e_j, x)),   upper(x) = b - (W_{j+1} + B(x, e_{j+1})) / (S_{j+1} + I(x, e_{j+1})).
@@ -48,6 +51,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "copula.hpp"
@@ -448,6 +452,70 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
             }
         }
     });
+}
+
+constexpr int Q_SCORE_THREADS = 256;
+
+// Normal scores z = normcdfinv(clamp(Fhat(x))) of stored samples (mlmc_density_scores_batch): problem = blockIdx.x = row of the
+// component-major arrays, blockIdx.y = a run of columns from c0 on.  LDS as in k_q_sample: Gauss nodes | weights | coefficients
+// (COEF_LDS) | P row (ROW_LDS), staged once per workgroup and read as broadcasts.  A lane owns TWO values and walks their
+// partial-cell rules as two interleaved chains (density_integral2), so one chain's latency hides behind the other's: with a
+// coarse array the fine and the coarse value of its column, without one the fine values of its column and of the column one
+// workgroup width further on.  Consecutive lanes take consecutive columns of a row: loads and stores are coalesced.  Every kept
+// value costs one partial-cell rule, so there are no lane lists; a value that is not kept rides along at x = a and is discarded.
+// The kernel has no loop over columns: normcdfinv sits behind the integrals' loop nest, not inside a loop that would keep its
+// constants in registers (copula.hip).  The arithmetic of u is k_q_cdf's (q_cell_of, q_edge, density_integral's chain): the same bits.
+template <bool COEF_LDS, bool ROW_LDS>
+__global__ __launch_bounds__(Q_SCORE_THREADS) void k_q_scores(const QProb *__restrict__ probs, const QDraw *__restrict__ draws, int nint,
+                                                              const double *__restrict__ coef, const double *__restrict__ tab,
+                                                              const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
+                                                              const double *__restrict__ fine, const double *__restrict__ coarse,
+                                                              int64_t c0, int64_t n, int64_t ld_in, double *__restrict__ z_fine,
+                                                              double *__restrict__ z_coarse, int64_t ld_out, double *__restrict__ u_fine,
+                                                              double *__restrict__ u_coarse) {
+    extern __shared__ __attribute__((aligned(16))) double q_score_lds[];
+    const QProb P = probs[blockIdx.x];
+    double *gx = q_score_lds, *gw = gx + deg, *cl = gw + deg, *rl = cl + (COEF_LDS ? P.n_coef : 0);
+    for (int k = threadIdx.x; k < deg; k += blockDim.x) {
+        gx[k] = nodes[k];
+        gw[k] = wts[k];
+    }
+    const double *c = coef + P.c_off, *row = tab + (int64_t)blockIdx.x * (nint + 1);
+    if constexpr (COEF_LDS) {
+        for (int r = threadIdx.x; r < P.n_coef; r += blockDim.x) cl[r] = c[r];
+        c = cl;
+    }
+    if constexpr (ROW_LDS) {
+        for (int j = threadIdx.x; j <= nint; j += blockDim.x) rl[j] = row[j];
+        row = rl;
+    }
+    __syncthreads();
+    const bool pair = coarse != nullptr;
+    const int64_t t0 = c0 + (int64_t)blockIdx.y * (pair ? 1 : 2) * blockDim.x + threadIdx.x, t1 = pair ? t0 : t0 + blockDim.x;
+    if (t0 >= n) return;
+    const bool have1 = t1 < n;
+    const int64_t in_row = (int64_t)blockIdx.x * ld_in, out_row = (int64_t)blockIdx.x * ld_out;
+    const double v0 = fine[in_row + t0], v1 = have1 ? (pair ? coarse : fine)[in_row + t1] : __builtin_nan("");
+    const double T = row[nint];
+    const bool ok = T > 0.0 && T < __builtin_inf() && !draws[blockIdx.x].nan_coef;
+    const bool keep0 = ok && v0 > P.a && v0 < P.b, keep1 = ok && v1 > P.a && v1 < P.b;      // false for NaN
+    const double x0 = keep0 ? v0 : P.a, x1 = keep1 ? v1 : P.a;
+    const double h = (P.b - P.a) / (double)nint;
+    const int j0 = q_cell_of(P, h, nint, x0), j1 = q_cell_of(P, h, nint, x1);
+    double i0, i1;
+    with_kind(P.bp.kind, [&](auto K) {
+        density_integral2<decltype(K)::value>(P.bp, c, P.n_coef, q_edge(P, h, nint, j0), x0, q_edge(P, h, nint, j1), x1, gx, gw, deg, i0, i1);
+    });
+    const double u0 = keep0 ? (row[j0] + i0) / T : __builtin_nan(""), u1 = keep1 ? (row[j1] + i1) / T : __builtin_nan("");
+    // a u that is NaN (the density left its basis' domain) stays NaN: fmax would turn it into the clamp's end
+    const double s0 = normcdfinv(fmin(fmax(u0, 0x1p-53), 1.0 - 0x1p-53)), s1 = normcdfinv(fmin(fmax(u1, 0x1p-53), 1.0 - 0x1p-53));
+    z_fine[out_row + t0] = u0 == u0 ? s0 : u0;
+    if (u_fine) u_fine[out_row + t0] = u0;
+    if (have1) {
+        (pair ? z_coarse : z_fine)[out_row + t1] = u1 == u1 ? s1 : u1;
+        double *u_second = pair ? u_coarse : u_fine;
+        if (u_second) u_second[out_row + t1] = u1;
+    }
 }
 
 // one pair of a divergences call: problems `first` (p) and `second` (q) on [lo, hi]; three doubles wide, staged as such
@@ -874,17 +942,29 @@ struct QSampleLaunch {
         gy = (unsigned)std::clamp<int64_t>((n_max + th * list / 2) / (th * list), 1, 65535);
     }
 };
-// u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch)
-static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in) {
+// What a workgroup of k_q_sample / k_q_scores stages in LDS for the problems of a call: the rule always, the coefficients if every
+// problem has at most Q_SAMPLE_MAX_COEF, and then the P row if all of it fits into Q_SAMPLE_LDS_BYTES
+struct QLdsPlan {
+    bool coef_lds, row_lds;
+    size_t bytes;
+};
+static QLdsPlan q_lds_plan(const QSetup &S, int nint, int deg) {
     int max_coef = 0;
     for (const QProb &p : S.probs) max_coef = std::max(max_coef, p.n_coef);
     const bool coef_lds = max_coef <= Q_SAMPLE_MAX_COEF;
     const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)), lds_row = sizeof(double) * ((size_t)nint + 1);
     const bool row_lds = coef_lds && lds_head + lds_row <= Q_SAMPLE_LDS_BYTES;
+    return QLdsPlan{coef_lds, row_lds, lds_head + (row_lds ? lds_row : 0)};
+}
+
+// u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch)
+static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in) {
+    const QLdsPlan plan = q_lds_plan(S, nint, deg);
+    const bool coef_lds = plan.coef_lds, row_lds = plan.row_lds;
     QSampleLaunch L;
     if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
     else L.kernel = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
-    L.lds_bytes = lds_head + (row_lds ? lds_row : 0);
+    L.lds_bytes = plan.bytes;
     int resident = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, L.kernel, Q_SAMPLE_THREADS, L.lds_bytes) == hipSuccess && resident > 0)
         L.waves_per_cu = (int64_t)resident * (Q_SAMPLE_THREADS / 64);
@@ -1092,6 +1172,101 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
         MLMC_HIP_CHECK(hipGetLastError());
     }
     if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)M * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
+    for (size_t k = 0; k < timed; ++k) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
+        tm.ms += ms;
+        ++tm.launches;
+    }
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+// mlmc_density_scores_batch: normal scores of the stored samples of M problems, device arrays [M][ld] in place.  Table and masses
+// are those of q_on_rule's CDF branch.
+static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                    const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *fine, const double *coarse,
+                    int64_t n, int64_t ld_in, double *z_fine, double *z_coarse, int64_t ld_out, double *u_fine, double *u_coarse,
+                    double *mass_out) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (M < 0) return fail(std::string(fn) + ": M < 0");
+    if (M == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (n < 0) return fail(std::string(fn) + ": n < 0");
+    if (ld_in < n || ld_out < n) return fail(std::string(fn) + ": ld_in and ld_out must be at least n");
+    if (ld_in > INT64_MAX / 8 / M || ld_out > INT64_MAX / 8 / M) return fail(std::string(fn) + ": M * ld overflows int64");
+    QSetup S;
+    const std::vector<int64_t> counts((size_t)M, n);
+    if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
+    std::vector<QDraw> draws;
+    const QSampling none = {0, nullptr, nullptr, 0, nullptr};                      // of the table, this entry reads nan_coef alone
+    if (q_draws(fn, S, none, draws)) return 1;
+    if (!coarse) z_coarse = u_coarse = nullptr;
+    if (n > 0 && (!fine || !z_fine || (coarse && !z_coarse))) return fail(std::string(fn) + ": null argument");
+    if (n == 0 && !mass_out) return 0;
+    if (n > 0) {
+        // the bytes an array [M][ld] with n columns used spans; an output may overlap neither an input nor another output
+        const auto span = [&](const double *p, int64_t ld) {
+            return std::pair<uintptr_t, uintptr_t>((uintptr_t)p, (uintptr_t)p + (p ? sizeof(double) * (uintptr_t)((M - 1) * ld + n) : 0));
+        };
+        const std::pair<uintptr_t, uintptr_t> in[2] = {span(fine, ld_in), span(coarse, ld_in)};
+        const double *outs[4] = {z_fine, z_coarse, u_fine, u_coarse};
+        for (int i = 0; i < 4; ++i) {
+            if (!outs[i]) continue;
+            const auto o = span(outs[i], ld_out);
+            for (int k = 0; k < 2; ++k)
+                if ((k == 0 || coarse) && o.first < in[k].second && in[k].first < o.second)
+                    return fail(std::string(fn) + ": an output array overlaps an input array");
+            for (int k = 0; k < i; ++k) {
+                if (!outs[k]) continue;
+                const auto q = span(outs[k], ld_out);
+                if (o.first < q.second && q.first < o.second) return fail(std::string(fn) + ": two output arrays overlap");
+            }
+        }
+    }
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    hipStream_t st = rt().stream;
+    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
+    const int64_t plane = (int64_t)G * (nint + 1);
+    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double));
+    QBlock K;
+    if (q_stage(S, deg, {n_draw}, {(size_t)M, (size_t)plane}, {(size_t)M}, K)) return 1;
+    if (K.upload({(const double *)draws.data()}, n_draw)) return 1;
+    const QDraw *d_draws = (const QDraw *)K.d_in[0];
+    double *d_mass = K.d[0], *d_tab = K.d[1];
+    const QLdsPlan plan = q_lds_plan(S, nint, deg);
+    const auto kernel = plan.row_lds ? k_q_scores<true, true> : plan.coef_lds ? k_q_scores<true, false> : k_q_scores<false, false>;
+    const size_t lds_bytes = plan.bytes;
+    const int64_t wg_cols = (coarse ? 1 : 2) * Q_SCORE_THREADS, launch_cols = 65535 * wg_cols;     // a grid has 65535 blocks in y
+    QTiming &tm = q_timing();
+    size_t timed = 0;
+    for (int g0 = 0; g0 < M; g0 += G) {
+        const int np_g = std::min(G, M - g0);
+        const int64_t n_cells = (int64_t)np_g * nint;
+        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
+                           K.gw, deg, d_tab, plane);
+        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
+                           d_mass + g0, (double *)nullptr);
+        if (n > 0) {
+            hipEvent_t e0, e1;
+            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            const int64_t in_off = (int64_t)g0 * ld_in, out_off = (int64_t)g0 * ld_out;
+            for (int64_t c0 = 0; c0 < n; c0 += launch_cols) {
+                const unsigned gy = (unsigned)((std::min(launch_cols, n - c0) + wg_cols - 1) / wg_cols);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)np_g, gy), dim3(Q_SCORE_THREADS), lds_bytes, st, K.probs + g0, d_draws + g0, nint,
+                                   K.coef, (const double *)d_tab, K.gx, K.gw, deg, fine + in_off, coarse ? coarse + in_off : nullptr, c0, n,
+                                   ld_in, z_fine + out_off, z_coarse ? z_coarse + out_off : nullptr, ld_out,
+                                   u_fine ? u_fine + out_off : nullptr, u_coarse ? u_coarse + out_off : nullptr);
+            }
+            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+        }
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
     if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
@@ -1325,6 +1500,15 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
     MLMC_API_GUARD;
     return q_joint("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
                    streams, first, n, flags, out, u_out, z_out, mass_out, mem_kind);
+}
+
+int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                              const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *fine,
+                              const double *coarse, int64_t n, int64_t ld_in, double *z_fine, double *z_coarse, int64_t ld_out,
+                              double *u_fine, double *u_coarse, double *mass_out) {
+    MLMC_API_GUARD;
+    return q_scores("mlmc_density_scores_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, fine, coarse, n, ld_in,
+                    z_fine, z_coarse, ld_out, u_fine, u_coarse, mass_out);
 }
 
 int mlmc_density_divergences_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,

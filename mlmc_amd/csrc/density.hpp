@@ -106,4 +106,22 @@ __device__ __forceinline__ double density_integral(const BasisParams &bp, const 
     return acc * half;
 }
 
+// density_integral over [a0, b0] and over [a1, b1] at once: node k of both in one step through density_value2, so that the two
+// chains of a node overlap.  Each integral is density_integral's chain of operations, hence so are its bits.
+template <int KIND>
+__device__ __forceinline__ void density_integral2(const BasisParams &bp, const double *__restrict__ c, int R, double a0, double b0,
+                                                  double a1, double b1, const double *__restrict__ nodes,
+                                                  const double *__restrict__ wts, int deg, double &i0, double &i1) {
+    const double half0 = 0.5 * (b0 - a0), mid0 = 0.5 * (b0 + a0), half1 = 0.5 * (b1 - a1), mid1 = 0.5 * (b1 + a1);
+    double acc0 = 0.0, acc1 = 0.0;
+    for (int k = 0; k < deg; ++k) {
+        double d0, d1;
+        density_value2<KIND>(bp, c, R, __builtin_fma(half0, nodes[k], mid0), __builtin_fma(half1, nodes[k], mid1), d0, d1);
+        acc0 = __builtin_fma(wts[k], d0, acc0);
+        acc1 = __builtin_fma(wts[k], d1, acc1);
+    }
+    i0 = acc0 * half0;
+    i1 = acc1 * half1;
+}
+
 }  // namespace mlmc

@@ -63,8 +63,9 @@ class _ComponentCovNode(qmod.Quantity):
     never materialised: estimate_mean sends the raw component values to the component-covariance accumulator."""
     _at_bottom = True
 
-    def __init__(self, quantity, shift, qtype):
+    def __init__(self, quantity, shift, qtype, scores=None):
         self._shift = shift
+        self._scores = scores
         self._moments_fn = None
         super().__init__(quantity_type=qtype, input_quantities=[quantity], operation=self._eval)
 
@@ -73,9 +74,32 @@ class _ComponentCovNode(qmod.Quantity):
                                   "estimate_mean(component_covariance(...))")
 
 
-def component_covariance(quantity, shift=None):
+# Bound of the score workspace of component_covariance(scores=...): the fine and coarse scores of one column block (the
+# counterpart of Q_JOINT_BYTES in mlmc_amd/csrc/density.hip).  A level is processed in blocks of a FIXED number of columns, so
+# that the same input gives the same bits; MLMC_SCORE_BLOCK_COLUMNS in the environment, read per estimate, overrides the
+# number of columns (a test aid: the sums then differ by the rounding of another order of addition).
+SCORE_BLOCK_BYTES = 64 << 20
+
+
+def score_block_columns(n_comp):
+    """columns of a score block for `n_comp` components (plus the row of ones): whole tiles of 64 within SCORE_BLOCK_BYTES"""
+    env = int(os.environ.get("MLMC_SCORE_BLOCK_COLUMNS", "0") or 0)
+    if env > 0:
+        return env
+    return max(64, SCORE_BLOCK_BYTES // (2 * 8 * (int(n_comp) + 1)) // 64 * 64)
+
+
+def component_covariance(quantity, shift=None, scores=None):
     """Quantity of qtype ArrayType((M, M)) whose estimate_mean is the multilevel covariance between the M scalar components
     of `quantity` (row order: as Estimate.construct_densities documents -- the qtype flattened from the outside in).
+
+    scores = a list of M distributions with multipliers (tool.simple_distribution, one quadrature): the components enter not as
+    they are but as their NORMAL SCORES z_m = Phi^-1(Fhat_m(x_m)) under these marginals (mlmc_density_scores_batch), followed by
+    a row of ones, so the qtype is ArrayType((M + 1, M + 1)): entry (i, j), i, j < M, is the multilevel second moment of the
+    scores, row / column M their multilevel means and entry (M, M) is 1.  estimate_mean transforms each (fine, coarse) pair on the
+    device right before the push, in column blocks of score_block_columns(M) columns; the scores never leave the device and every
+    stored chunk is read once.  A value that is NaN or outside its marginal's open domain has the score NaN and drops the sample
+    pair like any NaN.  No shift can be given (the scores are centred if the marginals fit), and M <= 1023.
 
     Per level l and kept sample k, with f_k / c_k the fine / coarse component vectors and a the shift (the same for every
     level, fine and coarse, so the levels telescope):
@@ -93,6 +117,18 @@ def component_covariance(quantity, shift=None):
         raise TypeError("component_covariance: needs a Quantity whose samples are component values, got {}".format(
             type(quantity).__name__))
     M = int(quantity.size())
+    if scores is not None:
+        scores = list(scores)
+        if shift is not None:
+            raise ValueError("component_covariance: scores and shift exclude each other")
+        if len(scores) != M:
+            raise ValueError("component_covariance: {} score distributions for {} components".format(len(scores), M))
+        if M + 1 > engine.ComponentCovAccumulator.MAX_COMPONENTS:
+            raise ValueError("component_covariance: {} components, at most {} are supported with scores".format(
+                M, engine.ComponentCovAccumulator.MAX_COMPONENTS - 1))
+        if len({d.n_intervals for d in scores}) != 1 or len({d._gauss_degree for d in scores}) != 1:
+            raise ValueError("component_covariance: every distribution must use the same quadrature")
+        return _ComponentCovNode(quantity, None, qt.ArrayType(shape=(M + 1, M + 1), qtype=qt.ScalarType()), scores=scores)
     if M > engine.ComponentCovAccumulator.MAX_COMPONENTS:
         raise ValueError("component_covariance: {} components, at most {} are supported".format(
             M, engine.ComponentCovAccumulator.MAX_COMPONENTS))
@@ -1121,7 +1157,7 @@ def _estimate_mean(quantity, group, variance):
     elif isinstance(quantity, _ComponentCovNode):
         # the raw component values go to the component-covariance accumulator: M x M rows, i.e. M "rows per component"
         source, fn, mode = quantity._input_quantities[0], None, engine.LevelAccumulator.COMPONENT_COV
-        rows_per_comp = int(source.size())
+        rows_per_comp = int(source.size()) + (1 if quantity._scores is not None else 0)      # scores: plus the row of ones
     else:
         source, fn, mode, rows_per_comp = quantity, None, engine.LevelAccumulator.MOMENTS, 1
     rows_out = rows_per_comp                                      # rows per component the caller sees
@@ -1164,7 +1200,7 @@ def _estimate_mean(quantity, group, variance):
         if pair is None:
             return
         if acc is None:
-            n_comp = pair[0].shape[0]
+            n_comp = pair[0].shape[0] + (1 if scores is not None else 0)
             if pair[0].shape[-1] > 0:
                 assert n_comp * rows_out == quantity_vec_size
             acc = _acc_pool.take(fn, n_levels, mode, n_comp, mean_only=not variance)
@@ -1173,6 +1209,10 @@ def _estimate_mean(quantity, group, variance):
         if pair[0].shape[-1] == 0:                               # empty chunk / every sample deselected
             return
         fine, coarse = pair
+        if scores is not None:
+            flush_gathered()
+            push_scores(level_id, fine, coarse)
+            return
         if n_comp == 1:
             fine, coarse = fine[0], (None if coarse is None else coarse[0])
         # Resident chunks are gathered and handed over in ONE call of the C ABI at the end (mlmc_accum_estimate: reset +
@@ -1185,6 +1225,48 @@ def _estimate_mean(quantity, group, variance):
             return
         flush_gathered()
         acc.push(level_id, fine, coarse)
+
+    # component_covariance(scores=...): the pair becomes its normal scores plus a row of ones, block by block of a fixed number
+    # of columns, in one workspace per side that every block reuses (the library's stream orders a block's push before the
+    # next block's scores).  The row of ones sits behind the M score rows of a block, so it is rewritten when the width changes.
+    scores = quantity._scores if isinstance(quantity, _ComponentCovNode) else None
+    score_ws = {}
+
+    def push_scores(level_id, fine, coarse):
+        import torch
+        from .. import _lib
+        from ..tool import simple_distribution
+        M = len(scores)
+        if "head" not in score_ws:
+            score_ws["head"], score_ws["keep"] = simple_distribution._scores_problem_args(scores, "component_covariance")
+            score_ws["nb"] = score_block_columns(M)
+            score_ws["width"] = None
+        nb = score_ws["nb"]
+        dev = torch.device("cuda", _lib_device())
+
+        def on_device(x):
+            if x is None:
+                return None
+            if isinstance(x, np.ndarray):                            # a host chunk is uploaded first, once
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+            return x.contiguous()
+        fine, coarse = on_device(fine), on_device(coarse)
+        n = int(fine.shape[-1])
+        if "buf" not in score_ws:
+            score_ws["buf"] = torch.empty((2, (M + 1) * nb), dtype=torch.float64, device=dev)
+        buf = score_ws["buf"]
+        for c0 in range(0, n, nb):
+            nc = min(nb, n - c0)
+            z = [buf[side, :(M + 1) * nc].view(M + 1, nc) for side in range(2)]
+            if score_ws["width"] != nc:
+                _lib.check(_lib.lib().mlmc_synchronize())           # earlier pushes have read the workspace
+                z[0][M].fill_(1.0)
+                z[1][M].fill_(1.0)
+                score_ws["width"] = nc
+            torch.cuda.current_stream(dev).synchronize()            # the library reads and writes on its own stream
+            simple_distribution._scores_into(score_ws["head"], fine[:, c0:], None if coarse is None else coarse[:, c0:], nc, n,
+                                             z[0], None if coarse is None else z[1], nc)
+            acc.push(level_id, z[0], None if coarse is None else z[1])
 
     gathered = []
     pushed_directly = False

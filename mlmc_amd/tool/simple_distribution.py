@@ -500,6 +500,85 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
     return (out,) + extra if extra else out
 
 
+def _scores_problem_args(distrs, what):
+    """the problem arguments of mlmc_density_scores_batch for a list of distributions, ready to be splatted into the call:
+    (M, handles, r1, lam, sig, a, b, n_intervals, gauss_degree) as ctypes values, and the arrays that must outlive the call"""
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    handles, r1, lam, sig = _batch_problem_args(distrs)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    keep = (handles, r1, lam, sig, a, b)
+    head = (M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()),
+            int(degs.pop()))
+    return head, keep
+
+
+def _scores_into(head, fine, coarse, n, ld_in, z_fine, z_coarse, ld_out, u_fine=None, u_coarse=None):
+    """one call of mlmc_density_scores_batch on float64 device tensors (rows `ld_in` / `ld_out` apart, n columns used); the caller
+    has synchronised the stream that produced the inputs"""
+    _lib.check(_lib.lib().mlmc_density_scores_batch(*head, _lib.ptr(fine), _lib.ptr(coarse), int(n), int(ld_in), _lib.ptr(z_fine),
+                                                    _lib.ptr(z_coarse), int(ld_out), _lib.ptr(u_fine), _lib.ptr(u_coarse), None))
+
+
+def normal_scores(distrs, fine, coarse=None, device=False, return_uniforms=False):
+    """Normal scores of stored samples under their fitted marginals through ONE device call (mlmc_density_scores_batch): row m of
+    the result is z = Phi^-1(clamp(Fhat_m(x))) of row m of the input, Fhat_m of `cdfs_on_rule` (bit for bit its value), the clamp
+    to [2^-53, 1 - 2^-53] of `joint_samples`.  A value that is NaN or outside the OPEN domain of its distribution gives NaN (the
+    end points too): the densities were fitted to the in-domain samples alone, so the probability-integral transform is uniform
+    on exactly those, and a NaN drops the sample in `quantity_estimate.component_covariance`.  So do all values of a distribution
+    whose mass is not finite and positive or whose multipliers hold a NaN.  A score depends on (distribution, quadrature, value)
+    alone.  The correlation of these scores is what a Gaussian copula over the marginals takes (`Estimate.estimate_score_correlation`).
+    :param distrs: M distributions with multipliers, on one quadrature
+    :param fine: [M, n] values, a NumPy array or a float64 torch device tensor; host input is uploaded once
+    :param coarse: None or an array like `fine` (the coarse values of the same samples)
+    :param device: return float64 torch device tensors
+    :param return_uniforms: also return u = Fhat(x) (NaN where z is NaN)
+    :return: z_fine, or (z_fine, z_coarse) with `coarse`; with return_uniforms the uniforms follow in the same order"""
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError("normal_scores: no distributions")
+    if len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1:
+        raise ValueError("normal_scores: every distribution must use the same quadrature")
+
+    def checked(x, name):                                           # before anything touches the device
+        if hasattr(x, "data_ptr"):
+            if not x.is_cuda or str(x.dtype) != "torch.float64":
+                raise ValueError("normal_scores: {} must be a NumPy array or a float64 device tensor".format(name))
+        else:
+            x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[0] != M:
+            raise ValueError("normal_scores: {} must be [M, n] with M = {} distributions, got shape {}".format(name, M, tuple(x.shape)))
+        return x
+    fine = checked(fine, "fine")
+    coarse = None if coarse is None else checked(coarse, "coarse")
+    if coarse is not None and tuple(coarse.shape) != tuple(fine.shape):
+        raise ValueError("normal_scores: fine {} and coarse {} differ in shape".format(tuple(fine.shape), tuple(coarse.shape)))
+    import torch
+    head, _keep = _scores_problem_args(distrs, "normal_scores")                       # _keep: the arrays `head` points into
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def on_device(x):
+        return x.contiguous() if hasattr(x, "data_ptr") else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    f = on_device(fine)
+    c = None if coarse is None else on_device(coarse)
+    n = int(f.shape[1])
+    outs = [torch.empty_like(f) for _ in range((1 if c is None else 2) * (2 if return_uniforms else 1))]
+    torch.cuda.current_stream(f.device).synchronize()               # the library reads and writes on its own stream
+    zf, zc = outs[0], (None if c is None else outs[1])
+    uf = outs[-1 if c is None else -2] if return_uniforms else None
+    uc = outs[-1] if return_uniforms and c is not None else None
+    _scores_into(head, f, c, n, n, zf, zc, n, uf, uc)
+    return_list = outs if device else [t.cpu().numpy() for t in outs]
+    return return_list[0] if len(return_list) == 1 else tuple(return_list)
+
+
 def _rvs(dist, n, seed, stream, first, antithetic, device):
     """the B = 1 call of `samples`"""
     return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device)[0]

@@ -62,8 +62,15 @@ simple_distribution.quantiles on the device uniforms; the three take turns after
   joint_kernel_ms / samples_kernel_ms / quantiles_kernel_ms   HIP-event time of one call's point kernels (the joint entry's normals,
                                                 uniforms and sampling kernels together; torch's kernels are not in the third)
   joint_over_samples_wall / torch_over_joint_wall   ratios of the mean wall times
+--scores: normal_scores(device=True) of n (fine, coarse) pairs of M components (mlmc_density_scores_batch) against cdfs_on_rule on fine
+and on coarse followed by torch clamp and torch.special.ndtri, the routes taking turns in one process, for M x R1 x n = 12 x 25 x 10^6,
+64 x 25 x 10^6, 256 x 25 x 10^5 (--config M,R1,n,levels with --scores: that shape alone):
+  scores_ms / cdf_ndtri_ms                      wall time of the whole route up to a device synchronise, [min, mean, max]
+  scores_kernel_ms / cdf_kernel_ms              HIP-event time of one route's point kernels (k_q_scores; the two k_q_cdf launches)
+  score_correlation_ms / component_covariance_ms   levels > 0: Estimate.estimate_score_correlation against estimate_component_covariance
+                                                on a DeviceMemory store of `levels` levels of n pairs, end to end, mean wall time
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
-                                                             [--tails | --divergences | --moments | --samples | --joint] [--reps K]"""
+                                                             [--tails | --divergences | --moments | --samples | --joint | --scores] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -400,6 +407,69 @@ def joint_shape(M, R1, n, K, reps):
                 all_success=ok)
 
 
+def scores_shape(M, R1, n, reps, levels=0):
+    """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
+    device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
+    inputs here are all in-domain); the two routes take turns in one process.  levels > 0: in addition
+    Estimate.estimate_score_correlation against estimate_component_covariance on a DeviceMemory store of that many levels of n
+    pairs each, end to end."""
+    distrs, ok = mixtures(M, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    gen = torch.Generator(device="cuda").manual_seed(1000 * M + R1)
+    fine = (torch.rand(M, n, dtype=torch.float64, device="cuda", generator=gen) * 0.96 + 0.02) * (DOM[1] - DOM[0]) + DOM[0]
+    coarse = (fine + 0.05 * torch.randn(M, n, dtype=torch.float64, device="cuda", generator=gen)).clamp_(DOM[0] + 0.1, DOM[1] - 0.1)
+
+    def scores_route():
+        z = sd.normal_scores(distrs, fine, coarse, device=True)
+        torch.cuda.synchronize()
+        return z
+
+    def cdf_route():
+        z = [torch.special.ndtri(torch.stack(sd.cdfs_on_rule(distrs, list(x))).clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)) for x in (fine, coarse)]
+        torch.cuda.synchronize()
+        return z
+    routes = (scores_route, cdf_route)
+    results = [fn() for fn in routes]
+    # the two routes share Fhat bit for bit; normcdfinv and torch's ndtri agree to rounding
+    diff = max(float((a - b).abs().max()) for a, b in zip(*results))
+    del results
+    wall, kern = [[] for _ in routes], [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    mean = lambda t: sum(t) / len(t)
+    # one partial-cell rule per value: 21 nodes x (2 R1 + EXP_FLOPS) operations, as many_points counts them
+    deg = distrs[0]._gauss_degree
+    flops = 2.0 * M * n * deg * (2 * R1 + EXP_FLOPS)
+    out = dict(M=M, R1=R1, n=n, scores_ms=span(wall[0]), cdf_ndtri_ms=span(wall[1]), scores_kernel_ms=span(kern[0]),
+               cdf_kernel_ms=span(kern[1]), cdf_over_scores_wall=round(mean(wall[1]) / mean(wall[0]), 3),
+               scores_kernel_share_of_fp64_peak=round(flops / (mean(kern[0]) * 1e-3) / PEAK_FP64, 4), max_abs_diff_z=diff, all_success=ok)
+    if levels > 0:
+        from mlmc_amd.estimator import Estimate
+        from mlmc_amd.quantity import quantity_estimate as qe
+        from mlmc_amd.quantity.quantity import make_root_quantity
+        from mlmc_amd.quantity.quantity_spec import QuantitySpec
+        from mlmc_amd.sample_storage import DeviceMemory
+        spec = [QuantitySpec(name="q", unit="m", shape=(M, 1), times=[1], locations=['0'])]
+        dev = DeviceMemory()
+        dev.save_global_data(result_format=spec, level_parameters=[[0.5 ** l] for l in range(levels)])
+        for l in range(levels):
+            dev.set_level_samples(l, torch.stack([fine, coarse if l > 0 else torch.zeros_like(fine)], dim=-1))
+        qe.device_cache_clear()
+        est = Estimate(make_root_quantity(dev, spec)['q'], dev, Legendre(R1, DOM))
+        pdfs = [(d, None, None, None) for d in distrs]
+        est_ms = alternating([lambda: est.estimate_score_correlation(densities=pdfs), lambda: est.estimate_component_covariance()], reps)
+        out.update(levels=levels, score_correlation_ms=round(est_ms[0], 3), component_covariance_ms=round(est_ms[1], 3))
+    return out
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -433,12 +503,21 @@ def main():
     ap.add_argument("--samples", action="store_true", help="samples against torch.rand + quantiles (DESIGN.md section 3.5.12)")
     ap.add_argument("--joint", action="store_true", help="joint_samples against samples and torch.randn + matmul + ndtr + quantiles "
                                                          "(DESIGN.md section 3.5.13)")
+    ap.add_argument("--scores", action="store_true", help="normal_scores against cdfs_on_rule + torch ndtri, and estimate_score_correlation "
+                                                          "against estimate_component_covariance (DESIGN.md section 3.5.14)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.scores:
+        shapes = [(12, 25, 1_000_000, 5), (64, 25, 1_000_000, 0), (256, 25, 100_000, 0)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 10_000, 2)]
+        out["scores"] = [scores_shape(M, R1, n, a.reps, levels) for M, R1, n, levels in shapes]
     elif a.joint:
         shapes = [(12, 25, 1_000_000, 12), (64, 25, 1_000_000, 64), (256, 25, 100_000, 256), (12, 25, 1_000_000, 3)]
         if a.config:
