@@ -40,7 +40,8 @@ extern "C" {
                               *    mlmc_density_quantiles_kernel_time, mlmc_level_diagnostics, mlmc_diag_merge,
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
-                              *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch */
+                              *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
+                              *    mlmc_density_sample_conditional_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -474,6 +475,40 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
                                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                     int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
                                     int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
+/* Seeded CONDITIONAL joint draws under the Gaussian copula, B sets of observed values at once -- added within 8.  The M problems
+ * are the UNOBSERVED components; problems, rule, table, Q_m, the latent normals z[k][j] (seed, streams, first, n, flags) and every
+ * argument up to `flags` are those of mlmc_density_sample_joint_batch.  With the conditional factor F [M][K] (host, row-major; the
+ * Schur-complement Cholesky block of the scores' correlation) and the conditional means shift [B][M] (host; NULL: zeros), draw j
+ * of problem m in set b is
+ *     x = Q_m(u),   u = min(max(normcdf(y), 2^-53), 1 - 2^-53),   y = shift[b][m] (+) acc,
+ *   acc the chain of the joint entry (k ascending in the groups of four of v_mfma_f64_16x16x4_f64, from 0) and (+) ONE fp64
+ *   addition rounded to nearest after the chain has ended.  x is bit for bit mlmc_density_quantiles_batch at p = u.  With a zero
+ *   shift and unit rows the entry gives the bits of mlmc_density_sample_joint_batch in u, x and z (0 + (-0) = +0 does not change
+ *   normcdf).
+ * Every entry of F must be finite and every row must satisfy sum_k F[m][k]^2 <= 1 + 1e-6; it need not be 1 (the conditional
+ * standard deviation of the score is at most 1) and a row of zeros is allowed: every draw of it is Q_m(clamp(normcdf(shift))).  A
+ * violation names the row.  Every shift must be finite; a violation names set and row.  Large shifts are fine: |shift| = 40 gives
+ * u = 2^-53 or 1 - 2^-53 exactly and a finite x.
+ * Layout: rows [M] (host int32, strictly increasing, 0 <= rows[m] < ld_rows; NULL: the identity) and ld_rows >= M.  Draw j of
+ * problem m in set b goes to out[((b * ld_rows) + rows[m]) * n + (j - first)]; u_out (may be NULL) has the same layout; rows that
+ * `rows` does not name are NOT touched (the caller fills them with the observed values).  out and u_out are host or device arrays
+ * by mem_kind, z_out [K][n] (may be NULL) too; mass_out [M] (may be NULL) is host.
+ * u[b][m][j] depends on (seed, streams, j, flag, row m of F, shift[b][m]) alone and x in addition on problem m and the rule: neither
+ * depends on B, on the position of a set, on M, on rows / ld_rows, on n, on first, on the blocks the draws are processed in or on
+ * the launch geometry.  The M tables, the normals and their launch are made once per block of draws for all sets; every set forms
+ * its tile of the product on the matrix cores and adds its shift.
+ * The block of draws is chosen so that the normals [K][nb] and the uniforms [B * M][nb] stay within 192 MiB
+ * (MLMC_JOINT_BLOCK_DRAWS as for the joint entry).  If a block of 64 draws alone exceeds that (B * M beyond about 3.9e5 rows) the
+ * call is an error that says to split the sets across calls, which changes no value.
+ * Argument errors, no-ops (M = 0; n = 0 still returns the masses), degenerate problems (a row of NaN draws in every set, u_out /
+ * z_out still written), the one host wait and the accounting of mlmc_density_quantiles_kernel_time (one launch per block and
+ * group) are those of the joint entry; B < 1, a rows array that is not strictly increasing within 0 .. ld_rows - 1, ld_rows < M
+ * and B * ld_rows * n beyond int64 are errors of the call.  No atomics. */
+int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                          const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                          int32_t gauss_degree, int32_t K, const double *factor, uint64_t seed, const uint32_t *streams,
+                                          int64_t first, int64_t n, int32_t flags, int32_t B, const double *shift, const int32_t *rows,
+                                          int32_t ld_rows, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
 /* Normal scores of stored samples under the densities of M problems in one call -- added within 8: the probability-integral
  * transform followed by normcdfinv, the step between the fitted marginals and a correlation of the Gaussian copula
  * (mlmc_density_sample_joint_batch).  Problems, rule, table, masses and Fhat_m are those of mlmc_density_cdf_batch (lambda / sigma

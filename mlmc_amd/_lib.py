@@ -103,6 +103,9 @@ SIGNATURES = {
                                             C.c_int32, _vp, _vp, _vp, C.c_int]),
     "mlmc_density_sample_joint_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_uint64,
                                                   _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_density_sample_conditional_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                                        C.c_uint64, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
+                                                        _vp, _vp, _vp, _vp, C.c_int]),
     "mlmc_density_scores_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, C.c_int64,
                                             _vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "mlmc_density_quantiles_kernel_time": (C.c_int, [_dp, _ip]),

@@ -1,5 +1,6 @@
-// The Gaussian copula of mlmc_density_sample_joint_batch on the device (gfx950): seeded latent normals and the copula uniforms
-// u = clamp(normcdf(F z)) that k_q_sample (density.hip) then inverts.  The host path is density.hip's (q_joint).
+// The Gaussian copula of mlmc_density_sample_joint_batch / mlmc_density_sample_conditional_batch on the device (gfx950): seeded
+// latent normals and the copula uniforms u = clamp(normcdf(F z)) (conditional: of shift + F z) that k_q_sample (density.hip) then
+// inverts.  The host paths are density.hip's (q_joint, q_conditional).
 //
 //   k_cop_normals  : Z[k][c] = normcdfinv(uniform of (seed, streams[k], first + c)), negated for the odd draws of an antithetic
 //                    call; one thread per element, consecutive lanes write consecutive draws
@@ -8,6 +9,8 @@
 //                    it and all 64 draws (4 accumulator tiles, 16 doubles per lane).  It walks K from 0 in panels of 32: the F panel
 //                    [64][32] and the Z panel [32][64] go to LDS with zeros beyond M, K and the draws of the call, then 8 steps of 4 k.
 //                    Row tile = blockIdx.y: row tiles beyond the first re-read the same Z panels from memory.
+//                    The instance with SHIFT (mlmc_density_sample_conditional_batch) has the set on blockIdx.z: every set forms the
+//                    product of its tile anew and adds its own shift in the epilogue.
 // Neither kernel loops over rows: the compiler would keep the constants of the inlined normcdfinv / normcdf in registers across
 // the loop (256 and 208 VGPRs instead of 24 and 114).
 // y[m][c] is the chain acc = mfma(F[m][4 s .. 4 s + 3], Z[4 s .. 4 s + 3][c], acc), s = 0, 1, ... from acc = 0: what it adds and in
@@ -40,13 +43,26 @@ __global__ __launch_bounds__(COP_NORMAL_THREADS) void k_cop_normals(uint64_t see
     Z[(int64_t)k * ldz + c] = (antithetic && (j & 1)) ? -z : z;
 }
 
+// SHIFT (mlmc_density_sample_conditional_batch): set = blockIdx.z; the epilogue adds shift[set * set_rows + row] to the finished
+// chain, one rounded addition, and the tile goes to rows set * set_rows + row of U.  A lane's four rows are its registers' rows for
+// every J, so it loads its four shifts once, ahead of the panels, and the epilogue waits for no memory.
+template <bool SHIFT>
 __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__restrict__ F, int M, int K, const double *__restrict__ Z,
-                                                              int64_t ldz, int64_t ncols, double *__restrict__ U, int64_t ldu) {
+                                                              int64_t ldz, int64_t ncols, double *__restrict__ U, int64_t ldu,
+                                                              const double *__restrict__ shift, int64_t set_rows) {
     __shared__ double fl[COP_TILE * COP_F_STRIDE];
     __shared__ double zl[COP_PANEL * COP_Z_STRIDE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t col0 = (int64_t)blockIdx.x * COP_TILE;
     const int row0 = blockIdx.y * COP_TILE;
+    [[maybe_unused]] double sh[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (SHIFT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = row0 + 16 * wave + (lane >> 4) + 4 * r;
+            if (row < M) sh[r] = shift[(int64_t)blockIdx.z * set_rows + row];
+        }
+    }
     v4f64 acc[COP_TILE / 16];
 #pragma unroll
     for (int J = 0; J < COP_TILE / 16; ++J) acc[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
@@ -87,7 +103,13 @@ __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__re
         for (int r = 0; r < 4; ++r) {
             const int row = row0 + 16 * wave + (lane >> 4) + 4 * r;
             const int64_t col = col0 + 16 * J + (lane & 15);
-            if (row < M && col < ncols) U[(int64_t)row * ldu + col] = fmin(fmax(normcdf(acc[J][r]), 0x1p-53), 1.0 - 0x1p-53);
+            if constexpr (SHIFT) {
+                if (row < M && col < ncols)
+                    U[((int64_t)blockIdx.z * set_rows + row) * ldu + col] =
+                        fmin(fmax(normcdf(__dadd_rn(sh[r], acc[J][r])), 0x1p-53), 1.0 - 0x1p-53);
+            } else {
+                if (row < M && col < ncols) U[(int64_t)row * ldu + col] = fmin(fmax(normcdf(acc[J][r]), 0x1p-53), 1.0 - 0x1p-53);
+            }
         }
 }
 
@@ -108,9 +130,23 @@ void cop_launch_uniforms(hipStream_t st, const double *F, int M, int K, const do
     for (int m0 = 0; m0 < M; m0 += rows) {
         const int Ml = std::min(M - m0, rows);
         const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE));
-        hipLaunchKernelGGL(k_cop_uniforms, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols, U + (int64_t)m0 * ldu,
-                           ldu);
+        hipLaunchKernelGGL(k_cop_uniforms<false>, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
+                           U + (int64_t)m0 * ldu, ldu, (const double *)nullptr, (int64_t)0);
     }
+}
+
+void cop_launch_uniforms_shifted(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                                 int64_t ldu, const double *shift, int B, int64_t set_rows) {
+    // set of a launch = blockIdx.z, row tile = blockIdx.y: more of either than a grid has go in several launches
+    constexpr int rows = 65535 * COP_TILE;
+    for (int b0 = 0; b0 < B; b0 += 65535)
+        for (int m0 = 0; m0 < M; m0 += rows) {
+            const int Ml = std::min(M - m0, rows);
+            const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE),
+                            (unsigned)std::min(B - b0, 65535));
+            hipLaunchKernelGGL(k_cop_uniforms<true>, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
+                               U + ((int64_t)b0 * set_rows + m0) * ldu, ldu, shift + (int64_t)b0 * set_rows + m0, set_rows);
+        }
 }
 
 }  // namespace mlmc

@@ -28,5 +28,9 @@ void cop_launch_normals(hipStream_t st, uint64_t seed, const uint32_t *streams, 
 // U[m * ldu + c] = clamp(normcdf(sum_k F[m * K + k] Z[k * ldz + c])), m < M, c < ncols (k_cop_uniforms); all device
 void cop_launch_uniforms(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
                          int64_t ldu);
+// U[(b * set_rows + m) * ldu + c] = clamp(normcdf(shift[b * set_rows + m] + sum_k F[m * K + k] Z[k * ldz + c])), b < B, m < M,
+// c < ncols (k_cop_uniforms<true>): the sum as above, then one rounded addition; all device
+void cop_launch_uniforms_shifted(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                                 int64_t ldu, const double *shift, int B, int64_t set_rows);
 
 }  // namespace mlmc

@@ -21,7 +21,8 @@
 //                   coefficients and P row staged in LDS once, the uniform of a draw made in registers by Philox4x32-10 from
 //                   (seed, stream, j), then k_q_quantile's inversion reading LDS; a lane walks its own list of draws and starts
 //                   the next when its current one has ended (QInversion), so a slow draw holds up one lane, not its wave;
-//                   the instances with U_IN (mlmc_density_sample_joint_batch) read the uniforms that copula.hip's kernels have
+//                   the instances with U_IN (mlmc_density_sample_joint_batch, and with SETS mlmc_density_sample_conditional_batch)
+//                   read the uniforms that copula.hip's kernels have
 //                   made (u = clamp(normcdf(F z)), a Gaussian copula over the problems) instead of making them
 //   k_q_scores    : normal scores normcdfinv(clamp(Fhat(x))) of stored samples (mlmc_density_scores_batch): one workgroup per
 //                   (problem, run of columns) of the component-major arrays, LDS staging as k_q_sample, a lane owns the fine and
@@ -387,14 +388,21 @@ constexpr int Q_SAMPLE_WAVES_PER_CU = 16;              // resident waves per CU 
 // U_IN (mlmc_density_sample_joint_batch): the uniforms are not made here but read, draw t of problem blockIdx.x from
 // u_in[blockIdx.x * u_ld + t], t < u_n (a block of the call's draws, the same count for every problem); `out` points at the
 // block's first draw.  seed, antithetic, u_out and the draws' first / stream are not used then.
-template <bool COEF_LDS, bool ROW_LDS, bool U_IN = false>
+// SETS (mlmc_density_sample_conditional_batch, with U_IN): set = blockIdx.z.  The set's uniforms are rows u_set further on in u_in
+// per set and its draws x_set elements further on in out; with u_out the draw's uniform goes there too, at the draw's place.
+template <bool COEF_LDS, bool ROW_LDS, bool U_IN = false, bool SETS = false>
 __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__restrict__ probs, const QDraw *__restrict__ draws, int nint,
                                                                const double *__restrict__ coef, const double *__restrict__ tab,
                                                                const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
                                                                uint64_t seed, int antithetic, double *__restrict__ out,
                                                                double *__restrict__ u_out, const double *__restrict__ u_in, int64_t u_ld,
-                                                               int64_t u_n) {
+                                                               int64_t u_n, int64_t u_set, int64_t x_set) {
     extern __shared__ double q_sample_lds[];
+    static_assert(U_IN || !SETS, "the sets of a call read their uniforms");
+    if constexpr (SETS) {
+        out += (int64_t)blockIdx.z * x_set;
+        if (u_out) u_out += (int64_t)blockIdx.z * x_set;
+    }
     const QProb P = probs[blockIdx.x];
     const int64_t n_draws = U_IN ? u_n : P.n;
     const int64_t t0 = (int64_t)blockIdx.y * blockDim.x;
@@ -426,7 +434,7 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
         [[maybe_unused]] const double *ur = nullptr;
         [[maybe_unused]] double u_next = 0.0;
         if constexpr (U_IN) {
-            ur = u_in + (int64_t)blockIdx.x * u_ld;
+            ur = u_in + ((SETS ? (int64_t)blockIdx.z * u_set : 0) + (int64_t)blockIdx.x) * u_ld;
             if (t < n_draws) u_next = ur[t];
         }
         while (busy || t < n_draws) {
@@ -435,6 +443,9 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
                 if constexpr (U_IN) {
                     u = u_next;
                     if (t + stride < n_draws) u_next = ur[t + stride];
+                    if constexpr (SETS) {
+                        if (u_out) u_out[P.x_off + t] = u;
+                    }
                 } else {
                     const uint64_t j = (uint64_t)(D.first + t);
                     u = q_uniform(seed, D.stream, antithetic ? j >> 1 : j);
@@ -782,7 +793,7 @@ struct QBlock {
     const QProb *probs;               // device
     const double *coef, *gx, *gw;     // device
     double *h_in[2], *d_in[2];        // staged point arrays: pinned and device side
-    double *d[5];                     // device only
+    double *d[6];                     // device only
     double *h[1];                     // pinned only
     size_t head_bytes, in_bytes;      // up to the end of the Gauss rule / of the staged arrays
     bool direct;
@@ -957,12 +968,16 @@ static QLdsPlan q_lds_plan(const QSetup &S, int nint, int deg) {
     return QLdsPlan{coef_lds, row_lds, lds_head + (row_lds ? lds_row : 0)};
 }
 
-// u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch)
-static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in) {
+// u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch); sets: the one that reads them per set
+// (mlmc_density_sample_conditional_batch)
+static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in, bool sets = false) {
     const QLdsPlan plan = q_lds_plan(S, nint, deg);
     const bool coef_lds = plan.coef_lds, row_lds = plan.row_lds;
     QSampleLaunch L;
-    if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
+    if (sets)
+        L.kernel = row_lds ? k_q_sample<true, true, true, true>
+                   : coef_lds ? k_q_sample<true, false, true, true> : k_q_sample<false, false, true, true>;
+    else if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
     else L.kernel = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
     L.lds_bytes = plan.bytes;
     int resident = 0;
@@ -1037,7 +1052,7 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
                 hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0,
                                    (const QDraw *)K.d_in[0] + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, smp->seed,
                                    (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower, (const double *)nullptr, (int64_t)0,
-                                   (int64_t)0);
+                                   (int64_t)0, (int64_t)0, (int64_t)0);
             } else {
                 hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts,
                                    K.coef, (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
@@ -1159,7 +1174,7 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
             L.geometry((int64_t)np_g * nc, nc, threads, gy);
             hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0, d_draws + g0, nint, K.coef,
                                (const double *)d_tab, K.gx, K.gw, deg, seed, 0, d_out + c0, (double *)nullptr,
-                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc);
+                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc, (int64_t)0, (int64_t)0);
             if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
             MLMC_HIP_CHECK(hipGetLastError());
             if (stage && z_out && g0 == 0)
@@ -1172,6 +1187,156 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
         MLMC_HIP_CHECK(hipGetLastError());
     }
     if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)M * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
+    for (size_t k = 0; k < timed; ++k) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
+        tm.ms += ms;
+        ++tm.launches;
+    }
+    meb_ws().trim(MEB_KEEP_BYTES);
+    return 0;
+}
+
+// mlmc_density_sample_conditional_batch: q_joint's draws for B sets at once, y = shift[b][m] + (F z)[m].  Table, masses, normals and
+// the chain of the product are those of q_joint and are made once per block for all sets; the uniforms U [B][M][nb] always live in
+// the workspace (k_cop_uniforms<true>, set on blockIdx.z), and the SETS instance of k_q_sample inverts them and writes draw and
+// uniform at row rows[m] of set b.  Host arrays are staged compactly ([B][M][n]) and come back in runs of consecutive rows, so
+// the rows that `rows` does not name are not touched.  No value depends on nb or on B.
+static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                         const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf,
+                         const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, int32_t B,
+                         const double *shift, const int32_t *rows, int32_t ld_rows, double *out, double *u_out, double *z_out,
+                         double *mass_out, int mem_kind) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (M < 0) return fail(std::string(fn) + ": M < 0");
+    if (M == 0) return 0;
+    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    if (flags & ~MLMC_SAMPLE_ANTITHETIC) return fail(std::string(fn) + ": unknown flag bits");
+    if (Kf < 1) return fail(std::string(fn) + ": K < 1");
+    if (!factor) return fail(std::string(fn) + ": null factor");
+    if (n < 0) return fail(std::string(fn) + ": n < 0");
+    if (first < 0) return fail(std::string(fn) + ": first < 0");
+    if (first > INT64_MAX - n) return fail(std::string(fn) + ": first + n overflows int64");
+    if (B < 1) return fail(std::string(fn) + ": B < 1");
+    if (ld_rows < M) return fail(std::string(fn) + ": ld_rows < M");
+    for (int m = 0; rows && m < M; ++m)
+        if (rows[m] < 0 || rows[m] >= ld_rows || (m > 0 && rows[m] <= rows[m - 1]))
+            return fail(std::string(fn) + ": rows must be strictly increasing within 0 .. ld_rows - 1 (entry " + std::to_string(m) + ")");
+    if (n > 0 && (int64_t)B * ld_rows > INT64_MAX / 8 / n) return fail(std::string(fn) + ": B * ld_rows * n overflows int64");
+    for (int m = 0; m < M; ++m) {
+        const double *row = factor + (size_t)m * Kf;
+        double ss = 0.0;
+        for (int k = 0; k < Kf; ++k) ss += row[k] * row[k];          // a value that is not finite makes the sum not finite
+        if (!std::isfinite(ss)) return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": an entry is not finite");
+        if (!(ss <= 1.0 + 1e-6))
+            return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": the sum of squares must be at most 1 + 1e-6");
+    }
+    for (int64_t i = 0; shift && i < (int64_t)B * M; ++i)
+        if (!std::isfinite(shift[i]))
+            return fail(std::string(fn) + ": shift of set " + std::to_string(i / M) + ", row " + std::to_string(i % M) + " is not finite");
+    const size_t BM = (size_t)B * (size_t)M;
+    if (sizeof(double) * 64 * (BM + (size_t)Kf) > Q_JOINT_BYTES)
+        return fail(std::string(fn) + ": the uniforms of B * M = " + std::to_string(BM) +
+                    " rows do not fit into the workspace even for a block of 64 draws; split the sets across calls (no value depends on B)");
+    QSetup S;
+    const std::vector<int64_t> counts((size_t)M, n);
+    if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
+    std::vector<QDraw> draws;
+    const QSampling no_streams = {seed, nullptr, nullptr, flags, nullptr};        // of the table, this entry reads nan_coef alone
+    if (q_draws(fn, S, no_streams, draws)) return 1;
+    if (n > 0 && !out) return fail(std::string(fn) + ": null argument");
+    if (n == 0 && !mass_out) return 0;
+    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
+    hipStream_t st = rt().stream;
+    const bool stage = mem_kind == MLMC_HOST && n > 0;
+    // where a set's draws go: rows[m] of the caller's device array [B][ld_rows][n], or row m of the compact staged one [B][M][n]
+    const int64_t x_set = (stage ? (int64_t)M : (int64_t)ld_rows) * n;
+    if (!stage && rows)
+        for (int m = 0; m < M; ++m) S.probs[m].x_off = (int64_t)rows[m] * n;
+    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
+    const int64_t plane = (int64_t)G * (nint + 1);
+    // the draws of a block: Z and U of a block within Q_JOINT_BYTES, whole tiles of the matrix kernel
+    int64_t nb = std::max<int64_t>(64, (int64_t)(Q_JOINT_BYTES / (sizeof(double) * (BM + (size_t)Kf))) / 64 * 64);
+    if (const char *env = std::getenv("MLMC_JOINT_BLOCK_DRAWS")) {
+        const long long v = std::atoll(env);
+        if (v > 0) nb = v;
+    }
+    nb = std::min(nb, std::max<int64_t>(n, 1));
+    const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out);
+    // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts
+    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
+    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sh = n > 0 ? BM : 0, n_in = n_draw + n_str + n_fac + n_sh;
+    std::vector<double> packed(n_in);
+    std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
+    if (n > 0) {
+        uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
+        for (int k = 0; k < Kf; ++k) sv[k] = streams ? streams[k] : (uint32_t)k;
+        std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
+        if (shift) std::memcpy(packed.data() + n_draw + n_str + n_fac, shift, sizeof(double) * n_sh);         // NULL: the zeros of `packed`
+    }
+    const size_t n_stage = stage ? BM * (size_t)n : 0;
+    QBlock K;
+    if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, n_stage, n > 0 ? BM * (size_t)nb : 0, z_ws ? (size_t)Kf * (size_t)nb : 0,
+                                u_out ? n_stage : 0},
+                {(size_t)M}, K))
+        return 1;
+    if (K.upload({packed.data()}, n_in)) return 1;
+    const QDraw *d_draws = (const QDraw *)K.d_in[0];
+    const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
+    const double *d_factor = K.d_in[0] + n_draw + n_str, *d_shift = d_factor + n_fac;
+    double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out, *U = K.d[3];
+    double *d_u = stage && u_out ? K.d[5] : u_out;
+    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, true);
+    QTiming &tm = q_timing();
+    size_t timed = 0;
+    for (int g0 = 0; g0 < M; g0 += G) {
+        const int np_g = std::min(G, M - g0);
+        const int64_t n_cells = (int64_t)np_g * nint;
+        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
+                           K.gw, deg, d_tab, plane);
+        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
+                           d_mass + g0, (double *)nullptr);
+        for (int64_t c0 = 0; c0 < n; c0 += nb) {
+            const int64_t nc = std::min(nb, n - c0);
+            double *Z = z_ws ? K.d[4] : z_out + c0;
+            const int64_t ldz = z_ws ? nb : n;
+            hipEvent_t e0, e1;
+            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            if (g0 == 0 || z_ws)               // a later group finds the normals of the block in the caller's array
+                cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
+            cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * nb, nb, d_shift + g0, B, M);
+            unsigned threads, gy;
+            L.geometry((int64_t)B * np_g * nc, nc, threads, gy);
+            for (int b0 = 0; b0 < B; b0 += 65535)         // set of a launch = blockIdx.z
+                hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy, (unsigned)std::min(B - b0, 65535)), dim3(threads), L.lds_bytes, st,
+                                   K.probs + g0, d_draws + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, seed, 0,
+                                   d_out + b0 * x_set + c0, d_u ? d_u + b0 * x_set + c0 : (double *)nullptr,
+                                   (const double *)(U + ((int64_t)b0 * M + g0) * nb), nb, nc, (int64_t)M, x_set);
+            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+            MLMC_HIP_CHECK(hipGetLastError());
+            if (stage && z_out && g0 == 0)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c0, sizeof(double) * n, Z, sizeof(double) * ldz, sizeof(double) * nc, (size_t)Kf,
+                                                hipMemcpyDeviceToHost, st));
+        }
+        MLMC_HIP_CHECK(hipGetLastError());
+    }
+    // a staged array comes back in runs of consecutive rows: run m0 .. m1 - 1 of every set in one strided copy
+    for (int m0 = 0, m1; stage && m0 < M; m0 = m1) {
+        for (m1 = m0 + 1; m1 < M && (rows ? rows[m1] == rows[m1 - 1] + 1 : true); ++m1) {}
+        const int64_t to = (int64_t)(rows ? rows[m0] : m0) * n, from = (int64_t)m0 * n;
+        const size_t width = sizeof(double) * (size_t)(m1 - m0) * (size_t)n, dpitch = sizeof(double) * (size_t)ld_rows * (size_t)n;
+        MLMC_HIP_CHECK(hipMemcpy2DAsync(out + to, dpitch, d_out + from, sizeof(double) * (size_t)x_set, width, (size_t)B,
+                                        hipMemcpyDeviceToHost, st));
+        if (u_out)
+            MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + to, dpitch, d_u + from, sizeof(double) * (size_t)x_set, width, (size_t)B,
+                                            hipMemcpyDeviceToHost, st));
+    }
     if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
@@ -1500,6 +1665,16 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
     MLMC_API_GUARD;
     return q_joint("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
                    streams, first, n, flags, out, u_out, z_out, mass_out, mem_kind);
+}
+
+int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                          const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                          int32_t gauss_degree, int32_t K, const double *factor, uint64_t seed, const uint32_t *streams,
+                                          int64_t first, int64_t n, int32_t flags, int32_t B, const double *shift, const int32_t *rows,
+                                          int32_t ld_rows, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return q_conditional("mlmc_density_sample_conditional_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor,
+                         seed, streams, first, n, flags, B, shift, rows, ld_rows, out, u_out, z_out, mass_out, mem_kind);
 }
 
 int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,

@@ -752,6 +752,28 @@ class Estimate:
         return ScoreCorrelation(corr, cov, cov_var, mean, var, np.asarray(r.n_samples, dtype=np.int64),
                                 np.asarray(r.n_rm_samples, dtype=np.int64))
 
+    def _copula_correlation(self, what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns):
+        """the correlation matrix of the normal scores that `corr` of sample_joint / sample_conditional stands for: None = the
+        Pearson correlation of the components, "scores" = estimate_score_correlation with the densities (constructed here if
+        need be), a matrix = itself.  :return: (corr, densities), densities as passed in unless "scores" had to construct them"""
+        if isinstance(corr, str):
+            if corr != "scores":
+                raise ValueError("{}: corr must be None, 'scores' or a correlation matrix, got {!r}".format(what, corr))
+            if densities is None:
+                densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+            corr = self.estimate_score_correlation(densities=densities).corr
+        elif corr is None:
+            cov, _ = self.estimate_component_covariance()
+            var = np.diag(cov)
+            bad = np.flatnonzero(~(np.isfinite(var) & (var > 0)))
+            if bad.size:
+                raise ValueError("{}: component {} has no positive finite variance estimate ({})".format(what, int(bad[0]),
+                                                                                                         var[bad[0]]))
+            sd = np.sqrt(var)
+            corr = cov / sd[:, None] / sd[None, :]
+            np.fill_diagonal(corr, 1.0)
+        return corr, densities
+
     def sample_joint(self, n, seed, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
                      antithetic=False, device=False):
         """Seeded JOINT draws of all scalar components of the quantity, in one batched device call
@@ -782,22 +804,7 @@ class Estimate:
         from .tool import simple_distribution
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("sample_joint: n must be a non-negative integer")
-        if isinstance(corr, str):
-            if corr != "scores":
-                raise ValueError("sample_joint: corr must be None, 'scores' or a correlation matrix, got {!r}".format(corr))
-            if densities is None:
-                densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
-            corr = self.estimate_score_correlation(densities=densities).corr
-        elif corr is None:
-            cov, _ = self.estimate_component_covariance()
-            var = np.diag(cov)
-            bad = np.flatnonzero(~(np.isfinite(var) & (var > 0)))
-            if bad.size:
-                raise ValueError("sample_joint: component {} has no positive finite variance estimate ({})".format(int(bad[0]),
-                                                                                                                  var[bad[0]]))
-            sd = np.sqrt(var)
-            corr = cov / sd[:, None] / sd[None, :]
-            np.fill_diagonal(corr, 1.0)
+        corr, densities = self._copula_correlation("sample_joint", corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         factor, _ = simple_distribution.correlation_factor(corr)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
@@ -805,6 +812,50 @@ class Estimate:
                                                   antithetic=antithetic, device=device)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return draws, success, factor @ factor.T
+
+    def sample_conditional(self, n, seed, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
+                           densities=None, first=0, antithetic=False, device=False):
+        """Seeded joint draws of the components that are not in `given`, CONDITIONAL on measured or fixed values of the others, in
+        one batched device call (tool.simple_distribution.conditional_samples): the marginals and the Gaussian copula of
+        `sample_joint`, with the scores of the given components fixed at Phi^-1(Fhat_o(x_o)).  Scenarios of the rest of a field
+        given the head at an observation well, of the rest of a series given its first steps.
+        :param given: mapping component index -> value, or -> array [B] for B sets of values at once (a what-if fan); the tables
+            of the marginals and the latent normals are made once for all sets
+        :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
+        :param densities: as in estimate_component_quantiles
+        :return: (samples, success [M], ConditionalFactorInfo): samples [M, n] for scalar values and [B, M, n] for arrays, rows
+            of given components hold the given values; the solver's verdict per component; the components that were drawn,
+            their conditional standard deviations in score space and what `correlation_factor` did to the matrix"""
+        from .tool import simple_distribution
+        if isinstance(n, bool) or int(n) != n or n < 0:
+            raise ValueError("sample_conditional: n must be a non-negative integer")
+        corr, densities = self._copula_correlation("sample_conditional", corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        distrs = [d[0] for d in densities]
+        observed = simple_distribution._parse_given("sample_conditional", given, len(distrs))[0]
+        cond = simple_distribution.conditional_factor(corr, observed)
+        draws = simple_distribution.conditional_samples(distrs, int(n), seed, given, factor_info=cond, first=first,
+                                                        antithetic=antithetic, device=device)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return draws, success, cond[2]
+
+    def estimate_conditional_quantiles(self, probs, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
+                                       densities=None):
+        """Quantiles of every component that is not in `given`, conditional on the given values of the others
+        (tool.simple_distribution.conditional_quantiles): medians and bands of the rest of the vector once some of it is known.
+        :param probs: probabilities, the same for every component
+        :param given, corr, densities: as in sample_conditional
+        :return: (q, success): q [q, len(probs)] for scalar values, [B, q, len(probs)] for arrays, row m = the m-th component
+            that is not given, ascending; success [M] bool, the solver's verdict per component"""
+        from .tool import simple_distribution
+        corr, densities = self._copula_correlation("estimate_conditional_quantiles", corr, densities, tol, reg_param,
+                                                   orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        q = simple_distribution.conditional_quantiles([d[0] for d in densities], probs, given, corr)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return q, success
 
     def estimate_component_shortfall(self, probs, tail="upper", tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                      densities=None):

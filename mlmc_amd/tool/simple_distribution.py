@@ -500,6 +500,223 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
     return (out,) + extra if extra else out
 
 
+ConditionalFactorInfo = collections.namedtuple("ConditionalFactorInfo", "unobserved s min_eig_in repaired")
+
+
+def conditional_factor(corr, observed, min_eig=1e-10):
+    """What conditioning a Gaussian copula on the components `observed` needs, on the host in NumPy.  With C' = F F^T of
+    `correlation_factor(corr, min_eig)` (repaired, unit diagonal), O = the observed components ascending, U the others ascending
+    and L = cholesky(C'[P, P]) for P = O ++ U in blocks L_OO, L_UO, L_UU, the scores of U given the scores z_O of O are normal with
+        mean  W z_O,  W = L_UO L_OO^-1 [q, p] (a triangular solve),   and factor  F_c = L_UU [q, q] (lower triangular),
+    so their covariance F_c F_c^T (the Schur complement C'_UU - C'_UO C'_OO^-1 C'_OU) does not depend on z_O.  Row m of F_c has
+    norm s_m in (0, 1], the conditional standard deviation of score m, and |L_UO[m]|^2 + s_m^2 = 1.
+    :param observed: distinct component indices in any order; may be empty: then W is [M, 0] and F_c the factor of
+        `correlation_factor` itself
+    :return: (W [q, p], F_c [q, q], ConditionalFactorInfo(unobserved [q], s [q], min_eig_in, repaired)), the last two those of
+        `correlation_factor`"""
+    factor, info = correlation_factor(corr, min_eig)
+    M = factor.shape[0]
+    observed = list(observed)
+    if any(isinstance(o, (bool, np.bool_)) or not isinstance(o, (int, np.integer)) for o in observed):
+        raise ValueError("conditional_factor: observed must hold component indices, got {!r}".format(observed))
+    obs = np.array(observed, dtype=np.int64).reshape(-1)
+    if np.any(obs < 0) or np.any(obs >= M):
+        raise ValueError("conditional_factor: observed component out of range 0 .. {}: {}".format(M - 1, obs.tolist()))
+    if np.unique(obs).size != obs.size:
+        raise ValueError("conditional_factor: observed components must be distinct: {}".format(obs.tolist()))
+    obs = np.sort(obs)
+    p = obs.size
+    if p == M:
+        raise ValueError("conditional_factor: every component is observed, nothing is left to condition")
+    unobs = np.setdiff1d(np.arange(M, dtype=np.int64), obs)
+    if p == 0:
+        w, fc = np.zeros((M, 0)), factor
+    else:
+        perm = np.concatenate([obs, unobs])
+        c = factor @ factor.T
+        c = 0.5 * (c + c.T)
+        low = np.linalg.cholesky(c[np.ix_(perm, perm)])
+        w = scipy.linalg.solve_triangular(low[:p, :p], low[p:, :p].T, lower=True, trans="T").T
+        fc = np.ascontiguousarray(low[p:, p:])
+    s = np.sqrt(np.sum(fc * fc, axis=1))
+    return np.ascontiguousarray(w), fc, ConditionalFactorInfo(unobs, s, info.min_eig_in, info.repaired)
+
+
+def _parse_given(what, given, M):
+    """(observed [p] ascending, values [p, B], every value a scalar?) of a mapping component -> scalar or array [B]; scalars next to
+    arrays stand for the same value in every set"""
+    if not hasattr(given, "items"):
+        raise ValueError(what + ": given must map component indices to values")
+    keys, vals = [], []
+    for k, v in given.items():
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise ValueError(what + ": a key of given must be a component index, got {!r}".format(k))
+        if not 0 <= int(k) < M:
+            raise ValueError(what + ": given names component {}, there are components 0 .. {}".format(int(k), M - 1))
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1:
+            raise ValueError(what + ": the value of component {} must be a scalar or a 1-D array, got shape {}".format(int(k), v.shape))
+        keys.append(int(k))
+        vals.append(v)
+    if len(set(keys)) != len(keys):
+        raise ValueError(what + ": given names a component twice")
+    if len(keys) == M:
+        raise ValueError(what + ": every component is given, nothing is left to condition")
+    sizes = {v.size for v in vals if v.ndim == 1}
+    if len(sizes) > 1:
+        raise ValueError(what + ": the arrays of given must share one length, got {}".format(sorted(sizes)))
+    scalar = not sizes
+    B = 1 if scalar else sizes.pop()
+    if B < 1:
+        raise ValueError(what + ": the arrays of given are empty")
+    order = np.argsort(keys) if keys else []
+    observed = np.array([keys[i] for i in order], dtype=np.int64)
+    values = np.empty((len(keys), B))
+    for row, i in enumerate(order):
+        values[row] = vals[i]
+    return observed, values, scalar
+
+
+def _conditioning(what, distrs, given, corr, cond):
+    """what the conditional entries share: (observed [p], values [p, B], scalar?, u_O [p, B], (W, F_c, info), mu [B, q]): the scores
+    of the given values through ONE `normal_scores` call and the conditional means W z_O on the host"""
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    observed, values, scalar = _parse_given(what, given, M)
+    if (corr is None) == (cond is None):
+        raise ValueError(what + ": exactly one of corr and the result of conditional_factor must be given")
+    if cond is None:
+        cond = conditional_factor(corr, observed)
+    w, fc, info = cond
+    w, fc = np.asarray(w, dtype=np.float64), np.ascontiguousarray(fc, dtype=np.float64)
+    p, q, B = observed.size, M - observed.size, values.shape[1]
+    if w.shape != (q, p) or fc.ndim != 2 or fc.shape[0] != q or fc.shape[1] < 1 \
+            or not np.array_equal(np.asarray(info.unobserved), np.setdiff1d(np.arange(M), observed)):
+        raise ValueError(what + ": the conditional factor does not belong to the components of given")
+    if p == 0:
+        return observed, values, scalar, np.empty((0, B)), (w, fc, info), np.zeros((B, q))
+    z, u = normal_scores([distrs[o] for o in observed], values, return_uniforms=True)
+    bad = np.argwhere(~np.isfinite(z))
+    if bad.size:
+        raise ValueError(what + ": the given value {!r} of component {} (set {}) is NaN or outside the open domain of its "
+                         "distribution".format(float(values[bad[0, 0], bad[0, 1]]), int(observed[bad[0, 0]]), int(bad[0, 1])))
+    return observed, values, scalar, u, (w, fc, info), np.ascontiguousarray((w @ z).T)
+
+
+def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, streams=None, first=0, antithetic=False, device=False,
+                        return_uniforms=False):
+    """Seeded joint draws of the components that are NOT in `given`, conditional on the given values of the others, under the
+    Gaussian copula of `joint_samples`; B sets of given values through ONE device call (mlmc_density_sample_conditional_batch).
+    The given values go to normal scores z_O (one `normal_scores` call); with (W, F_c) of `conditional_factor` the scores of the
+    other components are W z_O + F_c z, z the latent normals of `joint_samples` (same seed, streams, first, antithetic), and
+        x[b, m, j] = Q_m(clamp(Phi(mu[b, m] + (F_c z)[m, j]))),   mu[b] = W z_O[b].
+    The tables of the marginals, the normals and their launch are made once for all sets; no value depends on B or on the
+    position of a set.
+    :param given: mapping component index -> scalar, or -> array [B] (all arrays share B; a scalar next to arrays holds in every
+        set).  A value that is NaN or outside the open domain of its distribution is an error that names component and set.  An
+        empty mapping gives the draws of `joint_samples` bit for bit
+    :param corr: correlation matrix [M, M] of the normal scores of ALL components
+    :param factor_info: or the tuple `conditional_factor(corr, observed)` returned.  Exactly one of the two must be given
+    :param streams: one uint32 stream per latent normal (there are q = M - len(given)); default: stream k = k
+    :param return_uniforms: also return u shaped like the draws; rows of given components hold Fhat_o(x_o)
+    :return: draws [M, n] when every given value is a scalar, [B, M, n] otherwise: rows of the other components hold the draws, rows
+        of given components the given values exactly; float64 torch device tensors with device=True"""
+    what = "conditional_samples"
+    distrs = list(distrs)
+    M = len(distrs)
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(what + ": seed must be an integer in 0 .. 2^64 - 1")
+    n = int(_per_distribution_int(what, "n", n, 1)[0])
+    first = int(_per_distribution_int(what, "first", first, 1)[0])
+    _parse_given(what, given, M)                              # its errors come before anything touches the device
+    if M and (len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1):
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    observed, values, scalar, u_obs, (_, fc, info), mu = _conditioning(what, distrs, given, corr, factor_info)
+    unobs = np.ascontiguousarray(info.unobserved, dtype=np.int32)
+    q, K, B = unobs.size, fc.shape[1], values.shape[1]
+    if streams is not None:
+        st = np.asarray(streams)
+        if st.shape != (K,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
+            raise ValueError(what + ": streams must be one integer in 0 .. 2^32 - 1 per latent normal")
+        streams = np.ascontiguousarray(st.astype(np.uint32))
+    free = [distrs[m] for m in unobs]
+    handles, r1, lam, sig = _batch_problem_args(free)
+    a = np.ascontiguousarray([float(d.domain[0]) for d in free], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in free], dtype=np.float64)
+    if device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((B, M, n), dtype=torch.float64, device=dev)
+        u = torch.empty((B, M, n), dtype=torch.float64, device=dev) if return_uniforms else None
+        if observed.size:
+            out[:, observed.tolist(), :] = torch.from_numpy(np.ascontiguousarray(values.T)).to(dev)[:, :, None]
+            if u is not None:
+                u[:, observed.tolist(), :] = torch.from_numpy(np.ascontiguousarray(u_obs.T)).to(dev)[:, :, None]
+        torch.cuda.current_stream(dev).synchronize()         # the library writes the other rows on its own stream
+        kind = _lib.DEVICE
+    else:
+        out = np.empty((B, M, n))
+        u = np.empty((B, M, n)) if return_uniforms else None
+        out[:, observed, :] = values.T[:, :, None]
+        if u is not None:
+            u[:, observed, :] = u_obs.T[:, :, None]
+        kind = _lib.HOST
+    _lib.check(_lib.lib().mlmc_density_sample_conditional_batch(
+        q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
+        int(distrs[0].n_intervals), int(distrs[0]._gauss_degree), K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
+        _lib.SAMPLE_ANTITHETIC if antithetic else 0, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
+        _lib.ptr(u), None, None, kind))
+    if scalar:
+        out, u = out[0], (None if u is None else u[0])
+    return (out, u) if return_uniforms else out
+
+
+def _conditional_law(what, distrs, given, corr):
+    """(the distributions that are not given, mu [B, q], s [q], every given value a scalar?) of `conditional_quantiles` / `_cdfs`"""
+    distrs = list(distrs)
+    _, _, scalar, _, (_, _, info), mu = _conditioning(what, distrs, given, corr, None)
+    return [distrs[m] for m in info.unobserved], mu, np.asarray(info.s), scalar
+
+
+def conditional_quantiles(distrs, probs, given, corr):
+    """Quantiles of every component that is not in `given`, conditional on the given values of the others, under the Gaussian
+    copula: given z_O the score of component m is N(mu_m, s_m^2) (`conditional_factor`), so its conditional quantile at p is
+        Q_m(p'),   p' = Phi(mu_m + s_m Phi^-1(p)),
+    mapped on the host (SciPy's ndtri / ndtr) and inverted by ONE `quantiles` call for all sets, components and probabilities.
+    p = 0 and p = 1 give the end points of the domain exactly, a NaN or out-of-range p gives NaN.
+    :param probs: [P] probabilities, the same for every component and set
+    :param given, corr: as in `conditional_samples`
+    :return: [q, P] when every given value is a scalar, [B, q, P] otherwise; row m = component info.unobserved[m]"""
+    from scipy.special import ndtr, ndtri
+    free, mu, s, scalar = _conditional_law("conditional_quantiles", distrs, given, corr)
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        mapped = ndtr(mu[:, :, None] + s[None, :, None] * ndtri(probs)[None, None, :])             # [B, q, P]
+    q = quantiles(free, [np.ascontiguousarray(mapped[:, m, :]).reshape(-1) for m in range(len(free))])
+    out = np.stack([np.asarray(r).reshape(mu.shape[0], probs.size) for r in q], axis=1)
+    return out[0] if scalar else out
+
+
+def conditional_cdfs(distrs, values, given, corr):
+    """Conditional CDFs of every component that is not in `given`, the inverse of `conditional_quantiles`:
+        Phi((Phi^-1(clamp(Fhat_m(x))) - mu_m) / s_m),
+    Fhat_m through ONE `cdfs_on_rule` call, the clamp to [2^-53, 1 - 2^-53] of `normal_scores`, the map on the host.
+    :param values: an array that broadcasts to [B, q, P] ([P]: the same points for every component and set; the result of
+        `conditional_quantiles` as it is)
+    :return: [q, P] when every given value is a scalar, [B, q, P] otherwise"""
+    from scipy.special import ndtr, ndtri
+    free, mu, s, scalar = _conditional_law("conditional_cdfs", distrs, given, corr)
+    values = np.asarray(values, dtype=np.float64)
+    B, q = mu.shape
+    x = np.broadcast_to(values, (B, q) + values.shape[-1:]) if values.ndim else np.broadcast_to(values, (B, q, 1))
+    f = cdfs_on_rule(free, [np.ascontiguousarray(x[:, m, :]).reshape(-1) for m in range(q)])
+    f = np.stack([np.asarray(r).reshape(B, -1) for r in f], axis=1)
+    z = ndtri(np.minimum(np.maximum(f, 2.0 ** -53), 1.0 - 2.0 ** -53))
+    out = ndtr((z - mu[:, :, None]) / s[None, :, None])
+    return out[0] if scalar else out
+
+
 def _scores_problem_args(distrs, what):
     """the problem arguments of mlmc_density_scores_batch for a list of distributions, ready to be splatted into the call:
     (M, handles, r1, lam, sig, a, b, n_intervals, gauss_degree) as ctypes values, and the arrays that must outlive the call"""

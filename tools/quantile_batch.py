@@ -69,8 +69,15 @@ and on coarse followed by torch clamp and torch.special.ndtri, the routes taking
   scores_kernel_ms / cdf_kernel_ms              HIP-event time of one route's point kernels (k_q_scores; the two k_q_cdf launches)
   score_correlation_ms / component_covariance_ms   levels > 0: Estimate.estimate_score_correlation against estimate_component_covariance
                                                 on a DeviceMemory store of `levels` levels of n pairs, end to end, mean wall time
+--conditional: simple_distribution.conditional_samples(..., device=True) with component 0 of M = 12 given,
+R1 = 25, for (B, n) = (1, 10^6), (64, 10^4), (1024, 10^3) against a Python loop of B single-set calls and against joint_samples of the
+11 other components with B n draws, the three taking turns after a warm-up call each (--config M,R1,B,n: that shape alone):
+  conditional_ms / loop_ms / joint_ms           wall time of the whole route up to a device synchronise, [min, median, max]
+  conditional_kernel_ms / loop_kernel_ms / joint_kernel_ms   HIP-event time of one route's point kernels (normals, uniforms, sampling)
+  loop_over_conditional_wall / conditional_over_joint_wall   ratios of the median wall times
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
-                                                             [--tails | --divergences | --moments | --samples | --joint | --scores] [--reps K]"""
+                                                             [--tails | --divergences | --moments | --samples | --joint | --scores |
+                                                              --conditional] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -407,6 +414,58 @@ def joint_shape(M, R1, n, K, reps):
                 all_success=ok)
 
 
+def conditional_shape(M, R1, B, n, reps):
+    """conditional_samples(device=True) of B sets of n draws, component 0 of M given, against (a) a Python loop of B single-set calls
+    and (b) joint_samples of the M - 1 other components with B n draws; the routes take turns in one process"""
+    distrs, ok = mixtures(M, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    rng = np.random.default_rng(7)
+    A = rng.standard_normal((M, M + 3))
+    c = A @ A.T
+    d = 1.0 / np.sqrt(np.diag(c))
+    cond = sd.conditional_factor(c * d[:, None] * d[None, :], [0])
+    unit = np.ascontiguousarray(cond[1] / cond[2].s[:, None])                  # rows of unit norm: what joint_samples takes
+    xs = sd.quantiles([distrs[0]], [np.linspace(0.05, 0.95, B) if B > 1 else np.array([0.3])])[0]
+    seed = [1000 * M + R1]
+
+    def batched_route():
+        seed[0] += 1
+        x = sd.conditional_samples(distrs, n, seed[0], {0: xs}, factor_info=cond, device=True)
+        torch.cuda.synchronize()
+        return x
+
+    def loop_route():
+        seed[0] += 1
+        x = [sd.conditional_samples(distrs, n, seed[0], {0: float(v)}, factor_info=cond, device=True) for v in xs]
+        torch.cuda.synchronize()
+        return x
+
+    def joint_route():
+        seed[0] += 1
+        x = sd.joint_samples(distrs[1:], B * n, seed[0], factor=unit, device=True)
+        torch.cuda.synchronize()
+        return x
+    routes = (batched_route, loop_route, joint_route)
+    for fn in routes:
+        fn()
+    wall, kern = [[] for _ in routes], [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(float(np.median(t)), 3), round(max(t), 3)]
+    med = lambda t: float(np.median(t))
+    return dict(M=M, R1=R1, B=B, n=n, conditional_ms=span(wall[0]), loop_ms=span(wall[1]), joint_ms=span(wall[2]),
+                conditional_kernel_ms=span(kern[0]), loop_kernel_ms=span(kern[1]), joint_kernel_ms=span(kern[2]),
+                loop_over_conditional_wall=round(med(wall[1]) / med(wall[0]), 3),
+                conditional_over_joint_wall=round(med(wall[0]) / med(wall[2]), 3), all_success=ok)
+
+
 def scores_shape(M, R1, n, reps, levels=0):
     """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
     device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
@@ -505,12 +564,21 @@ def main():
                                                          "(DESIGN.md section 3.5.13)")
     ap.add_argument("--scores", action="store_true", help="normal_scores against cdfs_on_rule + torch ndtri, and estimate_score_correlation "
                                                           "against estimate_component_covariance (DESIGN.md section 3.5.14)")
+    ap.add_argument("--conditional", action="store_true", help="conditional_samples of B sets against a loop of single-set calls and "
+                                                               "joint_samples of as many draws (DESIGN.md section 3.5.15)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.conditional:
+        shapes = [(12, 25, 1, 1_000_000), (12, 25, 64, 10_000), (12, 25, 1024, 1_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 3, 1_000)]
+        out["conditional"] = [conditional_shape(M, R1, B, n, a.reps) for M, R1, B, n in shapes]
     elif a.scores:
         shapes = [(12, 25, 1_000_000, 5), (64, 25, 1_000_000, 0), (256, 25, 100_000, 0)]
         if a.config:
