@@ -41,7 +41,8 @@ extern "C" {
                               *    mlmc_chebyshev_connection_table, mlmc_bootstrap_create_multi, mlmc_bootstrap_finalize_multi,
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
                               *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
-                              *    mlmc_density_sample_conditional_batch */
+                              *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
+                              *    three sampling entries) */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -437,8 +438,44 @@ int mlmc_density_moments_batch(int32_t B, const mlmc_basis *const *bases, const 
  * for all its draws, its u_out are still the uniforms, and it is no error.  So does a problem with a NaN among its effective
  * coefficients (NaN multipliers): the clip of the exponent hides them from the mass, and this entry does not draw from what
  * is left (the one case where a draw is not the quantile entry's value).  One workgroup per (problem, share of its draws), no
- * atomics; one host wait. */
+ * atomics; one host wait.
+ *
+ * MLMC_SAMPLE_SOBOL in `flags` (this entry, mlmc_density_sample_joint_batch and mlmc_density_sample_conditional_batch; added within
+ * 8) replaces the Philox uniform of (seed, stream s, index i) by coordinate d = s of point i of a scrambled Sobol' sequence:
+ * randomised quasi-Monte Carlo.  Everything downstream of "the uniform" is unchanged (Q here; normcdfinv, the product, the clamp and
+ * the shift in the joint entries), and without the flag every entry returns the bits it returned before the flag existed.
+ *   Direction numbers: those of Joe and Kuo (2008), 52 bits, dimensions 0 .. 1023.  V[d][t] = m_{d,t+1} << (51 - t), t = 0 .. 51;
+ *     dimension 0 has every m = 1; for d >= 1, with the primitive polynomial p_d of degree s (leading and trailing bits included)
+ *     and the initial values m_1 .. m_s,
+ *       m_k = m_{k-s} ^ (m_{k-s} << s) ^ XOR_{i=1}^{s-1} [bit (s - i) of p_d] (m_{k-i} << i).
+ *     This reproduces scipy.stats.qmc.Sobol(1024, scramble=False, bits=52).
+ *   Raw point: raw(d, i) = XOR { V[d][t] : bit t of i ^ (i >> 1) is set }, the Gray-code order (point 0 is 0).
+ *   Scramble, always applied and keyed by `seed`: a random linear matrix scramble and a digital shift.  word52(c0, c1) is the 52-bit
+ *     word (r0 << 20) | (r1 >> 12) of Philox4x32-10 (the keying by `seed` above) of the counter (c0, c1, 0, 0x534F424C).  Digit r
+ *     (r = 0 .. 51) sits at bit 51 - r.  mask_r = (word52(d, r) & ~(2^(52-r) - 1) & (2^52 - 1)) | (1 << (51 - r)): random bits on
+ *     the more significant digits, a one on the diagonal; bit 51 - r of S_d(raw) is the parity of mask_r & raw.  S_d is linear
+ *     over GF(2), so with V'[d][t] = S_d(V[d][t]) and shift_d = word52(d, 52)
+ *       m(d, i) = XOR { V'[d][t] : bit t of i ^ (i >> 1) is set } ^ shift_d,     u = (2 m + 1) 2^-53.
+ *     The host scrambles the 52 direction numbers of every distinct dimension of a call once; the device only XORs.
+ *   Properties.  u is an odd multiple of 2^-53: 0 < u < 1, u and 1 - u are exact and normcdfinv(u) is finite, as for the Philox
+ *     uniform.  For one seed the 2^k points whose indices start at a multiple of 2^k hit every stratum [a 2^-k, (a + 1) 2^-k) of
+ *     each dimension exactly once (the scramble keeps the net property).  Distinct seeds give independent randomisations: the
+ *     sample standard deviation of the means of R seeds is the error estimate of randomised quasi-Monte Carlo.  The balance holds
+ *     for blocks aligned to powers of two; any first and n are allowed.
+ *   Here d = streams[i] (NULL: i) for problem i; in the joint and the conditional entry d = streams[k] (NULL: k) for latent normal
+ *     k and z = normcdfinv(u).  Equal streams give equal coordinates (comonotone draws), as without the flag.
+ *   Errors: the flag together with MLMC_SAMPLE_ANTITHETIC is an error of the call; a stream >= 1024 is an error that names the
+ *     problem (here) or the latent normal; first + n > 2^52 is an error (here it names the problem).  Every other rule of the
+ *     entries carries over: the draw is bit for bit mlmc_density_quantiles_batch at the returned u, first = 50, n = 100 gives
+ *     elements [50, 150) of first = 0, n = 150, and no value depends on the batch, on positions, on the blocks or on the launch
+ *     geometry. */
 #define MLMC_SAMPLE_ANTITHETIC 1
+#define MLMC_SAMPLE_SOBOL 8   /* bits 2 and 4 stay unknown */
+/* The table behind MLMC_SAMPLE_SOBOL, host arithmetic only (no device, callable before mlmc_init) -- added within 8.  For the nd
+ * dimensions dims[i] < 1024 (host uint32): dirs_out[i][t], t < 52, and shift_out[i].  scramble = 0: the raw Joe-Kuo V[d][t] and
+ * zero shifts; scramble = 1: V'[d][t] and shift_d under `seed`, what the sampling entries upload.  nd = 0 is a no-op; nd < 0, a
+ * null array, a scramble other than 0 / 1 and a dimension >= 1024 are errors. */
+int mlmc_sobol_table(uint64_t seed, int32_t scramble, const uint32_t *dims, int32_t nd, uint64_t *dirs_out, uint64_t *shift_out);
 int mlmc_density_sample_batch(int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                               const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                               uint64_t seed, const uint32_t *streams, const int64_t *first, const int64_t *n, int32_t flags,

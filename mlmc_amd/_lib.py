@@ -19,6 +19,7 @@ MODE_MEAN_ONLY = 0x100
 HOST, DEVICE = 0, 1
 FLAG_TIMING = 1
 SAMPLE_ANTITHETIC = 1      # MLMC_SAMPLE_ANTITHETIC
+SAMPLE_SOBOL = 8           # MLMC_SAMPLE_SOBOL
 
 
 class MlmcHipError(RuntimeError):
@@ -72,6 +73,7 @@ SIGNATURES = {
     "mlmc_accum_kernel_flops": (C.c_int, [_vp, _ip]),
     "mlmc_accum_aux_kernel_time": (C.c_int, [_vp, _dp, _ip, _ip]),
     "mlmc_linearization_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "mlmc_sobol_table": (C.c_int, [C.c_uint64, C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "mlmc_chebyshev_connection_table": (C.c_int, [C.c_int32, _vp, C.c_int64]),
     "mlmc_percentiles": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _ip, C.c_int]),
     "mlmc_percentiles_rows": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int]),

@@ -58,6 +58,7 @@
 #include "copula.hpp"
 #include "density.hpp"
 #include "maxent_batch.hpp"
+#include "sobol.hpp"
 
 namespace mlmc {
 
@@ -390,15 +391,25 @@ constexpr int Q_SAMPLE_WAVES_PER_CU = 16;              // resident waves per CU 
 // block's first draw.  seed, antithetic, u_out and the draws' first / stream are not used then.
 // SETS (mlmc_density_sample_conditional_batch, with U_IN): set = blockIdx.z.  The set's uniforms are rows u_set further on in u_in
 // per set and its draws x_set elements further on in out; with u_out the draw's uniform goes there too, at the draw's place.
-template <bool COEF_LDS, bool ROW_LDS, bool U_IN = false, bool SETS = false>
+// QMC (MLMC_SAMPLE_SOBOL): a lane's list is a RUN of consecutive draws, not every stride-th one.  The points whose indices agree
+// in their low a bits share the leading a digits of every coordinate, so with a stride that is a multiple of 2^a (it always is
+// one of 64) a lane would draw all its uniforms from one stratum of width 2^-a: the lanes of the tail strata would get nothing but
+// slow draws and their waves would take several times as long as the others.  Consecutive points are balanced.
+// Without U_IN, u_j is coordinate j of the problem's dimension of the scrambled Sobol' sequence (sobol.hpp) instead of the Philox
+// uniform.  The draws' `stream` is then the row of the dimension in `sobol`, the call's table; the row's 53 words are staged in
+// LDS behind the P row, a lane forms the first point of its run from the set bits of its Gray code and steps to the next with one
+// XOR (the Gray codes of j - 1 and j differ in bit ctz(j)).
+template <bool COEF_LDS, bool ROW_LDS, bool U_IN = false, bool SETS = false, bool QMC = false>
 __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__restrict__ probs, const QDraw *__restrict__ draws, int nint,
                                                                const double *__restrict__ coef, const double *__restrict__ tab,
                                                                const double *__restrict__ nodes, const double *__restrict__ wts, int deg,
                                                                uint64_t seed, int antithetic, double *__restrict__ out,
                                                                double *__restrict__ u_out, const double *__restrict__ u_in, int64_t u_ld,
-                                                               int64_t u_n, int64_t u_set, int64_t x_set) {
+                                                               int64_t u_n, int64_t u_set, int64_t x_set,
+                                                               const uint64_t *__restrict__ sobol) {
     extern __shared__ double q_sample_lds[];
     static_assert(U_IN || !SETS, "the sets of a call read their uniforms");
+    constexpr bool SOBOL = QMC && !U_IN;
     if constexpr (SETS) {
         out += (int64_t)blockIdx.z * x_set;
         if (u_out) u_out += (int64_t)blockIdx.z * x_set;
@@ -406,7 +417,9 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
     const QProb P = probs[blockIdx.x];
     const int64_t n_draws = U_IN ? u_n : P.n;
     const int64_t t0 = (int64_t)blockIdx.y * blockDim.x;
-    if (t0 >= n_draws) return;                             // the whole workgroup: no draw of this problem is left for it
+    const int64_t stride = (int64_t)gridDim.y * blockDim.x;
+    const int64_t run = QMC ? (n_draws + stride - 1) / stride : 1;          // QMC: lane g owns the draws g run .. g run + run - 1
+    if (t0 * run >= n_draws) return;                       // the whole workgroup: no draw of this problem is left for it
     const QDraw D = draws[blockIdx.x];
     double *gx = q_sample_lds, *gw = gx + deg, *cl = gw + deg, *rl = cl + (COEF_LDS ? P.n_coef : 0);
     for (int k = threadIdx.x; k < deg; k += blockDim.x) {
@@ -422,30 +435,41 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
         for (int j = threadIdx.x; j <= nint; j += blockDim.x) rl[j] = row[j];
         row = rl;
     }
+    [[maybe_unused]] uint64_t *sl = (uint64_t *)(rl + (ROW_LDS ? nint + 1 : 0));
+    if constexpr (SOBOL) {
+        for (int k = threadIdx.x; k < SOBOL_ROW; k += blockDim.x) sl[k] = sobol[(int64_t)D.stream * SOBOL_ROW + k];
+    }
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.y * blockDim.x;
     with_kind(P.bp.kind, [&](auto K) {
         QInversion<decltype(K)::value> s;
         bool busy = false;
         int64_t cur = 0;                                    // the draw `s` iterates on
-        int64_t t = t0 + threadIdx.x;
+        int64_t t = (t0 + threadIdx.x) * run;
+        const int64_t step = QMC ? 1 : stride, t_end = QMC ? std::min(t + run, n_draws) : n_draws;
+        [[maybe_unused]] const int64_t t_first = t;
+        [[maybe_unused]] uint64_t point = 0;                // SOBOL: m of the lane's last point
         // U_IN: the uniform of the lane's next draw is loaded while it inverts the one before, so that no wave waits for memory
         // at the start of a draw
         [[maybe_unused]] const double *ur = nullptr;
         [[maybe_unused]] double u_next = 0.0;
         if constexpr (U_IN) {
             ur = u_in + ((SETS ? (int64_t)blockIdx.z * u_set : 0) + (int64_t)blockIdx.x) * u_ld;
-            if (t < n_draws) u_next = ur[t];
+            if (t < t_end) u_next = ur[t];
         }
-        while (busy || t < n_draws) {
+        while (busy || t < t_end) {
             if (!busy) {                                    // this lane's next draw, while other lanes go on with theirs
                 double u;
                 if constexpr (U_IN) {
                     u = u_next;
-                    if (t + stride < n_draws) u_next = ur[t + stride];
+                    if (t + step < t_end) u_next = ur[t + step];
                     if constexpr (SETS) {
                         if (u_out) u_out[P.x_off + t] = u;
                     }
+                } else if constexpr (SOBOL) {
+                    const uint64_t j = (uint64_t)(D.first + t);
+                    point = t == t_first ? sobol_point(sl, j) : point ^ sl[__builtin_ctzll(j)];
+                    u = sobol_unit(point);
+                    if (u_out) u_out[P.x_off + t] = u;
                 } else {
                     const uint64_t j = (uint64_t)(D.first + t);
                     u = q_uniform(seed, D.stream, antithetic ? j >> 1 : j);
@@ -455,7 +479,7 @@ __global__ __launch_bounds__(Q_SAMPLE_THREADS) void k_q_sample(const QProb *__re
                 busy = !D.nan_coef && s.begin(P, row, nint, u);
                 if (!busy) out[P.x_off + t] = D.nan_coef ? __builtin_nan("") : s.value;
                 cur = t;
-                t += stride;
+                t += step;
             }
             if (busy && !s.step(P, c, gx, gw, deg)) {
                 out[P.x_off + cur] = s.value;
@@ -918,6 +942,14 @@ struct QSampling {
     double *u_out;                    // may be NULL
 };
 
+// the flags of a sampling call
+static int q_sample_flags(const char *fn, int32_t flags) {
+    if (flags & ~(MLMC_SAMPLE_ANTITHETIC | MLMC_SAMPLE_SOBOL)) return fail(std::string(fn) + ": unknown flag bits");
+    if ((flags & MLMC_SAMPLE_ANTITHETIC) && (flags & MLMC_SAMPLE_SOBOL))
+        return fail(std::string(fn) + ": MLMC_SAMPLE_SOBOL and MLMC_SAMPLE_ANTITHETIC exclude each other");
+    return 0;
+}
+
 // the draws table of a sampling call
 static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::vector<QDraw> &draws) {
     draws.resize(S.probs.size());
@@ -926,6 +958,8 @@ static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::v
         const int64_t first = smp.first ? smp.first[i] : 0;
         if (first < 0) return meb_fail(fn, (int)i, "first < 0");
         if (first > INT64_MAX - p.n) return meb_fail(fn, (int)i, "first + n overflows int64");
+        if ((smp.flags & MLMC_SAMPLE_SOBOL) && first + p.n > SOBOL_MAX_INDEX)
+            return meb_fail(fn, (int)i, "first + n is beyond the 2^52 points of the Sobol' sequence");
         const double *c = S.coef.data() + p.c_off;
         const bool nan_coef = std::any_of(c, c + p.n_coef, [](double v) { return v != v; });
         draws[i] = QDraw{first, smp.streams ? smp.streams[i] : (uint32_t)i, nan_coef ? 1u : 0u};
@@ -954,27 +988,38 @@ struct QSampleLaunch {
     }
 };
 // What a workgroup of k_q_sample / k_q_scores stages in LDS for the problems of a call: the rule always, the coefficients if every
-// problem has at most Q_SAMPLE_MAX_COEF, and then the P row if all of it fits into Q_SAMPLE_LDS_BYTES
+// problem has at most Q_SAMPLE_MAX_COEF, and then the P row if all of it fits into Q_SAMPLE_LDS_BYTES; `extra` bytes go on top
+// (the Sobol' row of a problem's dimension)
 struct QLdsPlan {
     bool coef_lds, row_lds;
     size_t bytes;
 };
-static QLdsPlan q_lds_plan(const QSetup &S, int nint, int deg) {
+static QLdsPlan q_lds_plan(const QSetup &S, int nint, int deg, size_t extra = 0) {
     int max_coef = 0;
     for (const QProb &p : S.probs) max_coef = std::max(max_coef, p.n_coef);
     const bool coef_lds = max_coef <= Q_SAMPLE_MAX_COEF;
-    const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)), lds_row = sizeof(double) * ((size_t)nint + 1);
+    const size_t lds_head = sizeof(double) * (2 * (size_t)deg + (coef_lds ? max_coef : 0)) + extra, lds_row = sizeof(double) * ((size_t)nint + 1);
     const bool row_lds = coef_lds && lds_head + lds_row <= Q_SAMPLE_LDS_BYTES;
     return QLdsPlan{coef_lds, row_lds, lds_head + (row_lds ? lds_row : 0)};
 }
 
 // u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch); sets: the one that reads them per set
-// (mlmc_density_sample_conditional_batch)
-static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in, bool sets = false) {
-    const QLdsPlan plan = q_lds_plan(S, nint, deg);
+// (mlmc_density_sample_conditional_batch); qmc: the instances of MLMC_SAMPLE_SOBOL, whose lanes own runs of draws and which, in
+// mlmc_density_sample_batch, make Sobol' uniforms
+static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in, bool sets = false, bool qmc = false) {
+    const QLdsPlan plan = q_lds_plan(S, nint, deg, qmc && !u_in ? sizeof(uint64_t) * SOBOL_ROW : 0);
     const bool coef_lds = plan.coef_lds, row_lds = plan.row_lds;
     QSampleLaunch L;
-    if (sets)
+    if (qmc && sets)
+        L.kernel = row_lds ? k_q_sample<true, true, true, true, true>
+                   : coef_lds ? k_q_sample<true, false, true, true, true> : k_q_sample<false, false, true, true, true>;
+    else if (qmc && u_in)
+        L.kernel = row_lds ? k_q_sample<true, true, true, false, true>
+                   : coef_lds ? k_q_sample<true, false, true, false, true> : k_q_sample<false, false, true, false, true>;
+    else if (qmc)
+        L.kernel = row_lds ? k_q_sample<true, true, false, false, true>
+                   : coef_lds ? k_q_sample<true, false, false, false, true> : k_q_sample<false, false, false, false, true>;
+    else if (sets)
         L.kernel = row_lds ? k_q_sample<true, true, true, true>
                    : coef_lds ? k_q_sample<true, false, true, true> : k_q_sample<false, false, true, true>;
     else if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
@@ -1001,11 +1046,19 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
     const bool tails = mode == Q_TAILS, sample = mode == Q_SAMPLE;
-    if (sample && (smp->flags & ~MLMC_SAMPLE_ANTITHETIC)) return fail(std::string(fn) + ": unknown flag bits");
+    if (sample && q_sample_flags(fn, smp->flags)) return 1;
+    const bool sobol = sample && (smp->flags & MLMC_SAMPLE_SOBOL);
     QSetup S;
     if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
     std::vector<QDraw> draws;
     if (sample && q_draws(fn, S, *smp, draws)) return 1;
+    // MLMC_SAMPLE_SOBOL: the rows of the call's distinct dimensions; a problem's draws entry names its row instead of its stream
+    std::vector<uint64_t> sobol_tab;
+    if (sobol) {
+        std::vector<uint32_t> slot;
+        if (sobol_call_table(fn, "problem", smp->seed, smp->streams, B, sobol_tab, slot)) return 1;
+        for (int i = 0; i < B; ++i) draws[i].stream = slot[i];
+    }
     if (S.n_tot > 0 && ((!sample && !x) || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
     if (S.n_tot == 0 && !mass_out && !mean_out) return 0;
     const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
@@ -1017,16 +1070,23 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     const size_t np = stage ? (size_t)S.n_tot : 0, nm = (size_t)B * (tails ? 2 : 1);      // staged points; masses, then means
     // what goes up with the block: the points, or the draws table of a sampling call; a sampling call returns the uniforms in
     // the place of the lower tail means
-    const size_t n_in = sample ? draws.size() * (sizeof(QDraw) / sizeof(double)) : np;
+    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double));
+    const size_t n_in = sample ? n_draw + sobol_tab.size() : np;
     if (sample) lower_out = smp->u_out;
+    std::vector<double> packed;                          // MLMC_SAMPLE_SOBOL: the draws table | the Sobol' table (uint64)
+    if (sobol) {
+        packed.resize(n_in);
+        std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
+        std::memcpy(packed.data() + n_draw, sobol_tab.data(), sizeof(uint64_t) * sobol_tab.size());
+    }
     QBlock K;
     if (q_stage(S, deg, {n_in}, {nm, rows * (size_t)plane, np, lower_out ? np : 0, tails ? np : 0}, {nm}, K)) return 1;
-    if (K.upload({sample ? (const double *)draws.data() : x}, n_in)) return 1;
+    if (K.upload({sobol ? packed.data() : sample ? (const double *)draws.data() : x}, n_in)) return 1;
     double *d_mass = K.d[0], *d_mean = d_mass + B, *d_tab = K.d[1];
     const double *d_x = stage ? K.d_in[0] : x;
     double *d_out = stage ? K.d[2] : out, *d_lower = stage && lower_out ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
     QSampleLaunch L;
-    if (sample) L = q_sample_launch(S, nint, deg, false);
+    if (sample) L = q_sample_launch(S, nint, deg, false, false, sobol);
     const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
     const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
     QTiming &tm = q_timing();
@@ -1052,7 +1112,7 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
                 hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0,
                                    (const QDraw *)K.d_in[0] + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, smp->seed,
                                    (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower, (const double *)nullptr, (int64_t)0,
-                                   (int64_t)0, (int64_t)0, (int64_t)0);
+                                   (int64_t)0, (int64_t)0, (int64_t)0, sobol ? (const uint64_t *)(K.d_in[0] + n_draw) : nullptr);
             } else {
                 hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts,
                                    K.coef, (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
@@ -1096,12 +1156,18 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
     if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
     if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
-    if (flags & ~MLMC_SAMPLE_ANTITHETIC) return fail(std::string(fn) + ": unknown flag bits");
+    if (q_sample_flags(fn, flags)) return 1;
+    const bool sobol = flags & MLMC_SAMPLE_SOBOL;
     if (Kf < 1) return fail(std::string(fn) + ": K < 1");
     if (!factor) return fail(std::string(fn) + ": null factor");
     if (n < 0) return fail(std::string(fn) + ": n < 0");
     if (first < 0) return fail(std::string(fn) + ": first < 0");
     if (first > INT64_MAX - n) return fail(std::string(fn) + ": first + n overflows int64");
+    if (sobol && first + n > SOBOL_MAX_INDEX) return fail(std::string(fn) + ": first + n is beyond the 2^52 points of the Sobol' sequence");
+    // MLMC_SAMPLE_SOBOL: the rows of the call's distinct dimensions; latent normal k names its row instead of its stream
+    std::vector<uint64_t> sobol_tab;
+    std::vector<uint32_t> sobol_slot;
+    if (sobol && sobol_call_table(fn, "latent normal", seed, streams, Kf, sobol_tab, sobol_slot)) return 1;
     for (int m = 0; m < M; ++m) {
         const double *row = factor + (size_t)m * Kf;
         double ss = 0.0;
@@ -1131,15 +1197,16 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
     }
     nb = std::min(nb, std::max<int64_t>(n, 1));
     const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && !(mem_kind == MLMC_DEVICE && u_out);
-    // what goes up with the block: the draws table | the streams (uint32) | the factor
+    // what goes up with the block: the draws table | the streams (uint32) | the factor | the Sobol' table (uint64)
     const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
-    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_in = n_draw + n_str + n_fac;
+    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sob = n > 0 ? sobol_tab.size() : 0, n_in = n_draw + n_str + n_fac + n_sob;
     std::vector<double> packed(n_in);
     std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
     if (n > 0) {
         uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
-        for (int k = 0; k < Kf; ++k) sv[k] = streams ? streams[k] : (uint32_t)k;
+        for (int k = 0; k < Kf; ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
         std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
+        std::memcpy(packed.data() + n_draw + n_str + n_fac, sobol_tab.data(), sizeof(uint64_t) * n_sob);
     }
     QBlock K;
     if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, stage ? (size_t)M * (size_t)n : 0, u_ws ? (size_t)M * (size_t)nb : 0,
@@ -1149,8 +1216,9 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
     const QDraw *d_draws = (const QDraw *)K.d_in[0];
     const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
     const double *d_factor = K.d_in[0] + n_draw + n_str;
+    const uint64_t *d_sobol = (const uint64_t *)(d_factor + n_fac);
     double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
-    const QSampleLaunch L = q_sample_launch(S, nint, deg, true);
+    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, false, sobol);
     QTiming &tm = q_timing();
     size_t timed = 0;
     for (int g0 = 0; g0 < M; g0 += G) {
@@ -1167,14 +1235,17 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
             const int64_t ldz = z_ws ? nb : n, ldu = u_ws ? nb : n;
             hipEvent_t e0, e1;
             const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
-            if (g0 == 0 || z_ws)               // a later group finds the normals of the block in the caller's array
+            if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
+                cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
+            else if (g0 == 0 || z_ws)
                 cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
             cop_launch_uniforms(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu);
             unsigned threads, gy;
             L.geometry((int64_t)np_g * nc, nc, threads, gy);
             hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0, d_draws + g0, nint, K.coef,
                                (const double *)d_tab, K.gx, K.gw, deg, seed, 0, d_out + c0, (double *)nullptr,
-                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc, (int64_t)0, (int64_t)0);
+                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc, (int64_t)0, (int64_t)0,
+                               (const uint64_t *)nullptr);
             if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
             MLMC_HIP_CHECK(hipGetLastError());
             if (stage && z_out && g0 == 0)
@@ -1217,12 +1288,18 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
     if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
     if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
-    if (flags & ~MLMC_SAMPLE_ANTITHETIC) return fail(std::string(fn) + ": unknown flag bits");
+    if (q_sample_flags(fn, flags)) return 1;
+    const bool sobol = flags & MLMC_SAMPLE_SOBOL;
     if (Kf < 1) return fail(std::string(fn) + ": K < 1");
     if (!factor) return fail(std::string(fn) + ": null factor");
     if (n < 0) return fail(std::string(fn) + ": n < 0");
     if (first < 0) return fail(std::string(fn) + ": first < 0");
     if (first > INT64_MAX - n) return fail(std::string(fn) + ": first + n overflows int64");
+    if (sobol && first + n > SOBOL_MAX_INDEX) return fail(std::string(fn) + ": first + n is beyond the 2^52 points of the Sobol' sequence");
+    // MLMC_SAMPLE_SOBOL: the rows of the call's distinct dimensions; latent normal k names its row instead of its stream
+    std::vector<uint64_t> sobol_tab;
+    std::vector<uint32_t> sobol_slot;
+    if (sobol && sobol_call_table(fn, "latent normal", seed, streams, Kf, sobol_tab, sobol_slot)) return 1;
     if (B < 1) return fail(std::string(fn) + ": B < 1");
     if (ld_rows < M) return fail(std::string(fn) + ": ld_rows < M");
     for (int m = 0; rows && m < M; ++m)
@@ -1269,16 +1346,18 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
     }
     nb = std::min(nb, std::max<int64_t>(n, 1));
     const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out);
-    // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts
+    // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts | the Sobol' table (uint64)
     const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
-    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sh = n > 0 ? BM : 0, n_in = n_draw + n_str + n_fac + n_sh;
+    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sh = n > 0 ? BM : 0, n_sob = n > 0 ? sobol_tab.size() : 0;
+    const size_t n_in = n_draw + n_str + n_fac + n_sh + n_sob;
     std::vector<double> packed(n_in);
     std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
     if (n > 0) {
         uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
-        for (int k = 0; k < Kf; ++k) sv[k] = streams ? streams[k] : (uint32_t)k;
+        for (int k = 0; k < Kf; ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
         std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
         if (shift) std::memcpy(packed.data() + n_draw + n_str + n_fac, shift, sizeof(double) * n_sh);         // NULL: the zeros of `packed`
+        std::memcpy(packed.data() + n_draw + n_str + n_fac + n_sh, sobol_tab.data(), sizeof(uint64_t) * n_sob);
     }
     const size_t n_stage = stage ? BM * (size_t)n : 0;
     QBlock K;
@@ -1290,9 +1369,10 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
     const QDraw *d_draws = (const QDraw *)K.d_in[0];
     const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
     const double *d_factor = K.d_in[0] + n_draw + n_str, *d_shift = d_factor + n_fac;
+    const uint64_t *d_sobol = (const uint64_t *)(d_shift + n_sh);
     double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out, *U = K.d[3];
     double *d_u = stage && u_out ? K.d[5] : u_out;
-    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, true);
+    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, true, sobol);
     QTiming &tm = q_timing();
     size_t timed = 0;
     for (int g0 = 0; g0 < M; g0 += G) {
@@ -1308,7 +1388,9 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
             const int64_t ldz = z_ws ? nb : n;
             hipEvent_t e0, e1;
             const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
-            if (g0 == 0 || z_ws)               // a later group finds the normals of the block in the caller's array
+            if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
+                cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
+            else if (g0 == 0 || z_ws)
                 cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
             cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * nb, nb, d_shift + g0, B, M);
             unsigned threads, gy;
@@ -1317,7 +1399,8 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
                 hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy, (unsigned)std::min(B - b0, 65535)), dim3(threads), L.lds_bytes, st,
                                    K.probs + g0, d_draws + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, seed, 0,
                                    d_out + b0 * x_set + c0, d_u ? d_u + b0 * x_set + c0 : (double *)nullptr,
-                                   (const double *)(U + ((int64_t)b0 * M + g0) * nb), nb, nc, (int64_t)M, x_set);
+                                   (const double *)(U + ((int64_t)b0 * M + g0) * nb), nb, nc, (int64_t)M, x_set,
+                                   (const uint64_t *)nullptr);
             if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
             MLMC_HIP_CHECK(hipGetLastError());
             if (stage && z_out && g0 == 0)

@@ -687,7 +687,7 @@ class Estimate:
         return np.array(q, dtype=np.float64).reshape(len(densities), probs.size), success
 
     def sample_components(self, n, seed, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
-                          antithetic=False, device=False):
+                          antithetic=False, device=False, qmc=False):
         """Seeded draws from the maximum-entropy density of EVERY scalar component of the quantity, in one batched device call
         (tool.simple_distribution.samples): draws first .. first + n - 1 of component m come from stream m under `seed`.
 
@@ -696,6 +696,9 @@ class Estimate:
         :param n: draws per component
         :param seed: required, 0 <= seed < 2^64; there is no global generator
         :param densities: as in estimate_component_quantiles
+        :param qmc: scrambled Sobol' points instead of pseudo-random ones (see tool.simple_distribution.samples): the streams are
+            dimensions (at most 1024 components: component m is dimension m), n should be a power of two with `first` a multiple of it, and R seeds give R
+            independent estimates whose spread is the error bar.  Not together with antithetic
         :param device: return the draws as a float64 torch device tensor
         :return: (samples, success): samples [M, n], row m = `.rvs(n, seed, stream=m, first=first, antithetic=antithetic)` of
             component m's distribution (the row order of construct_densities); success [M] bool, the solver's verdict per
@@ -703,9 +706,10 @@ class Estimate:
         from .tool import simple_distribution
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("sample_components: n must be a non-negative integer")
+        simple_distribution._sample_flags("sample_components", antithetic, qmc)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
-        flat, _, _ = simple_distribution._samples_flat([d[0] for d in densities], int(n), seed, None, first, antithetic, device, False)
+        flat, _, _ = simple_distribution._samples_flat([d[0] for d in densities], int(n), seed, None, first, antithetic, device, False, qmc)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return flat.reshape(len(densities), int(n)), success           # the call's one array, viewed as [M, n]
 
@@ -775,7 +779,7 @@ class Estimate:
         return corr, densities
 
     def sample_joint(self, n, seed, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
-                     antithetic=False, device=False):
+                     antithetic=False, device=False, qmc=False):
         """Seeded JOINT draws of all scalar components of the quantity, in one batched device call
         (tool.simple_distribution.joint_samples): the maximum-entropy marginals of `construct_densities` joined by a Gaussian
         copula.  Column j of the result is one scenario of the whole vector: use it for the sum of the components, the CVaR of a
@@ -798,23 +802,27 @@ class Estimate:
             `sample_components` with the same seed up to rounding: use another seed where the two must be independent
         :param corr: None, "scores", or a correlation matrix [M, M] of the normal scores
         :param densities: as in estimate_component_quantiles
+        :param qmc: scrambled Sobol' points instead of pseudo-random ones (see tool.simple_distribution.joint_samples): the streams are
+            dimensions (at most 1024 latent normals: latent normal k is dimension k), n should be a power of two with `first` a multiple of it, and R seeds give R
+            independent estimates whose spread is the error bar.  Not together with antithetic
         :param device: return the draws as a float64 torch device tensor
         :return: (samples [M, n], success [M], corr_used [M, M]): row m = component m (the row order of construct_densities);
             the solver's verdict per component; F F^T of the factor that was used"""
         from .tool import simple_distribution
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("sample_joint: n must be a non-negative integer")
+        simple_distribution._sample_flags("sample_joint", antithetic, qmc)
         corr, densities = self._copula_correlation("sample_joint", corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         factor, _ = simple_distribution.correlation_factor(corr)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
         draws = simple_distribution.joint_samples([d[0] for d in densities], int(n), seed, factor=factor, first=first,
-                                                  antithetic=antithetic, device=device)
+                                                  antithetic=antithetic, device=device, qmc=qmc)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return draws, success, factor @ factor.T
 
     def sample_conditional(self, n, seed, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
-                           densities=None, first=0, antithetic=False, device=False):
+                           densities=None, first=0, antithetic=False, device=False, qmc=False):
         """Seeded joint draws of the components that are not in `given`, CONDITIONAL on measured or fixed values of the others, in
         one batched device call (tool.simple_distribution.conditional_samples): the marginals and the Gaussian copula of
         `sample_joint`, with the scores of the given components fixed at Phi^-1(Fhat_o(x_o)).  Scenarios of the rest of a field
@@ -823,12 +831,16 @@ class Estimate:
             of the marginals and the latent normals are made once for all sets
         :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
         :param densities: as in estimate_component_quantiles
+        :param qmc: scrambled Sobol' points instead of pseudo-random ones (see tool.simple_distribution.conditional_samples): the streams are
+            dimensions (at most 1024 latent normals: latent normal k is dimension k), n should be a power of two with `first` a multiple of it, and R seeds give R
+            independent estimates whose spread is the error bar.  Not together with antithetic
         :return: (samples, success [M], ConditionalFactorInfo): samples [M, n] for scalar values and [B, M, n] for arrays, rows
             of given components hold the given values; the solver's verdict per component; the components that were drawn,
             their conditional standard deviations in score space and what `correlation_factor` did to the matrix"""
         from .tool import simple_distribution
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("sample_conditional: n must be a non-negative integer")
+        simple_distribution._sample_flags("sample_conditional", antithetic, qmc)
         corr, densities = self._copula_correlation("sample_conditional", corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
@@ -836,7 +848,7 @@ class Estimate:
         observed = simple_distribution._parse_given("sample_conditional", given, len(distrs))[0]
         cond = simple_distribution.conditional_factor(corr, observed)
         draws = simple_distribution.conditional_samples(distrs, int(n), seed, given, factor_info=cond, first=first,
-                                                        antithetic=antithetic, device=device)
+                                                        antithetic=antithetic, device=device, qmc=qmc)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return draws, success, cond[2]
 

@@ -139,10 +139,12 @@ class Distribution:
         distribution; p may be a float64 torch device tensor)."""
         return _quantile(self, p)
 
-    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False):
+    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False, qmc=False):
         """n seeded draws from the density of the stored multipliers: draws first .. first + n - 1 of stream `stream` under `seed`
-        (simple_distribution.samples with one distribution)."""
-        return _rvs(self, n, seed, stream, first, antithetic, device)
+        (simple_distribution.samples with one distribution).  qmc=True: coordinate `stream` (a dimension below 1024) of the
+        scrambled Sobol' points first .. first + n - 1; n should be a power of two and `first` a multiple of it for the balance
+        to hold, and the spread of the means of R seeds is the error bar."""
+        return _rvs(self, n, seed, stream, first, antithetic, device, qmc)
 
     def expected_shortfall(self, p, tail="upper"):
         """Expected shortfall (CVaR) at level p of the stored multipliers on this distribution's quadrature: E[X | X >= Q(p)]

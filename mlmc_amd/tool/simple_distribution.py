@@ -326,7 +326,7 @@ def _per_distribution_int(what, name, value, B):
     return np.ascontiguousarray(np.broadcast_to(arr.astype(np.int64), (B,)))
 
 
-def samples(distrs, n, seed, streams=None, first=0, antithetic=False, device=False, return_uniforms=False):
+def samples(distrs, n, seed, streams=None, first=0, antithetic=False, device=False, return_uniforms=False, qmc=False):
     """Seeded draws from many distributions through ONE device call (mlmc_density_sample_batch): inverse-transform sampling on
     each distribution's quadrature.  Draw j of stream s under `seed` is Q(u_j) with Q of `quantiles` (bit for bit its value at
     p = u_j) and u_j the Philox4x32-10 uniform that include/mlmc_hip.h defines, an odd multiple of 2^-53 in (0, 1).  Entry b holds
@@ -338,10 +338,15 @@ def samples(distrs, n, seed, streams=None, first=0, antithetic=False, device=Fal
     :param streams: one uint32 stream per distribution; default: stream b = b
     :param first: index of the first draw, one int for all or one per distribution
     :param antithetic: draws 2k and 2k + 1 come from u and 1 - u
+    :param qmc: randomised quasi-Monte Carlo (MLMC_SAMPLE_SOBOL): u_j is coordinate `stream` of point j of the scrambled Sobol'
+        sequence of include/mlmc_hip.h instead of the Philox uniform.  The streams are then DIMENSIONS and must be below 1024; n
+        should be a power of two and `first` a multiple of it, since the points are balanced over blocks aligned to powers of two
+        (any first and n are allowed).  For an error bar repeat with R seeds: the seeds give independent scrambles, and the sample
+        standard deviation of the R means estimates the error of their mean.  Not together with antithetic
     :param device: return float64 torch device tensors; nothing but the problem table touches the host then
     :param return_uniforms: also return the list of the u_j
     :return: list of arrays [n[b]] (and the same list of uniforms); every distribution must use the same quadrature"""
-    out, u, n = _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms)
+    out, u, n = _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms, qmc)
 
     def per_distribution(flat):
         if device:
@@ -353,11 +358,19 @@ def samples(distrs, n, seed, streams=None, first=0, antithetic=False, device=Fal
     return (per_distribution(out), per_distribution(u)) if return_uniforms else per_distribution(out)
 
 
-def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms):
+def _sample_flags(what, antithetic, qmc):
+    """the flags word of a sampling entry; qmc with antithetic is an error before anything touches the device"""
+    if qmc and antithetic:
+        raise ValueError(what + ": qmc and antithetic exclude each other")
+    return (_lib.SAMPLE_ANTITHETIC if antithetic else 0) | (_lib.SAMPLE_SOBOL if qmc else 0)
+
+
+def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_uniforms, qmc=False):
     """the call behind `samples`: (draws, uniforms or None, counts [B]) with the distributions' draws one after another in one
     array or device tensor; (None, None, counts) for an empty list"""
     distrs = list(distrs)
     B = len(distrs)
+    flags = _sample_flags("samples", antithetic, qmc)
     if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
         raise ValueError("samples: seed must be an integer in 0 .. 2^64 - 1")
     if B == 0:
@@ -393,9 +406,25 @@ def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_un
         kind = _lib.HOST
     _lib.check(lib.mlmc_density_sample_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a),
                                              _lib.ptr(b), int(n_int.pop()), int(degs.pop()), int(seed), _lib.ptr(streams),
-                                             _lib.ptr(first), _lib.ptr(n), _lib.SAMPLE_ANTITHETIC if antithetic else 0,
+                                             _lib.ptr(first), _lib.ptr(n), flags,
                                              _lib.ptr(out), _lib.ptr(u), None, kind))
     return out, u, n
+
+
+def sobol_table(seed, dims, scramble=True):
+    """The table behind qmc=True (mlmc_sobol_table; host arithmetic, needs no device): for the dimensions `dims` (integers below
+    1024) the 52 direction numbers [len(dims), 52] and the digital shifts [len(dims)] as uint64, scrambled under `seed`, or with
+    scramble=False the raw Joe-Kuo numbers and zero shifts.  Point i of a dimension is the XOR of the direction numbers at the set
+    bits of i ^ (i >> 1), XOR the shift; u = (2 m + 1) 2^-53."""
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("sobol_table: seed must be an integer in 0 .. 2^64 - 1")
+    d = np.asarray(dims)
+    if d.ndim != 1 or (d.size and (d.dtype.kind not in "iu" or np.any(d < 0) or np.any(d.astype(np.uint64) >= 2 ** 32))):
+        raise ValueError("sobol_table: dims must be a 1-D array of integers in 0 .. 1023")
+    d = np.ascontiguousarray(d.astype(np.uint32))
+    dirs, shift = np.zeros((d.size, 52), dtype=np.uint64), np.zeros(d.size, dtype=np.uint64)
+    _lib.check(_lib.load().mlmc_sobol_table(int(seed), 1 if scramble else 0, _lib.ptr(d), int(d.size), _lib.ptr(dirs), _lib.ptr(shift)))
+    return dirs, shift
 
 
 CorrelationFactorInfo = collections.namedtuple("CorrelationFactorInfo", "min_eig_in repaired max_change")
@@ -432,7 +461,7 @@ def correlation_factor(corr, min_eig=1e-10):
 
 
 def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0, antithetic=False, device=False,
-                  return_uniforms=False, return_normals=False):
+                  return_uniforms=False, return_normals=False, qmc=False):
     """Seeded JOINT draws from many distributions through ONE device call (mlmc_density_sample_joint_batch): a Gaussian copula
     over the marginals.  With K latent standard normals z and a factor F [M, K] of the correlation matrix of the normal scores,
         x[m, j] = Q_m(u[m, j]),   u = clamp(Phi(F z)),
@@ -448,11 +477,17 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         ones [M, 1] comonotone draws.  Exactly one of corr / factor must be given
     :param streams: one uint32 stream per latent normal; default: stream k = k
     :param antithetic: draws 2k and 2k + 1 come from z and -z
+    :param qmc: randomised quasi-Monte Carlo (MLMC_SAMPLE_SOBOL): the uniform behind latent normal k is coordinate streams[k] of point j of the scrambled Sobol'
+        sequence of include/mlmc_hip.h instead of the Philox uniform.  The streams are then DIMENSIONS and must be below 1024; n
+        should be a power of two and `first` a multiple of it, since the points are balanced over blocks aligned to powers of two
+        (any first and n are allowed).  For an error bar repeat with R seeds: the seeds give independent scrambles, and the sample
+        standard deviation of the R means estimates the error of their mean.  Not together with antithetic
     :param device: return float64 torch device tensors
     :param return_uniforms, return_normals: also return u [M, n] and / or z [K, n], in this order
     :return: draws [M, n]; every distribution must use the same quadrature"""
     distrs = list(distrs)
     M = len(distrs)
+    flags = _sample_flags("joint_samples", antithetic, qmc)
     if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
         raise ValueError("joint_samples: seed must be an integer in 0 .. 2^64 - 1")
     if (corr is None) == (factor is None):
@@ -494,7 +529,7 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         kind = _lib.HOST
     _lib.check(_lib.lib().mlmc_density_sample_joint_batch(
         M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()),
-        int(degs.pop()), K, _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, _lib.SAMPLE_ANTITHETIC if antithetic else 0,
+        int(degs.pop()), K, _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, flags,
         _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
     extra = tuple(v for v, want in ((u, return_uniforms), (z, return_normals)) if want)
     return (out,) + extra if extra else out
@@ -605,7 +640,7 @@ def _conditioning(what, distrs, given, corr, cond):
 
 
 def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, streams=None, first=0, antithetic=False, device=False,
-                        return_uniforms=False):
+                        return_uniforms=False, qmc=False):
     """Seeded joint draws of the components that are NOT in `given`, conditional on the given values of the others, under the
     Gaussian copula of `joint_samples`; B sets of given values through ONE device call (mlmc_density_sample_conditional_batch).
     The given values go to normal scores z_O (one `normal_scores` call); with (W, F_c) of `conditional_factor` the scores of the
@@ -619,12 +654,18 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
     :param corr: correlation matrix [M, M] of the normal scores of ALL components
     :param factor_info: or the tuple `conditional_factor(corr, observed)` returned.  Exactly one of the two must be given
     :param streams: one uint32 stream per latent normal (there are q = M - len(given)); default: stream k = k
+    :param qmc: randomised quasi-Monte Carlo (MLMC_SAMPLE_SOBOL): the uniform behind latent normal k is coordinate streams[k] of point j of the scrambled Sobol'
+        sequence of include/mlmc_hip.h instead of the Philox uniform.  The streams are then DIMENSIONS and must be below 1024; n
+        should be a power of two and `first` a multiple of it, since the points are balanced over blocks aligned to powers of two
+        (any first and n are allowed).  For an error bar repeat with R seeds: the seeds give independent scrambles, and the sample
+        standard deviation of the R means estimates the error of their mean.  Not together with antithetic
     :param return_uniforms: also return u shaped like the draws; rows of given components hold Fhat_o(x_o)
     :return: draws [M, n] when every given value is a scalar, [B, M, n] otherwise: rows of the other components hold the draws, rows
         of given components the given values exactly; float64 torch device tensors with device=True"""
     what = "conditional_samples"
     distrs = list(distrs)
     M = len(distrs)
+    flags = _sample_flags(what, antithetic, qmc)
     if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
         raise ValueError(what + ": seed must be an integer in 0 .. 2^64 - 1")
     n = int(_per_distribution_int(what, "n", n, 1)[0])
@@ -665,7 +706,7 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
     _lib.check(_lib.lib().mlmc_density_sample_conditional_batch(
         q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
         int(distrs[0].n_intervals), int(distrs[0]._gauss_degree), K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
-        _lib.SAMPLE_ANTITHETIC if antithetic else 0, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
+        flags, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
         _lib.ptr(u), None, None, kind))
     if scalar:
         out, u = out[0], (None if u is None else u[0])
@@ -796,9 +837,9 @@ def normal_scores(distrs, fine, coarse=None, device=False, return_uniforms=False
     return return_list[0] if len(return_list) == 1 else tuple(return_list)
 
 
-def _rvs(dist, n, seed, stream, first, antithetic, device):
+def _rvs(dist, n, seed, stream, first, antithetic, device, qmc=False):
     """the B = 1 call of `samples`"""
-    return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device)[0]
+    return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device, qmc=qmc)[0]
 
 
 Divergences = collections.namedtuple("Divergences", "kl l2 tv hellinger mass_prior mass_posterior")
@@ -1152,10 +1193,12 @@ class SimpleDistribution:
         is a device tensor then, e.g. for inverse-transform sampling with the caller's own uniforms)."""
         return _quantile(self, p)
 
-    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False):
+    def rvs(self, n, seed, stream=0, first=0, antithetic=False, device=False, qmc=False):
         """n seeded draws from this density: draws first .. first + n - 1 of stream `stream` under `seed` (see `samples`, of which
-        this is the call with one distribution, hence bit for bit its values; `seed` is required)."""
-        return _rvs(self, n, seed, stream, first, antithetic, device)
+        this is the call with one distribution, hence bit for bit its values; `seed` is required).  qmc=True: coordinate `stream`
+        (a dimension below 1024) of the scrambled Sobol' points first .. first + n - 1; n should be a power of two and `first` a
+        multiple of it for the balance to hold, and the spread of the means of R seeds is the error bar."""
+        return _rvs(self, n, seed, stream, first, antithetic, device, qmc)
 
     def expected_shortfall(self, p, tail="upper"):
         """Expected shortfall (CVaR) at level p on this distribution's quadrature: E[X | X >= Q(p)] for tail = "upper",

@@ -75,9 +75,16 @@ R1 = 25, for (B, n) = (1, 10^6), (64, 10^4), (1024, 10^3) against a Python loop 
   conditional_ms / loop_ms / joint_ms           wall time of the whole route up to a device synchronise, [min, median, max]
   conditional_kernel_ms / loop_kernel_ms / joint_kernel_ms   HIP-event time of one route's point kernels (normals, uniforms, sampling)
   loop_over_conditional_wall / conditional_over_joint_wall   ratios of the median wall times
+--qmc: (a) samples, joint_samples and conditional_samples (device=True) with and without qmc=True on the
+shapes of --samples, --joint and --conditional (streams = index mod 1024 for both variants), the two taking turns after a warm-up
+call each:
+  philox_ms / qmc_ms, philox_kernel_ms / qmc_kernel_ms   wall time up to a device synchronise and HIP-event time of the call's point
+                                                kernels, [min, median, max]; qmc_over_philox_wall / _kernel the ratios of the medians
+(b) the RMS error over seeds 1 .. 8 of the mean of g(u) from joint_samples for n = 2^10, 2^12, .. 2^20 with and without qmc:
+g = prod_m (1 + 0.8 (u_m - 1/2)) under M = K = 4, F = I, and g = u_0 u_1 under the 3 x 3 correlation of the tests
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --scores |
-                                                              --conditional] [--reps K]"""
+                                                              --conditional | --qmc] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -466,6 +473,99 @@ def conditional_shape(M, R1, B, n, reps):
                 conditional_over_joint_wall=round(med(wall[0]) / med(wall[2]), 3), all_success=ok)
 
 
+def qmc_pair(call, reps):
+    """wall and kernel ms of call(qmc=False) and call(qmc=True), the two taking turns inside every repetition on the same box"""
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    for flag in (False, True):
+        call(flag)
+    wall, kern = [[], []], [[], []]
+    for _ in range(reps):
+        for k, flag in enumerate((False, True)):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            call(flag)
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(float(np.median(t)), 3), round(max(t), 3)]
+    med = lambda t: float(np.median(t))
+    return dict(philox_ms=span(wall[0]), qmc_ms=span(wall[1]), philox_kernel_ms=span(kern[0]), qmc_kernel_ms=span(kern[1]),
+                qmc_over_philox_wall=round(med(wall[1]) / med(wall[0]), 3), qmc_over_philox_kernel=round(med(kern[1]) / med(kern[0]), 3))
+
+
+def qmc_times(reps, quick):
+    """samples, joint_samples and conditional_samples with and without qmc on the shapes of --samples, --joint and --conditional"""
+    out = dict(samples=[], joint=[], conditional=[])
+    seed = [77]
+
+    def fresh():
+        seed[0] += 1
+        return seed[0]
+    for B, R1, n in ([(4, 9, 10_000)] if quick else [(1, 9, 10_000_000), (1, 25, 10_000_000), (1, 64, 10_000_000), (64, 25, 1_000_000),
+                                                    (3600, 25, 1_000)]):
+        distrs, ok = mixtures(B, R1, seed=5)
+        streams = np.arange(B) % 1024                        # dimensions under qmc; the same streams for both variants
+
+        def call(qmc):
+            x = sd.samples(distrs, n, fresh(), streams=streams, device=True, qmc=qmc)
+            torch.cuda.synchronize()
+            return x
+        out["samples"].append(dict(B=B, R1=R1, n=n, all_success=ok, **qmc_pair(call, reps)))
+        print(json.dumps(out["samples"][-1]), file=sys.stderr, flush=True)                 # progress; the result line goes to stdout
+    rng = np.random.default_rng(7)
+    for M, R1, n, K in ([(4, 9, 10_000, 4)] if quick else [(12, 25, 1_000_000, 12), (64, 25, 1_000_000, 64), (256, 25, 100_000, 256),
+                                                          (12, 25, 1_000_000, 3)]):
+        distrs, ok = mixtures(M, R1, seed=5)
+        factor = rng.standard_normal((M, K))
+        factor = np.ascontiguousarray(factor / np.sqrt(np.sum(factor * factor, axis=1))[:, None])
+
+        def call(qmc):
+            x = sd.joint_samples(distrs, n, fresh(), factor=factor, device=True, qmc=qmc)
+            torch.cuda.synchronize()
+            return x
+        out["joint"].append(dict(M=M, R1=R1, n=n, K=K, all_success=ok, **qmc_pair(call, reps)))
+        print(json.dumps(out["joint"][-1]), file=sys.stderr, flush=True)                 # progress; the result line goes to stdout
+    for M, R1, B, n in ([(4, 9, 3, 1_000)] if quick else [(12, 25, 1, 1_000_000), (12, 25, 64, 10_000), (12, 25, 1024, 1_000)]):
+        distrs, ok = mixtures(M, R1, seed=5)
+        A = rng.standard_normal((M, M + 3))
+        c = A @ A.T
+        d = 1.0 / np.sqrt(np.diag(c))
+        cond = sd.conditional_factor(c * d[:, None] * d[None, :], [0])
+        xs = sd.quantiles([distrs[0]], [np.linspace(0.05, 0.95, B) if B > 1 else np.array([0.3])])[0]
+
+        def call(qmc):
+            x = sd.conditional_samples(distrs, n, fresh(), {0: xs}, factor_info=cond, device=True, qmc=qmc)
+            torch.cuda.synchronize()
+            return x
+        out["conditional"].append(dict(M=M, R1=R1, B=B, n=n, all_success=ok, **qmc_pair(call, reps)))
+        print(json.dumps(out["conditional"][-1]), file=sys.stderr, flush=True)                 # progress; the result line goes to stdout
+    return out
+
+
+CORR3 = np.array([[1.0, 0.8, -0.5], [0.8, 1.0, -0.2], [-0.5, -0.2, 1.0]])
+
+
+def qmc_errors(quick):
+    """RMS error over seeds 1 .. 8 of the mean of g(u) from joint_samples, with and without qmc, n = 2^10, 2^12, .. 2^20:
+    g = prod_m (1 + 0.8 (u_m - 1/2)) under M = K = 4, F = I (exact 1), and g = u_0 u_1 under CORR3 (exact 1/4 + arcsin(rho / 2) / 2 pi)"""
+    distrs, _ = mixtures(4, 9, seed=5)
+    cases = (("product4", distrs, np.eye(4), lambda u: torch.prod(1.0 + 0.8 * (u - 0.5), dim=0), 1.0),
+             ("u0u1_corr3", distrs[:3], sd.correlation_factor(CORR3)[0], lambda u: u[0] * u[1],
+              0.25 + float(np.arcsin(CORR3[0, 1] / 2.0)) / (2.0 * np.pi)))
+    rows = []
+    for tag, ds, factor, g, exact in cases:
+        for k in ((10, 12) if quick else range(10, 21, 2)):
+            rms = []
+            for qmc in (False, True):
+                err = [float(g(sd.joint_samples(ds, 2 ** k, seed, factor=factor, device=True, return_uniforms=True, qmc=qmc)[1]).mean())
+                       - exact for seed in range(1, 9)]
+                rms.append(float(np.sqrt(np.mean(np.square(err)))))
+            rows.append(dict(integrand=tag, n=2 ** k, philox_rms=float("%.3g" % rms[0]), qmc_rms=float("%.3g" % rms[1]),
+                             philox_over_qmc=round(rms[0] / rms[1], 1)))
+    return rows
+
+
 def scores_shape(M, R1, n, reps, levels=0):
     """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
     device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
@@ -566,12 +666,17 @@ def main():
                                                           "against estimate_component_covariance (DESIGN.md section 3.5.14)")
     ap.add_argument("--conditional", action="store_true", help="conditional_samples of B sets against a loop of single-set calls and "
                                                                "joint_samples of as many draws (DESIGN.md section 3.5.15)")
+    ap.add_argument("--qmc", action="store_true", help="samples / joint_samples / conditional_samples with and without qmc, and the RMS "
+                                                       "error of two integrals against n (DESIGN.md section 3.5.16)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.qmc:
+        out["qmc_times"] = qmc_times(a.reps, a.quick)
+        out["qmc_errors"] = qmc_errors(a.quick)
     elif a.conditional:
         shapes = [(12, 25, 1, 1_000_000), (12, 25, 64, 10_000), (12, 25, 1024, 1_000)]
         if a.config:
