@@ -42,7 +42,7 @@ extern "C" {
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
                               *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
-                              *    three sampling entries) */
+                              *    three sampling entries), mlmc_copula_box_prob_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -578,6 +578,48 @@ int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const i
  * sampling kernel, one launch per group; a joint sampling call counts its normals, uniforms and sampling kernels together as one
  * launch per block and group; a scores call counts its scores kernels, one launch per group. */
 int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
+
+/* ---- joint box probabilities under the Gaussian copula -- added within 8 ------------------------------------ */
+/* P(lo < Y < hi) for Y = shift + L z, z standard normal [M], for B boxes and R seeds in one call: Genz's separation of variables
+ * (Genz, J. Comput. Graph. Statist. 1, 1992) on the points of the sampling entries.  Everything is in SCORE space: the caller maps
+ * limits to normal scores (mlmc_density_scores_batch) and brings the factor.
+ *   L [M][M] host, row-major, lower triangular with a positive diagonal; the upper part is ignored and rows need not have unit norm
+ *     (a conditional factor has not).  1 <= M <= MLMC_BOX_PROB_MAX_M.
+ *   lo, hi [B][M] host, +-inf allowed; shift [B][M] host (NULL: zeros), the mean of the scores per box; seeds [R] host uint64;
+ *   streams [M-1] host uint32 (NULL: i); first, n: the points first .. first + n - 1, n >= 1, first + n <= 2^52.
+ *   flags: 0 or MLMC_SAMPLE_SOBOL.  With it w_i of point j under seed r is coordinate d = streams[i] of point j of the scrambled
+ *     Sobol' sequence keyed by seeds[r] (above); without it the Philox uniform j of stream streams[i] under seeds[r]
+ *     (mlmc_density_sample_batch).  Either is an odd multiple of 2^-53 in (0, 1).
+ * The integrand of point j, box b, seed r, every operation ONE fp64 operation rounded to nearest (no FMA anywhere), f = 1 and for
+ * i = 0 .. M-1:
+ *     s   = shift[b][i], then for k = 0 .. i-1 ascending   s = s + (L[i][k] * y_k)      (0 without a shift)
+ *     a'  = (lo[b][i] - s) / L[i][i],   b' = (hi[b][i] - s) / L[i][i]
+ *     if a' > 0 (the reflected side):   d = normcdf(-b'), e = normcdf(-a'), sign = -1
+ *     else:                             d = normcdf(a'),  e = normcdf(b'),  sign = +1
+ *     width = e - d if lo[b][i] < hi[b][i], else 0;      f = f * width
+ *     for i < M-1:   y_i = sign * normcdfinv(min(max(d + (w_i * width), 2^-1022), 1 - 2^-53))
+ *   The reflection makes an upper-tail box a difference of two small numbers instead of two numbers next to 1; the clamp keeps
+ *   every y finite (|y| < 37.6), so no step forms inf - inf or 0 * inf: a box with lo >= hi in some component has f = 0 exactly,
+ *   an f that has become 0 stays 0 and never NaN (a box at [40, 41] gives 0), and the box (-inf, inf)^M gives exactly 1.
+ * mean [R][B] host: the sum of f over the n points, divided by n.  The sum is a fixed tree: the points are taken in blocks of 64
+ *   aligned to multiples of 64 of the index j; within a block, with +0 for the j outside [first, first + n), v_l += v_(l ^ 32), then
+ *   ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; of the blocks' sums p_0, p_1, ... thread t < 256 adds p_t, p_(t + 256), ... in ascending order from 0, and
+ *   the 256 sums fold by halves (t < 128: v_t += v_(t + 128), then 64, ... 1).  The tree is fixed by (first, n) alone: mean[r][b] is
+ *   bitwise repeatable, depends on (L, box b, seed r, streams, first, n, flag) alone -- not on B, on R, on the position of the box
+ *   or the seed, on how the launches are split (MLMC_BOX_PROB_BLOCK_POINTS in the environment, read per call, sets the points of a
+ *   launch: a test aid) -- and is the same with and without f_out.  M = 1 uses no point: mean = e - d exactly, for any n.
+ * f_out [R][B][n] (may be NULL), host or device by mem_kind: the integrand, column j - first.
+ * Errors: M < 1 or above the cap, B < 1, R < 1, n < 1, first < 0, first + n > 2^52, a null array, bad mem_kind, unknown bits in
+ *   flags, MLMC_SAMPLE_ANTITHETIC (it does not apply), a diagonal entry that is not finite and positive or a lower entry that is
+ *   not finite (names the row), a NaN limit or a shift that is not finite (names box and component), with the flag a stream
+ *   >= 1024 (names the coordinate); more than 1 GiB of block sums (R * B * n / 64 doubles) or, with a host f_out, 64 points of all
+ *   pairs beyond 192 MiB say to split boxes or seeds across calls, which changes no value.
+ * One wave per (seed, box, block of 64 points), a lane per point, y in LDS (512 (M - 1) bytes per wave); no atomics; one host
+ * wait. */
+#define MLMC_BOX_PROB_MAX_M 128
+int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
+                               const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
+                               double *f_out, int mem_kind);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

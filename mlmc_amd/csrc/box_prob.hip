@@ -1,0 +1,249 @@
+// mlmc_copula_box_prob_batch (include/mlmc_hip.h): rectangle probabilities of a correlated normal vector by Genz's separation of
+// variables, on the device (gfx950).
+//
+//   k_box_prob : one workgroup of ONE wave owns the 64 points j = 64 a .. 64 a + 63 (a = an absolute block of the sequence) of one
+//                (seed, box); a lane owns one point and runs the M-step chain of the header: two normcdf, one normcdfinv and the
+//                triangular dot product of step i.  The lane's y_0 .. y_{M-2} live in LDS as y[k][lane] (dynamic, 512 (M - 1) bytes
+//                per workgroup: small M keeps its occupancy, the cap M = 128 takes 65024 bytes); a lane reads back only what it
+//                wrote itself, so the chain needs no barrier.  L, the limits and the shift are uniform over the wave: the compiler
+//                fetches them with scalar loads.  Under MLMC_SAMPLE_SOBOL the block is aligned to 64 points, so the Gray code of
+//                j = 64 a ^ lane is G(64 a) ^ G(lane): the part of the block is an XOR of scalar loads, the lane adds at most six
+//                of the words V'[0 .. 5].  The wave sums its 64 values in a fixed butterfly and lane 0 stores the block's partial.
+//   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
+// The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
+// k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
+// fixed by (first, n) alone.  Launches are split by whole blocks, so no value depends on the split.
+// The chain loops over i around normcdf / normcdfinv; copula.hip and sobol.hip avoid such a loop because the inlined functions'
+// constants then stay in registers.  Here the two are called through functions that are not inlined (below); the resource figures
+// are in DESIGN.md 3.5.17.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "copula.hpp"
+#include "sobol.hpp"
+
+namespace mlmc {
+
+constexpr int BOX_LANES = 64;                          // points of a block = lanes of its wave
+constexpr int BOX_MEAN_THREADS = 256;
+constexpr size_t BOX_F_BYTES = (size_t)192 << 20;      // the staged integrand of a launch (host f_out)
+constexpr size_t BOX_PARTIAL_BYTES = (size_t)1 << 30;  // the partials of a call
+
+// coordinate of point j = 64 a ^ lane from its dimension's row: the block's part on the scalar unit, the lane's six bits selected
+__device__ __forceinline__ double box_sobol_unit(const uint64_t *__restrict__ row, uint64_t a, int lane) {
+    const uint64_t j0 = a << 6;
+    uint64_t g = j0 ^ (j0 >> 1), m = row[SOBOL_BITS];
+    while (g) {
+        m ^= row[__builtin_ctzll(g)];                  // bit 52 only for the lanes beyond the last point of a call that ends at 2^52
+        g &= g - 1;
+    }
+    const uint32_t gl = (uint32_t)lane ^ ((uint32_t)lane >> 1);
+#pragma unroll
+    for (int t = 0; t < 6; ++t) m ^= ((gl >> t) & 1u) ? row[t] : (uint64_t)0;
+    return sobol_unit(m);
+}
+
+// Called, not inlined: inlined into the loop over i their constants stay in registers across it (256 VGPRs, 156 AGPRs and scratch
+// instead of 30 / 38 VGPRs and none); a call costs a few cycles next to the hundred-odd fp64 operations of a body.
+__device__ __attribute__((noinline)) double box_normcdf(double x) { return normcdf(x); }
+__device__ __attribute__((noinline)) double box_normcdfinv(double p) { return normcdfinv(p); }
+
+// grid (blocks of the launch, boxes, seeds); box = b0 + blockIdx.y, seed = r0 + blockIdx.z
+template <bool SOBOL>
+__global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__restrict__ L, const double *__restrict__ lo,
+                                                        const double *__restrict__ hi, const double *__restrict__ shift, int B, int b0,
+                                                        const uint64_t *__restrict__ seeds, int r0, const uint32_t *__restrict__ streams,
+                                                        const uint64_t *__restrict__ table, int table_rows, int64_t first, int64_t n,
+                                                        int64_t blk0, int64_t call_blk0, int64_t call_blocks,
+                                                        double *__restrict__ partials, double *__restrict__ f_out, int64_t ldf,
+                                                        int64_t c_off) {
+    extern __shared__ double ys[];                     // y[k][lane]
+    const int lane = threadIdx.x;
+    const int b = b0 + (int)blockIdx.y, r = r0 + (int)blockIdx.z;
+    const int64_t a = blk0 + blockIdx.x;
+    const int64_t j = (a << 6) | lane;
+    const bool active = j >= first && j < first + n;
+    const double *lo_b = lo + (int64_t)b * M, *hi_b = hi + (int64_t)b * M;
+    const double *sh_b = shift ? shift + (int64_t)b * M : nullptr;
+    const uint64_t seed = seeds[r];
+    const uint64_t *tab = SOBOL ? table + (int64_t)r * table_rows * SOBOL_ROW : nullptr;
+    double f = 1.0;
+    for (int i = 0; i < M; ++i) {
+        const double *Li = L + (int64_t)i * M;
+        double s = sh_b ? sh_b[i] : 0.0;
+        for (int k = 0; k < i; ++k) s = __dadd_rn(s, __dmul_rn(Li[k], ys[k * BOX_LANES + lane]));
+        const double lii = Li[i], l = lo_b[i], h = hi_b[i];
+        const double ap = (l - s) / lii, bp = (h - s) / lii;
+        const bool refl = ap > 0.0;
+        const double d = box_normcdf(refl ? -bp : ap), e = box_normcdf(refl ? -ap : bp);
+        const double width = l < h ? e - d : 0.0;
+        f *= width;
+        if (i < M - 1) {
+            double w;
+            if constexpr (SOBOL) w = box_sobol_unit(tab + (int64_t)streams[i] * SOBOL_ROW, (uint64_t)a, lane);
+            else w = q_uniform(seed, streams[i], (uint64_t)j);
+            const double p = fmin(fmax(__dadd_rn(d, __dmul_rn(w, width)), 0x1p-1022), 1.0 - 0x1p-53);
+            const double y = box_normcdfinv(p);
+            ys[i * BOX_LANES + lane] = refl ? -y : y;
+        }
+    }
+    if (active && f_out) f_out[((int64_t)r * B + b) * ldf + (j - first - c_off)] = f;
+    double v = active ? f : 0.0;
+#pragma unroll
+    for (int o = BOX_LANES / 2; o; o >>= 1) v += __shfl_xor(v, o);
+    // M = 1 uses no point: every lane holds e - d, and k_box_mean hands it on as it is
+    if (lane == 0) partials[((int64_t)r * B + b) * call_blocks + (a - call_blk0)] = M == 1 ? f : v;
+}
+
+__global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__restrict__ partials, int64_t call_blocks, int64_t n,
+                                                               int single, double *__restrict__ mean) {
+    __shared__ double sh[BOX_MEAN_THREADS];
+    const int t = threadIdx.x;
+    const double *p = partials + (int64_t)blockIdx.x * call_blocks;
+    double acc = 0.0;
+    for (int64_t k = t; k < call_blocks; k += BOX_MEAN_THREADS) acc += p[k];
+    sh[t] = acc;
+    __syncthreads();
+    for (int s = BOX_MEAN_THREADS / 2; s; s >>= 1) {
+        if (t < s) sh[t] += sh[t + s];
+        __syncthreads();
+    }
+    if (t == 0) mean[blockIdx.x] = single ? p[0] : sh[0] / (double)n;
+}
+
+static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
+                    const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
+                    int mem_kind) {
+    const std::string e(fn);
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (M < 1) return fail(e + ": M < 1");
+    if (M > MLMC_BOX_PROB_MAX_M) return fail(e + ": M = " + std::to_string(M) + " is above the cap " + std::to_string(MLMC_BOX_PROB_MAX_M));
+    if (B < 1) return fail(e + ": B < 1");
+    if (R < 1) return fail(e + ": R < 1");
+    if (!L || !lo || !hi || !seeds || !mean) return fail(e + ": null argument");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(e + ": bad mem_kind");
+    if (flags & ~(MLMC_SAMPLE_ANTITHETIC | MLMC_SAMPLE_SOBOL)) return fail(e + ": unknown bits in flags");
+    if (flags & MLMC_SAMPLE_ANTITHETIC) return fail(e + ": MLMC_SAMPLE_ANTITHETIC does not apply to this entry");
+    const bool sobol = flags & MLMC_SAMPLE_SOBOL;
+    if (n < 1) return fail(e + ": n < 1");
+    if (first < 0) return fail(e + ": first < 0");
+    if (first > SOBOL_MAX_INDEX - n) return fail(e + ": first + n is beyond 2^52");
+    for (int i = 0; i < M; ++i) {
+        const double dg = L[(size_t)i * M + i];
+        if (!std::isfinite(dg) || !(dg > 0.0))
+            return fail(e + ": factor row " + std::to_string(i) + ": the diagonal entry must be finite and positive");
+        for (int k = 0; k < i; ++k)
+            if (!std::isfinite(L[(size_t)i * M + k]))
+                return fail(e + ": factor row " + std::to_string(i) + ": entry " + std::to_string(k) + " is not finite");
+    }
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < M; ++i) {
+            const size_t at = (size_t)b * M + i;
+            if (std::isnan(lo[at]) || std::isnan(hi[at]))
+                return fail(e + ": box " + std::to_string(b) + ", component " + std::to_string(i) + ": a limit is NaN");
+            if (shift && !std::isfinite(shift[at]))
+                return fail(e + ": box " + std::to_string(b) + ", component " + std::to_string(i) + ": the shift is not finite");
+        }
+    // the coordinates: streams (Philox), or the rows of the call's distinct dimensions, one table per seed (MLMC_SAMPLE_SOBOL)
+    const int nc = M - 1;
+    std::vector<uint32_t> coord((size_t)nc);
+    std::vector<uint64_t> tables;
+    int table_rows = 0;
+    if (sobol && nc > 0) {
+        std::vector<uint64_t> tab;
+        std::vector<uint32_t> slot;
+        for (int r = 0; r < R; ++r) {
+            if (sobol_call_table(fn, "coordinate", seeds[r], streams, nc, tab, slot)) return 1;
+            tables.insert(tables.end(), tab.begin(), tab.end());
+        }
+        table_rows = (int)(tab.size() / SOBOL_ROW);
+        coord = slot;
+    } else
+        for (int i = 0; i < nc; ++i) coord[i] = streams ? streams[i] : (uint32_t)i;
+
+    const int64_t call_blk0 = first >> 6, call_blocks = ((first + n - 1) >> 6) - call_blk0 + 1;
+    const size_t pairs = (size_t)R * (size_t)B;
+    if ((double)pairs * (double)call_blocks * sizeof(double) > (double)BOX_PARTIAL_BYTES)
+        return fail(e + ": R * B * n / 64 partial sums exceed 1 GiB: split the boxes or the seeds across calls (no value depends on it)");
+    // blocks of a launch: all of them, or what keeps the staged integrand within BOX_F_BYTES (MLMC_BOX_PROB_BLOCK_POINTS in the
+    // environment, read per call, sets the points of a launch, rounded up to whole blocks: a test aid, no value depends on it)
+    const bool stage = f_out && mem_kind == MLMC_HOST;
+    int64_t lb = std::min<int64_t>(call_blocks, 0x7fffffff);
+    if (stage) {
+        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * pairs)));
+        if (lb < 1) return fail(e + ": the integrand of one block of 64 points of R * B pairs exceeds 192 MiB: split the boxes or the seeds across calls");
+    }
+    if (const char *env = std::getenv("MLMC_BOX_PROB_BLOCK_POINTS")) {
+        const long long v = std::atoll(env);
+        if (v > 0) lb = std::min<int64_t>(lb, (v + BOX_LANES - 1) / BOX_LANES);
+    }
+    const int64_t ldf = stage ? lb * BOX_LANES : n;
+
+    // what goes up: L | lo | hi | shift | seeds | tables | coordinates (uint32)
+    const size_t nL = (size_t)M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nc + 1) / 2;
+    const size_t n_in = nL + 2 * nbx + nsh + (size_t)R + ntab + nco;
+    std::vector<double> packed(n_in);
+    double *q = packed.data();
+    std::memcpy(q, L, sizeof(double) * nL), q += nL;
+    std::memcpy(q, lo, sizeof(double) * nbx), q += nbx;
+    std::memcpy(q, hi, sizeof(double) * nbx), q += nbx;
+    if (nsh) std::memcpy(q, shift, sizeof(double) * nsh), q += nsh;
+    std::memcpy(q, seeds, sizeof(uint64_t) * (size_t)R), q += R;
+    if (ntab) std::memcpy(q, tables.data(), sizeof(uint64_t) * ntab), q += ntab;
+    if (nc) std::memcpy(q, coord.data(), sizeof(uint32_t) * (size_t)nc);
+
+    const size_t b_in = mm_align(sizeof(double) * n_in), b_part = mm_align(sizeof(double) * pairs * (size_t)call_blocks);
+    const size_t b_mean = mm_align(sizeof(double) * pairs), b_f = stage ? mm_align(sizeof(double) * pairs * (size_t)ldf) : 0;
+    static MultiWorkspace ws;
+    if (ws.reserve(b_in + b_part + b_mean + b_f)) return 1;
+    double *d_in = (double *)ws.dev, *d_part = (double *)(ws.dev + b_in), *d_mean = (double *)(ws.dev + b_in + b_part);
+    double *d_f = stage ? (double *)(ws.dev + b_in + b_part + b_mean) : f_out;
+    hipStream_t st = rt().stream;
+    MLMC_HIP_CHECK(hipMemcpyAsync(d_in, packed.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+    const double *d_L = d_in, *d_lo = d_L + nL, *d_hi = d_lo + nbx, *d_shift = nsh ? d_hi + nbx : nullptr;
+    const uint64_t *d_seeds = (const uint64_t *)(d_hi + nbx + nsh), *d_tab = d_seeds + R;
+    const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
+
+    const size_t lds = sizeof(double) * BOX_LANES * (size_t)nc;
+    const auto kernel = sobol ? k_box_prob<true> : k_box_prob<false>;
+    for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
+        const int64_t kb = std::min(lb, call_blocks - k0);
+        // the first point of the launch within the call: column 0 of the staged integrand
+        const int64_t c_lo = std::max<int64_t>(((call_blk0 + k0) << 6) - first, 0);
+        const int64_t c_hi = std::min<int64_t>(((call_blk0 + k0 + kb) << 6) - first, n);
+        for (int r0 = 0; r0 < R; r0 += 65535)
+            for (int b0 = 0; b0 < B; b0 += 65535) {
+                const dim3 grid((unsigned)kb, (unsigned)std::min(B - b0, 65535), (unsigned)std::min(R - r0, 65535));
+                hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, d_shift, (int)B, b0, d_seeds, r0, d_coord,
+                                   d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part, d_f, ldf,
+                                   stage ? c_lo : (int64_t)0);
+            }
+        MLMC_HIP_CHECK(hipGetLastError());
+        if (stage)
+            MLMC_HIP_CHECK(hipMemcpy2DAsync(f_out + c_lo, sizeof(double) * (size_t)n, d_f, sizeof(double) * (size_t)ldf,
+                                            sizeof(double) * (size_t)(c_hi - c_lo), pairs, hipMemcpyDeviceToHost, st));
+    }
+    hipLaunchKernelGGL(k_box_mean, dim3((unsigned)pairs), dim3(BOX_MEAN_THREADS), 0, st, (const double *)d_part, call_blocks, n,
+                       (int)(M == 1), d_mean);
+    MLMC_HIP_CHECK(hipGetLastError());
+    MLMC_HIP_CHECK(hipMemcpyAsync(mean, d_mean, sizeof(double) * pairs, hipMemcpyDeviceToHost, st));
+    MLMC_HIP_CHECK(wait_stream(st));
+    return 0;
+}
+
+}  // namespace mlmc
+
+using namespace mlmc;
+
+extern "C" {
+
+int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
+                               const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
+                               double *f_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind);
+}
+
+}  // extern "C"

@@ -783,7 +783,7 @@ class Estimate:
         """Seeded JOINT draws of all scalar components of the quantity, in one batched device call
         (tool.simple_distribution.joint_samples): the maximum-entropy marginals of `construct_densities` joined by a Gaussian
         copula.  Column j of the result is one scenario of the whole vector: use it for the sum of the components, the CVaR of a
-        portfolio of outputs or joint exceedance.
+        portfolio of outputs or joint exceedance (small joint probabilities: `estimate_joint_exceedance`, which does not count).
 
         What the dependence is: the copula takes the correlation of the NORMAL SCORES Phi^-1(F_m(X_m)), and there are two
         estimates of it to choose from.
@@ -851,6 +851,49 @@ class Estimate:
                                                         antithetic=antithetic, device=device, qmc=qmc)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return draws, success, cond[2]
+
+    def estimate_joint_probability(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
+                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+        """Probability that the components lie in a box AT ONCE, P(lower_m < X_m < upper_m for all m), under the marginals and the
+        Gaussian copula of `sample_joint`, for B boxes in one batched device call (tool.simple_distribution.joint_probabilities):
+        Genz's separation of variables on scrambled Sobol' points.  Its error is relative and falls like 1 / n, so the small
+        probabilities of a reliability question (1e-4 .. 1e-8) are resolved, where counting the scenarios of `sample_joint`
+        would need 1e8 .. 1e12 draws.  Components that no box constrains (limits -inf / +inf) are dropped before the
+        factorisation and cost nothing.
+        :param lower, upper: broadcast to [B, M] in the components' own units; with `given` to [B, q] over the components that are
+            not given.  +-inf, or a value at or beyond an end of the component's domain, does not constrain that side
+        :param n: points per seed; a power of two with `first` a multiple of it
+        :param seeds: one independent scramble each; the spread of their means is the error bar
+        :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
+        :param given: None, or as in sample_conditional: the probability is conditional on the given values; arrays [B] pair
+            with the boxes
+        :param densities: as in estimate_component_quantiles
+        :param qmc: False: Philox uniforms instead of Sobol' points (plain Monte Carlo over the unit cube)
+        :return: (JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds), success [M])"""
+        from .tool import simple_distribution
+        what = "estimate_joint_probability"
+        n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
+        if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
+            raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
+        corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        result = simple_distribution.joint_probabilities([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
+                                                         given=given, first=first, qmc=qmc)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return result, success
+
+    def estimate_joint_exceedance(self, thresholds, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
+                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+        """P(X_m > t_m for all constrained m): `estimate_joint_probability` with lower = thresholds and upper = +inf.
+        :param thresholds: broadcast to [B, M]; -inf leaves a component unconstrained
+        :return: as estimate_joint_probability"""
+        t = np.asarray(thresholds, dtype=np.float64)
+        if np.any(np.isnan(t)):
+            raise ValueError("estimate_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
+        return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
+                                               orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
+                                               first=first, qmc=qmc)
 
     def estimate_conditional_quantiles(self, probs, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                        densities=None):

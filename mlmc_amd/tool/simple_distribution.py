@@ -758,6 +758,215 @@ def conditional_cdfs(distrs, values, given, corr):
     return out[0] if scalar else out
 
 
+JointProbability = collections.namedtuple("JointProbability", "prob stderr replicates n seeds")
+
+
+def _box_call_args(what, n, seeds, first):
+    """(n, seeds [R] uint64, first) of a box-probability call, checked"""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(what + ": n must be a positive integer")
+    if isinstance(first, (bool, np.bool_)) or not isinstance(first, (int, np.integer)) or first < 0:
+        raise ValueError(what + ": first must be a non-negative integer")
+    if int(first) + int(n) > 2 ** 52:
+        raise ValueError(what + ": first + n must not exceed 2^52")
+    try:
+        seed_list = list(seeds)
+    except TypeError:
+        raise ValueError(what + ": seeds must be a sequence of integers in 0 .. 2^64 - 1") from None
+    if not seed_list:
+        raise ValueError(what + ": at least one seed is required")
+    for s in seed_list:
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < 2 ** 64:
+            raise ValueError(what + ": seeds must be integers in 0 .. 2^64 - 1, got {!r}".format(s))
+    return int(n), np.array([int(s) for s in seed_list], dtype=np.uint64), int(first)
+
+
+def _box_limits(what, lower, upper, M, name="M"):
+    """lower and upper broadcast to one [B, M] pair; a NaN is an error that names box and component"""
+    lo, hi = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    if lo.ndim > 2 or hi.ndim > 2:
+        raise ValueError(what + ": lower and upper must broadcast to [B, {}]".format(name))
+    try:
+        shape = np.broadcast_shapes(lo.shape, hi.shape, (1, M))
+    except ValueError:
+        raise ValueError(what + ": lower {} and upper {} do not broadcast to [B, {}] with {} = {}".format(
+            lo.shape, hi.shape, name, name, M)) from None
+    if shape[1] != M or shape[0] < 1:
+        raise ValueError(what + ": lower {} and upper {} do not broadcast to [B, {}] with {} = {}".format(
+            lo.shape, hi.shape, name, name, M))
+    lo, hi = np.ascontiguousarray(np.broadcast_to(lo, shape)), np.ascontiguousarray(np.broadcast_to(hi, shape))
+    bad = np.argwhere(np.isnan(lo) | np.isnan(hi))
+    if bad.size:
+        raise ValueError(what + ": a limit of box {}, component {} is NaN".format(int(bad[0, 0]), int(bad[0, 1])))
+    return lo, hi
+
+
+def _box_streams(what, streams, M, qmc):
+    if streams is None:
+        return None
+    st = np.asarray(streams)
+    if st.shape != (M - 1,) or (st.size and (st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32))):
+        raise ValueError(what + ": streams must be one integer in 0 .. 2^32 - 1 per coordinate, {} of them".format(M - 1))
+    if qmc and st.size and np.any(st.astype(np.uint64) >= 1024):
+        raise ValueError(what + ": with qmc the streams are Sobol' dimensions and must be below 1024")
+    return np.ascontiguousarray(st.astype(np.uint32))
+
+
+def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
+                             device=False):
+    """P(lower < Y < upper) for Y = shift + F z, z standard normal, for B boxes and R seeds through ONE device call
+    (mlmc_copula_box_prob_batch): Genz's separation of variables, which conditions through the lower-triangular factor with one
+    Phi^-1 and two Phi per component, so that the integrand is a smooth function on the unit cube.  Everything is in SCORE space
+    (`joint_probabilities` maps limits in the components' own units).  On scrambled Sobol' points (qmc=True) the error falls
+    like 1 / n and is relative: a probability of 1e-8 is resolved as well as one of 0.1, which counting scenarios of
+    `joint_samples` cannot do.  Each seed gives one independent estimate; `prob` is their mean and `stderr` the sample standard
+    deviation of the R means over sqrt(R) (NaN for one seed).  A replicate depends on (factor, box, seed, streams, first, n, qmc)
+    alone and is bitwise repeatable.
+    :param factor: [M, M] lower triangular with a positive diagonal (the upper part is ignored); rows need not have unit norm, so
+        F_c of `conditional_factor` is accepted.  M <= 128
+    :param lower, upper: broadcast to [B, M], +-inf allowed; a box that is empty in some component has probability exactly 0
+    :param n: points per seed, indices first .. first + n - 1; with qmc a power of two with `first` a multiple of it
+    :param seeds: R integers in 0 .. 2^64 - 1
+    :param shift: None or the mean of the scores, broadcast to [B, M]
+    :param streams: one stream (qmc: Sobol' dimension below 1024) per coordinate, M - 1 of them; default: i
+    :param qmc: scrambled Sobol' points (MLMC_SAMPLE_SOBOL); False: Philox uniforms
+    :param return_integrand: also return the integrand [R, B, n] (a float64 torch device tensor with device=True)
+    :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
+    what = "copula_box_probabilities"
+    f = np.array(factor, dtype=np.float64)
+    if f.ndim != 2 or f.shape[0] != f.shape[1] or f.shape[0] < 1:
+        raise ValueError(what + ": the factor must be a square matrix, got shape {}".format(f.shape))
+    M = f.shape[0]
+    if M > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} components exceed the cap of {}".format(M, _lib.BOX_PROB_MAX_M))
+    f = np.ascontiguousarray(np.tril(f))
+    diag = np.diag(f)
+    bad = np.flatnonzero(~(np.isfinite(diag) & (diag > 0)))
+    if bad.size:
+        raise ValueError(what + ": the diagonal entry of factor row {} must be finite and positive, got {}".format(
+            int(bad[0]), diag[bad[0]]))
+    if not np.all(np.isfinite(f)):
+        raise ValueError(what + ": factor row {} has an entry that is not finite".format(int(np.argwhere(~np.isfinite(f))[0, 0])))
+    lo, hi = _box_limits(what, lower, upper, M)
+    B = lo.shape[0]
+    if shift is not None:
+        sh = np.asarray(shift, dtype=np.float64)
+        try:
+            sh = np.ascontiguousarray(np.broadcast_to(sh, (B, M)))
+        except ValueError:
+            raise ValueError(what + ": shift {} does not broadcast to [B, M] = {}".format(sh.shape, (B, M))) from None
+        if not np.all(np.isfinite(sh)):
+            raise ValueError(what + ": the shift must be finite")
+        shift = sh
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    streams = _box_streams(what, streams, M, qmc)
+    R = seeds.size
+    flags = _lib.SAMPLE_SOBOL if qmc else 0
+    mean = np.empty((R, B))
+    integrand, kind = None, _lib.HOST
+    if return_integrand and device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        integrand = torch.empty((R, B, n), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()         # the library writes it on its own stream
+        kind = _lib.DEVICE
+    elif return_integrand:
+        integrand = np.empty((R, B, n))
+    _lib.check(_lib.lib().mlmc_copula_box_prob_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R, _lib.ptr(seeds),
+                                                    _lib.ptr(streams), first, n, flags, _lib.ptr(mean), _lib.ptr(integrand), kind))
+    result = _joint_probability(mean, n, seeds)
+    return (result, integrand) if return_integrand else result
+
+
+def _joint_probability(replicates, n, seeds):
+    """JointProbability of the seeds' means [R, B]"""
+    R = replicates.shape[0]
+    prob = replicates.mean(axis=0)
+    stderr = np.std(replicates, axis=0, ddof=1) / np.sqrt(R) if R > 1 else np.full(replicates.shape[1], np.nan)
+    return JointProbability(prob, stderr, replicates, n, seeds)
+
+
+def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True,
+                        return_integrand=False, device=False):
+    """Joint box probabilities P(lower_m < X_m < upper_m for all m) under the Gaussian copula of `joint_samples`, for B boxes in
+    the components' own units through `copula_box_probabilities`; with `given`, conditional on the given values of some
+    components as in `conditional_samples`.  A limit that is +-inf or lies at or beyond an end of its distribution's domain is an
+    infinite score exactly; every other limit goes through ONE `normal_scores` call.  Components that no box of the call
+    constrains are dropped before the factorisation (the marginal law of a Gaussian sub-vector is the sub-matrix of its
+    correlation), so two constrained components out of 64 are a two-dimensional problem.
+    :param lower, upper: broadcast to [B, M]; with `given` to [B, q] over the q components that are not given, ascending
+    :param corr: correlation matrix [M, M] of the normal scores (goes through `correlation_factor`, as in `joint_samples`)
+    :param factor: or a factor [M, K] with rows of unit norm: F F^T is taken as the correlation.  Exactly one of the two
+    :param given: None, or the mapping of `conditional_samples`; arrays [B] pair with the boxes (one box pairs with all sets)
+    :param streams: per coordinate of the REDUCED problem (constrained components - 1)
+    :param n, seeds, first, qmc, return_integrand, device: as in `copula_box_probabilities`
+    :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
+    what = "joint_probabilities"
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    if (corr is None) == (factor is None):
+        raise ValueError(what + ": exactly one of corr and factor must be given")
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    if len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1:
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    if factor is not None:
+        fac = np.asarray(factor, dtype=np.float64)
+        if fac.ndim != 2 or fac.shape[0] != M or fac.shape[1] < 1 or not np.all(np.isfinite(fac)):
+            raise ValueError(what + ": the factor must be a finite [M, K] matrix with M = {} distributions".format(M))
+        corr = fac @ fac.T
+    corr = np.array(corr, dtype=np.float64)
+    if corr.shape != (M, M):
+        raise ValueError(what + ": corr must be [M, M] with M = {} distributions, got shape {}".format(M, corr.shape))
+    if given is not None:
+        observed, values, _ = _parse_given(what, given, M)
+        free = np.setdiff1d(np.arange(M, dtype=np.int64), observed)
+    else:
+        observed, values, free = np.zeros(0, dtype=np.int64), np.zeros((0, 1)), np.arange(M, dtype=np.int64)
+    q = free.size
+    lo, hi = _box_limits(what, lower, upper, q, "q" if given is not None else "M")
+    B = lo.shape[0]
+    Bg = values.shape[1]
+    if Bg != 1 and B != 1 and Bg != B:
+        raise ValueError(what + ": the arrays of given hold {} sets, there are {} boxes".format(Bg, B))
+    if B == 1 and Bg > 1:
+        lo, hi = np.repeat(lo, Bg, axis=0), np.repeat(hi, Bg, axis=0)
+        B = Bg
+    # scores of the limits: infinite where the limit is, or lies at or beyond an end of the domain; the rest in one device call
+    a = np.array([float(distrs[m].domain[0]) for m in free])
+    b = np.array([float(distrs[m].domain[1]) for m in free])
+    z_lo, z_hi = np.full((B, q), -np.inf), np.full((B, q), np.inf)
+    z_lo[lo >= b[None, :]] = np.inf
+    z_hi[hi <= a[None, :]] = -np.inf
+    in_lo, in_hi = (lo > a[None, :]) & (lo < b[None, :]), (hi > a[None, :]) & (hi < b[None, :])
+    keep = np.flatnonzero(np.any((z_lo > 0) | in_lo | (z_hi < 0) | in_hi, axis=0))           # constrained in some box
+    streams = _box_streams(what, streams, max(keep.size, 1), qmc)
+    if keep.size > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
+    if keep.size == 0:
+        ones = _joint_probability(np.ones((seeds.size, B)), n, seeds)
+        return (ones, None) if return_integrand else ones
+    if np.any(in_lo) or np.any(in_hi):
+        mid = 0.5 * (a + b)
+        x = np.concatenate([np.where(in_lo, lo, mid[None, :]), np.where(in_hi, hi, mid[None, :])], axis=0).T     # [q, 2 B]
+        z = normal_scores([distrs[m] for m in free[keep]], np.ascontiguousarray(x[keep]))
+        z_lo[:, keep] = np.where(in_lo[:, keep], z[:, :B].T, z_lo[:, keep])
+        z_hi[:, keep] = np.where(in_hi[:, keep], z[:, B:].T, z_hi[:, keep])
+        if np.any(np.isnan(z_lo)) or np.any(np.isnan(z_hi)):
+            raise ValueError(what + ": a limit has no normal score (a distribution without a positive finite mass?)")
+    if observed.size:
+        _, _, _, _, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
+        cov = fc @ fc.T
+        low = np.linalg.cholesky(cov[np.ix_(keep, keep)])
+        shift = np.ascontiguousarray(np.broadcast_to(mu[:, keep], (B, keep.size)))
+    else:
+        low = correlation_factor(corr[np.ix_(free[keep], free[keep])])[0]
+        shift = None
+    return copula_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], shift=shift, streams=streams,
+                                    first=first, qmc=qmc, return_integrand=return_integrand, device=device)
+
+
 def _scores_problem_args(distrs, what):
     """the problem arguments of mlmc_density_scores_batch for a list of distributions, ready to be splatted into the call:
     (M, handles, r1, lam, sig, a, b, n_intervals, gauss_degree) as ctypes values, and the arrays that must outlive the call"""

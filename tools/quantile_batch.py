@@ -82,9 +82,15 @@ call each:
                                                 kernels, [min, median, max]; qmc_over_philox_wall / _kernel the ratios of the medians
 (b) the RMS error over seeds 1 .. 8 of the mean of g(u) from joint_samples for n = 2^10, 2^12, .. 2^20 with and without qmc:
 g = prod_m (1 + 0.8 (u_m - 1/2)) under M = K = 4, F = I, and g = u_0 u_1 under the 3 x 3 correlation of the tests
+--boxprob: copula_box_probabilities of B copies of the box (t, inf)^M under equicorrelation 1/2 with 8
+seeds per call (t = 0: the orthant, exactly 1 / (M + 1); for M = 12 also the t at which the probability is 1e-6, against a
+one-dimensional quadrature), M = 2 / 12 / 64, B = 1 / 64, n = 2^12 .. 2^20 (--config M,B,n: one orthant shape):
+  call_ms, rel_rms             wall time of the call and the RMS over the seeds of a seed's relative error
+  count_ms_per_seed, count_rel_rms, count_zero_seeds   the counting route at the same n: joint_samples(device=True), the comparison
+                               of the copula uniforms with Phi(t) and the mean in torch, one call per seed
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --scores |
-                                                              --conditional | --qmc] [--reps K]"""
+                                                              --conditional | --qmc | --boxprob] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -566,6 +572,43 @@ def qmc_errors(quick):
     return rows
 
 
+def equicorrelated_exceedance(M, t, rho=0.5):
+    """P(Y_m > t for all m) for M equicorrelated standard normals: with a common factor x, Y_m = sqrt(rho) x + sqrt(1 - rho) e_m, the
+    integral over x of phi(x) Phi((sqrt(rho) x - t) / sqrt(1 - rho))^M, by adaptive quadrature"""
+    from scipy.special import log_ndtr
+    g = lambda x: np.exp(-0.5 * x * x + M * log_ndtr((np.sqrt(rho) * x - t) / np.sqrt(1.0 - rho))) / np.sqrt(2.0 * np.pi)
+    return quad(g, -12.0, 12.0, epsabs=0.0, epsrel=1e-12, limit=400)[0]
+
+
+def boxprob_shape(M, B, n, reps, t, seeds=tuple(range(1, 9))):
+    """copula_box_probabilities of B copies of the box (t, inf)^M under equicorrelation 1/2 (t = 0: the orthant, exactly
+    1 / (M + 1); otherwise the one-dimensional integral above), R = 8 seeds in one call: the time per call and the RMS over the seeds
+    of the relative error of a seed's mean, next to the counting route at the same n on the same box: joint_samples on the
+    device (one call per seed), the comparison of the copula uniforms with Phi(t) and the mean in torch."""
+    from scipy.special import ndtr
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    low = np.linalg.cholesky(corr)
+    exact = 1.0 / (M + 1) if t == 0.0 else equicorrelated_exceedance(M, t)
+    lo, hi = np.full((B, M), t), np.full((B, M), np.inf)
+    ms, res = timed(lambda: sd.copula_box_probabilities(low, lo, hi, n, seeds), reps)
+    rms = float(np.sqrt(np.mean(np.square(res.replicates[:, 0] / exact - 1.0))))
+    distrs, _ = mixtures(M, 9, seed=5)
+    factor = low / np.sqrt(np.sum(low * low, axis=1))[:, None]
+    level = float(ndtr(t))
+
+    def count(seed):
+        u = sd.joint_samples(distrs, n, seed, factor=factor, device=True, return_uniforms=True)[1]
+        return float(torch.all(u > level, dim=0).double().mean())
+    count_ms, _ = timed(lambda: count(seeds[0]), reps)
+    counted = np.array([count(s) for s in seeds])
+    return dict(M=M, B=B, n=n, R=len(seeds), threshold=round(t, 4), exact=float("%.6g" % exact), prob=float("%.6g" % res.prob[0]),
+                stderr=float("%.3g" % res.stderr[0]), call_ms=round(ms, 3), ms_per_box_and_seed=round(ms / (B * len(seeds)), 4),
+                rel_rms=float("%.3g" % rms), count_ms_per_seed=round(count_ms, 3),
+                count_rel_rms=float("%.3g" % np.sqrt(np.mean(np.square(counted / exact - 1.0)))),
+                count_zero_seeds=int(np.sum(counted == 0.0)))
+
+
 def scores_shape(M, R1, n, reps, levels=0):
     """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
     device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
@@ -668,12 +711,25 @@ def main():
                                                                "joint_samples of as many draws (DESIGN.md section 3.5.15)")
     ap.add_argument("--qmc", action="store_true", help="samples / joint_samples / conditional_samples with and without qmc, and the RMS "
                                                        "error of two integrals against n (DESIGN.md section 3.5.16)")
+    ap.add_argument("--boxprob", action="store_true", help="copula_box_probabilities against closed forms, next to counting the "
+                                                           "scenarios of joint_samples (DESIGN.md section 3.5.17)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.boxprob:
+        # the orthant under equicorrelation 1/2, and for M = 12 the threshold at which all twelve exceed it with probability 1e-6
+        t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
+        shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
+        shapes += [(12, 1, 2 ** k, t6) for k in (12, 16, 20)]
+        if a.config:
+            M, B, n = (int(v) for v in a.config.split(","))
+            shapes = [(M, B, n, 0.0)]
+        elif a.quick:
+            shapes = [(2, 1, 2 ** 12, 0.0), (12, 3, 2 ** 12, 0.0), (12, 1, 2 ** 12, t6)]
+        out["boxprob"] = [boxprob_shape(M, B, n, a.reps, t) for M, B, n, t in shapes]
     elif a.qmc:
         out["qmc_times"] = qmc_times(a.reps, a.quick)
         out["qmc_errors"] = qmc_errors(a.quick)
