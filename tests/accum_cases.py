@@ -221,7 +221,8 @@ def component_levels(case, m):
 def sums_of(case, dtype=ax.LD, variant="A"):
     """What the entry of `case` must return, in `dtype`: an ax.Sums with n, n_rm [L] and s, sp, S, SP [L, K].  "component":
     n, n_rm [L, M] and s ... [L, M, K], every component from its own desc and its own keep rule.  "cov": s, S are the
-    covariance means [L, R * R] and their scales (sp, SP: None -- the covariance variances are not judged here)."""
+    covariance means [L, R * R] and their scales (sp, SP: None -- the covariance variances, every size, route and kernel of the
+    covariance, are judged by tests/cov_exact.py with the cases of tests/cov_cases.py)."""
     if case.entry == "component":
         per = [ax.level_sums(d, component_levels(case, m), dtype, variant) for m, d in enumerate(case.descs)]
         out = ax.Sums()

@@ -15,6 +15,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from tests import cov_exact as cx
 from tests.test_chebyshev_tables_cpu import DOMAIN, _exact_connection, _lib_table
 
 M = 64
@@ -113,35 +114,6 @@ def test_row_sum_route_on_the_benchmark_samples():
             P[k] = ((2 * k - 1) * tl * P[k - 1] - (k - 1) * P[k - 2]) / k
         return P
 
-    def legendre_diff_sums(tf, tc):                  # c_k sum_n (q_k(f_n) - q_k(c_n)), q_k = 2t q_{k-1} - 4 g_k q_{k-2}
-        out = np.empty(M)
-        state = [(2.0 * t, np.zeros_like(t), np.ones_like(t)) for t in (tf, tc)]
-        c = 1.0
-        out[0] = np.sum(state[0][2] - state[1][2])
-        for k in range(1, M):
-            g4 = 0.0 if k < 2 else 4.0 * ((k - 1) * (k - 1) / ((2 * k - 1) * (2 * k - 3)))
-            state = [(x2, q1, x2 * q1 - g4 * q2) for x2, q2, q1 in state]
-            c = c * (2 * k - 1) / (2 * k)
-            out[k] = c * np.sum(state[0][2] - state[1][2])
-        return out
-
-    def chebyshev_tail_sums(tf, tc):                 # sum_n (T_k(f_n) - T_k(c_n)), k = 64..126
-        state = []
-        for t in (tf, tc):
-            x2 = 2.0 * t
-            a, bb = t.copy(), x2 * t - 1.0            # (T_1, T_2) -> (T_64, T_65) in six doublings, two steps back
-            for _ in range(6):
-                a2 = 2.0 * a
-                a, bb = a2 * a - 1.0, a2 * bb - t
-            p1 = x2 * a - bb                          # T_63
-            p2 = x2 * p1 - a                          # T_62
-            state.append((x2, p2, p1))
-        out = np.empty(K1 - M)
-        for k in range(M, K1):
-            state = [(x2, p1, x2 * p1 - p2) for x2, p2, p1 in state]
-            out[k - M] = np.sum(state[0][2] - state[1][2])
-        return out
-
     worst = []
     for l in (1, L - 1):
         f, c = onp.synth_level_samples(l, N, steps)
@@ -154,7 +126,7 @@ def test_row_sum_route_on_the_benchmark_samples():
         F2, C2, FC = F * F, C * C, F * C
         sp_ref = F2 @ F2.T + C2 @ C2.T - 2 * (FC @ FC.T)
         gate_scale = np.sqrt(np.abs(sp_ref) * n).astype(float) + 1e-300
-        S = np.concatenate([b @ legendre_diff_sums(tf, tc), chebyshev_tail_sums(tf, tc)])
+        S = np.concatenate([b @ cx.legendre_monic_sums(tf, tc, M), cx.chebyshev_sums(tf, tc, K1)[M:]])
         assert S[0] == 0.0
         s = np.tensordot(S, t1, axes=(0, 0))
         assert s[0, 0] == 0.0
