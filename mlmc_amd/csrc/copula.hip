@@ -1,6 +1,6 @@
 // The Gaussian copula of mlmc_density_sample_joint_batch / mlmc_density_sample_conditional_batch on the device (gfx950): seeded
 // latent normals and the copula uniforms u = clamp(normcdf(F z)) (conditional: of shift + F z) that k_q_sample (density.hip) then
-// inverts.  The host paths are density.hip's (q_joint, q_conditional).
+// inverts.  The host path of both entries is density.hip's (q_copula).
 //
 //   k_cop_normals  : Z[k][c] = normcdfinv(uniform of (seed, streams[k], first + c)), negated for the odd draws of an antithetic
 //                    call; one thread per element, consecutive lanes write consecutive draws

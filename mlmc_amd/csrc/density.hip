@@ -739,25 +739,46 @@ __global__ __launch_bounds__(Q_MOM_THREADS) void k_q_moments(const QProb *__rest
 }
 
 // HIP-event time of the point kernels (k_q_quantile / k_q_cdf / k_q_sample; k_q_quantile + k_q_tails of a tail-means call as one), for
-// mlmc_density_quantiles_kernel_time: one event pair per group of a call, read after the call's own wait
+// mlmc_density_quantiles_kernel_time: one event pair per timed span of a call (begin() .. end() around the point kernels of a group
+// or block), read by collect() after the call's own wait.  Best effort: the timing never fails a call, a span whose events cannot
+// be made or recorded is not counted.
 struct QTiming {
     std::vector<hipEvent_t> ev;
     double ms = 0.0;
     int64_t launches = 0;
-    // best effort: the timing never fails a call (false: this launch is not timed)
-    bool pair(size_t k, hipEvent_t &a, hipEvent_t &b) {
-        while (ev.size() < 2 * (k + 1)) {
+    size_t timed = 0;                 // recorded spans of the running call
+    bool open = false;                // the running span has its first event
+    void begin(hipStream_t st) {
+        open = false;
+        while (ev.size() < 2 * (timed + 1)) {
             hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return false;
+            if (hipEventCreate(&e) != hipSuccess) return;
             ev.push_back(e);
         }
-        a = ev[2 * k];
-        b = ev[2 * k + 1];
-        return true;
+        open = hipEventRecord(ev[2 * timed], st) == hipSuccess;
+    }
+    void end(hipStream_t st) {
+        if (open && hipEventRecord(ev[2 * timed + 1], st) == hipSuccess) ++timed;
+        open = false;
+    }
+    void collect() {
+        for (size_t k = 0; k < timed; ++k) {
+            float span = 0.0f;
+            if (hipEventElapsedTime(&span, ev[2 * k], ev[2 * k + 1]) != hipSuccess) continue;
+            ms += span;
+            ++launches;
+        }
+        timed = 0;
     }
 };
 static QTiming &q_timing() {
     static QTiming t;
+    return t;
+}
+// the timing of a new call: no spans yet, whatever an earlier call that failed has left
+static QTiming &q_call_timing() {
+    QTiming &t = q_timing();
+    t.timed = 0;
     return t;
 }
 
@@ -876,13 +897,72 @@ static int q_stage(const QSetup &S, int deg, std::initializer_list<size_t> stage
     return 0;
 }
 
+// The head of an entry: the bound device, the count of problems (named `count` in the message) and the arguments every call needs
+// (`args`: all of them given).  0: go on; 1: failed; -1: a call without problems, which is no error and does nothing.
+static int q_head(const char *fn, const char *count, int32_t B, bool args) {
+    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (B < 0) return fail(std::string(fn) + ": " + count + " < 0");
+    if (B == 0) return -1;
+    if (!args) return fail(std::string(fn) + ": null argument");
+    return 0;
+}
+
+// The rule of an entry: the cells nint and the Gauss degree deg from the arguments and their zero defaults; mem_kind is checked
+// behind them for the entries that take one
+static int q_rule(const char *fn, int32_t n_intervals, int32_t gauss_degree, int &nint, int &deg, int mem_kind = MLMC_HOST) {
+    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
+    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    nint = n_intervals > 0 ? n_intervals : 64;
+    deg = gauss_degree > 0 ? gauss_degree : 21;
+    return 0;
+}
+
+// The groups of the table bound: `count` problems with `rows` table rows of nint + 1 entries each run G at a time, and a row of
+// the group's table is `plane` entries from the next
+struct QGroups {
+    int G;
+    int64_t plane;
+};
+static QGroups q_groups(int count, size_t rows, int nint) {
+    const int G = (int)std::min<size_t>((size_t)count, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * rows * ((size_t)nint + 1))));
+    return QGroups{G, (int64_t)G * (nint + 1)};
+}
+
+// The tables of the np_g problems from g0 (tails: with the rows of the tail means), in stream order behind whatever read the
+// table of the group before: the cell integrals and their prefix, which leaves the masses at d_mass and, tails, the means at d_mean
+static void q_tables(hipStream_t st, bool tails, const QBlock &K, int g0, int np_g, int nint, int deg, double *d_tab, int64_t plane,
+                     double *d_mass, double *d_mean) {
+    const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
+    const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
+    const int64_t n_cells = (int64_t)np_g * nint;
+    hipLaunchKernelGGL(cells, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx, K.gw, deg,
+                       d_tab, plane);
+    hipLaunchKernelGGL(prefix, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0, d_mass, d_mean);
+}
+
+// The one staged array of a call that sends more than doubles: the parts one after another, each from a whole double on.  add()
+// copies a part in (src NULL: zeros) and hands back where it starts; at() is its place on the device once q_stage has laid out
+// the block and upload() has sent `data`.
+struct QPack {
+    std::vector<double> data;
+    template <class T>
+    size_t add(const T *src, size_t count) {
+        const size_t at = data.size();
+        data.resize(at + (sizeof(T) * count + sizeof(double) - 1) / sizeof(double));
+        if (src && count) std::memcpy(data.data() + at, src, sizeof(T) * count);
+        return at;
+    }
+    template <class T>
+    const T *at(const QBlock &K, size_t part) const {
+        return (const T *)(K.d_in[0] + part);
+    }
+};
+
 // mlmc_density_eval (single; x and out in host or device memory) and mlmc_density_eval_batch
 static int q_eval(const char *fn, bool single, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                   const double *sigma, const double *x, const int64_t *n, double *out, int mem_kind) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (B < 0) return fail(std::string(fn) + ": B < 0");
-    if (B == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !n) return fail(std::string(fn) + ": null argument");
+    if (const int r = q_head(fn, "B", B, bases && R1 && lambda && sigma && n)) return r > 0;
     QSetup S;
     if (q_prepare(fn, single, B, bases, R1, lambda, sigma, nullptr, nullptr, n, S)) return 1;
     if (S.n_tot == 0) return 0;
@@ -908,10 +988,7 @@ static int q_eval(const char *fn, bool single, int32_t B, const mlmc_basis *cons
 // mlmc_density_integrate (single) and mlmc_density_integrate_batch
 static int q_integrate(const char *fn, bool single, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                        const double *sigma, const double *lo, const double *hi, const int64_t *n, int32_t degree, double *out) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (B < 0) return fail(std::string(fn) + ": B < 0");
-    if (B == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !n) return fail(std::string(fn) + ": null argument");
+    if (const int r = q_head(fn, "B", B, bases && R1 && lambda && sigma && n)) return r > 0;
     if (degree <= 0 || degree > 64) return fail(std::string(fn) + ": degree must be in 1..64");
     QSetup S;
     if (q_prepare(fn, single, B, bases, R1, lambda, sigma, nullptr, nullptr, n, S)) return 1;
@@ -950,9 +1027,20 @@ static int q_sample_flags(const char *fn, int32_t flags) {
     return 0;
 }
 
-// the draws table of a sampling call
+// The draws table of the problems of a call, as every entry with k_q_sample or k_q_scores stages it: the nan_coef flag of each
+// problem, first = 0 and the problem's index as its stream.  The entries whose uniforms come from elsewhere read the flag alone.
+static std::vector<QDraw> q_draw_table(const QSetup &S) {
+    std::vector<QDraw> draws(S.probs.size());
+    for (size_t i = 0; i < S.probs.size(); ++i) {
+        const double *c = S.coef.data() + S.probs[i].c_off;
+        const bool nan_coef = std::any_of(c, c + S.probs[i].n_coef, [](double v) { return v != v; });
+        draws[i] = QDraw{0, (uint32_t)i, nan_coef ? 1u : 0u};
+    }
+    return draws;
+}
+
+// first draw and stream of every problem of mlmc_density_sample_batch, into its draws table
 static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::vector<QDraw> &draws) {
-    draws.resize(S.probs.size());
     for (size_t i = 0; i < S.probs.size(); ++i) {
         const QProb &p = S.probs[i];
         const int64_t first = smp.first ? smp.first[i] : 0;
@@ -960,9 +1048,8 @@ static int q_draws(const char *fn, const QSetup &S, const QSampling &smp, std::v
         if (first > INT64_MAX - p.n) return meb_fail(fn, (int)i, "first + n overflows int64");
         if ((smp.flags & MLMC_SAMPLE_SOBOL) && first + p.n > SOBOL_MAX_INDEX)
             return meb_fail(fn, (int)i, "first + n is beyond the 2^52 points of the Sobol' sequence");
-        const double *c = S.coef.data() + p.c_off;
-        const bool nan_coef = std::any_of(c, c + p.n_coef, [](double v) { return v != v; });
-        draws[i] = QDraw{first, smp.streams ? smp.streams[i] : (uint32_t)i, nan_coef ? 1u : 0u};
+        draws[i].first = first;
+        if (smp.streams) draws[i].stream = smp.streams[i];
     }
     return 0;
 }
@@ -1006,24 +1093,21 @@ static QLdsPlan q_lds_plan(const QSetup &S, int nint, int deg, size_t extra = 0)
 // u_in: the instance that reads its uniforms (mlmc_density_sample_joint_batch); sets: the one that reads them per set
 // (mlmc_density_sample_conditional_batch); qmc: the instances of MLMC_SAMPLE_SOBOL, whose lanes own runs of draws and which, in
 // mlmc_density_sample_batch, make Sobol' uniforms
+template <bool U_IN, bool SETS, bool QMC>
+static QSampler q_sampler(const QLdsPlan &plan) {
+    return plan.row_lds    ? k_q_sample<true, true, U_IN, SETS, QMC>
+           : plan.coef_lds ? k_q_sample<true, false, U_IN, SETS, QMC>
+                           : k_q_sample<false, false, U_IN, SETS, QMC>;
+}
 static QSampleLaunch q_sample_launch(const QSetup &S, int nint, int deg, bool u_in, bool sets = false, bool qmc = false) {
     const QLdsPlan plan = q_lds_plan(S, nint, deg, qmc && !u_in ? sizeof(uint64_t) * SOBOL_ROW : 0);
-    const bool coef_lds = plan.coef_lds, row_lds = plan.row_lds;
     QSampleLaunch L;
-    if (qmc && sets)
-        L.kernel = row_lds ? k_q_sample<true, true, true, true, true>
-                   : coef_lds ? k_q_sample<true, false, true, true, true> : k_q_sample<false, false, true, true, true>;
-    else if (qmc && u_in)
-        L.kernel = row_lds ? k_q_sample<true, true, true, false, true>
-                   : coef_lds ? k_q_sample<true, false, true, false, true> : k_q_sample<false, false, true, false, true>;
-    else if (qmc)
-        L.kernel = row_lds ? k_q_sample<true, true, false, false, true>
-                   : coef_lds ? k_q_sample<true, false, false, false, true> : k_q_sample<false, false, false, false, true>;
-    else if (sets)
-        L.kernel = row_lds ? k_q_sample<true, true, true, true>
-                   : coef_lds ? k_q_sample<true, false, true, true> : k_q_sample<false, false, true, true>;
-    else if (u_in) L.kernel = row_lds ? k_q_sample<true, true, true> : coef_lds ? k_q_sample<true, false, true> : k_q_sample<false, false, true>;
-    else L.kernel = row_lds ? k_q_sample<true, true> : coef_lds ? k_q_sample<true, false> : k_q_sample<false, false>;
+    if (qmc && sets) L.kernel = q_sampler<true, true, true>(plan);
+    else if (qmc && u_in) L.kernel = q_sampler<true, false, true>(plan);
+    else if (qmc) L.kernel = q_sampler<false, false, true>(plan);
+    else if (sets) L.kernel = q_sampler<true, true, false>(plan);
+    else if (u_in) L.kernel = q_sampler<true, false, false>(plan);
+    else L.kernel = q_sampler<false, false, false>(plan);
     L.lds_bytes = plan.bytes;
     int resident = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, L.kernel, Q_SAMPLE_THREADS, L.lds_bytes) == hipSuccess && resident > 0)
@@ -1038,19 +1122,16 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                      const double *x, const int64_t *n, double *out, double *mass_out, int mem_kind, double *lower_out = nullptr,
                      double *upper_out = nullptr, double *mean_out = nullptr, const QSampling *smp = nullptr) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (B < 0) return fail(std::string(fn) + ": B < 0");
-    if (B == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !a || !b || !n) return fail(std::string(fn) + ": null argument");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
-    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+    if (const int r = q_head(fn, "B", B, bases && R1 && lambda && sigma && a && b && n)) return r > 0;
+    int nint, deg;
+    if (q_rule(fn, n_intervals, gauss_degree, nint, deg, mem_kind)) return 1;
     const bool tails = mode == Q_TAILS, sample = mode == Q_SAMPLE;
     if (sample && q_sample_flags(fn, smp->flags)) return 1;
     const bool sobol = sample && (smp->flags & MLMC_SAMPLE_SOBOL);
     QSetup S;
     if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, n, S)) return 1;
     std::vector<QDraw> draws;
+    if (sample) draws = q_draw_table(S);
     if (sample && q_draws(fn, S, *smp, draws)) return 1;
     // MLMC_SAMPLE_SOBOL: the rows of the call's distinct dimensions; a problem's draws entry names its row instead of its stream
     std::vector<uint64_t> sobol_tab;
@@ -1061,48 +1142,34 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     }
     if (S.n_tot > 0 && ((!sample && !x) || !out || (tails && (!lower_out || !upper_out)))) return fail(std::string(fn) + ": null argument");
     if (S.n_tot == 0 && !mass_out && !mean_out) return 0;
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     hipStream_t st = rt().stream;
     const bool stage = mem_kind == MLMC_HOST && S.n_tot > 0;
     const size_t rows = tails ? Q_TAIL_ROWS : 1;                             // table rows per problem
-    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * rows * ((size_t)nint + 1))));
-    const int64_t plane = (int64_t)G * (nint + 1);
+    const auto [G, plane] = q_groups(B, rows, nint);
     const size_t np = stage ? (size_t)S.n_tot : 0, nm = (size_t)B * (tails ? 2 : 1);      // staged points; masses, then means
-    // what goes up with the block: the points, or the draws table of a sampling call; a sampling call returns the uniforms in
-    // the place of the lower tail means
-    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double));
-    const size_t n_in = sample ? n_draw + sobol_tab.size() : np;
+    // what goes up with the block: the points, or of a sampling call the draws table | the Sobol' table (uint64); a sampling call
+    // returns the uniforms in the place of the lower tail means
+    QPack pack;
+    pack.add(draws.data(), draws.size());
+    const size_t at_sobol = pack.add(sobol_tab.data(), sobol_tab.size());
+    const size_t n_in = sample ? pack.data.size() : np;
     if (sample) lower_out = smp->u_out;
-    std::vector<double> packed;                          // MLMC_SAMPLE_SOBOL: the draws table | the Sobol' table (uint64)
-    if (sobol) {
-        packed.resize(n_in);
-        std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
-        std::memcpy(packed.data() + n_draw, sobol_tab.data(), sizeof(uint64_t) * sobol_tab.size());
-    }
     QBlock K;
     if (q_stage(S, deg, {n_in}, {nm, rows * (size_t)plane, np, lower_out ? np : 0, tails ? np : 0}, {nm}, K)) return 1;
-    if (K.upload({sobol ? packed.data() : sample ? (const double *)draws.data() : x}, n_in)) return 1;
+    if (K.upload({sample ? pack.data.data() : x}, n_in)) return 1;
     double *d_mass = K.d[0], *d_mean = d_mass + B, *d_tab = K.d[1];
     const double *d_x = stage ? K.d_in[0] : x;
     double *d_out = stage ? K.d[2] : out, *d_lower = stage && lower_out ? K.d[3] : lower_out, *d_upper = stage ? K.d[4] : upper_out;
     QSampleLaunch L;
     if (sample) L = q_sample_launch(S, nint, deg, false, false, sobol);
-    const auto cells = tails ? k_q_cells<true> : k_q_cells<false>;
-    const auto prefix = tails ? k_q_prefix<true> : k_q_prefix<false>;
-    QTiming &tm = q_timing();
-    size_t timed = 0;
+    QTiming &tm = q_call_timing();
     for (int g0 = 0; g0 < B; g0 += G) {
         const int np_g = std::min(G, B - g0);
-        const int64_t n_cells = (int64_t)np_g * nint;
-        hipLaunchKernelGGL(cells, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx, K.gw, deg,
-                           d_tab, plane);
-        hipLaunchKernelGGL(prefix, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0, d_mass + g0,
-                           d_mean + g0);
+        q_tables(st, tails, K, g0, np_g, nint, deg, d_tab, plane, d_mass + g0, d_mean + g0);
         const int64_t pt0 = S.probs[g0].x_off;
         const int64_t npts = (g0 + np_g < B ? S.probs[g0 + np_g].x_off : S.n_tot) - pt0;
         if (npts > 0) {
-            hipEvent_t e0, e1;
-            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            tm.begin(st);
             const dim3 grid((unsigned)((npts + Q_THREADS - 1) / Q_THREADS));           // of the one-thread-per-point kernels
             if (sample) {
                 int64_t n_max = 0;
@@ -1112,7 +1179,7 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
                 hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0,
                                    (const QDraw *)K.d_in[0] + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, smp->seed,
                                    (int)(smp->flags & MLMC_SAMPLE_ANTITHETIC), d_out, d_lower, (const double *)nullptr, (int64_t)0,
-                                   (int64_t)0, (int64_t)0, (int64_t)0, sobol ? (const uint64_t *)(K.d_in[0] + n_draw) : nullptr);
+                                   (int64_t)0, (int64_t)0, (int64_t)0, sobol ? pack.at<uint64_t>(K, at_sobol) : nullptr);
             } else {
                 hipLaunchKernelGGL(mode != Q_CDF ? k_q_quantile : k_q_cdf, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts,
                                    K.coef, (const double *)d_tab, K.gx, K.gw, deg, d_x, d_out);
@@ -1120,7 +1187,7 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
             if (tails)                           // the quantiles, as k_q_quantile has just written them, are the points
                 hipLaunchKernelGGL(k_q_tails, grid, dim3(Q_THREADS), 0, st, K.probs + g0, np_g, nint, pt0, npts, K.coef, (const double *)d_tab,
                                    plane, K.gx, K.gw, deg, (const double *)d_out, d_lower, d_upper);
-            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+            tm.end(st);
         }
         MLMC_HIP_CHECK(hipGetLastError());
     }
@@ -1131,31 +1198,37 @@ static int q_on_rule(const char *fn, QMode mode, int32_t B, const mlmc_basis *co
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * B);
     if (mean_out) std::memcpy(mean_out, K.h[0] + B, sizeof(double) * B);
-    for (size_t k = 0; k < timed; ++k) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
-        tm.ms += ms;
-        ++tm.launches;
-    }
+    tm.collect();
     meb_ws().trim(MEB_KEEP_BYTES);
     return 0;
 }
 
-// mlmc_density_sample_joint_batch: draws of M problems joined by a Gaussian copula.  Table, masses and inversion are those of
-// q_on_rule's sampling branch; the uniforms come from copula.hip instead of q_uniform.  The draws are processed in blocks of nb
-// columns: latent normals Z [K][nb], copula uniforms U [M][nb], inversion of the block.  Z and U live in the workspace unless the
-// caller's device arrays take them in place.  No value depends on nb.
-static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
-                   const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf, const double *factor,
-                   uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *out, double *u_out,
-                   double *z_out, double *mass_out, int mem_kind) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (M < 0) return fail(std::string(fn) + ": M < 0");
-    if (M == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
-    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
+// the sets of mlmc_density_sample_conditional_batch: y = shift[b][m] + (F z)[m] for b < B, draws and uniforms of problem m at row
+// rows[m] (NULL: m) of the set's ld_rows rows
+struct QSets {
+    int32_t B;
+    const double *shift;              // [B][M] or NULL: zeros
+    const int32_t *rows;              // [M] or NULL
+    int32_t ld_rows;
+};
+
+// mlmc_density_sample_joint_batch (sets == NULL) and mlmc_density_sample_conditional_batch: draws of M problems joined by a
+// Gaussian copula.  Table, masses and inversion are those of q_on_rule's sampling branch; the uniforms come from copula.hip
+// instead of q_uniform.  The draws are processed in blocks of nb columns: latent normals Z [K][nb], copula uniforms U [M][nb],
+// inversion of the block.  No value depends on nb.
+// The joint entry: Z and U live in the workspace unless the caller's device arrays take them in place.
+// The conditional entry: the same draws for B sets at once.  Table, masses, normals and the chain of the product are made once per
+// block for all sets; the uniforms U [B][M][nb] always live in the workspace (k_cop_uniforms<true>, set on blockIdx.z), and the
+// SETS instance of k_q_sample inverts them and writes draw and uniform at row rows[m] of set b.  Host arrays are staged compactly
+// ([B][M][n]) and come back in runs of consecutive rows, so the rows that `rows` does not name are not touched.  No value
+// depends on B.
+static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
+                    const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf, const double *factor,
+                    uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, const QSets *sets, double *out,
+                    double *u_out, double *z_out, double *mass_out, int mem_kind) {
+    if (const int r = q_head(fn, "M", M, bases && R1 && lambda && sigma && a && b)) return r > 0;
+    int nint, deg;
+    if (q_rule(fn, n_intervals, gauss_degree, nint, deg, mem_kind)) return 1;
     if (q_sample_flags(fn, flags)) return 1;
     const bool sobol = flags & MLMC_SAMPLE_SOBOL;
     if (Kf < 1) return fail(std::string(fn) + ": K < 1");
@@ -1168,176 +1241,49 @@ static int q_joint(const char *fn, int32_t M, const mlmc_basis *const *bases, co
     std::vector<uint64_t> sobol_tab;
     std::vector<uint32_t> sobol_slot;
     if (sobol && sobol_call_table(fn, "latent normal", seed, streams, Kf, sobol_tab, sobol_slot)) return 1;
+    const int32_t B = sets ? sets->B : 1;
+    const int32_t *rows = sets ? sets->rows : nullptr;
+    const int32_t ld_rows = sets ? sets->ld_rows : M;
+    if (sets) {
+        if (B < 1) return fail(std::string(fn) + ": B < 1");
+        if (ld_rows < M) return fail(std::string(fn) + ": ld_rows < M");
+        for (int m = 0; rows && m < M; ++m)
+            if (rows[m] < 0 || rows[m] >= ld_rows || (m > 0 && rows[m] <= rows[m - 1]))
+                return fail(std::string(fn) + ": rows must be strictly increasing within 0 .. ld_rows - 1 (entry " + std::to_string(m) + ")");
+        if (n > 0 && (int64_t)B * ld_rows > INT64_MAX / 8 / n) return fail(std::string(fn) + ": B * ld_rows * n overflows int64");
+    }
+    // a row of the factor has unit norm; under a condition it has the norm of what the condition leaves, at most 1
     for (int m = 0; m < M; ++m) {
         const double *row = factor + (size_t)m * Kf;
         double ss = 0.0;
         for (int k = 0; k < Kf; ++k) ss += row[k] * row[k];          // a value that is not finite makes the sum not finite
         if (!std::isfinite(ss)) return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": an entry is not finite");
-        if (!(std::fabs(ss - 1.0) <= 1e-6))
-            return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": the sum of squares must be 1 within 1e-6");
+        if (sets ? !(ss <= 1.0 + 1e-6) : !(std::fabs(ss - 1.0) <= 1e-6))
+            return fail(std::string(fn) + ": factor row " + std::to_string(m) +
+                        (sets ? ": the sum of squares must be at most 1 + 1e-6" : ": the sum of squares must be 1 within 1e-6"));
     }
-    QSetup S;
-    const std::vector<int64_t> counts((size_t)M, n);
-    if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
-    std::vector<QDraw> draws;
-    const QSampling no_streams = {seed, nullptr, nullptr, flags, nullptr};        // of the table, the joint entry reads nan_coef alone
-    if (q_draws(fn, S, no_streams, draws)) return 1;
-    if (n > 0 && !out) return fail(std::string(fn) + ": null argument");
-    if (n == 0 && !mass_out) return 0;
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
-    hipStream_t st = rt().stream;
-    const bool stage = mem_kind == MLMC_HOST && n > 0;
-    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
-    const int64_t plane = (int64_t)G * (nint + 1);
-    // the draws of a block: Z and U of a block within Q_JOINT_BYTES, whole tiles of the matrix kernel
-    int64_t nb = std::max<int64_t>(64, (int64_t)(Q_JOINT_BYTES / (sizeof(double) * ((size_t)M + (size_t)Kf))) / 64 * 64);
-    if (const char *env = std::getenv("MLMC_JOINT_BLOCK_DRAWS")) {
-        const long long v = std::atoll(env);
-        if (v > 0) nb = v;
-    }
-    nb = std::min(nb, std::max<int64_t>(n, 1));
-    const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && !(mem_kind == MLMC_DEVICE && u_out);
-    // what goes up with the block: the draws table | the streams (uint32) | the factor | the Sobol' table (uint64)
-    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
-    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sob = n > 0 ? sobol_tab.size() : 0, n_in = n_draw + n_str + n_fac + n_sob;
-    std::vector<double> packed(n_in);
-    std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
-    if (n > 0) {
-        uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
-        for (int k = 0; k < Kf; ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
-        std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
-        std::memcpy(packed.data() + n_draw + n_str + n_fac, sobol_tab.data(), sizeof(uint64_t) * n_sob);
-    }
-    QBlock K;
-    if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, stage ? (size_t)M * (size_t)n : 0, u_ws ? (size_t)M * (size_t)nb : 0,
-                                z_ws ? (size_t)Kf * (size_t)nb : 0}, {(size_t)M}, K))
-        return 1;
-    if (K.upload({packed.data()}, n_in)) return 1;
-    const QDraw *d_draws = (const QDraw *)K.d_in[0];
-    const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
-    const double *d_factor = K.d_in[0] + n_draw + n_str;
-    const uint64_t *d_sobol = (const uint64_t *)(d_factor + n_fac);
-    double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
-    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, false, sobol);
-    QTiming &tm = q_timing();
-    size_t timed = 0;
-    for (int g0 = 0; g0 < M; g0 += G) {
-        const int np_g = std::min(G, M - g0);
-        const int64_t n_cells = (int64_t)np_g * nint;
-        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
-                           K.gw, deg, d_tab, plane);
-        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
-                           d_mass + g0, (double *)nullptr);
-        for (int64_t c0 = 0; c0 < n; c0 += nb) {
-            const int64_t nc = std::min(nb, n - c0);
-            // the block's Z and U: in the caller's device arrays at column c0 (row length n), or in the workspace (row length nb)
-            double *Z = z_ws ? K.d[4] : z_out + c0, *U = u_ws ? K.d[3] : u_out + c0;
-            const int64_t ldz = z_ws ? nb : n, ldu = u_ws ? nb : n;
-            hipEvent_t e0, e1;
-            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
-            if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
-                cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
-            else if (g0 == 0 || z_ws)
-                cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
-            cop_launch_uniforms(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu);
-            unsigned threads, gy;
-            L.geometry((int64_t)np_g * nc, nc, threads, gy);
-            hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy), dim3(threads), L.lds_bytes, st, K.probs + g0, d_draws + g0, nint, K.coef,
-                               (const double *)d_tab, K.gx, K.gw, deg, seed, 0, d_out + c0, (double *)nullptr,
-                               (const double *)(U + (int64_t)g0 * ldu), ldu, nc, (int64_t)0, (int64_t)0,
-                               (const uint64_t *)nullptr);
-            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
-            MLMC_HIP_CHECK(hipGetLastError());
-            if (stage && z_out && g0 == 0)
-                MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c0, sizeof(double) * n, Z, sizeof(double) * ldz, sizeof(double) * nc, (size_t)Kf,
-                                                hipMemcpyDeviceToHost, st));
-            if (stage && u_out)
-                MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + (int64_t)g0 * n + c0, sizeof(double) * n, U + (int64_t)g0 * ldu, sizeof(double) * ldu,
-                                                sizeof(double) * nc, (size_t)np_g, hipMemcpyDeviceToHost, st));
-        }
-        MLMC_HIP_CHECK(hipGetLastError());
-    }
-    if (stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)M * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
-    MLMC_HIP_CHECK(wait_stream(st));
-    if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
-    for (size_t k = 0; k < timed; ++k) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
-        tm.ms += ms;
-        ++tm.launches;
-    }
-    meb_ws().trim(MEB_KEEP_BYTES);
-    return 0;
-}
-
-// mlmc_density_sample_conditional_batch: q_joint's draws for B sets at once, y = shift[b][m] + (F z)[m].  Table, masses, normals and
-// the chain of the product are those of q_joint and are made once per block for all sets; the uniforms U [B][M][nb] always live in
-// the workspace (k_cop_uniforms<true>, set on blockIdx.z), and the SETS instance of k_q_sample inverts them and writes draw and
-// uniform at row rows[m] of set b.  Host arrays are staged compactly ([B][M][n]) and come back in runs of consecutive rows, so
-// the rows that `rows` does not name are not touched.  No value depends on nb or on B.
-static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
-                         const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf,
-                         const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, int32_t B,
-                         const double *shift, const int32_t *rows, int32_t ld_rows, double *out, double *u_out, double *z_out,
-                         double *mass_out, int mem_kind) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (M < 0) return fail(std::string(fn) + ": M < 0");
-    if (M == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
-    if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
-    if (q_sample_flags(fn, flags)) return 1;
-    const bool sobol = flags & MLMC_SAMPLE_SOBOL;
-    if (Kf < 1) return fail(std::string(fn) + ": K < 1");
-    if (!factor) return fail(std::string(fn) + ": null factor");
-    if (n < 0) return fail(std::string(fn) + ": n < 0");
-    if (first < 0) return fail(std::string(fn) + ": first < 0");
-    if (first > INT64_MAX - n) return fail(std::string(fn) + ": first + n overflows int64");
-    if (sobol && first + n > SOBOL_MAX_INDEX) return fail(std::string(fn) + ": first + n is beyond the 2^52 points of the Sobol' sequence");
-    // MLMC_SAMPLE_SOBOL: the rows of the call's distinct dimensions; latent normal k names its row instead of its stream
-    std::vector<uint64_t> sobol_tab;
-    std::vector<uint32_t> sobol_slot;
-    if (sobol && sobol_call_table(fn, "latent normal", seed, streams, Kf, sobol_tab, sobol_slot)) return 1;
-    if (B < 1) return fail(std::string(fn) + ": B < 1");
-    if (ld_rows < M) return fail(std::string(fn) + ": ld_rows < M");
-    for (int m = 0; rows && m < M; ++m)
-        if (rows[m] < 0 || rows[m] >= ld_rows || (m > 0 && rows[m] <= rows[m - 1]))
-            return fail(std::string(fn) + ": rows must be strictly increasing within 0 .. ld_rows - 1 (entry " + std::to_string(m) + ")");
-    if (n > 0 && (int64_t)B * ld_rows > INT64_MAX / 8 / n) return fail(std::string(fn) + ": B * ld_rows * n overflows int64");
-    for (int m = 0; m < M; ++m) {
-        const double *row = factor + (size_t)m * Kf;
-        double ss = 0.0;
-        for (int k = 0; k < Kf; ++k) ss += row[k] * row[k];          // a value that is not finite makes the sum not finite
-        if (!std::isfinite(ss)) return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": an entry is not finite");
-        if (!(ss <= 1.0 + 1e-6))
-            return fail(std::string(fn) + ": factor row " + std::to_string(m) + ": the sum of squares must be at most 1 + 1e-6");
-    }
-    for (int64_t i = 0; shift && i < (int64_t)B * M; ++i)
-        if (!std::isfinite(shift[i]))
-            return fail(std::string(fn) + ": shift of set " + std::to_string(i / M) + ", row " + std::to_string(i % M) + " is not finite");
     const size_t BM = (size_t)B * (size_t)M;
-    if (sizeof(double) * 64 * (BM + (size_t)Kf) > Q_JOINT_BYTES)
-        return fail(std::string(fn) + ": the uniforms of B * M = " + std::to_string(BM) +
-                    " rows do not fit into the workspace even for a block of 64 draws; split the sets across calls (no value depends on B)");
+    if (sets) {
+        for (int64_t i = 0; sets->shift && i < (int64_t)B * M; ++i)
+            if (!std::isfinite(sets->shift[i]))
+                return fail(std::string(fn) + ": shift of set " + std::to_string(i / M) + ", row " + std::to_string(i % M) + " is not finite");
+        if (sizeof(double) * 64 * (BM + (size_t)Kf) > Q_JOINT_BYTES)
+            return fail(std::string(fn) + ": the uniforms of B * M = " + std::to_string(BM) +
+                        " rows do not fit into the workspace even for a block of 64 draws; split the sets across calls (no value depends on B)");
+    }
     QSetup S;
     const std::vector<int64_t> counts((size_t)M, n);
     if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
-    std::vector<QDraw> draws;
-    const QSampling no_streams = {seed, nullptr, nullptr, flags, nullptr};        // of the table, this entry reads nan_coef alone
-    if (q_draws(fn, S, no_streams, draws)) return 1;
+    const std::vector<QDraw> draws = q_draw_table(S);
     if (n > 0 && !out) return fail(std::string(fn) + ": null argument");
     if (n == 0 && !mass_out) return 0;
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     hipStream_t st = rt().stream;
     const bool stage = mem_kind == MLMC_HOST && n > 0;
     // where a set's draws go: rows[m] of the caller's device array [B][ld_rows][n], or row m of the compact staged one [B][M][n]
     const int64_t x_set = (stage ? (int64_t)M : (int64_t)ld_rows) * n;
     if (!stage && rows)
         for (int m = 0; m < M; ++m) S.probs[m].x_off = (int64_t)rows[m] * n;
-    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
-    const int64_t plane = (int64_t)G * (nint + 1);
+    const auto [G, plane] = q_groups(M, 1, nint);
     // the draws of a block: Z and U of a block within Q_JOINT_BYTES, whole tiles of the matrix kernel
     int64_t nb = std::max<int64_t>(64, (int64_t)(Q_JOINT_BYTES / (sizeof(double) * (BM + (size_t)Kf))) / 64 * 64);
     if (const char *env = std::getenv("MLMC_JOINT_BLOCK_DRAWS")) {
@@ -1345,72 +1291,70 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
         if (v > 0) nb = v;
     }
     nb = std::min(nb, std::max<int64_t>(n, 1));
-    const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out);
-    // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts | the Sobol' table (uint64)
-    const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double)), n_str = n > 0 ? ((size_t)Kf + 1) / 2 : 0;
-    const size_t n_fac = n > 0 ? (size_t)M * Kf : 0, n_sh = n > 0 ? BM : 0, n_sob = n > 0 ? sobol_tab.size() : 0;
-    const size_t n_in = n_draw + n_str + n_fac + n_sh + n_sob;
-    std::vector<double> packed(n_in);
-    std::memcpy(packed.data(), draws.data(), sizeof(double) * n_draw);
-    if (n > 0) {
-        uint32_t *sv = (uint32_t *)(packed.data() + n_draw);
-        for (int k = 0; k < Kf; ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
-        std::memcpy(packed.data() + n_draw + n_str, factor, sizeof(double) * n_fac);
-        if (shift) std::memcpy(packed.data() + n_draw + n_str + n_fac, shift, sizeof(double) * n_sh);         // NULL: the zeros of `packed`
-        std::memcpy(packed.data() + n_draw + n_str + n_fac + n_sh, sobol_tab.data(), sizeof(uint64_t) * n_sob);
-    }
-    const size_t n_stage = stage ? BM * (size_t)n : 0;
+    const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && (sets || !(mem_kind == MLMC_DEVICE && u_out));
+    // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts of the sets | the Sobol' table
+    // (uint64); a call without draws sends the draws table alone
+    QPack pack;
+    pack.add(draws.data(), draws.size());
+    std::vector<uint32_t> sv(n > 0 ? (size_t)Kf : 0);
+    for (size_t k = 0; k < sv.size(); ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
+    const size_t at_streams = pack.add(sv.data(), sv.size()), at_factor = pack.add(factor, n > 0 ? (size_t)M * Kf : 0);
+    const size_t at_shift = sets ? pack.add(sets->shift, n > 0 ? BM : 0) : 0, at_sobol = pack.add(sobol_tab.data(), n > 0 ? sobol_tab.size() : 0);
+    const size_t n_in = pack.data.size(), n_stage = stage ? BM * (size_t)n : 0;
     QBlock K;
-    if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, n_stage, n > 0 ? BM * (size_t)nb : 0, z_ws ? (size_t)Kf * (size_t)nb : 0,
-                                u_out ? n_stage : 0},
+    if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, n_stage, u_ws ? BM * (size_t)nb : 0, z_ws ? (size_t)Kf * (size_t)nb : 0,
+                                sets && u_out ? n_stage : 0},
                 {(size_t)M}, K))
         return 1;
-    if (K.upload({packed.data()}, n_in)) return 1;
-    const QDraw *d_draws = (const QDraw *)K.d_in[0];
-    const uint32_t *d_streams = (const uint32_t *)(K.d_in[0] + n_draw);
-    const double *d_factor = K.d_in[0] + n_draw + n_str, *d_shift = d_factor + n_fac;
-    const uint64_t *d_sobol = (const uint64_t *)(d_shift + n_sh);
-    double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out, *U = K.d[3];
-    double *d_u = stage && u_out ? K.d[5] : u_out;
-    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, true, sobol);
-    QTiming &tm = q_timing();
-    size_t timed = 0;
+    if (K.upload({pack.data.data()}, n_in)) return 1;
+    const QDraw *d_draws = pack.at<QDraw>(K, 0);
+    const uint32_t *d_streams = pack.at<uint32_t>(K, at_streams);
+    const double *d_factor = pack.at<double>(K, at_factor), *d_shift = pack.at<double>(K, at_shift);
+    const uint64_t *d_sobol = pack.at<uint64_t>(K, at_sobol);
+    double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
+    // the uniforms k_q_sample writes next to the draws: those of the sets; the joint entry's U is the output itself
+    double *d_u = !sets ? nullptr : stage && u_out ? K.d[5] : u_out;
+    const QSampleLaunch L = q_sample_launch(S, nint, deg, true, sets != nullptr, sobol);
+    QTiming &tm = q_call_timing();
     for (int g0 = 0; g0 < M; g0 += G) {
         const int np_g = std::min(G, M - g0);
-        const int64_t n_cells = (int64_t)np_g * nint;
-        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
-                           K.gw, deg, d_tab, plane);
-        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
-                           d_mass + g0, (double *)nullptr);
+        q_tables(st, false, K, g0, np_g, nint, deg, d_tab, plane, d_mass + g0, nullptr);
         for (int64_t c0 = 0; c0 < n; c0 += nb) {
             const int64_t nc = std::min(nb, n - c0);
-            double *Z = z_ws ? K.d[4] : z_out + c0;
-            const int64_t ldz = z_ws ? nb : n;
-            hipEvent_t e0, e1;
-            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            // the block's Z and U: in the caller's device arrays at column c0 (row length n), or in the workspace (row length nb)
+            double *Z = z_ws ? K.d[4] : z_out + c0, *U = u_ws ? K.d[3] : u_out + c0;
+            const int64_t ldz = z_ws ? nb : n, ldu = u_ws ? nb : n;
+            tm.begin(st);
             if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
                 cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
             else if (g0 == 0 || z_ws)
                 cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
-            cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * nb, nb, d_shift + g0, B, M);
+            if (sets)
+                cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, d_shift + g0, B, M);
+            else
+                cop_launch_uniforms(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu);
             unsigned threads, gy;
             L.geometry((int64_t)B * np_g * nc, nc, threads, gy);
-            for (int b0 = 0; b0 < B; b0 += 65535)         // set of a launch = blockIdx.z
+            for (int b0 = 0; b0 < B; b0 += 65535)         // set of a launch = blockIdx.z; the joint entry has the one
                 hipLaunchKernelGGL(L.kernel, dim3((unsigned)np_g, gy, (unsigned)std::min(B - b0, 65535)), dim3(threads), L.lds_bytes, st,
                                    K.probs + g0, d_draws + g0, nint, K.coef, (const double *)d_tab, K.gx, K.gw, deg, seed, 0,
                                    d_out + b0 * x_set + c0, d_u ? d_u + b0 * x_set + c0 : (double *)nullptr,
-                                   (const double *)(U + ((int64_t)b0 * M + g0) * nb), nb, nc, (int64_t)M, x_set,
-                                   (const uint64_t *)nullptr);
-            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+                                   (const double *)(U + ((int64_t)b0 * M + g0) * ldu), ldu, nc, sets ? (int64_t)M : (int64_t)0,
+                                   sets ? x_set : (int64_t)0, (const uint64_t *)nullptr);
+            tm.end(st);
             MLMC_HIP_CHECK(hipGetLastError());
             if (stage && z_out && g0 == 0)
                 MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c0, sizeof(double) * n, Z, sizeof(double) * ldz, sizeof(double) * nc, (size_t)Kf,
                                                 hipMemcpyDeviceToHost, st));
+            if (!sets && stage && u_out)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + (int64_t)g0 * n + c0, sizeof(double) * n, U + (int64_t)g0 * ldu, sizeof(double) * ldu,
+                                                sizeof(double) * nc, (size_t)np_g, hipMemcpyDeviceToHost, st));
         }
         MLMC_HIP_CHECK(hipGetLastError());
     }
-    // a staged array comes back in runs of consecutive rows: run m0 .. m1 - 1 of every set in one strided copy
-    for (int m0 = 0, m1; stage && m0 < M; m0 = m1) {
+    if (!sets && stage) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)M * (size_t)n, hipMemcpyDeviceToHost, st));
+    // a staged array of sets comes back in runs of consecutive rows: run m0 .. m1 - 1 of every set in one strided copy
+    for (int m0 = 0, m1; sets && stage && m0 < M; m0 = m1) {
         for (m1 = m0 + 1; m1 < M && (rows ? rows[m1] == rows[m1 - 1] + 1 : true); ++m1) {}
         const int64_t to = (int64_t)(rows ? rows[m0] : m0) * n, from = (int64_t)m0 * n;
         const size_t width = sizeof(double) * (size_t)(m1 - m0) * (size_t)n, dpitch = sizeof(double) * (size_t)ld_rows * (size_t)n;
@@ -1423,12 +1367,7 @@ static int q_conditional(const char *fn, int32_t M, const mlmc_basis *const *bas
     if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
-    for (size_t k = 0; k < timed; ++k) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
-        tm.ms += ms;
-        ++tm.launches;
-    }
+    tm.collect();
     meb_ws().trim(MEB_KEEP_BYTES);
     return 0;
 }
@@ -1439,21 +1378,16 @@ static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, c
                     const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, const double *fine, const double *coarse,
                     int64_t n, int64_t ld_in, double *z_fine, double *z_coarse, int64_t ld_out, double *u_fine, double *u_coarse,
                     double *mass_out) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (M < 0) return fail(std::string(fn) + ": M < 0");
-    if (M == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !a || !b) return fail(std::string(fn) + ": null argument");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (const int r = q_head(fn, "M", M, bases && R1 && lambda && sigma && a && b)) return r > 0;
+    int nint, deg;
+    if (q_rule(fn, n_intervals, gauss_degree, nint, deg)) return 1;
     if (n < 0) return fail(std::string(fn) + ": n < 0");
     if (ld_in < n || ld_out < n) return fail(std::string(fn) + ": ld_in and ld_out must be at least n");
     if (ld_in > INT64_MAX / 8 / M || ld_out > INT64_MAX / 8 / M) return fail(std::string(fn) + ": M * ld overflows int64");
     QSetup S;
     const std::vector<int64_t> counts((size_t)M, n);
     if (q_prepare(fn, false, M, bases, R1, lambda, sigma, a, b, counts.data(), S)) return 1;
-    std::vector<QDraw> draws;
-    const QSampling none = {0, nullptr, nullptr, 0, nullptr};                      // of the table, this entry reads nan_coef alone
-    if (q_draws(fn, S, none, draws)) return 1;
+    const std::vector<QDraw> draws = q_draw_table(S);
     if (!coarse) z_coarse = u_coarse = nullptr;
     if (n > 0 && (!fine || !z_fine || (coarse && !z_coarse))) return fail(std::string(fn) + ": null argument");
     if (n == 0 && !mass_out) return 0;
@@ -1477,10 +1411,8 @@ static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, c
             }
         }
     }
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     hipStream_t st = rt().stream;
-    const int G = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * ((size_t)nint + 1))));
-    const int64_t plane = (int64_t)G * (nint + 1);
+    const auto [G, plane] = q_groups(M, 1, nint);
     const size_t n_draw = draws.size() * (sizeof(QDraw) / sizeof(double));
     QBlock K;
     if (q_stage(S, deg, {n_draw}, {(size_t)M, (size_t)plane}, {(size_t)M}, K)) return 1;
@@ -1491,18 +1423,12 @@ static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     const auto kernel = plan.row_lds ? k_q_scores<true, true> : plan.coef_lds ? k_q_scores<true, false> : k_q_scores<false, false>;
     const size_t lds_bytes = plan.bytes;
     const int64_t wg_cols = (coarse ? 1 : 2) * Q_SCORE_THREADS, launch_cols = 65535 * wg_cols;     // a grid has 65535 blocks in y
-    QTiming &tm = q_timing();
-    size_t timed = 0;
+    QTiming &tm = q_call_timing();
     for (int g0 = 0; g0 < M; g0 += G) {
         const int np_g = std::min(G, M - g0);
-        const int64_t n_cells = (int64_t)np_g * nint;
-        hipLaunchKernelGGL(k_q_cells<false>, dim3((unsigned)((n_cells + 127) / 128)), dim3(128), 0, st, K.probs + g0, np_g, nint, K.coef, K.gx,
-                           K.gw, deg, d_tab, plane);
-        hipLaunchKernelGGL(k_q_prefix<false>, dim3((unsigned)((np_g + 63) / 64)), dim3(64), 0, st, np_g, nint, d_tab, plane, K.probs + g0,
-                           d_mass + g0, (double *)nullptr);
+        q_tables(st, false, K, g0, np_g, nint, deg, d_tab, plane, d_mass + g0, nullptr);
         if (n > 0) {
-            hipEvent_t e0, e1;
-            const bool timing = tm.pair(timed, e0, e1) && hipEventRecord(e0, st) == hipSuccess;
+            tm.begin(st);
             const int64_t in_off = (int64_t)g0 * ld_in, out_off = (int64_t)g0 * ld_out;
             for (int64_t c0 = 0; c0 < n; c0 += launch_cols) {
                 const unsigned gy = (unsigned)((std::min(launch_cols, n - c0) + wg_cols - 1) / wg_cols);
@@ -1511,19 +1437,14 @@ static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, c
                                    ld_in, z_fine + out_off, z_coarse ? z_coarse + out_off : nullptr, ld_out,
                                    u_fine ? u_fine + out_off : nullptr, u_coarse ? u_coarse + out_off : nullptr);
             }
-            if (timing && hipEventRecord(e1, st) == hipSuccess) ++timed;
+            tm.end(st);
         }
         MLMC_HIP_CHECK(hipGetLastError());
     }
     if (mass_out) MLMC_HIP_CHECK(hipMemcpyAsync(K.h[0], d_mass, sizeof(double) * M, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
     if (mass_out) std::memcpy(mass_out, K.h[0], sizeof(double) * M);
-    for (size_t k = 0; k < timed; ++k) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]) != hipSuccess) continue;
-        tm.ms += ms;
-        ++tm.launches;
-    }
+    tm.collect();
     meb_ws().trim(MEB_KEEP_BYTES);
     return 0;
 }
@@ -1532,14 +1453,15 @@ static int q_scores(const char *fn, int32_t M, const mlmc_basis *const *bases, c
 static int q_divergences(const char *fn, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                          const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int64_t P,
                          const int32_t *first, const int32_t *second, const double *lo, const double *hi, double *out) {
+    // the head in line, not q_head: P < 0 is an error of a call without problems too
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (B < 0) return fail(std::string(fn) + ": B < 0");
     if (P < 0) return fail(std::string(fn) + ": P < 0");
     if (B == 0 || P == 0) return 0;
     if (!bases || !R1 || !lambda || !sigma || !a || !b || !first || !second || !out) return fail(std::string(fn) + ": null argument");
     if (!lo != !hi) return fail(std::string(fn) + ": lo and hi must both be given or both be NULL");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    int nint, deg;
+    if (q_rule(fn, n_intervals, gauss_degree, nint, deg)) return 1;
     QSetup S;
     const std::vector<int64_t> no_points(B, 0);
     if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, no_points.data(), S)) return 1;
@@ -1564,7 +1486,6 @@ static int q_divergences(const char *fn, int32_t B, const mlmc_basis *const *bas
     }
     const size_t lds = sizeof(double) * (size_t)max_coef;
     if (lds > 65536) return fail(std::string(fn) + ": more than 8192 terms in the two bases of a pair");
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     const size_t row = (size_t)MLMC_DIV_COUNT * nint, n_out = (size_t)MLMC_DIV_COUNT * (size_t)P;
     const int64_t G = (int64_t)std::min<size_t>((size_t)P, std::max<size_t>(1, Q_TABLE_BYTES / (sizeof(double) * row)));
     hipStream_t st = rt().stream;
@@ -1606,12 +1527,9 @@ static QMomLayout q_mom_layout(int n_col_max, int max_coef, int nint, int deg) {
 static int q_moments(const char *fn, int32_t B, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                      const mlmc_basis *const *test, const int32_t *K, double *out, double *mass_out, double *entropy_out) {
-    if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (B < 0) return fail(std::string(fn) + ": B < 0");
-    if (B == 0) return 0;
-    if (!bases || !R1 || !lambda || !sigma || !a || !b || !test || !K || !out) return fail(std::string(fn) + ": null argument");
-    if (n_intervals < 0 || n_intervals > Q_MAX_INTERVALS) return fail(std::string(fn) + ": n_intervals must be in 0..1048576 (0 = 64)");
-    if (gauss_degree < 0 || gauss_degree > 64) return fail(std::string(fn) + ": gauss_degree must be in 0..64 (0 = 21)");
+    if (const int r = q_head(fn, "B", B, bases && R1 && lambda && sigma && a && b && test && K && out)) return r > 0;
+    int nint, deg;
+    if (q_rule(fn, n_intervals, gauss_degree, nint, deg)) return 1;
     QSetup S;
     const std::vector<int64_t> no_points(B, 0);
     if (q_prepare(fn, false, B, bases, R1, lambda, sigma, a, b, no_points.data(), S)) return 1;
@@ -1634,7 +1552,6 @@ static int q_moments(const char *fn, int32_t B, const mlmc_basis *const *bases, 
         max_coef = std::max(max_coef, S.probs[(size_t)i].n_coef);
     }
     if (max_coef > 4096) return fail(std::string(fn) + ": more than 4096 terms in the basis of a density");
-    const int nint = n_intervals > 0 ? n_intervals : 64, deg = gauss_degree > 0 ? gauss_degree : 21;
     const QMomLayout L = q_mom_layout(n_col_max, max_coef, nint, deg);
     const size_t lds = sizeof(double) * ((size_t)L.coef_cap + (size_t)L.cps * ((size_t)deg * L.stride + L.chunk));
     if (L.cps < 1 || lds > Q_MOM_LDS_BYTES) return fail(std::string(fn) + ": internal error: the tile does not fit");
@@ -1746,8 +1663,8 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
                                     int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
                                     int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind) {
     MLMC_API_GUARD;
-    return q_joint("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
-                   streams, first, n, flags, out, u_out, z_out, mass_out, mem_kind);
+    return q_copula("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
+                    streams, first, n, flags, nullptr, out, u_out, z_out, mass_out, mem_kind);
 }
 
 int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
@@ -1756,8 +1673,9 @@ int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *ba
                                           int64_t first, int64_t n, int32_t flags, int32_t B, const double *shift, const int32_t *rows,
                                           int32_t ld_rows, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind) {
     MLMC_API_GUARD;
-    return q_conditional("mlmc_density_sample_conditional_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor,
-                         seed, streams, first, n, flags, B, shift, rows, ld_rows, out, u_out, z_out, mass_out, mem_kind);
+    const QSets sets = {B, shift, rows, ld_rows};
+    return q_copula("mlmc_density_sample_conditional_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
+                    streams, first, n, flags, &sets, out, u_out, z_out, mass_out, mem_kind);
 }
 
 int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,

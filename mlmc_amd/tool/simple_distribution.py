@@ -161,6 +161,50 @@ def _batch_problem_args(distrs):
     return handles, r1, lam, sig
 
 
+def _common_quadrature(what, distrs):
+    """(n_intervals, Gauss degree) of a non-empty list of distributions, which must all use the same"""
+    n_int = {d.n_intervals for d in distrs}
+    degs = {d._gauss_degree for d in distrs}
+    if len(n_int) != 1 or len(degs) != 1:
+        raise ValueError(what + ": every distribution must use the same quadrature")
+    return int(n_int.pop()), int(degs.pop())
+
+
+def _domain_arrays(distrs):
+    """(a [B], b [B]): the ends of the distributions' domains in the layout of the batched density entry points"""
+    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
+    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    return a, b
+
+
+def _check_seed(what, seed):
+    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(what + ": seed must be an integer in 0 .. 2^64 - 1")
+
+
+def _checked_streams(what, streams, count, per):
+    """None, or `streams` as a uint32 array [count]; `per` says in the message what has a stream of its own"""
+    if streams is None:
+        return None
+    st = np.asarray(streams)
+    if st.shape != (count,) or (st.size and (st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32))):
+        raise ValueError("{}: streams must be one integer in 0 .. 2^32 - 1 per {}".format(what, per))
+    return np.ascontiguousarray(st.astype(np.uint32))
+
+
+def _output_arrays(device, shapes):
+    """float64 arrays of the given shapes (None: no array) for the library to write, and their memory kind: NumPy arrays, or
+    (device) tensors on the current device, made before a synchronise of its current stream, since the library writes them on
+    its own stream"""
+    if not device:
+        return [None if s is None else np.empty(s) for s in shapes], _lib.HOST
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    arrays = [None if s is None else torch.empty(s, dtype=torch.float64, device=dev) for s in shapes]
+    torch.cuda.current_stream(dev).synchronize()
+    return arrays, _lib.DEVICE
+
+
 def cdfs(distrs, values):
     """cdf() of many distributions through ONE device call (mlmc_density_integrate_batch).
     values: one array of points for all or a sequence with one array per distribution, as in `densities`.
@@ -212,14 +256,10 @@ def _on_rule(distrs, points, inverse, what, tails=False):
     :return: (list of arrays shaped like the points, masses [B]); with tails ((q, lower, upper, means [B]), masses [B]), q, lower
         and upper each such a list"""
     B = len(distrs)
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError(what + ": every distribution must use the same quadrature")
+    n_int, deg = _common_quadrature(what, distrs)
     on_device = [hasattr(p, "data_ptr") and p.is_cuda for p in points]
     handles, r1, lam, sig = _batch_problem_args(distrs)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    a, b = _domain_arrays(distrs)
     mass = np.empty(B)
     if any(on_device):
         import torch
@@ -238,7 +278,7 @@ def _on_rule(distrs, points, inverse, what, tails=False):
         n = np.array([p.size for p in shaped], dtype=np.int64)
         kind = _lib.HOST
     head = (B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
-            int(n_int.pop()), int(degs.pop()), _lib.ptr(flat), _lib.ptr(n))
+            n_int, deg, _lib.ptr(flat), _lib.ptr(n))
     if tails:
         mean = np.empty(B)
         _lib.check(_lib.lib().mlmc_density_tail_means_batch(*head, _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
@@ -371,41 +411,22 @@ def _samples_flat(distrs, n, seed, streams, first, antithetic, device, return_un
     distrs = list(distrs)
     B = len(distrs)
     flags = _sample_flags("samples", antithetic, qmc)
-    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError("samples: seed must be an integer in 0 .. 2^64 - 1")
+    _check_seed("samples", seed)
     if B == 0:
         return None, None, np.zeros(0, dtype=np.int64)
     n = _per_distribution_int("samples", "n", n, B)
     first = _per_distribution_int("samples", "first", first, B)
+    streams = _checked_streams("samples", streams, B, "distribution")
     if streams is None:
         streams = np.arange(B, dtype=np.uint32)
-    else:
-        st = np.asarray(streams)
-        if st.shape != (B,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
-            raise ValueError("samples: streams must be one integer in 0 .. 2^32 - 1 per distribution")
-        streams = np.ascontiguousarray(st.astype(np.uint32))
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError("samples: every distribution must use the same quadrature")
+    n_int, deg = _common_quadrature("samples", distrs)
     handles, r1, lam, sig = _batch_problem_args(distrs)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    a, b = _domain_arrays(distrs)
     total = int(n.sum())
     lib = _lib.lib()
-    if device:
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        out = torch.empty(total, dtype=torch.float64, device=dev)
-        u = torch.empty(total, dtype=torch.float64, device=dev) if return_uniforms else None
-        torch.cuda.current_stream(dev).synchronize()         # the library writes them on its own stream
-        kind = _lib.DEVICE
-    else:
-        out = np.empty(total)
-        u = np.empty(total) if return_uniforms else None
-        kind = _lib.HOST
+    (out, u), kind = _output_arrays(device, [total, total if return_uniforms else None])
     _lib.check(lib.mlmc_density_sample_batch(B, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a),
-                                             _lib.ptr(b), int(n_int.pop()), int(degs.pop()), int(seed), _lib.ptr(streams),
+                                             _lib.ptr(b), n_int, deg, int(seed), _lib.ptr(streams),
                                              _lib.ptr(first), _lib.ptr(n), flags,
                                              _lib.ptr(out), _lib.ptr(u), None, kind))
     return out, u, n
@@ -416,8 +437,7 @@ def sobol_table(seed, dims, scramble=True):
     1024) the 52 direction numbers [len(dims), 52] and the digital shifts [len(dims)] as uint64, scrambled under `seed`, or with
     scramble=False the raw Joe-Kuo numbers and zero shifts.  Point i of a dimension is the XOR of the direction numbers at the set
     bits of i ^ (i >> 1), XOR the shift; u = (2 m + 1) 2^-53."""
-    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError("sobol_table: seed must be an integer in 0 .. 2^64 - 1")
+    _check_seed("sobol_table", seed)
     d = np.asarray(dims)
     if d.ndim != 1 or (d.size and (d.dtype.kind not in "iu" or np.any(d < 0) or np.any(d.astype(np.uint64) >= 2 ** 32))):
         raise ValueError("sobol_table: dims must be a 1-D array of integers in 0 .. 1023")
@@ -488,8 +508,7 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
     distrs = list(distrs)
     M = len(distrs)
     flags = _sample_flags("joint_samples", antithetic, qmc)
-    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError("joint_samples: seed must be an integer in 0 .. 2^64 - 1")
+    _check_seed("joint_samples", seed)
     if (corr is None) == (factor is None):
         raise ValueError("joint_samples: exactly one of corr and factor must be given")
     if M == 0:
@@ -502,35 +521,14 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
     if factor.ndim != 2 or factor.shape[0] != M or factor.shape[1] < 1:
         raise ValueError("joint_samples: the factor must be [M, K] with M = {} distributions, got shape {}".format(M, factor.shape))
     K = factor.shape[1]
-    if streams is not None:
-        st = np.asarray(streams)
-        if st.shape != (K,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
-            raise ValueError("joint_samples: streams must be one integer in 0 .. 2^32 - 1 per latent normal")
-        streams = np.ascontiguousarray(st.astype(np.uint32))
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError("joint_samples: every distribution must use the same quadrature")
+    streams = _checked_streams("joint_samples", streams, K, "latent normal")
+    n_int, deg = _common_quadrature("joint_samples", distrs)
     handles, r1, lam, sig = _batch_problem_args(distrs)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
-    if device:
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        out = torch.empty((M, n), dtype=torch.float64, device=dev)
-        u = torch.empty((M, n), dtype=torch.float64, device=dev) if return_uniforms else None
-        z = torch.empty((K, n), dtype=torch.float64, device=dev) if return_normals else None
-        torch.cuda.current_stream(dev).synchronize()         # the library writes them on its own stream
-        kind = _lib.DEVICE
-    else:
-        out = np.empty((M, n))
-        u = np.empty((M, n)) if return_uniforms else None
-        z = np.empty((K, n)) if return_normals else None
-        kind = _lib.HOST
+    a, b = _domain_arrays(distrs)
+    (out, u, z), kind = _output_arrays(device, [(M, n), (M, n) if return_uniforms else None, (K, n) if return_normals else None])
     _lib.check(_lib.lib().mlmc_density_sample_joint_batch(
-        M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()),
-        int(degs.pop()), K, _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, flags,
-        _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
+        M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg, K,
+        _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, flags, _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
     extra = tuple(v for v, want in ((u, return_uniforms), (z, return_normals)) if want)
     return (out,) + extra if extra else out
 
@@ -666,25 +664,19 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
     distrs = list(distrs)
     M = len(distrs)
     flags = _sample_flags(what, antithetic, qmc)
-    if seed is None or isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(what + ": seed must be an integer in 0 .. 2^64 - 1")
+    _check_seed(what, seed)
     n = int(_per_distribution_int(what, "n", n, 1)[0])
     first = int(_per_distribution_int(what, "first", first, 1)[0])
-    _parse_given(what, given, M)                              # its errors come before anything touches the device
-    if M and (len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1):
-        raise ValueError(what + ": every distribution must use the same quadrature")
+    _parse_given(what, given, M)                # its errors come before anything touches the device; one of them is M = 0
+    n_int, deg = _common_quadrature(what, distrs)
     observed, values, scalar, u_obs, (_, fc, info), mu = _conditioning(what, distrs, given, corr, factor_info)
     unobs = np.ascontiguousarray(info.unobserved, dtype=np.int32)
     q, K, B = unobs.size, fc.shape[1], values.shape[1]
-    if streams is not None:
-        st = np.asarray(streams)
-        if st.shape != (K,) or st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32):
-            raise ValueError(what + ": streams must be one integer in 0 .. 2^32 - 1 per latent normal")
-        streams = np.ascontiguousarray(st.astype(np.uint32))
+    streams = _checked_streams(what, streams, K, "latent normal")
     free = [distrs[m] for m in unobs]
     handles, r1, lam, sig = _batch_problem_args(free)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in free], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in free], dtype=np.float64)
+    a, b = _domain_arrays(free)
+    # the arrays are not those of _output_arrays: the rows of the given components are filled in before the synchronise
     if device:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -705,7 +697,7 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
         kind = _lib.HOST
     _lib.check(_lib.lib().mlmc_density_sample_conditional_batch(
         q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
-        int(distrs[0].n_intervals), int(distrs[0]._gauss_degree), K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
+        n_int, deg, K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
         flags, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
         _lib.ptr(u), None, None, kind))
     if scalar:
@@ -802,14 +794,10 @@ def _box_limits(what, lower, upper, M, name="M"):
 
 
 def _box_streams(what, streams, M, qmc):
-    if streams is None:
-        return None
-    st = np.asarray(streams)
-    if st.shape != (M - 1,) or (st.size and (st.dtype.kind not in "iu" or np.any(st < 0) or np.any(st.astype(np.uint64) >= 2 ** 32))):
-        raise ValueError(what + ": streams must be one integer in 0 .. 2^32 - 1 per coordinate, {} of them".format(M - 1))
-    if qmc and st.size and np.any(st.astype(np.uint64) >= 1024):
+    st = _checked_streams(what, streams, M - 1, "coordinate, {} of them".format(M - 1))
+    if qmc and st is not None and np.any(st >= 1024):
         raise ValueError(what + ": with qmc the streams are Sobol' dimensions and must be below 1024")
-    return np.ascontiguousarray(st.astype(np.uint32))
+    return st
 
 
 def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
@@ -863,15 +851,7 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     R = seeds.size
     flags = _lib.SAMPLE_SOBOL if qmc else 0
     mean = np.empty((R, B))
-    integrand, kind = None, _lib.HOST
-    if return_integrand and device:
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        integrand = torch.empty((R, B, n), dtype=torch.float64, device=dev)
-        torch.cuda.current_stream(dev).synchronize()         # the library writes it on its own stream
-        kind = _lib.DEVICE
-    elif return_integrand:
-        integrand = np.empty((R, B, n))
+    (integrand,), kind = _output_arrays(device and return_integrand, [(R, B, n) if return_integrand else None])
     _lib.check(_lib.lib().mlmc_copula_box_prob_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R, _lib.ptr(seeds),
                                                     _lib.ptr(streams), first, n, flags, _lib.ptr(mean), _lib.ptr(integrand), kind))
     result = _joint_probability(mean, n, seeds)
@@ -909,8 +889,7 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
-    if len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1:
-        raise ValueError(what + ": every distribution must use the same quadrature")
+    _common_quadrature(what, distrs)
     if factor is not None:
         fac = np.asarray(factor, dtype=np.float64)
         if fac.ndim != 2 or fac.shape[0] != M or fac.shape[1] < 1 or not np.all(np.isfinite(fac)):
@@ -934,8 +913,7 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         lo, hi = np.repeat(lo, Bg, axis=0), np.repeat(hi, Bg, axis=0)
         B = Bg
     # scores of the limits: infinite where the limit is, or lies at or beyond an end of the domain; the rest in one device call
-    a = np.array([float(distrs[m].domain[0]) for m in free])
-    b = np.array([float(distrs[m].domain[1]) for m in free])
+    a, b = _domain_arrays([distrs[m] for m in free])
     z_lo, z_hi = np.full((B, q), -np.inf), np.full((B, q), np.inf)
     z_lo[lo >= b[None, :]] = np.inf
     z_hi[hi <= a[None, :]] = -np.inf
@@ -973,16 +951,11 @@ def _scores_problem_args(distrs, what):
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError(what + ": every distribution must use the same quadrature")
+    n_int, deg = _common_quadrature(what, distrs)
     handles, r1, lam, sig = _batch_problem_args(distrs)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    a, b = _domain_arrays(distrs)
     keep = (handles, r1, lam, sig, a, b)
-    head = (M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()),
-            int(degs.pop()))
+    head = (M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg)
     return head, keep
 
 
@@ -1011,8 +984,7 @@ def normal_scores(distrs, fine, coarse=None, device=False, return_uniforms=False
     M = len(distrs)
     if M == 0:
         raise ValueError("normal_scores: no distributions")
-    if len({d.n_intervals for d in distrs}) != 1 or len({d._gauss_degree for d in distrs}) != 1:
-        raise ValueError("normal_scores: every distribution must use the same quadrature")
+    _common_quadrature("normal_scores", distrs)
 
     def checked(x, name):                                           # before anything touches the device
         if hasattr(x, "data_ptr"):
@@ -1078,14 +1050,10 @@ def divergences(priors, posteriors, intervals=None):
         if id(d) not in index:
             index[id(d)] = len(distrs)
             distrs.append(d)
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError("divergences: every distribution must use the same quadrature")
+    n_int, deg = _common_quadrature("divergences", distrs)
     first = np.array([index[id(d)] for d in priors], dtype=np.int32)
     second = np.array([index[id(d)] for d in posteriors], dtype=np.int32)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    a, b = _domain_arrays(distrs)
     lo = hi = None                                                   # the library takes the intersections
     if intervals is None:
         empty = np.flatnonzero(~(np.maximum(a[first], a[second]) < np.minimum(b[first], b[second])))
@@ -1100,9 +1068,8 @@ def divergences(priors, posteriors, intervals=None):
     handles, r1, lam, sig = _batch_problem_args(distrs)
     out = np.empty((P, 6))
     _lib.check(_lib.lib().mlmc_density_divergences_batch(len(distrs), C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam),
-                                                         _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), int(n_int.pop()), int(degs.pop()),
-                                                         P, _lib.ptr(first), _lib.ptr(second), _lib.ptr(lo), _lib.ptr(hi),
-                                                         _lib.ptr(out)))
+                                                         _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg, P, _lib.ptr(first),
+                                                         _lib.ptr(second), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(out)))
     return Divergences(out[:, 0].copy(), np.sqrt(out[:, 1]), out[:, 2].copy(), np.sqrt(out[:, 3]), out[:, 4].copy(), out[:, 5].copy())
 
 
@@ -1146,10 +1113,8 @@ def _moment_problems(what, distrs, moments_fns, sizes):
             raise ValueError("{}: distribution {}: size must be an integer in 1..{}, got {!r}".format(what, i, fn.size, k))
         if getattr(fn, "_kind", None) not in (_lib.LEGENDRE, _lib.MONOMIAL, _lib.FOURIER, _lib.SPLINE):
             raise ValueError("{}: distribution {}: {} moments are not supported".format(what, i, type(fn).__name__))
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) > 1 or len(degs) > 1:
-        raise ValueError(what + ": every distribution must use the same quadrature")
+    if distrs:
+        _common_quadrature(what, distrs)
     return fns, np.array(sizes, dtype=np.int32)
 
 
@@ -1158,8 +1123,7 @@ def _raw_density_moments(what, distrs, moments_fns, sizes):
     fns, k = _moment_problems(what, distrs, moments_fns, sizes)
     B = len(distrs)
     handles, r1, lam, sig = _batch_problem_args(distrs)
-    a = np.ascontiguousarray([float(d.domain[0]) for d in distrs], dtype=np.float64)
-    b = np.ascontiguousarray([float(d.domain[1]) for d in distrs], dtype=np.float64)
+    a, b = _domain_arrays(distrs)
     tests = (C.c_void_p * B)(*[fn._basis_handle().value for fn in fns])
     out = np.empty((B, int(k.max())))
     mass, ent = np.empty(B), np.empty(B)
@@ -1268,16 +1232,12 @@ def estimate_densities_minimize(distrs, tol=1e-5, reg_param=0.01):
     distrs = list(distrs)
     if not distrs:
         return []
-    n_int = {d.n_intervals for d in distrs}
-    degs = {d._gauss_degree for d in distrs}
-    if len(n_int) != 1 or len(degs) != 1:
-        raise ValueError("estimate_densities_minimize: every distribution must use the same quadrature")
+    n_int, deg = _common_quadrature("estimate_densities_minimize", distrs)
     for d in distrs:
         d._initialize_params(d.approx_size, tol)
     solved = _solve_batch_on_device([d.moments_fn for d in distrs], [d.moment_means for d in distrs],
                                     [d._moment_errs for d in distrs], [d.domain for d in distrs],
-                                    [d.multipliers for d in distrs], tol, max_it=100, n_intervals=n_int.pop(),
-                                    gauss_degree=degs.pop())
+                                    [d.multipliers for d in distrs], tol, max_it=100, n_intervals=n_int, gauss_degree=deg)
     return [d._finish_minimize(lam, grad, hess, info, tol) for d, (lam, grad, hess, info) in zip(distrs, solved)]
 
 

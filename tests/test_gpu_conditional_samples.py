@@ -1,5 +1,5 @@
 """GPU tests of the conditional joint draws under the Gaussian copula (the SHIFT instance of k_cop_uniforms in
-mlmc_amd/csrc/copula.hip, the SETS instances of k_q_sample and q_conditional in density.hip) through
+mlmc_amd/csrc/copula.hip, the SETS instances of k_q_sample and q_copula with sets in density.hip) through
 mlmc_density_sample_conditional_batch, simple_distribution.conditional_samples / conditional_quantiles / conditional_cdfs and
 Estimate.sample_conditional / estimate_conditional_quantiles.
 
