@@ -42,7 +42,7 @@ extern "C" {
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
                               *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
-                              *    three sampling entries), mlmc_copula_box_prob_batch */
+                              *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -620,6 +620,31 @@ int mlmc_density_quantiles_kernel_time(double *ms, int64_t *launches);
 int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                                const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
                                double *f_out, int mem_kind);
+/* Scenarios of Y = shift + L z GIVEN lo < Y < hi, with importance weights -- added within 8: the conditioned normals y_0 .. y_{M-1}
+ * of the chain above are a sequential importance sample of the truncated normal vector (the GHK sampler), every point a scenario
+ * inside the box, its weight the integrand f.  M, L, B, lo, hi, shift, R, seeds, first, n, flags, mean and every argument error
+ * are those of mlmc_copula_box_prob_batch; streams is [M] (NULL: i): coordinate M-1 draws the last component.  The chain is the
+ * chain above operation by operation, with for EVERY i = 0 .. M-1 (i = M-1 included; the same clamp of the argument):
+ *     y_i = sign * normcdfinv(min(max(d + (w_i * width), 2^-1022), 1 - 2^-53))
+ *     z_i = min(max(s + (L[i][i] * y_i), lo[b][i]), hi[b][i])           (one rounded product, one rounded sum, no FMA)
+ *     u_i = min(max(normcdf(z_i), 2^-53), 1 - 2^-53)                    (the clamp of mlmc_density_sample_joint_batch)
+ * f_out [R][B][n] the weights, z_out and u_out (may be NULL) [R][B][M][n], column j - first; host or device arrays by mem_kind;
+ * f_out and z_out must not be NULL.  mean [R][B] host.  Host outputs are staged within the 192 MiB of the entry above (the
+ * weights, z and u of a launch together), split by whole blocks of 64 points.
+ *   f_out and mean are bit for bit those of mlmc_copula_box_prob_batch for the same L, box, seed, first, n, flag and
+ *     streams[0 .. M-2].  M = 1 draws from its one coordinate; its weight is e - d, as there.
+ *   lo_i <= z_i <= hi_i for every draw of a box that is not empty, draws of weight 0 included (a width that underflowed), and every
+ *     such z is finite: y is finite by the clamp and the limits only bound it.  In a component of an empty box (lo_i >= hi_i)
+ *     every draw is z_i = hi_i (finite where hi_i is) and the weight is 0; the chain goes on with y_i, which stays finite.
+ *   A value depends on (L, box, seed, streams, j, flag) alone: not on B, on R, on the position of the box or the seed, on first / n
+ *     (first = 50, n = 100 gives the columns [50, 150) of first = 0, n = 150), on the launch split (MLMC_BOX_PROB_BLOCK_POINTS as
+ *     above), on the presence of u_out or on host / device outputs.
+ *   The box (-inf, inf)^M gives weights exactly 1 and z = L normcdfinv(w): plain joint draws.
+ * A lane stores its z_i at consecutive j, so the stores of a wave are coalesced per component; the last y stays in a register
+ * (LDS 512 (M - 1) bytes per wave and the cap as above); no atomics; one host wait. */
+int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
+                                const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
+                                double *f_out, double *z_out, double *u_out, int mem_kind);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

@@ -114,6 +114,8 @@ SIGNATURES = {
     "mlmc_density_quantiles_kernel_time": (C.c_int, [_dp, _ip]),
     "mlmc_copula_box_prob_batch": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int64, C.c_int64,
                                              C.c_int32, _vp, _vp, C.c_int]),
+    "mlmc_copula_box_draws_batch": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int64, C.c_int64,
+                                              C.c_int32, _vp, _vp, _vp, _vp, C.c_int]),
     "mlmc_expr_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "mlmc_expr_destroy": (None, [_vp]),
     "mlmc_expr_eval": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _ip]),

@@ -9,13 +9,16 @@
 //                fetches them with scalar loads.  Under MLMC_SAMPLE_SOBOL the block is aligned to 64 points, so the Gray code of
 //                j = 64 a ^ lane is G(64 a) ^ G(lane): the part of the block is an XOR of scalar loads, the lane adds at most six
 //                of the words V'[0 .. 5].  The wave sums its 64 values in a fixed butterfly and lane 0 stores the block's partial.
+//                The DRAWS instances (mlmc_copula_box_draws_batch) are the same text: they also take a coordinate for the last
+//                component, keep its y in a register, and store every step's score z_i (clamped to its limits) and, if asked,
+//                its normcdf at column j of row (seed, box, i): a wave writes 64 consecutive doubles per component.
 //   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
 // The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
 // k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
 // fixed by (first, n) alone.  Launches are split by whole blocks, so no value depends on the split.
 // The chain loops over i around normcdf / normcdfinv; copula.hip and sobol.hip avoid such a loop because the inlined functions'
 // constants then stay in registers.  Here the two are called through functions that are not inlined (below); the resource figures
-// are in DESIGN.md 3.5.17.
+// are in DESIGN.md 3.5.17 and 3.5.18.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -50,15 +53,17 @@ __device__ __forceinline__ double box_sobol_unit(const uint64_t *__restrict__ ro
 __device__ __attribute__((noinline)) double box_normcdf(double x) { return normcdf(x); }
 __device__ __attribute__((noinline)) double box_normcdfinv(double p) { return normcdfinv(p); }
 
-// grid (blocks of the launch, boxes, seeds); box = b0 + blockIdx.y, seed = r0 + blockIdx.z
-template <bool SOBOL>
+// grid (blocks of the launch, boxes, seeds); box = b0 + blockIdx.y, seed = r0 + blockIdx.z.  DRAWS (mlmc_copula_box_draws_batch): the
+// same chain, one text; coordinate M - 1 draws the last component too (its y stays in a register), and every step stores the
+// score z_i = s + L_ii y_i clamped to its limits, and its normcdf, at column j of row i: consecutive lanes, consecutive doubles.
+template <bool SOBOL, bool DRAWS>
 __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__restrict__ L, const double *__restrict__ lo,
                                                         const double *__restrict__ hi, const double *__restrict__ shift, int B, int b0,
                                                         const uint64_t *__restrict__ seeds, int r0, const uint32_t *__restrict__ streams,
                                                         const uint64_t *__restrict__ table, int table_rows, int64_t first, int64_t n,
                                                         int64_t blk0, int64_t call_blk0, int64_t call_blocks,
                                                         double *__restrict__ partials, double *__restrict__ f_out, int64_t ldf,
-                                                        int64_t c_off) {
+                                                        int64_t c_off, double *__restrict__ z_out, double *__restrict__ u_out) {
     extern __shared__ double ys[];                     // y[k][lane]
     const int lane = threadIdx.x;
     const int b = b0 + (int)blockIdx.y, r = r0 + (int)blockIdx.z;
@@ -80,13 +85,24 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
         const double d = box_normcdf(refl ? -bp : ap), e = box_normcdf(refl ? -ap : bp);
         const double width = l < h ? e - d : 0.0;
         f *= width;
-        if (i < M - 1) {
+        if (DRAWS || i < M - 1) {
             double w;
             if constexpr (SOBOL) w = box_sobol_unit(tab + (int64_t)streams[i] * SOBOL_ROW, (uint64_t)a, lane);
             else w = q_uniform(seed, streams[i], (uint64_t)j);
             const double p = fmin(fmax(__dadd_rn(d, __dmul_rn(w, width)), 0x1p-1022), 1.0 - 0x1p-53);
-            const double y = box_normcdfinv(p);
-            ys[i * BOX_LANES + lane] = refl ? -y : y;
+            double y = box_normcdfinv(p);
+            y = refl ? -y : y;
+            if (i < M - 1) ys[i * BOX_LANES + lane] = y;
+            if constexpr (DRAWS) {
+                // an empty component (l >= h) gives h: max(., l) >= l >= h
+                const double z = fmin(fmax(__dadd_rn(s, __dmul_rn(lii, y)), l), h);
+                const int64_t at = (((int64_t)r * B + b) * M + i) * ldf + (j - first - c_off);
+                if (active) z_out[at] = z;
+                if (u_out) {
+                    const double u = fmin(fmax(box_normcdf(z), 0x1p-53), 1.0 - 0x1p-53);
+                    if (active) u_out[at] = u;
+                }
+            }
         }
     }
     if (active && f_out) f_out[((int64_t)r * B + b) * ldf + (j - first - c_off)] = f;
@@ -115,14 +131,14 @@ __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__r
 
 static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                     const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
-                    int mem_kind) {
+                    int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr) {
     const std::string e(fn);
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (M < 1) return fail(e + ": M < 1");
     if (M > MLMC_BOX_PROB_MAX_M) return fail(e + ": M = " + std::to_string(M) + " is above the cap " + std::to_string(MLMC_BOX_PROB_MAX_M));
     if (B < 1) return fail(e + ": B < 1");
     if (R < 1) return fail(e + ": R < 1");
-    if (!L || !lo || !hi || !seeds || !mean) return fail(e + ": null argument");
+    if (!L || !lo || !hi || !seeds || !mean || (draws && (!f_out || !z_out))) return fail(e + ": null argument");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(e + ": bad mem_kind");
     if (flags & ~(MLMC_SAMPLE_ANTITHETIC | MLMC_SAMPLE_SOBOL)) return fail(e + ": unknown bits in flags");
     if (flags & MLMC_SAMPLE_ANTITHETIC) return fail(e + ": MLMC_SAMPLE_ANTITHETIC does not apply to this entry");
@@ -147,7 +163,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                 return fail(e + ": box " + std::to_string(b) + ", component " + std::to_string(i) + ": the shift is not finite");
         }
     // the coordinates: streams (Philox), or the rows of the call's distinct dimensions, one table per seed (MLMC_SAMPLE_SOBOL)
-    const int nc = M - 1;
+    const int nc = draws ? M : M - 1;                   // the draws take one more coordinate for the last component
     std::vector<uint32_t> coord((size_t)nc);
     std::vector<uint64_t> tables;
     int table_rows = 0;
@@ -170,10 +186,15 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     // blocks of a launch: all of them, or what keeps the staged integrand within BOX_F_BYTES (MLMC_BOX_PROB_BLOCK_POINTS in the
     // environment, read per call, sets the points of a launch, rounded up to whole blocks: a test aid, no value depends on it)
     const bool stage = f_out && mem_kind == MLMC_HOST;
+    // staged rows of a pair: the integrand, and with draws the M rows of z and of u
+    const size_t zrows = draws ? pairs * (size_t)M : 0, urows = u_out ? zrows : 0, rows = pairs + zrows + urows;
     int64_t lb = std::min<int64_t>(call_blocks, 0x7fffffff);
     if (stage) {
-        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * pairs)));
-        if (lb < 1) return fail(e + ": the integrand of one block of 64 points of R * B pairs exceeds 192 MiB: split the boxes or the seeds across calls");
+        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * rows)));
+        if (lb < 1)
+            return fail(e + (draws ? ": the draws" : ": the integrand") +
+                        " of one block of 64 points of R * B pairs exceed" + (draws ? "" : "s") +
+                        " 192 MiB: split the boxes or the seeds across calls");
     }
     if (const char *env = std::getenv("MLMC_BOX_PROB_BLOCK_POINTS")) {
         const long long v = std::atoll(env);
@@ -196,18 +217,22 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
 
     const size_t b_in = mm_align(sizeof(double) * n_in), b_part = mm_align(sizeof(double) * pairs * (size_t)call_blocks);
     const size_t b_mean = mm_align(sizeof(double) * pairs), b_f = stage ? mm_align(sizeof(double) * pairs * (size_t)ldf) : 0;
+    const size_t b_z = stage ? mm_align(sizeof(double) * zrows * (size_t)ldf) : 0, b_u = stage ? mm_align(sizeof(double) * urows * (size_t)ldf) : 0;
     static MultiWorkspace ws;
-    if (ws.reserve(b_in + b_part + b_mean + b_f)) return 1;
+    if (ws.reserve(b_in + b_part + b_mean + b_f + b_z + b_u)) return 1;
     double *d_in = (double *)ws.dev, *d_part = (double *)(ws.dev + b_in), *d_mean = (double *)(ws.dev + b_in + b_part);
     double *d_f = stage ? (double *)(ws.dev + b_in + b_part + b_mean) : f_out;
+    double *d_z = stage && draws ? (double *)(ws.dev + b_in + b_part + b_mean + b_f) : z_out;
+    double *d_u = stage && u_out ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z) : u_out;
     hipStream_t st = rt().stream;
     MLMC_HIP_CHECK(hipMemcpyAsync(d_in, packed.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, st));
     const double *d_L = d_in, *d_lo = d_L + nL, *d_hi = d_lo + nbx, *d_shift = nsh ? d_hi + nbx : nullptr;
     const uint64_t *d_seeds = (const uint64_t *)(d_hi + nbx + nsh), *d_tab = d_seeds + R;
     const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
 
-    const size_t lds = sizeof(double) * BOX_LANES * (size_t)nc;
-    const auto kernel = sobol ? k_box_prob<true> : k_box_prob<false>;
+    const size_t lds = sizeof(double) * BOX_LANES * (size_t)(M - 1);
+    const auto kernel = draws ? (sobol ? k_box_prob<true, true> : k_box_prob<false, true>)
+                              : (sobol ? k_box_prob<true, false> : k_box_prob<false, false>);
     for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
         const int64_t kb = std::min(lb, call_blocks - k0);
         // the first point of the launch within the call: column 0 of the staged integrand
@@ -218,12 +243,19 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                 const dim3 grid((unsigned)kb, (unsigned)std::min(B - b0, 65535), (unsigned)std::min(R - r0, 65535));
                 hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, d_shift, (int)B, b0, d_seeds, r0, d_coord,
                                    d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part, d_f, ldf,
-                                   stage ? c_lo : (int64_t)0);
+                                   stage ? c_lo : (int64_t)0, d_z, d_u);
             }
         MLMC_HIP_CHECK(hipGetLastError());
-        if (stage)
+        if (stage) {
             MLMC_HIP_CHECK(hipMemcpy2DAsync(f_out + c_lo, sizeof(double) * (size_t)n, d_f, sizeof(double) * (size_t)ldf,
                                             sizeof(double) * (size_t)(c_hi - c_lo), pairs, hipMemcpyDeviceToHost, st));
+            if (draws)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c_lo, sizeof(double) * (size_t)n, d_z, sizeof(double) * (size_t)ldf,
+                                                sizeof(double) * (size_t)(c_hi - c_lo), zrows, hipMemcpyDeviceToHost, st));
+            if (u_out)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + c_lo, sizeof(double) * (size_t)n, d_u, sizeof(double) * (size_t)ldf,
+                                                sizeof(double) * (size_t)(c_hi - c_lo), urows, hipMemcpyDeviceToHost, st));
+        }
     }
     hipLaunchKernelGGL(k_box_mean, dim3((unsigned)pairs), dim3(BOX_MEAN_THREADS), 0, st, (const double *)d_part, call_blocks, n,
                        (int)(M == 1), d_mean);
@@ -244,6 +276,14 @@ int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const doub
                                double *f_out, int mem_kind) {
     MLMC_API_GUARD;
     return box_prob("mlmc_copula_box_prob_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind);
+}
+
+int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
+                                const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
+                                double *f_out, double *z_out, double *u_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_draws_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
+                    z_out, u_out);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ BootstrapReplicates = collections.namedtuple("BootstrapReplicates", "n_samples l
 ComponentBootstrapReplicates = collections.namedtuple("ComponentBootstrapReplicates", "n_samples l_means l_vars mean var seed")
 QuantileBands = collections.namedtuple("QuantileBands", "q lo hi replicates success n_ok seed")
 ScoreCorrelation = collections.namedtuple("ScoreCorrelation", "corr cov cov_var mean var n_samples n_rm_samples")
+EventMeans = collections.namedtuple("EventMeans", "mean stderr prob ess")
 
 
 def quantile_bands(replicates, success, level):
@@ -894,6 +895,51 @@ class Estimate:
         return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
                                                first=first, qmc=qmc)
+
+    def sample_given_event(self, n, lower, upper, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
+                           orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True):
+        """Joint scenarios of all components GIVEN that they lie in a box at once (lower_m < X_m < upper_m for all m), under the
+        marginals and the Gaussian copula of `sample_joint`, for B events and R seeds (tool.simple_distribution.event_samples):
+        what the system looks like when the event of `estimate_joint_probability` happens.  Every scenario lies in the event and
+        carries an importance weight, at any probability of the event; filtering the scenarios of `sample_joint` keeps none of
+        2^16 at a probability of 1e-6.
+        :param n: scenarios per seed and event; a power of two with `first` a multiple of it
+        :param lower, upper: broadcast to [B, M] in the components' own units; +-inf does not constrain that side
+        :param seeds: one independent scramble each
+        :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
+        :param given: None, or as in sample_conditional: the scenarios are conditional on these values too; a given component
+            must not be constrained
+        :param densities: as in estimate_component_quantiles
+        :param device: the arrays of the result are float64 torch device tensors
+        :return: (EventScenarios(draws [R, B, M, n], weights [R, B, n], prob, ess [R, B], ok [M], uniforms), success [M])"""
+        from .tool import simple_distribution
+        what = "sample_given_event"
+        n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
+        if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
+            raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
+        corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        result = simple_distribution.event_samples([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
+                                                   given=given, first=first, qmc=qmc, device=device)
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        return result, success
+
+    def estimate_event_means(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
+                             orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+        """Expected value of EVERY component given that the components lie in a box at once, E[X | lower < X < upper]: the weighted
+        means of the scenarios of `sample_given_event`.  `estimate_event_means(thresholds, np.inf)` is the companion of
+        `estimate_joint_exceedance`: the expected state of the system when all thresholds are exceeded.  The weights are smooth on
+        the Sobol' points, so the error falls like 1 / n at any probability of the event.
+        :param lower, upper, n, seeds, corr, given, densities, first, qmc: as in sample_given_event
+        :return: (EventMeans(mean [B, M], stderr [B, M], prob, ess [R, B]), success [M]): per seed the ratio sum f x / sum f, its
+            mean over the seeds and their spread over sqrt(R); prob the JointProbability of the event; ess the effective sample
+            size of each seed's n scenarios"""
+        scen, success = self.sample_given_event(n, lower, upper, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
+                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
+                                                first=first, qmc=qmc)
+        mean, stderr = scen.means()
+        return EventMeans(mean, stderr, scen.prob, scen.ess), success
 
     def estimate_conditional_quantiles(self, probs, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                        densities=None):

@@ -800,27 +800,8 @@ def _box_streams(what, streams, M, qmc):
     return st
 
 
-def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
-                             device=False):
-    """P(lower < Y < upper) for Y = shift + F z, z standard normal, for B boxes and R seeds through ONE device call
-    (mlmc_copula_box_prob_batch): Genz's separation of variables, which conditions through the lower-triangular factor with one
-    Phi^-1 and two Phi per component, so that the integrand is a smooth function on the unit cube.  Everything is in SCORE space
-    (`joint_probabilities` maps limits in the components' own units).  On scrambled Sobol' points (qmc=True) the error falls
-    like 1 / n and is relative: a probability of 1e-8 is resolved as well as one of 0.1, which counting scenarios of
-    `joint_samples` cannot do.  Each seed gives one independent estimate; `prob` is their mean and `stderr` the sample standard
-    deviation of the R means over sqrt(R) (NaN for one seed).  A replicate depends on (factor, box, seed, streams, first, n, qmc)
-    alone and is bitwise repeatable.
-    :param factor: [M, M] lower triangular with a positive diagonal (the upper part is ignored); rows need not have unit norm, so
-        F_c of `conditional_factor` is accepted.  M <= 128
-    :param lower, upper: broadcast to [B, M], +-inf allowed; a box that is empty in some component has probability exactly 0
-    :param n: points per seed, indices first .. first + n - 1; with qmc a power of two with `first` a multiple of it
-    :param seeds: R integers in 0 .. 2^64 - 1
-    :param shift: None or the mean of the scores, broadcast to [B, M]
-    :param streams: one stream (qmc: Sobol' dimension below 1024) per coordinate, M - 1 of them; default: i
-    :param qmc: scrambled Sobol' points (MLMC_SAMPLE_SOBOL); False: Philox uniforms
-    :param return_integrand: also return the integrand [R, B, n] (a float64 torch device tensor with device=True)
-    :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
-    what = "copula_box_probabilities"
+def _box_problem(what, factor, lower, upper, shift):
+    """(factor [M, M] lower triangular, lo [B, M], hi [B, M], shift [B, M] or None) of a call in score space, checked"""
     f = np.array(factor, dtype=np.float64)
     if f.ndim != 2 or f.shape[0] != f.shape[1] or f.shape[0] < 1:
         raise ValueError(what + ": the factor must be a square matrix, got shape {}".format(f.shape))
@@ -846,6 +827,32 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
         if not np.all(np.isfinite(sh)):
             raise ValueError(what + ": the shift must be finite")
         shift = sh
+    return f, lo, hi, shift
+
+
+def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
+                             device=False):
+    """P(lower < Y < upper) for Y = shift + F z, z standard normal, for B boxes and R seeds through ONE device call
+    (mlmc_copula_box_prob_batch): Genz's separation of variables, which conditions through the lower-triangular factor with one
+    Phi^-1 and two Phi per component, so that the integrand is a smooth function on the unit cube.  Everything is in SCORE space
+    (`joint_probabilities` maps limits in the components' own units).  On scrambled Sobol' points (qmc=True) the error falls
+    like 1 / n and is relative: a probability of 1e-8 is resolved as well as one of 0.1, which counting scenarios of
+    `joint_samples` cannot do.  Each seed gives one independent estimate; `prob` is their mean and `stderr` the sample standard
+    deviation of the R means over sqrt(R) (NaN for one seed).  A replicate depends on (factor, box, seed, streams, first, n, qmc)
+    alone and is bitwise repeatable.
+    :param factor: [M, M] lower triangular with a positive diagonal (the upper part is ignored); rows need not have unit norm, so
+        F_c of `conditional_factor` is accepted.  M <= 128
+    :param lower, upper: broadcast to [B, M], +-inf allowed; a box that is empty in some component has probability exactly 0
+    :param n: points per seed, indices first .. first + n - 1; with qmc a power of two with `first` a multiple of it
+    :param seeds: R integers in 0 .. 2^64 - 1
+    :param shift: None or the mean of the scores, broadcast to [B, M]
+    :param streams: one stream (qmc: Sobol' dimension below 1024) per coordinate, M - 1 of them; default: i
+    :param qmc: scrambled Sobol' points (MLMC_SAMPLE_SOBOL); False: Philox uniforms
+    :param return_integrand: also return the integrand [R, B, n] (a float64 torch device tensor with device=True)
+    :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
+    what = "copula_box_probabilities"
+    f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
+    M, B = f.shape[0], lo.shape[0]
     n, seeds, first = _box_call_args(what, n, seeds, first)
     streams = _box_streams(what, streams, M, qmc)
     R = seeds.size
@@ -864,6 +871,31 @@ def _joint_probability(replicates, n, seeds):
     prob = replicates.mean(axis=0)
     stderr = np.std(replicates, axis=0, ddof=1) / np.sqrt(R) if R > 1 else np.full(replicates.shape[1], np.nan)
     return JointProbability(prob, stderr, replicates, n, seeds)
+
+
+def _limit_scores(what, distrs, lo, hi):
+    """Normal scores of the limits lo, hi [B, q] of q distributions: (z_lo, z_hi, keep, finish).  A limit that is infinite, or lies
+    at or beyond an end of its distribution's domain, is an infinite score exactly and is set here, on the host; keep holds the
+    components that some box constrains; finish() fills in the other limits in place through ONE `normal_scores` call"""
+    B, q = lo.shape
+    a, b = _domain_arrays(distrs)
+    z_lo, z_hi = np.full((B, q), -np.inf), np.full((B, q), np.inf)
+    z_lo[lo >= b[None, :]] = np.inf
+    z_hi[hi <= a[None, :]] = -np.inf
+    in_lo, in_hi = (lo > a[None, :]) & (lo < b[None, :]), (hi > a[None, :]) & (hi < b[None, :])
+    keep = np.flatnonzero(np.any((z_lo > 0) | in_lo | (z_hi < 0) | in_hi, axis=0))           # constrained in some box
+
+    def finish():
+        if not (np.any(in_lo) or np.any(in_hi)):
+            return
+        mid = 0.5 * (a + b)
+        x = np.concatenate([np.where(in_lo, lo, mid[None, :]), np.where(in_hi, hi, mid[None, :])], axis=0).T     # [q, 2 B]
+        z = normal_scores([distrs[m] for m in keep], np.ascontiguousarray(x[keep]))
+        z_lo[:, keep] = np.where(in_lo[:, keep], z[:, :B].T, z_lo[:, keep])
+        z_hi[:, keep] = np.where(in_hi[:, keep], z[:, B:].T, z_hi[:, keep])
+        if np.any(np.isnan(z_lo)) or np.any(np.isnan(z_hi)):
+            raise ValueError(what + ": a limit has no normal score (a distribution without a positive finite mass?)")
+    return z_lo, z_hi, keep, finish
 
 
 def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True,
@@ -912,27 +944,14 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
     if B == 1 and Bg > 1:
         lo, hi = np.repeat(lo, Bg, axis=0), np.repeat(hi, Bg, axis=0)
         B = Bg
-    # scores of the limits: infinite where the limit is, or lies at or beyond an end of the domain; the rest in one device call
-    a, b = _domain_arrays([distrs[m] for m in free])
-    z_lo, z_hi = np.full((B, q), -np.inf), np.full((B, q), np.inf)
-    z_lo[lo >= b[None, :]] = np.inf
-    z_hi[hi <= a[None, :]] = -np.inf
-    in_lo, in_hi = (lo > a[None, :]) & (lo < b[None, :]), (hi > a[None, :]) & (hi < b[None, :])
-    keep = np.flatnonzero(np.any((z_lo > 0) | in_lo | (z_hi < 0) | in_hi, axis=0))           # constrained in some box
+    z_lo, z_hi, keep, finish = _limit_scores(what, [distrs[m] for m in free], lo, hi)
     streams = _box_streams(what, streams, max(keep.size, 1), qmc)
     if keep.size > _lib.BOX_PROB_MAX_M:
         raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
     if keep.size == 0:
         ones = _joint_probability(np.ones((seeds.size, B)), n, seeds)
         return (ones, None) if return_integrand else ones
-    if np.any(in_lo) or np.any(in_hi):
-        mid = 0.5 * (a + b)
-        x = np.concatenate([np.where(in_lo, lo, mid[None, :]), np.where(in_hi, hi, mid[None, :])], axis=0).T     # [q, 2 B]
-        z = normal_scores([distrs[m] for m in free[keep]], np.ascontiguousarray(x[keep]))
-        z_lo[:, keep] = np.where(in_lo[:, keep], z[:, :B].T, z_lo[:, keep])
-        z_hi[:, keep] = np.where(in_hi[:, keep], z[:, B:].T, z_hi[:, keep])
-        if np.any(np.isnan(z_lo)) or np.any(np.isnan(z_hi)):
-            raise ValueError(what + ": a limit has no normal score (a distribution without a positive finite mass?)")
+    finish()
     if observed.size:
         _, _, _, _, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
@@ -943,6 +962,206 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         shift = None
     return copula_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], shift=shift, streams=streams,
                                     first=first, qmc=qmc, return_integrand=return_integrand, device=device)
+
+
+BoxDraws = collections.namedtuple("BoxDraws", "z u weights prob")
+
+
+def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, device=False):
+    """Scenarios of Y = shift + F z GIVEN lower < Y < upper, for B boxes and R seeds through ONE device call
+    (mlmc_copula_box_draws_batch): the conditioned normals of the chain of `copula_box_probabilities` are a sequential importance
+    sample of the truncated normal vector (the GHK sampler).  Every point is a scenario inside the box; its weight is the
+    integrand of the box probability, so sum(weights * g(z)) / sum(weights) estimates E[g(Y) | box] and the mean of the weights
+    is the probability itself.  Everything is in SCORE space (`event_samples` works in the components' own units).  The weights
+    vary least when the components that the box constrains come first in the chain; a box that constrains nothing gives weights
+    exactly 1 and plain joint draws.  A value depends on (factor, box, seed, streams, point index, qmc) alone.
+    :param factor, lower, upper, n, seeds, shift, first, qmc: as in `copula_box_probabilities`
+    :param streams: one stream (qmc: Sobol' dimension below 1024) per coordinate, M of them (the last draws the last component);
+        default: i.  The weights and `prob` are those of `copula_box_probabilities` with the first M - 1 of them, bit for bit
+    :param device: return z, u and the weights as float64 torch device tensors
+    :return: BoxDraws(z [R, B, M, n], u [R, B, M, n], weights [R, B, n], prob): the scores, lower <= z <= upper; u = Phi(z) clamped
+        to [2^-53, 1 - 2^-53] as in `joint_samples`; prob the JointProbability of the event"""
+    what = "copula_box_draws"
+    f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
+    M, B = f.shape[0], lo.shape[0]
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    streams = _box_streams(what, streams, M + 1, qmc)
+    R = seeds.size
+    mean = np.empty((R, B))
+    (z, u, w), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n)])
+    _lib.check(_lib.lib().mlmc_copula_box_draws_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R, _lib.ptr(seeds),
+                                                     _lib.ptr(streams), first, n, _lib.SAMPLE_SOBOL if qmc else 0, _lib.ptr(mean),
+                                                     _lib.ptr(w), _lib.ptr(z), _lib.ptr(u), kind))
+    return BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+
+
+def _event_order(constrained, q):
+    """chain order of q components: the constrained ones first, ascending, then the rest, ascending.  With a constrained component
+    behind an unconstrained one the weights carry the whole conditioning of the earlier draws (a tenth of the effective sample
+    size in the example of DESIGN 3.5.18); in front, one constrained component alone has constant weights"""
+    constrained = np.asarray(constrained, dtype=np.int64)
+    return np.concatenate([constrained, np.setdiff1d(np.arange(q, dtype=np.int64), constrained)])
+
+
+def _event_host(what, arrays):
+    if any(hasattr(a, "data_ptr") for a in arrays):
+        raise ValueError(what + ": the scenarios are device tensors (device=True); copy them to the host first: this package "
+                         "does no arithmetic in torch")
+
+
+class EventScenarios:
+    """What `event_samples` returns.
+    draws [R, B, M, n]: scenarios in the components' own units, all inside the event; weights [R, B, n]: their importance weights;
+    prob: the JointProbability of the event; ess [R, B]: (sum f)^2 / sum f^2, the effective sample size of each seed's n scenarios
+    (NaN where every weight is 0); ok [M]: whether component m has a positive finite mass (false: its draws are NaN);
+    uniforms [R, B, M, n]: the u behind the draws, draws = `quantiles(distrs, uniforms)` bit for bit (rows of given components:
+    Fhat of the given value)."""
+
+    def __init__(self, draws, weights, prob, ess, ok, uniforms):
+        self.draws, self.weights, self.prob, self.ess, self.ok, self.uniforms = draws, weights, prob, ess, ok, uniforms
+
+    def means(self):
+        """(mean [B, M], stderr [B, M]) of E[X_m | event]: per seed the ratio sum f x / sum f, then the mean over the seeds and their
+        sample standard deviation over sqrt(R) (NaN for one seed).  NaN for a box whose weights are all 0 in some seed"""
+        _event_host("EventScenarios.means", (self.draws, self.weights))
+        f = self.weights
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ratio = np.einsum("rbn,rbmn->rbm", f, self.draws) / f.sum(axis=2)[:, :, None]
+            R = ratio.shape[0]
+            stderr = np.std(ratio, axis=0, ddof=1) / np.sqrt(R) if R > 1 else np.full(ratio.shape[1:], np.nan)
+            return ratio.mean(axis=0), stderr
+
+    def weighted_quantiles(self, probs):
+        """[B, M, len(probs)]: the weighted quantiles of every component given the event from the scenarios of all seeds pooled:
+        the smallest draw at which the cumulated normalised weight reaches p.  NaN for a box whose weights are all 0"""
+        _event_host("EventScenarios.weighted_quantiles", (self.draws, self.weights))
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+        R, B, M, n = self.draws.shape
+        out = np.full((B, M, probs.size), np.nan)
+        valid = (probs >= 0) & (probs <= 1)
+        for b in range(B):
+            f = self.weights[:, b, :].reshape(-1)
+            total = f.sum()
+            if not total > 0:
+                continue
+            for m in range(M):
+                x = self.draws[:, b, m, :].reshape(-1)
+                if np.any(np.isnan(x)):
+                    continue
+                order = np.argsort(x, kind="stable")
+                cum = np.cumsum(f[order]) / total
+                at = np.minimum(np.searchsorted(cum, np.where(valid, probs, 0.0), side="left"), x.size - 1)
+                out[b, m] = np.where(valid, x[order][at], np.nan)
+        return out
+
+
+def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True, device=False):
+    """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m for all m, under the marginals and the Gaussian
+    copula of `joint_samples`, for B events and R seeds through `copula_box_draws` and ONE `quantiles` call: what the system
+    looks like when the event of `joint_probabilities` happens.  Every scenario lies in the event and carries a weight; rejection
+    (filtering `joint_samples`) keeps a fraction P of its draws, none at P = 1e-6.  Limits map to scores as in
+    `joint_probabilities`; no component is dropped.  The components are drawn in the order: those that some box of the call
+    constrains, ascending, then the others, ascending (the weights then vary least: `_event_order`), through the Cholesky factor
+    of the correlation permuted so; the results come back in the caller's order.
+    :param lower, upper: broadcast to [B, M] in the components' own units; +-inf, or a value at or beyond an end of the domain,
+        does not constrain that side.  A given component must not be constrained
+    :param corr, factor: as in `joint_probabilities`; exactly one of the two
+    :param given: None, or the mapping of `conditional_samples`: the scenarios are conditional on these values too (the Schur
+        factor, the conditional means as the shift); arrays [B] pair with the boxes (one box pairs with all sets).  The rows of
+        given components hold the given values
+    :param streams: one per chain position (there are M - len(given)); coordinate streams[i] draws the i-th component of the
+        order above
+    :param n, seeds, first, qmc: as in `copula_box_probabilities`
+    :param device: draws, uniforms and weights are float64 torch device tensors; `means` and `weighted_quantiles` then raise
+    :return: EventScenarios"""
+    what = "event_samples"
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    if (corr is None) == (factor is None):
+        raise ValueError(what + ": exactly one of corr and factor must be given")
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    _common_quadrature(what, distrs)
+    if factor is not None:
+        fac = np.asarray(factor, dtype=np.float64)
+        if fac.ndim != 2 or fac.shape[0] != M or fac.shape[1] < 1 or not np.all(np.isfinite(fac)):
+            raise ValueError(what + ": the factor must be a finite [M, K] matrix with M = {} distributions".format(M))
+        corr = fac @ fac.T
+    corr = np.array(corr, dtype=np.float64)
+    if corr.shape != (M, M):
+        raise ValueError(what + ": corr must be [M, M] with M = {} distributions, got shape {}".format(M, corr.shape))
+    if given is not None:
+        observed, values, _ = _parse_given(what, given, M)
+    else:
+        observed, values = np.zeros(0, dtype=np.int64), np.zeros((0, 1))
+    free = np.setdiff1d(np.arange(M, dtype=np.int64), observed)
+    q = free.size
+    lo, hi = _box_limits(what, lower, upper, M)
+    B, Bg = lo.shape[0], values.shape[1]
+    if Bg != 1 and B != 1 and Bg != B:
+        raise ValueError(what + ": the arrays of given hold {} sets, there are {} boxes".format(Bg, B))
+    if B == 1 and Bg > 1:
+        lo, hi = np.repeat(lo, Bg, axis=0), np.repeat(hi, Bg, axis=0)
+        B = Bg
+    if q > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} components exceed the cap of {}".format(q, _lib.BOX_PROB_MAX_M))
+    z_lo, z_hi, keep, finish = _limit_scores(what, distrs, lo, hi)
+    both = np.intersect1d(keep, observed)
+    if both.size:
+        raise ValueError(what + ": component {} is given and constrained by a limit: a given value is the condition, leave its "
+                         "limits at -inf / +inf".format(int(both[0])))
+    streams = _box_streams(what, streams, q + 1, qmc)
+    finish()
+    # the chain: positions within the free components, constrained first
+    perm = _event_order(np.searchsorted(free, keep), q)
+    order = free[perm]                                                                       # chain position -> component
+    if observed.size:
+        _, _, _, u_obs, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
+        cov = fc @ fc.T
+        low = np.linalg.cholesky(0.5 * (cov + cov.T)[np.ix_(perm, perm)])
+        shift = np.ascontiguousarray(np.broadcast_to(mu[:, perm], (B, q)))
+    else:
+        low = correlation_factor(corr[np.ix_(order, order)])[0]
+        u_obs, shift = None, None
+    box = copula_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], shift=shift, streams=streams, first=first,
+                           qmc=qmc, device=device)
+    R = seeds.size
+    # one quantiles call for all components: component order[i] takes the u of chain position i
+    chain = [distrs[m] for m in order]
+    if device:
+        pts = [box.u[:, :, i, :].contiguous() for i in range(q)]
+    else:
+        pts = [np.ascontiguousarray(box.u[:, :, i, :]) for i in range(q)]
+    xs, mass = _on_rule(chain, pts, True, what)
+    ok = np.ones(M, dtype=bool)
+    ok[order] = np.isfinite(mass) & (mass > 0)
+    if device:
+        import torch
+        dev = box.u.device
+        draws, uniforms = box.u.new_empty((R, B, M, n)), box.u.new_empty((R, B, M, n))
+        for i, m in enumerate(order):
+            draws[:, :, int(m), :] = xs[i]
+            uniforms[:, :, int(m), :] = pts[i]
+        if observed.size:
+            vals = np.ascontiguousarray(np.broadcast_to(values.T, (B, observed.size)))
+            uo = np.ascontiguousarray(np.broadcast_to(u_obs.T, (B, observed.size)))
+            draws[:, :, observed.tolist(), :] = torch.from_numpy(vals).to(dev)[None, :, :, None]
+            uniforms[:, :, observed.tolist(), :] = torch.from_numpy(uo).to(dev)[None, :, :, None]
+        torch.cuda.current_stream(dev).synchronize()
+        f = box.weights.cpu().numpy()
+    else:
+        draws, uniforms = np.empty((R, B, M, n)), np.empty((R, B, M, n))
+        for i, m in enumerate(order):
+            draws[:, :, m, :] = xs[i]
+            uniforms[:, :, m, :] = pts[i]
+        if observed.size:
+            draws[:, :, observed, :] = np.broadcast_to(values.T, (B, observed.size))[None, :, :, None]
+            uniforms[:, :, observed, :] = np.broadcast_to(u_obs.T, (B, observed.size))[None, :, :, None]
+        f = box.weights
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ess = f.sum(axis=2) ** 2 / (f * f).sum(axis=2)
+    return EventScenarios(draws, box.weights, box.prob, ess, ok, uniforms)
 
 
 def _scores_problem_args(distrs, what):

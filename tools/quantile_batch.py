@@ -88,9 +88,15 @@ one-dimensional quadrature), M = 2 / 12 / 64, B = 1 / 64, n = 2^12 .. 2^20 (--co
   call_ms, rel_rms             wall time of the call and the RMS over the seeds of a seed's relative error
   count_ms_per_seed, count_rel_rms, count_zero_seeds   the counting route at the same n: joint_samples(device=True), the comparison
                                of the copula uniforms with Phi(t) and the mean in torch, one call per seed
+--boxdraws: event_samples(device=True) of the event "components 0 and 1 exceed their 0.9-quantile" (for
+M = 12 also their 0.999-quantile) under equicorrelation 1/2 with 8 seeds per call, M = 2 / 12 / 64, n = 2^12 .. 2^20 (--config M,n:
+one shape), next to rejection: joint_samples(device=True) of the same n per seed and a filter in torch:
+  call_ms, inside_per_ms, ess_fraction, event_mean, event_stderr   wall time of the call up to a device synchronise, its R n scenarios
+                               per ms, ess / n, and the conditional mean of component 2 (M = 2: 0) with the seeds' standard error
+  reject_ms_per_seed, reject_inside_per_ms, reject_mean, reject_stderr, reject_zero_seeds   the same for what the filter keeps
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --scores |
-                                                              --conditional | --qmc | --boxprob] [--reps K]"""
+                                                              --conditional | --qmc | --boxprob | --boxdraws] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -609,6 +615,49 @@ def boxprob_shape(M, B, n, reps, t, seeds=tuple(range(1, 9))):
                 count_zero_seeds=int(np.sum(counted == 0.0)))
 
 
+def boxdraws_shape(M, n, reps, p, seeds=tuple(range(1, 9))):
+    """event_samples(device=True) of the event "components 0 and 1 exceed their p-quantile" for M mixture marginals under
+    equicorrelation 1/2, R = 8 seeds in one call, next to rejection: joint_samples(device=True) of the same n per seed and a filter
+    in torch.  For both routes the scenarios inside the event per millisecond (all R n of the call; what the filter keeps) and the
+    standard error over the seeds of the conditional mean of component 2 (of component 0 for M = 2)."""
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    distrs, _ = mixtures(M, 9, seed=5)
+    factor = sd.correlation_factor(corr)[0]
+    t = np.array([sd.quantiles([distrs[m]], [np.array([p])])[0][0] for m in (0, 1)])
+    lower = np.full(M, -np.inf)
+    lower[:2] = t
+    comp = 2 if M > 2 else 0
+    R = len(seeds)
+
+    def event():
+        ev = sd.event_samples(distrs, lower, np.inf, n, seeds, factor=factor, device=True)
+        torch.cuda.synchronize()
+        return ev
+    ms, ev = timed(event, reps)
+    f, x = ev.weights[:, 0], ev.draws[:, 0, comp]
+    ratio = ((f * x).sum(dim=1) / f.sum(dim=1)).cpu().numpy()
+    prob, ess = float(ev.prob.prob[0]), float(np.mean(ev.ess)) / n
+    del ev, f, x
+
+    def reject(seed):
+        x = sd.joint_samples(distrs, n, seed, factor=factor, device=True)
+        inside = (x[0] > t[0]) & (x[1] > t[1])
+        kept = int(inside.sum())
+        return kept, float(x[comp][inside].mean()) if kept else float("nan")
+    rej_ms, _ = timed(lambda: reject(seeds[0]), reps)
+    rejected = [reject(s) for s in seeds]
+    kept = np.array([k for k, _ in rejected], dtype=np.float64)
+    means = np.array([m for _, m in rejected])
+    return dict(M=M, n=n, R=R, quantile=p, prob=float("%.6g" % prob),
+                call_ms=round(ms, 3), inside_per_ms=float("%.4g" % (R * n / ms)), ess_fraction=float("%.3g" % ess),
+                event_mean=float("%.8g" % ratio.mean()), event_stderr=float("%.3g" % (np.std(ratio, ddof=1) / np.sqrt(R))),
+                reject_ms_per_seed=round(rej_ms, 3), reject_inside_per_ms=float("%.4g" % (kept.mean() / rej_ms)),
+                reject_mean=float("%.8g" % np.nanmean(means)) if np.any(kept > 0) else None,
+                reject_stderr=float("%.3g" % (np.nanstd(means, ddof=1) / np.sqrt(np.sum(kept > 0)))) if np.sum(kept > 0) > 1 else None,
+                reject_zero_seeds=int(np.sum(kept == 0)))
+
+
 def scores_shape(M, R1, n, reps, levels=0):
     """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
     device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
@@ -713,12 +762,21 @@ def main():
                                                        "error of two integrals against n (DESIGN.md section 3.5.16)")
     ap.add_argument("--boxprob", action="store_true", help="copula_box_probabilities against closed forms, next to counting the "
                                                            "scenarios of joint_samples (DESIGN.md section 3.5.17)")
+    ap.add_argument("--boxdraws", action="store_true", help="event_samples against rejection from joint_samples (DESIGN.md section 3.5.18)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.boxdraws:
+        shapes = [(M, 2 ** k, 0.9) for M in (2, 12, 64) for k in (12, 16, 20)] + [(12, 2 ** k, 0.999) for k in (12, 16, 20)]
+        if a.config:
+            M, n = (int(v) for v in a.config.split(","))
+            shapes = [(M, n, 0.9)]
+        elif a.quick:
+            shapes = [(2, 2 ** 12, 0.9), (12, 2 ** 12, 0.999)]
+        out["boxdraws"] = [boxdraws_shape(M, n, a.reps, p) for M, n, p in shapes]
     elif a.boxprob:
         # the orthant under equicorrelation 1/2, and for M = 12 the threshold at which all twelve exceed it with probability 1e-6
         t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
