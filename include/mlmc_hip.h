@@ -42,7 +42,8 @@ extern "C" {
                               *    mlmc_density_tail_means_batch, mlmc_density_divergences_batch, mlmc_density_moments_batch,
                               *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
-                              *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch */
+                              *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch,
+                              *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -783,6 +784,24 @@ int mlmc_bootstrap_create_multi(int32_t M, const mlmc_basis *const *bases, int32
  * NaN or an out-of-domain value of component m drops the sample for component m alone.  The counts are exact.  Refuses a handle
  * of mlmc_bootstrap_create.  The totals stay (reset to start over). */
 int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *bs, int64_t *n_out, double *s_out, double *sp_out);
+/* Component covariance of the bootstrap replicates -- added within 8.  A handle for the M components of a vector quantity
+ * (M in 1 .. 1024, no basis): per replicate b and level l, with the weights w_b of mlmc_bootstrap_weights, a shift a [M] and
+ * f~ = f - a, c~ = c - a (both rounded to fp64),
+ *     n = sum_i w_bi keep_i,   s1[m] = sum_i w_bi keep_i (f~_im - c~_im),   s2[i][j] = sum_i w_bi keep_i (f~_i f~_j - c~_i c~_j)
+ * (level 0 / coarse NULL: f~_im and f~_i f~_j), keep_i = 0 when any of the sample's M fine or M coarse values is NaN: the rule of
+ * mlmc_xcov_create, the sample is dropped from the whole matrix and contributes exact zeros.  No sums of squares: the replicates
+ * are the error estimate.  Device state: the totals [n_levels][B][1 + M + M (M + 1) / 2] doubles (refused above 2 GiB) and the
+ * 64 MiB of scratch; the columns run in groups of at most 2048.  mlmc_bootstrap_accum / _reset / _destroy / _kernel_time serve
+ * the handle unchanged (fine / coarse: DEVICE [M][n]); mlmc_bootstrap_finalize and mlmc_bootstrap_finalize_multi refuse it.
+ * Deterministic: runs are bit-identical and a replicate's sums do not depend on B. */
+int mlmc_bootstrap_create_xcov(int32_t M, int32_t n_levels, int64_t B, mlmc_bootstrap **out);
+/* The shift a (host, M finite doubles; NULL: zeros) of a handle of mlmc_bootstrap_create_xcov.  It takes effect at the next
+ * mlmc_bootstrap_reset; an error while chunks have been accumulated since the last reset (the rule of mlmc_xcov_set_shift). */
+int mlmc_bootstrap_set_shift(mlmc_bootstrap *bs, const double *shift_host);
+/* Wait for the stream and write (host) n_out [B][n_levels], s1_out [B][n_levels][M], s2_out [B][n_levels][M * M] (row i * M + j,
+ * bitwise symmetric: one computed value goes to (i, j) and (j, i)).  The counts are exact.  Refuses the handles of
+ * mlmc_bootstrap_create and mlmc_bootstrap_create_multi.  The totals stay (reset to start over). */
+int mlmc_bootstrap_finalize_xcov(mlmc_bootstrap *bs, int64_t *n_out, double *s1_out, double *s2_out);
 
 /* ---- synthetic samples in HBM (mlmc/sim/synth_simulation.py:37-46,75-131; seeding mlmc/sampling_pool.py:75-84; sample
  * ids mlmc/sampler.py:120) -------------------------------------------------------------------------------------------

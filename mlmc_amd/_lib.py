@@ -134,6 +134,9 @@ SIGNATURES = {
     "mlmc_bootstrap_kernel_time": (C.c_int, [_vp, _dp, _dp, _ip]),
     "mlmc_bootstrap_create_multi": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_vp)]),
     "mlmc_bootstrap_finalize_multi": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mlmc_bootstrap_create_xcov": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(_vp)]),
+    "mlmc_bootstrap_set_shift": (C.c_int, [_vp, _vp]),
+    "mlmc_bootstrap_finalize_xcov": (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 _lock = threading.Lock()

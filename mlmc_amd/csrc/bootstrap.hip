@@ -26,6 +26,12 @@
 // Per-component route (mlmc_bootstrap_create_multi, Estimate.est_bootstrap_components): one basis and one mask per component, the
 // same weights, the same plan, the same k_bs_contract and k_bs_reduce under another column layout (BsPerComponent instead of
 // BsSharedBasis below), keep bytes from k_bs_keep_multi, components in groups of at most 2048 columns.
+//
+// Component covariance of the replicates (mlmc_bootstrap_create_xcov, Estimate.est_bootstrap_component_covariance): no basis; the
+// columns are the keep flag, the M shifted first moments f~_m - c~_m and the M (M + 1) / 2 upper-triangle products
+// f~_i f~_j - c~_i c~_j (f~ = f - a, c~ = c - a).  The same weights, plan, replicate groups and sample ranges; a contraction of its
+// own (k_bs_xcov_contract: all 256 threads fill Phi, one MFMA per 16-column tile and k-step) and its fixed-order reduction
+// (k_bs_xcov_reduce), columns in groups of at most 2048.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -403,7 +409,16 @@ struct mlmc_bootstrap {
     std::vector<const mlmc_basis *> bases;
     mlmc::BasisParams *d_tab = nullptr;   // [M]
     uint8_t *d_keep_m = nullptr;          // [M][keep_tiles * BS_TILE]
-    size_t tot_bytes() const { return sizeof(double) * (size_t)L * (size_t)B * (multi ? (size_t)M * (2 * (size_t)R + 1) : 2 * (size_t)MR); }
+    // component-covariance handle (mlmc_bootstrap_create_xcov): no basis, totals [L][B][C], C = 1 + M + M (M + 1) / 2, no d_cnt
+    bool xcov = false;
+    int64_t C = 0;
+    double *d_shift = nullptr;            // [M]: uploaded by reset from shift_host (mlmc_bootstrap_set_shift)
+    std::vector<double> shift_host;
+    int64_t pushes = 0;                   // chunks accumulated since the last reset
+    size_t tot_bytes() const {
+        if (xcov) return sizeof(double) * (size_t)L * (size_t)B * (size_t)C;
+        return sizeof(double) * (size_t)L * (size_t)B * (multi ? (size_t)M * (2 * (size_t)R + 1) : 2 * (size_t)MR);
+    }
 };
 
 namespace mlmc {
@@ -515,9 +530,41 @@ static BsPlan bs_plan(int64_t n, int64_t B, int64_t cols, int64_t keep_tiles) {
     return BsPlan{JT, tpr * BS_TILE, ny * BS_REPS};
 }
 
-// One chunk (mlmc_bootstrap_accum has checked the arguments; ds: the device view of the pinned sizes).  Per (replicate group,
-// sample range): the weight slab and the keep bytes once, then per component group the contraction and its fixed-order reduction.
-// The shared-basis handle has one group of all M components.
+// The walk over one chunk that every kind of handle shares (ds: the device view of the pinned sizes): replicates in groups of
+// p.BG, samples in ranges of p.nr; per group pass A, per (group, range) pass B into the weight slab and then
+// contract(g, ng, i0, len) -- the keep bytes, the contractions and their reductions -- between the contraction's timing events.
+template <class F>
+static int bs_walk(mlmc_bootstrap *a, int64_t n, const BsPlan &p, const int64_t *sizes, const int64_t *ds, uint64_t seed, uint32_t stream,
+                   F contract) {
+    const int64_t B = a->B, nr = p.nr, BG = p.BG;
+    for (int64_t g = 0; g < B; g += BG) {
+        const int64_t ng = std::min(BG, B - g);
+        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
+        if (int rc = bs_time(a, 0, false)) return rc;
+        if (int rc = launch_tile_counts(n, ng, ds + g, mx, g, seed, stream, a->sc.counts)) return rc;
+        if (int rc = bs_time(a, 0, true)) return rc;
+        for (int64_t i0 = 0; i0 < n; i0 += nr) {
+            const int64_t len = std::min(nr, n - i0);
+            if (int rc = bs_time(a, 0, false)) return rc;
+            if (int rc = launch_expand(n, ng, i0 / BS_TILE, cdiv(len, BS_TILE), a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
+            if (int rc = bs_time(a, 0, true)) return rc;
+            if (int rc = bs_time(a, 1, false)) return rc;
+            if (int rc = contract(g, ng, i0, len)) return rc;
+            if (int rc = bs_time(a, 1, true)) return rc;
+        }
+    }
+    return 0;
+}
+
+// MFMA batches of BS_KB samples that the workgroups of one replicate tile and column block run over a range of len samples
+static int64_t bs_batches(int64_t len) {
+    const int64_t nx = cdiv(len, BS_SW);
+    return (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
+}
+
+// One chunk of a moments handle (mlmc_bootstrap_accum has checked the arguments).  Per (replicate group, sample range): the keep
+// bytes once, then per component group the contraction and its fixed-order reduction.  The shared-basis handle has one group of
+// all M components.
 static int bs_accum(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n, const int64_t *sizes,
                     const int64_t *ds, uint64_t seed, uint32_t stream) {
     const int64_t B = a->B, M = a->M, R = a->R;
@@ -525,52 +572,233 @@ static int bs_accum(mlmc_bootstrap *a, int32_t level, const double *fine, const 
     const int64_t mg = a->multi ? bs_group_comps(M, R) : M;
     const BsPlan p = bs_plan(n, B, mg * cw, a->keep_tiles);
     const int JT = p.JT, JB = 16 * JT;
-    const int64_t nr = p.nr, BG = p.BG;
+    const int64_t nr = p.nr;
     const int64_t ldk = a->keep_tiles * BS_TILE;
     const int64_t ld_tot = a->multi ? M * (2 * R + 1) : 2 * M * R;
     const BasisParams bp = a->basis->p;
     double *tot = a->d_tot + (size_t)level * B * ld_tot;
-    for (int64_t g = 0; g < B; g += BG) {
-        const int64_t ng = std::min(BG, B - g);
-        const int64_t nyg = cdiv(ng, BS_REPS);
-        const int64_t mx = *std::max_element(sizes + g, sizes + g + ng);
-        if (int rc = bs_time(a, 0, false)) return rc;
-        if (int rc = launch_tile_counts(n, ng, ds + g, mx, g, seed, stream, a->sc.counts)) return rc;
-        if (int rc = bs_time(a, 0, true)) return rc;
-        for (int64_t i0 = 0; i0 < n; i0 += nr) {
-            const int64_t len = std::min(nr, n - i0);
-            const int64_t nt = cdiv(len, BS_TILE), nx = cdiv(len, BS_SW);
-            if (int rc = bs_time(a, 0, false)) return rc;
-            if (int rc = launch_expand(n, ng, i0 / BS_TILE, nt, a->sc.counts, g, seed, stream, a->sc.w, nr, i0)) return rc;
-            if (int rc = bs_time(a, 0, true)) return rc;
-            if (int rc = bs_time(a, 1, false)) return rc;
-            if (a->multi)
-                hipLaunchKernelGGL(k_bs_keep_multi, dim3((unsigned)cdiv(len, 256), (unsigned)M), dim3(256), 0, rt().stream, a->d_tab, fine,
-                                   coarse, n, (int)M, i0, len, ldk, a->d_keep_m);
-            else
-                hipLaunchKernelGGL(k_bs_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, bp, fine, coarse, n, (int)M, i0,
-                                   len, a->sc.keep);
-            MLMC_HIP_CHECK(hipGetLastError());
+    return bs_walk(a, n, p, sizes, ds, seed, stream, [&](int64_t g, int64_t ng, int64_t i0, int64_t len) -> int {
+        const int64_t nyg = cdiv(ng, BS_REPS), nx = cdiv(len, BS_SW);
+        if (a->multi)
+            hipLaunchKernelGGL(k_bs_keep_multi, dim3((unsigned)cdiv(len, 256), (unsigned)M), dim3(256), 0, rt().stream, a->d_tab, fine,
+                               coarse, n, (int)M, i0, len, ldk, a->d_keep_m);
+        else
+            hipLaunchKernelGGL(k_bs_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, bp, fine, coarse, n, (int)M, i0,
+                               len, a->sc.keep);
+        MLMC_HIP_CHECK(hipGetLastError());
+        for (int64_t m0 = 0; m0 < M; m0 += mg) {
+            const int64_t mc = std::min(mg, M - m0);
+            const int cols = (int)(mc * cw);
+            const int64_t ncb = cdiv(cols, JB);
+            const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
+            const double *f = fine + m0 * n, *c = coarse ? coarse + m0 * n : nullptr;
+            const int rc = a->multi
+                ? bs_contract_reduce(BsPerComponent{a->d_tab + m0, a->d_keep_m + m0 * ldk, ldk, (int)R, cols, tot + m0 * (2 * R + 1), ld_tot},
+                                     bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng)
+                : bs_contract_reduce(BsSharedBasis{bp, a->sc.keep, (int)R, cols, a->sc.pcnt, tot, a->d_cnt + (size_t)level * B},
+                                     bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng);
+            if (rc) return rc;
             // executed matrix-core flops: every batch of every workgroup runs KB / 4 k-steps of 2 JT MFMAs per wave
-            const int64_t batches = (nx - 1) * (BS_SW / BS_KB) + cdiv(len - (nx - 1) * BS_SW, BS_KB);
-            for (int64_t m0 = 0; m0 < M; m0 += mg) {
-                const int64_t mc = std::min(mg, M - m0);
-                const int cols = (int)(mc * cw);
-                const int64_t ncb = cdiv(cols, JB);
-                const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
-                const double *f = fine + m0 * n, *c = coarse ? coarse + m0 * n : nullptr;
-                const int rc = a->multi
-                    ? bs_contract_reduce(BsPerComponent{a->d_tab + m0, a->d_keep_m + m0 * ldk, ldk, (int)R, cols, tot + m0 * (2 * R + 1), ld_tot},
-                                         bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng)
-                    : bs_contract_reduce(BsSharedBasis{bp, a->sc.keep, (int)R, cols, a->sc.pcnt, tot, a->d_cnt + (size_t)level * B},
-                                         bp.kind, JT, grid, f, c, n, (int)mc, i0, len, a->sc, nr, g, (int)ng);
-                if (rc) return rc;
-                a->flops += batches * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
-            }
-            if (int rc = bs_time(a, 1, true)) return rc;
+            a->flops += bs_batches(len) * nyg * ncb * 4 * (BS_KB / 4) * 2 * JT * (int64_t)(16 * 16 * 4 * 2);
         }
+        return 0;
+    });
+}
+
+// ---- component covariance of the replicates (mlmc_bootstrap_create_xcov) -------------------------------------------------------
+// Columns of a replicate's row of totals: 0 = the kept count (a flag column, exact as in BsPerComponent), 1 + m = the first
+// moment of component m, 1 + M + p = product pair p = (i, j), i <= j, row-major over the upper triangle (row i starts at
+// i M - i (i - 1) / 2).
+constexpr int BSX_MAX_M = 1024;
+
+static int64_t bsx_cols(int64_t M) { return 1 + M + M * (M + 1) / 2; }
+
+// column -> (ci, cj): (-1, -1) the flag, (m, -1) a first moment, (i, j) a product pair, (-2, -2) past the last column
+__device__ __forceinline__ void bsx_column(int64_t col, int M, int64_t C, int &ci, int &cj) {
+    if (col >= C) { ci = cj = -2; return; }
+    if (col == 0) { ci = cj = -1; return; }
+    if (col <= M) { ci = (int)col - 1; cj = -1; return; }
+    const int64_t p = col - 1 - M;
+    const double h = 2.0 * M + 1.0;
+    int i = (int)((h - sqrt(h * h - 8.0 * (double)p)) * 0.5);          // a guess; the two loops make it exact
+    i = std::max(0, std::min(i, M - 1));
+    while (i > 0 && (int64_t)i * M - (int64_t)i * (i - 1) / 2 > p) --i;
+    while (i + 1 < M && (int64_t)(i + 1) * M - (int64_t)(i + 1) * i / 2 <= p) ++i;
+    ci = i;
+    cj = i + (int)(p - ((int64_t)i * M - (int64_t)i * (i - 1) / 2));
+}
+
+// keep byte of samples i0 .. i0 + nr - 1: no NaN among the M fine and M coarse values (the rule of k_xcov_mask)
+__global__ __launch_bounds__(256) void k_bs_xcov_keep(const double *__restrict__ f, const double *__restrict__ c, int64_t n, int M,
+                                                      int64_t i0, int64_t nr, uint8_t *__restrict__ keep) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
+        bool k = true;
+        for (int m = 0; m < M; ++m) {
+            const double v = f[(int64_t)m * n + i0 + i];
+            k = k && !(v != v);
+            if (c) {
+                const double u = c[(int64_t)m * n + i0 + i];
+                k = k && !(u != u);
+            }
+        }
+        keep[i] = k ? 1 : 0;
     }
-    return 0;
+}
+
+// The contraction of the columns col0 + blockIdx.z * JB .. of one (replicate group, sample range): grid as k_bs_contract (slices of
+// BS_SW samples, 64-replicate tiles, column blocks of JB = 16 JT).  Per batch of BS_KB samples: the weights [64][KB] -> LDS; Phi
+// [JB][KB] -> LDS, every element one flag, one shifted difference or one product pair, its factors read from global memory (a
+// wave owns one column per trip, its 64 lanes the 64 samples: coalesced along the samples), the shift subtracted and a dropped
+// sample written as 0.0; then each wave runs KB / 4 k-steps of JT MFMAs for its 16 replicates.  Partial rows: [64][JB] per
+// workgroup.
+template <bool PAIR, int JT>
+__global__ __launch_bounds__(256) void k_bs_xcov_contract(const double *__restrict__ fine, const double *__restrict__ coarse,
+                                                          const double *__restrict__ shift, const uint8_t *__restrict__ keep, int64_t n,
+                                                          int M, int64_t C, int64_t col0, int64_t i0, int64_t nr,
+                                                          const int32_t *__restrict__ W, int64_t ldw, int reps,
+                                                          double *__restrict__ partials) {
+    constexpr int JB = 16 * JT;
+    constexpr int KB = BS_KB;
+    constexpr int WS = KB + 4;                       // as k_bs_contract
+    constexpr int KS = KB + 2;                       // == 2 (mod 32): the fragment reads hit distinct bank pairs (xcov.hip)
+    __shared__ int32_t wl[BS_REPS * WS];
+    __shared__ double ph[JB * KS];
+    __shared__ int cpi[JB], cpj[JB];
+    __shared__ double sai[JB], saj[JB];              // the shifts of the column's two components
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int y0 = blockIdx.y * BS_REPS;
+    const int64_t s_begin = (int64_t)blockIdx.x * BS_SW, s_end = std::min(nr, s_begin + BS_SW);
+    if (threadIdx.x < JB) {
+        int ci, cj;
+        bsx_column(col0 + (int64_t)blockIdx.z * JB + threadIdx.x, M, C, ci, cj);
+        cpi[threadIdx.x] = ci;
+        cpj[threadIdx.x] = cj;
+        sai[threadIdx.x] = ci >= 0 ? shift[ci] : 0.0;
+        saj[threadIdx.x] = cj >= 0 ? shift[cj] : 0.0;
+    }
+    __syncthreads();
+
+    v4f64 acc[JT];
+#pragma unroll
+    for (int J = 0; J < JT; ++J) acc[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    for (int64_t s0 = s_begin; s0 < s_end; s0 += KB) {
+        const int kb = (int)std::min((int64_t)KB, s_end - s0);
+        for (int e = threadIdx.x; e < BS_REPS * KB; e += 256) {
+            const int r = e / KB, k = e % KB;
+            wl[r * WS + k] = (y0 + r < reps && k < kb) ? W[(int64_t)(y0 + r) * ldw + s0 + k] : 0;
+        }
+        {
+            // Every load is unconditional (a flag or first-moment column reads component 0 in place of the factor it does not
+            // have, a lane past the batch reads the batch's first sample) and NH elements' loads are issued before the first use:
+            // behind a branch they would wait for each other, one memory latency per element.
+            constexpr int NE = JB / 4, NH = NE < 8 ? NE : 8;             // elements per thread and batch; ... loaded together
+            const bool kept = lane < kb && keep[s0 + lane] != 0;
+            const int64_t at = i0 + s0 + (lane < kb ? lane : 0);         // < n
+#pragma unroll
+            for (int h = 0; h < NE; h += NH) {
+                double fi[NH], fj[NH], gi[NH], gj[NH];
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const int jj = wave + 4 * (h + t);
+                    const int64_t oi = (int64_t)std::max(cpi[jj], 0) * n + at, oj = (int64_t)std::max(cpj[jj], 0) * n + at;
+                    fi[t] = fine[oi];
+                    fj[t] = fine[oj];
+                    gi[t] = PAIR ? coarse[oi] : 0.0;
+                    gj[t] = PAIR ? coarse[oj] : 0.0;
+                }
+#pragma unroll
+                for (int t = 0; t < NH; ++t) {
+                    const int jj = wave + 4 * (h + t);
+                    const int ci = cpi[jj], cj = cpj[jj];
+                    const double ai = sai[jj], aj = saj[jj];
+                    const double xi = fi[t] - ai, yi = gi[t] - ai;
+                    double v;
+                    if (cj >= 0) {
+                        v = xi * (fj[t] - aj);
+                        if (PAIR) v -= yi * (gj[t] - aj);
+                    } else {
+                        v = PAIR ? xi - yi : xi;
+                    }
+                    if (ci == -1) v = 1.0;
+                    ph[jj * KS + lane] = (kept && ci != -2) ? v : 0.0;   // a dropped sample: 0.0, never a product with a NaN
+                }
+            }
+        }
+        __syncthreads();
+        const int arow = (16 * wave + (lane & 15)) * WS;
+#pragma unroll 4
+        for (int kk = 0; kk < KB / 4; ++kk) {
+            const int k = 4 * kk + (lane >> 4);
+            const double a = (double)wl[arow + k];
+#pragma unroll
+            for (int J = 0; J < JT; ++J)
+                acc[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ph[(16 * J + (lane & 15)) * KS + k], acc[J], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // f64 MFMA C/D layout: register r of lane l holds (row l / 16 + 4 r, column l % 16) of the tile
+    double *__restrict__ prow = partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (BS_REPS * JB);
+#pragma unroll
+    for (int J = 0; J < JT; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) prow[(16 * wave + (lane >> 4) + 4 * r) * JB + 16 * J + (lane & 15)] = acc[J][r];
+}
+
+// Level totals [B][C] += the partial rows of one k_bs_xcov_contract launch, summed over the slices in a fixed order.
+// grid (ceil(64 JB / 256), 64-replicate tiles, column blocks)
+__global__ __launch_bounds__(256) void k_bs_xcov_reduce(const double *__restrict__ partials, int nx, int JB, int64_t C, int64_t col0,
+                                                        int64_t b_first, int reps, double *__restrict__ tot) {
+    const int row = BS_REPS * JB;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= row) return;
+    const int b = blockIdx.y * BS_REPS + e / JB;
+    const int64_t col = col0 + (int64_t)blockIdx.z * JB + e % JB;
+    if (b >= reps || col >= C) return;
+    const double *__restrict__ p = partials + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * nx * row + e;
+    double s = 0.0;
+    for (int x = 0; x < nx; ++x) s += p[(int64_t)x * row];
+    tot[(b_first + b) * C + col] += s;
+}
+
+using BsXcovFn = void (*)(const double *, const double *, const double *, const uint8_t *, int64_t, int, int64_t, int64_t, int64_t,
+                          int64_t, const int32_t *, int64_t, int, double *);
+
+static BsXcovFn bs_xcov_kernel(bool pair, int JT) {
+    static const BsXcovFn fn[2][3] = {{k_bs_xcov_contract<false, 1>, k_bs_xcov_contract<false, 2>, k_bs_xcov_contract<false, 4>},
+                                      {k_bs_xcov_contract<true, 1>, k_bs_xcov_contract<true, 2>, k_bs_xcov_contract<true, 4>}};
+    return fn[pair][JT / 2];
+}
+
+// One chunk of a component-covariance handle: the walk of bs_accum; per (group, range) the keep bytes once, then per group of at
+// most BS_MAX_COLS columns the contraction and its reduction.
+static int bs_accum_xcov(mlmc_bootstrap *a, int32_t level, const double *fine, const double *coarse, int64_t n, const int64_t *sizes,
+                         const int64_t *ds, uint64_t seed, uint32_t stream) {
+    const int64_t B = a->B, M = a->M, C = a->C;
+    const BsPlan p = bs_plan(n, B, std::min<int64_t>(C, BS_MAX_COLS), a->keep_tiles);
+    const int JT = p.JT, JB = 16 * JT;
+    const int64_t nr = p.nr;
+    double *tot = a->d_tot + (size_t)level * B * C;
+    const BsXcovFn kernel = bs_xcov_kernel(coarse != nullptr, JT);
+    return bs_walk(a, n, p, sizes, ds, seed, stream, [&](int64_t g, int64_t ng, int64_t i0, int64_t len) -> int {
+        const int64_t nyg = cdiv(ng, BS_REPS), nx = cdiv(len, BS_SW);
+        hipLaunchKernelGGL(k_bs_xcov_keep, dim3((unsigned)cdiv(len, 256)), dim3(256), 0, rt().stream, fine, coarse, n, (int)M, i0, len,
+                           a->sc.keep);
+        MLMC_HIP_CHECK(hipGetLastError());
+        for (int64_t c0 = 0; c0 < C; c0 += BS_MAX_COLS) {
+            const int64_t ncb = cdiv(std::min<int64_t>(BS_MAX_COLS, C - c0), JB);
+            const dim3 grid((unsigned)nx, (unsigned)nyg, (unsigned)ncb);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, rt().stream, fine, coarse, a->d_shift, a->sc.keep, n, (int)M, C, c0, i0, len,
+                               a->sc.w, nr, (int)ng, a->sc.part);
+            MLMC_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_bs_xcov_reduce, dim3((unsigned)cdiv(BS_REPS * JB, 256), grid.y, grid.z), dim3(256), 0, rt().stream,
+                               a->sc.part, (int)nx, JB, C, c0, g, (int)ng, tot);
+            MLMC_HIP_CHECK(hipGetLastError());
+            // executed matrix-core flops: every batch of every workgroup runs KB / 4 k-steps of JT MFMAs per wave
+            a->flops += bs_batches(len) * nyg * ncb * 4 * (BS_KB / 4) * JT * (int64_t)(16 * 16 * 4 * 2);
+        }
+        return 0;
+    });
 }
 
 // what both create functions check first (e: the entry point's name)
@@ -666,6 +894,7 @@ extern "C" void mlmc_bootstrap_destroy(mlmc_bootstrap *a) {
     if (a->d_cnt) (void)hipFree(a->d_cnt);
     if (a->d_tab) (void)hipFree(a->d_tab);
     if (a->d_keep_m) (void)hipFree(a->d_keep_m);
+    if (a->d_shift) (void)hipFree(a->d_shift);
     bs_scratch_free(a->sc);
     for (int64_t *p : a->h_sizes) (void)hipHostFree(p);
     for (hipEvent_t e : a->ev) (void)hipEventDestroy(e);
@@ -681,6 +910,10 @@ extern "C" int mlmc_bootstrap_reset(mlmc_bootstrap *a) {
     a->ev_used = 0;
     MLMC_HIP_CHECK(hipMemsetAsync(a->d_tot, 0, a->tot_bytes(), rt().stream));
     if (a->d_cnt) MLMC_HIP_CHECK(hipMemsetAsync(a->d_cnt, 0, sizeof(int64_t) * (size_t)a->L * (size_t)a->B, rt().stream));
+    if (a->xcov)            // the shift set since the previous reset takes effect now (mlmc_bootstrap_set_shift)
+        MLMC_HIP_CHECK(hipMemcpyAsync(a->d_shift, a->shift_host.data(), sizeof(double) * a->shift_host.size(), hipMemcpyHostToDevice,
+                                      rt().stream));
+    a->pushes = 0;
     return 0;
 }
 
@@ -707,6 +940,8 @@ extern "C" int mlmc_bootstrap_accum(mlmc_bootstrap *a, int32_t level, const doub
     std::memcpy(hs, sizes, sizeof(int64_t) * (size_t)B);
     int64_t *ds = nullptr;
     MLMC_HIP_CHECK(hipHostGetDevicePointer((void **)&ds, hs, 0));
+    a->pushes += 1;
+    if (a->xcov) return bs_accum_xcov(a, level, fine, coarse, n, sizes, ds, seed, stream);
     return bs_accum(a, level, fine, coarse, n, sizes, ds, seed, stream);
 }
 
@@ -715,6 +950,7 @@ extern "C" int mlmc_bootstrap_finalize(mlmc_bootstrap *a, int64_t *n_out, double
     using namespace mlmc;
     if (!a) return fail("mlmc_bootstrap_finalize: null handle");
     if (a->multi) return fail("mlmc_bootstrap_finalize: the handle comes from mlmc_bootstrap_create_multi (use mlmc_bootstrap_finalize_multi)");
+    if (a->xcov) return fail("mlmc_bootstrap_finalize: the handle comes from mlmc_bootstrap_create_xcov (use mlmc_bootstrap_finalize_xcov)");
     if (!n_out || !s_out || !sp_out) return fail("mlmc_bootstrap_finalize: null argument (n_out, s_out, sp_out)");
     const int64_t L = a->L, B = a->B, MR = a->MR;
     std::vector<double> tot((size_t)L * B * 2 * MR);
@@ -799,6 +1035,7 @@ extern "C" int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *a, int64_t *n_out, 
     MLMC_API_GUARD;
     using namespace mlmc;
     if (!a) return fail("mlmc_bootstrap_finalize_multi: null handle");
+    if (a->xcov) return fail("mlmc_bootstrap_finalize_multi: the handle comes from mlmc_bootstrap_create_xcov (use mlmc_bootstrap_finalize_xcov)");
     if (!a->multi) return fail("mlmc_bootstrap_finalize_multi: the handle comes from mlmc_bootstrap_create (use mlmc_bootstrap_finalize)");
     if (!n_out || !s_out || !sp_out) return fail("mlmc_bootstrap_finalize_multi: null argument (n_out, s_out, sp_out)");
     const int64_t L = a->L, B = a->B, M = a->M, K = a->R, C = 2 * K + 1;
@@ -819,6 +1056,92 @@ extern "C" int mlmc_bootstrap_finalize_multi(mlmc_bootstrap *a, int64_t *n_out, 
                     sp_out[o * K + k] = (c[k] * c[k]) * t[K + k];
                 }
             }
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_create_xcov(int32_t M, int32_t n_levels, int64_t B, mlmc_bootstrap **out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    const std::string e("mlmc_bootstrap_create_xcov");
+    if (int rc = bs_create_check(e, n_levels, B)) return rc;
+    if (!out) return fail(e + ": null argument (out)");
+    if (M < 1 || M > BSX_MAX_M) return fail(e + ": M = " + std::to_string(M) + " (must be in 1 .. " + std::to_string(BSX_MAX_M) + ")");
+    const int64_t C = bsx_cols(M);
+    // [n_levels][B][C] doubles; every factor is small enough for the product to stay inside 64 bits
+    const uint64_t tot_elems = (uint64_t)n_levels * (uint64_t)B * (uint64_t)C;
+    if (tot_elems > ((uint64_t)2 << 30) / sizeof(double))
+        return fail(e + ": the totals [n_levels][B][1 + M + M (M + 1) / 2] = [" + std::to_string(n_levels) + "][" + std::to_string(B) + "][" +
+                    std::to_string(C) + "] doubles take " + std::to_string((tot_elems * sizeof(double)) >> 20) +
+                    " MiB, at most 2048 MiB are supported (fewer replicates or components per call)");
+    mlmc_bootstrap *a = new mlmc_bootstrap();
+    a->xcov = true;
+    a->M = M;
+    a->L = n_levels;
+    a->B = B;
+    a->C = C;
+    a->keep_tiles = BS_TPR_MAX;
+    a->shift_host.assign(M, 0.0);
+    const size_t tot = a->tot_bytes();
+    if (hipMalloc((void **)&a->d_tot, tot) != hipSuccess || hipMalloc((void **)&a->d_shift, sizeof(double) * (size_t)M) != hipSuccess ||
+        bs_scratch_alloc(a->sc) != 0) {
+        (void)hipGetLastError();
+        mlmc_bootstrap_destroy(a);
+        return fail(e + ": out of device memory (" + std::to_string(tot >> 20) + " MiB of totals + 64 MiB of scratch)");
+    }
+    hipError_t err = hipMemsetAsync(a->d_tot, 0, tot, rt().stream);
+    if (err == hipSuccess) err = hipMemsetAsync(a->d_shift, 0, sizeof(double) * (size_t)M, rt().stream);
+    if (err != hipSuccess) {
+        mlmc_bootstrap_destroy(a);
+        return fail(e + ": " + hipGetErrorString(err));
+    }
+    *out = a;
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_set_shift(mlmc_bootstrap *a, const double *shift_host) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_set_shift: null argument");
+    if (!a->xcov) return fail("mlmc_bootstrap_set_shift: not a component-covariance handle (mlmc_bootstrap_create_xcov)");
+    if (a->pushes > 0) return fail("mlmc_bootstrap_set_shift: pushes are pending; reset the accumulator first");
+    if (shift_host)
+        for (int m = 0; m < a->M; ++m)
+            if (!std::isfinite(shift_host[m])) return fail("mlmc_bootstrap_set_shift: shift[" + std::to_string(m) + "] is not finite");
+    MLMC_HIP_CHECK(wait_stream(rt().stream));    // the previous reset's upload reads shift_host
+    if (shift_host) std::memcpy(a->shift_host.data(), shift_host, sizeof(double) * (size_t)a->M);
+    else std::fill(a->shift_host.begin(), a->shift_host.end(), 0.0);
+    return 0;
+}
+
+extern "C" int mlmc_bootstrap_finalize_xcov(mlmc_bootstrap *a, int64_t *n_out, double *s1_out, double *s2_out) {
+    MLMC_API_GUARD;
+    using namespace mlmc;
+    if (!a) return fail("mlmc_bootstrap_finalize_xcov: null handle");
+    if (!a->xcov)
+        return fail(std::string("mlmc_bootstrap_finalize_xcov: the handle comes from ") +
+                    (a->multi ? "mlmc_bootstrap_create_multi (use mlmc_bootstrap_finalize_multi)" : "mlmc_bootstrap_create (use mlmc_bootstrap_finalize)"));
+    if (!n_out || !s1_out || !s2_out) return fail("mlmc_bootstrap_finalize_xcov: null argument (n_out, s1_out, s2_out)");
+    const int64_t L = a->L, B = a->B, M = a->M, C = a->C;
+    std::vector<double> tot((size_t)L * B * C);
+    MLMC_HIP_CHECK(hipMemcpyAsync(tot.data(), a->d_tot, sizeof(double) * tot.size(), hipMemcpyDeviceToHost, rt().stream));
+    MLMC_HIP_CHECK(wait_stream(rt().stream));
+    a->sizes_used = 0;
+    if (int rc = bs_time_collect(a)) return rc;
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t l = 0; l < L; ++l) {
+            const double *t = tot.data() + (l * B + b) * C;
+            const int64_t o = b * L + l;
+            n_out[o] = (int64_t)t[0];                                     // an exact integer (the flag column)
+            std::memcpy(s1_out + o * M, t + 1, sizeof(double) * (size_t)M);
+            double *s2 = s2_out + o * M * M;
+            const double *q = t + 1 + M;
+            for (int64_t i = 0; i < M; ++i)
+                for (int64_t j = i; j < M; ++j) {
+                    const double v = *q++;                                // one computed value goes to (i, j) and (j, i)
+                    s2[i * M + j] = v;
+                    s2[j * M + i] = v;
+                }
+        }
     return 0;
 }
 

@@ -433,6 +433,47 @@ class BootstrapAccumulator:
         return ms_c.value, ms_r.value, fl.value
 
 
+class ComponentCovBootstrapAccumulator(BootstrapAccumulator):
+    """Per-replicate level sums of the covariance between the n_comp components of a vector quantity (mlmc_bootstrap_create_xcov):
+    with the weights of bootstrap_weights, a shift a and f~ = f - a, c~ = c - a, per replicate and level n = sum w keep,
+    s1[m] = sum w keep (f~_m - c~_m) and s2[i, j] = sum w keep (f~_i f~_j - c~_i c~_j) (level 0: f~_m, f~_i f~_j).  A sample with a
+    NaN in any of its fine or coarse values is dropped from the whole matrix (ComponentCovAccumulator's rule).  accum / reset /
+    close / kernel_time are BootstrapAccumulator's; finalize() returns n [B, L], s1 [B, L, M], s2 [B, L, M, M] (bitwise
+    symmetric)."""
+    MAX_COMPONENTS = 1024
+
+    def __init__(self, n_comp, n_levels, n_replicates):
+        n_comp = int(n_comp)
+        if not 1 <= n_comp <= self.MAX_COMPONENTS:
+            raise ValueError("component covariance bootstrap: {} components, supported are 1 .. {}".format(n_comp, self.MAX_COMPONENTS))
+        self._moments_fn = None
+        self.n_comp, self.n_levels, self.B = n_comp, int(n_levels), int(n_replicates)
+        self.K = n_comp * n_comp
+        self._keepalive = []
+        h = C.c_void_p()
+        _lib.check(_lib.lib().mlmc_bootstrap_create_xcov(self.n_comp, self.n_levels, self.B, C.byref(h)))
+        self._h = h
+
+    def set_shift(self, shift=None):
+        """Shift a [M] (None: zeros) for the following chunks: set, then the accumulator is reset (pending chunks are an error)."""
+        if shift is not None:
+            shift = _lib.as_f64(shift)
+            if shift.shape != (self.n_comp,):
+                raise ValueError("component covariance bootstrap: shift of shape {}, expected ({},)".format(shift.shape, self.n_comp))
+        _lib.check(_lib.lib().mlmc_bootstrap_set_shift(self._h, _lib.ptr(shift)))
+        self.reset()
+
+    def finalize(self):
+        """-> n [B, L] int64, s1 [B, L, M], s2 [B, L, M, M] float64 (one wait for the device)."""
+        M = self.n_comp
+        n = np.empty((self.B, self.n_levels), dtype=np.int64)
+        s1 = np.empty((self.B, self.n_levels, M), dtype=np.float64)
+        s2 = np.empty((self.B, self.n_levels, M, M), dtype=np.float64)
+        _lib.check(_lib.lib().mlmc_bootstrap_finalize_xcov(self._h, _lib.ptr(n), _lib.ptr(s1), _lib.ptr(s2)))
+        self._keepalive = []
+        return n, s1, s2
+
+
 class ComponentBootstrapAccumulator(BootstrapAccumulator):
     """BootstrapAccumulator with one moments object per component (mlmc_bootstrap_create_multi): component m (row m of the chunks)
     takes its first K moments from moments_fns[m] -- plain Legendre, Monomial or Fourier objects of one family, each with its own

@@ -19,6 +19,58 @@ ComponentBootstrapReplicates = collections.namedtuple("ComponentBootstrapReplica
 QuantileBands = collections.namedtuple("QuantileBands", "q lo hi replicates success n_ok seed")
 ScoreCorrelation = collections.namedtuple("ScoreCorrelation", "corr cov cov_var mean var n_samples n_rm_samples")
 EventMeans = collections.namedtuple("EventMeans", "mean stderr prob ess")
+CovarianceBootstrapReplicates = collections.namedtuple("CovarianceBootstrapReplicates", "n_samples mean cov corr ok seed")
+CorrelationBands = collections.namedtuple("CorrelationBands", "corr lo hi std replicates ok n_ok seed")
+ProbabilityBands = collections.namedtuple("ProbabilityBands", "prob stderr lo hi replicates ok n_ok seed")
+
+
+def covariance_replicates(n, s1, s2, sample_vector, shift=None, centered=True):
+    """Host finish of the component-covariance bootstrap (pure arithmetic, no device): n [B, L] kept counts, s1 [B, L, M] and
+    s2 [B, L, M, M] the per-replicate level sums of the shifted first moments and products
+    (quantity_estimate.bootstrap_component_covariance), sample_vector [L] the requested samples per level, shift a [M] | None.
+    Over the levels with sample_vector[l] > 0:  m_b = sum_l s1 / n,  S_b = sum_l s2 / n,  mean_b = m_b + a,
+    cov_b = S_b - m_b m_b^T (every replicate centred on its OWN mean; symmetrised), corr_b = cov_b / (sd sd^T) with a unit
+    diagonal.  centered=False: `cov` holds the raw second moments S_b instead (corr is still that of S_b - m_b m_b^T).
+    ok[b] is False when a level with sample_vector[l] > 0 has n = 0 or a variance is not positive and finite; the rows of such a
+    replicate are NaN.  -> (mean [B, M], cov [B, M, M], corr [B, M, M], ok [B])"""
+    n = np.asarray(n)
+    s1 = np.asarray(s1, dtype=np.float64)
+    s2 = np.asarray(s2, dtype=np.float64)
+    if n.ndim != 2 or s1.shape[:2] != n.shape or s2.shape != s1.shape + s1.shape[2:]:
+        raise ValueError("covariance_replicates: n [B, L], s1 [B, L, M] and s2 [B, L, M, M] expected, got shapes {}, {} and {}".format(
+            n.shape, s1.shape, s2.shape))
+    B, L, M = s1.shape
+    used = np.asarray(sample_vector).reshape(-1) > 0
+    if used.shape != (L,):
+        raise ValueError("covariance_replicates: sample_vector must hold one value per level ({}), got {!r}".format(L, sample_vector))
+    a = np.zeros(M) if shift is None else np.asarray(shift, dtype=np.float64).reshape(M)
+    nf = n[:, used].astype(np.float64)
+    ok = np.all(nf > 0, axis=1)
+    with np.errstate(all="ignore"):
+        m = np.sum(s1[:, used] / nf[:, :, None], axis=1)
+        S = np.sum(s2[:, used] / nf[:, :, None, None], axis=1)
+        cov = S - m[:, :, None] * m[:, None, :]
+        cov = 0.5 * (cov + cov.transpose(0, 2, 1))
+        var = np.diagonal(cov, axis1=1, axis2=2)
+        ok = ok & np.all(np.isfinite(var) & (var > 0), axis=1)
+        sd = np.sqrt(var)
+        corr = cov / (sd[:, :, None] * sd[:, None, :])
+    idx = np.arange(M)
+    corr[:, idx, idx] = 1.0
+    mean = m + a[None, :]
+    out_cov = cov if centered else 0.5 * (S + S.transpose(0, 2, 1))
+    mean[~ok] = np.nan
+    out_cov[~ok] = np.nan
+    corr[~ok] = np.nan
+    return mean, out_cov, corr, ok
+
+
+def _band_over_ok(replicates, ok, level):
+    """quantile_bands of replicates [B, ...] over the ok replicates -> (lo, hi) of the trailing shape"""
+    replicates = np.asarray(replicates, dtype=np.float64)
+    flat = replicates.reshape(replicates.shape[0], 1, -1)
+    lo, hi = quantile_bands(flat, np.asarray(ok, dtype=bool)[:, None], level)
+    return lo.reshape(replicates.shape[1:]), hi.reshape(replicates.shape[1:])
 
 
 def quantile_bands(replicates, success, level):
@@ -549,6 +601,143 @@ class Estimate:
         results = simple_distribution.estimate_densities_minimize(distrs, tol, reg_param)
         success = np.array([bool(r.success) for r in results], dtype=bool).reshape(B, M)
         return probs, densities, distrs, success, seed, level
+
+    @staticmethod
+    def _resampled_corr_arg(what, corr):
+        if corr is not None and not (isinstance(corr, str) and corr == "scores"):
+            if isinstance(corr, str):
+                raise ValueError("{}: corr must be None or 'scores', got {!r}".format(what, corr))
+            raise ValueError("{}: corr must be None or 'scores': a given correlation matrix has nothing to resample".format(what))
+
+    def est_bootstrap_component_covariance(self, n_subsamples=100, sample_vector=None, seed=None, centered=True, corr=None,
+                                           densities=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None):
+        """Bootstrap replicates of the multilevel covariance and correlation between the M scalar components of the quantity, every
+        replicate from one device pass per stored chunk (mlmc_bootstrap_create_xcov), seeded.  The weights are those of
+        est_bootstrap_batch / est_bootstrap_components with the same seed and sample_vector: replicate b here and replicate b there
+        are the same picks.  Bit-identical from run to run; the first B replicates do not depend on n_subsamples.
+
+        corr=None: the raw components.  centered=True: the sums are shifted by a = estimate_mean(quantity).mean (as
+        estimate_component_covariance; the shift only spares the sums the cancellation of raw second moments), every replicate is
+        then centred on its OWN mean: cov_b = S_b - m_b m_b^T.  centered=False: no shift, and `cov` holds the raw second moments.
+        corr="scores": the normal scores of the components under `densities` (constructed if missing).  The transform stays
+        fixed; only the samples are resampled.  A correlation matrix is an error: there is nothing to resample.
+        :return: CovarianceBootstrapReplicates(n_samples [B, L], mean [B, M], cov [B, M, M], corr [B, M, M], ok [B], seed); see
+            covariance_replicates for the arithmetic.  ok[b] False (a level without a kept pick, a variance that is not positive
+            and finite) leaves NaN rows; it is not an exception."""
+        what = "est_bootstrap_component_covariance"
+        self._resampled_corr_arg(what, corr)
+        B, k, seed = self._bootstrap_args(what, n_subsamples, sample_vector, seed)
+        M = int(self._quantity.size())
+        shift, scores = None, None
+        if corr == "scores":
+            if densities is None:
+                densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+            densities = list(densities)
+            if len(densities) != M:
+                raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
+            scores = [d[0] for d in densities]
+        elif centered:
+            shift = np.asarray(qe.estimate_mean(self._quantity).mean, dtype=np.float64).reshape(M)
+        n, s1, s2 = qe.bootstrap_component_covariance(self._quantity, B, k, seed, shift=shift, scores=scores)
+        mean, cov, corr_b, ok = covariance_replicates(n, s1, s2, k, shift, centered or scores is not None)
+        return CovarianceBootstrapReplicates(n, mean, cov, corr_b, ok, seed)
+
+    def bootstrap_component_correlation(self, n_subsamples=100, sample_vector=None, seed=None, level=0.9, corr=None, densities=None,
+                                        tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None):
+        """Bootstrap confidence bands of the correlation matrix the Gaussian copula takes (`sample_joint`): how far every entry moves
+        under resampling of the stored samples.
+        :param corr: None (the Pearson correlation of the components) or "scores" (estimate_score_correlation under `densities`)
+        :param level: coverage of the band, 0 < level < 1
+        :return: CorrelationBands(corr [M, M] the estimate's own matrix, lo, hi [M, M] = the percentiles of quantile_bands and
+            std [M, M] (ddof = 1) over the ok replicates, replicates [B, M, M] = est_bootstrap_component_covariance(...).corr,
+            ok [B], n_ok, seed)"""
+        what = "bootstrap_component_correlation"
+        level = _check_level(what, level)
+        self._resampled_corr_arg(what, corr)
+        B, k, seed = self._bootstrap_args(what, n_subsamples, sample_vector, seed)
+        corr0, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        r = self.est_bootstrap_component_covariance(B, k, seed, corr=corr, densities=densities, tol=tol, reg_param=reg_param,
+                                                    orth_moments_tol=orth_moments_tol, moments_fns=moments_fns)
+        lo, hi = _band_over_ok(r.corr, r.ok, level)
+        n_ok = int(np.sum(r.ok))
+        std = np.std(r.corr[r.ok], axis=0, ddof=1) if n_ok > 1 else np.full(r.corr.shape[1:], np.nan)
+        return CorrelationBands(np.asarray(corr0, dtype=np.float64), lo, hi, std, r.corr, r.ok, n_ok, seed)
+
+    def bootstrap_joint_probability(self, lower, upper, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
+                                    seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
+                                    orth_moments_tol=1e-4, moments_fns=None):
+        """Bootstrap confidence bands of estimate_joint_probability: how far the probability of a box moves when the stored samples
+        are resampled.  The `stderr` of estimate_joint_probability is the quasi-Monte Carlo integration error alone; the band here
+        is the sampling uncertainty of the correlation matrix (and, on request, of the marginals) pushed through the box integral.
+
+        Replicate b is joint_probabilities(distrs_b, lower, upper, n, seeds, corr=corr_b) with corr_b replicate b of
+        est_bootstrap_component_covariance(seed=seed): one call per replicate, with the SAME quasi-Monte Carlo seeds for all, so
+        the integration error is largely common to the replicates and does not widen the band.
+        :param marginals: "fixed": distrs_b are the estimate's densities, only the dependence is resampled.  "resampled":
+            distrs_b are replicate b's maximum-entropy densities, the replicate densities of bootstrap_component_quantiles with
+            the same seed and sample_vector -- the same picks, so replicate b is one coherent resample of marginals and dependence
+        :param corr: None (Pearson) or "scores"; a matrix is an error (nothing to resample)
+        :param n, seeds: as in estimate_joint_probability (smaller default n: there are n_subsamples + 1 integrals)
+        :return: ProbabilityBands(prob [n_boxes], stderr [n_boxes] = those of estimate_joint_probability with the same n and seeds,
+            lo, hi [n_boxes] = quantile_bands over the ok replicates, replicates [B, n_boxes], ok [B], n_ok, seed).  A replicate
+            whose correlation is not ok, whose solve failed for a component that a box constrains (a finite limit on either
+            side), or whose call raises is not ok and is left out of the bands.  `given` is not supported here."""
+        from .tool import simple_distribution
+        what = "bootstrap_joint_probability"
+        level = _check_level(what, level)
+        if marginals not in ("fixed", "resampled"):
+            raise ValueError("{}: marginals must be 'fixed' or 'resampled', got {!r}".format(what, marginals))
+        self._resampled_corr_arg(what, corr)
+        n, seeds, _ = simple_distribution._box_call_args(what, n, seeds, 0)
+        seeds = [int(v) for v in seeds]
+        lower = np.asarray(lower, dtype=np.float64)
+        upper = np.asarray(upper, dtype=np.float64)
+        if np.any(np.isnan(lower)) or np.any(np.isnan(upper)):
+            raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
+        B, k, seed = self._bootstrap_args(what, n_subsamples, sample_vector, seed)
+        M = int(self._quantity.size())
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        densities = list(densities)
+        if len(densities) != M:
+            raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
+        corr0, _ = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        distrs = [d[0] for d in densities]
+        base = simple_distribution.joint_probabilities(distrs, lower, upper, n, seeds, corr=corr0)
+        reps = self.est_bootstrap_component_covariance(B, k, seed, corr=corr, densities=densities)
+        ok = reps.ok.copy()
+        rep_distrs, success = None, None
+        if marginals == "resampled":
+            _, _, rep_distrs, success, _, _ = self._bootstrap_replicate_densities(what, None, B, k, seed, level, tol, reg_param,
+                                                                                  orth_moments_tol, moments_fns, densities)
+            lo_b, up_b = np.broadcast_to(lower, (np.size(base.prob), M)), np.broadcast_to(upper, (np.size(base.prob), M))
+            constrained = np.any(np.isfinite(lo_b) | np.isfinite(up_b), axis=0)
+            ok &= np.all(success[:, constrained], axis=1)
+        replicates = np.full((B, np.size(base.prob)), np.nan)
+        for b in range(B):
+            if not ok[b]:
+                continue
+            d_b = distrs if rep_distrs is None else rep_distrs[b * M:(b + 1) * M]
+            try:
+                replicates[b] = simple_distribution.joint_probabilities(d_b, lower, upper, n, seeds, corr=reps.corr[b]).prob
+            except Exception:
+                ok[b] = False
+        lo, hi = _band_over_ok(replicates, ok, level)
+        return ProbabilityBands(np.asarray(base.prob), np.asarray(base.stderr), lo, hi, replicates, ok, int(np.sum(ok)), seed)
+
+    def bootstrap_joint_exceedance(self, thresholds, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
+                                   seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
+                                   orth_moments_tol=1e-4, moments_fns=None):
+        """P(X_m > t_m for all constrained m) with its bootstrap band: `bootstrap_joint_probability` with lower = thresholds and
+        upper = +inf.
+        :param thresholds: broadcast to [n_boxes, M]; -inf leaves a component unconstrained
+        :return: as bootstrap_joint_probability"""
+        t = np.asarray(thresholds, dtype=np.float64)
+        if np.any(np.isnan(t)):
+            raise ValueError("bootstrap_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
+        return self.bootstrap_joint_probability(t, np.inf, n_subsamples=n_subsamples, sample_vector=sample_vector, seed=seed,
+                                                level=level, n=n, seeds=seeds, corr=corr, marginals=marginals, densities=densities,
+                                                tol=tol, reg_param=reg_param, orth_moments_tol=orth_moments_tol, moments_fns=moments_fns)
 
     def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
         """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""

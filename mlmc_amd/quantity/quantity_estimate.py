@@ -1437,9 +1437,65 @@ def bootstrap_component_moments(quantity, moments_fns, n_replicates, sample_vect
                                n_replicates, sample_vector, seed)
 
 
-def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sample_vector, seed):
+def bootstrap_component_covariance(quantity, n_replicates, sample_vector, seed, shift=None, scores=None):
+    """Level sums of the covariance between the M scalar components of `quantity` for n_replicates bootstrap sub-samples at once
+    (Estimate.est_bootstrap_component_covariance; engine.ComponentCovBootstrapAccumulator): per replicate b and level l, with
+    f~ = f - shift, c~ = c - shift, n = sum w keep, s1[m] = sum w keep (f~_m - c~_m), s2[i, j] = sum w keep (f~_i f~_j - c~_i c~_j)
+    (level 0: f~_m, f~_i f~_j).  The chunk walk, sizes and Philox streams are those of bootstrap_moments and
+    bootstrap_component_moments, so replicate b is drawn with exactly the weights of those calls with the same seed.  A sample
+    with a NaN in any component, fine or coarse, is dropped from the whole matrix.
+
+    scores = a list of M distributions with multipliers (the checks of component_covariance(scores=...)): the rows pushed are the
+    NORMAL SCORES of the chunk under these marginals (tool.simple_distribution.normal_scores); a NaN or out-of-domain value has
+    the score NaN and drops the sample.  The scores of a whole chunk of n samples are computed into a workspace of 16 M n bytes
+    (fine and coarse), which is released when the chunk is done (one wait for the device per chunk on this route).  No shift can
+    be given with scores.
+    -> n [B, L] kept counts, s1 [B, L, M], s2 [B, L, M, M] (bitwise symmetric)"""
+    if not isinstance(quantity, qmod.Quantity) or isinstance(quantity, (_MomentsNode, _CovarianceNode, _ComponentCovNode)):
+        raise TypeError("bootstrap_component_covariance: needs a Quantity whose samples are component values, got {}".format(
+            type(quantity).__name__))
+    M = int(quantity.size())
+    if M > engine.ComponentCovBootstrapAccumulator.MAX_COMPONENTS:
+        raise ValueError("bootstrap_component_covariance: {} components, at most {} are supported".format(
+            M, engine.ComponentCovBootstrapAccumulator.MAX_COMPONENTS))
+    if scores is not None:
+        scores = list(scores)
+        if shift is not None:
+            raise ValueError("bootstrap_component_covariance: scores and shift exclude each other")
+        if len(scores) != M:
+            raise ValueError("bootstrap_component_covariance: {} score distributions for {} components".format(len(scores), M))
+        if len({d.n_intervals for d in scores}) != 1 or len({d._gauss_degree for d in scores}) != 1:
+            raise ValueError("bootstrap_component_covariance: every distribution must use the same quadrature")
+    if shift is not None:
+        shift = np.array(shift, dtype=np.float64)
+        if shift.shape != (M,):
+            raise ValueError("bootstrap_component_covariance: shift of shape {}, expected ({},)".format(shift.shape, M))
+        if not np.all(np.isfinite(shift)):
+            raise ValueError("bootstrap_component_covariance: the shift must be finite")
+    chunk_map = None
+    if scores is not None:
+        state = {}
+
+        def chunk_map(fine, coarse, n):
+            import torch
+            from ..tool import simple_distribution
+            if "head" not in state:
+                state["head"], state["keep"] = simple_distribution._scores_problem_args(scores, "bootstrap_component_covariance")
+            ws = torch.empty((2, M, n), dtype=torch.float64, device=fine.device)      # 16 M n bytes
+            torch.cuda.current_stream(fine.device).synchronize()     # the library reads and writes on its own stream
+            simple_distribution._scores_into(state["head"], fine, coarse, n, n, ws[0], None if coarse is None else ws[1], n)
+            return ws[0], (None if coarse is None else ws[1])
+    with _estimate_lock:
+        return _bootstrap_walk(quantity, "acc_xcov", lambda n_levels: ("xcov", M, n_levels, int(n_replicates)),
+                               lambda n_levels: engine.ComponentCovBootstrapAccumulator(M, n_levels, n_replicates), scores,
+                               n_replicates, sample_vector, seed, setup=lambda acc: acc.set_shift(shift), chunk_map=chunk_map)
+
+
+def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sample_vector, seed, setup=None, chunk_map=None):
     """One bootstrap pass over the stored chunks of `quantity` into the pooled accumulator of `slot` (reused when make_key(n_levels)
-    matches the last call's, else replaced by make_acc(n_levels)); `alive` is kept with it.  -> the accumulator's finalize()"""
+    matches the last call's, else replaced by make_acc(n_levels)); `alive` is kept with it.  setup(acc): called once before the
+    first chunk; chunk_map(fine, coarse, n) -> (fine, coarse): device rows made for this chunk, accumulated in place of the
+    chunk's own and released after a wait for their accumulation.  -> the accumulator's finalize()"""
     import torch
     cache_clear()
     storage_q = quantity.get_quantity_storage()
@@ -1466,6 +1522,8 @@ def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sam
     copied = False
     pushed = 0
     try:
+        if setup is not None:
+            setup(acc)
         for chunk_spec in storage_q.chunks():
             level = int(chunk_spec.level_id)
             c = chunk_no[level]
@@ -1488,7 +1546,13 @@ def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sam
                 torch.cuda.current_stream(dev).synchronize()     # the library reads them on its own stream
                 copied = False
             sizes = bootstrap_sizes(seed, level, c, sample_vector[level], n_level[level], n, n_replicates)
+            if chunk_map is not None:
+                pair = chunk_map(pair[0], pair[1], n)
             acc.accum(level, pair[0], pair[1], sizes, seed, bootstrap_stream(level, c))
+            if chunk_map is not None:                            # its rows are a workspace of this chunk: released once they are read
+                from .. import _lib
+                _lib.check(_lib.lib().mlmc_synchronize())
+                acc._keepalive.pop()
             pushed += 1
         if pushed == 0:
             raise Exception("All samples were masked")
