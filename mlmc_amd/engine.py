@@ -383,6 +383,8 @@ class BootstrapAccumulator:
     and s, sp [B, L, n_comp * R] (row m * R + r) -- what a LevelAccumulator in MOMENTS mode gives for the resampled chunks."""
 
     def __init__(self, moments_fn, n_comp, n_levels, n_replicates):
+        # kept for the accumulator's lifetime: the library reads the basis handle until destroy, and quantity_estimate's pool of
+        # bootstrap accumulators is keyed by id(moments_fn), which stays unique only while the object lives
         self._moments_fn = moments_fn
         self.n_comp, self.n_levels, self.B = int(n_comp), int(n_levels), int(n_replicates)
         self.K = self.n_comp * int(moments_fn.size)
@@ -415,6 +417,11 @@ class BootstrapAccumulator:
         self._keepalive.append((fine, coarse))             # launches are asynchronous
         _lib.check(_lib.lib().mlmc_bootstrap_accum(self._h, int(level), _lib.ptr(fine), _lib.ptr(coarse), int(fine.shape[1]),
                                                    _lib.ptr(sizes), int(seed) & (2 ** 64 - 1), int(stream) & 0xFFFFFFFF))
+
+    def release_last(self):
+        """Let go of the rows of the last accum(): the caller has waited for their accumulation (mlmc_synchronize) and frees or
+        reuses them, instead of holding every chunk's rows until finalize()."""
+        self._keepalive.pop()
 
     def finalize(self):
         """-> n [B, L] int64, s [B, L, K], sp [B, L, K] float64 (one wait for the device)."""
@@ -481,7 +488,7 @@ class ComponentBootstrapAccumulator(BootstrapAccumulator):
     counts and s, sp [B, L, M, K].  No column cap: components run in groups inside the library."""
 
     def __init__(self, moments_fns, K, n_levels, n_replicates):
-        self._moments_fn = list(moments_fns)                   # the library reads the basis handles until destroy
+        self._moments_fn = list(moments_fns)                   # kept, as in BootstrapAccumulator: handles and pool-key ids stay valid
         self.n_comp, self.n_levels, self.B = len(self._moments_fn), int(n_levels), int(n_replicates)
         self.n_moments = int(K)
         self.K = self.n_comp * self.n_moments

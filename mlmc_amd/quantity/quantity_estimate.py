@@ -8,6 +8,9 @@ accumulation kernels (mlmc_amd/csrc/moments.hip, cov.hip).  Nothing of shape [M*
 ever materialised.
 """
 import collections
+import contextlib
+import functools
+import itertools
 import os
 import threading
 
@@ -113,32 +116,38 @@ def component_covariance(quantity, shift=None, scores=None):
     :param quantity: Quantity with M <= 1024 scalar components (not a moments / covariance node)
     :param shift: None (zeros) or M finite values
     """
-    if not isinstance(quantity, qmod.Quantity) or isinstance(quantity, (_MomentsNode, _CovarianceNode, _ComponentCovNode)):
-        raise TypeError("component_covariance: needs a Quantity whose samples are component values, got {}".format(
-            type(quantity).__name__))
-    M = int(quantity.size())
+    limit, note = engine.ComponentCovAccumulator.MAX_COMPONENTS, ""
     if scores is not None:
+        limit, note = limit - 1, " with scores"                  # the row of ones takes one of the accumulator's rows
+    M, shift, scores = _component_args("component_covariance", quantity, shift, scores, limit, note)
+    side = M if scores is None else M + 1
+    return _ComponentCovNode(quantity, shift, qt.ArrayType(shape=(side, side), qtype=qt.ScalarType()), scores=scores)
+
+
+def _component_args(what, quantity, shift, scores, max_components, limit_note="", limit_first=False):
+    """The checks of `shift` / `scores` that component_covariance and bootstrap_component_covariance share; `what` names the caller
+    in the messages, `limit_note` ends the one about max_components, which comes before (limit_first) or between the checks of the
+    scores, as each caller always had it.  -> M, shift as a float64 array [M] | None, scores as a list | None"""
+    if not isinstance(quantity, qmod.Quantity) or isinstance(quantity, (_MomentsNode, _CovarianceNode, _ComponentCovNode)):
+        raise TypeError("{}: needs a Quantity whose samples are component values, got {}".format(what, type(quantity).__name__))
+    M = int(quantity.size())
+    if scores is not None and not (limit_first and M > max_components):
         scores = list(scores)
         if shift is not None:
-            raise ValueError("component_covariance: scores and shift exclude each other")
+            raise ValueError("{}: scores and shift exclude each other".format(what))
         if len(scores) != M:
-            raise ValueError("component_covariance: {} score distributions for {} components".format(len(scores), M))
-        if M + 1 > engine.ComponentCovAccumulator.MAX_COMPONENTS:
-            raise ValueError("component_covariance: {} components, at most {} are supported with scores".format(
-                M, engine.ComponentCovAccumulator.MAX_COMPONENTS - 1))
-        if len({d.n_intervals for d in scores}) != 1 or len({d._gauss_degree for d in scores}) != 1:
-            raise ValueError("component_covariance: every distribution must use the same quadrature")
-        return _ComponentCovNode(quantity, None, qt.ArrayType(shape=(M + 1, M + 1), qtype=qt.ScalarType()), scores=scores)
-    if M > engine.ComponentCovAccumulator.MAX_COMPONENTS:
-        raise ValueError("component_covariance: {} components, at most {} are supported".format(
-            M, engine.ComponentCovAccumulator.MAX_COMPONENTS))
+            raise ValueError("{}: {} score distributions for {} components".format(what, len(scores), M))
+    if M > max_components:
+        raise ValueError("{}: {} components, at most {} are supported{}".format(what, M, max_components, limit_note))
+    if scores is not None and (len({d.n_intervals for d in scores}) != 1 or len({d._gauss_degree for d in scores}) != 1):
+        raise ValueError("{}: every distribution must use the same quadrature".format(what))
     if shift is not None:
         shift = np.array(shift, dtype=np.float64)
         if shift.shape != (M,):
-            raise ValueError("component_covariance: shift of shape {}, expected ({},)".format(shift.shape, M))
+            raise ValueError("{}: shift of shape {}, expected ({},)".format(what, shift.shape, M))
         if not np.all(np.isfinite(shift)):
-            raise ValueError("component_covariance: the shift must be finite")
-    return _ComponentCovNode(quantity, shift, qt.ArrayType(shape=(M, M), qtype=qt.ScalarType()))
+            raise ValueError("{}: the shift must be finite".format(what))
+    return M, shift, scores
 
 
 def moment(quantity, moments_fn, i=0):
@@ -284,6 +293,12 @@ def _lib_device():
     return _lib._bound_device
 
 
+@functools.lru_cache(maxsize=None)
+def _cuda_device(index):
+    import torch
+    return torch.device("cuda", index)
+
+
 _device_cache = _DeviceChunkCache()
 # One estimate at a time: one GPU stream, one sample cache, one memo of chunk evaluations shared by all quantities.
 _estimate_lock = threading.RLock()
@@ -390,7 +405,7 @@ class _LevelStreamer:
             yield item
         if not plans:
             return
-        dev = torch.device("cuda", _lib_device())
+        dev = _cuda_device(_lib_device())
         cap = max([self.block_doubles()] + [max(p["sizes"]) * p["sn"] for p in plans])
         # global lists: tasks (one per chunk, in order) and staging blocks (consecutive chunks of ONE level)
         tasks, blocks = [], []          # task: (plan index, chunk index, block index, offset in block); block: [plan index, length, tasks left, offset in level]
@@ -507,7 +522,7 @@ def _upload(host_array, count=True):
     a = np.ascontiguousarray(host_array, dtype=np.float64)
     if count:
         _device_cache.uploads += 1
-    dev = torch.device("cuda", _lib_device())
+    dev = _cuda_device(_lib_device())
     t = torch.from_numpy(a).to(dev)
     torch.cuda.current_stream(dev).synchronize()                 # the library reads it on its own stream
     return t
@@ -891,6 +906,47 @@ def _chunk_for_device(source, plan, chunk_spec, n_collected, use_cache, raw=None
     return item[0], item[1]
 
 
+# What a walk over the stored chunks of a quantity settles before the first chunk: the storage that hands out the chunk specs, the
+# lowered tree of the rows that are read (None: evaluated on the host), the stamps of the levels (None: the storage cannot tell),
+# whether chunks are served from / added to the device cache, and for its keys the identity of the rows and the object whose
+# lifetime bounds them; the torch device of the library.
+_Walk = collections.namedtuple("_Walk", "storage_q n_levels plan n_collected use_cache ident owner dev")
+
+
+def _walk_setup(quantity, source=None):
+    """The _Walk of estimate_mean, the per-component entries and the bootstraps.  The memo of host evaluations is cleared; the rows
+    of `source` -- the quantity whose chunks are read: `quantity` itself, or for an estimate the input of its moments / covariance
+    node -- are cached when there is a budget, the storage stamps its levels and the rows are not a fresh random draw per
+    evaluation (`_volatile`)."""
+    source = quantity if source is None else source
+    cache_clear()
+    storage_q = quantity.get_quantity_storage()
+    n_levels = int(max(storage_q.level_ids())) + 1
+    # a tree of per-sample nodes runs as one device program over the stored rows (quantity/lowering.py)
+    plan = lowering.plan_for(source) if _device_tree_enabled() else None
+    try:
+        n_collected = _level_stamps(storage_q)
+    except Exception:
+        n_collected = None
+    use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(source, "_volatile", False)
+    return _Walk(storage_q, n_levels, plan, n_collected, use_cache, _cache_ident(source, plan),
+                 _owner_of(plan) if plan is not None else source, _cuda_device(_lib_device()))
+
+
+def _device_rows(x, M, dev):
+    """x: [M, n] values, a host array or a tensor -> (contiguous float64 tensor [M, n] on `dev`, whether that took a copy).  A copy
+    runs on torch's stream and the library reads on its own: the caller decides when to wait."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.float64 and x.device == dev and x.dim() == 2 and x.shape[0] == M and x.is_contiguous():
+            return x, False                                      # (resident rows: the usual case)
+        t = x
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    rows = t.to(device=dev, dtype=torch.float64).reshape(M, t.shape[-1]).contiguous()
+    return rows, rows.data_ptr() != t.data_ptr()
+
+
 def fine_samples_for_device(quantity, chunk_spec):
     """Fine values of one chunk of `quantity` where the device wants them: a torch CUDA tensor when the tree is lowered
     (stored rows resident or generated in HBM, nothing crosses PCIe), else the host array of the host-evaluated tree.
@@ -926,9 +982,9 @@ def _subsample_on_device(pair, params):
     size = int(qmod.RNG.hypergeometric(params._orig_k, params._orig_n - params._orig_k, min(n, params._orig_n)))
     seed = int(qmod.RNG.integers(0, 2 ** 63 - 1))
     if not isinstance(fine, torch.Tensor):                       # host chunk (over the cache budget): upload for the gather
-        dev = torch.device("cuda", _lib_device())
-        fine = torch.from_numpy(np.ascontiguousarray(fine)).to(dev)
-        coarse = None if coarse is None else torch.from_numpy(np.ascontiguousarray(coarse)).to(dev)
+        dev = _cuda_device(_lib_device())
+        fine = _device_rows(fine, fine.shape[0], dev)[0]
+        coarse = None if coarse is None else _device_rows(coarse, coarse.shape[0], dev)[0]
         torch.cuda.current_stream(dev).synchronize()
     m = fine.shape[0]
     out_f = torch.empty((m, size), dtype=torch.float64, device=fine.device)
@@ -1007,39 +1063,30 @@ def _component_chunks(quantity, M, what):
     import ctypes as C
     import torch
     from .. import _lib
-    cache_clear()
-    storage_q = quantity.get_quantity_storage()
-    n_levels = int(np.max(storage_q.level_ids())) + 1
     if quantity.size() != M:
         raise ValueError("{}: {} moments objects for {} components".format(what, M, quantity.size()))
-    plan = lowering.plan_for(quantity) if _device_tree_enabled() else None
-    try:
-        n_collected = _level_stamps(storage_q)
-    except Exception:
-        n_collected = None
-    use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(quantity, "_volatile", False)
-    dev = torch.device("cuda", _lib_device())
+    walk = _walk_setup(quantity)
     levels, fines, coarses, ns, keep = [], [], [], [], []
-    for chunk_spec in storage_q.chunks():
-        fine, coarse = _chunk_for_device(quantity, plan, chunk_spec, n_collected, use_cache)
+    for chunk_spec in walk.storage_q.chunks():
+        fine, coarse = _chunk_for_device(quantity, walk.plan, chunk_spec, walk.n_collected, walk.use_cache)
         if fine.shape[-1] == 0:
             continue
-        fine = torch.as_tensor(fine, dtype=torch.float64, device=dev).reshape(M, -1).contiguous()
+        fine = _device_rows(fine, M, walk.dev)[0]
         if coarse is not None:
-            coarse = torch.as_tensor(coarse, dtype=torch.float64, device=dev).reshape(M, -1).contiguous()
+            coarse = _device_rows(coarse, M, walk.dev)[0]
         keep.append((fine, coarse))
         levels.append(int(chunk_spec.level_id))
         fines.append(fine.data_ptr())
         coarses.append(None if coarse is None else coarse.data_ptr())
         ns.append(fine.shape[-1])
-    torch.cuda.current_stream(dev).synchronize()
+    torch.cuda.current_stream(walk.dev).synchronize()
     nc = len(ns)
     lv = np.array(levels, dtype=np.int32)
     nn = np.array(ns, dtype=np.int64)
     fp = (C.c_void_p * max(nc, 1))(*fines)
     cp = (C.c_void_p * max(nc, 1))(*coarses)
     keep.append((lv, nn, fp, cp))
-    return n_levels, keep, (nc, _lib.ptr(lv), C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn))
+    return walk.n_levels, keep, (nc, _lib.ptr(lv), C.cast(fp, C.c_void_p), C.cast(cp, C.c_void_p), _lib.ptr(nn))
 
 
 def _component_entry(quantity, M, what, entry, lead, shapes):
@@ -1142,13 +1189,15 @@ def estimate_mean(quantity, group=None, variance=True):
         return _estimate_mean(quantity, group, variance)
 
 
-def _estimate_mean(quantity, group, variance):
-    cache_clear()
-    quantity_vec_size = quantity.size()
-    storage_q = quantity.get_quantity_storage()
-    level_ids = storage_q.level_ids()
-    n_levels = int(np.max(level_ids)) + 1
+_Target = collections.namedtuple("_Target", "source fn mode rows_per_comp rows_out lin_fn scores shift subsample_params")
 
+
+def _estimate_target(quantity, variance):
+    """What an estimate estimates, from the node at its root: the quantity whose sample rows are read, the moments object (or None),
+    accumulator mode and rows per component of the device pass, the rows per component the caller sees, the caller's moments object
+    when `fn` is its linearisation, the marginals and the shift of a component covariance, the per-level parameters of
+    Quantity.subsample.  No device work; _linearized_basis keeps its extended basis with the moments object."""
+    scores = shift = None
     if isinstance(quantity, (_MomentsNode, _CovarianceNode)):
         source = quantity._input_quantities[0]
         fn = quantity._moments_fn
@@ -1157,7 +1206,8 @@ def _estimate_mean(quantity, group, variance):
     elif isinstance(quantity, _ComponentCovNode):
         # the raw component values go to the component-covariance accumulator: M x M rows, i.e. M "rows per component"
         source, fn, mode = quantity._input_quantities[0], None, engine.LevelAccumulator.COMPONENT_COV
-        rows_per_comp = int(source.size()) + (1 if quantity._scores is not None else 0)      # scores: plus the row of ones
+        scores, shift = quantity._scores, quantity._shift
+        rows_per_comp = int(source.size()) + (1 if scores is not None else 0)                # scores: plus the row of ones
     else:
         source, fn, mode, rows_per_comp = quantity, None, engine.LevelAccumulator.MOMENTS, 1
     rows_out = rows_per_comp                                      # rows per component the caller sees
@@ -1177,215 +1227,240 @@ def _estimate_mean(quantity, group, variance):
     if sym is not None and sym[0] == "subsample" and _device_tree_enabled():
         subsample_params = sym[1]
         source = source._input_quantities[0]
+    return _Target(source, fn, mode, rows_per_comp, rows_out, lin_fn, scores, shift, subsample_params)
 
-    # a tree of per-sample nodes runs as one device program over the stored rows (quantity/lowering.py)
-    plan = lowering.plan_for(source) if _device_tree_enabled() else None
-    acc = None
-    n_comp = None
-    use_cache = _DeviceChunkCache.budget() > 0 and not getattr(source, "_volatile", False)
-    try:
-        n_collected = _level_stamps(storage_q)
-    except Exception:
-        n_collected = None
-        use_cache = False
-    # A level that arrives in several resident chunks (HDF5 files deliver levels that way) is concatenated into ONE tensor
-    # per level before it is pushed -- once; the level-wide entry replaces the chunk entries in the cache -- so every
-    # estimate, the first one included, is one push per level and gives bit-identical sums.
-    consolidate = use_cache and subsample_params is None
-    ident = _cache_ident(source, plan)
-    owner = _owner_of(plan) if plan is not None else source
 
-    def push_pair(level_id, pair):
-        nonlocal acc, n_comp
-        if pair is None:
-            return
-        if acc is None:
-            n_comp = pair[0].shape[0] + (1 if scores is not None else 0)
-            if pair[0].shape[-1] > 0:
-                assert n_comp * rows_out == quantity_vec_size
-            acc = _acc_pool.take(fn, n_levels, mode, n_comp, mean_only=not variance)
-            if mode == engine.LevelAccumulator.COMPONENT_COV:
-                acc.set_shift(quantity._shift)                  # this estimate's shift (the pooled one may carry another)
-        if pair[0].shape[-1] == 0:                               # empty chunk / every sample deselected
-            return
-        fine, coarse = pair
-        if scores is not None:
-            flush_gathered()
-            push_scores(level_id, fine, coarse)
-            return
-        if n_comp == 1:
-            fine, coarse = fine[0], (None if coarse is None else coarse[0])
-        # Resident chunks are gathered and handed over in ONE call of the C ABI at the end (mlmc_accum_estimate: reset +
-        # pushes + finalize); as soon as a host chunk shows up -- it is staged through a reused device buffer and has to be
-        # pushed at once -- everything goes through push() in arrival order.
-        resident = (not pushed_directly and getattr(fine, "is_cuda", False) and fine.is_contiguous()
-                    and (coarse is None or (getattr(coarse, "is_cuda", False) and coarse.is_contiguous())))
-        if resident:
-            gathered.append((level_id, fine, coarse))
-            return
-        flush_gathered()
-        acc.push(level_id, fine, coarse)
+class _ScoreRows:
+    """The normal scores of [M, n] device rows under M marginals (simple_distribution._scores_into); the problem arguments are
+    built with the first rows.  `what` names the caller in their error messages."""
 
-    # component_covariance(scores=...): the pair becomes its normal scores plus a row of ones, block by block of a fixed number
-    # of columns, in one workspace per side that every block reuses (the library's stream orders a block's push before the
-    # next block's scores).  The row of ones sits behind the M score rows of a block, so it is rewritten when the width changes.
-    scores = quantity._scores if isinstance(quantity, _ComponentCovNode) else None
-    score_ws = {}
+    def __init__(self, scores, what):
+        self._scores, self._what = scores, what
+        self._head = self._keep = self._buf = self._width = self._nb = None
 
-    def push_scores(level_id, fine, coarse):
+    def _into(self, fine, coarse, n, ld_in, z_fine, z_coarse):
+        from ..tool import simple_distribution
+        if self._head is None:
+            self._head, self._keep = simple_distribution._scores_problem_args(self._scores, self._what)
+        simple_distribution._scores_into(self._head, fine, coarse, n, ld_in, z_fine, z_coarse, n)
+
+    def chunk(self, fine, coarse, n):
+        """The scores of a whole chunk in a workspace of its own (16 M n bytes), which the caller releases.  -> fine, coarse | None"""
+        import torch
+        ws = torch.empty((2, len(self._scores), n), dtype=torch.float64, device=fine.device)
+        torch.cuda.current_stream(fine.device).synchronize()     # the library reads and writes on its own stream
+        self._into(fine, coarse, n, n, ws[0], None if coarse is None else ws[1])
+        return ws[0], (None if coarse is None else ws[1])
+
+    def blocks(self, fine, coarse, dev):
+        """Generator of (fine, coarse | None) [M + 1, nc]: the scores of a pair plus a row of ones, block by block of a fixed number
+        of columns (score_block_columns), in one workspace per side that every block reuses -- each block must be pushed before the
+        next one is asked for (the library's stream orders a block's push before the next block's scores).  The row of ones sits
+        behind the M score rows of a block, so it is rewritten when the width changes.  A host chunk is uploaded first, once."""
         import torch
         from .. import _lib
-        from ..tool import simple_distribution
-        M = len(scores)
-        if "head" not in score_ws:
-            score_ws["head"], score_ws["keep"] = simple_distribution._scores_problem_args(scores, "component_covariance")
-            score_ws["nb"] = score_block_columns(M)
-            score_ws["width"] = None
-        nb = score_ws["nb"]
-        dev = torch.device("cuda", _lib_device())
-
-        def on_device(x):
-            if x is None:
-                return None
-            if isinstance(x, np.ndarray):                            # a host chunk is uploaded first, once
-                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
-            return x.contiguous()
-        fine, coarse = on_device(fine), on_device(coarse)
+        M = len(self._scores)
+        if self._buf is None:
+            self._nb = score_block_columns(M)
+            self._buf = torch.empty((2, (M + 1) * self._nb), dtype=torch.float64, device=dev)
+        nb = self._nb
+        fine = _device_rows(fine, M, dev)[0]
+        coarse = None if coarse is None else _device_rows(coarse, M, dev)[0]
         n = int(fine.shape[-1])
-        if "buf" not in score_ws:
-            score_ws["buf"] = torch.empty((2, (M + 1) * nb), dtype=torch.float64, device=dev)
-        buf = score_ws["buf"]
         for c0 in range(0, n, nb):
             nc = min(nb, n - c0)
-            z = [buf[side, :(M + 1) * nc].view(M + 1, nc) for side in range(2)]
-            if score_ws["width"] != nc:
+            z = [self._buf[side, :(M + 1) * nc].view(M + 1, nc) for side in range(2)]
+            if self._width != nc:
                 _lib.check(_lib.lib().mlmc_synchronize())           # earlier pushes have read the workspace
                 z[0][M].fill_(1.0)
                 z[1][M].fill_(1.0)
-                score_ws["width"] = nc
+                self._width = nc
             torch.cuda.current_stream(dev).synchronize()            # the library reads and writes on its own stream
-            simple_distribution._scores_into(score_ws["head"], fine[:, c0:], None if coarse is None else coarse[:, c0:], nc, n,
-                                             z[0], None if coarse is None else z[1], nc)
-            acc.push(level_id, z[0], None if coarse is None else z[1])
+            self._into(fine[:, c0:], None if coarse is None else coarse[:, c0:], nc, n, z[0], None if coarse is None else z[1])
+            yield z[0], (None if coarse is None else z[1])
 
-    gathered = []
-    pushed_directly = False
 
-    def flush_gathered():
-        nonlocal pushed_directly
-        pushed_directly = True
-        for item in gathered:
-            acc.push(*item)
-        gathered.clear()
+class _LevelSink:
+    """Where the (level, pair) stream of an estimate ends: a pooled accumulator, taken with the first pair.  Resident pairs are
+    gathered and handed over in ONE call of the C ABI at the end (mlmc_accum_estimate: reset + pushes + finalize); as soon as a host
+    chunk shows up -- it is staged through a reused device buffer and has to be pushed at once -- or the pairs become normal scores,
+    everything goes through push() in arrival order."""
 
-    def flush_level(level_id, pairs, keys):
-        if not pairs:
+    def __init__(self, target, walk, vec_size, variance):
+        self._target, self._n_levels, self._dev, self._vec_size = target, walk.n_levels, walk.dev, vec_size
+        self._mean_only = not variance
+        self._scores = None if target.scores is None else _ScoreRows(target.scores, "component_covariance")
+        self._acc = self.n_comp = None
+        self._gathered = []
+        self._pushed_directly = False
+
+    def push(self, level_id, pair):
+        """pair: (fine [M, n], coarse [M, n] | None), device tensors or host arrays, or None"""
+        if pair is None:
             return
-        merged = _merge_level(pairs) if (consolidate and len(pairs) > 1) else None
-        if merged is None:
+        if self._acc is None:
+            self.n_comp = pair[0].shape[0] + (1 if self._scores is not None else 0)
+            if pair[0].shape[-1] > 0:
+                assert self.n_comp * self._target.rows_out == self._vec_size
+            self._acc = _acc_pool.take(self._target.fn, self._n_levels, self._target.mode, self.n_comp, mean_only=self._mean_only)
+            if self._target.mode == engine.LevelAccumulator.COMPONENT_COV:
+                self._acc.set_shift(self._target.shift)          # this estimate's shift (the pooled one may carry another)
+        if pair[0].shape[-1] == 0:                               # empty chunk / every sample deselected
+            return
+        fine, coarse = pair
+        if self._scores is not None:
+            self._flush()
+            for z_fine, z_coarse in self._scores.blocks(fine, coarse, self._dev):
+                self._acc.push(level_id, z_fine, z_coarse)
+            return
+        if self.n_comp == 1:
+            fine, coarse = fine[0], (None if coarse is None else coarse[0])
+        resident = (not self._pushed_directly and getattr(fine, "is_cuda", False) and fine.is_contiguous()
+                    and (coarse is None or (getattr(coarse, "is_cuda", False) and coarse.is_contiguous())))
+        if resident:
+            self._gathered.append((level_id, fine, coarse))
+            return
+        self._flush()
+        self._acc.push(level_id, fine, coarse)
+
+    def _flush(self):
+        self._pushed_directly = True
+        for item in self._gathered:
+            self._acc.push(*item)
+        self._gathered.clear()
+
+    def finish(self, group):
+        """-> n, n_rm [L], sums, sums_sq [L, K]; the accumulator goes back to the pool"""
+        if self._acc is None:
+            raise Exception("All samples were masked")
+        if self._gathered and not self._pushed_directly:
+            out = self._acc.estimate(self._gathered, group=group)
+        else:
+            self._flush()
+            out = self._acc.finalize(group=group)
+        _acc_pool.give(self._target.fn, self._n_levels, self._target.mode, self.n_comp, self._acc, mean_only=self._mean_only)
+        return out
+
+
+def _on_device_subsample(pair, target, level_id):
+    """the pair, or its share of the sub-sample of Quantity.subsample"""
+    if target.subsample_params is not None and pair is not None and pair[0].shape[-1] > 0:
+        return _subsample_on_device(pair, target.subsample_params[level_id])
+    return pair
+
+
+def _level_pairs(target, walk):
+    """Generator of (level id, (fine [M, n], coarse [M, n] | None)) of an estimate, in the order in which they are pushed: the
+    levels that are resident as ONE tensor, in sorted order; then the levels that the streaming feed lands as one tensor; then the
+    remaining chunks in storage order, read ahead by a helper thread while this thread uploads and launches.  A level that arrives
+    in several resident chunks (HDF5 files deliver levels that way) is concatenated into ONE tensor before it is handed on -- once;
+    the level-wide entry replaces the chunk entries in the cache -- so every estimate, the first one included, is one push per level
+    and gives bit-identical sums.  Closing the generator stops the read-ahead."""
+    level_ids = {int(l) for l in walk.storage_q.level_ids()}
+    done = set()
+    if walk.use_cache:
+        for level_id in sorted(level_ids):
+            item = _device_cache.get((walk.ident, level_id, "level", walk.n_collected[level_id]))
+            if item is not None:
+                done.add(level_id)
+                yield level_id, _on_device_subsample((item[0], item[1]), target, level_id)   # the whole level is one resident chunk
+    if done >= level_ids:
+        return      # (a storage that cuts its levels into hundreds of chunks: its chunk specs need not even be generated)
+    specs = [cs for cs in walk.storage_q.chunks() if int(cs.level_id) not in done]
+    first_raw, to_read = {}, []
+    if walk.plan is not None and not hasattr(getattr(walk.plan.leaf, "_storage", None), "device_row"):
+        for level_id, pair in _streamed_level_pairs(target, walk, specs, first_raw):
+            done.add(level_id)
+            yield level_id, pair
+        specs = [cs for cs in specs if int(cs.level_id) not in done]
+        to_read = _chunks_to_read(walk, specs, first_raw)
+    consolidate = walk.use_cache and target.subsample_params is None
+    prefetch = _ChunkPrefetcher(walk.plan.leaf, to_read) if len(to_read) > 1 else None
+    waiting = {id(cs) for cs in to_read} if prefetch is not None else ()
+    try:
+        for level_id, level_specs in itertools.groupby(specs, key=lambda cs: int(cs.level_id)):
+            level_specs, pairs = list(level_specs), []
+            for chunk_spec in level_specs:
+                raw = prefetch.get(chunk_spec) if id(chunk_spec) in waiting else first_raw.pop(id(chunk_spec), None)
+                pair = _chunk_for_device(target.source, walk.plan, chunk_spec, walk.n_collected, walk.use_cache, raw)
+                pairs.append(_on_device_subsample(pair, target, level_id))
+            merged = _merge_level(pairs) if (consolidate and len(pairs) > 1) else None
+            if merged is not None:
+                _device_cache.put_tensors((walk.ident, level_id, "level", walk.n_collected[level_id]), merged[0], merged[1],
+                                          owner=walk.owner)
+                for chunk_spec in level_specs:
+                    _device_cache.drop(_chunk_key(walk.ident, chunk_spec, walk.n_collected))
+                pairs = [merged]
             for pair in pairs:
-                push_pair(level_id, pair)
-            return
-        _device_cache.put_tensors((ident, level_id, "level", n_collected[level_id]), merged[0], merged[1], owner=owner)
-        for key in keys:
-            _device_cache.drop(key)
-        push_pair(level_id, merged)
+                yield level_id, pair
+    finally:
+        if prefetch is not None:
+            prefetch.close()
 
+
+def _streamed_level_pairs(target, walk, specs, first_raw):
+    """Levels of a lowered tree that the storage hands out in several chunks of [n][2][M] records: the whole level becomes ONE
+    device tensor in the storage's layout -- resident from an earlier estimate of any quantity over this storage, or streamed now
+    through pinned staging blocks (_LevelStreamer) -- and the tree runs as ONE k_expr launch over it.  A first chunk that was read
+    on the way for a level that does not qualify is left in `first_raw`."""
+    plan, n_collected, use_cache = walk.plan, walk.n_collected, walk.use_cache
+    by_level = collections.OrderedDict()
+    for cs in specs:
+        by_level.setdefault(int(cs.level_id), []).append(cs)
+    candidates = [(level_id, level_specs) for level_id, level_specs in by_level.items()
+                  if not (use_cache and any(_chunk_key(walk.ident, cs, n_collected) in _device_cache for cs in level_specs))]
+    for level_id, blk in _level_blocks_on_device(plan, walk.owner, candidates, n_collected, use_cache, first_raw):
+        t, sn, sw, n, width = blk
+        fine, coarse, _ = plan.evaluate([t[r:] for r in plan.in_rows], has_coarse=(width == 2), n=n, sample_stride=sn,
+                                        side_stride=max(sw, 1), sync=not use_cache)
+        if use_cache:
+            _device_cache.put_tensors((walk.ident, level_id, "level", n_collected[level_id]), fine, coarse, owner=walk.owner)
+        yield level_id, _on_device_subsample((fine, coarse), target, level_id)
+
+
+def _chunks_to_read(walk, specs, first_raw):
+    """The chunks of a lowered tree that have to come from the host storage (neither their result rows nor their stored block are
+    resident), for the read-ahead of _ChunkPrefetcher."""
+    to_read = []
+    if _ChunkPrefetcher.enabled():
+        have, owner = _device_cache, walk.owner
+        for cs in specs:
+            key = _chunk_key(walk.ident, cs, walk.n_collected)
+            resident = walk.use_cache and (key in have or (("block", id(owner)) + key[1:]) in have
+                                           or all((("row", id(owner)) + key[1:] + (r,)) in have for r in walk.plan.in_rows))
+            if not resident and id(cs) not in first_raw:
+                to_read.append(cs)
+    return to_read
+
+
+def _estimate_mean(quantity, group, variance):
+    target = _estimate_target(quantity, variance)
+    walk = _walk_setup(quantity, target.source)
+    fn, lin_fn, n_levels, rows_out = target.fn, target.lin_fn, walk.n_levels, target.rows_out
     memo_key = None
-    if n_collected is not None and subsample_params is None and group is None and not engine._dist_group_active(group):
-        memo_key = (ident, n_collected, _cache_generation)
-    if not variance and mode == engine.LevelAccumulator.MOMENTS and lin_fn is None and fn is not None:
-        short = _sums_from_linearized_memo(fn, memo_key, owner)
+    if walk.n_collected is not None and target.subsample_params is None and group is None and not engine._dist_group_active(group):
+        memo_key = (walk.ident, walk.n_collected, _cache_generation)
+    if not variance and target.mode == engine.LevelAccumulator.MOMENTS and lin_fn is None and fn is not None:
+        short = _sums_from_linearized_memo(fn, memo_key, walk.owner)
         if short is not None:
             n_samples, n_rm_samples, sums, n_comp = short
             return _finish_estimate(quantity, fn, n_levels, n_comp, rows_out, n_samples, n_rm_samples, sums,
                                     np.full_like(sums, np.nan))
-
-    level_done = set()
-    if use_cache:
-        for level_id in sorted({int(l) for l in level_ids}):
-            item = _device_cache.get((ident, level_id, "level", n_collected[level_id]))
-            if item is not None:
-                level_done.add(level_id)
-                pair = (item[0], item[1])
-                if subsample_params is not None and pair[0].shape[-1] > 0:   # the whole level is one resident chunk
-                    pair = _subsample_on_device(pair, subsample_params[level_id])
-                push_pair(level_id, pair)
-    # (a storage that cuts its levels into hundreds of chunks: when every level is served level-wide from HBM the chunk
-    # specs need not even be generated)
-    all_levels = {int(l) for l in level_ids}
-    specs = [] if level_done >= all_levels else [cs for cs in storage_q.chunks() if int(cs.level_id) not in level_done]
-    host_storage = plan is not None and not hasattr(getattr(plan.leaf, "_storage", None), "device_row")
-    # Levels of a lowered tree that the storage hands out in several chunks of [n][2][M] records: the whole level becomes
-    # ONE device tensor in the storage's layout -- resident from an earlier estimate of any quantity over this storage, or
-    # streamed now through pinned staging blocks (_LevelStreamer) -- and the tree runs as ONE k_expr launch over it.
-    first_raw = {}
-    if host_storage:
-        by_level = collections.OrderedDict()
-        for cs in specs:
-            by_level.setdefault(int(cs.level_id), []).append(cs)
-        candidates = [(level_id, level_specs) for level_id, level_specs in by_level.items()
-                      if not (use_cache and any(_chunk_key(ident, cs, n_collected) in _device_cache for cs in level_specs))]
-        for level_id, blk in _level_blocks_on_device(plan, owner, candidates, n_collected, use_cache, first_raw):
-            t, sn, sw, n, width = blk
-            fine, coarse, _ = plan.evaluate([t[r:] for r in plan.in_rows], has_coarse=(width == 2), n=n, sample_stride=sn,
-                                            side_stride=max(sw, 1), sync=not use_cache)
-            if use_cache:
-                _device_cache.put_tensors((ident, level_id, "level", n_collected[level_id]), fine, coarse, owner=owner)
-            pair = (fine, coarse)
-            if subsample_params is not None and n > 0:
-                pair = _subsample_on_device(pair, subsample_params[level_id])
-            push_pair(level_id, pair)
-            level_done.add(level_id)
-        specs = [cs for cs in specs if int(cs.level_id) not in level_done]
-    # remaining chunks of a lowered tree that have to come from the host storage (neither their result rows nor their stored
-    # block are resident): read ahead by a helper thread while this thread uploads and launches (_ChunkPrefetcher)
-    to_read = []
-    if host_storage and _ChunkPrefetcher.enabled():
-        have = _device_cache
-        for cs in specs:
-            key = _chunk_key(ident, cs, n_collected)
-            resident = use_cache and (key in have or (("block", id(owner)) + key[1:]) in have
-                                      or all((("row", id(owner)) + key[1:] + (r,)) in have for r in plan.in_rows))
-            if not resident and id(cs) not in first_raw:
-                to_read.append(cs)
-    prefetch = _ChunkPrefetcher(plan.leaf, to_read) if len(to_read) > 1 else None
-    waiting = {id(cs) for cs in to_read} if prefetch is not None else set()
-    current, pairs, keys = None, [], []
-    try:
-        for chunk_spec in specs:
-            level_id = int(chunk_spec.level_id)
-            if level_id != current:
-                flush_level(current, pairs, keys)
-                current, pairs, keys = level_id, [], []
-            raw = prefetch.get(chunk_spec) if id(chunk_spec) in waiting else first_raw.pop(id(chunk_spec), None)
-            pair = _chunk_for_device(source, plan, chunk_spec, n_collected, use_cache, raw)     # (fine [M, n], coarse | None)
-            if pair is not None and subsample_params is not None and pair[0].shape[-1] > 0:
-                pair = _subsample_on_device(pair, subsample_params[level_id])
-            pairs.append(pair)
-            keys.append(_chunk_key(ident, chunk_spec, n_collected))
-        flush_level(current, pairs, keys)
-    finally:
-        if prefetch is not None:
-            prefetch.close()
-    if acc is None:
-        raise Exception("All samples were masked")
-    if gathered and not pushed_directly:
-        n_samples, n_rm_samples, sums, sums_sq = acc.estimate(gathered, group=group)
-    else:
-        flush_gathered()
-        n_samples, n_rm_samples, sums, sums_sq = acc.finalize(group=group)
-    _acc_pool.give(fn, n_levels, mode, n_comp, acc, mean_only=not variance)
+    sink = _LevelSink(target, walk, quantity.size(), variance)
+    with contextlib.closing(_level_pairs(target, walk)) as pairs:    # (a push that raises still stops the read-ahead thread)
+        for level_id, pair in pairs:
+            sink.push(level_id, pair)
+    n_samples, n_rm_samples, sums, sums_sq = sink.finish(group)
     if int(np.sum(n_samples)) == 0:
         raise Exception("All samples were masked")
     if lin_fn is not None:
         if memo_key is not None:
             lin_fn.__dict__["_lin_memo"] = dict(key=memo_key, n=n_samples.copy(), n_rm=n_rm_samples.copy(), sums=sums.copy(),
-                                                n_comp=n_comp, K=fn.size, R=lin_fn.size, owner=_BlockMeta._ref(owner))
-        sums = linearize.covariance_sums_from_moment_sums(lin_fn, sums, n_comp)
+                                                n_comp=sink.n_comp, K=fn.size, R=lin_fn.size, owner=_BlockMeta._ref(walk.owner))
+        sums = linearize.covariance_sums_from_moment_sums(lin_fn, sums, sink.n_comp)
         sums_sq = np.full_like(sums, np.nan)                       # mean only: the variances were not asked for
         fn = lin_fn
-    return _finish_estimate(quantity, fn, n_levels, n_comp, rows_out, n_samples, n_rm_samples, sums, sums_sq)
+    return _finish_estimate(quantity, fn, n_levels, sink.n_comp, rows_out, n_samples, n_rm_samples, sums, sums_sq)
 
 
 BOOTSTRAP_FAMILIES = ("Legendre", "Monomial", "Fourier")     # moments families of the batched bootstrap (mlmc_bootstrap_create)
@@ -1415,9 +1490,9 @@ def bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
 
 
 def _bootstrap_moments(quantity, moments_fn, n_replicates, sample_vector, seed):
-    M = int(quantity.size())
-    return _bootstrap_walk(quantity, "acc", lambda n_levels: (id(moments_fn), M, n_levels, int(n_replicates)),
-                           lambda n_levels: engine.BootstrapAccumulator(moments_fn, M, n_levels, n_replicates), moments_fn,
+    M, walk = int(quantity.size()), _walk_setup(quantity)
+    return _bootstrap_walk(quantity, walk, ("acc", id(moments_fn), M, walk.n_levels, int(n_replicates)),
+                           lambda: engine.BootstrapAccumulator(moments_fn, M, walk.n_levels, n_replicates),
                            n_replicates, sample_vector, seed)
 
 
@@ -1432,8 +1507,9 @@ def bootstrap_component_moments(quantity, moments_fns, n_replicates, sample_vect
         M, R = len(fns), int(fns[0].size)
         if int(quantity.size()) != M:
             raise ValueError("bootstrap_component_moments: {} moments objects for {} components".format(M, quantity.size()))
-        return _bootstrap_walk(quantity, "acc_comp", lambda n_levels: (tuple(id(fn) for fn in fns), R, n_levels, int(n_replicates)),
-                               lambda n_levels: engine.ComponentBootstrapAccumulator(fns, R, n_levels, n_replicates), fns,
+        walk = _walk_setup(quantity)
+        return _bootstrap_walk(quantity, walk, ("acc_comp", tuple(id(fn) for fn in fns), R, walk.n_levels, int(n_replicates)),
+                               lambda: engine.ComponentBootstrapAccumulator(fns, R, walk.n_levels, n_replicates),
                                n_replicates, sample_vector, seed)
 
 
@@ -1451,108 +1527,60 @@ def bootstrap_component_covariance(quantity, n_replicates, sample_vector, seed, 
     (fine and coarse), which is released when the chunk is done (one wait for the device per chunk on this route).  No shift can
     be given with scores.
     -> n [B, L] kept counts, s1 [B, L, M], s2 [B, L, M, M] (bitwise symmetric)"""
-    if not isinstance(quantity, qmod.Quantity) or isinstance(quantity, (_MomentsNode, _CovarianceNode, _ComponentCovNode)):
-        raise TypeError("bootstrap_component_covariance: needs a Quantity whose samples are component values, got {}".format(
-            type(quantity).__name__))
-    M = int(quantity.size())
-    if M > engine.ComponentCovBootstrapAccumulator.MAX_COMPONENTS:
-        raise ValueError("bootstrap_component_covariance: {} components, at most {} are supported".format(
-            M, engine.ComponentCovBootstrapAccumulator.MAX_COMPONENTS))
-    if scores is not None:
-        scores = list(scores)
-        if shift is not None:
-            raise ValueError("bootstrap_component_covariance: scores and shift exclude each other")
-        if len(scores) != M:
-            raise ValueError("bootstrap_component_covariance: {} score distributions for {} components".format(len(scores), M))
-        if len({d.n_intervals for d in scores}) != 1 or len({d._gauss_degree for d in scores}) != 1:
-            raise ValueError("bootstrap_component_covariance: every distribution must use the same quadrature")
-    if shift is not None:
-        shift = np.array(shift, dtype=np.float64)
-        if shift.shape != (M,):
-            raise ValueError("bootstrap_component_covariance: shift of shape {}, expected ({},)".format(shift.shape, M))
-        if not np.all(np.isfinite(shift)):
-            raise ValueError("bootstrap_component_covariance: the shift must be finite")
-    chunk_map = None
-    if scores is not None:
-        state = {}
-
-        def chunk_map(fine, coarse, n):
-            import torch
-            from ..tool import simple_distribution
-            if "head" not in state:
-                state["head"], state["keep"] = simple_distribution._scores_problem_args(scores, "bootstrap_component_covariance")
-            ws = torch.empty((2, M, n), dtype=torch.float64, device=fine.device)      # 16 M n bytes
-            torch.cuda.current_stream(fine.device).synchronize()     # the library reads and writes on its own stream
-            simple_distribution._scores_into(state["head"], fine, coarse, n, n, ws[0], None if coarse is None else ws[1], n)
-            return ws[0], (None if coarse is None else ws[1])
+    M, shift, scores = _component_args("bootstrap_component_covariance", quantity, shift, scores,
+                                       engine.ComponentCovBootstrapAccumulator.MAX_COMPONENTS, limit_first=True)
+    score_rows = None if scores is None else _ScoreRows(scores, "bootstrap_component_covariance")
     with _estimate_lock:
-        return _bootstrap_walk(quantity, "acc_xcov", lambda n_levels: ("xcov", M, n_levels, int(n_replicates)),
-                               lambda n_levels: engine.ComponentCovBootstrapAccumulator(M, n_levels, n_replicates), scores,
-                               n_replicates, sample_vector, seed, setup=lambda acc: acc.set_shift(shift), chunk_map=chunk_map)
+        walk = _walk_setup(quantity)
+        return _bootstrap_walk(quantity, walk, ("acc_xcov", M, walk.n_levels, int(n_replicates)),
+                               lambda: engine.ComponentCovBootstrapAccumulator(M, walk.n_levels, n_replicates),
+                               n_replicates, sample_vector, seed, setup=lambda acc: acc.set_shift(shift), score_rows=score_rows)
 
 
-def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sample_vector, seed, setup=None, chunk_map=None):
-    """One bootstrap pass over the stored chunks of `quantity` into the pooled accumulator of `slot` (reused when make_key(n_levels)
-    matches the last call's, else replaced by make_acc(n_levels)); `alive` is kept with it.  setup(acc): called once before the
-    first chunk; chunk_map(fine, coarse, n) -> (fine, coarse): device rows made for this chunk, accumulated in place of the
-    chunk's own and released after a wait for their accumulation.  -> the accumulator's finalize()"""
+def _bootstrap_walk(quantity, walk, key, make_acc, n_replicates, sample_vector, seed, setup=None, score_rows=None):
+    """One bootstrap pass over the stored chunks of `quantity` (walk = its _walk_setup) into the pooled accumulator of the slot key[0]:
+    the last call's when its key was `key`, else make_acc() replaces it (an accumulator keeps its moments objects alive, so the ids
+    in a key stay unique).  setup(acc): called once before the first chunk; score_rows: a _ScoreRows whose scores of each chunk are
+    accumulated in place of the chunk's own rows and released after a wait for their accumulation.  -> the accumulator's finalize()"""
     import torch
-    cache_clear()
-    storage_q = quantity.get_quantity_storage()
-    n_levels = int(np.max(storage_q.level_ids())) + 1
-    n_level = [int(v) for v in storage_q.n_collected()]
-    plan = lowering.plan_for(quantity) if _device_tree_enabled() else None
-    try:
-        n_collected = _level_stamps(storage_q)
-    except Exception:
-        n_collected = None
-    use_cache = _DeviceChunkCache.budget() > 0 and n_collected is not None and not getattr(quantity, "_volatile", False)
-    dev = torch.device("cuda", _lib_device())
+    from .. import _lib
+    n_level = [int(v) for v in walk.storage_q.n_collected()]
     M = int(quantity.size())
-    key = make_key(n_levels)
-    kept = _bootstrap_pool.pop(slot, None)                        # the last accumulator (64 MiB of scratch, pinned size blocks)
+    kept = _bootstrap_pool.pop(key[0], None)                      # the last accumulator (64 MiB of scratch, pinned size blocks)
     if kept is not None and kept[0] == key:
         acc = kept[1]
         acc.reset()
     else:
         if kept is not None:
             kept[1].close()
-        acc = make_acc(n_levels)
+        acc = make_acc()
     chunk_no = collections.Counter()
-    copied = False
     pushed = 0
     try:
         if setup is not None:
             setup(acc)
-        for chunk_spec in storage_q.chunks():
+        for chunk_spec in walk.storage_q.chunks():
             level = int(chunk_spec.level_id)
             c = chunk_no[level]
             chunk_no[level] += 1
-            fine, coarse = _chunk_for_device(quantity, plan, chunk_spec, n_collected, use_cache)
+            fine, coarse = _chunk_for_device(quantity, walk.plan, chunk_spec, walk.n_collected, walk.use_cache)
             n = fine.shape[-1]
             if n == 0:
                 continue
-            pair = []
-            for t in (fine, coarse):
-                if t is None:
-                    pair.append(None)
-                    continue
-                if not isinstance(t, torch.Tensor):              # host chunk (over the cache budget): upload, as the gather path does
-                    t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
-                t2 = t.to(device=dev, dtype=torch.float64).reshape(M, n).contiguous()
-                copied = copied or t2.data_ptr() != t.data_ptr()
-                pair.append(t2)
+            # (a host chunk -- over the cache budget -- is uploaded, as the gather path does)
+            fine, copied = _device_rows(fine, M, walk.dev)
+            if coarse is not None:
+                coarse, copied_c = _device_rows(coarse, M, walk.dev)
+                copied = copied or copied_c
             if copied:
-                torch.cuda.current_stream(dev).synchronize()     # the library reads them on its own stream
-                copied = False
+                torch.cuda.current_stream(walk.dev).synchronize()     # the library reads them on its own stream
             sizes = bootstrap_sizes(seed, level, c, sample_vector[level], n_level[level], n, n_replicates)
-            if chunk_map is not None:
-                pair = chunk_map(pair[0], pair[1], n)
-            acc.accum(level, pair[0], pair[1], sizes, seed, bootstrap_stream(level, c))
-            if chunk_map is not None:                            # its rows are a workspace of this chunk: released once they are read
-                from .. import _lib
+            if score_rows is not None:
+                fine, coarse = score_rows.chunk(fine, coarse, n)
+            acc.accum(level, fine, coarse, sizes, seed, bootstrap_stream(level, c))
+            if score_rows is not None:                           # its rows are a workspace of this chunk: released once they are read
                 _lib.check(_lib.lib().mlmc_synchronize())
-                acc._keepalive.pop()
+                acc.release_last()
             pushed += 1
         if pushed == 0:
             raise Exception("All samples were masked")
@@ -1560,7 +1588,7 @@ def _bootstrap_walk(quantity, slot, make_key, make_acc, alive, n_replicates, sam
     except BaseException:
         acc.close()
         raise
-    _bootstrap_pool[slot] = (key, acc, alive)                     # (the moments objects kept alive: their ids stay unique)
+    _bootstrap_pool[key[0]] = (key, acc)
     return out
 
 

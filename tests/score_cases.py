@@ -38,6 +38,16 @@ def multipliers(rate):
     return np.array([np.log(mass), rate])
 
 
+def closed_distribution(rate, domain, quad=(64, 21)):
+    """the closed-form marginal as a distribution object with its multipliers set (no solve, no device work)"""
+    import mlmc_amd
+    from mlmc_amd.tool import simple_distribution as sd
+    d = sd.SimpleDistribution(mlmc_amd.Legendre(2, domain), np.stack([np.eye(2)[0], np.ones(2)], axis=1), domain=domain)
+    d.multipliers, d._moment_errs = multipliers(rate), np.ones(2)
+    d.n_intervals, d._gauss_degree = quad
+    return d
+
+
 def closed_cdf(rate, domain, x):
     a, b = domain
     t1 = 2.0 * (np.asarray(x, dtype=np.float64) - a) / (b - a)                        # t + 1

@@ -59,12 +59,7 @@ def _cycle(group, M):
 
 def _closed(rate, dom, quad=(64, 21)):
     """the truncated exponential of tests/score_cases.py as a distribution object"""
-    import mlmc_amd
-    from mlmc_amd.tool import simple_distribution as sd
-    d = sd.SimpleDistribution(mlmc_amd.Legendre(2, dom), np.stack([np.eye(2)[0], np.ones(2)], axis=1), domain=dom)
-    d.multipliers, d._moment_errs = sk.multipliers(rate), np.ones(2)
-    d.n_intervals, d._gauss_degree = quad
-    return d
+    return sk.closed_distribution(rate, dom, quad)
 
 
 def _closed_three(quad=(64, 21)):
