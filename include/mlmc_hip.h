@@ -43,7 +43,8 @@ extern "C" {
                               *    mlmc_density_sample_batch, mlmc_density_sample_joint_batch, mlmc_density_scores_batch,
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
                               *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch,
-                              *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov */
+                              *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov,
+                              *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -646,6 +647,52 @@ int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const doub
 int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                                 const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
                                 double *f_out, double *z_out, double *u_out, int mem_kind);
+
+/* ---- aggregates of joint scenarios (scenario.hip) -- added within 8 ----------------------------------------------------
+ * Functions of the M components of one scenario, once per scenario column.  x [S][M][ld]: S >= 1 sets of M >= 1 component rows,
+ * columns 0 .. n-1 are used (n >= 0, ld >= n); agg [S][Q][ld_out], ld_out >= n, columns >= n are not touched; both host or device
+ * arrays by mem_kind.  Q = A + the number of bits set in extras; the rows of a set are the A linear rows, then the extra rows in
+ * the order MAX, MIN, COUNT, ARGMAX, ARGMIN (the order of the bits).  Integer-valued rows are exact doubles, so every row goes
+ * through mlmc_rows_weighted_sums and mlmc_percentiles_rows unchanged.
+ *   linear row a (W [A][M] host, finite, A >= 0):  acc = +0.0, then for m = 0 .. M-1 ascending  acc = acc + (W[a][m] * x[m][j]):
+ *     one rounded product, one rounded sum, no FMA.  Plain IEEE: a NaN draw gives NaN, 0 * inf gives NaN.  With W[a] = e_m the row
+ *     equals x[m] under == (a -0.0 comes back as +0.0: +0 + (-0) = +0, the one difference in bits).
+ *   MAX, ARGMAX over the components with members[m] != 0 (members [M] host uint8; NULL: all): ARGMAX is np.argmax of the member
+ *     subvector mapped back to the component index -- the first NaN if there is one, else the first index attaining the maximum
+ *     under > -- and MAX is x at that index, bit for bit (of -0.0 and +0.0 the first stays).  MIN, ARGMIN: the same under <.
+ *   COUNT (lower, upper [M] host, either may be NULL = no limit on that side; -inf / +inf likewise): component m is inside when
+ *     lower[m] < x && x < upper[m]; count[j] = the number of components with at least one finite limit that are not inside, so
+ *     a NaN draw of such a component counts, and count == 0 is the box event of mlmc_copula_box_prob_batch.
+ * A value depends on its own column of its own set, on W, the limits and the members alone: not on n, ld, ld_out, S, the position
+ * of the set, the alignment of a row, the launch geometry or the blocks a caller walks the columns in (columns [50, 150) of a call
+ * equal a call on that slice); host and device arrays give the same bits.
+ * Errors: S < 1, M < 1, n < 0, A < 0, ld < n, ld_out < n, n > 2^38, null x / agg where they are not empty (W with A > 0), bad mem_kind, unknown bits in
+ * extras, a weight that is not finite (names row and component), an extreme row without a member, MLMC_AGG_COUNT with lower and
+ * upper both NULL, a NaN limit (names the component).  n = 0 and Q = 0 are no-ops.
+ * One lane per column, the components in order with a row stride (coalesced at any alignment), up to 8 linear accumulators in
+ * registers per pass over x, further linear rows in further passes; no atomics; one host wait. */
+enum { MLMC_AGG_MAX = 1, MLMC_AGG_MIN = 2, MLMC_AGG_COUNT = 4, MLMC_AGG_ARGMAX = 8, MLMC_AGG_ARGMIN = 16 };
+int mlmc_scenario_aggregates(const double *x, int64_t S, int32_t M, int64_t n, int64_t ld, const double *W, int32_t A,
+                             const uint8_t *members, const double *lower, const double *upper, int32_t extras, double *agg,
+                             int64_t ld_out, int mem_kind);
+/* Weighted statistics of rows in one pass -- added within 8.  y [n_rows][ld] (columns 0 .. n-1) and the weights f [n] (NULL: every
+ * weight is 1) are host or device arrays by mem_kind; c [n_rows] (NULL: zeros; finite) and the thresholds t [n_rows][P] (P >= 0, no
+ * NaN) are host.  With d = y - c[r], over the columns where neither y nor f is NaN:
+ *   n_used [n_rows], n_skipped [n_rows] host int64: those columns and the others;
+ *   sums [n_rows][3] host: sum f, sum (f d), sum ((f d) d);
+ *   tail_sums [n_rows][P][2] host: sum f 1, sum (f d) 1, the indicator y >= t for MLMC_TAIL_UPPER, y <= t for MLMC_TAIL_LOWER.
+ * Give the mean of a first call as c of a second: the second moment is then a sum of terms of the size of the result.
+ * Fixed order: with per = max(2048, ceil(ceil(n / 1024) / 256) * 256) columns per block, thread t < 256 of block b adds the columns
+ * b per + t, + 256, ... ascending from +0; within a wave v_l += v_(l ^ 32), then ^ 16, 8, 4, 2, 1; the four waves ((w0 + w1) + w2) + w3;
+ * the blocks ascending from +0.  A row's bits depend on its data, c, t and n alone: not on n_rows, its position, ld or mem_kind.
+ * No floating-point atomics.  A negative or infinite weight in a used column is an error of the call, found on the device in the
+ * same pass and reported after the wait.  Other errors: a negative count, ld < n, null y (unless empty) / n_used / n_skipped / sums (t and
+ * tail_sums with P > 0), bad tail or mem_kind, a centre that is not finite, a NaN threshold.  n_rows = 0 and n = 0 are no-ops that
+ * write zeros.  Thresholds run 8 per pass over the rows; one host wait. */
+enum { MLMC_TAIL_UPPER = 0, MLMC_TAIL_LOWER = 1 };
+int mlmc_rows_weighted_sums(const double *y, int64_t n_rows, int64_t n, int64_t ld, const double *f, const double *c, const double *t,
+                            int32_t P, int32_t tail, int64_t *n_used, int64_t *n_skipped, double *sums, double *tail_sums,
+                            int mem_kind);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

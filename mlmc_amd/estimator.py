@@ -123,6 +123,27 @@ def _check_level(what, level):
     return float(level)
 
 
+AggregateSummary = collections.namedtuple(
+    "AggregateSummary", "names probs quantiles quantiles_stderr mean mean_stderr var var_stderr shortfall shortfall_stderr count_prob "
+    "count_prob_stderr worst_prob worst_prob_stderr best_prob best_prob_stderr prob n seeds")
+
+
+def _weighted_row_quantiles(rows, f, probs):
+    """[Q, K]: the weighted quantiles of every row under the weights f by the rule of EventScenarios.weighted_quantiles: the smallest
+    value at which the cumulated normalised weight reaches p.  NaN for a row that holds a NaN or when the weights sum to nothing"""
+    out = np.full((rows.shape[0], probs.size), np.nan)
+    total = f.sum()
+    if not total > 0:
+        return out
+    for k, x in enumerate(rows):
+        if np.any(np.isnan(x)):
+            continue
+        order = np.argsort(x, kind="stable")
+        cum = np.cumsum(f[order]) / total
+        out[k] = x[order][np.minimum(np.searchsorted(cum, probs, side="left"), x.size - 1)]
+    return out
+
+
 def _check_tail(what, tail):
     if tail not in ("upper", "lower"):
         raise ValueError("{}: tail must be 'upper' or 'lower', got {!r}".format(what, tail))
@@ -1129,6 +1150,124 @@ class Estimate:
                                                 first=first, qmc=qmc)
         mean, stderr = scen.means()
         return EventMeans(mean, stderr, scen.prob, scen.ess), success
+
+    def estimate_aggregates(self, weights=None, probs=(0.05, 0.5, 0.95), n=2 ** 16, seeds=tuple(range(8)), corr=None, given=None,
+                            lower=None, upper=None, members=None, extremes=("max", "min"), event=None, tail="upper", qmc=True,
+                            block=2 ** 20, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
+                            antithetic=False):
+        """The distribution of FUNCTIONS of the components under the marginals and the Gaussian copula of `sample_joint`: the total
+        over a field (sum_m w_m X_m), the worst component and which one it is, how many components violate their limits at
+        once.  The scenarios are drawn and reduced block by block on the device (tool.simple_distribution.joint_aggregates), so the
+        scenario matrix [M, n] never exists; every statistic is formed per seed and the seeds give the error bar.
+        The rows: one per row of `weights` ('linear0', ...), then 'max', 'min' (over `members`) as listed in `extremes`, 'count' when
+        limits are given, and 'argmax' / 'argmin' next to 'max' / 'min'.  Per seed and row: the quantiles at `probs`
+        (np.percentile of the row, bit for bit; with `event` the weighted rule of EventScenarios.weighted_quantiles), mean and
+        variance, and the expected shortfall beyond each quantile (tool.simple_distribution.row_statistics with the quantile as
+        the threshold; tail 'upper': E[Y | Y >= q_p]).  From the count row count_prob[k] = P(N = k), k = 0 .. M, so count_prob[0] is
+        the box probability of `estimate_joint_probability` by counting; from the argmax row worst_prob[m] = P(argmax = m), from the
+        argmin row best_prob[m] = P(argmin = m).  Over the seeds: the mean, and the sample standard deviation over sqrt(R) as
+        `*_stderr` (NaN for one seed).
+        :param weights: None, [M] or [A, M]: the linear rows
+        :param probs: probabilities in [0, 1]
+        :param n: scenarios per seed, indices first .. first + n - 1; with qmc a power of two with `first` a multiple of it
+        :param seeds: one independent replicate each
+        :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
+        :param given: None, or as in sample_conditional: arrays [B] give every result a leading axis B
+        :param lower, upper: None or the limits [M] of the count row (-inf / +inf: none on that side)
+        :param members: None or a mask [M]: the components the extremes run over
+        :param extremes: names among 'max', 'min'
+        :param event: None, or (lower_e, upper_e): the scenarios are those of `sample_given_event` for these B boxes and every
+            statistic carries their weights; `prob` is the JointProbability of the event.  qmc then chooses Sobol' or Philox points
+        :param block: scenario columns per device block
+        :return: (AggregateSummary, success [M]).  Statistics are [Q, ...], with a leading axis B for arrays in `given` and for the B
+            boxes of `event` (always, also for one box); count_prob [.., M + 1], worst_prob / best_prob [.., M] are None without their row"""
+        from .tool import simple_distribution as sd
+        what = "estimate_aggregates"
+        M = int(self._quantity.size())
+        n, seeds, first = sd._box_call_args(what, n, seeds, first)
+        sd._sample_flags(what, antithetic, qmc)
+        _check_tail(what, tail)
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+        if probs.size == 0 or not np.all((probs >= 0) & (probs <= 1)):
+            raise ValueError(what + ": probs must be probabilities in [0, 1], got {}".format(probs.tolist()))
+        if isinstance(extremes, str):
+            extremes = (extremes,)
+        extremes = tuple(extremes)
+        if any(name not in ("max", "min") for name in extremes):
+            raise ValueError(what + ": extremes must be among 'max', 'min', got {!r}".format(extremes))
+        extremes = extremes + tuple("arg" + name for name in extremes)
+        agg = dict(weights=weights, lower=lower, upper=upper, members=members, extremes=extremes)
+        names = sd._aggregate_args(what, M, **agg)[-1]
+        if event is not None:
+            if antithetic:
+                raise ValueError(what + ": antithetic does not apply to the scenarios of an event")
+            try:
+                lower_e, upper_e = event
+            except (TypeError, ValueError):
+                raise ValueError(what + ": event must be a pair (lower, upper) of limits") from None
+            if np.any(np.isnan(np.asarray(lower_e, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper_e, dtype=np.float64))):
+                raise ValueError(what + ": a limit of the event is NaN (use -inf / +inf for a side without a limit)")
+        corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        distrs = [d[0] for d in densities]
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        Q, K, R = len(names), probs.size, seeds.size
+        prob = None
+        if event is None:
+            per_seed = [sd.joint_aggregates(distrs, n, int(s), corr=corr, given=given, first=first, antithetic=antithetic, qmc=qmc,
+                                            block=block, device=True, **agg).rows for s in seeds]
+            lead = tuple(per_seed[0].shape[:-2])
+            f_of = None
+        else:
+            scen = sd.event_samples(distrs, lower_e, upper_e, n, [int(s) for s in seeds], corr=corr, given=given, first=first, qmc=qmc,
+                                    device=True)
+            ev = sd.event_aggregates(scen, **agg)
+            B = int(ev.rows.shape[1])
+            per_seed = [ev.rows[r] for r in range(R)]
+            lead = (B,)
+            f_of = ev.weights.cpu().numpy()
+            prob = scen.prob
+        nB = int(np.prod(lead, dtype=np.int64))
+        rep = dict(quantiles=np.empty((R, nB, Q, K)), mean=np.empty((R, nB, Q)), var=np.empty((R, nB, Q)),
+                   shortfall=np.empty((R, nB, Q, K)))
+        k_count, k_max, k_min = (names.index(s) if s in names else None for s in ("count", "argmax", "argmin"))
+        if k_count is not None:
+            rep["count_prob"] = np.empty((R, nB, M + 1))
+        if k_max is not None:
+            rep["worst_prob"] = np.empty((R, nB, M))
+        if k_min is not None:
+            rep["best_prob"] = np.empty((R, nB, M))
+
+        def masses(stat):                                             # P(Y = k) from P(Y >= k), k = 0 .. len - 1
+            return stat.tail_prob - np.append(stat.tail_prob[1:], 0.0)
+
+        for r in range(R):
+            rows = per_seed[r].reshape(nB, Q, n)
+            for b in range(nB):
+                f = None if f_of is None else f_of[r, b]
+                if f is None:
+                    q = engine.row_percentiles(rows[b], 100.0 * probs, nan_policy="propagate")
+                else:
+                    q = _weighted_row_quantiles(rows[b].cpu().numpy(), f, probs)
+                ok = np.all(np.isfinite(q), axis=1)
+                st = sd.row_statistics(rows[b], f=f, thresholds=np.where(ok[:, None], q, 0.0), tail=tail)
+                rep["quantiles"][r, b], rep["mean"][r, b], rep["var"][r, b] = q, st.mean, st.var
+                rep["shortfall"][r, b] = np.where(ok[:, None], st.tail_mean, np.nan)
+                for key, k_row, size in (("count_prob", k_count, M + 1), ("worst_prob", k_max, M), ("best_prob", k_min, M)):
+                    if k_row is not None:
+                        rep[key][r, b] = masses(sd.row_statistics(rows[b, k_row], f=f, thresholds=np.arange(size, dtype=np.float64)))
+        out = {}
+        for key in ("quantiles", "mean", "var", "shortfall", "count_prob", "worst_prob", "best_prob"):
+            if key not in rep:
+                out[key] = out[key + "_stderr"] = None
+                continue
+            v = rep[key]
+            shape = lead + v.shape[2:]
+            with np.errstate(invalid="ignore"):
+                out[key] = v.mean(axis=0).reshape(shape)
+                out[key + "_stderr"] = (np.std(v, axis=0, ddof=1) / np.sqrt(R) if R > 1 else np.full(v.shape[1:], np.nan)).reshape(shape)
+        return AggregateSummary(names=names, probs=probs, prob=prob, n=n, seeds=seeds, **out), success
 
     def estimate_conditional_quantiles(self, probs, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
                                        densities=None):

@@ -1164,6 +1164,292 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
     return EventScenarios(draws, box.weights, box.prob, ess, ok, uniforms)
 
 
+# ---- aggregates of joint scenarios: functions of the components of one scenario column ------------------------------------------
+Aggregates = collections.namedtuple("Aggregates", "rows names")
+EventAggregates = collections.namedtuple("EventAggregates", "rows names weights")
+RowStatistics = collections.namedtuple("RowStatistics", "mean var tail_prob tail_mean weight_sum n_used n_skipped")
+_EXTREMES = {"max": _lib.AGG_MAX, "min": _lib.AGG_MIN, "argmax": _lib.AGG_ARGMAX, "argmin": _lib.AGG_ARGMIN}
+_EXTRA_ORDER = (("max", _lib.AGG_MAX), ("min", _lib.AGG_MIN), ("count", _lib.AGG_COUNT), ("argmax", _lib.AGG_ARGMAX),
+                ("argmin", _lib.AGG_ARGMIN))
+
+
+def _aggregate_args(what, M, weights, lower, upper, members, extremes):
+    """the checked arguments of mlmc_scenario_aggregates for M components, before anything touches the device:
+    (W [A, M] or None, lower [M] or None, upper [M] or None, members uint8 [M] or None, extras bits, names of the Q rows)"""
+    W = None
+    if weights is not None:
+        W = np.asarray(weights, dtype=np.float64)
+        if W.ndim == 1:
+            W = W[None, :]
+        if W.ndim != 2 or W.shape[1] != M:
+            raise ValueError("{}: weights must be [M] or [A, M] with M = {} components, got shape {}".format(
+                what, M, np.shape(weights)))
+        if not np.all(np.isfinite(W)):
+            a, m = np.argwhere(~np.isfinite(W))[0]
+            raise ValueError("{}: the weight of row {}, component {} is not finite".format(what, int(a), int(m)))
+        W = np.ascontiguousarray(W)
+    limits = []
+    for name, lim in (("lower", lower), ("upper", upper)):
+        if lim is not None:
+            lim = np.asarray(lim, dtype=np.float64)
+            try:
+                lim = np.ascontiguousarray(np.broadcast_to(lim, (M,)))
+            except ValueError:
+                raise ValueError("{}: {} must broadcast to [M] with M = {} components, got shape {}".format(
+                    what, name, M, lim.shape)) from None
+            if np.any(np.isnan(lim)):
+                raise ValueError("{}: the {} limit of component {} is NaN (use -inf / +inf for a side without a limit)".format(
+                    what, name, int(np.flatnonzero(np.isnan(lim))[0])))
+        limits.append(lim)
+    lower, upper = limits
+    if isinstance(extremes, str):
+        extremes = (extremes,)
+    extremes = tuple(extremes)
+    extras = 0
+    for name in extremes:
+        if name not in _EXTREMES:
+            raise ValueError("{}: extremes must be among 'max', 'min', 'argmax', 'argmin', got {!r}".format(what, name))
+        extras |= _EXTREMES[name]
+    if members is not None:
+        mem = np.asarray(members)
+        if mem.shape != (M,):
+            raise ValueError("{}: members must be a mask [M] with M = {} components, got shape {}".format(what, M, mem.shape))
+        members = np.ascontiguousarray(mem != 0, dtype=np.uint8)
+        if extras and not members.any():
+            raise ValueError(what + ": an extreme is requested and no component is a member")
+    if lower is not None or upper is not None:
+        extras |= _lib.AGG_COUNT
+    A = 0 if W is None else W.shape[0]
+    names = ["linear{}".format(a) for a in range(A)] + [name for name, bit in _EXTRA_ORDER if extras & bit]
+    if not names:
+        raise ValueError(what + ": nothing to compute: give weights, limits or extremes")
+    return W, lower, upper, members, extras, names
+
+
+def _aggregate_call(x, S, M, n, args, device):
+    """mlmc_scenario_aggregates of x [S, M, n] (C-contiguous float64 NumPy array or device tensor) -> rows [S, Q, n] of its kind"""
+    W, lower, upper, members, extras, names = args
+    if hasattr(x, "data_ptr"):
+        import torch
+        out = torch.empty((S, len(names), n), dtype=torch.float64, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()      # the library reads and writes on its own stream
+        kind = _lib.DEVICE
+    else:
+        out, kind = np.empty((S, len(names), n)), _lib.HOST
+    _lib.check(_lib.lib().mlmc_scenario_aggregates(_lib.ptr(x), S, M, n, n, _lib.ptr(W), 0 if W is None else W.shape[0], _lib.ptr(members),
+                                                   _lib.ptr(lower), _lib.ptr(upper), extras, _lib.ptr(out), n, kind))
+    return out
+
+
+def _scenario_array(what, draws, device, lead):
+    """draws as a C-contiguous float64 array of the kind the call works in (a device tensor for a device tensor or device=True), its
+    shape checked: `lead` names the allowed leading axes"""
+    if hasattr(draws, "data_ptr"):
+        import torch
+        if draws.dtype != torch.float64:
+            raise ValueError(what + ": the draws must be float64, got {}".format(draws.dtype))
+        x = draws.contiguous()
+        if not x.is_cuda:
+            x = x.numpy() if not device else x.cuda()
+    else:
+        x = np.ascontiguousarray(draws, dtype=np.float64)
+        if device:
+            import torch
+            x = torch.from_numpy(x).cuda()
+    if len(x.shape) not in lead:
+        raise ValueError("{}: the array must have {} axes, got shape {}".format(
+            what, " or ".join(str(k) for k in lead), tuple(x.shape)))
+    return x
+
+
+def scenario_aggregates(draws, weights=None, lower=None, upper=None, members=None, extremes=(), device=False):
+    """Functions of the components of every scenario column, in ONE device call (mlmc_scenario_aggregates): the step from the
+    scenarios of `joint_samples` / `conditional_samples` to the system-level quantities they exist for.  Per column j of a set:
+      linear rows   sum_m W[a, m] x[m, j], the chain acc = acc + (W[a, m] * x[m, j]) over m ascending from +0.0 (two roundings per
+                    step, no FMA): a total over a field, a portfolio;
+      'max', 'argmax' (and 'min', 'argmin') over the components of `members`: np.argmax of the member subvector as a component
+                    index (the first NaN if there is one) and x at that index: the worst component and which one it is;
+      'count'       the number of components that have a finite limit and are NOT inside lower[m] < x < upper[m] (a NaN draw of
+                    such a component counts): how many violate their limits at once; count == 0 is the box event of
+                    `joint_probabilities`.  The row is present when lower or upper is given.
+    A value depends on its own column, the weights, limits and members alone, so the result does not depend on n, on the sets
+    or on how the caller blocks the columns, and host and device inputs give the same bits.
+    :param draws: [M, n] or [S, M, n], a NumPy array or a float64 torch tensor (a device tensor is read in place)
+    :param weights: None, [M] or [A, M], finite
+    :param lower, upper: None or limits that broadcast to [M]; -inf / +inf: no limit on that side; NaN is an error
+    :param members: None (all) or a mask [M]
+    :param extremes: names among 'max', 'min', 'argmax', 'argmin'
+    :param device: return a float64 torch device tensor also for a host input (a device input always does)
+    :return: Aggregates(rows [Q, n] or [S, Q, n], names [Q]): the linear rows 'linear0' .. first, then 'max', 'min', 'count',
+        'argmax', 'argmin' as far as requested; integer-valued rows are exact doubles"""
+    what = "scenario_aggregates"
+    x = _scenario_array(what, draws, device, (2, 3))
+    M, n = int(x.shape[-2]), int(x.shape[-1])
+    args = _aggregate_args(what, M, weights, lower, upper, members, extremes)
+    S = 1 if len(x.shape) == 2 else int(x.shape[0])
+    if S < 1:
+        raise ValueError(what + ": no sets")
+    out = _aggregate_call(x, S, M, n, args, device)
+    return Aggregates(out[0] if len(x.shape) == 2 else out, args[-1])
+
+
+def row_statistics(rows, f=None, thresholds=None, tail="upper"):
+    """Weighted mean, variance, tail probability and tail mean of every row, through TWO calls of mlmc_rows_weighted_sums: the first
+    gives the mean, the second sums about it, so the variance is a sum of terms of its own size.  With the weights f (None: ones)
+    over the columns where neither the row nor f is NaN, d = y - mean1 of the first call:
+        mean = mean1 + sum f d / sum f,   var = sum f d^2 / sum f - (sum f d / sum f)^2       (the weighted population variance)
+        tail_prob[k] = sum f 1 / sum f,   tail_mean[k] = mean1 + sum f d 1 / sum f 1,   1 = (y >= t_k) for tail 'upper', (y <= t_k)
+    for 'lower': with t the p-quantile of the row, tail_mean is the expected shortfall beyond it.  The sums are in a fixed order
+    (include/mlmc_hip.h): a row's statistics do not depend on the other rows.  Negative or infinite weights are an error.
+    :param rows: [..., n], a NumPy array or a float64 torch tensor (host or device)
+    :param f: None or the weights [n] (brought to the memory of the rows)
+    :param thresholds: None or [..., P] over the same leading axes (or [P]: the same thresholds for every row)
+    :return: RowStatistics(mean [...], var [...], tail_prob [..., P], tail_mean [..., P], weight_sum [...], n_used [...],
+        n_skipped [...]); a row without weight has NaN statistics, a tail without weight a NaN tail_mean"""
+    what = "row_statistics"
+    _check_tail_name(what, tail)
+    y = _scenario_array(what, rows, False, tuple(range(1, 8)))
+    lead, n = tuple(y.shape[:-1]), int(y.shape[-1])
+    Rw = int(np.prod(lead, dtype=np.int64))
+    on_device = hasattr(y, "data_ptr")
+    if f is not None:
+        if hasattr(f, "data_ptr"):
+            f = f.detach().cpu().numpy()
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (n,):
+            raise ValueError("{}: the weights must be [n] with n = {} columns, got shape {}".format(what, n, f.shape))
+    if thresholds is None:
+        t = np.zeros((Rw, 0))
+    else:
+        t = np.asarray(thresholds, dtype=np.float64)
+        if t.ndim == 1:
+            t = np.broadcast_to(t, lead + t.shape)
+        if t.shape[:-1] != lead:
+            raise ValueError("{}: thresholds must be [P] or {} + [P], got shape {}".format(what, list(lead), t.shape))
+        if np.any(np.isnan(t)):
+            raise ValueError(what + ": a threshold is NaN")
+        t = np.ascontiguousarray(t.reshape(Rw, t.shape[-1]))
+    P = t.shape[1]
+    if on_device:
+        import torch
+        if f is not None:
+            f = torch.from_numpy(f).to(y.device)
+        torch.cuda.current_stream(y.device).synchronize()
+    kind = _lib.DEVICE if on_device else _lib.HOST
+    flag = _lib.TAIL_UPPER if tail == "upper" else _lib.TAIL_LOWER
+
+    def call(c, thr):
+        used, skipped = np.empty(Rw, dtype=np.int64), np.empty(Rw, dtype=np.int64)
+        sums, tails = np.empty((Rw, 3)), np.empty((Rw, thr.shape[1], 2))
+        _lib.check(_lib.lib().mlmc_rows_weighted_sums(_lib.ptr(y), Rw, n, n, _lib.ptr(f), _lib.ptr(c), _lib.ptr(thr), thr.shape[1], flag,
+                                                      _lib.ptr(used), _lib.ptr(skipped), _lib.ptr(sums), _lib.ptr(tails), kind))
+        return used, skipped, sums, tails
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        _, _, s1, _ = call(None, np.zeros((Rw, 0)))
+        centre = s1[:, 1] / s1[:, 0]
+        c = np.ascontiguousarray(np.where(np.isfinite(centre), centre, 0.0))
+        used, skipped, s2, tails = call(c, t)
+        sf = s2[:, 0]
+        shift = s2[:, 1] / sf
+        mean = np.where(np.isfinite(centre), c + shift, centre)
+        var = s2[:, 2] / sf - shift * shift
+        var = np.where(var < 0, 0.0, var)
+        tail_prob = tails[:, :, 0] / sf[:, None]
+        tail_mean = c[:, None] + tails[:, :, 1] / tails[:, :, 0]
+    return RowStatistics(mean.reshape(lead), var.reshape(lead), tail_prob.reshape(lead + (P,)), tail_mean.reshape(lead + (P,)),
+                         sf.reshape(lead), used.reshape(lead), skipped.reshape(lead))
+
+
+def _check_tail_name(what, tail):
+    if tail not in ("upper", "lower"):
+        raise ValueError("{}: tail must be 'upper' or 'lower', got {!r}".format(what, tail))
+
+
+def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, members=None, extremes=(), corr=None, factor=None,
+                     given=None, streams=None, first=0, antithetic=False, qmc=False, block=2 ** 20, device=False):
+    """`scenario_aggregates` of the scenarios of `joint_samples` (with `given`: of `conditional_samples`) WITHOUT the scenario
+    matrix: the draw indices first .. first + n - 1 are walked in blocks of `block` columns, each block is drawn on the device,
+    reduced there and dropped; only the aggregate rows are kept.  At M = 64 and n = 10^8 the matrix would be 51 GB, the result a
+    few rows.  A draw depends on (seed, streams, j) alone and an aggregate on its own column alone, so the result is bit for bit
+    `scenario_aggregates(joint_samples(distrs, n, ...), ...)` for EVERY block size.
+    :param distrs, n, seed, corr, factor, streams, first, antithetic, qmc: as in `joint_samples`
+    :param given: None, or the mapping of `conditional_samples` (arrays [B] give a leading axis B); `factor` then stands for the
+        correlation factor @ factor.T
+    :param weights, lower, upper, members, extremes: as in `scenario_aggregates`, over all M components (rows of given components
+        hold the given values)
+    :param block: columns per device block, >= 1 (with antithetic an even number)
+    :param device: return the rows as a float64 torch device tensor
+    :return: Aggregates(rows [Q, n], or [B, Q, n] for arrays in `given`; names)"""
+    what = "joint_aggregates"
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    _sample_flags(what, antithetic, qmc)
+    _check_seed(what, seed)
+    if (corr is None) == (factor is None):
+        raise ValueError(what + ": exactly one of corr and factor must be given")
+    n = int(_per_distribution_int(what, "n", n, 1)[0])
+    first = int(_per_distribution_int(what, "first", first, 1)[0])
+    if isinstance(block, (bool, np.bool_)) or not isinstance(block, (int, np.integer)) or block < 1:
+        raise ValueError(what + ": block must be a positive integer")
+    if antithetic and (block % 2 or first % 2):
+        raise ValueError(what + ": with antithetic, block and first must be even (a pair of draws shares its normals)")
+    args = _aggregate_args(what, M, weights, lower, upper, members, extremes)
+    lead = ()
+    if given is not None:
+        observed, values, scalar = _parse_given(what, given, M)
+        if factor is not None:
+            fac = np.asarray(factor, dtype=np.float64)
+            if fac.ndim != 2 or fac.shape[0] != M or fac.shape[1] < 1 or not np.all(np.isfinite(fac)):
+                raise ValueError(what + ": the factor must be a finite [M, K] matrix with M = {} distributions".format(M))
+            corr = fac @ fac.T
+        cond = conditional_factor(corr, observed)
+        lead = () if scalar else (values.shape[1],)
+    elif corr is not None:
+        factor = correlation_factor(corr)[0]
+    import torch
+    Q = len(args[-1])
+    if device:
+        rows = torch.empty(lead + (Q, n), dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        rows = np.empty(lead + (Q, n))
+    for off in range(0, n, int(block)):
+        nb = min(int(block), n - off)
+        if given is None:
+            x = joint_samples(distrs, nb, seed, factor=factor, streams=streams, first=first + off, antithetic=antithetic, device=True,
+                              qmc=qmc)
+        else:
+            x = conditional_samples(distrs, nb, seed, given, factor_info=cond, streams=streams, first=first + off,
+                                    antithetic=antithetic, device=True, qmc=qmc)
+        S = 1 if x.dim() == 2 else int(x.shape[0])
+        part = _aggregate_call(x, S, M, nb, args, True).reshape(lead + (Q, nb))
+        if device:
+            rows[..., off:off + nb] = part
+        else:
+            rows[..., off:off + nb] = part.cpu().numpy()
+    if device:
+        torch.cuda.current_stream(rows.device).synchronize()
+    return Aggregates(rows, args[-1])
+
+
+def event_aggregates(scen, weights=None, lower=None, upper=None, members=None, extremes=(), device=False):
+    """`scenario_aggregates` of the scenarios of an `EventScenarios` (host or device arrays) in ONE device call: the aggregate rows
+    of every seed and box next to the importance weights of the scenarios, ready for `row_statistics(rows[r, b], f=weights[r, b])`.
+    :param scen: what `event_samples` returned
+    :param weights, lower, upper, members, extremes, device: as in `scenario_aggregates` (`weights` are those of the linear rows)
+    :return: EventAggregates(rows [R, B, Q, n], names [Q], weights [R, B, n])"""
+    what = "event_aggregates"
+    x = _scenario_array(what, scen.draws, device, (4,))
+    R, B, M, n = (int(s) for s in x.shape)
+    args = _aggregate_args(what, M, weights, lower, upper, members, extremes)
+    if R * B < 1:
+        raise ValueError(what + ": no scenarios")
+    out = _aggregate_call(x.reshape(R * B, M, n), R * B, M, n, args, device)
+    return EventAggregates(out.reshape(R, B, len(args[-1]), n), args[-1], scen.weights)
+
+
 def _scores_problem_args(distrs, what):
     """the problem arguments of mlmc_density_scores_batch for a list of distributions, ready to be splatted into the call:
     (M, handles, r1, lam, sig, a, b, n_intervals, gauss_degree) as ctypes values, and the arrays that must outlive the call"""

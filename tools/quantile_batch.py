@@ -94,9 +94,19 @@ one shape), next to rejection: joint_samples(device=True) of the same n per seed
   call_ms, inside_per_ms, ess_fraction, event_mean, event_stderr   wall time of the call up to a device synchronise, its R n scenarios
                                per ms, ess / n, and the conditional mean of component 2 (M = 2: 0) with the seeds' standard error
   reject_ms_per_seed, reject_inside_per_ms, reject_mean, reject_stderr, reject_zero_seeds   the same for what the filter keeps
+--aggregates: mlmc_scenario_aggregates on device-resident scenarios x [S, M, n], A = 3 linear rows, all four
+extremes and the count (Q = 8), for S x M x n = 1 x 12 x 10^6, 1 x 64 x 10^6 and 64 given-sets x 12 x 10^4 (--config S,M,n: that shape
+alone), against the torch composition on the same materialised matrix -- matmul, max and min with their indices, compare and sum: five
+passes over x -- in the same process, the two taking turns after a warm-up call each:
+  entry_ms / torch_ms, torch_over_entry_wall   wall time of the whole route up to a device synchronise, and the ratio
+  event_ms, tbytes_per_s, fraction_of_stream_rate   HIP-event time around the entry on its stream (one small upload and the one
+                               kernel), the algorithmic bytes 8 M n read + 8 Q n written per set over it, and that rate over the
+                               5.4 TB/s of this package's own streaming kernels
+  extras_equal_torch, linear_rel_diff_torch    the extreme and count rows equal torch's exactly; the linear rows differ from matmul by
+                               its summation order
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --scores |
-                                                              --conditional | --qmc | --boxprob | --boxdraws] [--reps K]"""
+                                                              --conditional | --qmc | --boxprob | --boxdraws | --aggregates] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -721,6 +731,62 @@ def scores_shape(M, R1, n, reps, levels=0):
     return out
 
 
+STREAM_RATE = 5.4e12     # bytes / s of this package's own streaming kernels
+
+
+def aggregates_shape(S, M, n, reps):
+    """mlmc_scenario_aggregates on S sets of M x n device-resident scenarios, A = 3 linear rows, all extremes and the count (Q = 8),
+    against the torch composition on the same materialised matrix, the two taking turns"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(5)
+    x = torch.randn((S, M, n), dtype=torch.float64, device=dev, generator=gen)
+    rng = np.random.default_rng(6)
+    W = np.ascontiguousarray(rng.uniform(-1.0, 1.0, (3, M)))
+    lower, upper = np.full(M, -1.0), np.full(M, 1.5)
+    extras = _lib.AGG_MAX | _lib.AGG_MIN | _lib.AGG_COUNT | _lib.AGG_ARGMAX | _lib.AGG_ARGMIN
+    Q = 3 + 5
+    out = torch.empty((S, Q, n), dtype=torch.float64, device=dev)
+    Wd, lo_d, hi_d = torch.from_numpy(W).to(dev), torch.from_numpy(lower).to(dev)[:, None], torch.from_numpy(upper).to(dev)[:, None]
+    torch.cuda.synchronize()
+    lib = _lib.lib()
+
+    def entry():
+        _lib.check(lib.mlmc_scenario_aggregates(_lib.ptr(x), S, M, n, n, _lib.ptr(W), 3, None, _lib.ptr(lower), _lib.ptr(upper), extras,
+                                                _lib.ptr(out), n, _lib.DEVICE))
+
+    def composition():
+        lin = torch.matmul(Wd, x)
+        mx, amx = torch.max(x, dim=-2)
+        mn, amn = torch.min(x, dim=-2)
+        cnt = ((x <= lo_d) | (x >= hi_d)).sum(dim=-2)
+        torch.cuda.synchronize()
+        return lin, mx, mn, cnt, amx, amn
+
+    entry_ms, torch_ms = alternating([entry, composition], reps)
+    # the kernel's own time: HIP events on the stream the library launches on (main binds it to torch's), around the call: three small
+    # uploads and one launch
+    entry()
+    ev = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        entry()
+        b.record()
+        torch.cuda.synchronize()
+        ev.append(a.elapsed_time(b))
+    event_ms = float(np.median(ev))
+    lin, mx, mn, cnt, amx, amn = composition()
+    same_extras = bool(torch.equal(out[:, 3], mx) and torch.equal(out[:, 4], mn) and torch.equal(out[:, 5], cnt.to(torch.float64))
+                       and torch.equal(out[:, 6], amx.to(torch.float64)) and torch.equal(out[:, 7], amn.to(torch.float64)))
+    lin_err = float((out[:, :3] - lin).abs().max() / lin.abs().max())
+    alg_bytes = 8.0 * S * n * (M + Q)
+    rate = alg_bytes / (event_ms * 1e-3)
+    return dict(S=S, M=M, n=n, A=3, Q=Q, entry_ms=round(entry_ms, 3), torch_ms=round(torch_ms, 3), torch_over_entry_wall=round(torch_ms / entry_ms, 2),
+                event_ms=round(event_ms, 4), alg_gbytes=round(alg_bytes / 1e9, 4), tbytes_per_s=round(rate / 1e12, 3),
+                fraction_of_stream_rate=round(rate / STREAM_RATE, 3), extras_equal_torch=same_extras, linear_rel_diff_torch=lin_err)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -763,12 +829,22 @@ def main():
     ap.add_argument("--boxprob", action="store_true", help="copula_box_probabilities against closed forms, next to counting the "
                                                            "scenarios of joint_samples (DESIGN.md section 3.5.17)")
     ap.add_argument("--boxdraws", action="store_true", help="event_samples against rejection from joint_samples (DESIGN.md section 3.5.18)")
+    ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
+                                                              "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.aggregates:
+        shapes = [(1, 12, 1_000_000), (1, 64, 1_000_000), (64, 12, 10_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(1, 12, 10_000), (3, 5, 1_000)]
+        _lib.use_torch_stream()
+        out["aggregates"] = [aggregates_shape(S, M, n, a.reps) for S, M, n in shapes]
     elif a.boxdraws:
         shapes = [(M, 2 ** k, 0.9) for M in (2, 12, 64) for k in (12, 16, 20)] + [(12, 2 ** k, 0.999) for k in (12, 16, 20)]
         if a.config:
