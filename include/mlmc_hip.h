@@ -44,7 +44,7 @@ extern "C" {
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
                               *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch,
                               *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov,
-                              *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums */
+                              *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -693,6 +693,40 @@ enum { MLMC_TAIL_UPPER = 0, MLMC_TAIL_LOWER = 1 };
 int mlmc_rows_weighted_sums(const double *y, int64_t n_rows, int64_t n, int64_t ld, const double *f, const double *c, const double *t,
                             int32_t P, int32_t tail, int64_t *n_used, int64_t *n_skipped, double *sums, double *tail_sums,
                             int mem_kind);
+
+/* ---- concordance counts of the components (concordance.hip) -- added within 8 -------------------------------------------
+ * How often the components of a vector lie inside box events, pair by pair and all at once, for the fine and the coarse values of a
+ * level: the integers from which the multilevel estimate of a joint probability P(X_a in E_a, X_b in E_b) and its variance follow
+ * exactly (the level difference of an indicator product is -1, 0 or 1), e.g. the tail-dependence function of a copula.
+ *   fine, coarse: DEVICE arrays [M][ld], columns 0 .. n-1 are used (the component-major chunk of mlmc_accum_push); coarse may be
+ *     NULL (level 0).  0 <= M <= MLMC_CONCORDANCE_MAX_M, n >= 0, ld >= n.
+ *   lower, upper [G][M] host, 1 <= G <= MLMC_CONCORDANCE_MAX_G events; -inf / +inf: no limit on that side.
+ *   Component m of a value v is INSIDE event g iff lower[g][m] < v && v < upper[g][m] (the open box of
+ *     mlmc_copula_box_prob_batch): NaN is never inside, a value equal to a limit is outside.
+ *   A column is KEPT iff no row of fine, and of coarse when present, holds a NaN (mask_nan_samples over the [M, n, 2] chunk, the
+ *     rule of the component-covariance accumulator); a dropped column contributes to nothing.
+ * For a kept column, e^f_m / e^c_m the inside indicators of the fine / coarse value of component m (e^c = 0 without coarse),
+ *   J^f_ab = e^f_a e^f_b, J^c_ab = e^c_a e^c_b, A^f = prod_m e^f_m, A^c = prod_m e^c_m.  The entry ADDS to caller-owned DEVICE int64
+ *   counters (the caller zeroes them; a level's slice takes block after block):
+ *     pair [G][3][M][M]: [g][0][a][b] += sum_j J^f, [g][1][a][b] += sum_j J^c, [g][2][a][b] += sum_j [J^f != J^c]; full symmetric
+ *       matrices, the diagonal is the marginal count;
+ *     all [G][3]: the same three counts for A^f, A^c;      kept [1]: the number of kept columns (may be NULL).
+ *   pair or all may be NULL and is then skipped together with its work (no bit matrix, no Gram without pair).
+ * kernel_ms [2] host (may be NULL): the HIP-event time in ms of the streaming kernel and of the Gram kernel of the call's first
+ *   slab of columns (the columns are walked in slabs that keep the bit matrix within 256 MiB; G M n <= 2^30 is one
+ *   slab); best effort, zeros when the events cannot be made.
+ * Everything is integer: the counters do not depend on the launch geometry, on the slabs (MLMC_CONCORDANCE_SLAB_WORDS in the
+ * environment, read per call, sets the 64-column words of a slab: a test aid), on how the caller splits the columns across calls
+ * or on the order of the calls, and repeat bit for bit.  Integer atomics only (their order cannot matter).
+ * Errors: M < 0, n < 0, G < 1, M or G above its cap, ld < n, null fine (unless M = 0 or n = 0), null lower / upper, pair and all
+ *   both NULL, a NaN limit (names event and component).  n = 0 and M = 0 are no-ops.
+ * Two kernels per slab and a one-workgroup reduction: the values are read once, a wave's ballot makes 64 columns one word
+ * ([G][2][M][ceil(n / 64)] words, 1 / 64 of the input per event and side), a pair count is popcount(word_a & word_b); one host
+ * wait. */
+#define MLMC_CONCORDANCE_MAX_M 1024
+#define MLMC_CONCORDANCE_MAX_G 16
+int mlmc_concordance_counts(const double *fine, const double *coarse, int32_t M, int64_t n, int64_t ld, int32_t G, const double *lower,
+                            const double *upper, int64_t *pair, int64_t *all, int64_t *kept, double *kernel_ms);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

@@ -22,6 +22,9 @@ EventMeans = collections.namedtuple("EventMeans", "mean stderr prob ess")
 CovarianceBootstrapReplicates = collections.namedtuple("CovarianceBootstrapReplicates", "n_samples mean cov corr ok seed")
 CorrelationBands = collections.namedtuple("CorrelationBands", "corr lo hi std replicates ok n_ok seed")
 ProbabilityBands = collections.namedtuple("ProbabilityBands", "prob stderr lo hi replicates ok n_ok seed")
+TailDependence = collections.namedtuple("TailDependence",
+                                        "prob var chi model chi_model z marginal counts n_samples n_rm_samples corr")
+JointFrequency = collections.namedtuple("JointFrequency", "prob stderr counts n_samples")
 
 
 def covariance_replicates(n, s1, s2, sample_vector, shift=None, centered=True):
@@ -1105,6 +1108,96 @@ class Estimate:
         return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
                                                first=first, qmc=qmc)
+
+    def estimate_tail_dependence(self, probs=(0.9, 0.95, 0.99), tail="upper", corr=None, densities=None, tol=1e-8, reg_param=0.0,
+                                 orth_moments_tol=1e-4, moments_fns=None):
+        """A check of the Gaussian copula that `sample_joint`, `estimate_joint_probability` and their relatives assume: the
+        multilevel frequency with which TWO components lie beyond their p-quantile at once, for every pair, held against the
+        bivariate normal orthant at the copula's own correlation.  A Gaussian copula has no tail dependence; where the stored
+        samples have it, chi = P(both beyond) / (1 - p) stays above chi_model as p grows, z is large and positive, and every joint
+        tail probability computed under the copula is too small.
+
+        One pass over the stored samples: each fine and coarse value goes through its marginal's CDF on the device, a wave's
+        ballot turns 64 uniforms into one word and a pair count is a popcount (quantity_estimate.component_concordance(scores=...)).
+        The level difference of an indicator product is -1, 0 or 1, so the multilevel mean and its variance follow exactly from
+        three integers per pair, level and probability.
+        :param probs: probability levels p in (0, 1); at most 16 events per call ("both" makes two per level)
+        :param tail: "upper": the events u > p; "lower": u < 1 - p (the same model value, by symmetry); "both": the upper events
+            followed by the lower ones, 2 G events in one pass
+        :param corr: as in sample_joint: None (Pearson), "scores", or a correlation matrix [M, M] of the normal scores
+        :param densities: as in estimate_component_quantiles
+        :return: TailDependence(prob, var, chi, model, chi_model, z [G, M, M], marginal [G, M], counts, n_samples, n_rm_samples [L],
+            corr [M, M]):
+            prob, var: the multilevel estimate of P(U_a and U_b both beyond level p_g) and its variance; the diagonal of prob
+                (= marginal) is P(U_a beyond p_g) and equals 1 - p when the marginal fits: a calibration of each marginal there;
+            chi = prob / (1 - p); model = tool.simple_distribution.bivariate_orthant at the score of p_g and corr_ab,
+                chi_model = model / (1 - p);
+            z = (prob - model) / sqrt(var), NaN where var is not positive and finite, and on the diagonal;
+            counts: the integers per level (quantity_estimate.ComponentConcordance).
+        What z does NOT contain: the sampling error of the correlation estimate that `model` is evaluated at, and that of the
+        fitted marginals that turn values into uniforms -- var is the sampling variance of the frequency alone.  So |z| of 2 or 3
+        says little; a consistent sign over pairs and a growth with p says much."""
+        from scipy import special
+        from .tool import simple_distribution
+        what = "estimate_tail_dependence"
+        if tail not in ("upper", "lower", "both"):
+            raise ValueError("{}: tail must be 'upper', 'lower' or 'both', got {!r}".format(what, tail))
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or p.size == 0 or not np.all((p > 0.0) & (p < 1.0)):
+            raise ValueError(what + ": probs must be probability levels in (0, 1)")
+        if p.size * (2 if tail == "both" else 1) > simple_distribution._lib.CONCORDANCE_MAX_G:
+            raise ValueError("{}: at most {} events per call".format(what, simple_distribution._lib.CONCORDANCE_MAX_G))
+        if isinstance(densities, str):
+            raise ValueError(what + ": densities must be the list construct_densities returned")
+        corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        densities = list(densities)
+        M = int(self._quantity.size())
+        if len(densities) != M:
+            raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
+        corr = np.asarray(corr, dtype=np.float64)
+        if corr.shape != (M, M):
+            raise ValueError("{}: corr of shape {}, expected ({}, {})".format(what, corr.shape, M, M))
+        ones = np.ones((p.size, M))
+        lower, upper, levels = [], [], []
+        if tail in ("upper", "both"):
+            lower.append(p[:, None] * ones), upper.append(np.inf * ones), levels.append(p)
+        if tail in ("lower", "both"):
+            lower.append(-np.inf * ones), upper.append((1.0 - p)[:, None] * ones), levels.append(p)
+        lower, upper, levels = np.concatenate(lower), np.concatenate(upper), np.concatenate(levels)
+        counts = qe.component_concordance(self._quantity, lower, upper, scores=[d[0] for d in densities])
+        if int(np.sum(counts.n)) == 0:
+            raise Exception("All samples were masked")
+        st = qe.concordance_statistics(counts.n, counts.pair)
+        prob, var = st["prob"], st["var"]
+        h = special.ndtri(levels)
+        model = simple_distribution.bivariate_orthant(h[:, None, None], h[:, None, None], np.clip(corr, -1.0, 1.0)[None])
+        rest = (1.0 - levels)[:, None, None]
+        with np.errstate(all="ignore"):
+            z = np.where(np.isfinite(var) & (var > 0.0), (prob - model) / np.sqrt(var), np.nan)
+        z[:, np.arange(M), np.arange(M)] = np.nan
+        marginal = prob[:, np.arange(M), np.arange(M)].copy()
+        return TailDependence(prob, var, prob / rest, model, model / rest, z, marginal, counts, counts.n, counts.n_rm, corr)
+
+    def estimate_joint_frequency(self, lower, upper):
+        """The direct multilevel estimate of P(lower_m < X_m < upper_m for every component m) from the stored samples, in the units
+        of the components, for B boxes in one pass (quantity_estimate.component_concordance(pairs=False)): no densities and no
+        copula are involved.  This is the number to hold against `estimate_joint_probability(...).prob` at moderate probabilities:
+        where the two disagree beyond stderr, the marginals or the copula do not describe the samples.  It CANNOT resolve rare
+        events: it counts, so a box of probability P needs of the order of 100 / P samples on the coarsest level for a 10 % error,
+        and a box that no stored sample falls into gives exactly 0 with a variance of 0 -- where `estimate_joint_probability`
+        integrates the model and resolves 1e-6.  A sample with a NaN in any component, fine or coarse, is dropped.
+        :param lower, upper: broadcast to [B, M] ([M]: one box); -inf / +inf: no limit on that side; at most 16 boxes per call
+        :return: JointFrequency(prob [B], stderr [B], counts, n_samples [L]): stderr = sqrt(sum_l var_l / n_l), exact from the
+            integers (the level difference of an indicator is -1, 0 or 1); counts: quantity_estimate.ComponentConcordance"""
+        counts = qe.component_concordance(self._quantity, lower, upper, pairs=False)
+        if int(np.sum(counts.n)) == 0:
+            raise Exception("All samples were masked")
+        st = qe.concordance_statistics(counts.n, counts.all)
+        with np.errstate(all="ignore"):
+            stderr = np.sqrt(st["var"])
+        return JointFrequency(st["prob"], stderr, counts, counts.n)
 
     def sample_given_event(self, n, lower, upper, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
                            orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True):

@@ -1236,13 +1236,38 @@ class _ScoreRows:
 
     def __init__(self, scores, what):
         self._scores, self._what = scores, what
-        self._head = self._keep = self._buf = self._width = self._nb = None
+        self._head = self._keep = self._buf = self._width = self._nb = self._ubuf = None
 
-    def _into(self, fine, coarse, n, ld_in, z_fine, z_coarse):
+    def _into(self, fine, coarse, n, ld_in, z_fine, z_coarse, u_fine=None, u_coarse=None):
         from ..tool import simple_distribution
         if self._head is None:
             self._head, self._keep = simple_distribution._scores_problem_args(self._scores, self._what)
-        simple_distribution._scores_into(self._head, fine, coarse, n, ld_in, z_fine, z_coarse, n)
+        simple_distribution._scores_into(self._head, fine, coarse, n, ld_in, z_fine, z_coarse, n, u_fine, u_coarse)
+
+    def uniforms(self, fine, coarse, dev):
+        """Generator of (u_fine, u_coarse | None) [M, nc]: the uniforms u = Fhat_m(x) of a pair (the bits of mlmc_density_cdf_batch;
+        NaN for NaN and outside the open domain), block by block of score_block_columns(M) columns in one workspace that every block
+        reuses -- a block must be consumed before the next one is asked for.  A host chunk is uploaded first, once.  The uniforms
+        stay on the device."""
+        import torch
+        M = len(self._scores)
+        if self._ubuf is None:
+            self._nb = score_block_columns(M)
+            self._ubuf = torch.empty((4, M * self._nb), dtype=torch.float64, device=dev)     # z and u, fine and coarse
+        nb = self._nb
+        fine = _device_rows(fine, M, dev)[0]
+        coarse = None if coarse is None else _device_rows(coarse, M, dev)[0]
+        n = int(fine.shape[-1])
+        torch.cuda.current_stream(dev).synchronize()                # the library reads and writes on its own stream
+        for c0 in range(0, n, nb):
+            nc = min(nb, n - c0)
+            z_f, z_c, u_f, u_c = [self._ubuf[k, :M * nc].view(M, nc) for k in range(4)]
+            if coarse is None:
+                self._into(fine[:, c0:], None, nc, n, z_f, None, u_f, None)
+                yield u_f, None
+            else:
+                self._into(fine[:, c0:], coarse[:, c0:], nc, n, z_f, z_c, u_f, u_c)
+                yield u_f, u_c
 
     def chunk(self, fine, coarse, n):
         """The scores of a whole chunk in a workspace of its own (16 M n bytes), which the caller releases.  -> fine, coarse | None"""
@@ -1340,6 +1365,102 @@ class _LevelSink:
             out = self._acc.finalize(group=group)
         _acc_pool.give(self._target.fn, self._n_levels, self._target.mode, self.n_comp, self._acc, mean_only=self._mean_only)
         return out
+
+
+class _ConcordanceSink:
+    """Where the (level, pair) stream of component_concordance ends: int64 device counters [L, ...] whose level slice
+    mlmc_concordance_counts adds every pushed block to.  With scores the pair goes through _ScoreRows.uniforms block by block and
+    the uniforms are counted; without, the raw rows are (a host chunk is uploaded, as the covariance route uploads it)."""
+
+    def __init__(self, walk, M, lower, upper, scores, pairs):
+        import torch
+        self._dev, self._M, self._lower, self._upper = walk.dev, M, lower, upper
+        L, G = walk.n_levels, lower.shape[0]
+        self._scores = None if scores is None else _ScoreRows(scores, "component_concordance")
+        self._pair = torch.zeros((L, G, 3, M, M), dtype=torch.int64, device=walk.dev) if pairs else None
+        self._all = torch.zeros((L, G, 3), dtype=torch.int64, device=walk.dev)
+        self._kept = torch.zeros((L, 1), dtype=torch.int64, device=walk.dev)
+        self._seen = np.zeros(L, dtype=np.int64)
+        torch.cuda.current_stream(walk.dev).synchronize()           # the zeros, before the library adds on its own stream
+
+    def _count(self, level_id, fine, coarse, n, ld):
+        from ..tool import simple_distribution
+        simple_distribution._concordance_into(fine, coarse, self._M, n, ld, self._lower, self._upper,
+                                              None if self._pair is None else self._pair[level_id], self._all[level_id],
+                                              self._kept[level_id])
+
+    def push(self, level_id, pair):
+        import torch
+        if pair is None or pair[0].shape[-1] == 0:
+            return
+        fine, coarse = pair
+        n = int(fine.shape[-1])
+        self._seen[level_id] += n
+        if self._scores is not None:
+            for u_fine, u_coarse in self._scores.uniforms(fine, coarse, self._dev):
+                self._count(level_id, u_fine, u_coarse, u_fine.shape[-1], u_fine.shape[-1])
+            return
+        fine, copied = _device_rows(fine, self._M, self._dev)
+        if coarse is not None:
+            coarse, copied_c = _device_rows(coarse, self._M, self._dev)
+            copied = copied or copied_c
+        if copied:
+            torch.cuda.current_stream(self._dev).synchronize()      # the library reads them on its own stream
+        self._count(level_id, fine, coarse, n, n)
+
+    def finish(self):
+        """-> n, n_rm [L], pair [L, G, 3, M, M] | None, all [L, G, 3] (NumPy int64)"""
+        n = self._kept.cpu().numpy()[:, 0]
+        return n, self._seen - n, (None if self._pair is None else self._pair.cpu().numpy()), self._all.cpu().numpy()
+
+
+ComponentConcordance = collections.namedtuple("ComponentConcordance", "n n_rm pair all")
+
+
+def component_concordance(quantity, lower, upper, scores=None, pairs=True):
+    """Per level, how often the scalar components of `quantity` lie inside box events -- pair by pair and all at once, fine against
+    coarse (mlmc_concordance_counts, mlmc_amd/csrc/concordance.hip): the integers of a multilevel joint frequency, one pass per
+    stored chunk for the whole pair matrix (concordance_statistics turns them into means and variances).
+
+    Without `scores` the limits are in the units of the components and the raw rows are counted.  With scores = a list of M
+    distributions with multipliers (one quadrature) the limits are in U SPACE: every pair goes block by block (score_block_columns(M)
+    columns, one reused workspace) through the probability-integral transform u = Fhat_m(x) on the device, the bits of
+    mlmc_density_cdf_batch, and the uniforms are counted without ever being downloaded.  A value that is NaN or outside its
+    density's open domain has u = NaN and drops its column, like any NaN in any component, fine or coarse: so `n` equals the
+    n_samples of Estimate.estimate_score_correlation on the same store.  The counts are integers: the block width changes nothing.
+    :param lower, upper: limits that broadcast to [G, M]; -inf / +inf: no limit on that side; inside is lower < v < upper
+    :param pairs: False: the `all` counters alone
+    :return: ComponentConcordance(n [L], n_rm [L] kept and dropped samples, pair [L, G, 3, M, M] | None, all [L, G, 3]), int64; the
+        axis of 3 holds the counts of the fine event, of the coarse event and of the columns where the two differ"""
+    from .. import _lib
+    from ..tool import simple_distribution
+    M, _, scores = _component_args("component_concordance", quantity, None, scores, _lib.CONCORDANCE_MAX_M)
+    lower, upper = simple_distribution._concordance_limits("component_concordance", lower, upper, M)
+    with _estimate_lock:
+        target = _estimate_target(quantity, True)
+        walk = _walk_setup(quantity, target.source)
+        sink = _ConcordanceSink(walk, M, lower, upper, scores, pairs)
+        with contextlib.closing(_level_pairs(target, walk)) as level_pairs:
+            for level_id, pair in level_pairs:
+                sink.push(level_id, pair)
+        return ComponentConcordance(*sink.finish())
+
+
+def concordance_statistics(n, counts):
+    """Level statistics of indicator products from their counts: counts [L, G, 3, ...] (the fine event, the coarse event, the
+    columns where they differ) and n [L] kept samples.  The level difference is -1, 0 or 1, so with S = N^f - N^c and Q = N^x
+    mean_l = S / n_l and var_l = (Q - S^2 / n_l) / (n_l - 1) exactly (inf where n_l <= 1: engine.level_stats).
+    -> dict(l_means, l_vars [L, G, ...], prob = sum_l mean_l, var = sum_l var_l / n_l [G, ...])"""
+    counts = np.asarray(counts)
+    n = np.asarray(n, dtype=np.int64)
+    L = counts.shape[0]
+    s = (counts[:, :, 0] - counts[:, :, 1]).astype(np.float64)
+    shape = s.shape[1:]
+    l_means, l_vars = engine.level_stats(n, s.reshape(L, -1), counts[:, :, 2].astype(np.float64).reshape(L, -1))
+    with np.errstate(all="ignore"):
+        var = np.sum(l_vars / n.astype(np.float64)[:, None], axis=0)
+    return dict(l_means=l_means.reshape((L,) + shape), l_vars=l_vars.reshape((L,) + shape),
+                prob=np.sum(l_means, axis=0).reshape(shape), var=var.reshape(shape))
 
 
 def _on_device_subsample(pair, target, level_id):

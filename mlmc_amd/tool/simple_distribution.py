@@ -1523,6 +1523,139 @@ def normal_scores(distrs, fine, coarse=None, device=False, return_uniforms=False
     return return_list[0] if len(return_list) == 1 else tuple(return_list)
 
 
+ConcordanceCounts = collections.namedtuple("ConcordanceCounts", "pair all kept")
+
+
+def _concordance_limits(what, lower, upper, M):
+    """lower, upper broadcast together to C-contiguous float64 [G, M] ([M] is one event), checked: no NaN, 1 <= G <= the cap"""
+    lims = []
+    for name, lim in (("lower", lower), ("upper", upper)):
+        lim = np.asarray(lim, dtype=np.float64)
+        if lim.ndim > 2:
+            raise ValueError("{}: {} must broadcast to [G, M], got shape {}".format(what, name, lim.shape))
+        if np.any(np.isnan(lim)):
+            raise ValueError("{}: a {} limit is NaN (use -inf / +inf for a side without a limit)".format(what, name))
+        lims.append(np.atleast_2d(lim))
+    G = max(lims[0].shape[0], lims[1].shape[0])
+    try:
+        lims = [np.ascontiguousarray(np.broadcast_to(lim, (G, M))) for lim in lims]
+    except ValueError:
+        raise ValueError("{}: lower {} and upper {} must broadcast to [G, M] with M = {} components".format(
+            what, np.shape(lower), np.shape(upper), M)) from None
+    if not 1 <= G <= _lib.CONCORDANCE_MAX_G:
+        raise ValueError("{}: {} events, between 1 and {} are supported per call".format(what, G, _lib.CONCORDANCE_MAX_G))
+    return lims[0], lims[1]
+
+
+def _concordance_into(fine, coarse, M, n, ld, lower, upper, pair, all_, kept, kernel_ms=None):
+    """one call of mlmc_concordance_counts on float64 device tensors (rows `ld` apart, n columns used) and int64 device counters; the
+    caller has synchronised the stream that produced them"""
+    _lib.check(_lib.lib().mlmc_concordance_counts(_lib.ptr(fine), _lib.ptr(coarse), int(M), int(n), int(ld), int(lower.shape[0]),
+                                                  _lib.ptr(lower), _lib.ptr(upper), _lib.ptr(pair), _lib.ptr(all_), _lib.ptr(kept),
+                                                  None if kernel_ms is None else _lib.ptr(kernel_ms)))
+
+
+def concordance_counts(fine, coarse=None, lower=-np.inf, upper=np.inf, pairs=True, device=False, out=None, kernel_ms=None):
+    """How often the components lie inside box events, pair by pair and all at once, on bits in ONE device call
+    (mlmc_concordance_counts).  Component m of a column is inside event g iff lower[g, m] < v < upper[g, m] (NaN never, a value on a
+    limit not); a column with a NaN in any row of fine or coarse is dropped.  With e^f, e^c the inside indicators of a kept column
+    (e^c = 0 without coarse), J_ab = e_a e_b and A = prod_m e_m:
+      pair [G, 3, M, M] int64: sum J^f, sum J^c, sum [J^f != J^c] -- symmetric, the diagonal is the marginal count;
+      all [G, 3] int64: the same three for A^f, A^c;      kept [1] int64: the kept columns.
+    The level difference J^f - J^c is -1, 0 or 1, so its sum is pair[:, 0] - pair[:, 1] and the sum of its squares pair[:, 2]: the
+    multilevel mean and variance of a joint frequency follow exactly (quantity_estimate.concordance_statistics).  All integer: the
+    counts do not depend on how the columns are split across calls.
+    :param fine: [M, n] values, a NumPy array or a float64 torch device tensor (rows may be a view with a row stride)
+    :param coarse: None or an array like `fine`
+    :param lower, upper: limits that broadcast to [G, M] ([M]: one event); -inf / +inf: no limit on that side; NaN is an error
+    :param pairs: False: the `all` and `kept` counters alone (no bit matrix, no Gram); `pair` is None
+    :param device: return int64 torch device tensors
+    :param out: a ConcordanceCounts of int64 device tensors that the counts are ADDED to (it is returned: block after block)
+    :param kernel_ms: None or a float64 NumPy array [2] that takes the HIP-event times of the two kernels
+    :return: ConcordanceCounts(pair, all, kept)"""
+    what = "concordance_counts"
+
+    def checked(x, name):                                           # before anything touches the device
+        if hasattr(x, "data_ptr"):
+            if not x.is_cuda or str(x.dtype) != "torch.float64":
+                raise ValueError("{}: {} must be a NumPy array or a float64 device tensor".format(what, name))
+        else:
+            x = np.asarray(x, dtype=np.float64)
+        if len(x.shape) != 2:
+            raise ValueError("{}: {} must be [M, n], got shape {}".format(what, name, tuple(x.shape)))
+        return x
+    fine = checked(fine, "fine")
+    M, n = int(fine.shape[0]), int(fine.shape[1])
+    if coarse is not None:
+        coarse = checked(coarse, "coarse")
+        if tuple(coarse.shape) != (M, n):
+            raise ValueError("{}: fine {} and coarse {} differ in shape".format(what, tuple(fine.shape), tuple(coarse.shape)))
+    if M > _lib.CONCORDANCE_MAX_M:
+        raise ValueError("{}: {} components, at most {} are supported".format(what, M, _lib.CONCORDANCE_MAX_M))
+    lower, upper = _concordance_limits(what, lower, upper, M)
+    G = lower.shape[0]
+    shapes = ((G, 3, M, M) if pairs else None, (G, 3), (1,))
+    if out is not None:
+        for name, t, shape in zip(ConcordanceCounts._fields, out, shapes):
+            if shape is None and t is None:
+                continue
+            if shape is None or t is None or not getattr(t, "is_cuda", False) or str(t.dtype) != "torch.int64" \
+                    or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("{}: out.{} must be a contiguous int64 device tensor of shape {}".format(what, name, shape))
+    import torch
+    dev = fine.device if hasattr(fine, "data_ptr") else torch.device("cuda", torch.cuda.current_device())
+
+    def rows(x):
+        """x on the device with unit column stride -> (tensor, row stride)"""
+        if not hasattr(x, "data_ptr"):
+            return torch.from_numpy(np.ascontiguousarray(x)).to(dev), n
+        if n > 0 and M > 0 and (n == 1 or x.stride(1) == 1) and (M == 1 or x.stride(0) >= n):
+            return x, (n if M == 1 else int(x.stride(0)))
+        return x.contiguous(), n
+    f, ld = rows(fine)
+    c = None
+    if coarse is not None:
+        c, ld_c = rows(coarse)
+        if ld_c != ld:
+            f, c, ld = f.contiguous(), c.contiguous(), n
+    if out is None:
+        out = ConcordanceCounts(*[None if s is None else torch.zeros(s, dtype=torch.int64, device=dev) for s in shapes])
+    torch.cuda.current_stream(dev).synchronize()                    # the library reads and writes on its own stream
+    _concordance_into(f, c, M, n, ld, lower, upper, out.pair, out.all, out.kept, kernel_ms)
+    if device:
+        return out
+    return ConcordanceCounts(*[None if t is None else t.cpu().numpy() for t in out])
+
+
+_ORTHANT_RULE = {}
+
+
+def bivariate_orthant(h, k, rho, nodes=64):
+    """P(Z1 > h, Z2 > k) of standard normals with correlation rho, on the host, vectorised over arrays that broadcast: Plackett's
+    formula  Phi(-h) Phi(-k) + (1 / 2 pi) int_0^{asin rho} exp(-(h^2 + k^2 - 2 h k sin t) / (2 cos^2 t)) dt  with a fixed
+    Gauss-Legendre rule of `nodes` points.  The integrand is smooth on the closed interval for |rho| < 1 (64 nodes agree with
+    scipy.stats.multivariate_normal.cdf to 1e-16 absolute up to rho = 0.999 at the levels 0.9 and 0.99); rho = 1 and rho = -1
+    are taken as their limits Phi(-max(h, k)) and max(0, Phi(-k) - Phi(h)), not by the integral."""
+    from scipy import special
+    h, k, rho = np.broadcast_arrays(np.asarray(h, dtype=np.float64), np.asarray(k, dtype=np.float64), np.asarray(rho, dtype=np.float64))
+    if np.any(np.isnan(rho)) or np.any(np.abs(rho) > 1.0):
+        raise ValueError("bivariate_orthant: rho must lie in [-1, 1]")
+    if nodes not in _ORTHANT_RULE:
+        _ORTHANT_RULE[nodes] = np.polynomial.legendre.leggauss(int(nodes))
+    x, w = _ORTHANT_RULE[nodes]
+    inner = np.abs(rho) < 1.0
+    half = 0.5 * np.arcsin(np.where(inner, rho, 0.0))[..., None]
+    t = half * (1.0 + x)
+    hh, kk = h[..., None], k[..., None]
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = np.exp(-(hh * hh + kk * kk - 2.0 * hh * kk * np.sin(t)) / (2.0 * np.cos(t) ** 2))
+        integral = half[..., 0] * np.sum(w * f, axis=-1)
+    out = special.ndtr(-h) * special.ndtr(-k) + integral / (2.0 * np.pi)
+    out = np.where(rho >= 1.0, special.ndtr(-np.maximum(h, k)), out)
+    out = np.where(rho <= -1.0, np.maximum(0.0, special.ndtr(-k) - special.ndtr(h)), out)
+    return out if out.ndim else float(out)
+
+
 def _rvs(dist, n, seed, stream, first, antithetic, device, qmc=False):
     """the B = 1 call of `samples`"""
     return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device, qmc=qmc)[0]

@@ -104,9 +104,20 @@ passes over x -- in the same process, the two taking turns after a warm-up call 
                                5.4 TB/s of this package's own streaming kernels
   extras_equal_torch, linear_rel_diff_torch    the extreme and count rows equal torch's exactly; the linear rows differ from matmul by
                                its summation order
+--concordance: concordance_counts(..., device=True) on device-resident uniforms [M, n] with a coarse array and
+G = 3 events (u > 0.9, 0.95, 0.99), for M x n = 12 x 10^6, 64 x 10^6 and 256 x 10^5 (--config M,n: that shape alone), against the torch
+composition of the same counters -- the keep mask, the fp64 indicator matrices and three fp64 matmul Grams per event -- in the same
+process, the two taking turns after a warm-up call each (five repetitions unless --reps says otherwise):
+  entry_ms / torch_ms {min, mean, max}, torch_over_entry_wall   wall time of the whole route up to a device synchronise; the ratio of
+                               the means
+  bits_kernel_ms, gram_kernel_ms   HIP-event time of the streaming kernel and of the Gram kernel (median over the repetitions)
+  tbytes_per_s, fraction_of_hbm_peak   16 M n bytes, the one read of the inputs, over the time of the two kernels together, and that
+                               rate over the 8 TB/s of the data sheet
+  equal_torch                  every counter equals the composition's (exact while counts stay below 2^53)
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --scores |
-                                                              --conditional | --qmc | --boxprob | --boxdraws | --aggregates] [--reps K]"""
+                                                              --conditional | --qmc | --boxprob | --boxdraws | --aggregates |
+                                                              --concordance] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -787,6 +798,68 @@ def aggregates_shape(S, M, n, reps):
                 fraction_of_stream_rate=round(rate / STREAM_RATE, 3), extras_equal_torch=same_extras, linear_rel_diff_torch=lin_err)
 
 
+HBM_PEAK = 8.0e12        # bytes / s, MI355X data sheet
+
+
+def concordance_shape(M, n, reps, G=3):
+    """concordance_counts on device-resident uniforms with a coarse array against the torch composition, the two taking turns"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    fine = torch.rand((M, n), dtype=torch.float64, device=dev, generator=gen)
+    coarse = (fine + 0.02 * torch.randn((M, n), dtype=torch.float64, device=dev, generator=gen)).clamp_(0.0, 1.0)
+    fine[0, 5::1001] = float("nan")
+    probs = np.array([0.9, 0.95, 0.99])[:G]
+    lower, upper = probs[:, None] * np.ones((G, M)), np.full((G, M), np.inf)
+    lo_d = torch.from_numpy(lower).to(dev)
+    torch.cuda.synchronize()
+    ms = np.zeros(2)
+    kernel = []
+
+    def entry():
+        out = sd.concordance_counts(fine, coarse, lower, upper, device=True, kernel_ms=ms)
+        torch.cuda.synchronize()
+        kernel.append(ms.copy())
+        return out
+
+    def composition():
+        keep = ~(torch.isnan(fine).any(dim=0) | torch.isnan(coarse).any(dim=0))
+        pair = torch.empty((G, 3, M, M), dtype=torch.float64, device=dev)
+        all_ = torch.empty((G, 3), dtype=torch.float64, device=dev)
+        for g in range(G):
+            ef = ((fine > lo_d[g][:, None]) & keep).to(torch.float64)
+            ec = ((coarse > lo_d[g][:, None]) & keep).to(torch.float64)
+            # [J^f != J^c] = J^f + J^c - 2 J^f J^c, and sum_j J^f_ab J^c_ab is the Gram of the products e^f_a e^c_a: three Grams
+            fc = ef * ec
+            gf, gc, both = torch.matmul(ef, ef.T), torch.matmul(ec, ec.T), torch.matmul(fc, fc.T)
+            pair[g, 0], pair[g, 1], pair[g, 2] = gf, gc, gf + gc - 2.0 * both
+            af, ac = ef.prod(dim=0), ec.prod(dim=0)
+            all_[g, 0], all_[g, 1], all_[g, 2] = af.sum(), ac.sum(), (af != ac).sum()
+        kept = keep.sum()
+        torch.cuda.synchronize()
+        return pair, all_, kept
+
+    walls = [[], []]
+    for fn in (entry, composition):
+        fn()
+    kernel.clear()
+    for _ in range(reps):
+        for k, fn in enumerate((entry, composition)):
+            t0 = time.perf_counter()
+            fn()
+            walls[k].append((time.perf_counter() - t0) * 1e3)
+    got, ref = entry(), composition()
+    same = bool(torch.equal(got.pair.to(torch.float64), ref[0]) and torch.equal(got.all.to(torch.float64), ref[1])
+                and int(got.kept.item()) == int(ref[2].item()))
+    k_ms = np.median(np.array(kernel), axis=0)
+    rate = 16.0 * M * n / (float(k_ms.sum()) * 1e-3)
+    stats = lambda v: dict(min=round(min(v), 3), mean=round(sum(v) / len(v), 3), max=round(max(v), 3))
+    return dict(M=M, n=n, G=G, entry_ms=stats(walls[0]), torch_ms=stats(walls[1]),
+                torch_over_entry_wall=round(sum(walls[1]) / sum(walls[0]), 2), bits_kernel_ms=round(float(k_ms[0]), 4),
+                gram_kernel_ms=round(float(k_ms[1]), 4), tbytes_per_s=round(rate / 1e12, 3), fraction_of_hbm_peak=round(rate / HBM_PEAK, 3),
+                equal_torch=same)
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -831,12 +904,23 @@ def main():
     ap.add_argument("--boxdraws", action="store_true", help="event_samples against rejection from joint_samples (DESIGN.md section 3.5.18)")
     ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
+                                                               "fp64 Grams (DESIGN.md section 3.5.21)")
+    ap.add_argument("--reps", type=int, default=None)
     a = ap.parse_args()
+    if a.reps is None:
+        a.reps = 5 if a.concordance else 3
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.concordance:
+        shapes = [(12, 1_000_000), (64, 1_000_000), (256, 100_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(12, 10_000), (5, 1_000)]
+        out["concordance"] = [concordance_shape(M, n, a.reps) for M, n in shapes]
     elif a.aggregates:
         shapes = [(1, 12, 1_000_000), (1, 64, 1_000_000), (64, 12, 10_000)]
         if a.config:
