@@ -44,7 +44,8 @@ extern "C" {
                               *    mlmc_density_sample_conditional_batch, mlmc_sobol_table (and the flag MLMC_SAMPLE_SOBOL of the
                               *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch,
                               *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov,
-                              *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts */
+                              *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts,
+                              *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -514,6 +515,41 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
                                     const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                     int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
                                     int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
+/* ---- the Student-t copula (copula_t.hip) -- added within 8 -------------------------------------------------------------
+ * Two elementwise functions, one thread per element, unclamped; they are the definition that the sampling entry below refers to,
+ * and they exist as entries so that their accuracy can be tested at chosen arguments.  dof = nu is a double in [1, 64]; what
+ * depends on nu alone (the density at 0, log Gamma(nu / 2 + 1)) is made on the host once per call, in long double.
+ *   mlmc_student_t_cdf: u = T_nu(y), the CDF of Student's t.  For y <= 0 it is the lower tail with RELATIVE accuracy: with t = |y|,
+ *     t < min(1.2, sqrt(nu)): 1/2 - t f(0) (1 + t^2 / nu)^-(nu + 1)/2 sum_n ((nu + 1)/2)_n / (3/2)_n w^n, w = t^2 / (nu + t^2);
+ *     t < sqrt(nu): the continued fraction of I_x(nu / 2, 1/2) / 2, x = nu / (nu + t^2); beyond: its positive series in x <= 1/2.
+ *     For y > 0 it is 1 - T_nu(-y), one rounded subtraction, so that cdf(y) == 1 - cdf(-y) bit for bit.  0 / 1 at -inf / +inf,
+ *     NaN for NaN.
+ *   mlmc_chi2_mixing_scale: s = sqrt(nu / g), g the p-quantile of the chi-square law with nu degrees of freedom (Newton on the
+ *     logarithm of the regularised incomplete gamma function, lower or upper by the side of p); NaN for p outside (0, 1); finite
+ *     and positive for every odd multiple of 2^-53.  A standard normal times s with a uniform p is a Student-t variate.
+ * Every loop of both has a fixed upper trip count.  n = 0 is a no-op; dof outside [1, 64] or NaN, n < 0, a null array and a bad
+ * mem_kind are errors.  The arrays [n] are host or device by mem_kind. */
+int mlmc_student_t_cdf(double dof, int64_t n, const double *y, double *u_out, int mem_kind);
+int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out, int mem_kind);
+/* Seeded JOINT draws of M problems through a STUDENT-T copula with dof degrees of freedom -- added within 8.  Problems, rule, tables,
+ * the latent normals z[k][j], the chain acc = sum_k F[m][k] z[k][j] and Q_m are those of mlmc_density_sample_joint_batch, and so is
+ * every argument check, no-op, rule for degenerate problems, block rule and flag.  In addition:
+ *   Mixing uniform: p0[j] = uniform i of stream mix_stream under `seed` (the Philox uniform of mlmc_density_sample_batch), or under
+ *     MLMC_SAMPLE_SOBOL coordinate mix_stream (< 1024) of point j; i = j, or j >> 1 with MLMC_SAMPLE_ANTITHETIC: draws 2k and 2k + 1
+ *     then share s and negate z, an exact antithetic pair in y.  mix_stream equal to one of `streams` (NULL: k) is an error.
+ *   s[j] is bit for bit mlmc_chi2_mixing_scale(dof, p0[j]);  y = acc (x) s[j], ONE rounded multiplication after the chain has ended;
+ *   u = min(max(T, 2^-53), 1 - 2^-53) with T bit for bit mlmc_student_t_cdf(dof, y);  x = Q_m(u), bit for bit the quantile entry.
+ * s_out [n] (may be NULL) sits next to u_out and z_out (host or device by mem_kind).  u[m][j] depends on (seed, streams, mix_stream,
+ * j, flags, dof, row m of F) alone: not on M, the padding of K, n, first, the blocks, the memory kind or the launch geometry;
+ * first = 50, n = 100 gives columns [50, 150) of first = 0, n = 150.  dof outside [1, 64] or NaN is an error of the call.  The
+ * mixing scales of a block (8 bytes per draw) live next to the normals and uniforms, beyond the 192 MiB that size the block.
+ * mlmc_density_quantiles_kernel_time counts the mixing, normals, product, map and sampling kernels of a block and group as one
+ * launch.  Conditional draws, box probabilities and event scenarios under a t copula are not provided. */
+int mlmc_density_sample_joint_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                      int32_t K, const double *factor, double dof, uint64_t seed, const uint32_t *streams,
+                                      uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *out, double *u_out,
+                                      double *z_out, double *s_out, double *mass_out, int mem_kind);
 /* Seeded CONDITIONAL joint draws under the Gaussian copula, B sets of observed values at once -- added within 8.  The M problems
  * are the UNOBSERVED components; problems, rule, table, Q_m, the latent normals z[k][j] (seed, streams, first, n, flags) and every
  * argument up to `flags` are those of mlmc_density_sample_joint_batch.  With the conditional factor F [M][K] (host, row-major; the

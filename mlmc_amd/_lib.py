@@ -109,6 +109,11 @@ SIGNATURES = {
                                             C.c_int32, _vp, _vp, _vp, C.c_int]),
     "mlmc_density_sample_joint_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_uint64,
                                                   _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_density_sample_joint_t_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_double,
+                                                    C.c_uint64, _vp, C.c_uint32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                                    C.c_int]),
+    "mlmc_student_t_cdf": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
+    "mlmc_chi2_mixing_scale": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
     "mlmc_density_sample_conditional_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                                         C.c_uint64, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
                                                         _vp, _vp, _vp, _vp, C.c_int]),

@@ -46,7 +46,9 @@ __global__ __launch_bounds__(COP_NORMAL_THREADS) void k_cop_normals(uint64_t see
 // SHIFT (mlmc_density_sample_conditional_batch): set = blockIdx.z; the epilogue adds shift[set * set_rows + row] to the finished
 // chain, one rounded addition, and the tile goes to rows set * set_rows + row of U.  A lane's four rows are its registers' rows for
 // every J, so it loads its four shifts once, ahead of the panels, and the epilogue waits for no memory.
-template <bool SHIFT>
+// TSCALE (mlmc_density_sample_joint_t_batch): `shift` is the mixing scale s [ncols] of the draws; the epilogue multiplies the
+// finished chain by s[column], one rounded multiplication, and stores y itself: k_tcop_map (copula_t.hip) maps it in place.
+template <bool SHIFT, bool TSCALE = false>
 __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__restrict__ F, int M, int K, const double *__restrict__ Z,
                                                               int64_t ldz, int64_t ncols, double *__restrict__ U, int64_t ldu,
                                                               const double *__restrict__ shift, int64_t set_rows) {
@@ -107,6 +109,8 @@ __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__re
                 if (row < M && col < ncols)
                     U[((int64_t)blockIdx.z * set_rows + row) * ldu + col] =
                         fmin(fmax(normcdf(__dadd_rn(sh[r], acc[J][r])), 0x1p-53), 1.0 - 0x1p-53);
+            } else if constexpr (TSCALE) {
+                if (row < M && col < ncols) U[(int64_t)row * ldu + col] = __dmul_rn(acc[J][r], shift[col]);
             } else {
                 if (row < M && col < ncols) U[(int64_t)row * ldu + col] = fmin(fmax(normcdf(acc[J][r]), 0x1p-53), 1.0 - 0x1p-53);
             }
@@ -132,6 +136,17 @@ void cop_launch_uniforms(hipStream_t st, const double *F, int M, int K, const do
         const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE));
         hipLaunchKernelGGL(k_cop_uniforms<false>, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
                            U + (int64_t)m0 * ldu, ldu, (const double *)nullptr, (int64_t)0);
+    }
+}
+
+void cop_launch_scaled_product(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                               int64_t ldu, const double *s) {
+    constexpr int rows = 65535 * COP_TILE;
+    for (int m0 = 0; m0 < M; m0 += rows) {
+        const int Ml = std::min(M - m0, rows);
+        const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE));
+        hipLaunchKernelGGL((k_cop_uniforms<false, true>), grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
+                           U + (int64_t)m0 * ldu, ldu, s, (int64_t)0);
     }
 }
 

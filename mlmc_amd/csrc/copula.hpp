@@ -33,4 +33,28 @@ void cop_launch_uniforms(hipStream_t st, const double *F, int M, int K, const do
 void cop_launch_uniforms_shifted(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
                                  int64_t ldu, const double *shift, int B, int64_t set_rows);
 
+// ---- the Student-t copula (copula_t.hip) ----
+// what depends on nu alone, made on the host once per call (tcop_constants) and passed to the kernels by value
+struct TCopConst {
+    double dof, sqrt_dof;
+    double A;                          // (nu + 1) / 2
+    double c0;                         // Gamma((nu + 1) / 2) / (sqrt(nu pi) Gamma(nu / 2)): the t density at 0
+    double t_split;                    // |y| below: the centre series of student_t_cdf, from it on: the tail series
+    double a;                          // nu / 2
+    double lg_a1;                      // log Gamma(nu / 2 + 1)
+};
+TCopConst tcop_constants(double dof);
+// 0, or 1 with the error set: dof must lie in [1, 64] (NaN is outside)
+int tcop_check_dof(const char *fn, double dof);
+// s[c] = chi2_mixing_scale(nu, p0 of draw first + c), c < ncols (k_cop_mixing): p0 = uniform j (antithetic: j >> 1) of `stream`
+// under `seed`, or with sobol_row (device, [SOBOL_ROW]) the coordinate of point j in that row's dimension
+void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32_t stream, const uint64_t *sobol_row, int64_t first,
+                       int64_t ncols, int antithetic, double *s);
+// U[m * ldu + c] = (sum_k F[m * K + k] Z[k * ldz + c]) (x) s[c], m < M, c < ncols (k_cop_uniforms, the TSCALE instance): the sum as
+// above, then one rounded multiplication; all device
+void cop_launch_scaled_product(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                               int64_t ldu, const double *s);
+// U[m * ldu + c] = clamp(student_t_cdf(nu, U[m * ldu + c])) in place, m < M, c < ncols (k_tcop_map)
+void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, double *U, int64_t ldu);
+
 }  // namespace mlmc

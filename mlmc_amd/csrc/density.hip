@@ -838,7 +838,7 @@ struct QBlock {
     const QProb *probs;               // device
     const double *coef, *gx, *gw;     // device
     double *h_in[2], *d_in[2];        // staged point arrays: pinned and device side
-    double *d[6];                     // device only
+    double *d[7];                     // device only
     double *h[1];                     // pinned only
     size_t head_bytes, in_bytes;      // up to the end of the Gauss rule / of the staged arrays
     bool direct;
@@ -1212,6 +1212,13 @@ struct QSets {
     int32_t ld_rows;
 };
 
+// the Student-t copula of mlmc_density_sample_joint_t_batch: y = (F z) s with the mixing scale s[j] of draw j (copula_t.hip)
+struct QTCop {
+    double dof;
+    uint32_t mix_stream;
+    double *s_out;                    // [n] or NULL
+};
+
 // mlmc_density_sample_joint_batch (sets == NULL) and mlmc_density_sample_conditional_batch: draws of M problems joined by a
 // Gaussian copula.  Table, masses and inversion are those of q_on_rule's sampling branch; the uniforms come from copula.hip
 // instead of q_uniform.  The draws are processed in blocks of nb columns: latent normals Z [K][nb], copula uniforms U [M][nb],
@@ -1222,15 +1229,19 @@ struct QSets {
 // SETS instance of k_q_sample inverts them and writes draw and uniform at row rows[m] of set b.  Host arrays are staged compactly
 // ([B][M][n]) and come back in runs of consecutive rows, so the rows that `rows` does not name are not touched.  No value
 // depends on B.
+// The joint t entry (tc != NULL, sets == NULL): the mixing scales s [nb] of the block come first (k_cop_mixing), the product stores
+// y = (F z) s in U (the TSCALE instance of k_cop_uniforms) and k_tcop_map maps U in place; s lives next to Z in the workspace, beyond
+// the bound that sizes the block (8 bytes per draw), unless the caller's device array takes it.
 static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
                     const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf, const double *factor,
                     uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, const QSets *sets, double *out,
-                    double *u_out, double *z_out, double *mass_out, int mem_kind) {
+                    double *u_out, double *z_out, double *mass_out, int mem_kind, const QTCop *tc = nullptr) {
     if (const int r = q_head(fn, "M", M, bases && R1 && lambda && sigma && a && b)) return r > 0;
     int nint, deg;
     if (q_rule(fn, n_intervals, gauss_degree, nint, deg, mem_kind)) return 1;
     if (q_sample_flags(fn, flags)) return 1;
     const bool sobol = flags & MLMC_SAMPLE_SOBOL;
+    if (tc && tcop_check_dof(fn, tc->dof)) return 1;
     if (Kf < 1) return fail(std::string(fn) + ": K < 1");
     if (!factor) return fail(std::string(fn) + ": null factor");
     if (n < 0) return fail(std::string(fn) + ": n < 0");
@@ -1241,6 +1252,15 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     std::vector<uint64_t> sobol_tab;
     std::vector<uint32_t> sobol_slot;
     if (sobol && sobol_call_table(fn, "latent normal", seed, streams, Kf, sobol_tab, sobol_slot)) return 1;
+    // the mixing variable must not share its uniforms with a latent normal; under MLMC_SAMPLE_SOBOL it has a table row of its own
+    std::vector<uint64_t> mix_tab;
+    std::vector<uint32_t> mix_slot;
+    if (tc) {
+        for (int k = 0; k < Kf; ++k)
+            if ((streams ? streams[k] : (uint32_t)k) == tc->mix_stream)
+                return fail(std::string(fn) + ": mix_stream equals the stream of latent normal " + std::to_string(k));
+        if (sobol && sobol_call_table(fn, "mixing variable", seed, &tc->mix_stream, 1, mix_tab, mix_slot)) return 1;
+    }
     const int32_t B = sets ? sets->B : 1;
     const int32_t *rows = sets ? sets->rows : nullptr;
     const int32_t ld_rows = sets ? sets->ld_rows : M;
@@ -1292,6 +1312,7 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     }
     nb = std::min(nb, std::max<int64_t>(n, 1));
     const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && (sets || !(mem_kind == MLMC_DEVICE && u_out));
+    const bool s_ws = tc && n > 0 && !(mem_kind == MLMC_DEVICE && tc->s_out);
     // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts of the sets | the Sobol' table
     // (uint64); a call without draws sends the draws table alone
     QPack pack;
@@ -1300,10 +1321,11 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     for (size_t k = 0; k < sv.size(); ++k) sv[k] = sobol ? sobol_slot[k] : streams ? streams[k] : (uint32_t)k;
     const size_t at_streams = pack.add(sv.data(), sv.size()), at_factor = pack.add(factor, n > 0 ? (size_t)M * Kf : 0);
     const size_t at_shift = sets ? pack.add(sets->shift, n > 0 ? BM : 0) : 0, at_sobol = pack.add(sobol_tab.data(), n > 0 ? sobol_tab.size() : 0);
+    const size_t at_mix = pack.add(mix_tab.data(), n > 0 ? mix_tab.size() : 0);
     const size_t n_in = pack.data.size(), n_stage = stage ? BM * (size_t)n : 0;
     QBlock K;
     if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, n_stage, u_ws ? BM * (size_t)nb : 0, z_ws ? (size_t)Kf * (size_t)nb : 0,
-                                sets && u_out ? n_stage : 0},
+                                sets && u_out ? n_stage : 0, s_ws ? (size_t)nb : 0},
                 {(size_t)M}, K))
         return 1;
     if (K.upload({pack.data.data()}, n_in)) return 1;
@@ -1311,6 +1333,8 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     const uint32_t *d_streams = pack.at<uint32_t>(K, at_streams);
     const double *d_factor = pack.at<double>(K, at_factor), *d_shift = pack.at<double>(K, at_shift);
     const uint64_t *d_sobol = pack.at<uint64_t>(K, at_sobol);
+    const uint64_t *d_mix = tc && sobol ? pack.at<uint64_t>(K, at_mix) : nullptr;
+    const TCopConst tconst = tc ? tcop_constants(tc->dof) : TCopConst{};
     double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
     // the uniforms k_q_sample writes next to the draws: those of the sets; the joint entry's U is the output itself
     double *d_u = !sets ? nullptr : stage && u_out ? K.d[5] : u_out;
@@ -1324,14 +1348,20 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
             // the block's Z and U: in the caller's device arrays at column c0 (row length n), or in the workspace (row length nb)
             double *Z = z_ws ? K.d[4] : z_out + c0, *U = u_ws ? K.d[3] : u_out + c0;
             const int64_t ldz = z_ws ? nb : n, ldu = u_ws ? nb : n;
+            double *Sc = !tc ? nullptr : s_ws ? K.d[6] : tc->s_out + c0;
             tm.begin(st);
+            if (tc && (g0 == 0 || s_ws))       // as the normals below
+                cop_launch_mixing(st, tconst, seed, tc->mix_stream, d_mix, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Sc);
             if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
                 cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
             else if (g0 == 0 || z_ws)
                 cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
             if (sets)
                 cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, d_shift + g0, B, M);
-            else
+            else if (tc) {
+                cop_launch_scaled_product(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, Sc);
+                cop_launch_t_map(st, tconst, np_g, nc, U + (int64_t)g0 * ldu, ldu);
+            } else
                 cop_launch_uniforms(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu);
             unsigned threads, gy;
             L.geometry((int64_t)B * np_g * nc, nc, threads, gy);
@@ -1346,6 +1376,8 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
             if (stage && z_out && g0 == 0)
                 MLMC_HIP_CHECK(hipMemcpy2DAsync(z_out + c0, sizeof(double) * n, Z, sizeof(double) * ldz, sizeof(double) * nc, (size_t)Kf,
                                                 hipMemcpyDeviceToHost, st));
+            if (tc && stage && tc->s_out && g0 == 0)
+                MLMC_HIP_CHECK(hipMemcpyAsync(tc->s_out + c0, Sc, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
             if (!sets && stage && u_out)
                 MLMC_HIP_CHECK(hipMemcpy2DAsync(u_out + (int64_t)g0 * n + c0, sizeof(double) * n, U + (int64_t)g0 * ldu, sizeof(double) * ldu,
                                                 sizeof(double) * nc, (size_t)np_g, hipMemcpyDeviceToHost, st));
@@ -1665,6 +1697,17 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
     MLMC_API_GUARD;
     return q_copula("mlmc_density_sample_joint_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
                     streams, first, n, flags, nullptr, out, u_out, z_out, mass_out, mem_kind);
+}
+
+int mlmc_density_sample_joint_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                      const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
+                                      int32_t K, const double *factor, double dof, uint64_t seed, const uint32_t *streams,
+                                      uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *out, double *u_out,
+                                      double *z_out, double *s_out, double *mass_out, int mem_kind) {
+    MLMC_API_GUARD;
+    const QTCop tc{dof, mix_stream, s_out};
+    return q_copula("mlmc_density_sample_joint_t_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
+                    streams, first, n, flags, nullptr, out, u_out, z_out, mass_out, mem_kind, &tc);
 }
 
 int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,

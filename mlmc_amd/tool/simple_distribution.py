@@ -480,8 +480,83 @@ def correlation_factor(corr, min_eig=1e-10):
     return factor, CorrelationFactorInfo(min_eig_in, repaired, float(np.max(np.abs(factor @ factor.T - c))))
 
 
+def _check_dof(what, dof):
+    """None for the Gaussian copula (dof None or +inf), else nu as a float in [1, 64]"""
+    if dof is None:
+        return None
+    try:
+        nu = float(dof)
+    except (TypeError, ValueError):
+        nu = np.nan
+    if isinstance(dof, (bool, np.bool_)) or not (nu == np.inf or 1.0 <= nu <= 64.0):
+        raise ValueError("{}: dof must lie in [1, 64] (None or inf: the Gaussian copula), got {!r}".format(what, dof))
+    return None if nu == np.inf else nu
+
+
+def _t_elementwise(what, entry, x, dof, device):
+    """one of the elementwise entries of the t copula on a NumPy array or a float64 device tensor of any shape"""
+    nu = _check_dof(what, dof)
+    if nu is None:
+        raise ValueError(what + ": dof must be finite, in [1, 64]")
+    if hasattr(x, "data_ptr"):
+        import torch
+        if not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError(what + ": the argument must be a NumPy array or a float64 device tensor")
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        torch.cuda.current_stream(x.device).synchronize()           # the library reads and writes on its own stream
+        _lib.check(getattr(_lib.lib(), entry)(nu, int(x.numel()), _lib.ptr(x), _lib.ptr(out), _lib.DEVICE))
+        return out if device else out.cpu().numpy()
+    shape = np.shape(x)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    out = np.empty_like(x)
+    _lib.check(getattr(_lib.lib(), entry)(nu, int(x.size), _lib.ptr(x), _lib.ptr(out), _lib.HOST))
+    out = out.reshape(shape)
+    if device:
+        import torch
+        return torch.from_numpy(out).to(torch.device("cuda", torch.cuda.current_device()))
+    return out if out.ndim else float(out)
+
+
+def student_t_cdf(y, dof, device=False):
+    """The CDF of Student's t with `dof` degrees of freedom (a float in [1, 64]) on the device, elementwise
+    (mlmc_student_t_cdf): the function that the t copula of `joint_samples(dof=...)` maps with.  Relative accuracy in the lower
+    tail; cdf(y) == 1 - cdf(-y) bit for bit for y > 0; 0 / 1 at -inf / +inf, NaN for NaN.
+    :param y: a NumPy array or a float64 torch device tensor of any shape
+    :param device: return a float64 torch device tensor"""
+    return _t_elementwise("student_t_cdf", "mlmc_student_t_cdf", y, dof, device)
+
+
+def chi2_mixing_scale(p, dof, device=False):
+    """s = sqrt(dof / g) with g the p-quantile of the chi-square law with `dof` degrees of freedom (a float in [1, 64]) on the
+    device, elementwise (mlmc_chi2_mixing_scale): a standard normal times s, p uniform, is a Student-t variate.  NaN for p
+    outside (0, 1).
+    :param p: a NumPy array or a float64 torch device tensor of any shape
+    :param device: return a float64 torch device tensor"""
+    return _t_elementwise("chi2_mixing_scale", "mlmc_chi2_mixing_scale", p, dof, device)
+
+
+def _mixing_stream(what, dof, mix_stream, streams, K):
+    """the stream of the mixing variable of a t copula, checked against the streams of the latent normals (None: stream k = k,
+    and then K is the default)"""
+    if dof is None:
+        if mix_stream is not None:
+            raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
+        return None
+    if mix_stream is None:
+        if streams is not None:
+            raise ValueError(what + ": with explicit streams, mix_stream must be given too")
+        return K
+    if isinstance(mix_stream, (bool, np.bool_)) or int(mix_stream) != mix_stream or not 0 <= int(mix_stream) < 2 ** 32:
+        raise ValueError(what + ": mix_stream must be an integer in 0 .. 2^32 - 1")
+    used = np.arange(K) if streams is None else np.asarray(streams)
+    if np.any(used.astype(np.uint64) == np.uint64(int(mix_stream))):
+        raise ValueError("{}: mix_stream {} is the stream of a latent normal".format(what, int(mix_stream)))
+    return int(mix_stream)
+
+
 def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0, antithetic=False, device=False,
-                  return_uniforms=False, return_normals=False, qmc=False):
+                  return_uniforms=False, return_normals=False, qmc=False, dof=None, mix_stream=None, return_mixing=False):
     """Seeded JOINT draws from many distributions through ONE device call (mlmc_density_sample_joint_batch): a Gaussian copula
     over the marginals.  With K latent standard normals z and a factor F [M, K] of the correlation matrix of the normal scores,
         x[m, j] = Q_m(u[m, j]),   u = clamp(Phi(F z)),
@@ -503,12 +578,24 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         (any first and n are allowed).  For an error bar repeat with R seeds: the seeds give independent scrambles, and the sample
         standard deviation of the R means estimates the error of their mean.  Not together with antithetic
     :param device: return float64 torch device tensors
-    :param return_uniforms, return_normals: also return u [M, n] and / or z [K, n], in this order
+    :param dof: None or np.inf: the Gaussian copula above, bit for bit what it has always been.  A float in [1, 64]: a STUDENT-T
+        copula with that many degrees of freedom (mlmc_density_sample_joint_t_batch), which has tail dependence:
+            u = clamp(T_dof(s F z)),   s = sqrt(dof / chi2_dof) = chi2_mixing_scale(p0, dof),
+        one mixing uniform p0 per draw (with antithetic one per pair, so that the pair negates y exactly), T_dof of
+        `student_t_cdf`.  F is a factor of the copula's correlation matrix: for a t copula the correlation of the normal scores is
+        NOT that matrix; `Estimate.estimate_quadrant_correlation` estimates it consistently.  Conditional draws, box
+        probabilities and event scenarios exist for the Gaussian copula only
+    :param mix_stream: the uint32 stream (qmc: the dimension, below 1024) of the mixing uniform; default K when `streams` is
+        defaulted; with explicit `streams` it must be given and differ from all of them
+    :param return_uniforms, return_normals, return_mixing: also return u [M, n], z [K, n] and / or s [n] (dof only), in this order
     :return: draws [M, n]; every distribution must use the same quadrature"""
     distrs = list(distrs)
     M = len(distrs)
     flags = _sample_flags("joint_samples", antithetic, qmc)
     _check_seed("joint_samples", seed)
+    dof = _check_dof("joint_samples", dof)
+    if return_mixing and dof is None:
+        raise ValueError("joint_samples: return_mixing needs dof (the Gaussian copula has no mixing variable)")
     if (corr is None) == (factor is None):
         raise ValueError("joint_samples: exactly one of corr and factor must be given")
     if M == 0:
@@ -522,14 +609,22 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         raise ValueError("joint_samples: the factor must be [M, K] with M = {} distributions, got shape {}".format(M, factor.shape))
     K = factor.shape[1]
     streams = _checked_streams("joint_samples", streams, K, "latent normal")
+    mix_stream = _mixing_stream("joint_samples", dof, mix_stream, streams, K)
     n_int, deg = _common_quadrature("joint_samples", distrs)
     handles, r1, lam, sig = _batch_problem_args(distrs)
     a, b = _domain_arrays(distrs)
-    (out, u, z), kind = _output_arrays(device, [(M, n), (M, n) if return_uniforms else None, (K, n) if return_normals else None])
-    _lib.check(_lib.lib().mlmc_density_sample_joint_batch(
-        M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg, K,
-        _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, flags, _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
-    extra = tuple(v for v, want in ((u, return_uniforms), (z, return_normals)) if want)
+    (out, u, z, s), kind = _output_arrays(device, [(M, n), (M, n) if return_uniforms else None, (K, n) if return_normals else None,
+                                                   (n,) if return_mixing else None])
+    if dof is None:
+        _lib.check(_lib.lib().mlmc_density_sample_joint_batch(
+            M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg, K,
+            _lib.ptr(factor), int(seed), _lib.ptr(streams), first, n, flags, _lib.ptr(out), _lib.ptr(u), _lib.ptr(z), None, kind))
+    else:
+        _lib.check(_lib.lib().mlmc_density_sample_joint_t_batch(
+            M, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b), n_int, deg, K,
+            _lib.ptr(factor), dof, int(seed), _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(out), _lib.ptr(u), _lib.ptr(z),
+            _lib.ptr(s), None, kind))
+    extra = tuple(v for v, want in ((u, return_uniforms), (z, return_normals), (s, return_mixing)) if want)
     return (out,) + extra if extra else out
 
 
@@ -1367,7 +1462,8 @@ def _check_tail_name(what, tail):
 
 
 def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, members=None, extremes=(), corr=None, factor=None,
-                     given=None, streams=None, first=0, antithetic=False, qmc=False, block=2 ** 20, device=False):
+                     given=None, streams=None, first=0, antithetic=False, qmc=False, block=2 ** 20, device=False, dof=None,
+                     mix_stream=None):
     """`scenario_aggregates` of the scenarios of `joint_samples` (with `given`: of `conditional_samples`) WITHOUT the scenario
     matrix: the draw indices first .. first + n - 1 are walked in blocks of `block` columns, each block is drawn on the device,
     reduced there and dropped; only the aggregate rows are kept.  At M = 64 and n = 10^8 the matrix would be 51 GB, the result a
@@ -1380,12 +1476,19 @@ def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, memb
         hold the given values)
     :param block: columns per device block, >= 1 (with antithetic an even number)
     :param device: return the rows as a float64 torch device tensor
+    :param dof, mix_stream: the Student-t copula of `joint_samples`; not together with `given` (conditional draws exist under the
+        Gaussian copula only)
     :return: Aggregates(rows [Q, n], or [B, Q, n] for arrays in `given`; names)"""
     what = "joint_aggregates"
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
+    dof = _check_dof(what, dof)
+    if dof is not None and given is not None:
+        raise ValueError(what + ": dof together with given: conditional draws exist under the Gaussian copula only")
+    if dof is None and mix_stream is not None:
+        raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
     _sample_flags(what, antithetic, qmc)
     _check_seed(what, seed)
     if (corr is None) == (factor is None):
@@ -1419,7 +1522,7 @@ def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, memb
         nb = min(int(block), n - off)
         if given is None:
             x = joint_samples(distrs, nb, seed, factor=factor, streams=streams, first=first + off, antithetic=antithetic, device=True,
-                              qmc=qmc)
+                              qmc=qmc, dof=dof, mix_stream=mix_stream)
         else:
             x = conditional_samples(distrs, nb, seed, given, factor_info=cond, streams=streams, first=first + off,
                                     antithetic=antithetic, device=True, qmc=qmc)
@@ -1654,6 +1757,109 @@ def bivariate_orthant(h, k, rho, nodes=64):
     out = np.where(rho >= 1.0, special.ndtr(-np.maximum(h, k)), out)
     out = np.where(rho <= -1.0, np.maximum(0.0, special.ndtr(-k) - special.ndtr(h)), out)
     return out if out.ndim else float(out)
+
+
+_T_ORTHANT_RULE = {}
+
+
+def _t_orthant_rule(nodes=96):
+    """Gauss-Legendre panels in the probability of the mixing variable: (lower-tail probabilities, upper-tail probabilities,
+    weights of both), with breaks at 1e-6, 1e-3, 0.05, 0.5 from either end"""
+    if nodes not in _T_ORTHANT_RULE:
+        x, w = np.polynomial.legendre.leggauss(int(nodes))
+        breaks = (0.0, 1e-6, 1e-3, 0.05, 0.5)
+        pp = np.concatenate([0.5 * (lo + hi) + 0.5 * (hi - lo) * x for lo, hi in zip(breaks[:-1], breaks[1:])])
+        ww = np.concatenate([0.5 * (hi - lo) * w for lo, hi in zip(breaks[:-1], breaks[1:])])
+        _T_ORTHANT_RULE[nodes] = (pp, ww)
+    return _T_ORTHANT_RULE[nodes]
+
+
+def bivariate_t_orthant(h, k, rho, dof):
+    """P(T1 > h, T2 > k) of a bivariate Student-t pair with correlation parameter rho and `dof` degrees of freedom, on the host,
+    vectorised over h, k, rho that broadcast (dof is one number).  (T1, T2) = (Z1, Z2) / sqrt(W) with W = chi2_dof / dof, so
+        P = E_W[ bivariate_orthant(h sqrt(W), k sqrt(W), rho) ],
+    taken by Gauss-Legendre panels in the probability of W (breaks at 1e-6, 1e-3, 0.05, 0.5 and their mirrors, 96 nodes each;
+    W from the inverse incomplete gamma function of the nearer tail).  T1 and T2 share W, so they are dependent also at rho = 0:
+    the value is then NOT the product of the marginals.  dof = np.inf returns `bivariate_orthant` itself; |rho| = 1 gives the
+    limits, as there.  At h = k = 0 the value is 1/4 + asin(rho) / (2 pi) for every dof."""
+    from scipy import special
+    if isinstance(dof, (bool, np.bool_)) or np.ndim(dof) != 0 or not float(dof) > 0.0:
+        raise ValueError("bivariate_t_orthant: dof must be one positive number (np.inf: the normal orthant)")
+    nu = float(dof)
+    if nu == np.inf:
+        return bivariate_orthant(h, k, rho)
+    h, k, rho = np.broadcast_arrays(np.asarray(h, dtype=np.float64), np.asarray(k, dtype=np.float64), np.asarray(rho, dtype=np.float64))
+    if np.any(np.isnan(rho)) or np.any(np.abs(rho) > 1.0):
+        raise ValueError("bivariate_t_orthant: rho must lie in [-1, 1]")
+    pp, ww = _t_orthant_rule()
+    a = 0.5 * nu
+    root = np.sqrt(np.concatenate([special.gammaincinv(a, pp), special.gammainccinv(a, pp)]) / a)        # sqrt(W) at the nodes
+    weights = np.concatenate([ww, ww])
+    out = np.zeros(h.shape)
+    flat_h, flat_k, flat_r, flat_o = h.reshape(-1), k.reshape(-1), rho.reshape(-1), out.reshape(-1)
+    step = 256                                                       # points per slab: [step, nodes of W, nodes of the orthant]
+    for i in range(0, flat_h.size, step):
+        sl = slice(i, i + step)
+        vals = bivariate_orthant(flat_h[sl, None] * root, flat_k[sl, None] * root, flat_r[sl, None])
+        flat_o[sl] = np.sum(np.atleast_2d(vals) * weights, axis=-1)
+    return out if out.ndim else float(out)
+
+
+CopulaDofFit = collections.namedtuple("CopulaDofFit", "dof grid objective z")
+COPULA_DOF_GRID = (2, 3, 4, 5, 6, 8, 10, 15, 20, 30, np.inf)
+
+
+def _dof_grid(what, grid):
+    """the candidate nu of a fit as a float64 array: finite values in [1, 64], np.inf for the Gaussian copula"""
+    try:
+        g = np.array([float(v) for v in grid], dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        g = np.array([np.nan])
+    if g.size == 0 or not np.all((g == np.inf) | ((g >= 1.0) & (g <= 64.0))):
+        raise ValueError(what + ": the grid must hold values in [1, 64] or np.inf")
+    return g
+
+
+def fit_copula_dof(prob, var, probs, corr, grid=COPULA_DOF_GRID):
+    """The degrees of freedom of a Student-t copula from pair concordance frequencies, on the host: for every nu of `grid` the
+    frequencies are held against the t orthant, and the nu with the smallest sum of squared z wins.  The frequencies do not
+    depend on nu, so one pass over the samples serves the whole grid.
+    :param prob, var: [G, M, M]: the estimate of P(U_a and U_b both beyond level p_g) and its variance
+        (`Estimate.estimate_tail_dependence`, quantity_estimate.concordance_statistics)
+    :param probs: [G] the levels p_g (an event u < 1 - p has the same model value as u > p, by symmetry)
+    :param corr: [M, M] the copula's correlation matrix
+    :param grid: candidate nu: finite values in [1, 64], np.inf for the Gaussian copula
+    :return: CopulaDofFit(dof, grid, objective [len(grid)], z [len(grid), G, M, M]): z = (prob - model) / sqrt(var) with model =
+        `bivariate_t_orthant` at h = k = T_nu^-1(p) and corr_ab, NaN on the diagonal and where var is not positive and finite;
+        objective = the sum of z^2 over the pairs a < b and the events; dof = its argmin, a tie goes to the larger nu"""
+    from scipy import special
+    what = "fit_copula_dof"
+    prob, var = np.asarray(prob, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    corr = np.asarray(corr, dtype=np.float64)
+    if prob.ndim != 3 or prob.shape[1] != prob.shape[2] or var.shape != prob.shape:
+        raise ValueError("{}: prob and var must be [G, M, M], got {} and {}".format(what, prob.shape, var.shape))
+    G, M = prob.shape[0], prob.shape[1]
+    if p.shape != (G,) or not np.all((p > 0.0) & (p < 1.0)):
+        raise ValueError("{}: probs must be {} probability levels in (0, 1)".format(what, G))
+    if corr.shape != (M, M) or not np.all(np.isfinite(corr)):
+        raise ValueError("{}: corr must be a finite [{}, {}] matrix".format(what, M, M))
+    g = _dof_grid(what, grid)
+    rho = np.clip(corr, -1.0, 1.0)[None]
+    z = np.full((g.size, G, M, M), np.nan)
+    objective = np.empty(g.size)
+    good = np.isfinite(var) & (var > 0.0) & np.triu(np.ones((M, M), dtype=bool), 1)[None]
+    for i, nu in enumerate(g):
+        h = (special.ndtri(p) if nu == np.inf else special.stdtrit(nu, p))[:, None, None]
+        model = bivariate_t_orthant(h, h, rho, nu)
+        with np.errstate(all="ignore"):
+            zi = np.where(np.isfinite(var) & (var > 0.0), (prob - model) / np.sqrt(var), np.nan)
+        zi[:, np.arange(M), np.arange(M)] = np.nan
+        z[i] = zi
+        objective[i] = float(np.sum(zi[good] ** 2))
+    best = np.flatnonzero(objective == np.min(objective))
+    dof = float(np.max(g[best])) if best.size else np.nan
+    return CopulaDofFit(dof, g, objective, z)
 
 
 def _rvs(dist, n, seed, stream, first, antithetic, device, qmc=False):

@@ -75,6 +75,14 @@ R1 = 25, for (B, n) = (1, 10^6), (64, 10^4), (1024, 10^3) against a Python loop 
   conditional_ms / loop_ms / joint_ms           wall time of the whole route up to a device synchronise, [min, median, max]
   conditional_kernel_ms / loop_kernel_ms / joint_kernel_ms   HIP-event time of one route's point kernels (normals, uniforms, sampling)
   loop_over_conditional_wall / conditional_over_joint_wall   ratios of the median wall times
+--tcopula: simple_distribution.joint_samples(..., dof=nu, device=True), the Student-t copula, against the
+same call without dof (the Gaussian entry) on the shapes of --joint with K = M, nu = 3 and 30, the two taking turns in one process
+after a warm-up each, five repetitions:
+  t_ms / gauss_ms                   wall time of the whole route up to a device synchronise, [min, mean, max]
+  t_kernel_ms / gauss_kernel_ms     HIP-event time of one call's point kernels (mixing, normals, product, map, sampling)
+  map_entry_ms / mixing_entry_ms    wall time of student_t_cdf on M n device values of the t law and of chi2_mixing_scale on n device
+                                    uniforms: the map and the mixing kernel on their own, with the entry's launch and wait
+  t_over_gauss_wall / t_over_gauss_kernel   ratios of the means
 --qmc: (a) samples, joint_samples and conditional_samples (device=True) with and without qmc=True on the
 shapes of --samples, --joint and --conditional (streams = index mod 1024 for both variants), the two taking turns after a warm-up
 call each:
@@ -115,7 +123,7 @@ process, the two taking turns after a warm-up call each (five repetitions unless
                                rate over the 8 TB/s of the data sheet
   equal_torch                  every counter equals the composition's (exact while counts stay below 2^53)
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
-                                                             [--tails | --divergences | --moments | --samples | --joint | --scores |
+                                                             [--tails | --divergences | --moments | --samples | --joint | --tcopula | --scores |
                                                               --conditional | --qmc | --boxprob | --boxdraws | --aggregates |
                                                               --concordance] [--reps K]"""
 import argparse
@@ -452,6 +460,66 @@ def joint_shape(M, R1, n, K, reps):
                 joint_kernel_ms=span(kern[0]), samples_kernel_ms=span(kern[1]), quantiles_kernel_ms=span(kern[2]),
                 joint_over_samples_wall=round(mean(wall[0]) / mean(wall[1]), 3), torch_over_joint_wall=round(mean(wall[2]) / mean(wall[0]), 3),
                 all_success=ok)
+
+
+def tcopula_shape(M, R1, n, K, dof, reps):
+    """joint_samples(dof=...) against joint_samples of the same shape (the Gaussian entry), the two taking turns in one process
+    after a warm-up each; and the elementwise entries on arrays of the call's sizes, which are the map and the mixing kernels on
+    their own: student_t_cdf on M n values y = z s of the t law, chi2_mixing_scale on n uniforms"""
+    distrs, ok = mixtures(M, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    rng = np.random.default_rng(7)
+    A = rng.standard_normal((M, M + 3))
+    c = A @ A.T
+    d = 1.0 / np.sqrt(np.diag(c))
+    factor = sd.correlation_factor(c * d[:, None] * d[None, :])[0][:, :K] if K == M else None
+    if factor is None:
+        factor = rng.standard_normal((M, K))
+        factor = np.ascontiguousarray(factor / np.sqrt(np.sum(factor * factor, axis=1))[:, None])
+    seed = [1000 * M + R1]
+
+    def t_route():
+        seed[0] += 1
+        x = sd.joint_samples(distrs, n, seed[0], factor=factor, device=True, dof=dof)
+        torch.cuda.synchronize()
+        return x
+
+    def gauss_route():
+        seed[0] += 1
+        x = sd.joint_samples(distrs, n, seed[0], factor=factor, device=True)
+        torch.cuda.synchronize()
+        return x
+    p0 = torch.rand(n, dtype=torch.float64, device="cuda").clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+    y = torch.randn(M, n, dtype=torch.float64, device="cuda") * sd.chi2_mixing_scale(p0, dof, device=True)[None, :]
+
+    def map_route():
+        u = sd.student_t_cdf(y, dof, device=True)
+        torch.cuda.synchronize()
+        return u
+
+    def mixing_route():
+        s = sd.chi2_mixing_scale(p0, dof, device=True)
+        torch.cuda.synchronize()
+        return s
+    routes = (t_route, gauss_route, map_route, mixing_route)
+    for fn in routes:
+        fn()
+    wall, kern = [[] for _ in routes], [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    mean = lambda t: sum(t) / len(t)
+    return dict(M=M, R1=R1, n=n, K=K, dof=dof, t_ms=span(wall[0]), gauss_ms=span(wall[1]), t_kernel_ms=span(kern[0]),
+                gauss_kernel_ms=span(kern[1]), map_entry_ms=span(wall[2]), mixing_entry_ms=span(wall[3]),
+                t_over_gauss_wall=round(mean(wall[0]) / mean(wall[1]), 3),
+                t_over_gauss_kernel=round(mean(kern[0]) / mean(kern[1]), 3), all_success=ok)
 
 
 def conditional_shape(M, R1, B, n, reps):
@@ -893,6 +961,8 @@ def main():
     ap.add_argument("--samples", action="store_true", help="samples against torch.rand + quantiles (DESIGN.md section 3.5.12)")
     ap.add_argument("--joint", action="store_true", help="joint_samples against samples and torch.randn + matmul + ndtr + quantiles "
                                                          "(DESIGN.md section 3.5.13)")
+    ap.add_argument("--tcopula", action="store_true", help="joint_samples(dof=3, 30) against the Gaussian entry of the same shape, and "
+                                                           "the map and mixing functions on their own (DESIGN.md section 3.5.22)")
     ap.add_argument("--scores", action="store_true", help="normal_scores against cdfs_on_rule + torch ndtri, and estimate_score_correlation "
                                                           "against estimate_component_covariance (DESIGN.md section 3.5.14)")
     ap.add_argument("--conditional", action="store_true", help="conditional_samples of B sets against a loop of single-set calls and "
@@ -909,7 +979,7 @@ def main():
     ap.add_argument("--reps", type=int, default=None)
     a = ap.parse_args()
     if a.reps is None:
-        a.reps = 5 if a.concordance else 3
+        a.reps = 5 if a.concordance or a.tcopula else 3
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
@@ -965,6 +1035,13 @@ def main():
         elif a.quick:
             shapes = [(4, 9, 10_000, 2)]
         out["scores"] = [scores_shape(M, R1, n, a.reps, levels) for M, R1, n, levels in shapes]
+    elif a.tcopula:
+        shapes = [(12, 25, 1_000_000, 12), (64, 25, 1_000_000, 64), (256, 25, 100_000, 256)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 10_000, 4)]
+        out["tcopula"] = [tcopula_shape(M, R1, n, K, dof, a.reps) for M, R1, n, K in shapes for dof in (3.0, 30.0)]
     elif a.joint:
         shapes = [(12, 25, 1_000_000, 12), (64, 25, 1_000_000, 64), (256, 25, 100_000, 256), (12, 25, 1_000_000, 3)]
         if a.config:
