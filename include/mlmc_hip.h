@@ -45,7 +45,8 @@ extern "C" {
                               *    three sampling entries), mlmc_copula_box_prob_batch, mlmc_copula_box_draws_batch,
                               *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov,
                               *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts,
-                              *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch */
+                              *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch,
+                              *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -544,7 +545,8 @@ int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out
  * first = 50, n = 100 gives columns [50, 150) of first = 0, n = 150.  dof outside [1, 64] or NaN is an error of the call.  The
  * mixing scales of a block (8 bytes per draw) live next to the normals and uniforms, beyond the 192 MiB that size the block.
  * mlmc_density_quantiles_kernel_time counts the mixing, normals, product, map and sampling kernels of a block and group as one
- * launch.  Conditional draws, box probabilities and event scenarios under a t copula are not provided. */
+ * launch.  Box probabilities and event scenarios under the t copula are mlmc_copula_box_prob_t_batch / _draws_t_batch below;
+ * conditional draws under a t copula are not provided. */
 int mlmc_density_sample_joint_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                                       const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                       int32_t K, const double *factor, double dof, uint64_t seed, const uint32_t *streams,
@@ -683,6 +685,45 @@ int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const doub
 int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                                 const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
                                 double *f_out, double *z_out, double *u_out, int mem_kind);
+/* ---- the two entries above under the STUDENT-T copula -- added within 8 ---------------------------------------------------
+ * P(lo < Y < hi) and scenarios given lo < Y < hi for the multivariate t vector Y = s L z with dof degrees of freedom: z standard
+ * normal [M], s = sqrt(nu / chi2_nu) ONE mixing scale per point (Genz and Bretz, J. Comput. Graph. Statist. 11, 2002):
+ *     P(lo < Y < hi) = E_s[ P(lo / s < L z < hi / s) ],
+ * one more coordinate per point for s, every limit divided by s, the rest the Gaussian chain above.  Everything is in T-SCORE space:
+ * the caller maps limits to quantiles of Student's t.  M, L, B, lo, hi, R, seeds, first, n, flags, mean, f_out, z_out, u_out,
+ * mem_kind, the summation tree, the staging, the split by whole blocks (MLMC_BOX_PROB_BLOCK_POINTS) and every argument error are
+ * those of the Gaussian entries, with these differences:
+ *   There is no shift.  dof = nu lies in [1, 64] (NaN is outside): an error of the call otherwise.
+ *   streams [M-1] (draws: [M]; NULL: i) are the chain's; mix_stream is the stream of the mixing uniform, with MLMC_SAMPLE_SOBOL a
+ *     dimension below 1024 that goes into the call's Sobol' table with the chain's.  mix_stream equal to a chain stream is an error
+ *     that names the coordinate (so with streams = NULL it must be at least M - 1, draws: M).
+ *   s_out [R][n] (may be NULL), host or device by mem_kind: the mixing scales, column j - first.  The scales of a launch (8 bytes per
+ *     seed and point) are staged within the 192 MiB next to the other rows; they alone set the blocks of a launch where no
+ *     other output is staged.
+ * For seed r and point j, operation by operation (every one ONE fp64 operation rounded to nearest, no FMA):
+ *   1. p0 = the Philox uniform j of stream mix_stream under seeds[r], or coordinate mix_stream of point j of the Sobol' sequence
+ *      keyed by seeds[r];  s = chi2_mixing_scale(nu, p0), bit for bit the value of mlmc_chi2_mixing_scale.  s depends on (seed,
+ *      point) alone, not on the box: it is made once per point by a kernel of its own.
+ *   2. For component i:  lt = lo[b][i] / s,  ht = hi[b][i] / s  (one correctly rounded division each; an infinite limit stays
+ *      infinite), then step i of the Gaussian chain exactly as it is written above with lt, ht in the place of lo[b][i], hi[b][i]
+ *      and no shift (the test for an empty component is lt < ht).  f is the product of the widths.  So f[r][b][j] is bit for bit
+ *      the Gaussian entry's integrand at point j for the box (lo / s_j, hi / s_j) and the same chain streams.
+ *   3. Draws: the chain's normal z_i is clamped to [lt, ht] as above; the stored score is the t score
+ *          y_i = min(max(z_i * s, lo[b][i]), hi[b][i])                        (one rounded product), written to z_out, and
+ *          u_i = min(max(T, 2^-53), 1 - 2^-53),  T bit for bit mlmc_student_t_cdf(nu, y_i), written to u_out by a pass of its own.
+ *      lo_i <= y_i <= hi_i for every draw of a box that is not empty; a component with lo_i >= hi_i gives y_i = hi_i and weight 0.
+ * mean [R][B]: the tree of the Gaussian entry over f for EVERY M: under the t copula M = 1 uses its mixing point, so its mean is
+ *   the tree's value and not one width.  f_out and mean of the draws entry are bit for bit those of the probability entry for the
+ *   same streams[0 .. M-2] and mix_stream.  No value depends on B, R, the position of box or seed, first / n, the launch split,
+ *   the presence of f_out / u_out / s_out or host / device outputs.
+ * Conditional draws and probabilities (a shift) under a t copula are not provided: their law has nu + k degrees of freedom, which
+ * leaves [1, 64].  Every loop has a fixed upper trip count; no atomics; one host wait. */
+int mlmc_copula_box_prob_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                 const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                 int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind);
+int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out, int mem_kind);
 
 /* ---- aggregates of joint scenarios (scenario.hip) -- added within 8 ----------------------------------------------------
  * Functions of the M components of one scenario, once per scenario column.  x [S][M][ld]: S >= 1 sets of M >= 1 component rows,

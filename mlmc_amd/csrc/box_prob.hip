@@ -12,6 +12,12 @@
 //                The DRAWS instances (mlmc_copula_box_draws_batch) are the same text: they also take a coordinate for the last
 //                component, keep its y in a register, and store every step's score z_i (clamped to its limits) and, if asked,
 //                its normcdf at column j of row (seed, box, i): a wave writes 64 consecutive doubles per component.
+//                The TCOP instances (mlmc_copula_box_prob_t_batch / _draws_t_batch: the Student-t copula by Genz and Bretz's mixing
+//                variable) are again the same text: a lane reads its point's mixing scale, which k_box_mixing (copula_t.hip) has
+//                made once per (seed, point) before the launch, divides every limit by it and scales the stored score; the t CDF
+//                of the draws is a pass of k_tcop_map over the rows of scores afterwards.  Neither chi2_mixing_scale nor
+//                student_t_cdf is called from the chain: their series loops and constants stay out of the loop over i
+//                (DESIGN.md 3.5.23).
 //   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
 // The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
 // k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
@@ -56,14 +62,18 @@ __device__ __attribute__((noinline)) double box_normcdfinv(double p) { return no
 // grid (blocks of the launch, boxes, seeds); box = b0 + blockIdx.y, seed = r0 + blockIdx.z.  DRAWS (mlmc_copula_box_draws_batch): the
 // same chain, one text; coordinate M - 1 draws the last component too (its y stays in a register), and every step stores the
 // score z_i = s + L_ii y_i clamped to its limits, and its normcdf, at column j of row i: consecutive lanes, consecutive doubles.
-template <bool SOBOL, bool DRAWS>
+// TCOP (the t entries): `mix` holds the mixing scales of the launch, sc = mix[seed][64 blockIdx.x + lane] (k_box_mixing; a block
+// of gridDim.x * 64 doubles per seed of the call).  Every limit is divided by sc, the chain runs on the quotients without a shift, the
+// stored score is the t score min(max(z sc, l), h), and a row of u_out receives the same score: the CDF pass maps it in place.
+template <bool SOBOL, bool DRAWS, bool TCOP = false>
 __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__restrict__ L, const double *__restrict__ lo,
                                                         const double *__restrict__ hi, const double *__restrict__ shift, int B, int b0,
                                                         const uint64_t *__restrict__ seeds, int r0, const uint32_t *__restrict__ streams,
                                                         const uint64_t *__restrict__ table, int table_rows, int64_t first, int64_t n,
                                                         int64_t blk0, int64_t call_blk0, int64_t call_blocks,
                                                         double *__restrict__ partials, double *__restrict__ f_out, int64_t ldf,
-                                                        int64_t c_off, double *__restrict__ z_out, double *__restrict__ u_out) {
+                                                        int64_t c_off, double *__restrict__ z_out, double *__restrict__ u_out,
+                                                        const double *__restrict__ mix) {
     extern __shared__ double ys[];                     // y[k][lane]
     const int lane = threadIdx.x;
     const int b = b0 + (int)blockIdx.y, r = r0 + (int)blockIdx.z;
@@ -74,12 +84,14 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
     const double *sh_b = shift ? shift + (int64_t)b * M : nullptr;
     const uint64_t seed = seeds[r];
     const uint64_t *tab = SOBOL ? table + (int64_t)r * table_rows * SOBOL_ROW : nullptr;
+    double sc = 1.0;
+    if constexpr (TCOP) sc = mix[((int64_t)r * gridDim.x + blockIdx.x) * BOX_LANES + lane];
     double f = 1.0;
     for (int i = 0; i < M; ++i) {
         const double *Li = L + (int64_t)i * M;
         double s = sh_b ? sh_b[i] : 0.0;
         for (int k = 0; k < i; ++k) s = __dadd_rn(s, __dmul_rn(Li[k], ys[k * BOX_LANES + lane]));
-        const double lii = Li[i], l = lo_b[i], h = hi_b[i];
+        const double lii = Li[i], l = TCOP ? lo_b[i] / sc : lo_b[i], h = TCOP ? hi_b[i] / sc : hi_b[i];
         const double ap = (l - s) / lii, bp = (h - s) / lii;
         const bool refl = ap > 0.0;
         const double d = box_normcdf(refl ? -bp : ap), e = box_normcdf(refl ? -ap : bp);
@@ -95,10 +107,14 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
             if (i < M - 1) ys[i * BOX_LANES + lane] = y;
             if constexpr (DRAWS) {
                 // an empty component (l >= h) gives h: max(., l) >= l >= h
-                const double z = fmin(fmax(__dadd_rn(s, __dmul_rn(lii, y)), l), h);
+                double z = fmin(fmax(__dadd_rn(s, __dmul_rn(lii, y)), l), h);
                 const int64_t at = (((int64_t)r * B + b) * M + i) * ldf + (j - first - c_off);
+                if constexpr (TCOP) {
+                    z = fmin(fmax(__dmul_rn(z, sc), lo_b[i]), hi_b[i]);
+                    if (active && u_out) u_out[at] = z;
+                }
                 if (active) z_out[at] = z;
-                if (u_out) {
+                if (!TCOP && u_out) {
                     const double u = fmin(fmax(box_normcdf(z), 0x1p-53), 1.0 - 0x1p-53);
                     if (active) u_out[at] = u;
                 }
@@ -110,7 +126,8 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
 #pragma unroll
     for (int o = BOX_LANES / 2; o; o >>= 1) v += __shfl_xor(v, o);
     // M = 1 uses no point: every lane holds e - d, and k_box_mean hands it on as it is
-    if (lane == 0) partials[((int64_t)r * B + b) * call_blocks + (a - call_blk0)] = M == 1 ? f : v;
+    // (under TCOP the one width depends on the point's mixing scale: the tree as for every other M)
+    if (lane == 0) partials[((int64_t)r * B + b) * call_blocks + (a - call_blk0)] = M == 1 && !TCOP ? f : v;
 }
 
 __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__restrict__ partials, int64_t call_blocks, int64_t n,
@@ -131,9 +148,12 @@ __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__r
 
 static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                     const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
-                    int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr) {
+                    int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr, const double *dof = nullptr,
+                    uint32_t mix_stream = 0, double *s_out = nullptr) {
     const std::string e(fn);
+    const bool tcop = dof != nullptr;                  // the t entries: *dof degrees of freedom, the mixing stream, s_out [R][n] or NULL
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
+    if (tcop && tcop_check_dof(fn, *dof)) return 1;
     if (M < 1) return fail(e + ": M < 1");
     if (M > MLMC_BOX_PROB_MAX_M) return fail(e + ": M = " + std::to_string(M) + " is above the cap " + std::to_string(MLMC_BOX_PROB_MAX_M));
     if (B < 1) return fail(e + ": B < 1");
@@ -164,20 +184,32 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
         }
     // the coordinates: streams (Philox), or the rows of the call's distinct dimensions, one table per seed (MLMC_SAMPLE_SOBOL)
     const int nc = draws ? M : M - 1;                   // the draws take one more coordinate for the last component
-    std::vector<uint32_t> coord((size_t)nc);
+    // the t entries: the mixing variable is one more coordinate, behind the chain's, in the same table
+    const int nd = nc + (tcop ? 1 : 0);
+    std::vector<uint32_t> dims;
+    if (tcop) {
+        for (int i = 0; i < nc; ++i) {
+            dims.push_back(streams ? streams[i] : (uint32_t)i);
+            if (dims[i] == mix_stream) return fail(e + ": mix_stream equals the stream of coordinate " + std::to_string(i));
+        }
+        if (sobol && mix_stream >= 1024) return fail(e + ": mix_stream " + std::to_string(mix_stream) + " is not a Sobol' dimension below 1024");
+        dims.push_back(mix_stream);
+        streams = dims.data();
+    }
+    std::vector<uint32_t> coord((size_t)nd);
     std::vector<uint64_t> tables;
     int table_rows = 0;
-    if (sobol && nc > 0) {
+    if (sobol && nd > 0) {
         std::vector<uint64_t> tab;
         std::vector<uint32_t> slot;
         for (int r = 0; r < R; ++r) {
-            if (sobol_call_table(fn, "coordinate", seeds[r], streams, nc, tab, slot)) return 1;
+            if (sobol_call_table(fn, "coordinate", seeds[r], streams, nd, tab, slot)) return 1;
             tables.insert(tables.end(), tab.begin(), tab.end());
         }
         table_rows = (int)(tab.size() / SOBOL_ROW);
         coord = slot;
     } else
-        for (int i = 0; i < nc; ++i) coord[i] = streams ? streams[i] : (uint32_t)i;
+        for (int i = 0; i < nd; ++i) coord[i] = streams ? streams[i] : (uint32_t)i;
 
     const int64_t call_blk0 = first >> 6, call_blocks = ((first + n - 1) >> 6) - call_blk0 + 1;
     const size_t pairs = (size_t)R * (size_t)B;
@@ -189,8 +221,10 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     // staged rows of a pair: the integrand, and with draws the M rows of z and of u
     const size_t zrows = draws ? pairs * (size_t)M : 0, urows = u_out ? zrows : 0, rows = pairs + zrows + urows;
     int64_t lb = std::min<int64_t>(call_blocks, 0x7fffffff);
-    if (stage) {
-        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * rows)));
+    // the t entries keep the mixing scales of a launch, one row per seed, within the same bytes
+    if (stage || tcop) {
+        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * ((stage ? rows : 0) + (tcop ? (size_t)R : 0)))));
+        if (lb < 1 && !stage) return fail(e + ": the mixing scales of one block of 64 points of R seeds exceed 192 MiB: split the seeds across calls");
         if (lb < 1)
             return fail(e + (draws ? ": the draws" : ": the integrand") +
                         " of one block of 64 points of R * B pairs exceed" + (draws ? "" : "s") +
@@ -203,7 +237,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const int64_t ldf = stage ? lb * BOX_LANES : n;
 
     // what goes up: L | lo | hi | shift | seeds | tables | coordinates (uint32)
-    const size_t nL = (size_t)M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nc + 1) / 2;
+    const size_t nL = (size_t)M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nd + 1) / 2;
     const size_t n_in = nL + 2 * nbx + nsh + (size_t)R + ntab + nco;
     std::vector<double> packed(n_in);
     double *q = packed.data();
@@ -213,13 +247,15 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     if (nsh) std::memcpy(q, shift, sizeof(double) * nsh), q += nsh;
     std::memcpy(q, seeds, sizeof(uint64_t) * (size_t)R), q += R;
     if (ntab) std::memcpy(q, tables.data(), sizeof(uint64_t) * ntab), q += ntab;
-    if (nc) std::memcpy(q, coord.data(), sizeof(uint32_t) * (size_t)nc);
+    if (nd) std::memcpy(q, coord.data(), sizeof(uint32_t) * (size_t)nd);
 
     const size_t b_in = mm_align(sizeof(double) * n_in), b_part = mm_align(sizeof(double) * pairs * (size_t)call_blocks);
     const size_t b_mean = mm_align(sizeof(double) * pairs), b_f = stage ? mm_align(sizeof(double) * pairs * (size_t)ldf) : 0;
     const size_t b_z = stage ? mm_align(sizeof(double) * zrows * (size_t)ldf) : 0, b_u = stage ? mm_align(sizeof(double) * urows * (size_t)ldf) : 0;
+    const size_t b_s = tcop ? mm_align(sizeof(double) * (size_t)R * (size_t)lb * BOX_LANES) : 0;
     static MultiWorkspace ws;
-    if (ws.reserve(b_in + b_part + b_mean + b_f + b_z + b_u)) return 1;
+    if (ws.reserve(b_in + b_part + b_mean + b_f + b_z + b_u + b_s)) return 1;
+    double *d_s = tcop ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z + b_u) : nullptr;
     double *d_in = (double *)ws.dev, *d_part = (double *)(ws.dev + b_in), *d_mean = (double *)(ws.dev + b_in + b_part);
     double *d_f = stage ? (double *)(ws.dev + b_in + b_part + b_mean) : f_out;
     double *d_z = stage && draws ? (double *)(ws.dev + b_in + b_part + b_mean + b_f) : z_out;
@@ -231,20 +267,34 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
 
     const size_t lds = sizeof(double) * BOX_LANES * (size_t)(M - 1);
-    const auto kernel = draws ? (sobol ? k_box_prob<true, true> : k_box_prob<false, true>)
-                              : (sobol ? k_box_prob<true, false> : k_box_prob<false, false>);
+    const auto kernel = tcop ? (draws ? (sobol ? k_box_prob<true, true, true> : k_box_prob<false, true, true>)
+                                      : (sobol ? k_box_prob<true, false, true> : k_box_prob<false, false, true>))
+                             : (draws ? (sobol ? k_box_prob<true, true> : k_box_prob<false, true>)
+                                      : (sobol ? k_box_prob<true, false> : k_box_prob<false, false>));
+    const TCopConst tconst = tcop ? tcop_constants(*dof) : TCopConst{};
     for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
         const int64_t kb = std::min(lb, call_blocks - k0);
         // the first point of the launch within the call: column 0 of the staged integrand
         const int64_t c_lo = std::max<int64_t>(((call_blk0 + k0) << 6) - first, 0);
         const int64_t c_hi = std::min<int64_t>(((call_blk0 + k0 + kb) << 6) - first, n);
+        if (tcop) {
+            // the mixing scales of the launch's blocks, once per (seed, point): d_s [R][64 kb]
+            const int64_t j0 = (call_blk0 + k0) << 6;
+            cop_launch_box_mixing(st, tconst, R, d_seeds, coord[nc], sobol ? d_tab : nullptr, table_rows, j0, kb * BOX_LANES, first, n, d_s);
+            if (s_out)
+                MLMC_HIP_CHECK(hipMemcpy2DAsync(s_out + c_lo, sizeof(double) * (size_t)n, d_s + (first + c_lo - j0),
+                                                sizeof(double) * (size_t)(kb * BOX_LANES), sizeof(double) * (size_t)(c_hi - c_lo), (size_t)R,
+                                                mem_kind == MLMC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+        }
         for (int r0 = 0; r0 < R; r0 += 65535)
             for (int b0 = 0; b0 < B; b0 += 65535) {
                 const dim3 grid((unsigned)kb, (unsigned)std::min(B - b0, 65535), (unsigned)std::min(R - r0, 65535));
                 hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, d_shift, (int)B, b0, d_seeds, r0, d_coord,
                                    d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part, d_f, ldf,
-                                   stage ? c_lo : (int64_t)0, d_z, d_u);
+                                   stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)d_s);
             }
+        // the CDF pass of the t draws: the rows of u hold the t scores of the launch's columns and are mapped in place
+        if (tcop && u_out) cop_launch_t_map(st, tconst, (int)urows, c_hi - c_lo, d_u + (stage ? 0 : c_lo), ldf);
         MLMC_HIP_CHECK(hipGetLastError());
         if (stage) {
             MLMC_HIP_CHECK(hipMemcpy2DAsync(f_out + c_lo, sizeof(double) * (size_t)n, d_f, sizeof(double) * (size_t)ldf,
@@ -258,7 +308,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
         }
     }
     hipLaunchKernelGGL(k_box_mean, dim3((unsigned)pairs), dim3(BOX_MEAN_THREADS), 0, st, (const double *)d_part, call_blocks, n,
-                       (int)(M == 1), d_mean);
+                       (int)(M == 1 && !tcop), d_mean);
     MLMC_HIP_CHECK(hipGetLastError());
     MLMC_HIP_CHECK(hipMemcpyAsync(mean, d_mean, sizeof(double) * pairs, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
@@ -284,6 +334,22 @@ int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const dou
     MLMC_API_GUARD;
     return box_prob("mlmc_copula_box_draws_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
                     z_out, u_out);
+}
+
+int mlmc_copula_box_prob_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                 const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                 int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_t_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, false,
+                    nullptr, nullptr, &dof, mix_stream, s_out);
+}
+
+int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_draws_t_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
+                    z_out, u_out, &dof, mix_stream, s_out);
 }
 
 }  // extern "C"

@@ -50,6 +50,11 @@ int tcop_check_dof(const char *fn, double dof);
 // under `seed`, or with sobol_row (device, [SOBOL_ROW]) the coordinate of point j in that row's dimension
 void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32_t stream, const uint64_t *sobol_row, int64_t first,
                        int64_t ncols, int antithetic, double *s);
+// s[r * ncols + c] = chi2_mixing_scale(nu, p0 of point j0 + c under seeds[r]), r < R, c < ncols (k_box_mixing), and 1 for a point
+// outside [first, first + n): p0 = uniform j of `stream` under seeds[r], or with `table` (device, R tables of table_rows rows) the
+// coordinate of point j in row `stream` of seed r's table; seeds: device, [R]
+void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint64_t *seeds, uint32_t stream, const uint64_t *table,
+                           int table_rows, int64_t j0, int64_t ncols, int64_t first, int64_t n, double *s);
 // U[m * ldu + c] = (sum_k F[m * K + k] Z[k * ldz + c]) (x) s[c], m < M, c < ncols (k_cop_uniforms, the TSCALE instance): the sum as
 // above, then one rounded multiplication; all device
 void cop_launch_scaled_product(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,

@@ -4,6 +4,8 @@
 //
 //   k_cop_mixing : s[c] = chi2_mixing_scale(nu, p0) of draw first + c, p0 the Philox uniform of the mixing stream or the Sobol'
 //                  coordinate of the mixing dimension (sobol.hpp); one thread per draw
+//   k_box_mixing : the same scale for the t box entries (box_prob.hip): s[r][c] of point j0 + c under seed r, for all seeds of a
+//                  call and the whole blocks of one launch; one thread per (seed, point), once per point and not once per box
 //   k_tcop_map   : U = clamp(student_t_cdf(nu, U)) in place, one thread per element.  The map is a kernel of its own and not the
 //                  epilogue of the product: a lane of the product holds 16 accumulators, and the series loop over them would keep
 //                  them and the constants of pow / exp / log1p live together (the comment at the top of copula.hip).
@@ -196,6 +198,25 @@ __global__ __launch_bounds__(TC_THREADS) void k_cop_mixing(TCopConst C, uint64_t
     s[c] = chi2_mixing_scale(C, p0);
 }
 
+// The mixing scales of the blocks of one launch of the t box entries (box_prob.hip), for every seed of the call: column c is point
+// j0 + c, blockIdx.y the seed.  p0 is the Philox uniform j of `stream` under seeds[r], or with `table` the coordinate of point j in
+// row `stream` of seed r's table (table_rows rows per seed).  Points outside [first, first + n) pad their block with s = 1.
+__global__ __launch_bounds__(TC_THREADS) void k_box_mixing(TCopConst C, const uint64_t *__restrict__ seeds, uint32_t stream,
+                                                           const uint64_t *__restrict__ table, int table_rows, int64_t j0, int64_t ncols,
+                                                           int64_t first, int64_t n, double *__restrict__ s) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncols) return;
+    const int r = blockIdx.y;
+    const int64_t j = j0 + c;
+    double v = 1.0;
+    if (j >= first && j < first + n) {
+        const double p0 = table ? sobol_unit(sobol_point(table + ((int64_t)r * table_rows + stream) * SOBOL_ROW, (uint64_t)j))
+                                : q_uniform(seeds[r], stream, (uint64_t)j);
+        v = chi2_mixing_scale(C, p0);
+    }
+    s[(int64_t)r * ncols + c] = v;
+}
+
 __global__ __launch_bounds__(TC_THREADS) void k_tcop_map(TCopConst C, int64_t ncols, double *__restrict__ U, int64_t ldu) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ncols) return;
@@ -214,6 +235,16 @@ void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32
                        int64_t ncols, int antithetic, double *s) {
     hipLaunchKernelGGL(k_cop_mixing, dim3((unsigned)((ncols + TC_THREADS - 1) / TC_THREADS)), dim3(TC_THREADS), 0, st, C, seed, stream,
                        sobol_row, first, ncols, antithetic, s);
+}
+
+void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint64_t *seeds, uint32_t stream, const uint64_t *table,
+                           int table_rows, int64_t j0, int64_t ncols, int64_t first, int64_t n, double *s) {
+    // seed of a launch = blockIdx.y: more seeds than a grid has in y go in several launches
+    for (int r0 = 0; r0 < R; r0 += 65535)
+        hipLaunchKernelGGL(k_box_mixing, dim3((unsigned)((ncols + TC_THREADS - 1) / TC_THREADS), (unsigned)std::min(R - r0, 65535)),
+                           dim3(TC_THREADS), 0, st, C, seeds + r0, stream,
+                           table ? table + (int64_t)r0 * table_rows * SOBOL_ROW : nullptr, table_rows, j0, ncols, first, n,
+                           s + (int64_t)r0 * ncols);
 }
 
 void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, double *U, int64_t ldu) {

@@ -704,7 +704,7 @@ class Estimate:
 
     def bootstrap_joint_probability(self, lower, upper, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
                                     seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
-                                    orth_moments_tol=1e-4, moments_fns=None):
+                                    orth_moments_tol=1e-4, moments_fns=None, dof=None):
         """Bootstrap confidence bands of estimate_joint_probability: how far the probability of a box moves when the stored samples
         are resampled.  The `stderr` of estimate_joint_probability is the quasi-Monte Carlo integration error alone; the band here
         is the sampling uncertainty of the correlation matrix (and, on request, of the marginals) pushed through the box integral.
@@ -717,6 +717,10 @@ class Estimate:
             the same seed and sample_vector -- the same picks, so replicate b is one coherent resample of marginals and dependence
         :param corr: None (Pearson) or "scores"; a matrix is an error (nothing to resample)
         :param n, seeds: as in estimate_joint_probability (smaller default n: there are n_subsamples + 1 integrals)
+        :param dof: as in estimate_joint_probability: the Student-t copula with that many degrees of freedom.  The degrees of
+            freedom are HELD FIXED over the replicates: the band is the uncertainty of the correlation (and marginals) at the given
+            dof, not that of the fit of `estimate_copula_dof`.  The resampled correlation is the Pearson or scores one, which
+            estimates the t copula's matrix only approximately (the quadrant correlation is not resampled)
         :return: ProbabilityBands(prob [n_boxes], stderr [n_boxes] = those of estimate_joint_probability with the same n and seeds,
             lo, hi [n_boxes] = quantile_bands over the ok replicates, replicates [B, n_boxes], ok [B], n_ok, seed).  A replicate
             whose correlation is not ok, whose solve failed for a component that a box constrains (a finite limit on either
@@ -724,6 +728,7 @@ class Estimate:
         from .tool import simple_distribution
         what = "bootstrap_joint_probability"
         level = _check_level(what, level)
+        dof = simple_distribution._check_dof(what, dof)
         if marginals not in ("fixed", "resampled"):
             raise ValueError("{}: marginals must be 'fixed' or 'resampled', got {!r}".format(what, marginals))
         self._resampled_corr_arg(what, corr)
@@ -742,7 +747,7 @@ class Estimate:
             raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
         corr0, _ = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         distrs = [d[0] for d in densities]
-        base = simple_distribution.joint_probabilities(distrs, lower, upper, n, seeds, corr=corr0)
+        base = simple_distribution.joint_probabilities(distrs, lower, upper, n, seeds, corr=corr0, dof=dof)
         reps = self.est_bootstrap_component_covariance(B, k, seed, corr=corr, densities=densities)
         ok = reps.ok.copy()
         rep_distrs, success = None, None
@@ -758,7 +763,7 @@ class Estimate:
                 continue
             d_b = distrs if rep_distrs is None else rep_distrs[b * M:(b + 1) * M]
             try:
-                replicates[b] = simple_distribution.joint_probabilities(d_b, lower, upper, n, seeds, corr=reps.corr[b]).prob
+                replicates[b] = simple_distribution.joint_probabilities(d_b, lower, upper, n, seeds, corr=reps.corr[b], dof=dof).prob
             except Exception:
                 ok[b] = False
         lo, hi = _band_over_ok(replicates, ok, level)
@@ -766,17 +771,19 @@ class Estimate:
 
     def bootstrap_joint_exceedance(self, thresholds, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
                                    seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
-                                   orth_moments_tol=1e-4, moments_fns=None):
+                                   orth_moments_tol=1e-4, moments_fns=None, dof=None):
         """P(X_m > t_m for all constrained m) with its bootstrap band: `bootstrap_joint_probability` with lower = thresholds and
         upper = +inf.
         :param thresholds: broadcast to [n_boxes, M]; -inf leaves a component unconstrained
+        :param dof: the Student-t copula, its degrees of freedom held fixed over the replicates (bootstrap_joint_probability)
         :return: as bootstrap_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
             raise ValueError("bootstrap_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
         return self.bootstrap_joint_probability(t, np.inf, n_subsamples=n_subsamples, sample_vector=sample_vector, seed=seed,
                                                 level=level, n=n, seeds=seeds, corr=corr, marginals=marginals, densities=densities,
-                                                tol=tol, reg_param=reg_param, orth_moments_tol=orth_moments_tol, moments_fns=moments_fns)
+                                                tol=tol, reg_param=reg_param, orth_moments_tol=orth_moments_tol, moments_fns=moments_fns,
+                                                dof=dof)
 
     def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
         """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""
@@ -1095,7 +1102,7 @@ class Estimate:
         return draws, success, cond[2]
 
     def estimate_joint_probability(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
         """Probability that the components lie in a box AT ONCE, P(lower_m < X_m < upper_m for all m), under the marginals and the
         Gaussian copula of `sample_joint`, for B boxes in one batched device call (tool.simple_distribution.joint_probabilities):
         Genz's separation of variables on scrambled Sobol' points.  Its error is relative and falls like 1 / n, so the small
@@ -1111,9 +1118,16 @@ class Estimate:
             with the boxes
         :param densities: as in estimate_component_quantiles
         :param qmc: False: Philox uniforms instead of Sobol' points (plain Monte Carlo over the unit cube)
+        :param dof: None or np.inf: the Gaussian copula, bit for bit.  A float in [1, 64]: the STUDENT-T copula of
+            `sample_joint(dof=...)` with that many degrees of freedom (`estimate_copula_dof` fits it), by Genz and Bretz's mixing
+            variable: one more coordinate per point, the same relative accuracy in the tail.  Where `estimate_tail_dependence`
+            shows joint tails (a large positive z), this is the number to use: the Gaussian one is too small.  `corr` is then the t
+            copula's correlation matrix, which corr="quadrant" estimates consistently; None and "scores" only approximately.  Not
+            together with `given`
         :return: (JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds), success [M])"""
         from .tool import simple_distribution
         what = "estimate_joint_probability"
+        dof = simple_distribution._box_dof(what, dof, None, given)
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
             raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
@@ -1121,21 +1135,22 @@ class Estimate:
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
         result = simple_distribution.joint_probabilities([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
-                                                         given=given, first=first, qmc=qmc)
+                                                         given=given, first=first, qmc=qmc, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
 
     def estimate_joint_exceedance(self, thresholds, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
         """P(X_m > t_m for all constrained m): `estimate_joint_probability` with lower = thresholds and upper = +inf.
         :param thresholds: broadcast to [B, M]; -inf leaves a component unconstrained
+        :param dof: the Student-t copula, as in estimate_joint_probability
         :return: as estimate_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
             raise ValueError("estimate_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
         return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
-                                               first=first, qmc=qmc)
+                                               first=first, qmc=qmc, dof=dof)
 
     def estimate_tail_dependence(self, probs=(0.9, 0.95, 0.99), tail="upper", corr=None, densities=None, tol=1e-8, reg_param=0.0,
                                  orth_moments_tol=1e-4, moments_fns=None, dof=None):
@@ -1234,9 +1249,11 @@ class Estimate:
         """The degrees of freedom of a Student-t copula for the components, read off the tail concordance of the stored samples:
         ONE pass as in `estimate_tail_dependence` (the counts do not depend on nu), then host arithmetic over a grid of nu
         (tool.simple_distribution.fit_copula_dof): the nu whose t orthants lie closest to the frequencies, np.inf for the Gaussian
-        copula.  Feed the result to `sample_joint(dof=...)`, `estimate_aggregates(dof=...)` and
-        `estimate_tail_dependence(dof=...)`.  Not provided under a t copula: conditional draws, box probabilities
-        (Genz-Bretz), event scenarios, and a bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid.
+        copula.  Feed the result to `sample_joint(dof=...)`, `estimate_aggregates(dof=...)`, `estimate_tail_dependence(dof=...)`
+        and to the joint numbers themselves: `estimate_joint_probability(dof=...)`, `estimate_joint_exceedance(dof=...)`,
+        `sample_given_event(dof=...)`, `estimate_event_means(dof=...)` and the two bootstrap bands (Genz and Bretz's mixing
+        variable).  Not provided under a t copula: conditional draws and probabilities (`given`), and a bootstrap of nu -- the fit
+        has no error bar beyond the objective's shape over the grid.
         :param probs, tail, corr, densities: as in estimate_tail_dependence; corr="quadrant" is the estimate that is consistent
             under a t copula
         :param grid: candidate nu, finite values in [1, 64] or np.inf; None: 2, 3, 4, 5, 6, 8, 10, 15, 20, 30, inf
@@ -1294,7 +1311,7 @@ class Estimate:
         return JointFrequency(st["prob"], stderr, counts, counts.n)
 
     def sample_given_event(self, n, lower, upper, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                           orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True):
+                           orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True, dof=None):
         """Joint scenarios of all components GIVEN that they lie in a box at once (lower_m < X_m < upper_m for all m), under the
         marginals and the Gaussian copula of `sample_joint`, for B events and R seeds (tool.simple_distribution.event_samples):
         what the system looks like when the event of `estimate_joint_probability` happens.  Every scenario lies in the event and
@@ -1308,9 +1325,13 @@ class Estimate:
             must not be constrained
         :param densities: as in estimate_component_quantiles
         :param device: the arrays of the result are float64 torch device tensors
+        :param dof: None or np.inf: the Gaussian copula, bit for bit; a float in [1, 64]: the Student-t copula of
+            `sample_joint(dof=...)`, as in estimate_joint_probability (corr="quadrant" is the consistent correlation).  Not together
+            with `given`
         :return: (EventScenarios(draws [R, B, M, n], weights [R, B, n], prob, ess [R, B], ok [M], uniforms), success [M])"""
         from .tool import simple_distribution
         what = "sample_given_event"
+        dof = simple_distribution._box_dof(what, dof, None, given)
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
             raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
@@ -1318,23 +1339,23 @@ class Estimate:
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
         result = simple_distribution.event_samples([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
-                                                   given=given, first=first, qmc=qmc, device=device)
+                                                   given=given, first=first, qmc=qmc, device=device, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
 
     def estimate_event_means(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                             orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True):
+                             orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
         """Expected value of EVERY component given that the components lie in a box at once, E[X | lower < X < upper]: the weighted
         means of the scenarios of `sample_given_event`.  `estimate_event_means(thresholds, np.inf)` is the companion of
         `estimate_joint_exceedance`: the expected state of the system when all thresholds are exceeded.  The weights are smooth on
         the Sobol' points, so the error falls like 1 / n at any probability of the event.
-        :param lower, upper, n, seeds, corr, given, densities, first, qmc: as in sample_given_event
+        :param lower, upper, n, seeds, corr, given, densities, first, qmc, dof: as in sample_given_event
         :return: (EventMeans(mean [B, M], stderr [B, M], prob, ess [R, B]), success [M]): per seed the ratio sum f x / sum f, its
             mean over the seeds and their spread over sqrt(R); prob the JointProbability of the event; ess the effective sample
             size of each seed's n scenarios"""
         scen, success = self.sample_given_event(n, lower, upper, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                 orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
-                                                first=first, qmc=qmc)
+                                                first=first, qmc=qmc, dof=dof)
         mean, stderr = scen.means()
         return EventMeans(mean, stderr, scen.prob, scen.ess), success
 
@@ -1366,8 +1387,9 @@ class Estimate:
         :param event: None, or (lower_e, upper_e): the scenarios are those of `sample_given_event` for these B boxes and every
             statistic carries their weights; `prob` is the JointProbability of the event.  qmc then chooses Sobol' or Philox points
         :param block: scenario columns per device block
-        :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula of `sample_joint(dof=...)`.  Not
-            together with `given` or `event`: conditional draws and event scenarios exist under the Gaussian copula only
+        :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula of `sample_joint(dof=...)`, with
+            `event` that of `sample_given_event(dof=...)`.  Not together with `given`: conditional draws exist under the Gaussian
+            copula only
         :return: (AggregateSummary, success [M]).  Statistics are [Q, ...], with a leading axis B for arrays in `given` and for the B
             boxes of `event` (always, also for one box); count_prob [.., M + 1], worst_prob / best_prob [.., M] are None without their row"""
         from .tool import simple_distribution as sd
@@ -1376,9 +1398,8 @@ class Estimate:
         n, seeds, first = sd._box_call_args(what, n, seeds, first)
         sd._sample_flags(what, antithetic, qmc)
         dof = sd._check_dof(what, dof)
-        if dof is not None and (given is not None or event is not None):
-            raise ValueError(what + ": dof together with given or event: conditional draws and event scenarios exist under the "
-                                    "Gaussian copula only")
+        if dof is not None and given is not None:
+            raise ValueError(what + ": dof together with given: conditional draws exist under the Gaussian copula only")
         _check_tail(what, tail)
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
         if probs.size == 0 or not np.all((probs >= 0) & (probs <= 1)):
@@ -1414,7 +1435,7 @@ class Estimate:
             f_of = None
         else:
             scen = sd.event_samples(distrs, lower_e, upper_e, n, [int(s) for s in seeds], corr=corr, given=given, first=first, qmc=qmc,
-                                    device=True)
+                                    device=True, dof=dof)
             ev = sd.event_aggregates(scen, **agg)
             B = int(ev.rows.shape[1])
             per_seed = [ev.rows[r] for r in range(R)]

@@ -583,8 +583,9 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
             u = clamp(T_dof(s F z)),   s = sqrt(dof / chi2_dof) = chi2_mixing_scale(p0, dof),
         one mixing uniform p0 per draw (with antithetic one per pair, so that the pair negates y exactly), T_dof of
         `student_t_cdf`.  F is a factor of the copula's correlation matrix: for a t copula the correlation of the normal scores is
-        NOT that matrix; `Estimate.estimate_quadrant_correlation` estimates it consistently.  Conditional draws, box
-        probabilities and event scenarios exist for the Gaussian copula only
+        NOT that matrix; `Estimate.estimate_quadrant_correlation` estimates it consistently.  Box probabilities and
+        event scenarios under the same copula: `joint_probabilities(dof=...)`, `event_samples(dof=...)`.  Conditional draws
+        (`given`) exist for the Gaussian copula only
     :param mix_stream: the uint32 stream (qmc: the dimension, below 1024) of the mixing uniform; default K when `streams` is
         defaulted; with explicit `streams` it must be given and differ from all of them
     :param return_uniforms, return_normals, return_mixing: also return u [M, n], z [K, n] and / or s [n] (dof only), in this order
@@ -925,8 +926,34 @@ def _box_problem(what, factor, lower, upper, shift):
     return f, lo, hi, shift
 
 
+def _box_t_streams(what, dof, shift, streams, mix_stream, count, qmc):
+    """(chain streams uint32 [count], mixing stream) of a box call under the t copula, checked: by default the mixing variable takes
+    stream 0, the lowest Sobol' dimension (Genz and Bretz's order), and chain coordinate i stream i + 1"""
+    if shift is not None:
+        raise ValueError(what + ": dof together with shift: conditional laws exist under the Gaussian copula only")
+    if streams is None:
+        streams = np.arange(1, count + 1, dtype=np.uint32)
+        if mix_stream is None:
+            return streams, 0
+    mix_stream = _mixing_stream(what, dof, mix_stream, streams, count)
+    if qmc and mix_stream >= 1024:
+        raise ValueError(what + ": with qmc mix_stream is a Sobol' dimension and must be below 1024")
+    return streams, mix_stream
+
+
+def t_scores(z, dof):
+    """The Student-t scores of normal scores z, on the host: y with T_dof(y) = Phi(z), through the lower tail on either side so
+    that a far upper score keeps its relative accuracy: y = stdtrit(dof, ndtr(z)) for z <= 0 and -stdtrit(dof, ndtr(-z)) for z > 0
+    (scipy.special).  Infinite scores are kept, 0 gives 0, NaN stays NaN; odd in z bit for bit."""
+    from scipy.special import ndtr, stdtrit
+    z = np.asarray(z, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        y = np.where(z > 0, -1.0, 1.0) * stdtrit(float(dof), ndtr(-np.abs(z)))
+    return np.where(np.isinf(z) | (z == 0), z, y)
+
+
 def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
-                             device=False):
+                             device=False, dof=None, mix_stream=None, return_mixing=False):
     """P(lower < Y < upper) for Y = shift + F z, z standard normal, for B boxes and R seeds through ONE device call
     (mlmc_copula_box_prob_batch): Genz's separation of variables, which conditions through the lower-triangular factor with one
     Phi^-1 and two Phi per component, so that the integrand is a smooth function on the unit cube.  Everything is in SCORE space
@@ -944,8 +971,19 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     :param streams: one stream (qmc: Sobol' dimension below 1024) per coordinate, M - 1 of them; default: i
     :param qmc: scrambled Sobol' points (MLMC_SAMPLE_SOBOL); False: Philox uniforms
     :param return_integrand: also return the integrand [R, B, n] (a float64 torch device tensor with device=True)
+    :param dof: None or np.inf: the Gaussian law above, bit for bit what it has always been.  A float in [1, 64]: Y = s F z is a
+        multivariate STUDENT-T vector with that many degrees of freedom (mlmc_copula_box_prob_t_batch), s = chi2_mixing_scale(p0,
+        dof) one mixing scale per point: P(lower < Y < upper) = E_s[P(lower / s < F z < upper / s)] (Genz and Bretz), one more
+        coordinate per point, every limit divided by s, the rest the Gaussian chain.  The limits are T SCORES (`t_scores`).  Not
+        together with `shift`
+    :param mix_stream: the stream (qmc: the dimension, below 1024) of the mixing uniform.  Default 0, and chain coordinate i then
+        takes stream i + 1; with explicit `streams` it must be given and differ from all of them
+    :param return_mixing: also return the mixing scales s [R, n] (dof only), after the integrand
     :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
     what = "copula_box_probabilities"
+    dof = _check_dof(what, dof)
+    if dof is None and (mix_stream is not None or return_mixing):
+        raise ValueError(what + ": mix_stream and return_mixing need dof (the Gaussian copula has no mixing variable)")
     f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
     M, B = f.shape[0], lo.shape[0]
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -953,11 +991,22 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     R = seeds.size
     flags = _lib.SAMPLE_SOBOL if qmc else 0
     mean = np.empty((R, B))
-    (integrand,), kind = _output_arrays(device and return_integrand, [(R, B, n) if return_integrand else None])
-    _lib.check(_lib.lib().mlmc_copula_box_prob_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R, _lib.ptr(seeds),
-                                                    _lib.ptr(streams), first, n, flags, _lib.ptr(mean), _lib.ptr(integrand), kind))
+    if dof is None:
+        (integrand,), kind = _output_arrays(device and return_integrand, [(R, B, n) if return_integrand else None])
+        _lib.check(_lib.lib().mlmc_copula_box_prob_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R,
+                                                        _lib.ptr(seeds), _lib.ptr(streams), first, n, flags, _lib.ptr(mean),
+                                                        _lib.ptr(integrand), kind))
+        result = _joint_probability(mean, n, seeds)
+        return (result, integrand) if return_integrand else result
+    streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, M - 1, qmc)
+    (integrand, s), kind = _output_arrays(device and (return_integrand or return_mixing),
+                                          [(R, B, n) if return_integrand else None, (R, n) if return_mixing else None])
+    _lib.check(_lib.lib().mlmc_copula_box_prob_t_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                                      _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
+                                                      _lib.ptr(integrand), _lib.ptr(s), kind))
+    extra = tuple(v for v, want in ((integrand, return_integrand), (s, return_mixing)) if want)
     result = _joint_probability(mean, n, seeds)
-    return (result, integrand) if return_integrand else result
+    return (result,) + extra if extra else result
 
 
 def _joint_probability(replicates, n, seeds):
@@ -993,8 +1042,19 @@ def _limit_scores(what, distrs, lo, hi):
     return z_lo, z_hi, keep, finish
 
 
+def _box_dof(what, dof, mix_stream, given):
+    """dof of a box entry in the components' own units, checked (None: the Gaussian copula)"""
+    dof = _check_dof(what, dof)
+    if dof is not None and given is not None:
+        raise ValueError(what + ": dof together with given: conditional laws exist under the Gaussian copula only (given k components "
+                         "the others follow a t law with dof + k degrees of freedom)")
+    if dof is None and mix_stream is not None:
+        raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
+    return dof
+
+
 def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True,
-                        return_integrand=False, device=False):
+                        return_integrand=False, device=False, dof=None, mix_stream=None):
     """Joint box probabilities P(lower_m < X_m < upper_m for all m) under the Gaussian copula of `joint_samples`, for B boxes in
     the components' own units through `copula_box_probabilities`; with `given`, conditional on the given values of some
     components as in `conditional_samples`.  A limit that is +-inf or lies at or beyond an end of its distribution's domain is an
@@ -1007,12 +1067,18 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
     :param given: None, or the mapping of `conditional_samples`; arrays [B] pair with the boxes (one box pairs with all sets)
     :param streams: per coordinate of the REDUCED problem (constrained components - 1)
     :param n, seeds, first, qmc, return_integrand, device: as in `copula_box_probabilities`
+    :param dof, mix_stream: the STUDENT-T copula of `joint_samples(dof=...)` in the place of the Gaussian one: the normal scores of
+        the limits go to t scores on the host (`t_scores`) and the box goes through `copula_box_probabilities(dof=...)`; corr /
+        factor are then the t copula's correlation matrix (`Estimate.estimate_quadrant_correlation` estimates it).  Dropping the
+        unconstrained components stays valid: a sub-vector of a multivariate t is a t with the same dof and the sub-matrix.  None or
+        np.inf: the Gaussian copula, bit for bit.  Not together with `given`
     :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
     what = "joint_probabilities"
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
+    dof = _box_dof(what, dof, mix_stream, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1041,12 +1107,16 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         B = Bg
     z_lo, z_hi, keep, finish = _limit_scores(what, [distrs[m] for m in free], lo, hi)
     streams = _box_streams(what, streams, max(keep.size, 1), qmc)
+    if dof is not None:
+        streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, max(keep.size, 1) - 1, qmc)
     if keep.size > _lib.BOX_PROB_MAX_M:
         raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
     if keep.size == 0:
         ones = _joint_probability(np.ones((seeds.size, B)), n, seeds)
         return (ones, None) if return_integrand else ones
     finish()
+    if dof is not None:
+        z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
     if observed.size:
         _, _, _, _, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
@@ -1056,13 +1126,15 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         low = correlation_factor(corr[np.ix_(free[keep], free[keep])])[0]
         shift = None
     return copula_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], shift=shift, streams=streams,
-                                    first=first, qmc=qmc, return_integrand=return_integrand, device=device)
+                                    first=first, qmc=qmc, return_integrand=return_integrand, device=device, dof=dof,
+                                    mix_stream=mix_stream)
 
 
 BoxDraws = collections.namedtuple("BoxDraws", "z u weights prob")
 
 
-def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, device=False):
+def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, device=False, dof=None,
+                     mix_stream=None, return_mixing=False):
     """Scenarios of Y = shift + F z GIVEN lower < Y < upper, for B boxes and R seeds through ONE device call
     (mlmc_copula_box_draws_batch): the conditioned normals of the chain of `copula_box_probabilities` are a sequential importance
     sample of the truncated normal vector (the GHK sampler).  Every point is a scenario inside the box; its weight is the
@@ -1075,19 +1147,36 @@ def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, f
         default: i.  The weights and `prob` are those of `copula_box_probabilities` with the first M - 1 of them, bit for bit
     :param device: return z, u and the weights as float64 torch device tensors
     :return: BoxDraws(z [R, B, M, n], u [R, B, M, n], weights [R, B, n], prob): the scores, lower <= z <= upper; u = Phi(z) clamped
-        to [2^-53, 1 - 2^-53] as in `joint_samples`; prob the JointProbability of the event"""
+        to [2^-53, 1 - 2^-53] as in `joint_samples`; prob the JointProbability of the event
+    :param dof, mix_stream: the Student-t law of `copula_box_probabilities` (mlmc_copula_box_draws_t_batch): limits and the returned
+        z are then T scores, z = clip((chain's normal) * s, lower, upper), and u = T_dof(z) of `student_t_cdf`, clamped alike.  By
+        default the mixing stream is 0 and coordinate i takes stream i + 1, so weights and `prob` are again those of
+        `copula_box_probabilities` with the same dof, bit for bit.  Not together with `shift`
+    :param return_mixing: return (BoxDraws, s [R, n]) (dof only)"""
     what = "copula_box_draws"
+    dof = _check_dof(what, dof)
+    if dof is None and (mix_stream is not None or return_mixing):
+        raise ValueError(what + ": mix_stream and return_mixing need dof (the Gaussian copula has no mixing variable)")
     f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
     M, B = f.shape[0], lo.shape[0]
     n, seeds, first = _box_call_args(what, n, seeds, first)
     streams = _box_streams(what, streams, M + 1, qmc)
     R = seeds.size
+    flags = _lib.SAMPLE_SOBOL if qmc else 0
     mean = np.empty((R, B))
-    (z, u, w), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n)])
-    _lib.check(_lib.lib().mlmc_copula_box_draws_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R, _lib.ptr(seeds),
-                                                     _lib.ptr(streams), first, n, _lib.SAMPLE_SOBOL if qmc else 0, _lib.ptr(mean),
-                                                     _lib.ptr(w), _lib.ptr(z), _lib.ptr(u), kind))
-    return BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+    if dof is None:
+        (z, u, w), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n)])
+        _lib.check(_lib.lib().mlmc_copula_box_draws_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R,
+                                                         _lib.ptr(seeds), _lib.ptr(streams), first, n, flags, _lib.ptr(mean), _lib.ptr(w),
+                                                         _lib.ptr(z), _lib.ptr(u), kind))
+        return BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+    streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, M, qmc)
+    (z, u, w, s), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n), (R, n) if return_mixing else None])
+    _lib.check(_lib.lib().mlmc_copula_box_draws_t_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                                       _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean), _lib.ptr(w),
+                                                       _lib.ptr(z), _lib.ptr(u), _lib.ptr(s), kind))
+    box = BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+    return (box, s) if return_mixing else box
 
 
 def _event_order(constrained, q):
@@ -1150,7 +1239,8 @@ class EventScenarios:
         return out
 
 
-def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True, device=False):
+def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True, device=False,
+                  dof=None, mix_stream=None):
     """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m for all m, under the marginals and the Gaussian
     copula of `joint_samples`, for B events and R seeds through `copula_box_draws` and ONE `quantiles` call: what the system
     looks like when the event of `joint_probabilities` happens.  Every scenario lies in the event and carries a weight; rejection
@@ -1168,12 +1258,16 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
         order above
     :param n, seeds, first, qmc: as in `copula_box_probabilities`
     :param device: draws, uniforms and weights are float64 torch device tensors; `means` and `weighted_quantiles` then raise
+    :param dof, mix_stream: the STUDENT-T copula of `joint_samples(dof=...)`, as in `joint_probabilities`: the same chain order,
+        `copula_box_draws(dof=...)` and one `quantiles` call on its u.  Under default streams `prob` is bit for bit that of
+        `joint_probabilities(dof=...)` where no component is dropped there.  Not together with `given`
     :return: EventScenarios"""
     what = "event_samples"
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
+    dof = _box_dof(what, dof, mix_stream, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1207,7 +1301,11 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
         raise ValueError(what + ": component {} is given and constrained by a limit: a given value is the condition, leave its "
                          "limits at -inf / +inf".format(int(both[0])))
     streams = _box_streams(what, streams, q + 1, qmc)
+    if dof is not None:
+        streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, q, qmc)
     finish()
+    if dof is not None:
+        z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
     # the chain: positions within the free components, constrained first
     perm = _event_order(np.searchsorted(free, keep), q)
     order = free[perm]                                                                       # chain position -> component
@@ -1220,7 +1318,7 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
         low = correlation_factor(corr[np.ix_(order, order)])[0]
         u_obs, shift = None, None
     box = copula_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], shift=shift, streams=streams, first=first,
-                           qmc=qmc, device=device)
+                           qmc=qmc, device=device, dof=dof, mix_stream=mix_stream)
     R = seeds.size
     # one quantiles call for all components: component order[i] takes the u of chain position i
     chain = [distrs[m] for m in order]

@@ -102,6 +102,14 @@ one shape), next to rejection: joint_samples(device=True) of the same n per seed
   call_ms, inside_per_ms, ess_fraction, event_mean, event_stderr   wall time of the call up to a device synchronise, its R n scenarios
                                per ms, ess / n, and the conditional mean of component 2 (M = 2: 0) with the seeds' standard error
   reject_ms_per_seed, reject_inside_per_ms, reject_mean, reject_stderr, reject_zero_seeds   the same for what the filter keeps
+--tboxprob: the Student-t copula in the two routes above, nu = 3 and 30, against the Gaussian call of the same
+shape in the same run, the two taking turns after a warm-up each: copula_box_probabilities(dof=nu) on the shapes of --boxprob (the same
+numbers as limits in t-score space), then event_samples(dof=nu, device=True) on the shapes of --boxdraws (--config M,n: one shape of each
+with B = 1):
+  t_ms / gauss_ms, t_over_gauss_wall   wall time of the call, [min, mean, max], and the ratio of the means
+  mixing_entry_ms, map_entry_ms        chi2_mixing_scale on the call's R n device uniforms and (draws) student_t_cdf on its R M n device
+                                       scores: the mixing kernel and the CDF pass on their own, with the entry's launch and wait
+  prob, stderr / gauss_prob, gauss_stderr (draws: ess_fraction)   what the two calls returned
 --aggregates: mlmc_scenario_aggregates on device-resident scenarios x [S, M, n], A = 3 linear rows, all four
 extremes and the count (Q = 8), for S x M x n = 1 x 12 x 10^6, 1 x 64 x 10^6 and 64 given-sets x 12 x 10^4 (--config S,M,n: that shape
 alone), against the torch composition on the same materialised matrix -- matmul, max and min with their indices, compare and sum: five
@@ -124,7 +132,7 @@ process, the two taking turns after a warm-up call each (five repetitions unless
   equal_torch                  every counter equals the composition's (exact while counts stay below 2^53)
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --tcopula | --scores |
-                                                              --conditional | --qmc | --boxprob | --boxdraws | --aggregates |
+                                                              --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --aggregates |
                                                               --concordance] [--reps K]"""
 import argparse
 import ctypes as C
@@ -747,6 +755,84 @@ def boxdraws_shape(M, n, reps, p, seeds=tuple(range(1, 9))):
                 reject_zero_seeds=int(np.sum(kept == 0)))
 
 
+def _turns(routes, reps):
+    """[min, mean, max] wall ms of every route, the routes taking turns after a warm-up call each"""
+    for fn in routes:
+        fn()
+    wall = [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+    return [[round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)] for t in wall]
+
+
+def _t_parts(dof, n_mix, n_map):
+    """the mixing kernel and the CDF pass of a t box call on their own: chi2_mixing_scale on n_mix device uniforms and student_t_cdf
+    on n_map device values of the t law, each with its entry's launch and wait"""
+    p0 = torch.rand(n_mix, dtype=torch.float64, device="cuda").clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+    y = None
+    if n_map:
+        y = torch.randn(n_map, dtype=torch.float64, device="cuda") * sd.chi2_mixing_scale(p0, dof, device=True)[torch.arange(n_map, device="cuda") % n_mix]
+
+    def mixing_route():
+        sd.chi2_mixing_scale(p0, dof, device=True)
+        torch.cuda.synchronize()
+
+    def map_route():
+        sd.student_t_cdf(y, dof, device=True)
+        torch.cuda.synchronize()
+    return (mixing_route, map_route) if n_map else (mixing_route,)
+
+
+def tboxprob_shape(M, B, n, reps, t, dof, seeds=tuple(range(1, 9))):
+    """copula_box_probabilities(dof=...) of B copies of the box (t, inf)^M in t-score space under equicorrelation 1/2 against the
+    Gaussian call of the same shape (the same numbers as limits: the work is the same, the probabilities are not), the two taking
+    turns in one process; and the mixing kernel on its own, chi2_mixing_scale on the call's R n uniforms"""
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    low = np.linalg.cholesky(corr)
+    lo, hi = np.full((B, M), t), np.full((B, M), np.inf)
+    got = {}
+
+    def t_route():
+        got["t"] = sd.copula_box_probabilities(low, lo, hi, n, seeds, dof=dof)
+
+    def gauss_route():
+        got["g"] = sd.copula_box_probabilities(low, lo, hi, n, seeds)
+    wall = _turns((t_route, gauss_route) + _t_parts(dof, len(seeds) * n, 0), reps)
+    return dict(M=M, B=B, n=n, R=len(seeds), threshold=round(t, 4), dof=dof, t_ms=wall[0], gauss_ms=wall[1], mixing_entry_ms=wall[2],
+                t_over_gauss_wall=round(wall[0][1] / wall[1][1], 3), prob=float("%.6g" % got["t"].prob[0]),
+                stderr=float("%.3g" % got["t"].stderr[0]), gauss_prob=float("%.6g" % got["g"].prob[0]),
+                gauss_stderr=float("%.3g" % got["g"].stderr[0]))
+
+
+def tboxdraws_shape(M, n, reps, p, dof, seeds=tuple(range(1, 9))):
+    """event_samples(dof=..., device=True) of the event of --boxdraws against the Gaussian call of the same shape, the two taking
+    turns in one process; and the mixing kernel and the CDF pass on their own, on R n uniforms and R M n scores"""
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    distrs, _ = mixtures(M, 9, seed=5)
+    factor = sd.correlation_factor(corr)[0]
+    lower = np.full(M, -np.inf)
+    lower[:2] = [sd.quantiles([distrs[m]], [np.array([p])])[0][0] for m in (0, 1)]
+    got = {}
+
+    def route(key, dof):
+        def run():
+            ev = sd.event_samples(distrs, lower, np.inf, n, seeds, factor=factor, device=True, dof=dof)
+            torch.cuda.synchronize()
+            got[key] = (float(ev.prob.prob[0]), float(np.mean(ev.ess)) / n)
+        return run
+    R = len(seeds)
+    wall = _turns((route("t", dof), route("g", None)) + _t_parts(dof, R * n, R * M * n), reps)
+    return dict(M=M, n=n, R=R, quantile=p, dof=dof, t_ms=wall[0], gauss_ms=wall[1], mixing_entry_ms=wall[2], map_entry_ms=wall[3],
+                t_over_gauss_wall=round(wall[0][1] / wall[1][1], 3), prob=float("%.6g" % got["t"][0]),
+                ess_fraction=float("%.3g" % got["t"][1]), gauss_prob=float("%.6g" % got["g"][0]),
+                gauss_ess_fraction=float("%.3g" % got["g"][1]))
+
+
 def scores_shape(M, R1, n, reps, levels=0):
     """normal_scores(device=True) of n (fine, coarse) pairs of M components against the route without the entry: cdfs_on_rule on the
     device tensors of fine and of coarse, then torch clamp and torch.special.ndtri (which has no drop of out-of-domain values: the
@@ -972,6 +1058,8 @@ def main():
     ap.add_argument("--boxprob", action="store_true", help="copula_box_probabilities against closed forms, next to counting the "
                                                            "scenarios of joint_samples (DESIGN.md section 3.5.17)")
     ap.add_argument("--boxdraws", action="store_true", help="event_samples against rejection from joint_samples (DESIGN.md section 3.5.18)")
+    ap.add_argument("--tboxprob", action="store_true", help="copula_box_probabilities / event_samples with dof = 3, 30 against the Gaussian "
+                    "calls of the same shapes (DESIGN.md section 3.5.23)")
     ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
@@ -999,6 +1087,18 @@ def main():
             shapes = [(1, 12, 10_000), (3, 5, 1_000)]
         _lib.use_torch_stream()
         out["aggregates"] = [aggregates_shape(S, M, n, a.reps) for S, M, n in shapes]
+    elif a.tboxprob:
+        t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
+        shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
+        shapes += [(12, 1, 2 ** k, t6) for k in (12, 16, 20)]
+        draws = [(M, 2 ** k, 0.9) for M in (2, 12, 64) for k in (12, 16, 20)] + [(12, 2 ** k, 0.999) for k in (12, 16, 20)]
+        if a.config:
+            M, n = (int(v) for v in a.config.split(","))
+            shapes, draws = [(M, 1, n, 0.0)], [(M, n, 0.9)]
+        elif a.quick:
+            shapes, draws = [(2, 1, 2 ** 12, 0.0), (12, 3, 2 ** 12, t6)], [(2, 2 ** 12, 0.9), (12, 2 ** 12, 0.999)]
+        out["tboxprob"] = [tboxprob_shape(M, B, n, a.reps, t, dof) for M, B, n, t in shapes for dof in (3.0, 30.0)]
+        out["tboxdraws"] = [tboxdraws_shape(M, n, a.reps, p, dof) for M, n, p in draws for dof in (3.0, 30.0)]
     elif a.boxdraws:
         shapes = [(M, 2 ** k, 0.9) for M in (2, 12, 64) for k in (12, 16, 20)] + [(12, 2 ** k, 0.999) for k in (12, 16, 20)]
         if a.config:
