@@ -46,7 +46,8 @@ extern "C" {
                               *    mlmc_bootstrap_create_xcov, mlmc_bootstrap_set_shift, mlmc_bootstrap_finalize_xcov,
                               *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts,
                               *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch,
-                              *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch */
+                              *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch,
+                              *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -546,7 +547,7 @@ int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out
  * mixing scales of a block (8 bytes per draw) live next to the normals and uniforms, beyond the 192 MiB that size the block.
  * mlmc_density_quantiles_kernel_time counts the mixing, normals, product, map and sampling kernels of a block and group as one
  * launch.  Box probabilities and event scenarios under the t copula are mlmc_copula_box_prob_t_batch / _draws_t_batch below;
- * conditional draws under a t copula are not provided. */
+ * conditional draws under a t copula are mlmc_density_sample_conditional_t_batch. */
 int mlmc_density_sample_joint_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
                                       const double *sigma, const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree,
                                       int32_t K, const double *factor, double dof, uint64_t seed, const uint32_t *streams,
@@ -586,6 +587,38 @@ int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *ba
                                           int32_t gauss_degree, int32_t K, const double *factor, uint64_t seed, const uint32_t *streams,
                                           int64_t first, int64_t n, int32_t flags, int32_t B, const double *shift, const int32_t *rows,
                                           int32_t ld_rows, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
+/* Seeded CONDITIONAL joint draws under the STUDENT-T copula, B sets of observed values at once -- added within 8.  Given the t
+ * scores y_O of p observed components, the t scores of the others are multivariate t with nu + p degrees of freedom, location W y_O
+ * and scale matrix g F_c F_c^T, g = (nu + d) / (nu + p), d = y_O^T C_OO^-1 y_O: an extreme observation widens the law of the
+ * rest.  This entry defines the arithmetic; the caller supplies shift = W y_O, scale[b] = sqrt(g_b) and dof_mix = nu + p.
+ *   Arguments, layout (rows / ld_rows), no-ops, argument errors, the rule for degenerate problems, the block rule, the workspace
+ *     bound and the independence properties are those of mlmc_density_sample_conditional_batch.
+ *   The mixing uniform p0[j], the rules for mix_stream (equal to one of `streams` is an error), the antithetic pairing (draws 2k and
+ *     2k + 1 share s and negate z) and the handling of MLMC_SAMPLE_SOBOL are those of mlmc_density_sample_joint_t_batch.
+ *   dof lies in [1, 64], dof_mix in [1, 192]; NaN is outside both: errors of the call.  dof_mix need not be dof + an integer.
+ *   scale [B] (host; NULL: ones): every scale must be finite and positive; a violation names the set.
+ *   s[j] is bit for bit mlmc_chi2_conditional_scale(dof_mix, p0[j]);
+ *   y = shift[b][m] (+) ((acc (x) s[j]) (x) scale[b]): acc the chain of the joint entry, then THREE fp64 operations, each rounded to
+ *     nearest, in this order;
+ *   u = min(max(T, 2^-53), 1 - 2^-53) with T bit for bit mlmc_student_t_cdf(dof, y): the MARGINAL t CDF has dof degrees of freedom,
+ *     not dof_mix;  x = Q_m(u), bit for bit mlmc_density_quantiles_batch at p = u.
+ * With B = 1, NULL (or zero) shift, NULL (or unit) scale, dof_mix == dof and unit rows the entry returns the bits of
+ * mlmc_density_sample_joint_t_batch in out, u_out, z_out and s_out.  s_out [n] (may be NULL; host or device by mem_kind) sits next
+ * to z_out.  No value depends on B, the position of a set, M, rows / ld_rows, n, first, the block length, the memory kind or the
+ * launch geometry.  The mixing scales of a block live where the joint t entry keeps them; the product and the map are kernels of
+ * their own (the map runs over the rows of all sets), and mlmc_density_quantiles_kernel_time counts the kernels of a block and
+ * group as one launch.  Every loop has a fixed upper trip count; no atomics; one host wait. */
+int mlmc_density_sample_conditional_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                            const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                            int32_t gauss_degree, int32_t K, const double *factor, double dof, double dof_mix,
+                                            uint64_t seed, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                            int32_t flags, int32_t B, const double *shift, const double *scale, const int32_t *rows,
+                                            int32_t ld_rows, double *out, double *u_out, double *z_out, double *s_out, double *mass_out,
+                                            int mem_kind);
+/* mlmc_chi2_mixing_scale with dof_mix in [1, 192], the range of the mixing variable of the entry above -- added within 8.  For
+ * dof_mix <= 64 it gives the bits of mlmc_chi2_mixing_scale; the capped loops stay below half their caps up to 192.  It exists so
+ * that the scale can be tested at chosen arguments.  Errors and no-ops are those of mlmc_chi2_mixing_scale. */
+int mlmc_chi2_conditional_scale(double dof_mix, int64_t n, const double *p, double *s_out, int mem_kind);
 /* Normal scores of stored samples under the densities of M problems in one call -- added within 8: the probability-integral
  * transform followed by normcdfinv, the step between the fitted marginals and a correlation of the Gaussian copula
  * (mlmc_density_sample_joint_batch).  Problems, rule, table, masses and Fhat_m are those of mlmc_density_cdf_batch (lambda / sigma
@@ -716,8 +749,9 @@ int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const dou
  *   the tree's value and not one width.  f_out and mean of the draws entry are bit for bit those of the probability entry for the
  *   same streams[0 .. M-2] and mix_stream.  No value depends on B, R, the position of box or seed, first / n, the launch split,
  *   the presence of f_out / u_out / s_out or host / device outputs.
- * Conditional draws and probabilities (a shift) under a t copula are not provided: their law has nu + k degrees of freedom, which
- * leaves [1, 64].  Every loop has a fixed upper trip count; no atomics; one host wait. */
+ * Conditional PROBABILITIES and event scenarios (a shift) under a t copula are not provided: their law has nu + k degrees of
+ * freedom, which leaves the [1, 64] of these entries.  Conditional draws are mlmc_density_sample_conditional_t_batch, whose mixing
+ * variable alone takes up to 192.  Every loop has a fixed upper trip count; no atomics; one host wait. */
 int mlmc_copula_box_prob_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
                                  int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind);

@@ -117,6 +117,10 @@ SIGNATURES = {
     "mlmc_density_sample_conditional_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                                         C.c_uint64, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
                                                         _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_density_sample_conditional_t_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                                          C.c_double, C.c_double, C.c_uint64, _vp, C.c_uint32, C.c_int64, C.c_int64,
+                                                          C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_chi2_conditional_scale": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
     "mlmc_density_scores_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, C.c_int64,
                                             _vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "mlmc_density_quantiles_kernel_time": (C.c_int, [_dp, _ip]),

@@ -10,7 +10,8 @@
 //                    [64][32] and the Z panel [32][64] go to LDS with zeros beyond M, K and the draws of the call, then 8 steps of 4 k.
 //                    Row tile = blockIdx.y: row tiles beyond the first re-read the same Z panels from memory.
 //                    The instance with SHIFT (mlmc_density_sample_conditional_batch) has the set on blockIdx.z: every set forms the
-//                    product of its tile anew and adds its own shift in the epilogue.
+//                    product of its tile anew and adds its own shift in the epilogue.  The instances with
+//                    TSCALE (the Student-t copula) store y itself for k_tcop_map (copula_t.hip).
 // Neither kernel loops over rows: the compiler would keep the constants of the inlined normcdfinv / normcdf in registers across
 // the loop (256 and 208 VGPRs instead of 24 and 114).
 // y[m][c] is the chain acc = mfma(F[m][4 s .. 4 s + 3], Z[4 s .. 4 s + 3][c], acc), s = 0, 1, ... from acc = 0: what it adds and in
@@ -46,12 +47,17 @@ __global__ __launch_bounds__(COP_NORMAL_THREADS) void k_cop_normals(uint64_t see
 // SHIFT (mlmc_density_sample_conditional_batch): set = blockIdx.z; the epilogue adds shift[set * set_rows + row] to the finished
 // chain, one rounded addition, and the tile goes to rows set * set_rows + row of U.  A lane's four rows are its registers' rows for
 // every J, so it loads its four shifts once, ahead of the panels, and the epilogue waits for no memory.
-// TSCALE (mlmc_density_sample_joint_t_batch): `shift` is the mixing scale s [ncols] of the draws; the epilogue multiplies the
+// TSCALE (mlmc_density_sample_joint_t_batch): `mix` is the mixing scale s [ncols] of the draws; the epilogue multiplies the
 // finished chain by s[column], one rounded multiplication, and stores y itself: k_tcop_map (copula_t.hip) maps it in place.
+// SHIFT and TSCALE (mlmc_density_sample_conditional_t_batch): set = blockIdx.z as under SHIFT; a lane loads its four shifts and
+// its set's scale once, ahead of the panels, and the epilogue stores y = shift (+) ((acc (x) s[column]) (x) scale[set]): three
+// rounded operations in this order, so that scale = 1 and shift = 0 leave the bits of the TSCALE instance's y (up to the sign
+// of a zero, which the map does not see).  k_tcop_map maps the rows of all sets in place.
 template <bool SHIFT, bool TSCALE = false>
 __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__restrict__ F, int M, int K, const double *__restrict__ Z,
                                                               int64_t ldz, int64_t ncols, double *__restrict__ U, int64_t ldu,
-                                                              const double *__restrict__ shift, int64_t set_rows) {
+                                                              const double *__restrict__ shift, int64_t set_rows,
+                                                              const double *__restrict__ mix, const double *__restrict__ set_scale) {
     __shared__ double fl[COP_TILE * COP_F_STRIDE];
     __shared__ double zl[COP_PANEL * COP_Z_STRIDE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -65,6 +71,8 @@ __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__re
             if (row < M) sh[r] = shift[(int64_t)blockIdx.z * set_rows + row];
         }
     }
+    [[maybe_unused]] double sc = 1.0;
+    if constexpr (SHIFT && TSCALE) sc = set_scale[blockIdx.z];
     v4f64 acc[COP_TILE / 16];
 #pragma unroll
     for (int J = 0; J < COP_TILE / 16; ++J) acc[J] = (v4f64){0.0, 0.0, 0.0, 0.0};
@@ -105,12 +113,16 @@ __global__ __launch_bounds__(COP_THREADS) void k_cop_uniforms(const double *__re
         for (int r = 0; r < 4; ++r) {
             const int row = row0 + 16 * wave + (lane >> 4) + 4 * r;
             const int64_t col = col0 + 16 * J + (lane & 15);
-            if constexpr (SHIFT) {
+            if constexpr (SHIFT && TSCALE) {
+                if (row < M && col < ncols)
+                    U[((int64_t)blockIdx.z * set_rows + row) * ldu + col] =
+                        __dadd_rn(sh[r], __dmul_rn(__dmul_rn(acc[J][r], mix[col]), sc));
+            } else if constexpr (SHIFT) {
                 if (row < M && col < ncols)
                     U[((int64_t)blockIdx.z * set_rows + row) * ldu + col] =
                         fmin(fmax(normcdf(__dadd_rn(sh[r], acc[J][r])), 0x1p-53), 1.0 - 0x1p-53);
             } else if constexpr (TSCALE) {
-                if (row < M && col < ncols) U[(int64_t)row * ldu + col] = __dmul_rn(acc[J][r], shift[col]);
+                if (row < M && col < ncols) U[(int64_t)row * ldu + col] = __dmul_rn(acc[J][r], mix[col]);
             } else {
                 if (row < M && col < ncols) U[(int64_t)row * ldu + col] = fmin(fmax(normcdf(acc[J][r]), 0x1p-53), 1.0 - 0x1p-53);
             }
@@ -135,7 +147,7 @@ void cop_launch_uniforms(hipStream_t st, const double *F, int M, int K, const do
         const int Ml = std::min(M - m0, rows);
         const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE));
         hipLaunchKernelGGL(k_cop_uniforms<false>, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
-                           U + (int64_t)m0 * ldu, ldu, (const double *)nullptr, (int64_t)0);
+                           U + (int64_t)m0 * ldu, ldu, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (const double *)nullptr);
     }
 }
 
@@ -146,7 +158,7 @@ void cop_launch_scaled_product(hipStream_t st, const double *F, int M, int K, co
         const int Ml = std::min(M - m0, rows);
         const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE));
         hipLaunchKernelGGL((k_cop_uniforms<false, true>), grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
-                           U + (int64_t)m0 * ldu, ldu, s, (int64_t)0);
+                           U + (int64_t)m0 * ldu, ldu, (const double *)nullptr, (int64_t)0, s, (const double *)nullptr);
     }
 }
 
@@ -160,7 +172,22 @@ void cop_launch_uniforms_shifted(hipStream_t st, const double *F, int M, int K, 
             const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE),
                             (unsigned)std::min(B - b0, 65535));
             hipLaunchKernelGGL(k_cop_uniforms<true>, grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
-                               U + ((int64_t)b0 * set_rows + m0) * ldu, ldu, shift + (int64_t)b0 * set_rows + m0, set_rows);
+                               U + ((int64_t)b0 * set_rows + m0) * ldu, ldu, shift + (int64_t)b0 * set_rows + m0, set_rows,
+                               (const double *)nullptr, (const double *)nullptr);
+        }
+}
+
+void cop_launch_scaled_shifted(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                               int64_t ldu, const double *shift, const double *s, const double *scale, int B, int64_t set_rows) {
+    // the split of cop_launch_uniforms_shifted
+    constexpr int rows = 65535 * COP_TILE;
+    for (int b0 = 0; b0 < B; b0 += 65535)
+        for (int m0 = 0; m0 < M; m0 += rows) {
+            const int Ml = std::min(M - m0, rows);
+            const dim3 grid((unsigned)((ncols + COP_TILE - 1) / COP_TILE), (unsigned)((Ml + COP_TILE - 1) / COP_TILE),
+                            (unsigned)std::min(B - b0, 65535));
+            hipLaunchKernelGGL((k_cop_uniforms<true, true>), grid, dim3(COP_THREADS), 0, st, F + (int64_t)m0 * K, Ml, K, Z, ldz, ncols,
+                               U + ((int64_t)b0 * set_rows + m0) * ldu, ldu, shift + (int64_t)b0 * set_rows + m0, set_rows, s, scale + b0);
         }
 }
 

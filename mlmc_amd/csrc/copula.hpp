@@ -44,8 +44,11 @@ struct TCopConst {
     double lg_a1;                      // log Gamma(nu / 2 + 1)
 };
 TCopConst tcop_constants(double dof);
-// 0, or 1 with the error set: dof must lie in [1, 64] (NaN is outside)
-int tcop_check_dof(const char *fn, double dof);
+// the degrees of freedom of every entry but one end at 64; the mixing variable of the conditional entry has nu + p, up to 192: the
+// capped loops of copula_t.hip stay below half their caps there (tests/conditional_t_cases.py)
+constexpr int TCOP_MAX_DOF = 64, TCOP_MAX_DOF_MIX = 192;
+// 0, or 1 with the error set: `name` must lie in [1, max_dof] (NaN is outside)
+int tcop_check_dof(const char *fn, double dof, int max_dof = TCOP_MAX_DOF, const char *name = "dof");
 // s[c] = chi2_mixing_scale(nu, p0 of draw first + c), c < ncols (k_cop_mixing): p0 = uniform j (antithetic: j >> 1) of `stream`
 // under `seed`, or with sobol_row (device, [SOBOL_ROW]) the coordinate of point j in that row's dimension
 void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32_t stream, const uint64_t *sobol_row, int64_t first,
@@ -59,6 +62,10 @@ void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint
 // above, then one rounded multiplication; all device
 void cop_launch_scaled_product(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
                                int64_t ldu, const double *s);
+// U[(b * set_rows + m) * ldu + c] = shift[b * set_rows + m] (+) (((sum_k F[m * K + k] Z[k * ldz + c]) (x) s[c]) (x) scale[b]), b < B,
+// m < M, c < ncols (k_cop_uniforms, the SHIFT and TSCALE instance): the sum as above, then three rounded operations; all device
+void cop_launch_scaled_shifted(hipStream_t st, const double *F, int M, int K, const double *Z, int64_t ldz, int64_t ncols, double *U,
+                               int64_t ldu, const double *shift, const double *s, const double *scale, int B, int64_t set_rows);
 // U[m * ldu + c] = clamp(student_t_cdf(nu, U[m * ldu + c])) in place, m < M, c < ncols (k_tcop_map)
 void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, double *U, int64_t ldu);
 

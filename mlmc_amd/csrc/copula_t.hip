@@ -1,6 +1,8 @@
 // The Student-t copula of mlmc_density_sample_joint_t_batch on the device (gfx950), and the two elementwise entries that define
 // its functions (include/mlmc_hip.h): mlmc_student_t_cdf, mlmc_chi2_mixing_scale.  The host path of the sampling entry is
 // density.hip's (q_copula); the product y = (F z) (x) s is the TSCALE instance of k_cop_uniforms (copula.hip).
+// mlmc_density_sample_conditional_t_batch uses the same kernels: the mixing scale with the constants of nu_c = nu + p (up to 192,
+// mlmc_chi2_conditional_scale), the map with those of nu, over the rows of all sets.
 //
 //   k_cop_mixing : s[c] = chi2_mixing_scale(nu, p0) of draw first + c, p0 the Philox uniform of the mixing stream or the Sobol'
 //                  coordinate of the mixing dimension (sobol.hpp); one thread per draw
@@ -254,8 +256,9 @@ void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, 
                            dim3(TC_THREADS), 0, st, C, ncols, U + (int64_t)m0 * ldu, ldu);
 }
 
-int tcop_check_dof(const char *fn, double dof) {
-    if (!(dof >= 1.0 && dof <= 64.0)) return fail(std::string(fn) + ": dof must lie in [1, 64]");
+int tcop_check_dof(const char *fn, double dof, int max_dof, const char *name) {
+    if (!(dof >= 1.0 && dof <= (double)max_dof))
+        return fail(std::string(fn) + ": " + name + " must lie in [1, " + std::to_string(max_dof) + "]");
     return 0;
 }
 
@@ -264,9 +267,10 @@ static MultiWorkspace &t_ws() {
     return ws;
 }
 
-static int t_elementwise(const char *fn, bool chi2, double dof, int64_t n, const double *in, double *out, int mem_kind) {
+static int t_elementwise(const char *fn, bool chi2, double dof, int64_t n, const double *in, double *out, int mem_kind,
+                         int max_dof = TCOP_MAX_DOF, const char *dof_name = "dof") {
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
-    if (tcop_check_dof(fn, dof)) return 1;
+    if (tcop_check_dof(fn, dof, max_dof, dof_name)) return 1;
     if (n < 0) return fail(std::string(fn) + ": n < 0");
     if (mem_kind != MLMC_HOST && mem_kind != MLMC_DEVICE) return fail(std::string(fn) + ": bad mem_kind");
     if (!in || !out) return fail(std::string(fn) + ": null argument");
@@ -307,6 +311,11 @@ int mlmc_student_t_cdf(double dof, int64_t n, const double *y, double *u_out, in
 int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out, int mem_kind) {
     MLMC_API_GUARD;
     return t_elementwise("mlmc_chi2_mixing_scale", true, dof, n, p, s_out, mem_kind);
+}
+
+int mlmc_chi2_conditional_scale(double dof_mix, int64_t n, const double *p, double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return t_elementwise("mlmc_chi2_conditional_scale", true, dof_mix, n, p, s_out, mem_kind, TCOP_MAX_DOF_MIX, "dof_mix");
 }
 
 }  // extern "C"

@@ -1210,13 +1210,16 @@ struct QSets {
     const double *shift;              // [B][M] or NULL: zeros
     const int32_t *rows;              // [M] or NULL
     int32_t ld_rows;
+    const double *scale = nullptr;    // [B] or NULL: ones; read with a t copula only (mlmc_density_sample_conditional_t_batch)
 };
 
-// the Student-t copula of mlmc_density_sample_joint_t_batch: y = (F z) s with the mixing scale s[j] of draw j (copula_t.hip)
+// the Student-t copula of mlmc_density_sample_joint_t_batch: y = (F z) s with the mixing scale s[j] of draw j (copula_t.hip);
+// the conditional t entry draws s with dof_mix degrees of freedom and maps with dof
 struct QTCop {
     double dof;
     uint32_t mix_stream;
     double *s_out;                    // [n] or NULL
+    double dof_mix;
 };
 
 // mlmc_density_sample_joint_batch (sets == NULL) and mlmc_density_sample_conditional_batch: draws of M problems joined by a
@@ -1232,6 +1235,9 @@ struct QTCop {
 // The joint t entry (tc != NULL, sets == NULL): the mixing scales s [nb] of the block come first (k_cop_mixing), the product stores
 // y = (F z) s in U (the TSCALE instance of k_cop_uniforms) and k_tcop_map maps U in place; s lives next to Z in the workspace, beyond
 // the bound that sizes the block (8 bytes per draw), unless the caller's device array takes it.
+// The conditional t entry (tc != NULL, sets != NULL): blocks, workspace, staging and rows are the conditional entry's, s the joint
+// t entry's with the constants of dof_mix; the SHIFT and TSCALE instance of k_cop_uniforms stores y = shift + ((F z) s) scale[b] for
+// every set and k_tcop_map maps the B * M rows in place with the constants of dof.
 static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,
                     const double *a, const double *b, int32_t n_intervals, int32_t gauss_degree, int32_t Kf, const double *factor,
                     uint64_t seed, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, const QSets *sets, double *out,
@@ -1242,6 +1248,7 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     if (q_sample_flags(fn, flags)) return 1;
     const bool sobol = flags & MLMC_SAMPLE_SOBOL;
     if (tc && tcop_check_dof(fn, tc->dof)) return 1;
+    if (tc && sets && tcop_check_dof(fn, tc->dof_mix, TCOP_MAX_DOF_MIX, "dof_mix")) return 1;
     if (Kf < 1) return fail(std::string(fn) + ": K < 1");
     if (!factor) return fail(std::string(fn) + ": null factor");
     if (n < 0) return fail(std::string(fn) + ": n < 0");
@@ -1287,6 +1294,9 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
         for (int64_t i = 0; sets->shift && i < (int64_t)B * M; ++i)
             if (!std::isfinite(sets->shift[i]))
                 return fail(std::string(fn) + ": shift of set " + std::to_string(i / M) + ", row " + std::to_string(i % M) + " is not finite");
+        for (int b = 0; tc && sets->scale && b < B; ++b)
+            if (!(std::isfinite(sets->scale[b]) && sets->scale[b] > 0.0))
+                return fail(std::string(fn) + ": scale of set " + std::to_string(b) + " must be finite and positive");
         if (sizeof(double) * 64 * (BM + (size_t)Kf) > Q_JOINT_BYTES)
             return fail(std::string(fn) + ": the uniforms of B * M = " + std::to_string(BM) +
                         " rows do not fit into the workspace even for a block of 64 draws; split the sets across calls (no value depends on B)");
@@ -1314,7 +1324,7 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     const bool z_ws = n > 0 && !(mem_kind == MLMC_DEVICE && z_out), u_ws = n > 0 && (sets || !(mem_kind == MLMC_DEVICE && u_out));
     const bool s_ws = tc && n > 0 && !(mem_kind == MLMC_DEVICE && tc->s_out);
     // what goes up with the block: the draws table | the streams (uint32) | the factor | the shifts of the sets | the Sobol' table
-    // (uint64); a call without draws sends the draws table alone
+    // (uint64) | the mixing variable's table | the scales of the sets; a call without draws sends the draws table alone
     QPack pack;
     pack.add(draws.data(), draws.size());
     std::vector<uint32_t> sv(n > 0 ? (size_t)Kf : 0);
@@ -1322,6 +1332,8 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     const size_t at_streams = pack.add(sv.data(), sv.size()), at_factor = pack.add(factor, n > 0 ? (size_t)M * Kf : 0);
     const size_t at_shift = sets ? pack.add(sets->shift, n > 0 ? BM : 0) : 0, at_sobol = pack.add(sobol_tab.data(), n > 0 ? sobol_tab.size() : 0);
     const size_t at_mix = pack.add(mix_tab.data(), n > 0 ? mix_tab.size() : 0);
+    const std::vector<double> ones(sets && tc && !sets->scale && n > 0 ? (size_t)B : 0, 1.0);
+    const size_t at_scale = sets && tc ? pack.add(sets->scale ? sets->scale : ones.data(), n > 0 ? (size_t)B : 0) : 0;
     const size_t n_in = pack.data.size(), n_stage = stage ? BM * (size_t)n : 0;
     QBlock K;
     if (q_stage(S, deg, {n_in}, {(size_t)M, (size_t)plane, n_stage, u_ws ? BM * (size_t)nb : 0, z_ws ? (size_t)Kf * (size_t)nb : 0,
@@ -1334,7 +1346,10 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
     const double *d_factor = pack.at<double>(K, at_factor), *d_shift = pack.at<double>(K, at_shift);
     const uint64_t *d_sobol = pack.at<uint64_t>(K, at_sobol);
     const uint64_t *d_mix = tc && sobol ? pack.at<uint64_t>(K, at_mix) : nullptr;
+    const double *d_scale = pack.at<double>(K, at_scale);
+    // the constants of the map and those of the mixing scale: the same but for the conditional t entry
     const TCopConst tconst = tc ? tcop_constants(tc->dof) : TCopConst{};
+    const TCopConst tmix = tc && sets ? tcop_constants(tc->dof_mix) : tconst;
     double *d_mass = K.d[0], *d_tab = K.d[1], *d_out = stage ? K.d[2] : out;
     // the uniforms k_q_sample writes next to the draws: those of the sets; the joint entry's U is the output itself
     double *d_u = !sets ? nullptr : stage && u_out ? K.d[5] : u_out;
@@ -1351,12 +1366,20 @@ static int q_copula(const char *fn, int32_t M, const mlmc_basis *const *bases, c
             double *Sc = !tc ? nullptr : s_ws ? K.d[6] : tc->s_out + c0;
             tm.begin(st);
             if (tc && (g0 == 0 || s_ws))       // as the normals below
-                cop_launch_mixing(st, tconst, seed, tc->mix_stream, d_mix, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Sc);
+                cop_launch_mixing(st, tmix, seed, tc->mix_stream, d_mix, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Sc);
             if ((g0 == 0 || z_ws) && sobol)    // a later group finds the normals of the block in the caller's array
                 cop_launch_sobol_normals(st, d_sobol, d_streams, Kf, first + c0, nc, Z, ldz);
             else if (g0 == 0 || z_ws)
                 cop_launch_normals(st, seed, d_streams, Kf, first + c0, nc, (int)(flags & MLMC_SAMPLE_ANTITHETIC), Z, ldz);
-            if (sets)
+            if (sets && tc) {
+                cop_launch_scaled_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, d_shift + g0, Sc,
+                                          d_scale, B, M);
+                // the rows of a set's group are consecutive; those of all sets are when the group is the whole set
+                if (np_g == M)
+                    cop_launch_t_map(st, tconst, (int)BM, nc, U, ldu);
+                else
+                    for (int b = 0; b < B; ++b) cop_launch_t_map(st, tconst, np_g, nc, U + ((int64_t)b * M + g0) * ldu, ldu);
+            } else if (sets)
                 cop_launch_uniforms_shifted(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, d_shift + g0, B, M);
             else if (tc) {
                 cop_launch_scaled_product(st, d_factor + (size_t)g0 * Kf, np_g, Kf, Z, ldz, nc, U + (int64_t)g0 * ldu, ldu, Sc);
@@ -1705,7 +1728,7 @@ int mlmc_density_sample_joint_t_batch(int32_t M, const mlmc_basis *const *bases,
                                       uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *out, double *u_out,
                                       double *z_out, double *s_out, double *mass_out, int mem_kind) {
     MLMC_API_GUARD;
-    const QTCop tc{dof, mix_stream, s_out};
+    const QTCop tc{dof, mix_stream, s_out, dof};
     return q_copula("mlmc_density_sample_joint_t_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
                     streams, first, n, flags, nullptr, out, u_out, z_out, mass_out, mem_kind, &tc);
 }
@@ -1719,6 +1742,20 @@ int mlmc_density_sample_conditional_batch(int32_t M, const mlmc_basis *const *ba
     const QSets sets = {B, shift, rows, ld_rows};
     return q_copula("mlmc_density_sample_conditional_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor, seed,
                     streams, first, n, flags, &sets, out, u_out, z_out, mass_out, mem_kind);
+}
+
+int mlmc_density_sample_conditional_t_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda,
+                                            const double *sigma, const double *a, const double *b, int32_t n_intervals,
+                                            int32_t gauss_degree, int32_t K, const double *factor, double dof, double dof_mix,
+                                            uint64_t seed, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                            int32_t flags, int32_t B, const double *shift, const double *scale, const int32_t *rows,
+                                            int32_t ld_rows, double *out, double *u_out, double *z_out, double *s_out, double *mass_out,
+                                            int mem_kind) {
+    MLMC_API_GUARD;
+    const QSets sets = {B, shift, rows, ld_rows, scale};
+    const QTCop tc{dof, mix_stream, s_out, dof_mix};
+    return q_copula("mlmc_density_sample_conditional_t_batch", M, bases, R1, lambda, sigma, a, b, n_intervals, gauss_degree, K, factor,
+                    seed, streams, first, n, flags, &sets, out, u_out, z_out, mass_out, mem_kind, &tc);
 }
 
 int mlmc_density_scores_batch(int32_t M, const mlmc_basis *const *bases, const int32_t *R1, const double *lambda, const double *sigma,

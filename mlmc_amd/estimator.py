@@ -1071,7 +1071,7 @@ class Estimate:
         return draws, success, factor @ factor.T
 
     def sample_conditional(self, n, seed, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
-                           densities=None, first=0, antithetic=False, device=False, qmc=False):
+                           densities=None, first=0, antithetic=False, device=False, qmc=False, dof=None):
         """Seeded joint draws of the components that are not in `given`, CONDITIONAL on measured or fixed values of the others, in
         one batched device call (tool.simple_distribution.conditional_samples): the marginals and the Gaussian copula of
         `sample_joint`, with the scores of the given components fixed at Phi^-1(Fhat_o(x_o)).  Scenarios of the rest of a field
@@ -1083,6 +1083,11 @@ class Estimate:
         :param qmc: scrambled Sobol' points instead of pseudo-random ones (see tool.simple_distribution.conditional_samples): the streams are
             dimensions (at most 1024 latent normals: latent normal k is dimension k), n should be a power of two with `first` a multiple of it, and R seeds give R
             independent estimates whose spread is the error bar.  Not together with antithetic
+        :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula of `sample_joint(dof=...)`
+            (tool.simple_distribution.conditional_samples(dof=...)), under which an extreme given value widens the law of the other
+            components.  `corr` is then the t copula's correlation matrix, as in sample_joint ("quadrant" estimates it
+            consistently); dof + the number of given components must not exceed 192; the mixing variable takes the stream after
+            those of the latent normals
         :return: (samples, success [M], ConditionalFactorInfo): samples [M, n] for scalar values and [B, M, n] for arrays, rows
             of given components hold the given values; the solver's verdict per component; the components that were drawn,
             their conditional standard deviations in score space and what `correlation_factor` did to the matrix"""
@@ -1090,14 +1095,16 @@ class Estimate:
         if isinstance(n, bool) or int(n) != n or n < 0:
             raise ValueError("sample_conditional: n must be a non-negative integer")
         simple_distribution._sample_flags("sample_conditional", antithetic, qmc)
+        nu = simple_distribution._check_dof("sample_conditional", dof)
+        simple_distribution._check_conditional_dof("sample_conditional", nu, len(given) if hasattr(given, "items") else 0)
         corr, densities = self._copula_correlation("sample_conditional", corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
         distrs = [d[0] for d in densities]
         observed = simple_distribution._parse_given("sample_conditional", given, len(distrs))[0]
-        cond = simple_distribution.conditional_factor(corr, observed)
+        cond = simple_distribution.conditional_factor(corr, observed, return_observed=nu is not None)
         draws = simple_distribution.conditional_samples(distrs, int(n), seed, given, factor_info=cond, first=first,
-                                                        antithetic=antithetic, device=device, qmc=qmc)
+                                                        antithetic=antithetic, device=device, qmc=qmc, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return draws, success, cond[2]
 
@@ -1252,8 +1259,9 @@ class Estimate:
         copula.  Feed the result to `sample_joint(dof=...)`, `estimate_aggregates(dof=...)`, `estimate_tail_dependence(dof=...)`
         and to the joint numbers themselves: `estimate_joint_probability(dof=...)`, `estimate_joint_exceedance(dof=...)`,
         `sample_given_event(dof=...)`, `estimate_event_means(dof=...)` and the two bootstrap bands (Genz and Bretz's mixing
-        variable).  Not provided under a t copula: conditional draws and probabilities (`given`), and a bootstrap of nu -- the fit
-        has no error bar beyond the objective's shape over the grid.
+        variable), and to the what-if fan: `sample_conditional(dof=...)`, `estimate_conditional_quantiles(dof=...)`.  Not provided
+        under a t copula: conditional probabilities, event scenarios and aggregates (`given` on the entries above), and a
+        bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid.
         :param probs, tail, corr, densities: as in estimate_tail_dependence; corr="quadrant" is the estimate that is consistent
             under a t copula
         :param grid: candidate nu, finite values in [1, 64] or np.inf; None: 2, 3, 4, 5, 6, 8, 10, 15, 20, 30, inf
@@ -1484,19 +1492,21 @@ class Estimate:
         return AggregateSummary(names=names, probs=probs, prob=prob, n=n, seeds=seeds, **out), success
 
     def estimate_conditional_quantiles(self, probs, given, corr=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
-                                       densities=None):
+                                       densities=None, dof=None):
         """Quantiles of every component that is not in `given`, conditional on the given values of the others
         (tool.simple_distribution.conditional_quantiles): medians and bands of the rest of the vector once some of it is known.
         :param probs: probabilities, the same for every component
-        :param given, corr, densities: as in sample_conditional
+        :param given, corr, densities, dof: as in sample_conditional
         :return: (q, success): q [q, len(probs)] for scalar values, [B, q, len(probs)] for arrays, row m = the m-th component
             that is not given, ascending; success [M] bool, the solver's verdict per component"""
         from .tool import simple_distribution
+        nu = simple_distribution._check_dof("estimate_conditional_quantiles", dof)
+        simple_distribution._check_conditional_dof("estimate_conditional_quantiles", nu, len(given) if hasattr(given, "items") else 0)
         corr, densities = self._copula_correlation("estimate_conditional_quantiles", corr, densities, tol, reg_param,
                                                    orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
-        q = simple_distribution.conditional_quantiles([d[0] for d in densities], probs, given, corr)
+        q = simple_distribution.conditional_quantiles([d[0] for d in densities], probs, given, corr, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return q, success
 

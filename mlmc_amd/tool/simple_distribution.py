@@ -480,6 +480,10 @@ def correlation_factor(corr, min_eig=1e-10):
     return factor, CorrelationFactorInfo(min_eig_in, repaired, float(np.max(np.abs(factor @ factor.T - c))))
 
 
+# the largest degrees of freedom of the mixing variable of a conditional t law, nu + p (include/mlmc_hip.h)
+MAX_DOF_MIX = 192.0
+
+
 def _check_dof(what, dof):
     """None for the Gaussian copula (dof None or +inf), else nu as a float in [1, 64]"""
     if dof is None:
@@ -493,9 +497,21 @@ def _check_dof(what, dof):
     return None if nu == np.inf else nu
 
 
-def _t_elementwise(what, entry, x, dof, device):
-    """one of the elementwise entries of the t copula on a NumPy array or a float64 device tensor of any shape"""
-    nu = _check_dof(what, dof)
+def _check_dof_mix(what, dof_mix):
+    """the degrees of freedom of a conditional law's mixing variable, nu + p, as a float in [1, 192]"""
+    try:
+        nu = float(dof_mix)
+    except (TypeError, ValueError):
+        nu = np.nan
+    if isinstance(dof_mix, (bool, np.bool_)) or not 1.0 <= nu <= MAX_DOF_MIX:
+        raise ValueError("{}: dof_mix must lie in [1, {:g}], got {!r}".format(what, MAX_DOF_MIX, dof_mix))
+    return nu
+
+
+def _t_elementwise(what, entry, x, dof, device, mix=False):
+    """one of the elementwise entries of the t copula on a NumPy array or a float64 device tensor of any shape; mix: dof is the
+    dof_mix of `conditional_mixing_scale`"""
+    nu = _check_dof_mix(what, dof) if mix else _check_dof(what, dof)
     if nu is None:
         raise ValueError(what + ": dof must be finite, in [1, 64]")
     if hasattr(x, "data_ptr"):
@@ -534,6 +550,22 @@ def chi2_mixing_scale(p, dof, device=False):
     :param p: a NumPy array or a float64 torch device tensor of any shape
     :param device: return a float64 torch device tensor"""
     return _t_elementwise("chi2_mixing_scale", "mlmc_chi2_mixing_scale", p, dof, device)
+
+
+def conditional_mixing_scale(p, dof_mix, device=False):
+    """`chi2_mixing_scale` for the mixing variable of `conditional_samples(dof=...)`, whose degrees of freedom dof + p may reach
+    192 (mlmc_chi2_conditional_scale): dof_mix is a float in [1, 192]; up to 64 the values are those of `chi2_mixing_scale` bit
+    for bit.
+    :param p: a NumPy array or a float64 torch device tensor of any shape
+    :param device: return a float64 torch device tensor"""
+    return _t_elementwise("conditional_mixing_scale", "mlmc_chi2_conditional_scale", p, dof_mix, device, mix=True)
+
+
+def _check_conditional_dof(what, dof, p):
+    """the degrees of freedom nu + p of a t law conditioned on p components must stay within what the mixing scale is tested for"""
+    if dof is not None and dof + p > MAX_DOF_MIX:
+        raise ValueError("{}: dof + the number of given components = {:g} + {} exceeds {:g}, the largest degrees of freedom of the "
+                         "conditional mixing variable".format(what, dof, p, MAX_DOF_MIX))
 
 
 def _mixing_stream(what, dof, mix_stream, streams, K):
@@ -584,8 +616,8 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         one mixing uniform p0 per draw (with antithetic one per pair, so that the pair negates y exactly), T_dof of
         `student_t_cdf`.  F is a factor of the copula's correlation matrix: for a t copula the correlation of the normal scores is
         NOT that matrix; `Estimate.estimate_quadrant_correlation` estimates it consistently.  Box probabilities and
-        event scenarios under the same copula: `joint_probabilities(dof=...)`, `event_samples(dof=...)`.  Conditional draws
-        (`given`) exist for the Gaussian copula only
+        event scenarios under the same copula: `joint_probabilities(dof=...)`, `event_samples(dof=...)`; conditional draws,
+        quantiles and CDFs: `conditional_samples(dof=...)`, `conditional_quantiles(dof=...)`, `conditional_cdfs(dof=...)`
     :param mix_stream: the uint32 stream (qmc: the dimension, below 1024) of the mixing uniform; default K when `streams` is
         defaulted; with explicit `streams` it must be given and differ from all of them
     :param return_uniforms, return_normals, return_mixing: also return u [M, n], z [K, n] and / or s [n] (dof only), in this order
@@ -632,7 +664,7 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
 ConditionalFactorInfo = collections.namedtuple("ConditionalFactorInfo", "unobserved s min_eig_in repaired")
 
 
-def conditional_factor(corr, observed, min_eig=1e-10):
+def conditional_factor(corr, observed, min_eig=1e-10, return_observed=False):
     """What conditioning a Gaussian copula on the components `observed` needs, on the host in NumPy.  With C' = F F^T of
     `correlation_factor(corr, min_eig)` (repaired, unit diagonal), O = the observed components ascending, U the others ascending
     and L = cholesky(C'[P, P]) for P = O ++ U in blocks L_OO, L_UO, L_UU, the scores of U given the scores z_O of O are normal with
@@ -641,8 +673,10 @@ def conditional_factor(corr, observed, min_eig=1e-10):
     norm s_m in (0, 1], the conditional standard deviation of score m, and |L_UO[m]|^2 + s_m^2 = 1.
     :param observed: distinct component indices in any order; may be empty: then W is [M, 0] and F_c the factor of
         `correlation_factor` itself
+    :param return_observed: also return L_OO [p, p], the Cholesky factor of C'[O, O]: what the Student-t copula needs in addition,
+        since its conditional scale depends on d = |L_OO^-1 y_O|^2 (`conditional_samples(dof=...)`)
     :return: (W [q, p], F_c [q, q], ConditionalFactorInfo(unobserved [q], s [q], min_eig_in, repaired)), the last two those of
-        `correlation_factor`"""
+        `correlation_factor`; with return_observed a fourth item L_OO"""
     factor, info = correlation_factor(corr, min_eig)
     M = factor.shape[0]
     observed = list(observed)
@@ -658,6 +692,7 @@ def conditional_factor(corr, observed, min_eig=1e-10):
     if p == M:
         raise ValueError("conditional_factor: every component is observed, nothing is left to condition")
     unobs = np.setdiff1d(np.arange(M, dtype=np.int64), obs)
+    l_oo = np.zeros((0, 0))
     if p == 0:
         w, fc = np.zeros((M, 0)), factor
     else:
@@ -667,8 +702,10 @@ def conditional_factor(corr, observed, min_eig=1e-10):
         low = np.linalg.cholesky(c[np.ix_(perm, perm)])
         w = scipy.linalg.solve_triangular(low[:p, :p], low[p:, :p].T, lower=True, trans="T").T
         fc = np.ascontiguousarray(low[p:, p:])
+        l_oo = np.ascontiguousarray(low[:p, :p])
     s = np.sqrt(np.sum(fc * fc, axis=1))
-    return np.ascontiguousarray(w), fc, ConditionalFactorInfo(unobs, s, info.min_eig_in, info.repaired)
+    out = (np.ascontiguousarray(w), fc, ConditionalFactorInfo(unobs, s, info.min_eig_in, info.repaired))
+    return out + (l_oo,) if return_observed else out
 
 
 def _parse_given(what, given, M):
@@ -706,35 +743,58 @@ def _parse_given(what, given, M):
     return observed, values, scalar
 
 
-def _conditioning(what, distrs, given, corr, cond):
-    """what the conditional entries share: (observed [p], values [p, B], scalar?, u_O [p, B], (W, F_c, info), mu [B, q]): the scores
-    of the given values through ONE `normal_scores` call and the conditional means W z_O on the host"""
+def _conditional_t_scale(y_obs, l_oo, dof):
+    """r [B] = sqrt((nu + d) / (nu + p)), d = |L_OO^-1 y_O|^2, for the t scores y_O [p, B] of the given values: the factor by which a
+    Student-t copula widens (d > p) or narrows the conditional law of the other components; touches no device"""
+    y_obs = np.asarray(y_obs, dtype=np.float64)
+    p = y_obs.shape[0]
+    if p == 0:
+        return np.ones(y_obs.shape[1])
+    v = scipy.linalg.solve_triangular(np.asarray(l_oo, dtype=np.float64), y_obs, lower=True)
+    return np.sqrt((dof + np.sum(v * v, axis=0)) / (dof + p))
+
+
+def _conditioning(what, distrs, given, corr, cond, dof=None):
+    """what the conditional entries share: (observed [p], values [p, B], scalar?, u_O [p, B], (W, F_c, info), mu [B, q], r [B]):
+    the scores of the given values through ONE `normal_scores` call and the conditional means W z_O on the host.  With dof (a
+    Student-t copula) the scores are the t scores y_O, `cond` is the 4-tuple of conditional_factor(return_observed=True) and r
+    its conditional scale (`_conditional_t_scale`); without it r is ones"""
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
     observed, values, scalar = _parse_given(what, given, M)
+    _check_conditional_dof(what, dof, observed.size)
     if (corr is None) == (cond is None):
         raise ValueError(what + ": exactly one of corr and the result of conditional_factor must be given")
     if cond is None:
-        cond = conditional_factor(corr, observed)
-    w, fc, info = cond
+        cond = conditional_factor(corr, observed, return_observed=dof is not None)
+    if dof is not None and len(cond) != 4:
+        raise ValueError(what + ": with dof, factor_info must be the 4-tuple of conditional_factor(..., return_observed=True): the "
+                         "conditional scale of a t copula needs L_OO")
+    l_oo = np.asarray(cond[3], dtype=np.float64) if dof is not None else None
+    w, fc, info = cond[:3]
     w, fc = np.asarray(w, dtype=np.float64), np.ascontiguousarray(fc, dtype=np.float64)
     p, q, B = observed.size, M - observed.size, values.shape[1]
     if w.shape != (q, p) or fc.ndim != 2 or fc.shape[0] != q or fc.shape[1] < 1 \
             or not np.array_equal(np.asarray(info.unobserved), np.setdiff1d(np.arange(M), observed)):
         raise ValueError(what + ": the conditional factor does not belong to the components of given")
+    if l_oo is not None and l_oo.shape != (p, p):
+        raise ValueError(what + ": the conditional factor does not belong to the components of given")
     if p == 0:
-        return observed, values, scalar, np.empty((0, B)), (w, fc, info), np.zeros((B, q))
+        return observed, values, scalar, np.empty((0, B)), (w, fc, info), np.zeros((B, q)), np.ones(B)
     z, u = normal_scores([distrs[o] for o in observed], values, return_uniforms=True)
     bad = np.argwhere(~np.isfinite(z))
     if bad.size:
         raise ValueError(what + ": the given value {!r} of component {} (set {}) is NaN or outside the open domain of its "
                          "distribution".format(float(values[bad[0, 0], bad[0, 1]]), int(observed[bad[0, 0]]), int(bad[0, 1])))
-    return observed, values, scalar, u, (w, fc, info), np.ascontiguousarray((w @ z).T)
+    if dof is None:
+        return observed, values, scalar, u, (w, fc, info), np.ascontiguousarray((w @ z).T), np.ones(B)
+    y = t_scores(z, dof)
+    return observed, values, scalar, u, (w, fc, info), np.ascontiguousarray((w @ y).T), _conditional_t_scale(y, l_oo, dof)
 
 
 def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, streams=None, first=0, antithetic=False, device=False,
-                        return_uniforms=False, qmc=False):
+                        return_uniforms=False, qmc=False, dof=None, mix_stream=None, return_mixing=False):
     """Seeded joint draws of the components that are NOT in `given`, conditional on the given values of the others, under the
     Gaussian copula of `joint_samples`; B sets of given values through ONE device call (mlmc_density_sample_conditional_batch).
     The given values go to normal scores z_O (one `normal_scores` call); with (W, F_c) of `conditional_factor` the scores of the
@@ -754,6 +814,18 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
         (any first and n are allowed).  For an error bar repeat with R seeds: the seeds give independent scrambles, and the sample
         standard deviation of the R means estimates the error of their mean.  Not together with antithetic
     :param return_uniforms: also return u shaped like the draws; rows of given components hold Fhat_o(x_o)
+    :param dof: None or np.inf: the Gaussian copula above, bit for bit what it has always been.  A float in [1, 64]: the STUDENT-T
+        copula of `joint_samples(dof=...)` (mlmc_density_sample_conditional_t_batch).  Given the t scores y_O = t_scores(z_O, dof)
+        of the p given values, the t scores of the others are multivariate t with dof + p degrees of freedom, location W y_O and
+        scale matrix r^2 F_c F_c^T, r^2 = (dof + d) / (dof + p), d = |L_OO^-1 y_O|^2:
+            x[b, m, j] = Q_m(clamp(T_dof(mu[b, m] + r_b s_c[j] (F_c z)[m, j]))),   s_c = conditional_mixing_scale(p0, dof + p),
+        so an extreme given value WIDENS the law of the others (under the Gaussian copula the spread never depends on what was
+        observed).  dof + p must not exceed 192.  W, F_c and L_OO come from the same repaired matrix:
+        `factor_info` must then be the 4-tuple of conditional_factor(..., return_observed=True).  An empty `given` gives the draws
+        of `joint_samples(dof=...)` bit for bit
+    :param mix_stream: the stream (qmc: the dimension, below 1024) of the mixing uniform, as in `joint_samples`: default K when
+        `streams` is defaulted, required and different from all of them otherwise
+    :param return_mixing: also return the mixing scales s_c [n] (dof only), after the uniforms
     :return: draws [M, n] when every given value is a scalar, [B, M, n] otherwise: rows of the other components hold the draws, rows
         of given components the given values exactly; float64 torch device tensors with device=True"""
     what = "conditional_samples"
@@ -761,11 +833,31 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
     M = len(distrs)
     flags = _sample_flags(what, antithetic, qmc)
     _check_seed(what, seed)
+    dof = _check_dof(what, dof)
+    if return_mixing and dof is None:
+        raise ValueError(what + ": return_mixing needs dof (the Gaussian copula has no mixing variable)")
+    if dof is None:
+        _mixing_stream(what, dof, mix_stream, None, 0)
     n = int(_per_distribution_int(what, "n", n, 1)[0])
     first = int(_per_distribution_int(what, "first", first, 1)[0])
-    _parse_given(what, given, M)                # its errors come before anything touches the device; one of them is M = 0
+    observed = _parse_given(what, given, M)[0]  # its errors come before anything touches the device; one of them is M = 0
+    if dof is not None:                         # and so do those of the t copula: the factor is host work
+        _check_conditional_dof(what, dof, observed.size)
+        if (corr is None) == (factor_info is None):
+            raise ValueError(what + ": exactly one of corr and the result of conditional_factor must be given")
+        if factor_info is None:
+            factor_info, corr = conditional_factor(corr, observed, return_observed=True), None
+        if len(factor_info) != 4:
+            raise ValueError(what + ": with dof, factor_info must be the 4-tuple of conditional_factor(..., return_observed=True): "
+                             "the conditional scale of a t copula needs L_OO")
+        if np.ndim(factor_info[1]) != 2 or np.shape(factor_info[1])[1] < 1:
+            raise ValueError(what + ": the conditional factor does not belong to the components of given")
+        K = np.shape(factor_info[1])[1]
+        mix_stream = _mixing_stream(what, dof, mix_stream, _checked_streams(what, streams, K, "latent normal"), K)
+        if qmc and mix_stream >= 1024:
+            raise ValueError(what + ": with qmc mix_stream is a Sobol' dimension and must be below 1024")
     n_int, deg = _common_quadrature(what, distrs)
-    observed, values, scalar, u_obs, (_, fc, info), mu = _conditioning(what, distrs, given, corr, factor_info)
+    observed, values, scalar, u_obs, (_, fc, info), mu, r = _conditioning(what, distrs, given, corr, factor_info, dof)
     unobs = np.ascontiguousarray(info.unobserved, dtype=np.int32)
     q, K, B = unobs.size, fc.shape[1], values.shape[1]
     streams = _checked_streams(what, streams, K, "latent normal")
@@ -778,6 +870,7 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
         dev = torch.device("cuda", torch.cuda.current_device())
         out = torch.empty((B, M, n), dtype=torch.float64, device=dev)
         u = torch.empty((B, M, n), dtype=torch.float64, device=dev) if return_uniforms else None
+        s = torch.empty((n,), dtype=torch.float64, device=dev) if return_mixing else None
         if observed.size:
             out[:, observed.tolist(), :] = torch.from_numpy(np.ascontiguousarray(values.T)).to(dev)[:, :, None]
             if u is not None:
@@ -787,28 +880,75 @@ def conditional_samples(distrs, n, seed, given, corr=None, factor_info=None, str
     else:
         out = np.empty((B, M, n))
         u = np.empty((B, M, n)) if return_uniforms else None
+        s = np.empty(n) if return_mixing else None
         out[:, observed, :] = values.T[:, :, None]
         if u is not None:
             u[:, observed, :] = u_obs.T[:, :, None]
         kind = _lib.HOST
-    _lib.check(_lib.lib().mlmc_density_sample_conditional_batch(
-        q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
-        n_int, deg, K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
-        flags, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
-        _lib.ptr(u), None, None, kind))
+    if dof is None:
+        _lib.check(_lib.lib().mlmc_density_sample_conditional_batch(
+            q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
+            n_int, deg, K, _lib.ptr(fc), int(seed), _lib.ptr(streams), first, n,
+            flags, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(unobs), M, _lib.ptr(out),
+            _lib.ptr(u), None, None, kind))
+    else:
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        _lib.check(_lib.lib().mlmc_density_sample_conditional_t_batch(
+            q, C.cast(handles, C.c_void_p), _lib.ptr(r1), _lib.ptr(lam), _lib.ptr(sig), _lib.ptr(a), _lib.ptr(b),
+            n_int, deg, K, _lib.ptr(fc), dof, dof + observed.size, int(seed), _lib.ptr(streams), mix_stream, first, n,
+            flags, B, _lib.ptr(mu) if observed.size else None, _lib.ptr(r) if observed.size else None, _lib.ptr(unobs), M,
+            _lib.ptr(out), _lib.ptr(u), None, _lib.ptr(s), None, kind))
     if scalar:
         out, u = out[0], (None if u is None else u[0])
-    return (out, u) if return_uniforms else out
+    extra = tuple(v for v, want in ((u, return_uniforms), (s, return_mixing)) if want)
+    return (out,) + extra if extra else out
 
 
-def _conditional_law(what, distrs, given, corr):
-    """(the distributions that are not given, mu [B, q], s [q], every given value a scalar?) of `conditional_quantiles` / `_cdfs`"""
+def _conditional_law(what, distrs, given, corr, dof=None):
+    """(the distributions that are not given, mu [B, q], s [q], every given value a scalar?, dof or None, r [B], the number of
+    given components) of `conditional_quantiles` / `_cdfs`"""
     distrs = list(distrs)
-    _, _, scalar, _, (_, _, info), mu = _conditioning(what, distrs, given, corr, None)
-    return [distrs[m] for m in info.unobserved], mu, np.asarray(info.s), scalar
+    dof = _check_dof(what, dof)
+    if dof is not None:                          # before anything touches the device
+        _check_conditional_dof(what, dof, _parse_given(what, given, len(distrs))[0].size)
+    observed, _, scalar, _, (_, _, info), mu, r = _conditioning(what, distrs, given, corr, None, dof)
+    return [distrs[m] for m in info.unobserved], mu, np.asarray(info.s), scalar, dof, r, observed.size
 
 
-def conditional_quantiles(distrs, probs, given, corr):
+def _t_cdf_lower_tail(y, dof):
+    """T_dof(y) through the lower tail on either side (SciPy's stdtr), as `t_scores` inverts it"""
+    from scipy.special import stdtr
+    y = np.asarray(y, dtype=np.float64)
+    low = stdtr(float(dof), -np.abs(y))
+    return np.where(y > 0, 1.0 - low, low)
+
+
+def _t_quantile_lower_tail(p, dof):
+    """T_dof^-1(p) through the lower tail on either side (SciPy's stdtrit): -inf / +inf at 0 / 1, NaN for what is no probability"""
+    from scipy.special import stdtrit
+    p = np.asarray(p, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        upper = p > 0.5
+        t = stdtrit(float(dof), np.where(upper, 1.0 - p, p))
+        t = np.where(upper, -t, t)
+        t = np.where(p == 0.0, -np.inf, np.where(p == 1.0, np.inf, t))
+    return np.where((p >= 0.0) & (p <= 1.0), t, np.nan)
+
+
+def _t_conditional_quantile_map(p, mu, scale, dof, dof_c):
+    """p' = T_dof(mu + scale T_dofc^-1(p)): where the conditional quantile at p of a score that is t with dof_c degrees of freedom,
+    location mu and the given scale lies under its marginal t law with dof; host only, broadcasting"""
+    with np.errstate(invalid="ignore"):
+        return _t_cdf_lower_tail(mu + scale * _t_quantile_lower_tail(p, dof_c), dof)
+
+
+def _t_conditional_cdf_map(f, mu, scale, dof, dof_c):
+    """T_dofc((T_dof^-1(f) - mu) / scale), the inverse of `_t_conditional_quantile_map`; host only, broadcasting"""
+    with np.errstate(invalid="ignore"):
+        return _t_cdf_lower_tail((_t_quantile_lower_tail(f, dof) - mu) / scale, dof_c)
+
+
+def conditional_quantiles(distrs, probs, given, corr, dof=None):
     """Quantiles of every component that is not in `given`, conditional on the given values of the others, under the Gaussian
     copula: given z_O the score of component m is N(mu_m, s_m^2) (`conditional_factor`), so its conditional quantile at p is
         Q_m(p'),   p' = Phi(mu_m + s_m Phi^-1(p)),
@@ -816,33 +956,46 @@ def conditional_quantiles(distrs, probs, given, corr):
     p = 0 and p = 1 give the end points of the domain exactly, a NaN or out-of-range p gives NaN.
     :param probs: [P] probabilities, the same for every component and set
     :param given, corr: as in `conditional_samples`
+    :param dof: None or np.inf: the Gaussian copula.  A float in [1, 64]: the Student-t copula of `conditional_samples(dof=...)`:
+        the t score of component m given y_O is univariate t with dof + p degrees of freedom, location mu_m and scale r_b s_m, so
+            p' = T_dof(mu_m + r_b s_m T_{dof + p}^-1(p))
+        (SciPy's stdtrit / stdtr through the lower tail on either side, as `t_scores`)
     :return: [q, P] when every given value is a scalar, [B, q, P] otherwise; row m = component info.unobserved[m]"""
     from scipy.special import ndtr, ndtri
-    free, mu, s, scalar = _conditional_law("conditional_quantiles", distrs, given, corr)
+    free, mu, s, scalar, dof, r, n_given = _conditional_law("conditional_quantiles", distrs, given, corr, dof)
     probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
     with np.errstate(invalid="ignore"):
-        mapped = ndtr(mu[:, :, None] + s[None, :, None] * ndtri(probs)[None, None, :])             # [B, q, P]
+        if dof is None:
+            mapped = ndtr(mu[:, :, None] + s[None, :, None] * ndtri(probs)[None, None, :])         # [B, q, P]
+        else:
+            mapped = _t_conditional_quantile_map(probs[None, None, :], mu[:, :, None], r[:, None, None] * s[None, :, None], dof,
+                                                 dof + n_given)
     q = quantiles(free, [np.ascontiguousarray(mapped[:, m, :]).reshape(-1) for m in range(len(free))])
     out = np.stack([np.asarray(r).reshape(mu.shape[0], probs.size) for r in q], axis=1)
     return out[0] if scalar else out
 
 
-def conditional_cdfs(distrs, values, given, corr):
+def conditional_cdfs(distrs, values, given, corr, dof=None):
     """Conditional CDFs of every component that is not in `given`, the inverse of `conditional_quantiles`:
         Phi((Phi^-1(clamp(Fhat_m(x))) - mu_m) / s_m),
     Fhat_m through ONE `cdfs_on_rule` call, the clamp to [2^-53, 1 - 2^-53] of `normal_scores`, the map on the host.
     :param values: an array that broadcasts to [B, q, P] ([P]: the same points for every component and set; the result of
         `conditional_quantiles` as it is)
+    :param dof: None or np.inf: the Gaussian copula.  A float in [1, 64]: the Student-t copula of `conditional_quantiles(dof=...)`,
+        T_{dof + p}((T_dof^-1(clamp(Fhat_m(x))) - mu_m) / (r_b s_m))
     :return: [q, P] when every given value is a scalar, [B, q, P] otherwise"""
     from scipy.special import ndtr, ndtri
-    free, mu, s, scalar = _conditional_law("conditional_cdfs", distrs, given, corr)
+    free, mu, s, scalar, dof, r, n_given = _conditional_law("conditional_cdfs", distrs, given, corr, dof)
     values = np.asarray(values, dtype=np.float64)
     B, q = mu.shape
     x = np.broadcast_to(values, (B, q) + values.shape[-1:]) if values.ndim else np.broadcast_to(values, (B, q, 1))
     f = cdfs_on_rule(free, [np.ascontiguousarray(x[:, m, :]).reshape(-1) for m in range(q)])
     f = np.stack([np.asarray(r).reshape(B, -1) for r in f], axis=1)
-    z = ndtri(np.minimum(np.maximum(f, 2.0 ** -53), 1.0 - 2.0 ** -53))
-    out = ndtr((z - mu[:, :, None]) / s[None, :, None])
+    f = np.minimum(np.maximum(f, 2.0 ** -53), 1.0 - 2.0 ** -53)
+    if dof is None:
+        out = ndtr((ndtri(f) - mu[:, :, None]) / s[None, :, None])
+    else:
+        out = _t_conditional_cdf_map(f, mu[:, :, None], r[:, None, None] * s[None, :, None], dof, dof + n_given)
     return out[0] if scalar else out
 
 
@@ -1118,7 +1271,7 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
     if dof is not None:
         z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
     if observed.size:
-        _, _, _, _, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
+        _, _, _, _, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
         low = np.linalg.cholesky(cov[np.ix_(keep, keep)])
         shift = np.ascontiguousarray(np.broadcast_to(mu[:, keep], (B, keep.size)))
@@ -1310,7 +1463,7 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
     perm = _event_order(np.searchsorted(free, keep), q)
     order = free[perm]                                                                       # chain position -> component
     if observed.size:
-        _, _, _, u_obs, (_, fc, _), mu = _conditioning(what, distrs, given, corr, None)
+        _, _, _, u_obs, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
         low = np.linalg.cholesky(0.5 * (cov + cov.T)[np.ix_(perm, perm)])
         shift = np.ascontiguousarray(np.broadcast_to(mu[:, perm], (B, q)))

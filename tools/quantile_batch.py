@@ -83,6 +83,10 @@ after a warm-up each, five repetitions:
   map_entry_ms / mixing_entry_ms    wall time of student_t_cdf on M n device values of the t law and of chi2_mixing_scale on n device
                                     uniforms: the map and the mixing kernel on their own, with the entry's launch and wait
   t_over_gauss_wall / t_over_gauss_kernel   ratios of the means
+--tconditional: simple_distribution.conditional_samples(..., dof=nu, device=True), component 0 of M given in
+B sets, against the same call without dof on the shapes of --conditional, nu = 3 and 30, the two taking turns in one process after a
+warm-up each, five repetitions; the keys of --tcopula, with map_entry_ms on B (M - 1) n values and mixing_entry_ms
+(conditional_mixing_scale) on n uniforms at nu + 1 degrees of freedom
 --qmc: (a) samples, joint_samples and conditional_samples (device=True) with and without qmc=True on the
 shapes of --samples, --joint and --conditional (streams = index mod 1024 for both variants), the two taking turns after a warm-up
 call each:
@@ -131,7 +135,7 @@ process, the two taking turns after a warm-up call each (five repetitions unless
                                rate over the 8 TB/s of the data sheet
   equal_torch                  every counter equals the composition's (exact while counts stay below 2^53)
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
-                                                             [--tails | --divergences | --moments | --samples | --joint | --tcopula | --scores |
+                                                             [--tails | --divergences | --moments | --samples | --joint | --tcopula | --tconditional | --scores |
                                                               --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --aggregates |
                                                               --concordance] [--reps K]"""
 import argparse
@@ -525,6 +529,66 @@ def tcopula_shape(M, R1, n, K, dof, reps):
     span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
     mean = lambda t: sum(t) / len(t)
     return dict(M=M, R1=R1, n=n, K=K, dof=dof, t_ms=span(wall[0]), gauss_ms=span(wall[1]), t_kernel_ms=span(kern[0]),
+                gauss_kernel_ms=span(kern[1]), map_entry_ms=span(wall[2]), mixing_entry_ms=span(wall[3]),
+                t_over_gauss_wall=round(mean(wall[0]) / mean(wall[1]), 3),
+                t_over_gauss_kernel=round(mean(kern[0]) / mean(kern[1]), 3), all_success=ok)
+
+
+def tconditional_shape(M, R1, B, n, dof, reps):
+    """conditional_samples(dof=..., device=True) of B sets of n draws, component 0 of M given, against the Gaussian
+    conditional_samples of the same shape, the two taking turns in one process after a warm-up each; and the elementwise entries on
+    arrays of the call's sizes, which are the mixing kernel (n uniforms at dof + 1 degrees of freedom) and the map (B (M - 1) n
+    values of the t law) on their own, as in tcopula_shape"""
+    distrs, ok = mixtures(M, R1, seed=5)
+    lib = _lib.lib()
+    k_ms, k_n = C.c_double(), C.c_int64()
+    rng = np.random.default_rng(7)
+    A = rng.standard_normal((M, M + 3))
+    c = A @ A.T
+    d = 1.0 / np.sqrt(np.diag(c))
+    corr = c * d[:, None] * d[None, :]
+    cond_t, cond = sd.conditional_factor(corr, [0], return_observed=True), sd.conditional_factor(corr, [0])
+    xs = sd.quantiles([distrs[0]], [np.linspace(0.05, 0.95, B) if B > 1 else np.array([0.3])])[0]
+    seed = [1000 * M + R1]
+
+    def t_route():
+        seed[0] += 1
+        x = sd.conditional_samples(distrs, n, seed[0], {0: xs}, factor_info=cond_t, device=True, dof=dof)
+        torch.cuda.synchronize()
+        return x
+
+    def gauss_route():
+        seed[0] += 1
+        x = sd.conditional_samples(distrs, n, seed[0], {0: xs}, factor_info=cond, device=True)
+        torch.cuda.synchronize()
+        return x
+    p0 = torch.rand(n, dtype=torch.float64, device="cuda").clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+    y = torch.randn(B * (M - 1), n, dtype=torch.float64, device="cuda") * sd.conditional_mixing_scale(p0, dof + 1.0, device=True)[None, :]
+
+    def map_route():
+        u = sd.student_t_cdf(y, dof, device=True)
+        torch.cuda.synchronize()
+        return u
+
+    def mixing_route():
+        sc = sd.conditional_mixing_scale(p0, dof + 1.0, device=True)
+        torch.cuda.synchronize()
+        return sc
+    routes = (t_route, gauss_route, map_route, mixing_route)
+    for fn in routes:
+        fn()
+    wall, kern = [[] for _ in routes], [[] for _ in routes]
+    for _ in range(reps):
+        for k, fn in enumerate(routes):
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))       # reset
+            t0 = time.perf_counter()
+            fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            _lib.check(lib.mlmc_density_quantiles_kernel_time(C.byref(k_ms), C.byref(k_n)))
+            kern[k].append(k_ms.value)
+    span = lambda t: [round(min(t), 3), round(sum(t) / len(t), 3), round(max(t), 3)]
+    mean = lambda t: sum(t) / len(t)
+    return dict(M=M, R1=R1, B=B, n=n, dof=dof, t_ms=span(wall[0]), gauss_ms=span(wall[1]), t_kernel_ms=span(kern[0]),
                 gauss_kernel_ms=span(kern[1]), map_entry_ms=span(wall[2]), mixing_entry_ms=span(wall[3]),
                 t_over_gauss_wall=round(mean(wall[0]) / mean(wall[1]), 3),
                 t_over_gauss_kernel=round(mean(kern[0]) / mean(kern[1]), 3), all_success=ok)
@@ -1053,6 +1117,8 @@ def main():
                                                           "against estimate_component_covariance (DESIGN.md section 3.5.14)")
     ap.add_argument("--conditional", action="store_true", help="conditional_samples of B sets against a loop of single-set calls and "
                                                                "joint_samples of as many draws (DESIGN.md section 3.5.15)")
+    ap.add_argument("--tconditional", action="store_true", help="conditional_samples(dof=3, 30) against the Gaussian conditional_samples "
+                    "of the same shape, and the map and mixing functions on their own (DESIGN.md section 3.5.24)")
     ap.add_argument("--qmc", action="store_true", help="samples / joint_samples / conditional_samples with and without qmc, and the RMS "
                                                        "error of two integrals against n (DESIGN.md section 3.5.16)")
     ap.add_argument("--boxprob", action="store_true", help="copula_box_probabilities against closed forms, next to counting the "
@@ -1067,7 +1133,7 @@ def main():
     ap.add_argument("--reps", type=int, default=None)
     a = ap.parse_args()
     if a.reps is None:
-        a.reps = 5 if a.concordance or a.tcopula else 3
+        a.reps = 5 if a.concordance or a.tcopula or a.tconditional else 3
     _lib.init(0)
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
@@ -1121,6 +1187,13 @@ def main():
     elif a.qmc:
         out["qmc_times"] = qmc_times(a.reps, a.quick)
         out["qmc_errors"] = qmc_errors(a.quick)
+    elif a.tconditional:
+        shapes = [(12, 25, 1, 1_000_000), (12, 25, 64, 10_000), (12, 25, 1024, 1_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 9, 3, 1_000)]
+        out["tconditional"] = [tconditional_shape(M, R1, B, n, dof, a.reps) for M, R1, B, n in shapes for dof in (3.0, 30.0)]
     elif a.conditional:
         shapes = [(12, 25, 1, 1_000_000), (12, 25, 64, 10_000), (12, 25, 1024, 1_000)]
         if a.config:
