@@ -47,7 +47,8 @@ extern "C" {
                               *    mlmc_scenario_aggregates, mlmc_rows_weighted_sums, mlmc_concordance_counts,
                               *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch,
                               *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch,
-                              *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale */
+                              *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale,
+                              *    mlmc_student_t_quantile, mlmc_copula_log_density */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -518,7 +519,7 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
                                     int32_t K, const double *factor, uint64_t seed, const uint32_t *streams, int64_t first, int64_t n,
                                     int32_t flags, double *out, double *u_out, double *z_out, double *mass_out, int mem_kind);
 /* ---- the Student-t copula (copula_t.hip) -- added within 8 -------------------------------------------------------------
- * Two elementwise functions, one thread per element, unclamped; they are the definition that the sampling entry below refers to,
+ * Elementwise functions, one thread per element, unclamped; they are the definition that the sampling entry below refers to,
  * and they exist as entries so that their accuracy can be tested at chosen arguments.  dof = nu is a double in [1, 64]; what
  * depends on nu alone (the density at 0, log Gamma(nu / 2 + 1)) is made on the host once per call, in long double.
  *   mlmc_student_t_cdf: u = T_nu(y), the CDF of Student's t.  For y <= 0 it is the lower tail with RELATIVE accuracy: with t = |y|,
@@ -529,9 +530,17 @@ int mlmc_density_sample_joint_batch(int32_t M, const mlmc_basis *const *bases, c
  *   mlmc_chi2_mixing_scale: s = sqrt(nu / g), g the p-quantile of the chi-square law with nu degrees of freedom (Newton on the
  *     logarithm of the regularised incomplete gamma function, lower or upper by the side of p); NaN for p outside (0, 1); finite
  *     and positive for every odd multiple of 2^-53.  A standard normal times s with a uniform p is a Student-t variate.
- * Every loop of both has a fixed upper trip count.  n = 0 is a no-op; dof outside [1, 64] or NaN, n < 0, a null array and a bad
+ *   mlmc_student_t_quantile: y = T_nu^-1(p), the inverse of mlmc_student_t_cdf.  For 0 < p <= 1/2 it is -t with t >= 0 the root of
+ *     T_nu(-t) = p, T_nu(-t) the lower tail above: a start value (the tail's leading term, or the Cornish-Fisher expansion about the
+ *     normal quantile), then Halley steps on log T_nu(-t) - log p with both derivatives from the closed-form density, in log t
+ *     from the tail start and in t otherwise, the step clamped, at most 40 steps, until a step is below 2^-30 of t (of
+ *     max(t, T / density) in t, which near p = 1/2 is what one rounding of p moves the root by); a lane that does not converge
+ *     returns its last iterate.  For p > 1/2 it is -quantile(1 - p), and 1 - p is exact there, so quantile(1 - p) == -quantile(p)
+ *     bit for bit.  -inf at 0, +inf at 1, 0 at 1/2, NaN for NaN and for p outside [0, 1].
+ * Every loop of the three has a fixed upper trip count.  n = 0 is a no-op; dof outside [1, 64] or NaN, n < 0, a null array and a bad
  * mem_kind are errors.  The arrays [n] are host or device by mem_kind. */
 int mlmc_student_t_cdf(double dof, int64_t n, const double *y, double *u_out, int mem_kind);
+int mlmc_student_t_quantile(double dof, int64_t n, const double *p, double *y_out, int mem_kind);
 int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out, int mem_kind);
 /* Seeded JOINT draws of M problems through a STUDENT-T copula with dof degrees of freedom -- added within 8.  Problems, rule, tables,
  * the latent normals z[k][j], the chain acc = sum_k F[m][k] z[k][j] and Q_m are those of mlmc_density_sample_joint_batch, and so is
@@ -838,6 +847,44 @@ int mlmc_rows_weighted_sums(const double *y, int64_t n_rows, int64_t n, int64_t 
 #define MLMC_CONCORDANCE_MAX_G 16
 int mlmc_concordance_counts(const double *fine, const double *coarse, int32_t M, int64_t n, int64_t ld, int32_t G, const double *lower,
                             const double *upper, int64_t *pair, int64_t *all, int64_t *kept, double *kernel_ms);
+
+/* ---- copula log density (copula_lik.hip) -- added within 8 ---------------------------------------------------------------
+ * The log density of G copula models -- Gaussian or Student-t -- at columns of uniforms, for the fine and the coarse values of a
+ * level, and the sums from which the multilevel pseudo-likelihood (the mean of the log density at the samples' probability-integral
+ * transforms), its variance and those of every paired difference between two models follow.
+ *   A [G][M][M] host: the lower-triangular INVERSE Cholesky factor of model g's correlation matrix R_g = L L^T, A = L^-1 (what lies
+ *     above the diagonal is not read);  logdet [G] host = sum_i log L_ii = log det(R_g) / 2;  dof [G] host: nu in [1, 64], or +inf for
+ *     the Gaussian copula.  1 <= M <= MLMC_COPULA_LIK_MAX_M, 1 <= G <= MLMC_COPULA_LIK_MAX_G.
+ *   u_fine, u_coarse [M][ld], columns 0 .. n-1 are used, HOST or DEVICE by mem_kind; u_coarse may be NULL (level 0).  n >= 0, ld >= n.
+ *   A column is KEPT iff no u of it (fine, and coarse where present) is NaN, the rule of mlmc_concordance_counts.  Kept u are
+ *     clamped to [2^-53, 1 - 2^-53], as in mlmc_density_scores_batch.
+ * Per kept column, side and model, with v = A y (v_i = sum_{k <= i} A_ik y_k, k ascending, one rounded operation at a time) and
+ * Q = sum_i v_i^2 (i ascending):
+ *   Gaussian:  y = normcdfinv(u),  l = -1/2 (Q - sum_i y_i^2) - logdet, the two sums formed in the same order;
+ *   t:         y bit for bit mlmc_student_t_quantile(nu, u),
+ *              l = ((c - logdet) - (nu + M)/2 log1p(Q / nu)) + (nu + 1)/2 sum_i log1p(y_i^2 / nu),
+ *              c = lgamma((nu + M)/2) + (M - 1) lgamma(nu / 2) - M lgamma((nu + 1)/2), on the host in long double.
+ *   M = 1 (A = 1, logdet = 0) gives l = 0 for every model, and an identity A with logdet = 0 under the Gaussian model gives l = 0,
+ *   both exactly.  d_g = l^f_g - l^c_g; without u_coarse l^c = 0.
+ * Outputs.  kept [1] int64 host and sums [3 G + G G] host (either may be NULL): sum l^f [G], sum l^c [G], sum d [G], sum d_g d_h
+ *   [G][G] over the kept columns.  Optional per-column arrays, host or device by mem_kind, rows ldo >= n apart: y_out [G][M][ldo] the
+ *   scores of the fine side, ll_fine and ll_coarse [G][ldo] (ll_coarse needs u_coarse); NaN in dropped columns.
+ * A value depends on its column, the model and the side alone: not on n, ld, G, the order of the models, the presence of u_coarse,
+ *   mem_kind or the launch geometry.  The sums are a fixed tree set by n alone: columns 64 b .. 64 b + 63 are one block, a dropped
+ *   column and a lane beyond n add +0, the block adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; the blocks' partials are added by
+ *   256 threads, thread t the partials t, t + 256, ... in ascending order from 0, and the 256 sums fold by halves (128, 64, ... 1).
+ *   No floating-point atomics.  The columns go in launches of whole blocks that keep the scores within 192 MiB
+ *   (MLMC_COPULA_LIK_BLOCK_POINTS in the environment, read per call, sets the columns of a launch: a test aid, no value depends
+ *   on it).
+ * Errors, all before anything touches the device: M or G below 1 or above its cap, a null A / logdet / dof, n < 0, ld < n, a bad
+ *   mem_kind, ldo < n with an output array, ll_coarse without u_coarse, every output NULL, dof[g] neither in [1, 64] nor +inf, a
+ *   logdet that is not finite, a diagonal entry of A that is not finite and positive or an entry below it that is not finite (each
+ *   names the model), null u_fine with n > 0.  n = 0 sets kept and sums to 0. */
+#define MLMC_COPULA_LIK_MAX_M 128
+#define MLMC_COPULA_LIK_MAX_G 16
+int mlmc_copula_log_density(int32_t M, int32_t G, const double *A, const double *logdet, const double *dof, const double *u_fine,
+                            const double *u_coarse, int64_t n, int64_t ld, double *y_out, double *ll_fine, double *ll_coarse, int64_t ldo,
+                            int64_t *kept, double *sums, int mem_kind);
 
 /* ---- sample percentiles (Estimate.estimate_domain, mlmc/estimator.py:275-302) -------------------------- */
 /* out[i] = np.percentile(x[~isnan(x)], q_percent[i]) (NumPy "linear" method), bit-identical: exact order statistics by

@@ -24,6 +24,7 @@ BOX_PROB_MAX_M = 128       # MLMC_BOX_PROB_MAX_M
 AGG_MAX, AGG_MIN, AGG_COUNT, AGG_ARGMAX, AGG_ARGMIN = 1, 2, 4, 8, 16     # MLMC_AGG_*: the extra rows, in row order
 TAIL_UPPER, TAIL_LOWER = 0, 1                                            # MLMC_TAIL_*
 CONCORDANCE_MAX_M, CONCORDANCE_MAX_G = 1024, 16                          # MLMC_CONCORDANCE_MAX_M, _MAX_G
+COPULA_LIK_MAX_M, COPULA_LIK_MAX_G = 128, 16                             # MLMC_COPULA_LIK_MAX_M, _MAX_G
 
 
 class MlmcHipError(RuntimeError):
@@ -113,6 +114,7 @@ SIGNATURES = {
                                                     C.c_uint64, _vp, C.c_uint32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp,
                                                     C.c_int]),
     "mlmc_student_t_cdf": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
+    "mlmc_student_t_quantile": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
     "mlmc_chi2_mixing_scale": (C.c_int, [C.c_double, C.c_int64, _vp, _vp, C.c_int]),
     "mlmc_density_sample_conditional_batch": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                                         C.c_uint64, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int32,
@@ -137,6 +139,8 @@ SIGNATURES = {
     "mlmc_rows_weighted_sums": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp,
                                           _vp, C.c_int]),
     "mlmc_concordance_counts": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mlmc_copula_log_density": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                          _vp, _vp, C.c_int]),
     "mlmc_expr_create": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "mlmc_expr_destroy": (None, [_vp]),
     "mlmc_expr_eval": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _ip]),

@@ -68,5 +68,7 @@ void cop_launch_scaled_shifted(hipStream_t st, const double *F, int M, int K, co
                                int64_t ldu, const double *shift, const double *s, const double *scale, int B, int64_t set_rows);
 // U[m * ldu + c] = clamp(student_t_cdf(nu, U[m * ldu + c])) in place, m < M, c < ncols (k_tcop_map)
 void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, double *U, int64_t ldu);
+// Y[m * ldy + c] = student_t_quantile(nu, clamp(U[m * ldu + c])), NaN for NaN, m < M, c < ncols (k_tcop_scores); all device
+void cop_launch_t_scores(hipStream_t st, const TCopConst &C, int M, int64_t ncols, const double *U, int64_t ldu, double *Y, int64_t ldy);
 
 }  // namespace mlmc

@@ -1,6 +1,6 @@
-// The Student-t copula of mlmc_density_sample_joint_t_batch on the device (gfx950), and the two elementwise entries that define
-// its functions (include/mlmc_hip.h): mlmc_student_t_cdf, mlmc_chi2_mixing_scale.  The host path of the sampling entry is
-// density.hip's (q_copula); the product y = (F z) (x) s is the TSCALE instance of k_cop_uniforms (copula.hip).
+// The Student-t copula of mlmc_density_sample_joint_t_batch on the device (gfx950), and the elementwise entries that define its
+// functions (include/mlmc_hip.h): mlmc_student_t_cdf, mlmc_student_t_quantile, mlmc_chi2_mixing_scale.  The host path of the
+// sampling entry is density.hip's (q_copula); the product y = (F z) (x) s is the TSCALE instance of k_cop_uniforms (copula.hip).
 // mlmc_density_sample_conditional_t_batch uses the same kernels: the mixing scale with the constants of nu_c = nu + p (up to 192,
 // mlmc_chi2_conditional_scale), the map with those of nu, over the rows of all sets.
 //
@@ -11,7 +11,9 @@
 //   k_tcop_map   : U = clamp(student_t_cdf(nu, U)) in place, one thread per element.  The map is a kernel of its own and not the
 //                  epilogue of the product: a lane of the product holds 16 accumulators, and the series loop over them would keep
 //                  them and the constants of pow / exp / log1p live together (the comment at the top of copula.hip).
-//   k_t_cdf, k_chi2_scale : the elementwise entries, one thread per element
+//   k_tcop_scores : Y = student_t_quantile(clamp(U)), NaN for NaN, one thread per element: the t scores of
+//                  mlmc_copula_log_density (copula_lik.hip), a pass of its own ahead of the chain for the reason above
+//   k_t_elementwise : the elementwise entries, one thread per element
 //
 // student_t_cdf.  With t = |y|, a = nu / 2, A = (nu + 1) / 2 and c = Gamma(A) / (sqrt(nu pi) Gamma(a)) (the density at 0, from the
 // host), three regions:
@@ -29,6 +31,16 @@
 //   x < a + 1, Q = 1 - P the Lentz continued fraction beyond.  Start: Wilson-Hilferty, or (p Gamma(a + 1))^(1/a) where that is small.
 //   p <= 1/2: Newton on log P - log p in log x; p > 1/2: Newton on log Q - log(1 - p) in x (both nearly linear in their tail), the
 //   step clamped, at most C_NEWTON_CAP steps, stop once a step is below 2^-30 relative.
+// student_t_quantile.  For 0 < p <= 1/2 the root t >= 0 of t_lower(t) = p, y = -t; for p > 1/2 it is -Q(1 - p) (1 - p is exact
+//   there), so that Q(1 - p) == -Q(p) bit for bit.  Start: the leading term of the tail, t = sqrt(nu) / r with
+//   r = (p sqrt(nu) / c)^(1 / nu), where r < e^-0.7; else the Cornish-Fisher expansion about the normal quantile.  Halley steps on
+//   g = log T(-t) - log p (near the root from the difference T - p, which is then exact), both derivatives from the closed-form
+//   density f: g' = -f / T (beyond sqrt(nu) from the prefactor of the tail series: f may underflow where T does not) and
+//   f' / f = -(nu + 1) t / (nu + t^2).  From the tail start the variable is log t (g is nearly linear in it there: slope -nu),
+//   else t; the Halley factor is clamped to [1/2, 2] and the step to [-3, 3] (log t) or [-t / 2, max(1, t)]; at most
+//   T_NEWTON_CAP steps; stop once a step is below 2^-30 of t (log t) or of max(t, T / f) (t: near p = 1/2 the root tends to 0
+//   and T / f is what one rounding of p moves it by).  A lane that does not converge returns its last iterate.
+//   tests/copula_lik_cases.py counts the trips: at most 3.
 // Every loop has a fixed trip count.
 #include <algorithm>
 #include <cmath>
@@ -45,6 +57,8 @@ constexpr int T_LENTZ_CAP = 200;
 constexpr int C_SERIES_CAP = 400;
 constexpr int C_LENTZ_CAP = 400;
 constexpr int C_NEWTON_CAP = 40;
+constexpr int T_NEWTON_CAP = 40;
+constexpr double T_LOG_START = -0.7;                  // log r of the tail start below which the steps run in log t
 
 TCopConst tcop_constants(double dof) {
     TCopConst c;
@@ -122,6 +136,67 @@ __device__ double t_lower(const TCopConst &C, double t) {
 __device__ double student_t_cdf(const TCopConst &C, double y) {
     if (y != y) return y;
     return y <= 0.0 ? t_lower(C, -y) : 1.0 - t_lower(C, y);
+}
+
+// t >= 0 with T_nu(-t) = p, 0 < p <= 1/2
+__device__ double t_lower_root(const TCopConst &C, double p) {
+    const double nu = C.dof;
+    const double lr = log(p * C.sqrt_dof / C.c0) / nu;
+    const bool in_log = lr < T_LOG_START;
+    double t;
+    if (in_log) {
+        t = C.sqrt_dof * exp(-lr);
+        if (t == __builtin_inf()) return t;            // the root is beyond the largest number
+    } else {
+        const double z = -normcdfinv(p), z2 = z * z;
+        t = z + z * (z2 + 1.0) / (4.0 * nu) + z * ((5.0 * z2 + 16.0) * z2 + 3.0) / (96.0 * nu * nu);
+    }
+    for (int it = 0; it < T_NEWTON_CAP; ++it) {
+        const double T = t_lower(C, t);
+        double step;
+        if (!(T > 0.0)) {                              // beyond where T underflows: back towards the centre
+            step = in_log ? -3.0 : -0.5 * t;
+        } else {
+            const double rel = (T - p) / p;
+            const double g = fabs(rel) < 0.5 ? log1p(rel) : log(T / p);
+            // h = f / T = -g': beyond sqrt(nu) from the prefactor of the tail series, f = pre nu / t (f itself may underflow
+            // where T does not); w = -f' / f
+            double h;
+            if (t < C.sqrt_dof)
+                h = C.c0 * exp(-C.A * log1p(t * t / nu)) / T;
+            else {
+                const double r = C.sqrt_dof / t;
+                h = (C.c0 / C.sqrt_dof) * pow(r, nu) * exp(-C.A * log1p(r * r)) / T * (nu / t);
+            }
+            const double w = 2.0 * C.A / (nu / t + t);
+            if (in_log) {
+                const double th = t * h;
+                const double den = fmin(fmax(1.0 - 0.5 * g * (w / h - 1.0 - 1.0 / th), 0.5), 2.0);
+                step = fmin(fmax(g / th / den, -3.0), 3.0);
+            } else {
+                const double den = fmin(fmax(1.0 - 0.5 * g * (w / h - 1.0), 0.5), 2.0);
+                step = fmin(fmax(g / h / den, -0.5 * t), fmax(1.0, t));
+                if (fabs(step) <= 0x1p-30 * fmax(t, 1.0 / h)) {
+                    t += step;
+                    break;
+                }
+            }
+        }
+        if (in_log) {
+            t *= exp(step);
+            if (fabs(step) <= 0x1p-30) break;
+        } else
+            t += step;
+    }
+    return t;
+}
+
+__device__ double student_t_quantile(const TCopConst &C, double p) {
+    if (!(p >= 0.0 && p <= 1.0)) return __builtin_nan("");
+    if (p == 0.0) return -__builtin_inf();
+    if (p == 1.0) return __builtin_inf();
+    if (p == 0.5) return 0.0;
+    return p <= 0.5 ? -t_lower_root(C, p) : t_lower_root(C, 1.0 - p);
 }
 
 // P(a, x) (x < a + 1: the series) or Q(a, x) (the continued fraction), and D = x^a e^-x / Gamma(a + 1)
@@ -226,11 +301,22 @@ __global__ __launch_bounds__(TC_THREADS) void k_tcop_map(TCopConst C, int64_t nc
     *u = fmin(fmax(student_t_cdf(C, *u), 0x1p-53), 1.0 - 0x1p-53);
 }
 
-template <bool CHI2>
+enum { T_CDF = 0, T_CHI2 = 1, T_QUANTILE = 2 };         // the functions of k_t_elementwise
+
+template <int FN>
 __global__ __launch_bounds__(TC_THREADS) void k_t_elementwise(TCopConst C, int64_t n, const double *__restrict__ in, double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = CHI2 ? chi2_mixing_scale(C, in[i]) : student_t_cdf(C, in[i]);
+    out[i] = FN == T_CHI2 ? chi2_mixing_scale(C, in[i]) : FN == T_QUANTILE ? student_t_quantile(C, in[i]) : student_t_cdf(C, in[i]);
+}
+
+// Y = student_t_quantile(clamp(U)), NaN for NaN: one thread per element, blockIdx.y the row
+__global__ __launch_bounds__(TC_THREADS) void k_tcop_scores(TCopConst C, int64_t ncols, const double *__restrict__ U, int64_t ldu,
+                                                            double *__restrict__ Y, int64_t ldy) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncols) return;
+    const double u = U[(int64_t)blockIdx.y * ldu + c];
+    Y[(int64_t)blockIdx.y * ldy + c] = u != u ? u : student_t_quantile(C, fmin(fmax(u, 0x1p-53), 1.0 - 0x1p-53));
 }
 
 void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32_t stream, const uint64_t *sobol_row, int64_t first,
@@ -256,6 +342,12 @@ void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, 
                            dim3(TC_THREADS), 0, st, C, ncols, U + (int64_t)m0 * ldu, ldu);
 }
 
+void cop_launch_t_scores(hipStream_t st, const TCopConst &C, int M, int64_t ncols, const double *U, int64_t ldu, double *Y, int64_t ldy) {
+    for (int m0 = 0; m0 < M; m0 += 65535)
+        hipLaunchKernelGGL(k_tcop_scores, dim3((unsigned)((ncols + TC_THREADS - 1) / TC_THREADS), (unsigned)std::min(M - m0, 65535)),
+                           dim3(TC_THREADS), 0, st, C, ncols, U + (int64_t)m0 * ldu, ldu, Y + (int64_t)m0 * ldy, ldy);
+}
+
 int tcop_check_dof(const char *fn, double dof, int max_dof, const char *name) {
     if (!(dof >= 1.0 && dof <= (double)max_dof))
         return fail(std::string(fn) + ": " + name + " must lie in [1, " + std::to_string(max_dof) + "]");
@@ -267,7 +359,7 @@ static MultiWorkspace &t_ws() {
     return ws;
 }
 
-static int t_elementwise(const char *fn, bool chi2, double dof, int64_t n, const double *in, double *out, int mem_kind,
+static int t_elementwise(const char *fn, int which, double dof, int64_t n, const double *in, double *out, int mem_kind,
                          int max_dof = TCOP_MAX_DOF, const char *dof_name = "dof") {
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (tcop_check_dof(fn, dof, max_dof, dof_name)) return 1;
@@ -287,10 +379,12 @@ static int t_elementwise(const char *fn, bool chi2, double dof, int64_t n, const
         d_out = buf + n;
     }
     const dim3 grid((unsigned)((n + TC_THREADS - 1) / TC_THREADS));
-    if (chi2)
-        hipLaunchKernelGGL(k_t_elementwise<true>, grid, dim3(TC_THREADS), 0, st, C, n, d_in, d_out);
+    if (which == T_CHI2)
+        hipLaunchKernelGGL(k_t_elementwise<T_CHI2>, grid, dim3(TC_THREADS), 0, st, C, n, d_in, d_out);
+    else if (which == T_QUANTILE)
+        hipLaunchKernelGGL(k_t_elementwise<T_QUANTILE>, grid, dim3(TC_THREADS), 0, st, C, n, d_in, d_out);
     else
-        hipLaunchKernelGGL(k_t_elementwise<false>, grid, dim3(TC_THREADS), 0, st, C, n, d_in, d_out);
+        hipLaunchKernelGGL(k_t_elementwise<T_CDF>, grid, dim3(TC_THREADS), 0, st, C, n, d_in, d_out);
     MLMC_HIP_CHECK(hipGetLastError());
     if (mem_kind == MLMC_HOST) MLMC_HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
@@ -305,17 +399,22 @@ extern "C" {
 
 int mlmc_student_t_cdf(double dof, int64_t n, const double *y, double *u_out, int mem_kind) {
     MLMC_API_GUARD;
-    return t_elementwise("mlmc_student_t_cdf", false, dof, n, y, u_out, mem_kind);
+    return t_elementwise("mlmc_student_t_cdf", T_CDF, dof, n, y, u_out, mem_kind);
+}
+
+int mlmc_student_t_quantile(double dof, int64_t n, const double *p, double *y_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return t_elementwise("mlmc_student_t_quantile", T_QUANTILE, dof, n, p, y_out, mem_kind);
 }
 
 int mlmc_chi2_mixing_scale(double dof, int64_t n, const double *p, double *s_out, int mem_kind) {
     MLMC_API_GUARD;
-    return t_elementwise("mlmc_chi2_mixing_scale", true, dof, n, p, s_out, mem_kind);
+    return t_elementwise("mlmc_chi2_mixing_scale", T_CHI2, dof, n, p, s_out, mem_kind);
 }
 
 int mlmc_chi2_conditional_scale(double dof_mix, int64_t n, const double *p, double *s_out, int mem_kind) {
     MLMC_API_GUARD;
-    return t_elementwise("mlmc_chi2_conditional_scale", true, dof_mix, n, p, s_out, mem_kind, TCOP_MAX_DOF_MIX, "dof_mix");
+    return t_elementwise("mlmc_chi2_conditional_scale", T_CHI2, dof_mix, n, p, s_out, mem_kind, TCOP_MAX_DOF_MIX, "dof_mix");
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@ TailDependence = collections.namedtuple("TailDependence",
                                         "prob var chi model chi_model z marginal counts n_samples n_rm_samples corr")
 JointFrequency = collections.namedtuple("JointFrequency", "prob stderr counts n_samples")
 QuadrantCorrelation = collections.namedtuple("QuadrantCorrelation", "corr stderr prob var counts")
+CopulaLikelihood = collections.namedtuple("CopulaLikelihood",
+                                          "dof grid loglik stderr delta delta_stderr z l_means l_vars n_samples n_rm_samples corr")
 
 
 def quadrant_correlation(prob, var):
@@ -1261,7 +1263,8 @@ class Estimate:
         `sample_given_event(dof=...)`, `estimate_event_means(dof=...)` and the two bootstrap bands (Genz and Bretz's mixing
         variable), and to the what-if fan: `sample_conditional(dof=...)`, `estimate_conditional_quantiles(dof=...)`.  Not provided
         under a t copula: conditional probabilities, event scenarios and aggregates (`given` on the entries above), and a
-        bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid.
+        bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid (`estimate_copula_likelihood` fits
+        nu from every sample and gives each candidate a paired error bar).
         :param probs, tail, corr, densities: as in estimate_tail_dependence; corr="quadrant" is the estimate that is consistent
             under a t copula
         :param grid: candidate nu, finite values in [1, 64] or np.inf; None: 2, 3, 4, 5, 6, 8, 10, 15, 20, 30, inf
@@ -1273,6 +1276,103 @@ class Estimate:
         walk = self._tail_concordance(what, probs, tail, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         fit = simple_distribution.fit_copula_dof(walk["prob"], walk["var"], walk["levels"], walk["corr"], grid)
         return fit, self._tail_dependence(walk, None if fit.dof == np.inf else fit.dof)
+
+    def _likelihood_corr_specs(self, what, corr, G):
+        """one entry per grid value from `corr` of estimate_copula_likelihood: None, "scores", "quadrant" or a matrix [M, M] for all,
+        or a sequence of G such values; checked before any walk"""
+        def one(c):
+            if c is None:
+                return None
+            if isinstance(c, str):
+                if c not in ("scores", "quadrant"):
+                    raise ValueError("{}: corr must be None, 'scores', 'quadrant' or a correlation matrix, got {!r}".format(what, c))
+                return c
+            m = np.asarray(c, dtype=np.float64)
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError("{}: corr must be None, 'scores', 'quadrant' or a correlation matrix [M, M], or one such value "
+                                 "per grid entry; got an array of shape {}".format(what, m.shape))
+            return m
+        if corr is None or isinstance(corr, str):
+            return [one(corr)] * G
+        if isinstance(corr, (list, tuple)) and any(c is None or isinstance(c, str) or np.ndim(c) == 2 for c in corr):
+            if len(corr) != G:
+                raise ValueError("{}: {} correlations for {} grid values".format(what, len(corr), G))
+            return [one(c) for c in corr]
+        m = np.asarray(corr, dtype=np.float64)
+        if m.ndim == 3:
+            if m.shape[0] != G:
+                raise ValueError("{}: {} correlations for {} grid values".format(what, m.shape[0], G))
+            return [one(c) for c in m]
+        return [one(m)] * G
+
+    def estimate_copula_likelihood(self, dofs=None, corr="quadrant", densities=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4,
+                                   moments_fns=None):
+        """The degrees of freedom of a Student-t copula for the components by PSEUDO-LIKELIHOOD (inference functions for margins):
+        the multilevel mean of the copula log density at the probability-integral transforms of the stored samples, for every nu of
+        a grid, np.inf being the Gaussian copula.  Unlike `estimate_copula_dof`, which reads a few tail counts of pairs, it uses
+        every sample and the whole M-variate law, and it compares two models with an error bar: the paired differences of their log
+        densities.  ONE pass over the stored samples for the whole grid: each fine and coarse value goes through its marginal's CDF
+        on the device, and mlmc_copula_log_density evaluates all models on the device-resident uniforms
+        (quantity_estimate.component_copula_likelihood).
+        :param dofs: candidate nu, finite values in [1, 64] or np.inf; None: tool.simple_distribution.COPULA_DOF_GRID
+        :param corr: what `estimate_tail_dependence` takes -- None (Pearson), "scores", "quadrant" or a correlation matrix [M, M] --
+            or one such value per grid entry, e.g. "scores" for np.inf and "quadrant" for the finite nu ("quadrant" is the estimate
+            that is consistent under a t copula, "scores" the efficient one under the Gaussian copula).  Every matrix goes through
+            tool.simple_distribution.correlation_factor; the repaired matrix is the one whose density is evaluated
+        :param densities: as in estimate_component_quantiles
+        :return: (CopulaLikelihood, success).  CopulaLikelihood(dof, grid, loglik, stderr [G], delta, delta_stderr, z [G], l_means,
+            l_vars [L, G], n_samples, n_rm_samples [L], corr [G, M, M]):
+            loglik = sum over the levels of the mean of l^f - l^c, stderr = sqrt(sum_l var_l / n_l);
+            dof = the grid value with the largest loglik, a tie goes to the larger nu (as in fit_copula_dof);
+            delta = the paired multilevel difference of every model from the best one (<= 0), delta_stderr its standard error from
+            the sums of d_g d_h, z = delta / delta_stderr (0 at the best model, NaN where the standard error is not positive and
+            finite); corr the correlation matrices that were evaluated.  success [M]: whether each marginal's fit converged.
+        What the error bars do NOT contain: the sampling error of the correlation estimates and of the fitted marginals."""
+        from .tool import simple_distribution
+        what = "estimate_copula_likelihood"
+        grid = simple_distribution._dof_grid(what, simple_distribution.COPULA_DOF_GRID if dofs is None else dofs)
+        G = grid.size
+        if G > simple_distribution._lib.COPULA_LIK_MAX_G:
+            raise ValueError("{}: at most {} grid values per call".format(what, simple_distribution._lib.COPULA_LIK_MAX_G))
+        specs = self._likelihood_corr_specs(what, corr, G)
+        if isinstance(densities, str):
+            raise ValueError(what + ": densities must be the list construct_densities returned")
+        if densities is None:
+            densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        densities = list(densities)
+        M = int(self._quantity.size())
+        if len(densities) != M:
+            raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
+        success = np.array([bool(d[2].success) for d in densities], dtype=bool)
+        named, mats = {}, []
+        for spec in specs:
+            key = spec if (spec is None or isinstance(spec, str)) else None
+            if isinstance(spec, np.ndarray):
+                m = spec
+            else:
+                if key not in named:
+                    named[key] = np.asarray(self._copula_correlation(what, spec, densities, tol, reg_param, orth_moments_tol,
+                                                                     moments_fns)[0], dtype=np.float64)
+                m = named[key]
+            if m.shape != (M, M):
+                raise ValueError("{}: corr of shape {}, expected ({}, {})".format(what, m.shape, M, M))
+            mats.append(m)
+        sums = qe.component_copula_likelihood(self._quantity, [d[0] for d in densities], np.stack(mats), grid)
+        if int(np.sum(sums.n)) == 0:
+            raise Exception("All samples were masked")
+        st = simple_distribution.likelihood_statistics(sums.n, sums.sum_diff, sums.sum_gram)
+        loglik = st["loglik"]
+        best_ll = np.max(loglik)
+        ties = np.flatnonzero(loglik == best_ll)
+        best = int(ties[np.argmax(grid[ties])]) if ties.size else 0
+        with np.errstate(all="ignore"):
+            stderr = np.sqrt(st["var"])
+            delta = st["delta"][:, best].copy()
+            delta_stderr = np.sqrt(st["delta_var"][:, best])
+            z = np.where(np.isfinite(delta_stderr) & (delta_stderr > 0.0), delta / delta_stderr, np.nan)
+        z[best] = 0.0
+        return CopulaLikelihood(float(grid[best]), grid, loglik, stderr, delta, delta_stderr, z, st["l_means"], st["l_vars"],
+                                np.asarray(sums.n, dtype=np.int64), np.asarray(sums.n_rm, dtype=np.int64), sums.models.corr), success
 
     def estimate_quadrant_correlation(self, densities=None, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None):
         """The correlation matrix of the copula from how often two components lie above their medians at once: for every elliptical

@@ -1463,6 +1463,76 @@ def concordance_statistics(n, counts):
                 prob=np.sum(l_means, axis=0).reshape(shape), var=var.reshape(shape))
 
 
+class _LikelihoodSink:
+    """Where the (level, pair) stream of component_copula_likelihood ends: every pair goes block by block through
+    _ScoreRows.uniforms, mlmc_copula_log_density runs on each block of device-resident uniforms, and the level sums of the blocks
+    are added on the host in arrival order."""
+
+    def __init__(self, walk, M, models, scores):
+        self._dev, self._M, self._models = walk.dev, M, models
+        G = models.dof.size
+        self._scores = _ScoreRows(scores, "component_copula_likelihood")
+        self._kept = np.zeros(walk.n_levels, dtype=np.int64)
+        self._seen = np.zeros(walk.n_levels, dtype=np.int64)
+        self._sums = np.zeros((walk.n_levels, 3 * G + G * G))
+
+    def push(self, level_id, pair):
+        from ..tool import simple_distribution
+        if pair is None or pair[0].shape[-1] == 0:
+            return
+        fine, coarse = pair
+        self._seen[level_id] += int(fine.shape[-1])
+        for u_fine, u_coarse in self._scores.uniforms(fine, coarse, self._dev):
+            nc = int(u_fine.shape[-1])
+            kept, sums = simple_distribution._copula_log_density_into(self._models, u_fine, u_coarse, nc, nc)
+            self._kept[level_id] += kept
+            self._sums[level_id] += sums
+
+    def finish(self):
+        """-> n, n_rm [L], sum l^f, sum l^c, sum d [L, G], sum d_g d_h [L, G, G]"""
+        G = self._models.dof.size
+        s = self._sums
+        return (self._kept, self._seen - self._kept, s[:, :G].copy(), s[:, G:2 * G].copy(), s[:, 2 * G:3 * G].copy(),
+                s[:, 3 * G:].reshape(-1, G, G).copy())
+
+
+ComponentCopulaLikelihood = collections.namedtuple("ComponentCopulaLikelihood", "n n_rm sum_fine sum_coarse sum_diff sum_gram models")
+
+
+def component_copula_likelihood(quantity, scores, corrs, dofs):
+    """Per level, the sums of the log densities of G copula models at the probability-integral transforms of the stored samples of
+    the scalar components of `quantity` (mlmc_copula_log_density, mlmc_amd/csrc/copula_lik.hip): one pass per stored chunk for all
+    models (tool.simple_distribution.likelihood_statistics turns the sums into means, variances and paired differences).
+
+    Every pair goes block by block (score_block_columns(M) columns, one reused workspace) through u = Fhat_m(x) on the device, the
+    bits of mlmc_density_cdf_batch, and the entry runs on each block without the uniforms ever being downloaded.  A value that is
+    NaN or outside its density's open domain has u = NaN and drops its column, like any NaN in any component, fine or coarse: so
+    `n` equals the n_samples of Estimate.estimate_score_correlation on the same store.  The sums of a block are a fixed tree; the
+    blocks are added on the host in arrival order, so the float sums depend on the block width (`score_block_columns`) in their
+    last bits.  For a given store the result repeats bit for bit.
+    :param scores: a list of M distributions with multipliers (one quadrature)
+    :param corrs: one correlation matrix [M, M] for all models or one per model; each goes through correlation_factor
+    :param dofs: one value per model: floats in [1, 64], np.inf for the Gaussian copula
+    :return: ComponentCopulaLikelihood(n [L], n_rm [L] kept and dropped samples, sum_fine, sum_coarse, sum_diff [L, G] the sums of
+        l^f, l^c and d = l^f - l^c (l^c = 0 on a level without coarse values), sum_gram [L, G, G] the sums of d_g d_h, models the
+        CopulaModels that were evaluated)"""
+    from .. import _lib
+    from ..tool import simple_distribution
+    what = "component_copula_likelihood"
+    if scores is None:
+        raise ValueError(what + ": scores (the M marginal distributions) are required")
+    M, _, scores = _component_args(what, quantity, None, scores, _lib.COPULA_LIK_MAX_M)
+    models = simple_distribution._copula_models(what, corrs, dofs, M)
+    with _estimate_lock:
+        target = _estimate_target(quantity, True)
+        walk = _walk_setup(quantity, target.source)
+        sink = _LikelihoodSink(walk, M, models, scores)
+        with contextlib.closing(_level_pairs(target, walk)) as level_pairs:
+            for level_id, pair in level_pairs:
+                sink.push(level_id, pair)
+        return ComponentCopulaLikelihood(*sink.finish(), models)
+
+
 def _on_device_subsample(pair, target, level_id):
     """the pair, or its share of the sub-sample of Quantity.subsample"""
     if target.subsample_params is not None and pair is not None and pair[0].shape[-1] > 0:

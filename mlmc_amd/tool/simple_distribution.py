@@ -2113,6 +2113,179 @@ def fit_copula_dof(prob, var, probs, corr, grid=COPULA_DOF_GRID):
     return CopulaDofFit(dof, g, objective, z)
 
 
+CopulaLogDensity = collections.namedtuple("CopulaLogDensity", "fine coarse scores")
+CopulaModels = collections.namedtuple("CopulaModels", "A logdet dof corr")
+
+
+def _copula_models(what, corr, dofs, M=None):
+    """the models of mlmc_copula_log_density: `dofs` one value or a sequence of G (np.inf: Gaussian), `corr` one correlation matrix
+    for all or a sequence of G.  Each matrix goes through `correlation_factor` (the repaired matrix is the one that is inverted):
+    A = F^-1 by a triangular solve, logdet = sum log F_ii.  -> CopulaModels(A [G, M, M], logdet [G], dof [G], corr [G, M, M])"""
+    dof = _dof_grid(what, dofs if np.ndim(dofs) else [dofs])
+    G = dof.size
+    if G > _lib.COPULA_LIK_MAX_G:
+        raise ValueError("{}: {} models, at most {} are supported per call".format(what, G, _lib.COPULA_LIK_MAX_G))
+    try:
+        c = np.asarray(corr, dtype=np.float64)
+    except (TypeError, ValueError):
+        c = None
+    if c is None or c.ndim not in (2, 3) or c.shape[-1] != c.shape[-2] or (c.ndim == 3 and c.shape[0] != G):
+        raise ValueError("{}: corr must be one correlation matrix [M, M] or one per model [{}, M, M]".format(what, G))
+    if M is not None and c.shape[-1] != M:
+        raise ValueError("{}: corr of shape {}, expected ({}, {})".format(what, c.shape[-2:], M, M))
+    M = c.shape[-1]
+    if not 1 <= M <= _lib.COPULA_LIK_MAX_M:
+        raise ValueError("{}: {} components, between 1 and {} are supported".format(what, M, _lib.COPULA_LIK_MAX_M))
+    mats = [c] if c.ndim == 2 else list(c)
+    made = []
+    for m in mats:
+        F = correlation_factor(m)[0]
+        made.append((scipy.linalg.solve_triangular(F, np.eye(M), lower=True), float(np.sum(np.log(np.diag(F)))), F @ F.T))
+    if len(made) == 1:
+        made = made * G
+    return CopulaModels(np.ascontiguousarray(np.tril(np.stack([m[0] for m in made]))), np.array([m[1] for m in made]), dof,
+                        np.stack([m[2] for m in made]))
+
+
+def _copula_log_density_into(models, u_fine, u_coarse, n, ld, y_out=None, ll_fine=None, ll_coarse=None, ldo=0, sums=True, kind=None):
+    """one call of mlmc_copula_log_density; the arrays are NumPy arrays or float64 device tensors of one kind (rows ld / ldo apart, n
+    columns used); the caller has synchronised the stream that produced device inputs.  -> (kept, sums [3 G + G G]) or None"""
+    G, M = models.A.shape[0], models.A.shape[1]
+    kept = np.zeros(1, dtype=np.int64) if sums else None
+    out = np.zeros(3 * G + G * G) if sums else None
+    _lib.check(_lib.lib().mlmc_copula_log_density(M, G, _lib.ptr(models.A), _lib.ptr(models.logdet), _lib.ptr(models.dof),
+                                                  _lib.ptr(u_fine), _lib.ptr(u_coarse), int(n), int(ld), _lib.ptr(y_out),
+                                                  _lib.ptr(ll_fine), _lib.ptr(ll_coarse), int(ldo), _lib.ptr(kept), _lib.ptr(out),
+                                                  _lib.mem_kind(u_fine) if kind is None else kind))
+    return (int(kept[0]), out) if sums else None
+
+
+def student_t_quantile(p, dof, device=False):
+    """The quantile function of Student's t with `dof` degrees of freedom (a float in [1, 64]) on the device, elementwise
+    (mlmc_student_t_quantile): the inverse of `student_t_cdf`, by Halley steps on the logarithm of its lower tail.
+    quantile(1 - p) == -quantile(p) bit for bit for p > 1/2; -inf / +inf at 0 / 1, 0 at 1/2, NaN for NaN and outside [0, 1].
+    :param p: a NumPy array or a float64 torch device tensor of any shape
+    :param device: return a float64 torch device tensor"""
+    return _t_elementwise("student_t_quantile", "mlmc_student_t_quantile", p, dof, device)
+
+
+def copula_log_density(u, corr, dofs, u_coarse=None, device=False, return_scores=False):
+    """The log density of Gaussian and Student-t copulas at columns of uniforms, for G models in ONE device call
+    (mlmc_copula_log_density): l[g, j] = log c_g(u[:, j]).  A uniform is clamped to [2^-53, 1 - 2^-53]; a column with a NaN in any
+    row (of `u_coarse` too, when given) is dropped: NaN in every output.  The mean of l over the samples' probability-integral
+    transforms is the pseudo-likelihood of model g; `Estimate.estimate_copula_likelihood` forms it over the levels of a store.
+    :param u: [M, n] uniforms, a NumPy array or a float64 torch device tensor
+    :param corr: one correlation matrix [M, M] for all models, or a sequence of G; each goes through `correlation_factor`
+    :param dofs: one value or a sequence of G: floats in [1, 64], np.inf for the Gaussian copula
+    :param u_coarse: None or an array like `u` (the coarse values of the same samples)
+    :param device: return float64 torch device tensors
+    :param return_scores: also return the scores y [G, M, n] of `u`: normcdfinv(u) for a Gaussian model, the bits of
+        `student_t_quantile(u, dof)` for a t model
+    :return: l [G, n]; with `u_coarse` or `return_scores` CopulaLogDensity(fine, coarse, scores), None for what was not asked"""
+    what = "copula_log_density"
+
+    def checked(x, name):                                           # before anything touches the device
+        if hasattr(x, "data_ptr"):
+            if not x.is_cuda or str(x.dtype) != "torch.float64":
+                raise ValueError("{}: {} must be a NumPy array or a float64 device tensor".format(what, name))
+        else:
+            x = np.asarray(x, dtype=np.float64)
+        if len(x.shape) != 2 or x.shape[0] < 1:
+            raise ValueError("{}: {} must be [M, n], got shape {}".format(what, name, tuple(x.shape)))
+        return x
+    u = checked(u, "u")
+    M, n = int(u.shape[0]), int(u.shape[1])
+    if u_coarse is not None:
+        u_coarse = checked(u_coarse, "u_coarse")
+        if tuple(u_coarse.shape) != (M, n) or hasattr(u_coarse, "data_ptr") != hasattr(u, "data_ptr"):
+            raise ValueError("{}: u {} and u_coarse {} must be arrays of one kind and shape".format(what, tuple(u.shape),
+                                                                                                   tuple(u_coarse.shape)))
+    models = _copula_models(what, corr, dofs, M)
+    G = models.dof.size
+    on_device = hasattr(u, "data_ptr")
+    if on_device:
+        import torch
+        u = u.contiguous()
+        u_coarse = None if u_coarse is None else u_coarse.contiguous()
+    else:
+        u = np.ascontiguousarray(u)
+        u_coarse = None if u_coarse is None else np.ascontiguousarray(u_coarse)
+    shapes = ((G, M, n) if return_scores else None, (G, n), None if u_coarse is None else (G, n))
+    if on_device:
+        outs = [None if s is None else torch.empty(s, dtype=torch.float64, device=u.device) for s in shapes]
+        torch.cuda.current_stream(u.device).synchronize()           # the library reads and writes on its own stream
+    else:
+        outs = [None if s is None else np.empty(s) for s in shapes]
+    if n > 0:
+        _copula_log_density_into(models, u, u_coarse, n, n, outs[0], outs[1], outs[2], n, sums=False)
+    if on_device and not device:
+        outs = [None if t is None else t.cpu().numpy() for t in outs]
+    elif device and not on_device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        outs = [None if t is None else torch.from_numpy(t).to(dev) for t in outs]
+    if u_coarse is None and not return_scores:
+        return outs[1]
+    return CopulaLogDensity(outs[1], outs[2], outs[0])
+
+
+def likelihood_statistics(n, sd, sdd):
+    """Level statistics of copula log densities from their sums (`quantity_estimate.component_copula_likelihood`): n [L] kept
+    samples, sd [L, G] = sum_j d_g and sdd [L, G, G] = sum_j d_g d_h of the level differences d_g = l^f_g - l^c_g.  Through
+    engine.level_stats: mean_l = s / n_l, var_l = (q - s^2 / n_l) / (n_l - 1), inf where n_l <= 1.
+    -> dict(l_means, l_vars [L, G], loglik = sum_l mean_l, var = sum_l var_l / n_l [G], and the same for every paired difference
+    d_g - d_h, whose sum of squares is sdd_gg + sdd_hh - 2 sdd_gh: delta_l_means, delta_l_vars [L, G, G], delta, delta_var [G, G])"""
+    from .. import engine
+    n = np.asarray(n, dtype=np.int64)
+    sd = np.asarray(sd, dtype=np.float64)
+    sdd = np.asarray(sdd, dtype=np.float64)
+    if sd.ndim != 2 or n.shape != (sd.shape[0],) or sdd.shape != sd.shape + (sd.shape[1],):
+        raise ValueError("likelihood_statistics: n [L], sd [L, G] and sdd [L, G, G] are expected, got {}, {} and {}".format(
+            n.shape, sd.shape, sdd.shape))
+    L, G = sd.shape
+    nf = n.astype(np.float64)[:, None]
+    diag = sdd[:, np.arange(G), np.arange(G)]
+    l_means, l_vars = engine.level_stats(n, sd, diag)
+    ds = (sd[:, :, None] - sd[:, None, :]).reshape(L, G * G)
+    dq = (diag[:, :, None] + diag[:, None, :] - 2.0 * sdd).reshape(L, G * G)
+    d_means, d_vars = engine.level_stats(n, ds, dq)
+    with np.errstate(all="ignore"):
+        var = np.sum(l_vars / nf, axis=0)
+        d_var = np.sum(d_vars / nf, axis=0)
+    return dict(l_means=l_means, l_vars=l_vars, loglik=np.sum(l_means, axis=0), var=var,
+                delta_l_means=d_means.reshape(L, G, G), delta_l_vars=d_vars.reshape(L, G, G),
+                delta=np.sum(d_means, axis=0).reshape(G, G), delta_var=d_var.reshape(G, G))
+
+
+def joint_log_density(distrs, x, corr, dof=None):
+    """The log of the joint density that the marginals `distrs` and a copula define, at the columns of x [M, n]:
+    log c(Fhat_1(x_1), ..., Fhat_M(x_M)) + sum_m log rho_m(x_m), a host composition of `copula_log_density` with `cdfs_on_rule`
+    and `densities`.  NaN where a component is NaN or outside the open domain of its distribution.
+    :param corr: the copula's correlation matrix [M, M]
+    :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula
+    :return: [n]"""
+    what = "joint_log_density"
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    nu = _check_dof(what, dof)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[0] != M:
+        raise ValueError("{}: x must be [M, n] with M = {} distributions, got shape {}".format(what, M, x.shape))
+    models = _copula_models(what, corr, [np.inf if nu is None else nu], M)          # checks corr before any device call
+    a, b = _domain_arrays(distrs)
+    inside = (x > a[:, None]) & (x < b[:, None])
+    mid = 0.5 * (a + b)
+    safe = np.where(inside, x, mid[:, None])
+    u = np.stack(cdfs_on_rule(distrs, list(safe)))
+    rho = np.stack(densities(distrs, list(safe)))
+    ll = copula_log_density(u, corr, models.dof)[0]
+    with np.errstate(all="ignore"):
+        out = ll + np.sum(np.log(rho), axis=0)
+    return np.where(np.all(inside, axis=0), out, np.nan)
+
+
 def _rvs(dist, n, seed, stream, first, antithetic, device, qmc=False):
     """the B = 1 call of `samples`"""
     return samples([dist], n, seed, streams=[stream], first=first, antithetic=antithetic, device=device, qmc=qmc)[0]

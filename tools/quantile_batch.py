@@ -134,10 +134,20 @@ process, the two taking turns after a warm-up call each (five repetitions unless
   tbytes_per_s, fraction_of_hbm_peak   16 M n bytes, the one read of the inputs, over the time of the two kernels together, and that
                                rate over the 8 TB/s of the data sheet
   equal_torch                  every counter equals the composition's (exact while counts stay below 2^53)
+--loglik: copula_log_density(..., device=True) on device-resident uniforms [M, n] with a coarse array at
+equicorrelation 1/2, for M x n = 12 x 10^6 and 64 x 10^5 (--config M,n: that shape alone), once with the default grid of nu (G = 11)
+and once with the Gaussian model alone (G = 1), the routes of a shape taking turns after a warm-up call each:
+  entry_ms                     wall time of the call up to a device synchronise (the factors of the models are made on the host inside)
+  t_quantile_alone_ms, t_quantile_gvalues_per_s   student_t_quantile(nu = 3) on the M n device values of the fine side, and its rate
+  host_columns, host_ms_measured, host_ms_extrapolated_to_n, host_over_entry   the host composition of t_scores (SciPy's ndtri and
+                               stdtrit) with NumPy on the first host_columns columns of the same uniforms, its time scaled to n
+                               columns (the composition is linear in n; the whole of it would take minutes), and that over entry_ms
+  torch_ms, torch_over_entry   G = 1 only: torch.special.ndtri + torch.linalg.solve_triangular + the two sums, on the device
+  max_abs_difference_from_host / _from_torch   the largest difference of a log density from the composition's
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --tcopula | --tconditional | --scores |
                                                               --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --aggregates |
-                                                              --concordance] [--reps K]"""
+                                                              --concordance | --loglik] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -1078,6 +1088,83 @@ def concordance_shape(M, n, reps, G=3):
                 equal_torch=same)
 
 
+def loglik_shape(M, n, dofs, reps, n_host=20_000):
+    """copula_log_density on device-resident uniforms with a coarse array, for the models `dofs` at equicorrelation 1/2, against
+    the host composition of t_scores with NumPy (on the first n_host columns: SciPy's stdtrit takes about a microsecond per
+    value, so the time for n columns is extrapolated and marked so), at G = 1 (Gaussian) also against the torch composition
+    ndtri + solve_triangular, the two taking turns; and the t-quantile kernel alone at nu = 3 over M x n values"""
+    from scipy import special
+    dev = torch.device("cuda", torch.cuda.current_device())
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    lo, hi = 2.0 ** -53, 1.0 - 2.0 ** -53
+    fine = torch.rand((M, n), dtype=torch.float64, device=dev, generator=gen).clamp_(lo, hi)
+    coarse = (fine + 0.02 * torch.randn((M, n), dtype=torch.float64, device=dev, generator=gen)).clamp_(lo, hi)
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    dofs = np.asarray(dofs, dtype=np.float64)
+    G = dofs.size
+    models = sd._copula_models("loglik", corr, dofs, M)
+    L_d = torch.from_numpy(np.linalg.inv(models.A[0])).to(dev)
+    torch.cuda.synchronize()
+
+    def entry():
+        out = sd.copula_log_density(fine, corr, dofs, u_coarse=coarse, device=True)
+        torch.cuda.synchronize()
+        return out
+
+    def torch_gauss():
+        out = []
+        for u in (fine, coarse):
+            y = torch.special.ndtri(u)
+            v = torch.linalg.solve_triangular(L_d, y, upper=False)
+            out.append(-0.5 * ((v * v).sum(dim=0) - (y * y).sum(dim=0)) - float(models.logdet[0]))
+        torch.cuda.synchronize()
+        return out
+
+    def quantile_alone():
+        out = sd.student_t_quantile(fine, 3.0, device=True)
+        torch.cuda.synchronize()
+        return out
+
+    nh = min(n, n_host)
+    uf_h, uc_h = fine[:, :nh].cpu().numpy(), coarse[:, :nh].cpu().numpy()
+
+    def host():
+        out = np.empty((G, 2, nh))
+        for g, nu in enumerate(dofs):
+            for s, u in enumerate((uf_h, uc_h)):
+                z = special.ndtri(u)
+                y = z if nu == np.inf else sd.t_scores(z, nu)
+                v = models.A[g] @ y
+                Q = np.sum(v * v, axis=0)
+                if nu == np.inf:
+                    out[g, s] = -0.5 * (Q - np.sum(y * y, axis=0)) - models.logdet[g]
+                else:
+                    cg = special.gammaln(0.5 * (nu + M)) + (M - 1) * special.gammaln(0.5 * nu) - M * special.gammaln(0.5 * (nu + 1.0))
+                    out[g, s] = (cg - models.logdet[g] - 0.5 * (nu + M) * np.log1p(Q / nu)
+                                 + 0.5 * (nu + 1.0) * np.sum(np.log1p(y * y / nu), axis=0))
+        return out
+
+    fns = [entry, quantile_alone] + ([torch_gauss] if G == 1 and dofs[0] == np.inf else [])
+    walls = alternating(fns, reps)
+    t0 = time.perf_counter()
+    ref = host()
+    host_ms = (time.perf_counter() - t0) * 1e3
+    got = entry()
+    err = float(max(np.max(np.abs(got.fine[:, :nh].cpu().numpy() - ref[:, 0])), np.max(np.abs(got.coarse[:, :nh].cpu().numpy() - ref[:, 1]))))
+    res = dict(M=M, n=n, G=G, entry_ms=round(walls[0], 3), t_quantile_alone_ms=round(walls[1], 3),
+               t_quantile_gvalues_per_s=round(M * n / (walls[1] * 1e-3) / 1e9, 3), host_columns=nh, host_ms_measured=round(host_ms, 1),
+               host_ms_extrapolated_to_n=round(host_ms * n / nh, 1), host_over_entry=round(host_ms * n / nh / walls[0], 1),
+               max_abs_difference_from_host=err)
+    if len(fns) == 3:
+        tg = torch_gauss()
+        res["torch_ms"] = round(walls[2], 3)
+        res["torch_over_entry"] = round(walls[2] / walls[0], 2)
+        res["max_abs_difference_from_torch"] = float(max((got.fine[0] - tg[0]).abs().max().item(), (got.coarse[0] - tg[1]).abs().max().item()))
+    return res
+
+
 def single_entries(reps):
     distrs, ok = mixtures(1, 25, seed=5)
     d = distrs[0]
@@ -1130,6 +1217,9 @@ def main():
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
                                                                "fp64 Grams (DESIGN.md section 3.5.21)")
+    ap.add_argument("--loglik", action="store_true", help="copula_log_density with the default grid of nu and with the Gaussian model alone "
+                    "against the host composition of t_scores with NumPy and the torch composition, and the t-quantile kernel alone "
+                    "(DESIGN.md section 3.5.25)")
     ap.add_argument("--reps", type=int, default=None)
     a = ap.parse_args()
     if a.reps is None:
@@ -1138,6 +1228,14 @@ def main():
     out = dict(tool="quantile_batch", device=_lib.device_info()["name"])
     if a.single:
         out["single"] = single_entries(a.reps)
+    elif a.loglik:
+        shapes = [(12, 1_000_000), (64, 100_000)]
+        if a.config:
+            shapes = [tuple(int(v) for v in a.config.split(","))]
+        elif a.quick:
+            shapes = [(4, 10_000)]
+        out["loglik"] = [loglik_shape(M, n, dofs, a.reps, n_host=2_000 if a.quick else 20_000)
+                         for M, n in shapes for dofs in (sd.COPULA_DOF_GRID, (np.inf,))]
     elif a.concordance:
         shapes = [(12, 1_000_000), (64, 1_000_000), (256, 100_000)]
         if a.config:
