@@ -68,6 +68,9 @@ __device__ __forceinline__ double np_remainder(double a, double b) {   // numpy 
 __device__ __forceinline__ double np_maximum(double a, double b) { return (a >= b || a != a) ? a : b; }
 __device__ __forceinline__ double np_minimum(double a, double b) { return (a <= b || a != a) ? a : b; }
 __device__ __forceinline__ double np_sign(double a) { return a != a ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : 0.0)); }
+// expm1(-0) and log1p(-0) are -0 in C (Annex F) and NumPy; the device library returns +0
+__device__ __forceinline__ double np_expm1(double a) { return a == 0.0 ? a : expm1(a); }
+__device__ __forceinline__ double np_log1p(double a) { return a == 0.0 ? a : log1p(a); }
 
 // Register file in LDS: [reg][side][slot][thread]; a thread works on S samples (slots) per instruction so that the
 // decode of an instruction and the latency of its loads are shared by S samples.  The result of the latest value-
@@ -128,11 +131,11 @@ __device__ __forceinline__ void unary(int op, double (&r)[V], const double (&av)
             case MLMC_X_RECIP: r[s] = 1.0 / a; break;
             case MLMC_X_EXP: if (HEAVY) r[s] = exp(a); else r[s] = 0.0; break;
             case MLMC_X_EXP2: if (HEAVY) r[s] = exp2(a); else r[s] = 0.0; break;
-            case MLMC_X_EXPM1: if (HEAVY) r[s] = expm1(a); else r[s] = 0.0; break;
+            case MLMC_X_EXPM1: if (HEAVY) r[s] = np_expm1(a); else r[s] = 0.0; break;
             case MLMC_X_LOG: if (HEAVY) r[s] = log(a); else r[s] = 0.0; break;
             case MLMC_X_LOG2: if (HEAVY) r[s] = log2(a); else r[s] = 0.0; break;
             case MLMC_X_LOG10: if (HEAVY) r[s] = log10(a); else r[s] = 0.0; break;
-            case MLMC_X_LOG1P: if (HEAVY) r[s] = log1p(a); else r[s] = 0.0; break;
+            case MLMC_X_LOG1P: if (HEAVY) r[s] = np_log1p(a); else r[s] = 0.0; break;
             case MLMC_X_SIN: if (HEAVY) r[s] = sin(a); else r[s] = 0.0; break;
             case MLMC_X_COS: if (HEAVY) r[s] = cos(a); else r[s] = 0.0; break;
             case MLMC_X_TAN: if (HEAVY) r[s] = tan(a); else r[s] = 0.0; break;

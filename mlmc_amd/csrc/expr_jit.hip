@@ -102,11 +102,11 @@ const char *unary_expr(int op) {
         case MLMC_X_RECIP: return "1.0 / a";
         case MLMC_X_EXP: return "exp(a)";
         case MLMC_X_EXP2: return "exp2(a)";
-        case MLMC_X_EXPM1: return "expm1(a)";
+        case MLMC_X_EXPM1: return "np_expm1(a)";
         case MLMC_X_LOG: return "log(a)";
         case MLMC_X_LOG2: return "log2(a)";
         case MLMC_X_LOG10: return "log10(a)";
-        case MLMC_X_LOG1P: return "log1p(a)";
+        case MLMC_X_LOG1P: return "np_log1p(a)";
         case MLMC_X_SIN: return "sin(a)";
         case MLMC_X_COS: return "cos(a)";
         case MLMC_X_TAN: return "tan(a)";
@@ -165,6 +165,8 @@ __device__ __forceinline__ double np_remainder(double a, double b) {
 __device__ __forceinline__ double np_maximum(double a, double b) { return (a >= b || a != a) ? a : b; }
 __device__ __forceinline__ double np_minimum(double a, double b) { return (a <= b || a != a) ? a : b; }
 __device__ __forceinline__ double np_sign(double a) { return a != a ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : 0.0)); }
+__device__ __forceinline__ double np_expm1(double a) { return a == 0.0 ? a : expm1(a); }   // -0 stays -0, as in expr.hip
+__device__ __forceinline__ double np_log1p(double a) { return a == 0.0 ? a : log1p(a); }
 
 // PACKED: the stored rows are interleaved (fine, coarse) pairs, one 128-bit load per sample.  Loads are branch-free (index
 // clamped to the last sample, value selected afterwards), so the body is one basic block and the scheduler is free to issue
