@@ -48,7 +48,8 @@ extern "C" {
                               *    mlmc_student_t_cdf, mlmc_chi2_mixing_scale, mlmc_density_sample_joint_t_batch,
                               *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch,
                               *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale,
-                              *    mlmc_student_t_quantile, mlmc_copula_log_density */
+                              *    mlmc_student_t_quantile, mlmc_copula_log_density,
+                              *    mlmc_copula_box_prob_tc_batch, mlmc_copula_box_draws_tc_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -758,15 +759,47 @@ int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const dou
  *   the tree's value and not one width.  f_out and mean of the draws entry are bit for bit those of the probability entry for the
  *   same streams[0 .. M-2] and mix_stream.  No value depends on B, R, the position of box or seed, first / n, the launch split,
  *   the presence of f_out / u_out / s_out or host / device outputs.
- * Conditional PROBABILITIES and event scenarios (a shift) under a t copula are not provided: their law has nu + k degrees of
- * freedom, which leaves the [1, 64] of these entries.  Conditional draws are mlmc_density_sample_conditional_t_batch, whose mixing
- * variable alone takes up to 192.  Every loop has a fixed upper trip count; no atomics; one host wait. */
+ * Conditional PROBABILITIES and event scenarios (a shift) under a t copula are the _tc_ entries below: their law has nu + k degrees
+ * of freedom, which leaves the [1, 64] of these entries.  Conditional draws are mlmc_density_sample_conditional_t_batch, whose
+ * mixing variable takes up to 192 too.  Every loop has a fixed upper trip count; no atomics; one host wait. */
 int mlmc_copula_box_prob_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
                                  int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind);
 int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
                                   const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
                                   int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out, int mem_kind);
+/* ---- the two t entries for a CONDITIONAL law of the t copula -- added within 8 ---------------------------------------------
+ * Given the t scores y_O of p components, the t scores of the others are multivariate t with nu_c = nu + p degrees of freedom,
+ * location mu and scale matrix r^2 L L^T (the caller's host algebra).  With s_c = sqrt(nu_c / chi2_nu_c) ONE mixing scale per point:
+ *     P(lo < Y < hi | y_O) = E_sc[ P((lo - mu) / (r s_c) < L z < (hi - mu) / (r s_c)) ],   Y = mu + r s_c L z  inside the box.
+ * The arguments, the argument errors, the stream rules, the staging (192 MiB, s_out), the tree and the split are those of the
+ * _t_batch entries, with these additions:
+ *   dof = nu in [1, 64]: the degrees of freedom of the COPULA, with whose constants the draws' t scores are mapped to u: the
+ *     marginal law of a component is t with nu, not nu_c.  dof_mix = nu_c in [1, 192]: those of the mixing variable; s is bit for
+ *     bit mlmc_chi2_conditional_scale(dof_mix, p0).  NaN is outside both intervals: an error of the call.
+ *   shift [B][M] (NULL: none), finite; scale [B] (NULL: ones), finite and positive: errors of the call otherwise, before any launch.
+ * For box b, seed r and point j (every operation ONE fp64 operation rounded to nearest, no FMA):
+ *   1. c = scale[b] * s_j, one rounded product, once per lane (scale NULL: c = s_j).
+ *   2. For component i:  lt = (lo[b][i] - shift[b][i]) / c,  ht = (hi[b][i] - shift[b][i]) / c: one rounded subtraction and one
+ *      IEEE division each (shift NULL: no subtraction; an infinite limit stays infinite), then step i of the Gaussian chain on
+ *      (lt, ht) without a shift; the test for an empty component is lt < ht.  So f[r][b][j] is bit for bit the Gaussian entry's
+ *      integrand at point j for the box (lt, ht) and the same chain streams.
+ *   3. Draws: with zn the chain's normal clamped to [lt, ht],
+ *          y_i = min(max(shift[b][i] + zn * c, lo[b][i]), hi[b][i])        (one rounded product, one rounded sum), to z_out, and
+ *          u_i = min(max(T, 2^-53), 1 - 2^-53),  T bit for bit mlmc_student_t_cdf(dof, y_i), to u_out by the pass of the t entries.
+ *      The sign of a zero score: with shift NULL no sum is taken and y_i keeps the sign of zn * c (before the clamp) as in the
+ *      _t_batch entries; with a shift the sum follows IEEE (x + (-x) = +0, -0 + -0 = -0).  The clamp is fmin(fmax(y, lo), hi).
+ * With shift NULL, scale NULL and dof_mix == dof every output is bit for bit that of the _t_batch entries.  mean is the tree for
+ * every M (M = 1 uses its mixing point).  No value depends on B, R, the position of box or seed, first / n, the launch split, the
+ * presence of f_out / u_out / s_out or host / device outputs.  Fixed trip counts; no atomics; one host wait. */
+int mlmc_copula_box_prob_tc_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, double dof_mix,
+                                  const double *shift, const double *scale, int32_t R, const uint64_t *seeds, const uint32_t *streams,
+                                  uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
+                                  double *s_out, int mem_kind);
+int mlmc_copula_box_draws_tc_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, double dof_mix,
+                                   const double *shift, const double *scale, int32_t R, const uint64_t *seeds, const uint32_t *streams,
+                                   uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
+                                   double *z_out, double *u_out, double *s_out, int mem_kind);
 
 /* ---- aggregates of joint scenarios (scenario.hip) -- added within 8 ----------------------------------------------------
  * Functions of the M components of one scenario, once per scenario column.  x [S][M][ld]: S >= 1 sets of M >= 1 component rows,

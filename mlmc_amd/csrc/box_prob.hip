@@ -18,6 +18,10 @@
 //                of the draws is a pass of k_tcop_map over the rows of scores afterwards.  Neither chi2_mixing_scale nor
 //                student_t_cdf is called from the chain: their series loops and constants stay out of the loop over i
 //                (DESIGN.md 3.5.23).
+//                The TCOND instances (mlmc_copula_box_prob_tc_batch / _draws_tc_batch: a CONDITIONAL law of the t copula, location
+//                shift[b], scale matrix scale[b]^2 L L^T, the mixing variable with dof_mix degrees of freedom) are TCOP with one more
+//                flag: the lane multiplies its mixing scale by the box's scale once, takes the shift off every limit before the
+//                division, and adds it back to the stored t score.
 //   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
 // The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
 // k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
@@ -65,7 +69,10 @@ __device__ __attribute__((noinline)) double box_normcdfinv(double p) { return no
 // TCOP (the t entries): `mix` holds the mixing scales of the launch, sc = mix[seed][64 blockIdx.x + lane] (k_box_mixing; a block
 // of gridDim.x * 64 doubles per seed of the call).  Every limit is divided by sc, the chain runs on the quotients without a shift, the
 // stored score is the t score min(max(z sc, l), h), and a row of u_out receives the same score: the CDF pass maps it in place.
-template <bool SOBOL, bool DRAWS, bool TCOP = false>
+// TCOND (the tc entries, with TCOP): sc = scl[b] * sc once (scl NULL: ones); with a shift every limit is (lo - shift) / sc, one
+// rounded subtraction before the division, the chain itself runs without a shift, and the stored score is
+// min(max(shift + z sc, lo), hi).  With shift NULL neither the subtraction nor the sum is taken: the bits of TCOP.
+template <bool SOBOL, bool DRAWS, bool TCOP = false, bool TCOND = false>
 __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__restrict__ L, const double *__restrict__ lo,
                                                         const double *__restrict__ hi, const double *__restrict__ shift, int B, int b0,
                                                         const uint64_t *__restrict__ seeds, int r0, const uint32_t *__restrict__ streams,
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
                                                         int64_t blk0, int64_t call_blk0, int64_t call_blocks,
                                                         double *__restrict__ partials, double *__restrict__ f_out, int64_t ldf,
                                                         int64_t c_off, double *__restrict__ z_out, double *__restrict__ u_out,
-                                                        const double *__restrict__ mix) {
+                                                        const double *__restrict__ mix, const double *__restrict__ scl) {
     extern __shared__ double ys[];                     // y[k][lane]
     const int lane = threadIdx.x;
     const int b = b0 + (int)blockIdx.y, r = r0 + (int)blockIdx.z;
@@ -86,12 +93,17 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
     const uint64_t *tab = SOBOL ? table + (int64_t)r * table_rows * SOBOL_ROW : nullptr;
     double sc = 1.0;
     if constexpr (TCOP) sc = mix[((int64_t)r * gridDim.x + blockIdx.x) * BOX_LANES + lane];
+    if constexpr (TCOND)
+        if (scl) sc = __dmul_rn(scl[b], sc);
     double f = 1.0;
     for (int i = 0; i < M; ++i) {
         const double *Li = L + (int64_t)i * M;
-        double s = sh_b ? sh_b[i] : 0.0;
+        double s = !TCOND && sh_b ? sh_b[i] : 0.0;
         for (int k = 0; k < i; ++k) s = __dadd_rn(s, __dmul_rn(Li[k], ys[k * BOX_LANES + lane]));
-        const double lii = Li[i], l = TCOP ? lo_b[i] / sc : lo_b[i], h = TCOP ? hi_b[i] / sc : hi_b[i];
+        double lt = lo_b[i], ht = hi_b[i];
+        if constexpr (TCOND)
+            if (sh_b) lt = __dsub_rn(lt, sh_b[i]), ht = __dsub_rn(ht, sh_b[i]);
+        const double lii = Li[i], l = TCOP ? lt / sc : lt, h = TCOP ? ht / sc : ht;
         const double ap = (l - s) / lii, bp = (h - s) / lii;
         const bool refl = ap > 0.0;
         const double d = box_normcdf(refl ? -bp : ap), e = box_normcdf(refl ? -ap : bp);
@@ -110,7 +122,10 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
                 double z = fmin(fmax(__dadd_rn(s, __dmul_rn(lii, y)), l), h);
                 const int64_t at = (((int64_t)r * B + b) * M + i) * ldf + (j - first - c_off);
                 if constexpr (TCOP) {
-                    z = fmin(fmax(__dmul_rn(z, sc), lo_b[i]), hi_b[i]);
+                    z = __dmul_rn(z, sc);
+                    if constexpr (TCOND)
+                        if (sh_b) z = __dadd_rn(sh_b[i], z);
+                    z = fmin(fmax(z, lo_b[i]), hi_b[i]);
                     if (active && u_out) u_out[at] = z;
                 }
                 if (active) z_out[at] = z;
@@ -149,11 +164,14 @@ __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__r
 static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                     const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
                     int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr, const double *dof = nullptr,
-                    uint32_t mix_stream = 0, double *s_out = nullptr) {
+                    uint32_t mix_stream = 0, double *s_out = nullptr, const double *dof_mix = nullptr, const double *scale = nullptr) {
     const std::string e(fn);
     const bool tcop = dof != nullptr;                  // the t entries: *dof degrees of freedom, the mixing stream, s_out [R][n] or NULL
+    // the tc entries: a conditional law, *dof_mix degrees of freedom of the mixing variable, shift [B][M] or NULL, scale [B] or NULL
+    const bool tcond = tcop && dof_mix != nullptr;
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (tcop && tcop_check_dof(fn, *dof)) return 1;
+    if (tcond && tcop_check_dof(fn, *dof_mix, TCOP_MAX_DOF_MIX, "dof_mix")) return 1;
     if (M < 1) return fail(e + ": M < 1");
     if (M > MLMC_BOX_PROB_MAX_M) return fail(e + ": M = " + std::to_string(M) + " is above the cap " + std::to_string(MLMC_BOX_PROB_MAX_M));
     if (B < 1) return fail(e + ": B < 1");
@@ -182,6 +200,10 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
             if (shift && !std::isfinite(shift[at]))
                 return fail(e + ": box " + std::to_string(b) + ", component " + std::to_string(i) + ": the shift is not finite");
         }
+    if (tcond && scale)
+        for (int b = 0; b < B; ++b)
+            if (!std::isfinite(scale[b]) || !(scale[b] > 0.0))
+                return fail(e + ": box " + std::to_string(b) + ": the scale must be finite and positive");
     // the coordinates: streams (Philox), or the rows of the call's distinct dimensions, one table per seed (MLMC_SAMPLE_SOBOL)
     const int nc = draws ? M : M - 1;                   // the draws take one more coordinate for the last component
     // the t entries: the mixing variable is one more coordinate, behind the chain's, in the same table
@@ -236,15 +258,17 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     }
     const int64_t ldf = stage ? lb * BOX_LANES : n;
 
-    // what goes up: L | lo | hi | shift | seeds | tables | coordinates (uint32)
+    // what goes up: L | lo | hi | shift | scale | seeds | tables | coordinates (uint32)
     const size_t nL = (size_t)M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nd + 1) / 2;
-    const size_t n_in = nL + 2 * nbx + nsh + (size_t)R + ntab + nco;
+    const size_t nsc = tcond && scale ? (size_t)B : 0;
+    const size_t n_in = nL + 2 * nbx + nsh + nsc + (size_t)R + ntab + nco;
     std::vector<double> packed(n_in);
     double *q = packed.data();
     std::memcpy(q, L, sizeof(double) * nL), q += nL;
     std::memcpy(q, lo, sizeof(double) * nbx), q += nbx;
     std::memcpy(q, hi, sizeof(double) * nbx), q += nbx;
     if (nsh) std::memcpy(q, shift, sizeof(double) * nsh), q += nsh;
+    if (nsc) std::memcpy(q, scale, sizeof(double) * nsc), q += nsc;
     std::memcpy(q, seeds, sizeof(uint64_t) * (size_t)R), q += R;
     if (ntab) std::memcpy(q, tables.data(), sizeof(uint64_t) * ntab), q += ntab;
     if (nd) std::memcpy(q, coord.data(), sizeof(uint32_t) * (size_t)nd);
@@ -263,15 +287,20 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     hipStream_t st = rt().stream;
     MLMC_HIP_CHECK(hipMemcpyAsync(d_in, packed.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, st));
     const double *d_L = d_in, *d_lo = d_L + nL, *d_hi = d_lo + nbx, *d_shift = nsh ? d_hi + nbx : nullptr;
-    const uint64_t *d_seeds = (const uint64_t *)(d_hi + nbx + nsh), *d_tab = d_seeds + R;
+    const double *d_scale = nsc ? d_hi + nbx + nsh : nullptr;
+    const uint64_t *d_seeds = (const uint64_t *)(d_hi + nbx + nsh + nsc), *d_tab = d_seeds + R;
     const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
 
     const size_t lds = sizeof(double) * BOX_LANES * (size_t)(M - 1);
-    const auto kernel = tcop ? (draws ? (sobol ? k_box_prob<true, true, true> : k_box_prob<false, true, true>)
+    const auto kernel = tcond ? (draws ? (sobol ? k_box_prob<true, true, true, true> : k_box_prob<false, true, true, true>)
+                                       : (sobol ? k_box_prob<true, false, true, true> : k_box_prob<false, false, true, true>))
+                      : tcop ? (draws ? (sobol ? k_box_prob<true, true, true> : k_box_prob<false, true, true>)
                                       : (sobol ? k_box_prob<true, false, true> : k_box_prob<false, false, true>))
                              : (draws ? (sobol ? k_box_prob<true, true> : k_box_prob<false, true>)
                                       : (sobol ? k_box_prob<true, false> : k_box_prob<false, false>));
+    // the CDF pass maps with the constants of dof (the marginal law of a component), the mixing kernel takes those of dof_mix
     const TCopConst tconst = tcop ? tcop_constants(*dof) : TCopConst{};
+    const TCopConst tmix = tcond ? tcop_constants(*dof_mix) : tconst;
     for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
         const int64_t kb = std::min(lb, call_blocks - k0);
         // the first point of the launch within the call: column 0 of the staged integrand
@@ -280,7 +309,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
         if (tcop) {
             // the mixing scales of the launch's blocks, once per (seed, point): d_s [R][64 kb]
             const int64_t j0 = (call_blk0 + k0) << 6;
-            cop_launch_box_mixing(st, tconst, R, d_seeds, coord[nc], sobol ? d_tab : nullptr, table_rows, j0, kb * BOX_LANES, first, n, d_s);
+            cop_launch_box_mixing(st, tmix, R, d_seeds, coord[nc], sobol ? d_tab : nullptr, table_rows, j0, kb * BOX_LANES, first, n, d_s);
             if (s_out)
                 MLMC_HIP_CHECK(hipMemcpy2DAsync(s_out + c_lo, sizeof(double) * (size_t)n, d_s + (first + c_lo - j0),
                                                 sizeof(double) * (size_t)(kb * BOX_LANES), sizeof(double) * (size_t)(c_hi - c_lo), (size_t)R,
@@ -291,7 +320,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                 const dim3 grid((unsigned)kb, (unsigned)std::min(B - b0, 65535), (unsigned)std::min(R - r0, 65535));
                 hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, d_shift, (int)B, b0, d_seeds, r0, d_coord,
                                    d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part, d_f, ldf,
-                                   stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)d_s);
+                                   stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)d_s, d_scale);
             }
         // the CDF pass of the t draws: the rows of u hold the t scores of the launch's columns and are mapped in place
         if (tcop && u_out) cop_launch_t_map(st, tconst, (int)urows, c_hi - c_lo, d_u + (stage ? 0 : c_lo), ldf);
@@ -350,6 +379,24 @@ int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const d
     MLMC_API_GUARD;
     return box_prob("mlmc_copula_box_draws_t_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
                     z_out, u_out, &dof, mix_stream, s_out);
+}
+
+int mlmc_copula_box_prob_tc_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, double dof_mix,
+                                  const double *shift, const double *scale, int32_t R, const uint64_t *seeds, const uint32_t *streams,
+                                  uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
+                                  double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_tc_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, false,
+                    nullptr, nullptr, &dof, mix_stream, s_out, &dof_mix, scale);
+}
+
+int mlmc_copula_box_draws_tc_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, double dof_mix,
+                                   const double *shift, const double *scale, int32_t R, const uint64_t *seeds, const uint32_t *streams,
+                                   uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
+                                   double *z_out, double *u_out, double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_draws_tc_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
+                    z_out, u_out, &dof, mix_stream, s_out, &dof_mix, scale);
 }
 
 }  // extern "C"

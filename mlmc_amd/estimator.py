@@ -169,6 +169,19 @@ def _check_tail(what, tail):
         raise ValueError("{}: tail must be 'upper' or 'lower', got {!r}".format(what, tail))
 
 
+def _refuse_dof_with_given(what, dof, given):
+    """estimate_aggregates conditions under the Gaussian copula only"""
+    if dof is not None and given is not None:
+        raise ValueError(what + ": dof together with given: this method conditions under the Gaussian copula only; call "
+                         "estimate_conditional_aggregates")
+
+
+def _conditional_dof_with_given(what, dof, given):
+    """the conditional family: dof + the number of given components must stay within 192"""
+    from .tool import simple_distribution
+    simple_distribution._check_conditional_dof(what, dof, len(given) if hasattr(given, "items") else 0)
+
+
 class Estimate:
     """Wrapper methods for moment estimation, sample allocation and PDF reconstruction (reference: estimator.py:11-341)."""
 
@@ -1132,21 +1145,63 @@ class Estimate:
             variable: one more coordinate per point, the same relative accuracy in the tail.  Where `estimate_tail_dependence`
             shows joint tails (a large positive z), this is the number to use: the Gaussian one is too small.  `corr` is then the t
             copula's correlation matrix, which corr="quadrant" estimates consistently; None and "scores" only approximately.  Not
-            together with `given`
+            together with `given`: that is `estimate_conditional_probability`
         :return: (JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds), success [M])"""
         from .tool import simple_distribution
         what = "estimate_joint_probability"
         dof = simple_distribution._box_dof(what, dof, None, given)
+        return self._joint_probability(what, simple_distribution.joint_probabilities, lower, upper, n, seeds, corr, given, tol, reg_param,
+                                       orth_moments_tol, moments_fns, densities, first, qmc, dof)
+
+    def estimate_conditional_probability(self, lower, upper, given, n=2 ** 14, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
+                                         orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+        """Probability that the components that are NOT in `given` lie in a box at once, CONDITIONAL on measured or fixed values of
+        the others (tool.simple_distribution.conditional_probabilities): "how likely is it that the other components exceed their
+        limits at once, given this value at the well?".  With dof None this is `estimate_joint_probability(given=...)`, bit for
+        bit, through the same body.  With dof, a float in [1, 64], the copula is the Student-t copula of `sample_joint(dof=...)`,
+        under which an extreme given value WIDENS the law of the others (the Gaussian copula cannot): given p values the t scores
+        of the others are multivariate t with dof + p degrees of freedom (at most 192), as in `sample_conditional(dof=...)`.
+        :param lower, upper: broadcast to [B, q] over the components that are not given, ascending, in their own units
+        :param given: as in sample_conditional (required); arrays [B] pair with the boxes
+        :param corr: as in sample_joint; with dof corr="quadrant" is the consistent correlation, as for sample_conditional(dof=...)
+        :param n, seeds, densities, first, qmc: as in estimate_joint_probability
+        :return: (JointProbability, success [M])"""
+        from .tool import simple_distribution
+        what = "estimate_conditional_probability"
+        if given is None:
+            raise ValueError(what + ": given is required (without given values: estimate_joint_probability)")
+        nu = simple_distribution._check_dof(what, dof)
+        simple_distribution._check_conditional_dof(what, nu, len(given) if hasattr(given, "items") else 0)
+        return self._joint_probability(what, simple_distribution.conditional_probabilities, lower, upper, n, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns,
+                                       densities, first, qmc, nu)
+
+    def _joint_probability(self, what, entry, lower, upper, n, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns,
+                           densities, first, qmc, dof):
+        """the one body of estimate_joint_probability and estimate_conditional_probability; dof checked by the caller"""
+        from .tool import simple_distribution
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
             raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
         corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
-        result = simple_distribution.joint_probabilities([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
-                                                         given=given, first=first, qmc=qmc, dof=dof)
+        result = entry([d[0] for d in densities], lower, upper, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first,
+                       qmc=qmc, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
+
+    def estimate_conditional_exceedance(self, thresholds, given, n=2 ** 14, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
+                                        orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+        """P(X_m > t_m for all constrained m that are not given | the given values): `estimate_conditional_probability` with
+        lower = thresholds and upper = +inf.
+        :param thresholds: broadcast to [B, q] over the components that are not given; -inf leaves a component unconstrained
+        :return: as estimate_conditional_probability"""
+        t = np.asarray(thresholds, dtype=np.float64)
+        if np.any(np.isnan(t)):
+            raise ValueError("estimate_conditional_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
+        return self.estimate_conditional_probability(t, np.inf, given, n=n, seeds=seeds, corr=corr, tol=tol, reg_param=reg_param,
+                                                     orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
+                                                     first=first, qmc=qmc, dof=dof)
 
     def estimate_joint_exceedance(self, thresholds, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
@@ -1261,9 +1316,11 @@ class Estimate:
         copula.  Feed the result to `sample_joint(dof=...)`, `estimate_aggregates(dof=...)`, `estimate_tail_dependence(dof=...)`
         and to the joint numbers themselves: `estimate_joint_probability(dof=...)`, `estimate_joint_exceedance(dof=...)`,
         `sample_given_event(dof=...)`, `estimate_event_means(dof=...)` and the two bootstrap bands (Genz and Bretz's mixing
-        variable), and to the what-if fan: `sample_conditional(dof=...)`, `estimate_conditional_quantiles(dof=...)`.  Not provided
-        under a t copula: conditional probabilities, event scenarios and aggregates (`given` on the entries above), and a
-        bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid (`estimate_copula_likelihood` fits
+        variable), and to the what-if fan: `sample_conditional(dof=...)`, `estimate_conditional_quantiles(dof=...)`,
+        `estimate_conditional_probability(dof=...)`, `estimate_conditional_exceedance(dof=...)`, `sample_conditional_event(dof=...)`,
+        `estimate_conditional_event_means(dof=...)` and `estimate_conditional_aggregates(dof=...)` (`given` on the joint entries
+        themselves conditions under the Gaussian copula only).  Not provided under a t copula: bootstrap bands of conditional
+        probabilities, and a bootstrap of nu -- the fit has no error bar beyond the objective's shape over the grid (`estimate_copula_likelihood` fits
         nu from every sample and gives each candidate a paired error bar).
         :param probs, tail, corr, densities: as in estimate_tail_dependence; corr="quadrant" is the estimate that is consistent
             under a t copula
@@ -1435,19 +1492,43 @@ class Estimate:
         :param device: the arrays of the result are float64 torch device tensors
         :param dof: None or np.inf: the Gaussian copula, bit for bit; a float in [1, 64]: the Student-t copula of
             `sample_joint(dof=...)`, as in estimate_joint_probability (corr="quadrant" is the consistent correlation).  Not together
-            with `given`
+            with `given`: that is `sample_conditional_event`
         :return: (EventScenarios(draws [R, B, M, n], weights [R, B, n], prob, ess [R, B], ok [M], uniforms), success [M])"""
         from .tool import simple_distribution
         what = "sample_given_event"
         dof = simple_distribution._box_dof(what, dof, None, given)
+        return self._given_event(what, simple_distribution.event_samples, n, lower, upper, seeds, corr, given, tol, reg_param,
+                                 orth_moments_tol, moments_fns, densities, first, device, qmc, dof)
+
+    def sample_conditional_event(self, n, lower, upper, given, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
+                                 orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True, dof=None):
+        """Joint scenarios of all components GIVEN a box event AND measured or fixed values of some components
+        (tool.simple_distribution.conditional_event_samples).  With dof None this is `sample_given_event(given=...)`, bit for bit,
+        through the same body; with dof the copula is the Student-t copula, as in estimate_conditional_probability.
+        :param given: as in sample_conditional (required); a given component must not be constrained
+        :param n, lower, upper, seeds, corr, densities, first, device, qmc: as in sample_given_event
+        :return: (EventScenarios, success [M]); rows of given components hold the given values"""
+        from .tool import simple_distribution
+        what = "sample_conditional_event"
+        if given is None:
+            raise ValueError(what + ": given is required (without given values: sample_given_event)")
+        nu = simple_distribution._check_dof(what, dof)
+        simple_distribution._check_conditional_dof(what, nu, len(given) if hasattr(given, "items") else 0)
+        return self._given_event(what, simple_distribution.conditional_event_samples, n, lower, upper, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns,
+                                 densities, first, device, qmc, nu)
+
+    def _given_event(self, what, entry, n, lower, upper, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns, densities,
+                     first, device, qmc, dof):
+        """the one body of sample_given_event and sample_conditional_event; dof checked by the caller"""
+        from .tool import simple_distribution
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
             raise ValueError(what + ": a limit is NaN (use -inf / +inf for a side without a limit)")
         corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
-        result = simple_distribution.event_samples([d[0] for d in densities], lower, upper, n, [int(s) for s in seeds], corr=corr,
-                                                   given=given, first=first, qmc=qmc, device=device, dof=dof)
+        result = entry([d[0] for d in densities], lower, upper, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first,
+                       qmc=qmc, device=device, dof=dof)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
 
@@ -1464,6 +1545,18 @@ class Estimate:
         scen, success = self.sample_given_event(n, lower, upper, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                 orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
                                                 first=first, qmc=qmc, dof=dof)
+        mean, stderr = scen.means()
+        return EventMeans(mean, stderr, scen.prob, scen.ess), success
+
+    def estimate_conditional_event_means(self, lower, upper, given, n=2 ** 14, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
+                                         orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+        """E[X | lower < X < upper, the given values]: the weighted means of the scenarios of `sample_conditional_event`; with dof
+        None `estimate_event_means(given=...)` bit for bit.
+        :param lower, upper, given, n, seeds, corr, densities, first, qmc, dof: as in sample_conditional_event
+        :return: (EventMeans, success [M])"""
+        scen, success = self.sample_conditional_event(n, lower, upper, given, seeds=seeds, corr=corr, tol=tol, reg_param=reg_param,
+                                                      orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
+                                                      first=first, qmc=qmc, dof=dof)
         mean, stderr = scen.means()
         return EventMeans(mean, stderr, scen.prob, scen.ess), success
 
@@ -1496,18 +1589,40 @@ class Estimate:
             statistic carries their weights; `prob` is the JointProbability of the event.  qmc then chooses Sobol' or Philox points
         :param block: scenario columns per device block
         :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula of `sample_joint(dof=...)`, with
-            `event` that of `sample_given_event(dof=...)`.  Not together with `given`: conditional draws exist under the Gaussian
-            copula only
+            `event` that of `sample_given_event(dof=...)`.  Not together with `given`: that is `estimate_conditional_aggregates`
         :return: (AggregateSummary, success [M]).  Statistics are [Q, ...], with a leading axis B for arrays in `given` and for the B
             boxes of `event` (always, also for one box); count_prob [.., M + 1], worst_prob / best_prob [.., M] are None without their row"""
         from .tool import simple_distribution as sd
-        what = "estimate_aggregates"
+        return self._aggregates("estimate_aggregates", (_refuse_dof_with_given, sd.joint_aggregates, sd.event_samples), weights, probs, n, seeds, corr, given, lower, upper, members, extremes, event, tail, qmc,
+                                block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof)
+
+    def estimate_conditional_aggregates(self, given, weights=None, probs=(0.05, 0.5, 0.95), n=2 ** 16, seeds=tuple(range(8)), corr=None,
+                                        lower=None, upper=None, members=None, extremes=("max", "min"), event=None, tail="upper",
+                                        qmc=True, block=2 ** 20, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None,
+                                        densities=None, first=0, antithetic=False, dof=None):
+        """`estimate_aggregates(given=...)`, the aggregates member of the conditional family, through the same body: with dof None
+        bit for bit that call; with dof the scenarios are those of `sample_conditional(dof=...)`
+        (tool.simple_distribution.conditional_aggregates) or, with `event`, of `sample_conditional_event(dof=...)`.
+        :param given: as in sample_conditional (required); the other arguments as in estimate_aggregates
+        :return: (AggregateSummary, success [M])"""
+        from .tool import simple_distribution as sd
+        what = "estimate_conditional_aggregates"
+        if given is None:
+            raise ValueError(what + ": given is required (without given values: estimate_aggregates)")
+        return self._aggregates(what, (_conditional_dof_with_given, sd.conditional_aggregates, sd.conditional_event_samples), weights, probs, n, seeds, corr, given, lower, upper, members, extremes, event, tail, qmc,
+                                block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof)
+
+    def _aggregates(self, what, entries, weights, probs, n, seeds, corr, given, lower, upper, members, extremes, event, tail, qmc,
+                    block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof):
+        """the one body of estimate_aggregates and estimate_conditional_aggregates; entries: (the check of dof against given, the
+        aggregates entry, the event entry) of tool.simple_distribution"""
+        from .tool import simple_distribution as sd
+        check_given, aggregates, event_samples = entries
         M = int(self._quantity.size())
         n, seeds, first = sd._box_call_args(what, n, seeds, first)
         sd._sample_flags(what, antithetic, qmc)
         dof = sd._check_dof(what, dof)
-        if dof is not None and given is not None:
-            raise ValueError(what + ": dof together with given: conditional draws exist under the Gaussian copula only")
+        check_given(what, dof, given)
         _check_tail(what, tail)
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
         if probs.size == 0 or not np.all((probs >= 0) & (probs <= 1)):
@@ -1537,13 +1652,13 @@ class Estimate:
         Q, K, R = len(names), probs.size, seeds.size
         prob = None
         if event is None:
-            per_seed = [sd.joint_aggregates(distrs, n, int(s), corr=corr, given=given, first=first, antithetic=antithetic, qmc=qmc,
-                                            block=block, device=True, dof=dof, **agg).rows for s in seeds]
+            per_seed = [aggregates(distrs, n, int(s), corr=corr, given=given, first=first, antithetic=antithetic, qmc=qmc, block=block,
+                                   device=True, dof=dof, **agg).rows for s in seeds]
             lead = tuple(per_seed[0].shape[:-2])
             f_of = None
         else:
-            scen = sd.event_samples(distrs, lower_e, upper_e, n, [int(s) for s in seeds], corr=corr, given=given, first=first, qmc=qmc,
-                                    device=True, dof=dof)
+            scen = event_samples(distrs, lower_e, upper_e, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first, qmc=qmc,
+                                 device=True, dof=dof)
             ev = sd.event_aggregates(scen, **agg)
             B = int(ev.rows.shape[1])
             per_seed = [ev.rows[r] for r in range(R)]

@@ -617,7 +617,9 @@ def joint_samples(distrs, n, seed, corr=None, factor=None, streams=None, first=0
         `student_t_cdf`.  F is a factor of the copula's correlation matrix: for a t copula the correlation of the normal scores is
         NOT that matrix; `Estimate.estimate_quadrant_correlation` estimates it consistently.  Box probabilities and
         event scenarios under the same copula: `joint_probabilities(dof=...)`, `event_samples(dof=...)`; conditional draws,
-        quantiles and CDFs: `conditional_samples(dof=...)`, `conditional_quantiles(dof=...)`, `conditional_cdfs(dof=...)`
+        quantiles and CDFs: `conditional_samples(dof=...)`, `conditional_quantiles(dof=...)`, `conditional_cdfs(dof=...)`;
+        conditional probabilities, event scenarios and aggregates: `conditional_probabilities(dof=...)`,
+        `conditional_event_samples(dof=...)`, `conditional_aggregates(dof=...)`
     :param mix_stream: the uint32 stream (qmc: the dimension, below 1024) of the mixing uniform; default K when `streams` is
         defaulted; with explicit `streams` it must be given and differ from all of them
     :param return_uniforms, return_normals, return_mixing: also return u [M, n], z [K, n] and / or s [n] (dof only), in this order
@@ -1083,7 +1085,8 @@ def _box_t_streams(what, dof, shift, streams, mix_stream, count, qmc):
     """(chain streams uint32 [count], mixing stream) of a box call under the t copula, checked: by default the mixing variable takes
     stream 0, the lowest Sobol' dimension (Genz and Bretz's order), and chain coordinate i stream i + 1"""
     if shift is not None:
-        raise ValueError(what + ": dof together with shift: conditional laws exist under the Gaussian copula only")
+        raise ValueError(what + ": dof together with shift: this entry has no conditional law under the t copula (its mixing variable "
+                         "has dof + p degrees of freedom); call conditional_box_probabilities / conditional_box_draws")
     if streams is None:
         streams = np.arange(1, count + 1, dtype=np.uint32)
         if mix_stream is None:
@@ -1128,7 +1131,7 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
         multivariate STUDENT-T vector with that many degrees of freedom (mlmc_copula_box_prob_t_batch), s = chi2_mixing_scale(p0,
         dof) one mixing scale per point: P(lower < Y < upper) = E_s[P(lower / s < F z < upper / s)] (Genz and Bretz), one more
         coordinate per point, every limit divided by s, the rest the Gaussian chain.  The limits are T SCORES (`t_scores`).  Not
-        together with `shift`
+        together with `shift`: a conditional law of the t copula is `conditional_box_probabilities`
     :param mix_stream: the stream (qmc: the dimension, below 1024) of the mixing uniform.  Default 0, and chain coordinate i then
         takes stream i + 1; with explicit `streams` it must be given and differ from all of them
     :param return_mixing: also return the mixing scales s [R, n] (dof only), after the integrand
@@ -1199,8 +1202,22 @@ def _box_dof(what, dof, mix_stream, given):
     """dof of a box entry in the components' own units, checked (None: the Gaussian copula)"""
     dof = _check_dof(what, dof)
     if dof is not None and given is not None:
-        raise ValueError(what + ": dof together with given: conditional laws exist under the Gaussian copula only (given k components "
-                         "the others follow a t law with dof + k degrees of freedom)")
+        raise ValueError(what + ": dof together with given: this entry conditions under the Gaussian copula only (given k components "
+                         "the others follow a t law with dof + k degrees of freedom); call conditional_probabilities / "
+                         "conditional_event_samples")
+    if dof is None and mix_stream is not None:
+        raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
+    return dof
+
+
+def _conditional_dof(what, dof, mix_stream, given, M, plain):
+    """dof of an entry of the conditional family in the components' own units, checked (None: the Gaussian copula): `given` is
+    required (`plain` names the entry without it) and dof + the number of given components must stay within 192; touches no device"""
+    if given is None:
+        raise ValueError("{}: given is required (without given values: {})".format(what, plain))
+    dof = _check_dof(what, dof)
+    if dof is not None:
+        _check_conditional_dof(what, dof, _parse_given(what, given, M)[0].size)
     if dof is None and mix_stream is not None:
         raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
     return dof
@@ -1224,14 +1241,24 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         the limits go to t scores on the host (`t_scores`) and the box goes through `copula_box_probabilities(dof=...)`; corr /
         factor are then the t copula's correlation matrix (`Estimate.estimate_quadrant_correlation` estimates it).  Dropping the
         unconstrained components stays valid: a sub-vector of a multivariate t is a t with the same dof and the sub-matrix.  None or
-        np.inf: the Gaussian copula, bit for bit.  Not together with `given`
+        np.inf: the Gaussian copula, bit for bit.  Not together with `given`: that is `conditional_probabilities`
     :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
-    what = "joint_probabilities"
+    return _joint_probabilities("joint_probabilities", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc,
+                                return_integrand, device, dof, mix_stream)
+
+
+def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, return_integrand,
+                         device, dof, mix_stream):
+    """the one body of `joint_probabilities` and `conditional_probabilities` (conditional: the second one, where dof with given
+    components goes through `conditional_box_probabilities`); the argument errors come in the order they have always had"""
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
-    dof = _box_dof(what, dof, mix_stream, given)
+    if conditional:
+        dof = _conditional_dof(what, dof, mix_stream, given, M, "joint_probabilities")
+    else:
+        dof = _box_dof(what, dof, mix_stream, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1270,6 +1297,16 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
     finish()
     if dof is not None:
         z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
+    if observed.size and dof is not None:
+        cond = conditional_factor(corr, observed, return_observed=True)
+        _, _, _, _, (_, fc, _), mu, r = _conditioning(what, distrs, given, None, cond, dof)
+        cov = fc @ fc.T
+        low = np.linalg.cholesky(cov[np.ix_(keep, keep)])
+        shift = np.ascontiguousarray(np.broadcast_to(mu[:, keep], (B, keep.size)))
+        return conditional_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], dof,
+                                             dof_mix=dof + observed.size, shift=shift, scale=np.broadcast_to(r, (B,)), streams=streams,
+                                             first=first, qmc=qmc, return_integrand=return_integrand, device=device,
+                                             mix_stream=mix_stream)
     if observed.size:
         _, _, _, _, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
@@ -1304,7 +1341,7 @@ def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, f
     :param dof, mix_stream: the Student-t law of `copula_box_probabilities` (mlmc_copula_box_draws_t_batch): limits and the returned
         z are then T scores, z = clip((chain's normal) * s, lower, upper), and u = T_dof(z) of `student_t_cdf`, clamped alike.  By
         default the mixing stream is 0 and coordinate i takes stream i + 1, so weights and `prob` are again those of
-        `copula_box_probabilities` with the same dof, bit for bit.  Not together with `shift`
+        `copula_box_probabilities` with the same dof, bit for bit.  Not together with `shift` (`conditional_box_draws`)
     :param return_mixing: return (BoxDraws, s [R, n]) (dof only)"""
     what = "copula_box_draws"
     dof = _check_dof(what, dof)
@@ -1330,6 +1367,128 @@ def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, f
                                                        _lib.ptr(z), _lib.ptr(u), _lib.ptr(s), kind))
     box = BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
     return (box, s) if return_mixing else box
+
+
+def _conditional_box_problem(what, factor, lower, upper, dof, dof_mix, shift, scale):
+    """(factor, lo, hi, shift [B, M] or None, scale [B] or None, dof, dof_mix) of a conditional box call under the t copula,
+    checked; touches no device"""
+    dof = _check_dof(what, dof)
+    if dof is None:
+        raise ValueError(what + ": dof must be finite, in [1, 64] (the Gaussian copula: copula_box_probabilities / copula_box_draws "
+                         "with a shift)")
+    dof_mix = dof if dof_mix is None else _check_dof_mix(what, dof_mix)
+    f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
+    B = lo.shape[0]
+    if scale is not None:
+        sc = np.asarray(scale, dtype=np.float64)
+        try:
+            sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+        except ValueError:
+            raise ValueError(what + ": scale {} does not broadcast to [B] = {}".format(sc.shape, (B,))) from None
+        if not np.all(np.isfinite(sc) & (sc > 0)):
+            raise ValueError(what + ": the scale must be finite and positive")
+        scale = sc
+    return f, lo, hi, shift, scale, dof, dof_mix
+
+
+def conditional_box_probabilities(factor, lower, upper, n, seeds, dof, dof_mix=None, shift=None, scale=None, streams=None, first=0,
+                                  qmc=True, return_integrand=False, device=False, mix_stream=None, return_mixing=False):
+    """P(lower < Y < upper) for a CONDITIONAL law of the Student-t copula, Y = shift + scale s_c F z: z standard normal,
+    s_c = conditional_mixing_scale(p0, dof_mix) one mixing scale per point, for B boxes and R seeds through ONE device call
+    (mlmc_copula_box_prob_tc_batch).  Given the t scores y_O of p components, the t scores of the others are multivariate t with
+    dof_mix = dof + p degrees of freedom, location shift = W y_O and scale matrix scale^2 F F^T, scale^2 = (dof + d) / (dof + p),
+    d = |L_OO^-1 y_O|^2 (`conditional_factor(..., return_observed=True)`), so
+        P(lower < Y < upper) = E_sc[P((lower - shift) / (scale s_c) < F z < (upper - shift) / (scale s_c))],
+    the chain of `copula_box_probabilities(dof=...)` on these quotients.  Everything is in T-SCORE space (`conditional_probabilities`
+    works in the components' own units).  With shift None, scale None and dof_mix == dof the result is bit for bit that of
+    `copula_box_probabilities(dof=...)`.
+    :param factor, lower, upper, n, seeds, first, qmc, return_integrand, device: as in `copula_box_probabilities`
+    :param dof: the degrees of freedom of the copula, a float in [1, 64]
+    :param dof_mix: those of the mixing variable, a float in [1, 192]; default: dof
+    :param shift: None or the location, broadcast to [B, M], finite
+    :param scale: None (ones) or the scale of each box, broadcast to [B], finite and positive
+    :param streams, mix_stream: as in `copula_box_probabilities(dof=...)`: by default the mixing variable takes stream 0 and chain
+        coordinate i stream i + 1; with explicit `streams`, mix_stream must be given and differ from all of them
+    :param return_mixing: also return the mixing scales s_c [R, n], after the integrand
+    :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
+    what = "conditional_box_probabilities"
+    f, lo, hi, shift, scale, dof, dof_mix = _conditional_box_problem(what, factor, lower, upper, dof, dof_mix, shift, scale)
+    M, B = f.shape[0], lo.shape[0]
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    streams = _box_streams(what, streams, M, qmc)
+    R = seeds.size
+    flags = _lib.SAMPLE_SOBOL if qmc else 0
+    mean = np.empty((R, B))
+    streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, M - 1, qmc)
+    (integrand, s), kind = _output_arrays(device and (return_integrand or return_mixing),
+                                          [(R, B, n) if return_integrand else None, (R, n) if return_mixing else None])
+    _lib.check(_lib.lib().mlmc_copula_box_prob_tc_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, dof_mix, _lib.ptr(shift),
+                                                       _lib.ptr(scale), R, _lib.ptr(seeds), _lib.ptr(streams), mix_stream, first, n,
+                                                       flags, _lib.ptr(mean), _lib.ptr(integrand), _lib.ptr(s), kind))
+    extra = tuple(v for v, want in ((integrand, return_integrand), (s, return_mixing)) if want)
+    result = _joint_probability(mean, n, seeds)
+    return (result,) + extra if extra else result
+
+
+def conditional_box_draws(factor, lower, upper, n, seeds, dof, dof_mix=None, shift=None, scale=None, streams=None, first=0, qmc=True,
+                          device=False, mix_stream=None, return_mixing=False):
+    """Scenarios of the conditional t law of `conditional_box_probabilities` GIVEN lower < Y < upper, through ONE device call
+    (mlmc_copula_box_draws_tc_batch): the GHK sampler of `copula_box_draws(dof=...)` on the limits (lower - shift) / (scale s_c);
+    the returned t score is z = clip(shift + (chain's normal) * (scale s_c), lower, upper) and u = T_dof(z) of `student_t_cdf`
+    with the COPULA's dof (the marginal law of a component is t with dof, not dof_mix), clamped to [2^-53, 1 - 2^-53].  Weights and
+    `prob` are those of `conditional_box_probabilities` bit for bit under default streams.
+    :param streams: one per coordinate, M of them; the other arguments as in `conditional_box_probabilities`
+    :param return_mixing: return (BoxDraws, s_c [R, n])
+    :return: BoxDraws(z [R, B, M, n], u [R, B, M, n], weights [R, B, n], prob)"""
+    what = "conditional_box_draws"
+    f, lo, hi, shift, scale, dof, dof_mix = _conditional_box_problem(what, factor, lower, upper, dof, dof_mix, shift, scale)
+    M, B = f.shape[0], lo.shape[0]
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    streams = _box_streams(what, streams, M + 1, qmc)
+    R = seeds.size
+    flags = _lib.SAMPLE_SOBOL if qmc else 0
+    mean = np.empty((R, B))
+    streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, M, qmc)
+    (z, u, w, s), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n), (R, n) if return_mixing else None])
+    _lib.check(_lib.lib().mlmc_copula_box_draws_tc_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, dof_mix, _lib.ptr(shift),
+                                                        _lib.ptr(scale), R, _lib.ptr(seeds), _lib.ptr(streams), mix_stream, first, n,
+                                                        flags, _lib.ptr(mean), _lib.ptr(w), _lib.ptr(z), _lib.ptr(u), _lib.ptr(s), kind))
+    box = BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+    return (box, s) if return_mixing else box
+
+
+def conditional_probabilities(distrs, lower, upper, given, n, seeds, corr=None, factor=None, dof=None, streams=None, first=0, qmc=True,
+                              return_integrand=False, device=False, mix_stream=None):
+    """Joint box probabilities of the components that are NOT in `given`, conditional on the given values of the others: the
+    probability member of the conditional family (`conditional_samples`, `conditional_quantiles`, `conditional_cdfs`).  With dof
+    None (or np.inf) this is `joint_probabilities(given=...)`, bit for bit, through the same body.  With dof, a float in [1, 64],
+    the copula is the STUDENT-T copula of `joint_samples(dof=...)`: the limits go to t scores, the given values to t scores y_O, and
+    given them the others are multivariate t with dof + p degrees of freedom, location W y_O and scale matrix r^2 F_c F_c^T
+    (`conditional_samples(dof=...)`), so an extreme given value WIDENS the law of the others; the box goes through
+    `conditional_box_probabilities` with shift = mu, scale = r, dof_mix = dof + p.  Components that no box constrains are dropped
+    (a sub-vector of a multivariate t keeps its degrees of freedom).  dof + p must not exceed 192.
+    :param lower, upper: broadcast to [B, q] over the q components that are not given, ascending, in their own units
+    :param given: the mapping of `conditional_samples` (required); arrays [B] pair with the boxes (one box pairs with all sets)
+    :param corr, factor: as in `joint_probabilities`; with dof the t copula's correlation matrix
+    :param streams, mix_stream: per coordinate of the REDUCED problem, and the mixing stream, as in `joint_probabilities(dof=...)`
+    :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
+    return _joint_probabilities("conditional_probabilities", True, distrs, lower, upper, n, seeds, corr, factor, given, streams, first,
+                                qmc, return_integrand, device, dof, mix_stream)
+
+
+def conditional_event_samples(distrs, lower, upper, given, n, seeds, corr=None, factor=None, streams=None, first=0, qmc=True,
+                              device=False, dof=None, mix_stream=None):
+    """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m AND the given values of some components.  With dof
+    None (or np.inf) this is `event_samples(given=...)`, bit for bit, through the same body.  With dof the copula is the Student-t
+    copula, as in `conditional_probabilities`: the chain order of `event_samples`, `conditional_box_draws` with shift = mu,
+    scale = r and dof_mix = dof + p, and one `quantiles` call on its u.  Rows of given components hold the given values (uniforms:
+    Fhat of them).  Under default streams `prob` is bit for bit that of `conditional_probabilities` where no component is dropped
+    there.
+    :param lower, upper: broadcast to [B, M] in the components' own units; a given component must not be constrained
+    :param given: the mapping of `conditional_samples` (required)
+    :return: EventScenarios"""
+    return _event_samples("conditional_event_samples", True, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc,
+                          device, dof, mix_stream)
 
 
 def _event_order(constrained, q):
@@ -1413,14 +1572,24 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
     :param device: draws, uniforms and weights are float64 torch device tensors; `means` and `weighted_quantiles` then raise
     :param dof, mix_stream: the STUDENT-T copula of `joint_samples(dof=...)`, as in `joint_probabilities`: the same chain order,
         `copula_box_draws(dof=...)` and one `quantiles` call on its u.  Under default streams `prob` is bit for bit that of
-        `joint_probabilities(dof=...)` where no component is dropped there.  Not together with `given`
+        `joint_probabilities(dof=...)` where no component is dropped there.  Not together with `given`: that is
+        `conditional_event_samples`
     :return: EventScenarios"""
-    what = "event_samples"
+    return _event_samples("event_samples", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof,
+                          mix_stream)
+
+
+def _event_samples(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof, mix_stream):
+    """the one body of `event_samples` and `conditional_event_samples` (conditional: the second one, where dof with given components
+    goes through `conditional_box_draws`); the argument errors come in the order they have always had"""
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
-    dof = _box_dof(what, dof, mix_stream, given)
+    if conditional:
+        dof = _conditional_dof(what, dof, mix_stream, given, M, "event_samples")
+    else:
+        dof = _box_dof(what, dof, mix_stream, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1463,15 +1632,21 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
     perm = _event_order(np.searchsorted(free, keep), q)
     order = free[perm]                                                                       # chain position -> component
     if observed.size:
-        _, _, _, u_obs, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
+        cond = conditional_factor(corr, observed, return_observed=True) if dof is not None else None
+        _, _, _, u_obs, (_, fc, _), mu, r = _conditioning(what, distrs, given, corr if cond is None else None, cond, dof)
         cov = fc @ fc.T
         low = np.linalg.cholesky(0.5 * (cov + cov.T)[np.ix_(perm, perm)])
         shift = np.ascontiguousarray(np.broadcast_to(mu[:, perm], (B, q)))
     else:
         low = correlation_factor(corr[np.ix_(order, order)])[0]
         u_obs, shift = None, None
-    box = copula_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], shift=shift, streams=streams, first=first,
-                           qmc=qmc, device=device, dof=dof, mix_stream=mix_stream)
+    if observed.size and dof is not None:
+        box = conditional_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], dof, dof_mix=dof + observed.size,
+                                    shift=shift, scale=np.broadcast_to(r, (B,)), streams=streams, first=first, qmc=qmc, device=device,
+                                    mix_stream=mix_stream)
+    else:
+        box = copula_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], shift=shift, streams=streams,
+                               first=first, qmc=qmc, device=device, dof=dof, mix_stream=mix_stream)
     R = seeds.size
     # one quantiles call for all components: component order[i] takes the u of chain position i
     chain = [distrs[m] for m in order]
@@ -1727,19 +1902,42 @@ def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, memb
         hold the given values)
     :param block: columns per device block, >= 1 (with antithetic an even number)
     :param device: return the rows as a float64 torch device tensor
-    :param dof, mix_stream: the Student-t copula of `joint_samples`; not together with `given` (conditional draws exist under the
-        Gaussian copula only)
+    :param dof, mix_stream: the Student-t copula of `joint_samples`; not together with `given`: that is `conditional_aggregates`
     :return: Aggregates(rows [Q, n], or [B, Q, n] for arrays in `given`; names)"""
-    what = "joint_aggregates"
+    return _joint_aggregates("joint_aggregates", False, distrs, n, seed, weights, lower, upper, members, extremes, corr, factor, given,
+                             streams, first, antithetic, qmc, block, device, dof, mix_stream)
+
+
+def conditional_aggregates(distrs, n, seed, given, weights=None, lower=None, upper=None, members=None, extremes=(), corr=None,
+                           factor=None, streams=None, first=0, antithetic=False, qmc=False, block=2 ** 20, device=False, dof=None,
+                           mix_stream=None):
+    """`joint_aggregates(given=...)`, the aggregates member of the conditional family, through the same body; with dof the block
+    walk goes through `conditional_samples(dof=..., factor_info=the 4-tuple of conditional_factor)`, the conditional law of the
+    Student-t copula.  Bit for bit `scenario_aggregates(conditional_samples(distrs, n, seed, given, ...), ...)` for every block size.
+    :param given: the mapping of `conditional_samples` (required); the other arguments as in `joint_aggregates`
+    :param dof, mix_stream: as in `conditional_samples`
+    :return: Aggregates(rows [Q, n], or [B, Q, n] for arrays in `given`; names)"""
+    return _joint_aggregates("conditional_aggregates", True, distrs, n, seed, weights, lower, upper, members, extremes, corr, factor,
+                             given, streams, first, antithetic, qmc, block, device, dof, mix_stream)
+
+
+def _joint_aggregates(what, conditional, distrs, n, seed, weights, lower, upper, members, extremes, corr, factor, given, streams, first,
+                      antithetic, qmc, block, device, dof, mix_stream):
+    """the one body of `joint_aggregates` and `conditional_aggregates` (conditional: the second one, which takes dof with given);
+    the argument errors come in the order they have always had"""
     distrs = list(distrs)
     M = len(distrs)
     if M == 0:
         raise ValueError(what + ": no distributions")
-    dof = _check_dof(what, dof)
-    if dof is not None and given is not None:
-        raise ValueError(what + ": dof together with given: conditional draws exist under the Gaussian copula only")
-    if dof is None and mix_stream is not None:
-        raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
+    if conditional:
+        dof = _conditional_dof(what, dof, mix_stream, given, M, "joint_aggregates")
+    else:
+        dof = _check_dof(what, dof)
+        if dof is not None and given is not None:
+            raise ValueError(what + ": dof together with given: this entry conditions under the Gaussian copula only; call "
+                             "conditional_aggregates")
+        if dof is None and mix_stream is not None:
+            raise ValueError(what + ": mix_stream needs dof (the Gaussian copula has no mixing variable)")
     _sample_flags(what, antithetic, qmc)
     _check_seed(what, seed)
     if (corr is None) == (factor is None):
@@ -1759,7 +1957,7 @@ def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, memb
             if fac.ndim != 2 or fac.shape[0] != M or fac.shape[1] < 1 or not np.all(np.isfinite(fac)):
                 raise ValueError(what + ": the factor must be a finite [M, K] matrix with M = {} distributions".format(M))
             corr = fac @ fac.T
-        cond = conditional_factor(corr, observed)
+        cond = conditional_factor(corr, observed, return_observed=dof is not None)
         lead = () if scalar else (values.shape[1],)
     elif corr is not None:
         factor = correlation_factor(corr)[0]
@@ -1776,7 +1974,7 @@ def joint_aggregates(distrs, n, seed, weights=None, lower=None, upper=None, memb
                               qmc=qmc, dof=dof, mix_stream=mix_stream)
         else:
             x = conditional_samples(distrs, nb, seed, given, factor_info=cond, streams=streams, first=first + off,
-                                    antithetic=antithetic, device=True, qmc=qmc)
+                                    antithetic=antithetic, device=True, qmc=qmc, dof=dof, mix_stream=mix_stream)
         S = 1 if x.dim() == 2 else int(x.shape[0])
         part = _aggregate_call(x, S, M, nb, args, True).reshape(lead + (Q, nb))
         if device:

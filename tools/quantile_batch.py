@@ -114,6 +114,14 @@ with B = 1):
   mixing_entry_ms, map_entry_ms        chi2_mixing_scale on the call's R n device uniforms and (draws) student_t_cdf on its R M n device
                                        scores: the mixing kernel and the CDF pass on their own, with the entry's launch and wait
   prob, stderr / gauss_prob, gauss_stderr (draws: ess_fraction)   what the two calls returned
+--tcondbox: the conditional law of the t copula given p = 1 component (dof_mix = nu + 1, a shift and a scale
+per box) against the t call of the same shape in the same run, the two taking turns after a warm-up each: conditional_box_probabilities
+against copula_box_probabilities(dof=nu) on the shapes of --tboxprob with B in {1, 64} sets of given values, then conditional_box_draws
+against copula_box_draws(dof=nu) on the M, n of its draws (--config M,n: one shape of each with B = 1):
+  cond_ms / t_ms, cond_over_t_wall   wall time of the call, [min, mean, max], and the ratio of the means
+  cond_mixing_entry_ms / t_mixing_entry_ms   the mixing kernel of either call on its own: conditional_mixing_scale(nu + 1) and
+                                     chi2_mixing_scale(nu) on the call's R n device uniforms, with the entry's launch and wait
+  prob, stderr / t_prob, t_stderr    what the two calls returned for box 0
 --aggregates: mlmc_scenario_aggregates on device-resident scenarios x [S, M, n], A = 3 linear rows, all four
 extremes and the count (Q = 8), for S x M x n = 1 x 12 x 10^6, 1 x 64 x 10^6 and 64 given-sets x 12 x 10^4 (--config S,M,n: that shape
 alone), against the torch composition on the same materialised matrix -- matmul, max and min with their indices, compare and sum: five
@@ -146,7 +154,7 @@ and once with the Gaussian model alone (G = 1), the routes of a shape taking tur
   max_abs_difference_from_host / _from_torch   the largest difference of a log density from the composition's
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --tcopula | --tconditional | --scores |
-                                                              --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --aggregates |
+                                                              --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --tcondbox | --aggregates |
                                                               --concordance | --loglik] [--reps K]"""
 import argparse
 import ctypes as C
@@ -882,6 +890,53 @@ def tboxprob_shape(M, B, n, reps, t, dof, seeds=tuple(range(1, 9))):
                 gauss_stderr=float("%.3g" % got["g"].stderr[0]))
 
 
+def _tcond_problem(M, B, t):
+    """B boxes (t, inf)^M in t-score space under equicorrelation 1/2, each with the conditional location and scale of its own given
+    t score of one further component: y_O in (0, 3], mu = y_O / 2, r^2 = (nu + y_O^2) / (nu + 1) with nu filled in by the caller"""
+    corr = np.full((M + 1, M + 1), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    _, fc, _, _ = sd.conditional_factor(corr, [0], return_observed=True)
+    y_obs = 3.0 * np.arange(1, B + 1) / B
+    return fc, np.full((B, M), t), np.full((B, M), np.inf), np.repeat(0.5 * y_obs[:, None], M, axis=1), y_obs
+
+
+def tcondbox_shape(M, B, n, reps, t, dof, draws=False, seeds=tuple(range(1, 9))):
+    """conditional_box_probabilities (draws: conditional_box_draws with device outputs) of B sets of given values, p = 1, against the t
+    entry of the same factor, limits and shape, the two taking turns in one process"""
+    fc, lo, hi, shift, y_obs = _tcond_problem(M, B, t)
+    scale = np.sqrt((dof + y_obs * y_obs) / (dof + 1.0))
+    got = {}
+
+    def cond_route():
+        if draws:
+            got["c"] = sd.conditional_box_draws(fc, lo, hi, n, seeds, dof, dof_mix=dof + 1.0, shift=shift, scale=scale, device=True).prob
+            torch.cuda.synchronize()
+        else:
+            got["c"] = sd.conditional_box_probabilities(fc, lo, hi, n, seeds, dof, dof_mix=dof + 1.0, shift=shift, scale=scale)
+
+    def t_route():
+        if draws:
+            got["t"] = sd.copula_box_draws(fc, lo, hi, n, seeds, dof=dof, device=True).prob
+            torch.cuda.synchronize()
+        else:
+            got["t"] = sd.copula_box_probabilities(fc, lo, hi, n, seeds, dof=dof)
+    p0 = torch.rand(len(seeds) * n, dtype=torch.float64, device="cuda").clamp_(2.0 ** -53, 1.0 - 2.0 ** -53)
+
+    def cond_mixing_route():
+        sd.conditional_mixing_scale(p0, dof + 1.0, device=True)
+        torch.cuda.synchronize()
+
+    def t_mixing_route():
+        sd.chi2_mixing_scale(p0, dof, device=True)
+        torch.cuda.synchronize()
+    wall = _turns((cond_route, t_route, cond_mixing_route, t_mixing_route), reps)
+    return dict(M=M, B=B, n=n, R=len(seeds), threshold=round(t, 4), dof=dof, dof_mix=dof + 1.0, draws=draws, cond_ms=wall[0], t_ms=wall[1],
+                cond_mixing_entry_ms=wall[2], t_mixing_entry_ms=wall[3],
+                cond_over_t_wall=round(wall[0][1] / wall[1][1], 3), prob=float("%.6g" % got["c"].prob[0]),
+                stderr=float("%.3g" % got["c"].stderr[0]), t_prob=float("%.6g" % got["t"].prob[0]),
+                t_stderr=float("%.3g" % got["t"].stderr[0]))
+
+
 def tboxdraws_shape(M, n, reps, p, dof, seeds=tuple(range(1, 9))):
     """event_samples(dof=..., device=True) of the event of --boxdraws against the Gaussian call of the same shape, the two taking
     turns in one process; and the mixing kernel and the CDF pass on their own, on R n uniforms and R M n scores"""
@@ -1213,6 +1268,8 @@ def main():
     ap.add_argument("--boxdraws", action="store_true", help="event_samples against rejection from joint_samples (DESIGN.md section 3.5.18)")
     ap.add_argument("--tboxprob", action="store_true", help="copula_box_probabilities / event_samples with dof = 3, 30 against the Gaussian "
                     "calls of the same shapes (DESIGN.md section 3.5.23)")
+    ap.add_argument("--tcondbox", action="store_true", help="conditional_box_probabilities / conditional_box_draws (p = 1, B in {1, 64} sets) "
+                    "against the t entries of the same shapes (DESIGN.md section 3.5.26)")
     ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
@@ -1251,6 +1308,18 @@ def main():
             shapes = [(1, 12, 10_000), (3, 5, 1_000)]
         _lib.use_torch_stream()
         out["aggregates"] = [aggregates_shape(S, M, n, a.reps) for S, M, n in shapes]
+    elif a.tcondbox:
+        t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
+        shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
+        shapes += [(12, 1, 2 ** k, t6) for k in (12, 16, 20)]
+        draws = [(M, 1, 2 ** k) for M in (2, 12, 64) for k in (12, 16)] + [(M, 64, 2 ** 12) for M in (2, 12)]
+        if a.config:
+            M, n = (int(v) for v in a.config.split(","))
+            shapes, draws = [(M, 1, n, 0.0)], [(M, 1, n)]
+        elif a.quick:
+            shapes, draws = [(2, 1, 2 ** 12, 0.0), (12, 64, 2 ** 12, t6)], [(2, 1, 2 ** 12), (12, 64, 2 ** 12)]
+        out["tcondbox"] = [tcondbox_shape(M, B, n, a.reps, t, dof) for M, B, n, t in shapes for dof in (3.0, 30.0)]
+        out["tcondbox_draws"] = [tcondbox_shape(M, B, n, a.reps, 0.0, dof, draws=True) for M, B, n in draws for dof in (3.0, 30.0)]
     elif a.tboxprob:
         t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
         shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
