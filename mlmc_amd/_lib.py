@@ -225,10 +225,27 @@ def lib():
     return _lib
 
 
+_torch_stream = None       # handle of the torch stream use_torch_stream() moved the library onto; None: its own stream
+
+
 def use_torch_stream():
     """Enqueue all kernels on torch's current CUDA/HIP stream (the one torch.distributed collectives use)."""
+    global _torch_stream
     import torch
-    check(lib().mlmc_set_stream(C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    handle = int(torch.cuda.current_stream().cuda_stream)
+    check(lib().mlmc_set_stream(C.c_void_p(handle)))
+    _torch_stream = handle
+
+
+def order_after_torch(t):
+    """The rule for every entry that hands a CUDA tensor to the library: the work torch's current stream on that tensor's
+    device has queued (the tensor's producer, possibly a copy made a line earlier) is finished before the library reads or
+    writes the tensor on its own stream.  Nothing to wait for when that stream IS the library's (use_torch_stream):
+    decided by the stream handles, so a call under `with torch.cuda.stream(other):` is still ordered.  t: tensor or device."""
+    import torch
+    st = torch.cuda.current_stream(getattr(t, "device", t))
+    if _torch_stream is None or int(st.cuda_stream) != _torch_stream:
+        st.synchronize()
 
 
 def device_info():

@@ -94,6 +94,7 @@ class LevelAccumulator:
         else:
             assert fine.is_contiguous() and (coarse is None or coarse.is_contiguous())
             self._keepalive.append((fine, coarse))   # launches are asynchronous
+            _lib.order_after_torch(fine)             # the library reads them on its own stream
         n = fine.shape[-1]
         m = 1 if fine.ndim == 1 else fine.shape[0]
         if m != self.n_comp:
@@ -117,6 +118,8 @@ class LevelAccumulator:
         _, levels, fine, coarse, ns = cached
         L, K = self.n_levels, self.K
         self._keepalive = list(chunks)
+        if k:
+            _lib.order_after_torch(chunks[0][1])             # the library reads the chunks on its own stream
         if reduce and _dist_group_active(group):
             packed, on_gpu = self._packed_buffer(group)
             _lib.check(_lib.lib().mlmc_accum_estimate_packed(self._h, k, levels, fine, coarse, ns, _lib.DEVICE, _lib.ptr(packed),
@@ -317,6 +320,8 @@ def percentiles(values, q_percent, nan_policy="omit"):
     else:
         values = values.reshape(-1).contiguous()
         n = values.numel()
+        if values.is_cuda:
+            _lib.order_after_torch(values)                               # the library reads it on its own stream
     n_valid = C.c_int64()
     _lib.check(_lib.lib().mlmc_percentiles(_lib.ptr(values), int(n), _lib.ptr(q), int(q.size), _lib.ptr(out), C.byref(n_valid),
                                            _lib.mem_kind(values)))
@@ -350,8 +355,8 @@ def row_percentiles(values, q_percent, nan_policy="omit"):
         if values.stride(1) != 1 or (M > 1 and values.stride(0) < n):
             values = values.contiguous()
         ld = values.stride(0) if M > 1 else n
-        if values.is_cuda and not getattr(_lib, "_on_torch_stream", False):
-            torch.cuda.current_stream(values.device).synchronize()     # the library reads it on its own stream
+        if values.is_cuda:
+            _lib.order_after_torch(values)                               # the library reads it on its own stream
     out = np.empty((M, q.size), dtype=np.float64)
     n_valid = np.empty(M, dtype=np.int64)
     _lib.check(_lib.lib().mlmc_percentiles_rows(_lib.ptr(values), int(M), int(n), int(ld), _lib.ptr(q), int(q.size),
@@ -415,6 +420,7 @@ class BootstrapAccumulator:
         if sizes.shape != (self.B,):
             raise ValueError("bootstrap accum: sizes of shape {}, expected ({},)".format(sizes.shape, self.B))
         self._keepalive.append((fine, coarse))             # launches are asynchronous
+        _lib.order_after_torch(fine)                       # the library reads them on its own stream
         _lib.check(_lib.lib().mlmc_bootstrap_accum(self._h, int(level), _lib.ptr(fine), _lib.ptr(coarse), int(fine.shape[1]),
                                                    _lib.ptr(sizes), int(seed) & (2 ** 64 - 1), int(stream) & 0xFFFFFFFF))
 

@@ -258,6 +258,8 @@ class DeviceMemory(SampleStorage):
         if int(level_id) == 0 and pairs.shape[2] == 2:
             pairs = pairs[:, :, :1]
         self._levels[int(level_id)] = pairs.contiguous()
+        from . import _lib
+        _lib.order_after_torch(pairs)        # device_row hands the rows to the library, which reads them on its own stream
         self._level_versions[int(level_id)] = self._level_versions.get(int(level_id), 0) + 1
 
     def device_row(self, chunk_spec, stored_row):
