@@ -49,7 +49,8 @@ extern "C" {
                               *    mlmc_copula_box_prob_t_batch, mlmc_copula_box_draws_t_batch,
                               *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale,
                               *    mlmc_student_t_quantile, mlmc_copula_log_density,
-                              *    mlmc_copula_box_prob_tc_batch, mlmc_copula_box_draws_tc_batch */
+                              *    mlmc_copula_box_prob_tc_batch, mlmc_copula_box_draws_tc_batch,
+                              *    mlmc_copula_box_prob_tl_batch, mlmc_copula_box_draws_tl_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -800,6 +801,44 @@ int mlmc_copula_box_draws_tc_batch(int32_t M, const double *L, int32_t B, const 
                                    const double *shift, const double *scale, int32_t R, const uint64_t *seeds, const uint32_t *streams,
                                    uint32_t mix_stream, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
                                    double *z_out, double *u_out, double *s_out, int mem_kind);
+/* ---- the two t entries with a CONDITIONED LEAD component -- added within 8 ------------------------------------------------
+ * The _t_batch entries sample the mixing scale s plainly: a box that only a rare s reaches is carried by a handful of points.  These
+ * entries draw the lead score V = Y_0 / L_00, which is Student-t with nu degrees of freedom, INSIDE its limits by inversion, with the
+ * exact weight W0 = T_nu(hi_0 / L_00) - T_nu(lo_0 / L_00).  Given V = v the mixing scale follows s^2 = (nu + v^2) / chi2_{nu+1}, and
+ * given v and s the first chain normal is y_0 = v / s:
+ *     P(lo < Y < hi) = E[ W0 * prod_{i >= 1} width_i ],
+ * every factor O(1): the relative error does not grow with the depth of the box.  Component 0 of the CALLER'S order leads; it should
+ * be the most constraining one.  The arguments, the argument errors, the staging within 192 MiB, the summation tree, the split by
+ * whole blocks and the stream rules are those of the _t_batch entries, with these differences:
+ *   dof = nu in [1, 64]; the mixing variable uses nu + 1 through the constants of mlmc_chi2_conditional_scale.
+ *   streams [M] in BOTH entries (NULL: i): streams[0] is the lead's coordinate, streams[i], 1 <= i <= M - 2 (draws: M - 1), the
+ *     chain's.  The probability entry does not read streams[M-1] unless M = 1.  mix_stream equal to a stream that is read is an error.
+ *   s_out [R][B][n] (may be NULL): the scale now depends on the box.  lead_out [R][B][n] (may be NULL): the lead score v.  Both are
+ *     kept per (seed, box, point) of a launch in the workspace and count towards the 192 MiB that size a launch.
+ * For seed r, box b and point j (every operation ONE fp64 operation rounded to nearest, no FMA):
+ *   1. p0 = the uniform of mix_stream as in the _t_batch entries; g0 = bit for bit mlmc_chi2_conditional_scale(dof + 1, p0), made
+ *      once per (seed, point), not per box.
+ *   2. a = lo[b][0] / L_00, bq = hi[b][0] / L_00, refl = a > 0;  d = T(refl ? -bq : a), e = T(refl ? -a : bq), T bit for bit
+ *      mlmc_student_t_cdf(dof, .);  W0 = a < bq ? e - d : 0.  Once per box.
+ *   3. w = the uniform of streams[0];  p = min(max(d + w * W0, 2^-1022), 1 - 2^-53);  v = bit for bit
+ *      mlmc_student_t_quantile(dof, p), negated if refl;  v = min(max(v, a), bq), then min(max(v, -2^500), 2^500): v * v is finite.
+ *   4. q = sqrt((dof + v * v) / (dof + 1)), a correctly rounded square root;  sc = g0 * q;  y_0 = v / sc.
+ *   5. Components i = 1 .. M-1: step i of the _t_batch chain with sc in the place of s and streams[i].  g = the product of their
+ *      widths, from 1 in ascending i;  f = W0 * g, ONE rounded product at the end.  So f[r][b][j] is bit for bit W0 times the
+ *      Gaussian entry's integrand at point j for the factor L[1:, 1:], the box (lo[b][1:] / sc, hi[b][1:] / sc), the shift
+ *      L_i0 * y_0 (one rounded product) and streams[1:].
+ *   6. Draws: row 0 is min(max(v * L_00, lo[b][0]), hi[b][0]); the others as in the _t_batch entry; u_out by the same pass with dof.
+ *   7. M = 1 uses no point: mean = W0 itself for every seed, f = W0.
+ * An empty lead (a >= bq) gives W0 = 0, f = 0 and v = bq.  No value depends on B, R, the position of box or seed, first / n, the
+ * launch split, the presence of f_out / u_out / s_out / lead_out or host / device outputs.  Fixed trip counts; no atomics; one host
+ * wait.  Conditional laws (the _tc_ entries) keep plain mixing: nu + p + 1 would leave the tested range of the t functions. */
+int mlmc_copula_box_prob_tl_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, double *s_out, double *lead_out, int mem_kind);
+int mlmc_copula_box_draws_tl_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                   const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                   int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out,
+                                   double *lead_out, int mem_kind);
 
 /* ---- aggregates of joint scenarios (scenario.hip) -- added within 8 ----------------------------------------------------
  * Functions of the M components of one scenario, once per scenario column.  x [S][M][ld]: S >= 1 sets of M >= 1 component rows,

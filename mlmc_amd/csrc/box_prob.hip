@@ -22,6 +22,11 @@
 //                shift[b], scale matrix scale[b]^2 L L^T, the mixing variable with dof_mix degrees of freedom) are TCOP with one more
 //                flag: the lane multiplies its mixing scale by the box's scale once, takes the shift off every limit before the
 //                division, and adds it back to the stored t score.
+//                The LEAD instances (mlmc_copula_box_prob_tl_batch / _draws_tl_batch: the t copula with component 0 drawn INSIDE its
+//                limits and the mixing scale conditioned on it) are TCOP with one more flag: k_box_lead
+//                (copula_t.hip) has made the lead score v and the scale sc per (seed, box, point); the chain starts at i = 1 with
+//                y_0 = v / sc and the finished product of widths is multiplied by the lead's weight W0 of the box.  Again no t
+//                function is called from the chain.
 //   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
 // The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
 // k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
@@ -72,7 +77,11 @@ __device__ __attribute__((noinline)) double box_normcdfinv(double p) { return no
 // TCOND (the tc entries, with TCOP): sc = scl[b] * sc once (scl NULL: ones); with a shift every limit is (lo - shift) / sc, one
 // rounded subtraction before the division, the chain itself runs without a shift, and the stored score is
 // min(max(shift + z sc, lo), hi).  With shift NULL neither the subtraction nor the sum is taken: the bits of TCOP.
-template <bool SOBOL, bool DRAWS, bool TCOP = false, bool TCOND = false>
+// LEAD (the tl entries, with TCOP and without TCOND): the three pointers that a t entry leaves unused carry the lead's arrays, so that
+// every other instance keeps its arguments: `shift` holds W0 [B], `mix` holds sc and `scl` holds v, both
+// [seed][box][64 blockIdx.x + lane] over the R * B pairs of the call (k_box_lead).  ys[0] = v / sc, one division; steps 1 .. M - 1
+// are TCOP's; f = W0 * (the product of their widths), one rounded product at the end; with DRAWS row 0 is min(max(v L_00, lo), hi).
+template <bool SOBOL, bool DRAWS, bool TCOP = false, bool TCOND = false, bool LEAD = false>
 __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__restrict__ L, const double *__restrict__ lo,
                                                         const double *__restrict__ hi, const double *__restrict__ shift, int B, int b0,
                                                         const uint64_t *__restrict__ seeds, int r0, const uint32_t *__restrict__ streams,
@@ -88,15 +97,27 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
     const int64_t j = (a << 6) | lane;
     const bool active = j >= first && j < first + n;
     const double *lo_b = lo + (int64_t)b * M, *hi_b = hi + (int64_t)b * M;
-    const double *sh_b = shift ? shift + (int64_t)b * M : nullptr;
+    const double *sh_b = !LEAD && shift ? shift + (int64_t)b * M : nullptr;
     const uint64_t seed = seeds[r];
     const uint64_t *tab = SOBOL ? table + (int64_t)r * table_rows * SOBOL_ROW : nullptr;
     double sc = 1.0;
-    if constexpr (TCOP) sc = mix[((int64_t)r * gridDim.x + blockIdx.x) * BOX_LANES + lane];
+    if constexpr (TCOP && !LEAD) sc = mix[((int64_t)r * gridDim.x + blockIdx.x) * BOX_LANES + lane];
     if constexpr (TCOND)
         if (scl) sc = __dmul_rn(scl[b], sc);
     double f = 1.0;
-    for (int i = 0; i < M; ++i) {
+    if constexpr (LEAD) {
+        const int64_t at = (((int64_t)r * B + b) * gridDim.x + blockIdx.x) * BOX_LANES + lane;
+        const double vl = scl[at];
+        sc = mix[at];
+        if (M > 1) ys[lane] = vl / sc;
+        if constexpr (DRAWS) {
+            const double z = fmin(fmax(__dmul_rn(vl, L[0]), lo_b[0]), hi_b[0]);
+            const int64_t to = ((int64_t)r * B + b) * M * ldf + (j - first - c_off);
+            if (active && u_out) u_out[to] = z;
+            if (active) z_out[to] = z;
+        }
+    }
+    for (int i = LEAD ? 1 : 0; i < M; ++i) {
         const double *Li = L + (int64_t)i * M;
         double s = !TCOND && sh_b ? sh_b[i] : 0.0;
         for (int k = 0; k < i; ++k) s = __dadd_rn(s, __dmul_rn(Li[k], ys[k * BOX_LANES + lane]));
@@ -136,13 +157,14 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
             }
         }
     }
+    if constexpr (LEAD) f = __dmul_rn(shift[b], f);
     if (active && f_out) f_out[((int64_t)r * B + b) * ldf + (j - first - c_off)] = f;
     double v = active ? f : 0.0;
 #pragma unroll
     for (int o = BOX_LANES / 2; o; o >>= 1) v += __shfl_xor(v, o);
     // M = 1 uses no point: every lane holds e - d, and k_box_mean hands it on as it is
-    // (under TCOP the one width depends on the point's mixing scale: the tree as for every other M)
-    if (lane == 0) partials[((int64_t)r * B + b) * call_blocks + (a - call_blk0)] = M == 1 && !TCOP ? f : v;
+    // (under TCOP the one width depends on the point's mixing scale: the tree as for every other M; under LEAD it is W0 again)
+    if (lane == 0) partials[((int64_t)r * B + b) * call_blocks + (a - call_blk0)] = M == 1 && (!TCOP || LEAD) ? f : v;
 }
 
 __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__restrict__ partials, int64_t call_blocks, int64_t n,
@@ -164,11 +186,14 @@ __global__ __launch_bounds__(BOX_MEAN_THREADS) void k_box_mean(const double *__r
 static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                     const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
                     int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr, const double *dof = nullptr,
-                    uint32_t mix_stream = 0, double *s_out = nullptr, const double *dof_mix = nullptr, const double *scale = nullptr) {
+                    uint32_t mix_stream = 0, double *s_out = nullptr, const double *dof_mix = nullptr, const double *scale = nullptr,
+                    bool lead = false, double *lead_out = nullptr) {
     const std::string e(fn);
     const bool tcop = dof != nullptr;                  // the t entries: *dof degrees of freedom, the mixing stream, s_out [R][n] or NULL
     // the tc entries: a conditional law, *dof_mix degrees of freedom of the mixing variable, shift [B][M] or NULL, scale [B] or NULL
     const bool tcond = tcop && dof_mix != nullptr;
+    // the tl entries (lead, with tcop and without tcond): component 0 is drawn inside its limits, the mixing variable has *dof + 1
+    // degrees of freedom given it; s_out and lead_out are [R][B][n]
     if (!rt().ready) return fail("mlmc_init has not been called (no HIP device bound)");
     if (tcop && tcop_check_dof(fn, *dof)) return 1;
     if (tcond && tcop_check_dof(fn, *dof_mix, TCOP_MAX_DOF_MIX, "dof_mix")) return 1;
@@ -205,7 +230,8 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
             if (!std::isfinite(scale[b]) || !(scale[b] > 0.0))
                 return fail(e + ": box " + std::to_string(b) + ": the scale must be finite and positive");
     // the coordinates: streams (Philox), or the rows of the call's distinct dimensions, one table per seed (MLMC_SAMPLE_SOBOL)
-    const int nc = draws ? M : M - 1;                   // the draws take one more coordinate for the last component
+    // the draws take one more coordinate for the last component; the lead of the tl entries has coordinate 0 even where M = 1
+    const int nc = draws ? M : lead ? std::max(M - 1, 1) : M - 1;
     // the t entries: the mixing variable is one more coordinate, behind the chain's, in the same table
     const int nd = nc + (tcop ? 1 : 0);
     std::vector<uint32_t> dims;
@@ -243,9 +269,13 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     // staged rows of a pair: the integrand, and with draws the M rows of z and of u
     const size_t zrows = draws ? pairs * (size_t)M : 0, urows = u_out ? zrows : 0, rows = pairs + zrows + urows;
     int64_t lb = std::min<int64_t>(call_blocks, 0x7fffffff);
-    // the t entries keep the mixing scales of a launch, one row per seed, within the same bytes
+    // the t entries keep the mixing scales of a launch, one row per seed, within the same bytes; the tl entries also the lead score
+    // and the conditioned scale, one row per pair each
     if (stage || tcop) {
-        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES * ((stage ? rows : 0) + (tcop ? (size_t)R : 0)))));
+        lb = std::min<int64_t>(lb, (int64_t)(BOX_F_BYTES / (sizeof(double) * BOX_LANES *
+                                                            ((stage ? rows : 0) + (tcop ? (size_t)R : 0) + (lead ? 2 * pairs : 0)))));
+        if (lb < 1 && !stage && lead)
+            return fail(e + ": the lead scores of one block of 64 points of R * B pairs exceed 192 MiB: split the boxes or the seeds across calls");
         if (lb < 1 && !stage) return fail(e + ": the mixing scales of one block of 64 points of R seeds exceed 192 MiB: split the seeds across calls");
         if (lb < 1)
             return fail(e + (draws ? ": the draws" : ": the integrand") +
@@ -277,9 +307,15 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const size_t b_mean = mm_align(sizeof(double) * pairs), b_f = stage ? mm_align(sizeof(double) * pairs * (size_t)ldf) : 0;
     const size_t b_z = stage ? mm_align(sizeof(double) * zrows * (size_t)ldf) : 0, b_u = stage ? mm_align(sizeof(double) * urows * (size_t)ldf) : 0;
     const size_t b_s = tcop ? mm_align(sizeof(double) * (size_t)R * (size_t)lb * BOX_LANES) : 0;
+    // the tl entries: W0 | d [B], then v and sc [R * B][64 lb]
+    const size_t b_w = lead ? mm_align(sizeof(double) * 2 * (size_t)B) : 0;
+    const size_t b_v = lead ? mm_align(sizeof(double) * pairs * (size_t)lb * BOX_LANES) : 0;
     static MultiWorkspace ws;
-    if (ws.reserve(b_in + b_part + b_mean + b_f + b_z + b_u + b_s)) return 1;
+    if (ws.reserve(b_in + b_part + b_mean + b_f + b_z + b_u + b_s + b_w + 2 * b_v)) return 1;
     double *d_s = tcop ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z + b_u) : nullptr;
+    double *d_w = lead ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z + b_u + b_s) : nullptr;
+    double *d_v = lead ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z + b_u + b_s + b_w) : nullptr;
+    double *d_sc = lead ? (double *)(ws.dev + b_in + b_part + b_mean + b_f + b_z + b_u + b_s + b_w + b_v) : nullptr;
     double *d_in = (double *)ws.dev, *d_part = (double *)(ws.dev + b_in), *d_mean = (double *)(ws.dev + b_in + b_part);
     double *d_f = stage ? (double *)(ws.dev + b_in + b_part + b_mean) : f_out;
     double *d_z = stage && draws ? (double *)(ws.dev + b_in + b_part + b_mean + b_f) : z_out;
@@ -292,7 +328,9 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
 
     const size_t lds = sizeof(double) * BOX_LANES * (size_t)(M - 1);
-    const auto kernel = tcond ? (draws ? (sobol ? k_box_prob<true, true, true, true> : k_box_prob<false, true, true, true>)
+    const auto kernel = lead  ? (draws ? (sobol ? k_box_prob<true, true, true, false, true> : k_box_prob<false, true, true, false, true>)
+                                       : (sobol ? k_box_prob<true, false, true, false, true> : k_box_prob<false, false, true, false, true>))
+                      : tcond ? (draws ? (sobol ? k_box_prob<true, true, true, true> : k_box_prob<false, true, true, true>)
                                        : (sobol ? k_box_prob<true, false, true, true> : k_box_prob<false, false, true, true>))
                       : tcop ? (draws ? (sobol ? k_box_prob<true, true, true> : k_box_prob<false, true, true>)
                                       : (sobol ? k_box_prob<true, false, true> : k_box_prob<false, false, true>))
@@ -300,7 +338,9 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                                       : (sobol ? k_box_prob<true, false> : k_box_prob<false, false>));
     // the CDF pass maps with the constants of dof (the marginal law of a component), the mixing kernel takes those of dof_mix
     const TCopConst tconst = tcop ? tcop_constants(*dof) : TCopConst{};
-    const TCopConst tmix = tcond ? tcop_constants(*dof_mix) : tconst;
+    const TCopConst tmix = tcond ? tcop_constants(*dof_mix) : lead ? tcop_constants(*dof + 1.0) : tconst;
+    // the lead's weight of every box, once per call
+    if (lead) cop_launch_box_lead_weights(st, tconst, (int)M, d_L, d_lo, d_hi, (int)B, d_w);
     for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
         const int64_t kb = std::min(lb, call_blocks - k0);
         // the first point of the launch within the call: column 0 of the staged integrand
@@ -310,7 +350,20 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
             // the mixing scales of the launch's blocks, once per (seed, point): d_s [R][64 kb]
             const int64_t j0 = (call_blk0 + k0) << 6;
             cop_launch_box_mixing(st, tmix, R, d_seeds, coord[nc], sobol ? d_tab : nullptr, table_rows, j0, kb * BOX_LANES, first, n, d_s);
-            if (s_out)
+            if (lead) {
+                // v and sc of the launch's blocks for every pair: [R * B][64 kb], from the scales g0 [R][64 kb] just made
+                cop_launch_box_lead(st, tconst, (int)M, d_L, d_lo, d_hi, (int)B, R, d_seeds, coord[0], sobol ? d_tab : nullptr, table_rows, j0,
+                                    kb * BOX_LANES, first, n, d_s, d_w, d_v, d_sc);
+                const hipMemcpyKind kind = mem_kind == MLMC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+                if (s_out)
+                    MLMC_HIP_CHECK(hipMemcpy2DAsync(s_out + c_lo, sizeof(double) * (size_t)n, d_sc + (first + c_lo - j0),
+                                                    sizeof(double) * (size_t)(kb * BOX_LANES), sizeof(double) * (size_t)(c_hi - c_lo), pairs,
+                                                    kind, st));
+                if (lead_out)
+                    MLMC_HIP_CHECK(hipMemcpy2DAsync(lead_out + c_lo, sizeof(double) * (size_t)n, d_v + (first + c_lo - j0),
+                                                    sizeof(double) * (size_t)(kb * BOX_LANES), sizeof(double) * (size_t)(c_hi - c_lo), pairs,
+                                                    kind, st));
+            } else if (s_out)
                 MLMC_HIP_CHECK(hipMemcpy2DAsync(s_out + c_lo, sizeof(double) * (size_t)n, d_s + (first + c_lo - j0),
                                                 sizeof(double) * (size_t)(kb * BOX_LANES), sizeof(double) * (size_t)(c_hi - c_lo), (size_t)R,
                                                 mem_kind == MLMC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
@@ -318,9 +371,10 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
         for (int r0 = 0; r0 < R; r0 += 65535)
             for (int b0 = 0; b0 < B; b0 += 65535) {
                 const dim3 grid((unsigned)kb, (unsigned)std::min(B - b0, 65535), (unsigned)std::min(R - r0, 65535));
-                hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, d_shift, (int)B, b0, d_seeds, r0, d_coord,
-                                   d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part, d_f, ldf,
-                                   stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)d_s, d_scale);
+                hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, lead ? (const double *)d_w : d_shift, (int)B,
+                                   b0, d_seeds, r0, d_coord, d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part,
+                                   d_f, ldf, stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)(lead ? d_sc : d_s),
+                                   lead ? (const double *)d_v : d_scale);
             }
         // the CDF pass of the t draws: the rows of u hold the t scores of the launch's columns and are mapped in place
         if (tcop && u_out) cop_launch_t_map(st, tconst, (int)urows, c_hi - c_lo, d_u + (stage ? 0 : c_lo), ldf);
@@ -337,7 +391,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
         }
     }
     hipLaunchKernelGGL(k_box_mean, dim3((unsigned)pairs), dim3(BOX_MEAN_THREADS), 0, st, (const double *)d_part, call_blocks, n,
-                       (int)(M == 1 && !tcop), d_mean);
+                       (int)(M == 1 && (!tcop || lead)), d_mean);
     MLMC_HIP_CHECK(hipGetLastError());
     MLMC_HIP_CHECK(hipMemcpyAsync(mean, d_mean, sizeof(double) * pairs, hipMemcpyDeviceToHost, st));
     MLMC_HIP_CHECK(wait_stream(st));
@@ -379,6 +433,23 @@ int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const d
     MLMC_API_GUARD;
     return box_prob("mlmc_copula_box_draws_t_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
                     z_out, u_out, &dof, mix_stream, s_out);
+}
+
+int mlmc_copula_box_prob_tl_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                  const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, double *s_out, double *lead_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_tl_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, false,
+                    nullptr, nullptr, &dof, mix_stream, s_out, nullptr, nullptr, true, lead_out);
+}
+
+int mlmc_copula_box_draws_tl_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
+                                   const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
+                                   int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out,
+                                   double *lead_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_draws_tl_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, true,
+                    z_out, u_out, &dof, mix_stream, s_out, nullptr, nullptr, true, lead_out);
 }
 
 int mlmc_copula_box_prob_tc_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, double dof_mix,

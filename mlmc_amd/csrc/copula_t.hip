@@ -8,6 +8,9 @@
 //                  coordinate of the mixing dimension (sobol.hpp); one thread per draw
 //   k_box_mixing : the same scale for the t box entries (box_prob.hip): s[r][c] of point j0 + c under seed r, for all seeds of a
 //                  call and the whole blocks of one launch; one thread per (seed, point), once per point and not once per box
+//   k_box_lead_weights, k_box_lead : the conditioned lead component of the tl box entries: the lead's weight W0
+//                  per box from two t CDFs, and per (seed, box, point) the lead score v by student_t_quantile inside the lead's
+//                  limits and the scale sc = g0 sqrt((nu + v v) / (nu + 1)), g0 the scale k_box_mixing made with nu + 1
 //   k_tcop_map   : U = clamp(student_t_cdf(nu, U)) in place, one thread per element.  The map is a kernel of its own and not the
 //                  epilogue of the product: a lane of the product holds 16 accumulators, and the series loop over them would keep
 //                  them and the constants of pow / exp / log1p live together (the comment at the top of copula.hip).
@@ -294,6 +297,57 @@ __global__ __launch_bounds__(TC_THREADS) void k_box_mixing(TCopConst C, const ui
     s[(int64_t)r * ncols + c] = v;
 }
 
+// The lead component of the tl box entries (box_prob.hip).  With a = lo[b][0] / L_00 and bq = hi[b][0] / L_00 the
+// lead score V = Y_0 / L_00 is Student-t with nu degrees of freedom: w[b] = W0 = T(bq) - T(a) through the lower tail on either
+// side, w[B + b] = d, the lower end of the interval of p.  One thread per box, once per call.
+__global__ __launch_bounds__(TC_THREADS) void k_box_lead_weights(TCopConst C, int M, const double *__restrict__ L,
+                                                                 const double *__restrict__ lo, const double *__restrict__ hi, int B,
+                                                                 double *__restrict__ w) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double l00 = L[0], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
+    const bool refl = a > 0.0;
+    const double d = student_t_cdf(C, refl ? -bq : a), e = student_t_cdf(C, refl ? -a : bq);
+    w[b] = a < bq ? e - d : 0.0;
+    w[B + b] = d;
+}
+
+// v and sc of the tl box entries for the blocks of one launch: column c is point j0 + c, blockIdx.y the pair (seed r, box b) behind
+// pair0.  g0 [R][ncols] are the scales k_box_mixing made with the constants of nu + 1; C holds those of nu.  The uniform of the
+// lead is the Philox uniform j of `stream` under seeds[r] or the coordinate of point j in row `stream` of seed r's table.
+//   p = min(max(d + w W0, 2^-1022), 1 - 2^-53), v = T^-1(p) (negated for an upper-tail lead), clamped to [a, bq] and to +-2^500;
+//   sc = g0 sqrt((nu + v v) / (nu + 1)).
+// W0, d, a and bq are uniform over a wave (scalar loads); v and sc are not.  Points outside [first, first + n) pad with v = 0, sc = 1.
+__global__ __launch_bounds__(TC_THREADS) void k_box_lead(TCopConst C, int M, const double *__restrict__ L, const double *__restrict__ lo,
+                                                         const double *__restrict__ hi, int B, int64_t pair0,
+                                                         const uint64_t *__restrict__ seeds, uint32_t stream,
+                                                         const uint64_t *__restrict__ table, int table_rows, int64_t j0, int64_t ncols,
+                                                         int64_t first, int64_t n, const double *__restrict__ g0,
+                                                         const double *__restrict__ w, double *__restrict__ v_out,
+                                                         double *__restrict__ sc_out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncols) return;
+    const int64_t pair = pair0 + blockIdx.y;
+    const int r = (int)(pair / B), b = (int)(pair % B);
+    const int64_t j = j0 + c;
+    double v = 0.0, sc = 1.0;
+    if (j >= first && j < first + n) {
+        const double l00 = L[0], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
+        const bool refl = a > 0.0;
+        const double u = table ? sobol_unit(sobol_point(table + ((int64_t)r * table_rows + stream) * SOBOL_ROW, (uint64_t)j))
+                               : q_uniform(seeds[r], stream, (uint64_t)j);
+        const double p = fmin(fmax(__dadd_rn(w[B + b], __dmul_rn(u, w[b])), 0x1p-1022), 1.0 - 0x1p-53);
+        v = student_t_quantile(C, p);
+        v = refl ? -v : v;
+        v = fmin(fmax(v, a), bq);
+        v = fmin(fmax(v, -0x1p500), 0x1p500);          // v v stays finite
+        const double q = __dsqrt_rn(__dadd_rn(C.dof, __dmul_rn(v, v)) / __dadd_rn(C.dof, 1.0));
+        sc = __dmul_rn(g0[(int64_t)r * ncols + c], q);
+    }
+    v_out[pair * ncols + c] = v;
+    sc_out[pair * ncols + c] = sc;
+}
+
 __global__ __launch_bounds__(TC_THREADS) void k_tcop_map(TCopConst C, int64_t ncols, double *__restrict__ U, int64_t ldu) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ncols) return;
@@ -333,6 +387,22 @@ void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint
                            dim3(TC_THREADS), 0, st, C, seeds + r0, stream,
                            table ? table + (int64_t)r0 * table_rows * SOBOL_ROW : nullptr, table_rows, j0, ncols, first, n,
                            s + (int64_t)r0 * ncols);
+}
+
+void cop_launch_box_lead_weights(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B,
+                                 double *w) {
+    hipLaunchKernelGGL(k_box_lead_weights, dim3((unsigned)((B + TC_THREADS - 1) / TC_THREADS)), dim3(TC_THREADS), 0, st, C, M, L, lo, hi, B, w);
+}
+
+void cop_launch_box_lead(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B, int R,
+                         const uint64_t *seeds, uint32_t stream, const uint64_t *table, int table_rows, int64_t j0, int64_t ncols,
+                         int64_t first, int64_t n, const double *g0, const double *w, double *v, double *sc) {
+    // pair of a launch = blockIdx.y: more pairs than a grid has in y go in several launches
+    const int64_t pairs = (int64_t)R * B;
+    for (int64_t p0 = 0; p0 < pairs; p0 += 65535)
+        hipLaunchKernelGGL(k_box_lead, dim3((unsigned)((ncols + TC_THREADS - 1) / TC_THREADS), (unsigned)std::min<int64_t>(pairs - p0, 65535)),
+                           dim3(TC_THREADS), 0, st, C, M, L, lo, hi, B, p0, seeds, stream, table, table_rows, j0, ncols, first, n, g0, w, v,
+                           sc);
 }
 
 void cop_launch_t_map(hipStream_t st, const TCopConst &C, int M, int64_t ncols, double *U, int64_t ldu) {

@@ -735,7 +735,9 @@ class Estimate:
         :param dof: as in estimate_joint_probability: the Student-t copula with that many degrees of freedom.  The degrees of
             freedom are HELD FIXED over the replicates: the band is the uncertainty of the correlation (and marginals) at the given
             dof, not that of the fit of `estimate_copula_dof`.  The resampled correlation is the Pearson or scores one, which
-            estimates the t copula's matrix only approximately (the quadrant correlation is not resampled)
+            estimates the t copula's matrix only approximately (the quadrant correlation is not resampled).  The band keeps PLAIN
+            mixing (estimate_joint_probability(mixing="plain")): under dof it shares that entry's limit on boxes that only a rare
+            mixing scale reaches; for those take the point estimate from estimate_joint_probability(mixing="conditioned")
         :return: ProbabilityBands(prob [n_boxes], stderr [n_boxes] = those of estimate_joint_probability with the same n and seeds,
             lo, hi [n_boxes] = quantile_bands over the ok replicates, replicates [B, n_boxes], ok [B], n_ok, seed).  A replicate
             whose correlation is not ok, whose solve failed for a component that a box constrains (a finite limit on either
@@ -790,7 +792,8 @@ class Estimate:
         """P(X_m > t_m for all constrained m) with its bootstrap band: `bootstrap_joint_probability` with lower = thresholds and
         upper = +inf.
         :param thresholds: broadcast to [n_boxes, M]; -inf leaves a component unconstrained
-        :param dof: the Student-t copula, its degrees of freedom held fixed over the replicates (bootstrap_joint_probability)
+        :param dof: the Student-t copula, its degrees of freedom held fixed over the replicates (bootstrap_joint_probability); the
+            band keeps PLAIN mixing, as there
         :return: as bootstrap_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
@@ -1124,7 +1127,7 @@ class Estimate:
         return draws, success, cond[2]
 
     def estimate_joint_probability(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain"):
         """Probability that the components lie in a box AT ONCE, P(lower_m < X_m < upper_m for all m), under the marginals and the
         Gaussian copula of `sample_joint`, for B boxes in one batched device call (tool.simple_distribution.joint_probabilities):
         Genz's separation of variables on scrambled Sobol' points.  Its error is relative and falls like 1 / n, so the small
@@ -1146,12 +1149,18 @@ class Estimate:
             shows joint tails (a large positive z), this is the number to use: the Gaussian one is too small.  `corr` is then the t
             copula's correlation matrix, which corr="quadrant" estimates consistently; None and "scores" only approximately.  Not
             together with `given`: that is `estimate_conditional_probability`
+        :param mixing: "plain" (default, bit for bit as before) or "conditioned" (dof only, not with `given`): the component with the
+            smallest marginal probability of each box LEADS: it is drawn inside its limits and the mixing scale follows its law given
+            that draw (tool.simple_distribution.joint_probabilities / event_samples), so the relative error holds at any depth of
+            the box.  Plain mixing returns a number that is orders of magnitude too small, with a `stderr` that does not show it,
+            once only a rare mixing scale reaches the box (marginal levels of 1e-6 at dof = 3)
         :return: (JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds), success [M])"""
         from .tool import simple_distribution
         what = "estimate_joint_probability"
         dof = simple_distribution._box_dof(what, dof, None, given)
+        simple_distribution._check_mixing(what, mixing, dof, None, given)
         return self._joint_probability(what, simple_distribution.joint_probabilities, lower, upper, n, seeds, corr, given, tol, reg_param,
-                                       orth_moments_tol, moments_fns, densities, first, qmc, dof)
+                                       orth_moments_tol, moments_fns, densities, first, qmc, dof, mixing)
 
     def estimate_conditional_probability(self, lower, upper, given, n=2 ** 14, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
                                          orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
@@ -1165,6 +1174,8 @@ class Estimate:
         :param given: as in sample_conditional (required); arrays [B] pair with the boxes
         :param corr: as in sample_joint; with dof corr="quadrant" is the consistent correlation, as for sample_conditional(dof=...)
         :param n, seeds, densities, first, qmc: as in estimate_joint_probability
+        The conditional family keeps PLAIN mixing (there is no `mixing` keyword here): its mixing variable has dof + p degrees of
+        freedom, and a conditioned lead would need the t functions at dof + p + 1, outside their tested range.
         :return: (JointProbability, success [M])"""
         from .tool import simple_distribution
         what = "estimate_conditional_probability"
@@ -1176,8 +1187,9 @@ class Estimate:
                                        densities, first, qmc, nu)
 
     def _joint_probability(self, what, entry, lower, upper, n, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns,
-                           densities, first, qmc, dof):
-        """the one body of estimate_joint_probability and estimate_conditional_probability; dof checked by the caller"""
+                           densities, first, qmc, dof, mixing="plain"):
+        """the one body of estimate_joint_probability and estimate_conditional_probability; dof and mixing checked by the caller
+        (mixing goes to the entry only where it is not "plain": the conditional entry has no such keyword)"""
         from .tool import simple_distribution
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
@@ -1185,8 +1197,9 @@ class Estimate:
         corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        more = {} if mixing == "plain" else {"mixing": mixing}
         result = entry([d[0] for d in densities], lower, upper, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first,
-                       qmc=qmc, dof=dof)
+                       qmc=qmc, dof=dof, **more)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
 
@@ -1204,17 +1217,18 @@ class Estimate:
                                                      first=first, qmc=qmc, dof=dof)
 
     def estimate_joint_exceedance(self, thresholds, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain"):
         """P(X_m > t_m for all constrained m): `estimate_joint_probability` with lower = thresholds and upper = +inf.
         :param thresholds: broadcast to [B, M]; -inf leaves a component unconstrained
         :param dof: the Student-t copula, as in estimate_joint_probability
+        :param mixing: as in estimate_joint_probability; with dof and thresholds in the far tail use mixing="conditioned"
         :return: as estimate_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
             raise ValueError("estimate_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
         return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
-                                               first=first, qmc=qmc, dof=dof)
+                                               first=first, qmc=qmc, dof=dof, mixing=mixing)
 
     def estimate_tail_dependence(self, probs=(0.9, 0.95, 0.99), tail="upper", corr=None, densities=None, tol=1e-8, reg_param=0.0,
                                  orth_moments_tol=1e-4, moments_fns=None, dof=None):
@@ -1476,7 +1490,8 @@ class Estimate:
         return JointFrequency(st["prob"], stderr, counts, counts.n)
 
     def sample_given_event(self, n, lower, upper, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                           orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True, dof=None):
+                           orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True, dof=None,
+                           mixing="plain"):
         """Joint scenarios of all components GIVEN that they lie in a box at once (lower_m < X_m < upper_m for all m), under the
         marginals and the Gaussian copula of `sample_joint`, for B events and R seeds (tool.simple_distribution.event_samples):
         what the system looks like when the event of `estimate_joint_probability` happens.  Every scenario lies in the event and
@@ -1493,12 +1508,18 @@ class Estimate:
         :param dof: None or np.inf: the Gaussian copula, bit for bit; a float in [1, 64]: the Student-t copula of
             `sample_joint(dof=...)`, as in estimate_joint_probability (corr="quadrant" is the consistent correlation).  Not together
             with `given`: that is `sample_conditional_event`
+        :param mixing: "plain" (default, bit for bit as before) or "conditioned" (dof only, not with `given`): the component with the
+            smallest marginal probability of each box LEADS: it is drawn inside its limits and the mixing scale follows its law given
+            that draw (tool.simple_distribution.joint_probabilities / event_samples), so the relative error holds at any depth of
+            the box.  Plain mixing returns a number that is orders of magnitude too small, with a `stderr` that does not show it,
+            once only a rare mixing scale reaches the box (marginal levels of 1e-6 at dof = 3)
         :return: (EventScenarios(draws [R, B, M, n], weights [R, B, n], prob, ess [R, B], ok [M], uniforms), success [M])"""
         from .tool import simple_distribution
         what = "sample_given_event"
         dof = simple_distribution._box_dof(what, dof, None, given)
+        simple_distribution._check_mixing(what, mixing, dof, None, given)
         return self._given_event(what, simple_distribution.event_samples, n, lower, upper, seeds, corr, given, tol, reg_param,
-                                 orth_moments_tol, moments_fns, densities, first, device, qmc, dof)
+                                 orth_moments_tol, moments_fns, densities, first, device, qmc, dof, mixing)
 
     def sample_conditional_event(self, n, lower, upper, given, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, device=False, qmc=True, dof=None):
@@ -1507,6 +1528,7 @@ class Estimate:
         through the same body; with dof the copula is the Student-t copula, as in estimate_conditional_probability.
         :param given: as in sample_conditional (required); a given component must not be constrained
         :param n, lower, upper, seeds, corr, densities, first, device, qmc: as in sample_given_event
+        Like the whole conditional family this keeps PLAIN mixing (see estimate_conditional_probability).
         :return: (EventScenarios, success [M]); rows of given components hold the given values"""
         from .tool import simple_distribution
         what = "sample_conditional_event"
@@ -1518,8 +1540,8 @@ class Estimate:
                                  densities, first, device, qmc, nu)
 
     def _given_event(self, what, entry, n, lower, upper, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns, densities,
-                     first, device, qmc, dof):
-        """the one body of sample_given_event and sample_conditional_event; dof checked by the caller"""
+                     first, device, qmc, dof, mixing="plain"):
+        """the one body of sample_given_event and sample_conditional_event; dof and mixing checked by the caller"""
         from .tool import simple_distribution
         n, seeds, first = simple_distribution._box_call_args(what, n, seeds, first)
         if np.any(np.isnan(np.asarray(lower, dtype=np.float64))) or np.any(np.isnan(np.asarray(upper, dtype=np.float64))):
@@ -1527,24 +1549,25 @@ class Estimate:
         corr, densities = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
+        more = {} if mixing == "plain" else {"mixing": mixing}
         result = entry([d[0] for d in densities], lower, upper, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first,
-                       qmc=qmc, device=device, dof=dof)
+                       qmc=qmc, device=device, dof=dof, **more)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
         return result, success
 
     def estimate_event_means(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                             orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
+                             orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain"):
         """Expected value of EVERY component given that the components lie in a box at once, E[X | lower < X < upper]: the weighted
         means of the scenarios of `sample_given_event`.  `estimate_event_means(thresholds, np.inf)` is the companion of
         `estimate_joint_exceedance`: the expected state of the system when all thresholds are exceeded.  The weights are smooth on
         the Sobol' points, so the error falls like 1 / n at any probability of the event.
-        :param lower, upper, n, seeds, corr, given, densities, first, qmc, dof: as in sample_given_event
+        :param lower, upper, n, seeds, corr, given, densities, first, qmc, dof, mixing: as in sample_given_event
         :return: (EventMeans(mean [B, M], stderr [B, M], prob, ess [R, B]), success [M]): per seed the ratio sum f x / sum f, its
             mean over the seeds and their spread over sqrt(R); prob the JointProbability of the event; ess the effective sample
             size of each seed's n scenarios"""
         scen, success = self.sample_given_event(n, lower, upper, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                 orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
-                                                first=first, qmc=qmc, dof=dof)
+                                                first=first, qmc=qmc, dof=dof, mixing=mixing)
         mean, stderr = scen.means()
         return EventMeans(mean, stderr, scen.prob, scen.ess), success
 
@@ -1563,7 +1586,7 @@ class Estimate:
     def estimate_aggregates(self, weights=None, probs=(0.05, 0.5, 0.95), n=2 ** 16, seeds=tuple(range(8)), corr=None, given=None,
                             lower=None, upper=None, members=None, extremes=("max", "min"), event=None, tail="upper", qmc=True,
                             block=2 ** 20, tol=1e-8, reg_param=0.0, orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0,
-                            antithetic=False, dof=None):
+                            antithetic=False, dof=None, mixing="plain"):
         """The distribution of FUNCTIONS of the components under the marginals and the Gaussian copula of `sample_joint`: the total
         over a field (sum_m w_m X_m), the worst component and which one it is, how many components violate their limits at
         once.  The scenarios are drawn and reduced block by block on the device (tool.simple_distribution.joint_aggregates), so the
@@ -1590,11 +1613,15 @@ class Estimate:
         :param block: scenario columns per device block
         :param dof: None or np.inf: the Gaussian copula; a float in [1, 64]: the Student-t copula of `sample_joint(dof=...)`, with
             `event` that of `sample_given_event(dof=...)`.  Not together with `given`: that is `estimate_conditional_aggregates`
+        :param mixing: with `event` and dof: as in sample_given_event ("conditioned": the conditioned lead); without `event` there is
+            no box and "conditioned" raises
         :return: (AggregateSummary, success [M]).  Statistics are [Q, ...], with a leading axis B for arrays in `given` and for the B
             boxes of `event` (always, also for one box); count_prob [.., M + 1], worst_prob / best_prob [.., M] are None without their row"""
         from .tool import simple_distribution as sd
+        if sd._check_mixing("estimate_aggregates", mixing, sd._check_dof("estimate_aggregates", dof), None, given) and event is None:
+            raise ValueError('estimate_aggregates: mixing="conditioned" needs event (without a box there is no lead component)')
         return self._aggregates("estimate_aggregates", (_refuse_dof_with_given, sd.joint_aggregates, sd.event_samples), weights, probs, n, seeds, corr, given, lower, upper, members, extremes, event, tail, qmc,
-                                block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof)
+                                block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof, mixing)
 
     def estimate_conditional_aggregates(self, given, weights=None, probs=(0.05, 0.5, 0.95), n=2 ** 16, seeds=tuple(range(8)), corr=None,
                                         lower=None, upper=None, members=None, extremes=("max", "min"), event=None, tail="upper",
@@ -1613,7 +1640,7 @@ class Estimate:
                                 block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof)
 
     def _aggregates(self, what, entries, weights, probs, n, seeds, corr, given, lower, upper, members, extremes, event, tail, qmc,
-                    block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof):
+                    block, tol, reg_param, orth_moments_tol, moments_fns, densities, first, antithetic, dof, mixing="plain"):
         """the one body of estimate_aggregates and estimate_conditional_aggregates; entries: (the check of dof against given, the
         aggregates entry, the event entry) of tool.simple_distribution"""
         from .tool import simple_distribution as sd
@@ -1658,7 +1685,7 @@ class Estimate:
             f_of = None
         else:
             scen = event_samples(distrs, lower_e, upper_e, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first, qmc=qmc,
-                                 device=True, dof=dof)
+                                 device=True, dof=dof, **({} if mixing == "plain" else {"mixing": mixing}))
             ev = sd.event_aggregates(scen, **agg)
             B = int(ev.rows.shape[1])
             per_seed = [ev.rows[r] for r in range(R)]

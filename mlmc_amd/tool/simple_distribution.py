@@ -1108,8 +1108,24 @@ def t_scores(z, dof):
     return np.where(np.isinf(z) | (z == 0), z, y)
 
 
+def _check_mixing(what, mixing, dof, shift=None, given=None):
+    """True for mixing="conditioned" (the tl entries), checked; touches no device"""
+    if mixing not in ("plain", "conditioned"):
+        raise ValueError(what + ': mixing must be "plain" or "conditioned", got {!r}'.format(mixing))
+    if mixing == "plain":
+        return False
+    if dof is None:
+        raise ValueError(what + ': mixing="conditioned" needs dof (the Gaussian copula has no mixing variable)')
+    if shift is not None:
+        raise ValueError(what + ': mixing="conditioned" together with shift: the conditioned lead exists for the unconditional t law only')
+    if given is not None:
+        raise ValueError(what + ': mixing="conditioned" together with given: the conditional family keeps plain mixing (its mixing '
+                         "variable would have dof + p + 1 degrees of freedom, outside the tested range of the t functions)")
+    return True
+
+
 def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, return_integrand=False,
-                             device=False, dof=None, mix_stream=None, return_mixing=False):
+                             device=False, dof=None, mix_stream=None, return_mixing=False, mixing="plain", return_lead=False):
     """P(lower < Y < upper) for Y = shift + F z, z standard normal, for B boxes and R seeds through ONE device call
     (mlmc_copula_box_prob_batch): Genz's separation of variables, which conditions through the lower-triangular factor with one
     Phi^-1 and two Phi per component, so that the integrand is a smooth function on the unit cube.  Everything is in SCORE space
@@ -1135,15 +1151,28 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     :param mix_stream: the stream (qmc: the dimension, below 1024) of the mixing uniform.  Default 0, and chain coordinate i then
         takes stream i + 1; with explicit `streams` it must be given and differ from all of them
     :param return_mixing: also return the mixing scales s [R, n] (dof only), after the integrand
+    :param mixing: "plain" (default): the mixing scale is sampled as it is, bit for bit what this entry has always returned.  A box
+        that only a rare scale reaches is then carried by a handful of points: `prob` is off by orders of magnitude and `stderr`
+        does not show it (an orthant at marginal level 1e-6 with dof = 3: seeds between 1e-15 and 2e-6 against 1.6e-7).
+        "conditioned" (dof only, no shift;
+        mlmc_copula_box_prob_tl_batch): component 0 of the caller's order LEADS: its score is drawn inside its limits by inversion
+        of the t CDF with the exact weight W0 = T(upper_0 / F_00) - T(lower_0 / F_00), the mixing scale follows its law GIVEN that
+        score (dof + 1 degrees of freedom), and the chain runs over components 1 .. M - 1: the relative error of the Gaussian chain
+        at any depth.  Put the most constraining component first (`joint_probabilities` does).  streams are then M - 1 as before
+        with streams[0] the lead's coordinate; the mixing scales are [R, B, n]
+    :param return_lead: also return the lead scores v [R, B, n] (mixing="conditioned" only), after the mixing scales
     :return: JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds)"""
     what = "copula_box_probabilities"
     dof = _check_dof(what, dof)
+    lead = _check_mixing(what, mixing, dof, shift)
+    if return_lead and not lead:
+        raise ValueError(what + ': return_lead needs mixing="conditioned"')
     if dof is None and (mix_stream is not None or return_mixing):
         raise ValueError(what + ": mix_stream and return_mixing need dof (the Gaussian copula has no mixing variable)")
     f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
     M, B = f.shape[0], lo.shape[0]
     n, seeds, first = _box_call_args(what, n, seeds, first)
-    streams = _box_streams(what, streams, M, qmc)
+    streams = _box_streams(what, streams, 2 if lead and M == 1 else M, qmc)          # the lead of M = 1 has a coordinate
     R = seeds.size
     flags = _lib.SAMPLE_SOBOL if qmc else 0
     mean = np.empty((R, B))
@@ -1154,6 +1183,19 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
                                                         _lib.ptr(integrand), kind))
         result = _joint_probability(mean, n, seeds)
         return (result, integrand) if return_integrand else result
+    if lead:
+        # M = 1 has no chain coordinate but its lead has one; the entry takes [M] streams and does not read the last one for M > 1
+        streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, max(M - 1, 1), qmc)
+        streams = np.ascontiguousarray(np.concatenate([streams, streams[-1:]])[:M], dtype=np.uint32)
+        (integrand, s, v), kind = _output_arrays(device and (return_integrand or return_mixing or return_lead),
+                                                 [(R, B, n) if return_integrand else None, (R, B, n) if return_mixing else None,
+                                                  (R, B, n) if return_lead else None])
+        _lib.check(_lib.lib().mlmc_copula_box_prob_tl_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                                           _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
+                                                           _lib.ptr(integrand), _lib.ptr(s), _lib.ptr(v), kind))
+        extra = tuple(a for a, want in ((integrand, return_integrand), (s, return_mixing), (v, return_lead)) if want)
+        result = _joint_probability(mean, n, seeds)
+        return (result,) + extra if extra else result
     streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, M - 1, qmc)
     (integrand, s), kind = _output_arrays(device and (return_integrand or return_mixing),
                                           [(R, B, n) if return_integrand else None, (R, n) if return_mixing else None])
@@ -1223,8 +1265,30 @@ def _conditional_dof(what, dof, mix_stream, given, M, plain):
     return dof
 
 
+def lead_components(t_lo, t_hi, dof, candidates=None):
+    """The lead component of each box for mixing="conditioned", on the host: the one with the smallest marginal probability
+    T_dof(hi) - T_dof(lo), taken through the lower tail on either side as `t_scores` does (an upper-tail limit pair keeps its relative
+    accuracy); ties go to the lowest index.
+    :param t_lo, t_hi: [B, q] t scores of the limits
+    :param candidates: None (all q) or the column indices to choose among
+    :return: (lead [B] column indices, marginal [B, q] probabilities)"""
+    from scipy.special import stdtr
+    t_lo, t_hi = np.asarray(t_lo, dtype=np.float64), np.asarray(t_hi, dtype=np.float64)
+    upper = t_lo > 0
+    with np.errstate(invalid="ignore"):
+        marg = np.where(upper, stdtr(dof, -t_lo) - stdtr(dof, -t_hi), stdtr(dof, t_hi) - stdtr(dof, t_lo))
+    marg = np.where(t_lo < t_hi, marg, 0.0)
+    cand = np.arange(marg.shape[1]) if candidates is None else np.asarray(candidates, dtype=np.int64)
+    return cand[np.argmin(marg[:, cand], axis=1)], marg
+
+
+def _lead_groups(lead):
+    """[(lead column, box indices)] of the boxes grouped by their lead, ascending in the lead"""
+    return [(int(c), np.flatnonzero(lead == c)) for c in np.unique(lead)]
+
+
 def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True,
-                        return_integrand=False, device=False, dof=None, mix_stream=None):
+                        return_integrand=False, device=False, dof=None, mix_stream=None, mixing="plain"):
     """Joint box probabilities P(lower_m < X_m < upper_m for all m) under the Gaussian copula of `joint_samples`, for B boxes in
     the components' own units through `copula_box_probabilities`; with `given`, conditional on the given values of some
     components as in `conditional_samples`.  A limit that is +-inf or lies at or beyond an end of its distribution's domain is an
@@ -1242,13 +1306,20 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         factor are then the t copula's correlation matrix (`Estimate.estimate_quadrant_correlation` estimates it).  Dropping the
         unconstrained components stays valid: a sub-vector of a multivariate t is a t with the same dof and the sub-matrix.  None or
         np.inf: the Gaussian copula, bit for bit.  Not together with `given`: that is `conditional_probabilities`
+    :param mixing: "plain" (default): bit for bit what this entry has always returned; a box that only a rare mixing scale reaches
+        (marginal levels of 1e-6 at dof = 3) then comes out orders of magnitude too small with a `stderr` that does not show it.
+        "conditioned" (dof only): the conditioned lead of `copula_box_probabilities`.  After the unconstrained components are
+        dropped, the lead of each box is the component with the smallest marginal probability (`lead_components`; ties: the lowest
+        index); boxes are grouped by lead with one device call per group, the correlation permuted lead-first and refactored on the
+        host.  streams[0] is then the lead's coordinate, streams[i] that of the i-th other constrained component, ascending.  Out of
+        scope: `given` (raises: the conditional family keeps plain mixing) and Genz's full reordering beyond the lead
     :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
     return _joint_probabilities("joint_probabilities", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc,
-                                return_integrand, device, dof, mix_stream)
+                                return_integrand, device, dof, mix_stream, mixing)
 
 
 def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, return_integrand,
-                         device, dof, mix_stream):
+                         device, dof, mix_stream, mixing="plain"):
     """the one body of `joint_probabilities` and `conditional_probabilities` (conditional: the second one, where dof with given
     components goes through `conditional_box_probabilities`); the argument errors come in the order they have always had"""
     distrs = list(distrs)
@@ -1259,6 +1330,7 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
         dof = _conditional_dof(what, dof, mix_stream, given, M, "joint_probabilities")
     else:
         dof = _box_dof(what, dof, mix_stream, given)
+    lead = _check_mixing(what, mixing, dof, None, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1286,9 +1358,9 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
         lo, hi = np.repeat(lo, Bg, axis=0), np.repeat(hi, Bg, axis=0)
         B = Bg
     z_lo, z_hi, keep, finish = _limit_scores(what, [distrs[m] for m in free], lo, hi)
-    streams = _box_streams(what, streams, max(keep.size, 1), qmc)
+    streams = _box_streams(what, streams, 2 if lead and keep.size <= 1 else max(keep.size, 1), qmc)
     if dof is not None:
-        streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, max(keep.size, 1) - 1, qmc)
+        streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, max(keep.size - 1, 1 if lead else 0), qmc)
     if keep.size > _lib.BOX_PROB_MAX_M:
         raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
     if keep.size == 0:
@@ -1297,6 +1369,28 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
     finish()
     if dof is not None:
         z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
+    if lead:
+        # one device call per lead: the correlation of the constrained components permuted lead-first and refactored
+        t_lo, t_hi = z_lo[:, keep], z_hi[:, keep]
+        R = seeds.size
+        replicates = np.empty((R, B))
+        integrand = None
+        for c, boxes in _lead_groups(lead_components(t_lo, t_hi, dof)[0]):
+            order = np.concatenate([[c], np.delete(np.arange(keep.size), c)])
+            comp = free[keep][order]
+            low = correlation_factor(corr[np.ix_(comp, comp)])[0]
+            out = copula_box_probabilities(low, t_lo[np.ix_(boxes, order)], t_hi[np.ix_(boxes, order)], n, [int(s) for s in seeds],
+                                           streams=streams, first=first, qmc=qmc, return_integrand=return_integrand, device=device,
+                                           dof=dof, mix_stream=mix_stream, mixing=mixing)
+            res, f = out if return_integrand else (out, None)
+            replicates[:, boxes] = res.replicates
+            if return_integrand:
+                if integrand is None:
+                    integrand = f if boxes.size == B else (f.new_empty((R, B, n)) if device else np.empty((R, B, n)))
+                if boxes.size != B:
+                    integrand[:, boxes.tolist() if device else boxes, :] = f
+        result = _joint_probability(replicates, n, seeds)
+        return (result, integrand) if return_integrand else result
     if observed.size and dof is not None:
         cond = conditional_factor(corr, observed, return_observed=True)
         _, _, _, _, (_, fc, _), mu, r = _conditioning(what, distrs, given, None, cond, dof)
@@ -1324,7 +1418,7 @@ BoxDraws = collections.namedtuple("BoxDraws", "z u weights prob")
 
 
 def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, first=0, qmc=True, device=False, dof=None,
-                     mix_stream=None, return_mixing=False):
+                     mix_stream=None, return_mixing=False, mixing="plain", return_lead=False):
     """Scenarios of Y = shift + F z GIVEN lower < Y < upper, for B boxes and R seeds through ONE device call
     (mlmc_copula_box_draws_batch): the conditioned normals of the chain of `copula_box_probabilities` are a sequential importance
     sample of the truncated normal vector (the GHK sampler).  Every point is a scenario inside the box; its weight is the
@@ -1342,9 +1436,17 @@ def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, f
         z are then T scores, z = clip((chain's normal) * s, lower, upper), and u = T_dof(z) of `student_t_cdf`, clamped alike.  By
         default the mixing stream is 0 and coordinate i takes stream i + 1, so weights and `prob` are again those of
         `copula_box_probabilities` with the same dof, bit for bit.  Not together with `shift` (`conditional_box_draws`)
-    :param return_mixing: return (BoxDraws, s [R, n]) (dof only)"""
+    :param return_mixing: return (BoxDraws, s [R, n]) (dof only)
+    :param mixing: "plain" (default, bit for bit as before) or "conditioned" (dof only, no shift; mlmc_copula_box_draws_tl_batch):
+        the conditioned lead of `copula_box_probabilities`: component 0 leads, streams[0] is its coordinate, row 0 of z is
+        clip(v F_00, lower_0, upper_0) and the mixing scales are [R, B, n].  Weights and `prob` are those of
+        `copula_box_probabilities(mixing="conditioned")`, bit for bit
+    :param return_lead: append the lead scores v [R, B, n] to the returned tuple (mixing="conditioned" only)"""
     what = "copula_box_draws"
     dof = _check_dof(what, dof)
+    lead = _check_mixing(what, mixing, dof, shift)
+    if return_lead and not lead:
+        raise ValueError(what + ': return_lead needs mixing="conditioned"')
     if dof is None and (mix_stream is not None or return_mixing):
         raise ValueError(what + ": mix_stream and return_mixing need dof (the Gaussian copula has no mixing variable)")
     f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
@@ -1361,6 +1463,15 @@ def copula_box_draws(factor, lower, upper, n, seeds, shift=None, streams=None, f
                                                          _lib.ptr(z), _lib.ptr(u), kind))
         return BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
     streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, M, qmc)
+    if lead:
+        (z, u, w, s, v), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n), (R, B, n) if return_mixing else None,
+                                                        (R, B, n) if return_lead else None])
+        _lib.check(_lib.lib().mlmc_copula_box_draws_tl_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                                            _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean), _lib.ptr(w),
+                                                            _lib.ptr(z), _lib.ptr(u), _lib.ptr(s), _lib.ptr(v), kind))
+        box = BoxDraws(z, u, w, _joint_probability(mean, n, seeds))
+        extra = tuple(a for a, want in ((s, return_mixing), (v, return_lead)) if want)
+        return (box,) + extra if extra else box
     (z, u, w, s), kind = _output_arrays(device, [(R, B, M, n), (R, B, M, n), (R, B, n), (R, n) if return_mixing else None])
     _lib.check(_lib.lib().mlmc_copula_box_draws_t_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
                                                        _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean), _lib.ptr(w),
@@ -1552,7 +1663,7 @@ class EventScenarios:
 
 
 def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True, device=False,
-                  dof=None, mix_stream=None):
+                  dof=None, mix_stream=None, mixing="plain"):
     """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m for all m, under the marginals and the Gaussian
     copula of `joint_samples`, for B events and R seeds through `copula_box_draws` and ONE `quantiles` call: what the system
     looks like when the event of `joint_probabilities` happens.  Every scenario lies in the event and carries a weight; rejection
@@ -1574,12 +1685,47 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
         `copula_box_draws(dof=...)` and one `quantiles` call on its u.  Under default streams `prob` is bit for bit that of
         `joint_probabilities(dof=...)` where no component is dropped there.  Not together with `given`: that is
         `conditional_event_samples`
+    :param mixing: "plain" (default, bit for bit as before; ess / n of a deep event under a small dof is then tiny: the weights are
+        carried by the few points with a rare mixing scale) or "conditioned" (dof only): the conditioned lead of `copula_box_draws`.
+        The lead of each box is the constrained component with the smallest marginal probability (`lead_components`); it moves to
+        the front of the chain order above, boxes are grouped by lead with one device call per group, and draws, uniforms and
+        weights come back in the components' own order.  `prob` is bit for bit that of `joint_probabilities(mixing="conditioned")`
+        where no component is dropped there.  Out of scope: `given` (raises) and reordering beyond the lead
     :return: EventScenarios"""
     return _event_samples("event_samples", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof,
-                          mix_stream)
+                          mix_stream, mixing)
 
 
-def _event_samples(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof, mix_stream):
+def _lead_box_draws(corr, order, keep, t_lo, t_hi, n, seeds, streams, first, qmc, device, dof, mix_stream):
+    """BoxDraws of `event_samples(mixing="conditioned")` with the rows of z and u in the chain order `order` (chain position ->
+    component; the constrained components `keep` first): per box the lead (`lead_components` among `keep`; nothing constrained: the
+    first of the order) moves to the front, boxes are grouped by lead, one `copula_box_draws` call per group on the correlation
+    permuted so, and the rows go back to their chain positions"""
+    B, q, R = t_lo.shape[0], order.size, seeds.size
+    lead = lead_components(t_lo, t_hi, dof, keep)[0] if keep.size else np.full(B, order[0])
+    z = u = w = None
+    replicates = np.empty((R, B))
+    for c, boxes in _lead_groups(lead):
+        at = int(np.flatnonzero(order == c)[0])
+        pos = np.concatenate([[at], np.delete(np.arange(q), at)])                            # the group's chain -> chain position
+        comp = order[pos]
+        low = correlation_factor(corr[np.ix_(comp, comp)])[0]
+        box = copula_box_draws(low, t_lo[np.ix_(boxes, comp)], t_hi[np.ix_(boxes, comp)], n, [int(s) for s in seeds], streams=streams,
+                               first=first, qmc=qmc, device=device, dof=dof, mix_stream=mix_stream, mixing="conditioned")
+        replicates[:, boxes] = box.prob.replicates
+        if z is None:
+            new = (lambda shape: box.z.new_empty(shape)) if device else np.empty
+            z, u, w = new((R, B, q, n)), new((R, B, q, n)), new((R, B, n))
+        rows = boxes.tolist() if device else boxes
+        w[:, rows] = box.weights
+        for i, k in enumerate(pos):
+            z[:, rows, int(k)] = box.z[:, :, i]
+            u[:, rows, int(k)] = box.u[:, :, i]
+    return BoxDraws(z, u, w, _joint_probability(replicates, n, seeds))
+
+
+def _event_samples(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof, mix_stream,
+                   mixing="plain"):
     """the one body of `event_samples` and `conditional_event_samples` (conditional: the second one, where dof with given components
     goes through `conditional_box_draws`); the argument errors come in the order they have always had"""
     distrs = list(distrs)
@@ -1590,6 +1736,7 @@ def _event_samples(what, conditional, distrs, lower, upper, n, seeds, corr, fact
         dof = _conditional_dof(what, dof, mix_stream, given, M, "event_samples")
     else:
         dof = _box_dof(what, dof, mix_stream, given)
+    lead = _check_mixing(what, mixing, dof, None, given)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1640,7 +1787,9 @@ def _event_samples(what, conditional, distrs, lower, upper, n, seeds, corr, fact
     else:
         low = correlation_factor(corr[np.ix_(order, order)])[0]
         u_obs, shift = None, None
-    if observed.size and dof is not None:
+    if lead:
+        box = _lead_box_draws(corr, order, keep, z_lo, z_hi, n, seeds, streams, first, qmc, device, dof, mix_stream)
+    elif observed.size and dof is not None:
         box = conditional_box_draws(low, z_lo[:, order], z_hi[:, order], n, [int(s) for s in seeds], dof, dof_mix=dof + observed.size,
                                     shift=shift, scale=np.broadcast_to(r, (B,)), streams=streams, first=first, qmc=qmc, device=device,
                                     mix_stream=mix_stream)

@@ -122,6 +122,12 @@ against copula_box_draws(dof=nu) on the M, n of its draws (--config M,n: one sha
   cond_mixing_entry_ms / t_mixing_entry_ms   the mixing kernel of either call on its own: conditional_mixing_scale(nu + 1) and
                                      chi2_mixing_scale(nu) on the call's R n device uniforms, with the entry's launch and wait
   prob, stderr / t_prob, t_stderr    what the two calls returned for box 0
+--tlead: copula_box_probabilities(dof=nu, mixing="conditioned") against the plain t call of the same shape in
+the same run, the two taking turns after a warm-up each, on the probability shapes of --tboxprob (B in {1, 64}, nu = 3 and 30; --config
+M,n: one shape with B = 1):
+  lead_ms / plain_ms, lead_over_plain_wall   wall time of the call, [min, mean, max], and the ratio of the means
+  prob, stderr, ess_fraction / plain_prob, plain_stderr, plain_ess_fraction   what the two calls returned for box 0; ess / n from the
+                                     integrand of box 0 alone (a call of its own, not timed), the mean over the seeds
 --aggregates: mlmc_scenario_aggregates on device-resident scenarios x [S, M, n], A = 3 linear rows, all four
 extremes and the count (Q = 8), for S x M x n = 1 x 12 x 10^6, 1 x 64 x 10^6 and 64 given-sets x 12 x 10^4 (--config S,M,n: that shape
 alone), against the torch composition on the same materialised matrix -- matmul, max and min with their indices, compare and sum: five
@@ -154,7 +160,7 @@ and once with the Gaussian model alone (G = 1), the routes of a shape taking tur
   max_abs_difference_from_host / _from_torch   the largest difference of a log density from the composition's
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --tcopula | --tconditional | --scores |
-                                                              --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --tcondbox | --aggregates |
+                                                              --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --tcondbox | --tlead | --aggregates |
                                                               --concordance | --loglik] [--reps K]"""
 import argparse
 import ctypes as C
@@ -890,6 +896,33 @@ def tboxprob_shape(M, B, n, reps, t, dof, seeds=tuple(range(1, 9))):
                 gauss_stderr=float("%.3g" % got["g"].stderr[0]))
 
 
+def tlead_shape(M, B, n, reps, t, dof, seeds=tuple(range(1, 9))):
+    """copula_box_probabilities(dof=..., mixing="conditioned") of B copies of the box (t, inf)^M in t-score space under equicorrelation
+    1/2 against the plain t call of the same shape, the two taking turns in one process; ess / n of either from the integrand of one
+    box in a call of its own"""
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    low = np.linalg.cholesky(corr)
+    lo, hi = np.full((B, M), t), np.full((B, M), np.inf)
+    got = {}
+
+    def lead_route():
+        got["l"] = sd.copula_box_probabilities(low, lo, hi, n, seeds, dof=dof, mixing="conditioned")
+
+    def plain_route():
+        got["p"] = sd.copula_box_probabilities(low, lo, hi, n, seeds, dof=dof)
+    wall = _turns((lead_route, plain_route), reps)
+
+    def ess(**kw):
+        f = sd.copula_box_probabilities(low, lo[0], hi[0], n, seeds, dof=dof, return_integrand=True, **kw)[1][:, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return float("%.4g" % np.nanmean(f.sum(axis=1) ** 2 / (n * (f * f).sum(axis=1))))
+    return dict(M=M, B=B, n=n, R=len(seeds), threshold=round(t, 4), dof=dof, lead_ms=wall[0], plain_ms=wall[1],
+                lead_over_plain_wall=round(wall[0][1] / wall[1][1], 3), prob=float("%.6g" % got["l"].prob[0]),
+                stderr=float("%.3g" % got["l"].stderr[0]), ess_fraction=ess(mixing="conditioned"),
+                plain_prob=float("%.6g" % got["p"].prob[0]), plain_stderr=float("%.3g" % got["p"].stderr[0]), plain_ess_fraction=ess())
+
+
 def _tcond_problem(M, B, t):
     """B boxes (t, inf)^M in t-score space under equicorrelation 1/2, each with the conditional location and scale of its own given
     t score of one further component: y_O in (0, 3], mu = y_O / 2, r^2 = (nu + y_O^2) / (nu + 1) with nu filled in by the caller"""
@@ -1270,6 +1303,8 @@ def main():
                     "calls of the same shapes (DESIGN.md section 3.5.23)")
     ap.add_argument("--tcondbox", action="store_true", help="conditional_box_probabilities / conditional_box_draws (p = 1, B in {1, 64} sets) "
                     "against the t entries of the same shapes (DESIGN.md section 3.5.26)")
+    ap.add_argument("--tlead", action="store_true", help='copula_box_probabilities(dof = 3, 30, mixing="conditioned") against the plain t '
+                    "call of the same shapes: time, prob, stderr and ess / n of both (DESIGN.md section 3.5.27)")
     ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
@@ -1308,6 +1343,16 @@ def main():
             shapes = [(1, 12, 10_000), (3, 5, 1_000)]
         _lib.use_torch_stream()
         out["aggregates"] = [aggregates_shape(S, M, n, a.reps) for S, M, n in shapes]
+    elif a.tlead:
+        t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
+        shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
+        shapes += [(12, 1, 2 ** k, t6) for k in (12, 16, 20)]
+        if a.config:
+            M, n = (int(v) for v in a.config.split(","))
+            shapes = [(M, 1, n, 0.0)]
+        elif a.quick:
+            shapes = [(2, 1, 2 ** 12, 0.0), (2, 64, 2 ** 12, 0.0), (12, 3, 2 ** 12, t6)]
+        out["tlead"] = [tlead_shape(M, B, n, a.reps, t, dof) for M, B, n, t in shapes for dof in (3.0, 30.0)]
     elif a.tcondbox:
         t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
         shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
