@@ -50,7 +50,9 @@ extern "C" {
                               *    mlmc_density_sample_conditional_t_batch, mlmc_chi2_conditional_scale,
                               *    mlmc_student_t_quantile, mlmc_copula_log_density,
                               *    mlmc_copula_box_prob_tc_batch, mlmc_copula_box_draws_tc_batch,
-                              *    mlmc_copula_box_prob_tl_batch, mlmc_copula_box_draws_tl_batch */
+                              *    mlmc_copula_box_prob_tl_batch, mlmc_copula_box_draws_tl_batch,
+                              *    mlmc_copula_box_prob_pf_batch, mlmc_copula_box_prob_t_pf_batch,
+                              *    mlmc_copula_box_prob_tl_pf_batch, mlmc_copula_box_order_batch */
 
 /* basis kinds -- mlmc/moments.py: Legendre :174-229, Monomial :111-130, Fourier :133-171;
  * IDENTITY = the quantity itself (estimate_mean of a plain quantity, quantity_estimate.py:22-80);
@@ -839,6 +841,53 @@ int mlmc_copula_box_draws_tl_batch(int32_t M, const double *L, int32_t B, const 
                                    const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
                                    int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out,
                                    double *lead_out, int mem_kind);
+/* ---- the three probability entries with ONE FACTOR PER BOX -- added within 8 -----------------------------------------------
+ * mlmc_copula_box_prob_batch, _t_batch and _tl_batch with `int64_t factor_stride` (in doubles) behind L: box b reads the factor
+ * L + b * factor_stride, [M][M] row-major.  factor_stride is 0 (one factor for all boxes: the entry without _pf_, bit for bit) or
+ * at least M * M; anything else is an error of the call.  The checks of the factor run on EVERY factor and name the box.  Every
+ * other argument, every error, the chain, the tree, the staging and the split are those of the entry without _pf_: the three old
+ * entries ARE the factor_stride = 0 case of the same host body and the same kernels.  The arithmetic of a point does not know
+ * whether its factor is shared: a box with its own copy of a factor gives bit for bit what the shared call gives, and a call with B
+ * different factors gives bit for bit what B calls of one box give.  A wave owns one (seed, box), so the factor stays uniform over
+ * the wave.  The factors go to the device packed, so a caller's padding costs nothing there.  Under _tl_ the lead's L_00 is that of
+ * the box's factor.  Made for mlmc_copula_box_order_batch (one order, so one factor, per box) and for bootstrap replicates of a
+ * correlation matrix.  The draws entries and the _tc_ entries keep one shared factor. */
+int mlmc_copula_box_prob_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                  const double *shift, int32_t R, const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, int mem_kind);
+int mlmc_copula_box_prob_t_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                    double dof, int32_t R, const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first,
+                                    int64_t n, int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind);
+int mlmc_copula_box_prob_tl_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                     double dof, int32_t R, const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream,
+                                     int64_t first, int64_t n, int32_t flags, double *mean, double *f_out, double *s_out, double *lead_out,
+                                     int mem_kind);
+/* ---- Genz's variable reordering for the chain above (box_order.hip) -- added within 8 ---------------------------------------
+ * For each of B boxes a greedy pivoted Cholesky factorisation of a covariance that puts the component with the smallest expected
+ * conditional width first (Genz 1992; Gibson, Glasbey and Elston 1994): the chain of mlmc_copula_box_prob_pf_batch on the permuted
+ * problem has the same expectation and, for heterogeneous limits under correlation, a far smaller variance.  All arrays host.
+ *   C [M][M] row-major, symmetric positive definite, finite; box b reads C + b * cov_stride, cov_stride 0 (shared) or >= M * M.
+ *     Column c of the symmetric matrix is read as row c.  1 <= M <= MLMC_BOX_PROB_MAX_M.
+ *   lo, hi [B][M] (+-inf allowed, no NaN); shift [B][M] finite or NULL; first [B] int32 or NULL: a component forced to lead, -1: free.
+ *   perm [B][M] int32: perm[b][i] = the original component at position i.  L_out [B][M][M]: the lower-triangular factor of the
+ *     permuted covariance C[perm][:, perm], zeros above the diagonal.  ok [B] int32: 0 where a pivot was not positive and finite
+ *     (perm is then still a permutation; L_out is not a factor).
+ * With v_j = C_jj and s_j = +0 at the start, step i = 0 .. M-1, every operation ONE fp64 operation rounded to nearest (no FMA), for
+ * every component j that remains:
+ *     lt = lo_j - shift_j, ht = hi_j - shift_j (without a shift: the limits);  r = sqrt(v_j);  a = (lt - s_j) / r,  b = (ht - s_j) / r
+ *     if a > 0:  d = normcdf(-b), e = normcdf(-a);  else  d = normcdf(a), e = normcdf(b);     w_j = e - d if lo_j < hi_j, else 0
+ *   the component c with the smallest w is taken (a NaN width counts as +inf; ties go to the lowest ORIGINAL index; at step 0
+ *   first[b] >= 0 wins): perm[i] = c, L_ii = r_c, a pivot v_c that is not positive and finite clears ok, and
+ *     y_i = (phi(a) - phi(b)) / w,  phi(x) = exp(-0.5 * (x * x)) * 0.3989422804014327
+ *   or, where w is 0 or not finite or y is NaN, the box edge nearer to 0: a if a > 0, b if b < 0, else 0.  Every other remaining j:
+ *     acc = +0, then for k = 0 .. i-1 ascending  acc = acc + (L_jk * L_ck);   L_ji = (C[c][j] - acc) / L_ii
+ *     v_j = v_j - (L_ji * L_ji);   s_j = s_j + (L_ji * y_i)
+ * One workgroup per box, a thread per component that never moves (perm records positions; nothing is swapped), the partial rows
+ * in a global workspace laid out [k][component]; bitwise repeatable; the result of a box does not depend on B, on its position or
+ * on whether its covariance is shared.  Errors: M < 1 or above the cap, B < 1, a null array, a bad cov_stride, an entry of C that
+ * is not finite, a NaN limit, a shift that is not finite, first outside -1 .. M-1 (each names the box).  One host wait. */
+int mlmc_copula_box_order_batch(int32_t M, const double *C, int64_t cov_stride, int32_t B, const double *lo, const double *hi,
+                                const double *shift, const int32_t *first, int32_t *perm, double *L_out, int32_t *ok);
 
 /* ---- aggregates of joint scenarios (scenario.hip) -- added within 8 ----------------------------------------------------
  * Functions of the M components of one scenario, once per scenario column.  x [S][M][ld]: S >= 1 sets of M >= 1 component rows,

@@ -142,6 +142,13 @@ SIGNATURES = {
                                                 C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int]),
     "mlmc_copula_box_draws_tl_batch": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_double, C.c_int32, _vp, _vp, C.c_uint32, C.c_int64,
                                                  C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_copula_box_prob_pf_batch": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int64,
+                                                C.c_int64, C.c_int32, _vp, _vp, C.c_int]),
+    "mlmc_copula_box_prob_t_pf_batch": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_double, C.c_int32, _vp, _vp,
+                                                  C.c_uint32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int]),
+    "mlmc_copula_box_prob_tl_pf_batch": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_double, C.c_int32, _vp, _vp,
+                                                   C.c_uint32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int]),
+    "mlmc_copula_box_order_batch": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mlmc_scenario_aggregates": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                            _vp, C.c_int64, C.c_int]),
     "mlmc_rows_weighted_sums": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp,

@@ -27,6 +27,9 @@
 //                (copula_t.hip) has made the lead score v and the scale sc per (seed, box, point); the chain starts at i = 1 with
 //                y_0 = v / sc and the finished product of widths is multiplied by the lead's weight W0 of the box.  Again no t
 //                function is called from the chain.
+//                The _pf_ entries (one factor PER BOX, for Genz's variable reordering of box_order.hip and for bootstrap replicates) are
+//                the same instances: the kernel adds b * fstride to L, fstride = 0 for every other entry.  b is blockIdx.y, so the
+//                factor stays uniform over the wave and on the scalar unit; no operation of a point knows whether its factor is shared.
 //   k_box_mean : one workgroup per (seed, box) sums the partials of its blocks in a fixed tree and divides by n.
 // The tree: lanes outside [first, first + n) add +0; the wave adds v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; thread t of
 // k_box_mean adds the partials t, t + 256, ... in ascending order from 0 and the 256 sums fold by halves (128, 64, ... 1).  It is
@@ -89,10 +92,12 @@ __global__ __launch_bounds__(BOX_LANES) void k_box_prob(int M, const double *__r
                                                         int64_t blk0, int64_t call_blk0, int64_t call_blocks,
                                                         double *__restrict__ partials, double *__restrict__ f_out, int64_t ldf,
                                                         int64_t c_off, double *__restrict__ z_out, double *__restrict__ u_out,
-                                                        const double *__restrict__ mix, const double *__restrict__ scl) {
+                                                        const double *__restrict__ mix, const double *__restrict__ scl,
+                                                        int64_t fstride) {
     extern __shared__ double ys[];                     // y[k][lane]
     const int lane = threadIdx.x;
     const int b = b0 + (int)blockIdx.y, r = r0 + (int)blockIdx.z;
+    L += (int64_t)b * fstride;                         // the box's own factor (the _pf_ entries); uniform over the wave as before
     const int64_t a = blk0 + blockIdx.x;
     const int64_t j = (a << 6) | lane;
     const bool active = j >= first && j < first + n;
@@ -187,7 +192,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                     const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean, double *f_out,
                     int mem_kind, bool draws = false, double *z_out = nullptr, double *u_out = nullptr, const double *dof = nullptr,
                     uint32_t mix_stream = 0, double *s_out = nullptr, const double *dof_mix = nullptr, const double *scale = nullptr,
-                    bool lead = false, double *lead_out = nullptr) {
+                    bool lead = false, double *lead_out = nullptr, int64_t factor_stride = 0) {
     const std::string e(fn);
     const bool tcop = dof != nullptr;                  // the t entries: *dof degrees of freedom, the mixing stream, s_out [R][n] or NULL
     // the tc entries: a conditional law, *dof_mix degrees of freedom of the mixing variable, shift [B][M] or NULL, scale [B] or NULL
@@ -209,13 +214,22 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     if (n < 1) return fail(e + ": n < 1");
     if (first < 0) return fail(e + ": first < 0");
     if (first > SOBOL_MAX_INDEX - n) return fail(e + ": first + n is beyond 2^52");
-    for (int i = 0; i < M; ++i) {
-        const double dg = L[(size_t)i * M + i];
-        if (!std::isfinite(dg) || !(dg > 0.0))
-            return fail(e + ": factor row " + std::to_string(i) + ": the diagonal entry must be finite and positive");
-        for (int k = 0; k < i; ++k)
-            if (!std::isfinite(L[(size_t)i * M + k]))
-                return fail(e + ": factor row " + std::to_string(i) + ": entry " + std::to_string(k) + " is not finite");
+    // the _pf_ entries: box b reads the factor L + b * factor_stride (0: all boxes share one); every factor is checked
+    if (factor_stride != 0 && factor_stride < (int64_t)M * M)
+        return fail(e + ": factor_stride = " + std::to_string(factor_stride) + " must be 0 (one shared factor) or at least M * M = " +
+                    std::to_string((int64_t)M * M));
+    const int nf = factor_stride ? B : 1;
+    for (int g = 0; g < nf; ++g) {
+        const double *Lg = L + (size_t)g * (size_t)factor_stride;
+        const std::string at = factor_stride ? ": box " + std::to_string(g) + ", factor row " : ": factor row ";
+        for (int i = 0; i < M; ++i) {
+            const double dg = Lg[(size_t)i * M + i];
+            if (!std::isfinite(dg) || !(dg > 0.0))
+                return fail(e + at + std::to_string(i) + ": the diagonal entry must be finite and positive");
+            for (int k = 0; k < i; ++k)
+                if (!std::isfinite(Lg[(size_t)i * M + k]))
+                    return fail(e + at + std::to_string(i) + ": entry " + std::to_string(k) + " is not finite");
+        }
     }
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < M; ++i) {
@@ -289,12 +303,13 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const int64_t ldf = stage ? lb * BOX_LANES : n;
 
     // what goes up: L | lo | hi | shift | scale | seeds | tables | coordinates (uint32)
-    const size_t nL = (size_t)M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nd + 1) / 2;
+    // (the factors go up packed: M * M doubles apart on the device whatever the caller's stride)
+    const size_t nL = (size_t)nf * M * M, nbx = (size_t)B * M, nsh = shift ? nbx : 0, ntab = tables.size(), nco = ((size_t)nd + 1) / 2;
     const size_t nsc = tcond && scale ? (size_t)B : 0;
     const size_t n_in = nL + 2 * nbx + nsh + nsc + (size_t)R + ntab + nco;
     std::vector<double> packed(n_in);
     double *q = packed.data();
-    std::memcpy(q, L, sizeof(double) * nL), q += nL;
+    for (int g = 0; g < nf; ++g) std::memcpy(q, L + (size_t)g * (size_t)factor_stride, sizeof(double) * (size_t)M * M), q += (size_t)M * M;
     std::memcpy(q, lo, sizeof(double) * nbx), q += nbx;
     std::memcpy(q, hi, sizeof(double) * nbx), q += nbx;
     if (nsh) std::memcpy(q, shift, sizeof(double) * nsh), q += nsh;
@@ -327,6 +342,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const uint64_t *d_seeds = (const uint64_t *)(d_hi + nbx + nsh + nsc), *d_tab = d_seeds + R;
     const uint32_t *d_coord = (const uint32_t *)(d_tab + ntab);
 
+    const int64_t d_fstride = factor_stride ? (int64_t)M * M : 0;
     const size_t lds = sizeof(double) * BOX_LANES * (size_t)(M - 1);
     const auto kernel = lead  ? (draws ? (sobol ? k_box_prob<true, true, true, false, true> : k_box_prob<false, true, true, false, true>)
                                        : (sobol ? k_box_prob<true, false, true, false, true> : k_box_prob<false, false, true, false, true>))
@@ -340,7 +356,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
     const TCopConst tconst = tcop ? tcop_constants(*dof) : TCopConst{};
     const TCopConst tmix = tcond ? tcop_constants(*dof_mix) : lead ? tcop_constants(*dof + 1.0) : tconst;
     // the lead's weight of every box, once per call
-    if (lead) cop_launch_box_lead_weights(st, tconst, (int)M, d_L, d_lo, d_hi, (int)B, d_w);
+    if (lead) cop_launch_box_lead_weights(st, tconst, (int)M, d_L, d_fstride, d_lo, d_hi, (int)B, d_w);
     for (int64_t k0 = 0; k0 < call_blocks; k0 += lb) {
         const int64_t kb = std::min(lb, call_blocks - k0);
         // the first point of the launch within the call: column 0 of the staged integrand
@@ -352,7 +368,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
             cop_launch_box_mixing(st, tmix, R, d_seeds, coord[nc], sobol ? d_tab : nullptr, table_rows, j0, kb * BOX_LANES, first, n, d_s);
             if (lead) {
                 // v and sc of the launch's blocks for every pair: [R * B][64 kb], from the scales g0 [R][64 kb] just made
-                cop_launch_box_lead(st, tconst, (int)M, d_L, d_lo, d_hi, (int)B, R, d_seeds, coord[0], sobol ? d_tab : nullptr, table_rows, j0,
+                cop_launch_box_lead(st, tconst, (int)M, d_L, d_fstride, d_lo, d_hi, (int)B, R, d_seeds, coord[0], sobol ? d_tab : nullptr, table_rows, j0,
                                     kb * BOX_LANES, first, n, d_s, d_w, d_v, d_sc);
                 const hipMemcpyKind kind = mem_kind == MLMC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
                 if (s_out)
@@ -374,7 +390,7 @@ static int box_prob(const char *fn, int32_t M, const double *L, int32_t B, const
                 hipLaunchKernelGGL(kernel, grid, dim3(BOX_LANES), lds, st, (int)M, d_L, d_lo, d_hi, lead ? (const double *)d_w : d_shift, (int)B,
                                    b0, d_seeds, r0, d_coord, d_tab, table_rows, first, n, call_blk0 + k0, call_blk0, call_blocks, d_part,
                                    d_f, ldf, stage ? c_lo : (int64_t)0, d_z, d_u, (const double *)(lead ? d_sc : d_s),
-                                   lead ? (const double *)d_v : d_scale);
+                                   lead ? (const double *)d_v : d_scale, d_fstride);
             }
         // the CDF pass of the t draws: the rows of u hold the t scores of the launch's columns and are mapped in place
         if (tcop && u_out) cop_launch_t_map(st, tconst, (int)urows, c_hi - c_lo, d_u + (stage ? 0 : c_lo), ldf);
@@ -411,6 +427,14 @@ int mlmc_copula_box_prob_batch(int32_t M, const double *L, int32_t B, const doub
     return box_prob("mlmc_copula_box_prob_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind);
 }
 
+int mlmc_copula_box_prob_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                  const double *shift, int32_t R, const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n,
+                                  int32_t flags, double *mean, double *f_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_pf_batch", M, L, B, lo, hi, shift, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, false,
+                    nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, false, nullptr, factor_stride);
+}
+
 int mlmc_copula_box_draws_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, const double *shift, int32_t R,
                                 const uint64_t *seeds, const uint32_t *streams, int64_t first, int64_t n, int32_t flags, double *mean,
                                 double *f_out, double *z_out, double *u_out, int mem_kind) {
@@ -427,6 +451,14 @@ int mlmc_copula_box_prob_t_batch(int32_t M, const double *L, int32_t B, const do
                     nullptr, nullptr, &dof, mix_stream, s_out);
 }
 
+int mlmc_copula_box_prob_t_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                    double dof, int32_t R, const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first,
+                                    int64_t n, int32_t flags, double *mean, double *f_out, double *s_out, int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_t_pf_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind,
+                    false, nullptr, nullptr, &dof, mix_stream, s_out, nullptr, nullptr, false, nullptr, factor_stride);
+}
+
 int mlmc_copula_box_draws_t_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,
                                   const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream, int64_t first, int64_t n,
                                   int32_t flags, double *mean, double *f_out, double *z_out, double *u_out, double *s_out, int mem_kind) {
@@ -441,6 +473,15 @@ int mlmc_copula_box_prob_tl_batch(int32_t M, const double *L, int32_t B, const d
     MLMC_API_GUARD;
     return box_prob("mlmc_copula_box_prob_tl_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind, false,
                     nullptr, nullptr, &dof, mix_stream, s_out, nullptr, nullptr, true, lead_out);
+}
+
+int mlmc_copula_box_prob_tl_pf_batch(int32_t M, const double *L, int64_t factor_stride, int32_t B, const double *lo, const double *hi,
+                                     double dof, int32_t R, const uint64_t *seeds, const uint32_t *streams, uint32_t mix_stream,
+                                     int64_t first, int64_t n, int32_t flags, double *mean, double *f_out, double *s_out, double *lead_out,
+                                     int mem_kind) {
+    MLMC_API_GUARD;
+    return box_prob("mlmc_copula_box_prob_tl_pf_batch", M, L, B, lo, hi, nullptr, R, seeds, streams, first, n, flags, mean, f_out, mem_kind,
+                    false, nullptr, nullptr, &dof, mix_stream, s_out, nullptr, nullptr, true, lead_out, factor_stride);
 }
 
 int mlmc_copula_box_draws_tl_batch(int32_t M, const double *L, int32_t B, const double *lo, const double *hi, double dof, int32_t R,

@@ -59,14 +59,15 @@ void cop_launch_mixing(hipStream_t st, const TCopConst &C, uint64_t seed, uint32
 void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint64_t *seeds, uint32_t stream, const uint64_t *table,
                            int table_rows, int64_t j0, int64_t ncols, int64_t first, int64_t n, double *s);
 // the lead component of the tl box entries (k_box_lead_weights): w[b] = W0 = T(hi[b][0] / L_00) - T(lo[b][0] / L_00) through the lower
-// tail on either side (0 for an empty lead), w[B + b] = the lower end d of the interval of p; L, lo [B][M], hi, w [2 B]: device
-void cop_launch_box_lead_weights(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B,
-                                 double *w);
+// tail on either side (0 for an empty lead), w[B + b] = the lower end d of the interval of p; L, lo [B][M], hi, w [2 B]: device.
+// L_00 of box b is L[b * fstride]: fstride = 0 for one shared factor, the distance of the boxes' factors otherwise (here and below)
+void cop_launch_box_lead_weights(hipStream_t st, const TCopConst &C, int M, const double *L, int64_t fstride, const double *lo,
+                                 const double *hi, int B, double *w);
 // v[(r * B + b) * ncols + c] = the lead score of point j0 + c under seeds[r] in box b, sc[...] = g0[r * ncols + c] (x)
 // sqrt((nu + v v) / (nu + 1)) (k_box_lead); v = 0 and sc = 1 for a point outside [first, first + n).  C: the constants of nu; g0: the
 // scales of cop_launch_box_mixing with those of nu + 1; `stream` / `table` as there; all device
-void cop_launch_box_lead(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B, int R,
-                         const uint64_t *seeds, uint32_t stream, const uint64_t *table, int table_rows, int64_t j0, int64_t ncols,
+void cop_launch_box_lead(hipStream_t st, const TCopConst &C, int M, const double *L, int64_t fstride, const double *lo, const double *hi,
+                         int B, int R, const uint64_t *seeds, uint32_t stream, const uint64_t *table, int table_rows, int64_t j0, int64_t ncols,
                          int64_t first, int64_t n, const double *g0, const double *w, double *v, double *sc);
 // U[m * ldu + c] = (sum_k F[m * K + k] Z[k * ldz + c]) (x) s[c], m < M, c < ncols (k_cop_uniforms, the TSCALE instance): the sum as
 // above, then one rounded multiplication; all device

@@ -299,13 +299,14 @@ __global__ __launch_bounds__(TC_THREADS) void k_box_mixing(TCopConst C, const ui
 
 // The lead component of the tl box entries (box_prob.hip).  With a = lo[b][0] / L_00 and bq = hi[b][0] / L_00 the
 // lead score V = Y_0 / L_00 is Student-t with nu degrees of freedom: w[b] = W0 = T(bq) - T(a) through the lower tail on either
-// side, w[B + b] = d, the lower end of the interval of p.  One thread per box, once per call.
-__global__ __launch_bounds__(TC_THREADS) void k_box_lead_weights(TCopConst C, int M, const double *__restrict__ L,
+// side, w[B + b] = d, the lower end of the interval of p.  One thread per box, once per call.  L_00 of box b is L[b * fstride]
+// (fstride = 0: one factor for all boxes).
+__global__ __launch_bounds__(TC_THREADS) void k_box_lead_weights(TCopConst C, int M, const double *__restrict__ L, int64_t fstride,
                                                                  const double *__restrict__ lo, const double *__restrict__ hi, int B,
                                                                  double *__restrict__ w) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const double l00 = L[0], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
+    const double l00 = L[(int64_t)b * fstride], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
     const bool refl = a > 0.0;
     const double d = student_t_cdf(C, refl ? -bq : a), e = student_t_cdf(C, refl ? -a : bq);
     w[b] = a < bq ? e - d : 0.0;
@@ -318,8 +319,8 @@ __global__ __launch_bounds__(TC_THREADS) void k_box_lead_weights(TCopConst C, in
 //   p = min(max(d + w W0, 2^-1022), 1 - 2^-53), v = T^-1(p) (negated for an upper-tail lead), clamped to [a, bq] and to +-2^500;
 //   sc = g0 sqrt((nu + v v) / (nu + 1)).
 // W0, d, a and bq are uniform over a wave (scalar loads); v and sc are not.  Points outside [first, first + n) pad with v = 0, sc = 1.
-__global__ __launch_bounds__(TC_THREADS) void k_box_lead(TCopConst C, int M, const double *__restrict__ L, const double *__restrict__ lo,
-                                                         const double *__restrict__ hi, int B, int64_t pair0,
+__global__ __launch_bounds__(TC_THREADS) void k_box_lead(TCopConst C, int M, const double *__restrict__ L, int64_t fstride,
+                                                         const double *__restrict__ lo, const double *__restrict__ hi, int B, int64_t pair0,
                                                          const uint64_t *__restrict__ seeds, uint32_t stream,
                                                          const uint64_t *__restrict__ table, int table_rows, int64_t j0, int64_t ncols,
                                                          int64_t first, int64_t n, const double *__restrict__ g0,
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(TC_THREADS) void k_box_lead(TCopConst C, int M, con
     const int64_t j = j0 + c;
     double v = 0.0, sc = 1.0;
     if (j >= first && j < first + n) {
-        const double l00 = L[0], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
+        const double l00 = L[(int64_t)b * fstride], a = lo[(int64_t)b * M] / l00, bq = hi[(int64_t)b * M] / l00;
         const bool refl = a > 0.0;
         const double u = table ? sobol_unit(sobol_point(table + ((int64_t)r * table_rows + stream) * SOBOL_ROW, (uint64_t)j))
                                : q_uniform(seeds[r], stream, (uint64_t)j);
@@ -389,19 +390,19 @@ void cop_launch_box_mixing(hipStream_t st, const TCopConst &C, int R, const uint
                            s + (int64_t)r0 * ncols);
 }
 
-void cop_launch_box_lead_weights(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B,
-                                 double *w) {
-    hipLaunchKernelGGL(k_box_lead_weights, dim3((unsigned)((B + TC_THREADS - 1) / TC_THREADS)), dim3(TC_THREADS), 0, st, C, M, L, lo, hi, B, w);
+void cop_launch_box_lead_weights(hipStream_t st, const TCopConst &C, int M, const double *L, int64_t fstride, const double *lo,
+                                 const double *hi, int B, double *w) {
+    hipLaunchKernelGGL(k_box_lead_weights, dim3((unsigned)((B + TC_THREADS - 1) / TC_THREADS)), dim3(TC_THREADS), 0, st, C, M, L, fstride, lo, hi, B, w);
 }
 
-void cop_launch_box_lead(hipStream_t st, const TCopConst &C, int M, const double *L, const double *lo, const double *hi, int B, int R,
-                         const uint64_t *seeds, uint32_t stream, const uint64_t *table, int table_rows, int64_t j0, int64_t ncols,
+void cop_launch_box_lead(hipStream_t st, const TCopConst &C, int M, const double *L, int64_t fstride, const double *lo, const double *hi,
+                         int B, int R, const uint64_t *seeds, uint32_t stream, const uint64_t *table, int table_rows, int64_t j0, int64_t ncols,
                          int64_t first, int64_t n, const double *g0, const double *w, double *v, double *sc) {
     // pair of a launch = blockIdx.y: more pairs than a grid has in y go in several launches
     const int64_t pairs = (int64_t)R * B;
     for (int64_t p0 = 0; p0 < pairs; p0 += 65535)
         hipLaunchKernelGGL(k_box_lead, dim3((unsigned)((ncols + TC_THREADS - 1) / TC_THREADS), (unsigned)std::min<int64_t>(pairs - p0, 65535)),
-                           dim3(TC_THREADS), 0, st, C, M, L, lo, hi, B, p0, seeds, stream, table, table_rows, j0, ncols, first, n, g0, w, v,
+                           dim3(TC_THREADS), 0, st, C, M, L, fstride, lo, hi, B, p0, seeds, stream, table, table_rows, j0, ncols, first, n, g0, w, v,
                            sc);
 }
 

@@ -719,17 +719,23 @@ class Estimate:
 
     def bootstrap_joint_probability(self, lower, upper, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
                                     seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
-                                    orth_moments_tol=1e-4, moments_fns=None, dof=None):
+                                    orth_moments_tol=1e-4, moments_fns=None, dof=None, order="natural"):
         """Bootstrap confidence bands of estimate_joint_probability: how far the probability of a box moves when the stored samples
         are resampled.  The `stderr` of estimate_joint_probability is the quasi-Monte Carlo integration error alone; the band here
         is the sampling uncertainty of the correlation matrix (and, on request, of the marginals) pushed through the box integral.
 
         Replicate b is joint_probabilities(distrs_b, lower, upper, n, seeds, corr=corr_b) with corr_b replicate b of
-        est_bootstrap_component_covariance(seed=seed): one call per replicate, with the SAME quasi-Monte Carlo seeds for all, so
-        the integration error is largely common to the replicates and does not widen the band.
-        :param marginals: "fixed": distrs_b are the estimate's densities, only the dependence is resampled.  "resampled":
+        est_bootstrap_component_covariance(seed=seed), with the SAME quasi-Monte Carlo seeds for all, so the integration error is
+        largely common to the replicates and does not widen the band.
+        :param marginals: "fixed": distrs_b are the estimate's densities, only the dependence is resampled.  The estimate and all
+            replicates are then the boxes of ONE device call with one factor per box
+            (tool.simple_distribution.joint_probabilities_over_correlations): the limit scores are shared, replicate b brings the
+            factor of corr_b.  Every number is bit for bit that of one call per replicate.  "resampled":
             distrs_b are replicate b's maximum-entropy densities, the replicate densities of bootstrap_component_quantiles with
-            the same seed and sample_vector -- the same picks, so replicate b is one coherent resample of marginals and dependence
+            the same seed and sample_vector -- the same picks, so replicate b is one coherent resample of marginals and dependence.
+            This keeps one call per replicate: the limit scores and the set of constrained components differ between replicates
+        :param order: "natural" (default) or "genz": Genz's variable reordering of every (replicate, box) pair, as in
+            estimate_joint_probability
         :param corr: None (Pearson) or "scores"; a matrix is an error (nothing to resample)
         :param n, seeds: as in estimate_joint_probability (smaller default n: there are n_subsamples + 1 integrals)
         :param dof: as in estimate_joint_probability: the Student-t copula with that many degrees of freedom.  The degrees of
@@ -746,6 +752,7 @@ class Estimate:
         what = "bootstrap_joint_probability"
         level = _check_level(what, level)
         dof = simple_distribution._check_dof(what, dof)
+        simple_distribution._check_order(what, order)
         if marginals not in ("fixed", "resampled"):
             raise ValueError("{}: marginals must be 'fixed' or 'resampled', got {!r}".format(what, marginals))
         self._resampled_corr_arg(what, corr)
@@ -764,7 +771,23 @@ class Estimate:
             raise ValueError("{}: {} densities for {} components".format(what, len(densities), M))
         corr0, _ = self._copula_correlation(what, corr, densities, tol, reg_param, orth_moments_tol, moments_fns)
         distrs = [d[0] for d in densities]
-        base = simple_distribution.joint_probabilities(distrs, lower, upper, n, seeds, corr=corr0, dof=dof)
+        if marginals == "fixed":
+            # the estimate and the ok replicates: the boxes of one device call, one factor per box
+            reps = self.est_bootstrap_component_covariance(B, k, seed, corr=corr, densities=densities)
+            ok = reps.ok.copy()
+            at = np.flatnonzero(ok)
+            corrs = np.concatenate([np.asarray(corr0, dtype=np.float64)[None], reps.corr[at]], axis=0)
+            results, fine = simple_distribution.joint_probabilities_over_correlations(distrs, lower, upper, n, seeds, corrs, dof=dof,
+                                                                                      order=order)
+            base = results[0]
+            replicates = np.full((B, np.size(base.prob)), np.nan)
+            ok[at[~fine[1:]]] = False
+            for b, res in zip(at, results[1:]):
+                if res is not None:
+                    replicates[b] = res.prob
+            lo, hi = _band_over_ok(replicates, ok, level)
+            return ProbabilityBands(np.asarray(base.prob), np.asarray(base.stderr), lo, hi, replicates, ok, int(np.sum(ok)), seed)
+        base = simple_distribution.joint_probabilities(distrs, lower, upper, n, seeds, corr=corr0, dof=dof, order=order)
         reps = self.est_bootstrap_component_covariance(B, k, seed, corr=corr, densities=densities)
         ok = reps.ok.copy()
         rep_distrs, success = None, None
@@ -780,7 +803,8 @@ class Estimate:
                 continue
             d_b = distrs if rep_distrs is None else rep_distrs[b * M:(b + 1) * M]
             try:
-                replicates[b] = simple_distribution.joint_probabilities(d_b, lower, upper, n, seeds, corr=reps.corr[b], dof=dof).prob
+                replicates[b] = simple_distribution.joint_probabilities(d_b, lower, upper, n, seeds, corr=reps.corr[b], dof=dof,
+                                                                        order=order).prob
             except Exception:
                 ok[b] = False
         lo, hi = _band_over_ok(replicates, ok, level)
@@ -788,12 +812,13 @@ class Estimate:
 
     def bootstrap_joint_exceedance(self, thresholds, n_subsamples=100, sample_vector=None, seed=None, level=0.9, n=2 ** 12,
                                    seeds=tuple(range(8)), corr=None, marginals="fixed", densities=None, tol=1e-8, reg_param=0.0,
-                                   orth_moments_tol=1e-4, moments_fns=None, dof=None):
+                                   orth_moments_tol=1e-4, moments_fns=None, dof=None, order="natural"):
         """P(X_m > t_m for all constrained m) with its bootstrap band: `bootstrap_joint_probability` with lower = thresholds and
         upper = +inf.
         :param thresholds: broadcast to [n_boxes, M]; -inf leaves a component unconstrained
         :param dof: the Student-t copula, its degrees of freedom held fixed over the replicates (bootstrap_joint_probability); the
             band keeps PLAIN mixing, as there
+        :param order: as in bootstrap_joint_probability
         :return: as bootstrap_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
@@ -801,7 +826,7 @@ class Estimate:
         return self.bootstrap_joint_probability(t, np.inf, n_subsamples=n_subsamples, sample_vector=sample_vector, seed=seed,
                                                 level=level, n=n, seeds=seeds, corr=corr, marginals=marginals, densities=densities,
                                                 tol=tol, reg_param=reg_param, orth_moments_tol=orth_moments_tol, moments_fns=moments_fns,
-                                                dof=dof)
+                                                dof=dof, order=order)
 
     def bs_target_var_n_estimated(self, target_var, sample_vec=None, *, batch=False, seed=None):
         """batch=True: the 300 replicates come from est_bootstrap_batch(300, sample_vec, seed=seed)."""
@@ -1127,7 +1152,8 @@ class Estimate:
         return draws, success, cond[2]
 
     def estimate_joint_probability(self, lower, upper, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain"):
+                                   orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain",
+                                   order="natural"):
         """Probability that the components lie in a box AT ONCE, P(lower_m < X_m < upper_m for all m), under the marginals and the
         Gaussian copula of `sample_joint`, for B boxes in one batched device call (tool.simple_distribution.joint_probabilities):
         Genz's separation of variables on scrambled Sobol' points.  Its error is relative and falls like 1 / n, so the small
@@ -1154,13 +1180,18 @@ class Estimate:
             that draw (tool.simple_distribution.joint_probabilities / event_samples), so the relative error holds at any depth of
             the box.  Plain mixing returns a number that is orders of magnitude too small, with a `stderr` that does not show it,
             once only a rare mixing scale reaches the box (marginal levels of 1e-6 at dof = 3)
+        :param order: "natural" (default, bit for bit as before): the chain integrates the constrained components in their own
+            order.  "genz": Genz's variable reordering of every box on the device (tool.simple_distribution.box_order), still one
+            chain call: the same probability with a `stderr` that is orders of magnitude smaller where the limits differ much
+            between correlated components.  Independent components gain nothing
         :return: (JointProbability(prob [B], stderr [B], replicates [R, B], n, seeds), success [M])"""
         from .tool import simple_distribution
         what = "estimate_joint_probability"
         dof = simple_distribution._box_dof(what, dof, None, given)
         simple_distribution._check_mixing(what, mixing, dof, None, given)
+        simple_distribution._check_order(what, order)
         return self._joint_probability(what, simple_distribution.joint_probabilities, lower, upper, n, seeds, corr, given, tol, reg_param,
-                                       orth_moments_tol, moments_fns, densities, first, qmc, dof, mixing)
+                                       orth_moments_tol, moments_fns, densities, first, qmc, dof, mixing, order)
 
     def estimate_conditional_probability(self, lower, upper, given, n=2 ** 14, seeds=tuple(range(8)), corr=None, tol=1e-8, reg_param=0.0,
                                          orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None):
@@ -1187,7 +1218,7 @@ class Estimate:
                                        densities, first, qmc, nu)
 
     def _joint_probability(self, what, entry, lower, upper, n, seeds, corr, given, tol, reg_param, orth_moments_tol, moments_fns,
-                           densities, first, qmc, dof, mixing="plain"):
+                           densities, first, qmc, dof, mixing="plain", order="natural"):
         """the one body of estimate_joint_probability and estimate_conditional_probability; dof and mixing checked by the caller
         (mixing goes to the entry only where it is not "plain": the conditional entry has no such keyword)"""
         from .tool import simple_distribution
@@ -1198,6 +1229,8 @@ class Estimate:
         if densities is None:
             densities = self.construct_densities(tol, reg_param, orth_moments_tol, moments_fns)
         more = {} if mixing == "plain" else {"mixing": mixing}
+        if order != "natural":
+            more["order"] = order
         result = entry([d[0] for d in densities], lower, upper, n=n, seeds=[int(s) for s in seeds], corr=corr, given=given, first=first,
                        qmc=qmc, dof=dof, **more)
         success = np.array([bool(d[2].success) for d in densities], dtype=bool)
@@ -1217,18 +1250,20 @@ class Estimate:
                                                      first=first, qmc=qmc, dof=dof)
 
     def estimate_joint_exceedance(self, thresholds, n=2 ** 14, seeds=tuple(range(8)), corr=None, given=None, tol=1e-8, reg_param=0.0,
-                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain"):
+                                  orth_moments_tol=1e-4, moments_fns=None, densities=None, first=0, qmc=True, dof=None, mixing="plain",
+                                  order="natural"):
         """P(X_m > t_m for all constrained m): `estimate_joint_probability` with lower = thresholds and upper = +inf.
         :param thresholds: broadcast to [B, M]; -inf leaves a component unconstrained
         :param dof: the Student-t copula, as in estimate_joint_probability
         :param mixing: as in estimate_joint_probability; with dof and thresholds in the far tail use mixing="conditioned"
+        :param order: as in estimate_joint_probability; "genz" pays where the thresholds differ much between correlated components
         :return: as estimate_joint_probability"""
         t = np.asarray(thresholds, dtype=np.float64)
         if np.any(np.isnan(t)):
             raise ValueError("estimate_joint_exceedance: a threshold is NaN (use -inf for a component without a threshold)")
         return self.estimate_joint_probability(t, np.inf, n=n, seeds=seeds, corr=corr, given=given, tol=tol, reg_param=reg_param,
                                                orth_moments_tol=orth_moments_tol, moments_fns=moments_fns, densities=densities,
-                                               first=first, qmc=qmc, dof=dof, mixing=mixing)
+                                               first=first, qmc=qmc, dof=dof, mixing=mixing, order=order)
 
     def estimate_tail_dependence(self, probs=(0.9, 0.95, 0.99), tail="upper", corr=None, densities=None, tol=1e-8, reg_param=0.0,
                                  orth_moments_tol=1e-4, moments_fns=None, dof=None):

@@ -1051,11 +1051,15 @@ def _box_streams(what, streams, M, qmc):
     return st
 
 
-def _box_problem(what, factor, lower, upper, shift):
-    """(factor [M, M] lower triangular, lo [B, M], hi [B, M], shift [B, M] or None) of a call in score space, checked"""
+def _box_problem(what, factor, lower, upper, shift, per_box=False):
+    """(factor [M, M] lower triangular, lo [B, M], hi [B, M], shift [B, M] or None) of a call in score space, checked; with
+    per_box a factor [B, M, M], one per box, is accepted too (one box of limits then pairs with every factor)"""
     f = np.array(factor, dtype=np.float64)
+    if per_box and f.ndim == 3:
+        return _box_problem_per_box(what, f, lower, upper, shift)
     if f.ndim != 2 or f.shape[0] != f.shape[1] or f.shape[0] < 1:
-        raise ValueError(what + ": the factor must be a square matrix, got shape {}".format(f.shape))
+        raise ValueError(what + ": the factor must be a square matrix{}, got shape {}".format(
+            " [M, M] or one per box [B, M, M]" if per_box else "", f.shape))
     M = f.shape[0]
     if M > _lib.BOX_PROB_MAX_M:
         raise ValueError(what + ": {} components exceed the cap of {}".format(M, _lib.BOX_PROB_MAX_M))
@@ -1068,7 +1072,36 @@ def _box_problem(what, factor, lower, upper, shift):
     if not np.all(np.isfinite(f)):
         raise ValueError(what + ": factor row {} has an entry that is not finite".format(int(np.argwhere(~np.isfinite(f))[0, 0])))
     lo, hi = _box_limits(what, lower, upper, M)
-    B = lo.shape[0]
+    return (f,) + _box_shift(what, lo, hi, shift)
+
+
+def _box_problem_per_box(what, f, lower, upper, shift):
+    """`_box_problem` for one factor per box, f [B, M, M]: the same checks on every factor, the errors name the box"""
+    if f.shape[1] != f.shape[2] or f.shape[0] < 1 or f.shape[1] < 1:
+        raise ValueError(what + ": the factors must be [B, M, M] with B >= 1 and M >= 1, got shape {}".format(f.shape))
+    B, M = f.shape[0], f.shape[1]
+    if M > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} components exceed the cap of {}".format(M, _lib.BOX_PROB_MAX_M))
+    f = np.ascontiguousarray(np.tril(f))
+    diag = np.diagonal(f, axis1=1, axis2=2)
+    bad = np.argwhere(~(np.isfinite(diag) & (diag > 0)))
+    if bad.size:
+        raise ValueError(what + ": box {}: the diagonal entry of factor row {} must be finite and positive, got {}".format(
+            int(bad[0, 0]), int(bad[0, 1]), diag[bad[0, 0], bad[0, 1]]))
+    bad = np.argwhere(~np.isfinite(f))
+    if bad.size:
+        raise ValueError(what + ": box {}: factor row {} has an entry that is not finite".format(int(bad[0, 0]), int(bad[0, 1])))
+    lo, hi = _box_limits(what, lower, upper, M)
+    if lo.shape[0] == 1 and B > 1:
+        lo, hi = np.repeat(lo, B, axis=0), np.repeat(hi, B, axis=0)
+    if lo.shape[0] != B:
+        raise ValueError(what + ": {} factors, one per box, but the limits hold {} boxes".format(B, lo.shape[0]))
+    return (f,) + _box_shift(what, lo, hi, shift)
+
+
+def _box_shift(what, lo, hi, shift):
+    """(lo, hi, shift broadcast to [B, M] or None), the shift checked"""
+    B, M = lo.shape
     if shift is not None:
         sh = np.asarray(shift, dtype=np.float64)
         try:
@@ -1078,7 +1111,7 @@ def _box_problem(what, factor, lower, upper, shift):
         if not np.all(np.isfinite(sh)):
             raise ValueError(what + ": the shift must be finite")
         shift = sh
-    return f, lo, hi, shift
+    return lo, hi, shift
 
 
 def _box_t_streams(what, dof, shift, streams, mix_stream, count, qmc):
@@ -1135,7 +1168,10 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     deviation of the R means over sqrt(R) (NaN for one seed).  A replicate depends on (factor, box, seed, streams, first, n, qmc)
     alone and is bitwise repeatable.
     :param factor: [M, M] lower triangular with a positive diagonal (the upper part is ignored); rows need not have unit norm, so
-        F_c of `conditional_factor` is accepted.  M <= 128
+        F_c of `conditional_factor` is accepted.  M <= 128.  Or [B, M, M]: ONE FACTOR PER BOX, still one device call
+        (mlmc_copula_box_prob_pf_batch and its t twins; every `dof` and `mixing`): box b is integrated through factor[b], as
+        `box_order` and the bootstrap of a correlation matrix need it.  One box of limits pairs with every factor.  A box gives bit
+        for bit what a call with its factor alone gives, and B copies of one factor give what [M, M] gives
     :param lower, upper: broadcast to [B, M], +-inf allowed; a box that is empty in some component has probability exactly 0
     :param n: points per seed, indices first .. first + n - 1; with qmc a power of two with `first` a multiple of it
     :param seeds: R integers in 0 .. 2^64 - 1
@@ -1169,8 +1205,11 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
         raise ValueError(what + ': return_lead needs mixing="conditioned"')
     if dof is None and (mix_stream is not None or return_mixing):
         raise ValueError(what + ": mix_stream and return_mixing need dof (the Gaussian copula has no mixing variable)")
-    f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift)
-    M, B = f.shape[0], lo.shape[0]
+    f, lo, hi, shift = _box_problem(what, factor, lower, upper, shift, per_box=True)
+    M, B = f.shape[-1], lo.shape[0]
+    # one factor per box: the _pf_ entries, which take the distance of the factors (in doubles) behind them
+    stride = (M * M,) if f.ndim == 3 else ()
+    entry = lambda name: getattr(_lib.lib(), name + ("_pf_batch" if stride else "_batch"))          # noqa: E731
     n, seeds, first = _box_call_args(what, n, seeds, first)
     streams = _box_streams(what, streams, 2 if lead and M == 1 else M, qmc)          # the lead of M = 1 has a coordinate
     R = seeds.size
@@ -1178,9 +1217,9 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
     mean = np.empty((R, B))
     if dof is None:
         (integrand,), kind = _output_arrays(device and return_integrand, [(R, B, n) if return_integrand else None])
-        _lib.check(_lib.lib().mlmc_copula_box_prob_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R,
-                                                        _lib.ptr(seeds), _lib.ptr(streams), first, n, flags, _lib.ptr(mean),
-                                                        _lib.ptr(integrand), kind))
+        _lib.check(entry("mlmc_copula_box_prob")(M, _lib.ptr(f), *stride, B, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(shift), R,
+                                                 _lib.ptr(seeds), _lib.ptr(streams), first, n, flags, _lib.ptr(mean),
+                                                 _lib.ptr(integrand), kind))
         result = _joint_probability(mean, n, seeds)
         return (result, integrand) if return_integrand else result
     if lead:
@@ -1190,18 +1229,18 @@ def copula_box_probabilities(factor, lower, upper, n, seeds, shift=None, streams
         (integrand, s, v), kind = _output_arrays(device and (return_integrand or return_mixing or return_lead),
                                                  [(R, B, n) if return_integrand else None, (R, B, n) if return_mixing else None,
                                                   (R, B, n) if return_lead else None])
-        _lib.check(_lib.lib().mlmc_copula_box_prob_tl_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
-                                                           _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
-                                                           _lib.ptr(integrand), _lib.ptr(s), _lib.ptr(v), kind))
+        _lib.check(entry("mlmc_copula_box_prob_tl")(M, _lib.ptr(f), *stride, B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                                    _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
+                                                    _lib.ptr(integrand), _lib.ptr(s), _lib.ptr(v), kind))
         extra = tuple(a for a, want in ((integrand, return_integrand), (s, return_mixing), (v, return_lead)) if want)
         result = _joint_probability(mean, n, seeds)
         return (result,) + extra if extra else result
     streams, mix_stream = _box_t_streams(what, dof, shift, streams, mix_stream, M - 1, qmc)
     (integrand, s), kind = _output_arrays(device and (return_integrand or return_mixing),
                                           [(R, B, n) if return_integrand else None, (R, n) if return_mixing else None])
-    _lib.check(_lib.lib().mlmc_copula_box_prob_t_batch(M, _lib.ptr(f), B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
-                                                      _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
-                                                      _lib.ptr(integrand), _lib.ptr(s), kind))
+    _lib.check(entry("mlmc_copula_box_prob_t")(M, _lib.ptr(f), *stride, B, _lib.ptr(lo), _lib.ptr(hi), dof, R, _lib.ptr(seeds),
+                                               _lib.ptr(streams), mix_stream, first, n, flags, _lib.ptr(mean),
+                                               _lib.ptr(integrand), _lib.ptr(s), kind))
     extra = tuple(v for v, want in ((integrand, return_integrand), (s, return_mixing)) if want)
     result = _joint_probability(mean, n, seeds)
     return (result,) + extra if extra else result
@@ -1287,8 +1326,93 @@ def _lead_groups(lead):
     return [(int(c), np.flatnonzero(lead == c)) for c in np.unique(lead)]
 
 
+BoxOrder = collections.namedtuple("BoxOrder", "perm factor lower upper shift ok")
+
+
+def _box_order_problem(what, cov, lower, upper, shift, first):
+    """(cov [M, M] or [B, M, M] symmetrised, lo, hi, shift or None, first int32 [B] or None) of `box_order`, checked"""
+    c = np.array(cov, dtype=np.float64)
+    if c.ndim not in (2, 3) or c.shape[-1] != c.shape[-2] or c.shape[-1] < 1 or c.shape[0] < 1:
+        raise ValueError(what + ": the covariance must be [M, M] or one per box [B, M, M], got shape {}".format(c.shape))
+    M = c.shape[-1]
+    if M > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} components exceed the cap of {}".format(M, _lib.BOX_PROB_MAX_M))
+    if not np.all(np.isfinite(c)):
+        raise ValueError(what + ": the covariance must be finite")
+    c = np.ascontiguousarray(0.5 * (c + np.swapaxes(c, -1, -2)))
+    lo, hi = _box_limits(what, lower, upper, M)
+    if c.ndim == 3:
+        if lo.shape[0] == 1 and c.shape[0] > 1:
+            lo, hi = np.repeat(lo, c.shape[0], axis=0), np.repeat(hi, c.shape[0], axis=0)
+        if lo.shape[0] != c.shape[0]:
+            raise ValueError(what + ": {} covariances, one per box, but the limits hold {} boxes".format(c.shape[0], lo.shape[0]))
+    lo, hi, shift = _box_shift(what, lo, hi, shift)
+    B = lo.shape[0]
+    if first is not None:
+        fi = np.asarray(first)
+        if fi.dtype.kind not in "iu" or fi.ndim > 1:
+            raise ValueError(what + ": first must hold integers: a component per box, -1 for a free lead")
+        try:
+            fi = np.broadcast_to(fi, (B,))
+        except ValueError:
+            raise ValueError(what + ": first {} does not broadcast to the {} boxes".format(fi.shape, B)) from None
+        bad = np.flatnonzero((fi < -1) | (fi >= M))
+        if bad.size:
+            raise ValueError(what + ": first of box {} is {}: neither -1 nor a component below {}".format(int(bad[0]), int(fi[bad[0]]), M))
+        first = np.ascontiguousarray(fi, dtype=np.int32)
+    return c, lo, hi, shift, first
+
+
+def box_order(cov, lower, upper, shift=None, first=None, check=True):
+    """Genz's VARIABLE REORDERING for `copula_box_probabilities`, for B boxes through ONE device call
+    (mlmc_copula_box_order_batch; Genz 1992, Gibson, Glasbey and Elston 1994): a greedy pivoted Cholesky factorisation of the
+    covariance of the scores.  At every step the remaining component with the smallest expected conditional width
+    Phi(b) - Phi(a) (given the expected values of the components already placed) is integrated next; ties go to the lowest
+    original index.  The probability of a box does not depend on the order of its components; the variance of the chain's estimate
+    does, by orders of magnitude where the limits are heterogeneous and the components correlated.  Everything is in NORMAL-SCORE
+    space.  The result goes to `copula_box_probabilities(order.factor, order.lower, order.upper, ..., shift=order.shift)`:
+    one factor per box.
+    :param cov: [M, M] symmetric positive definite (it is symmetrised), or one per box [B, M, M].  M <= 128
+    :param lower, upper: broadcast to [B, M], +-inf allowed
+    :param shift: None or the mean of the scores, broadcast to [B, M]
+    :param first: None, or integers broadcast to [B]: the component that is forced to lead its box, -1 for a free choice
+    :param check: raise ValueError for a box whose factorisation met a pivot that is not positive (names the box); False: see `ok`
+    :return: BoxOrder(perm [B, M] int32: perm[b, i] is the original component at position i; factor [B, M, M]: the lower-triangular
+        factor of cov[perm][:, perm]; lower, upper [B, M] and shift ([B, M] or None) permuted; ok [B] bool)"""
+    what = "box_order"
+    problem = _box_order_problem(what, cov, lower, upper, shift, first)
+    # host arrays, all of them: this entry takes no device memory
+    c = np.ascontiguousarray(problem[0])
+    lo = np.ascontiguousarray(problem[1])
+    hi = np.ascontiguousarray(problem[2])
+    sh = None if problem[3] is None else np.ascontiguousarray(problem[3])
+    lead = None if problem[4] is None else np.ascontiguousarray(problem[4])
+    B, M = lo.shape
+    perm = np.empty((B, M), dtype=np.int32)
+    factor = np.empty((B, M, M))
+    ok = np.empty(B, dtype=np.int32)
+    _lib.check(_lib.lib().mlmc_copula_box_order_batch(M, _lib.ptr(c), M * M if c.ndim == 3 else 0, B, _lib.ptr(lo), _lib.ptr(hi),
+                                                     _lib.ptr(sh), _lib.ptr(lead), _lib.ptr(perm), _lib.ptr(factor), _lib.ptr(ok)))
+    fine = ok != 0
+    if check and not np.all(fine):
+        raise ValueError(what + ": box {}: the covariance is not positive definite (a pivot of the factorisation is not positive)".format(
+            int(np.flatnonzero(~fine)[0])))
+    take = lambda x: None if x is None else np.ascontiguousarray(np.take_along_axis(x, perm.astype(np.int64), axis=1))   # noqa: E731
+    return BoxOrder(perm, factor, take(lo), take(hi), take(sh), fine)
+
+
+def _check_order(what, order, out_of_scope=None):
+    """True for order="genz", checked; out_of_scope: why this entry cannot reorder (it then raises for "genz")"""
+    if order not in ("natural", "genz"):
+        raise ValueError(what + ': order must be "natural" or "genz", got {!r}'.format(order))
+    if order == "genz" and out_of_scope:
+        raise ValueError(what + ': order="genz" is out of scope here: ' + out_of_scope)
+    return order == "genz"
+
+
 def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True,
-                        return_integrand=False, device=False, dof=None, mix_stream=None, mixing="plain"):
+                        return_integrand=False, device=False, dof=None, mix_stream=None, mixing="plain", order="natural",
+                        return_order=False):
     """Joint box probabilities P(lower_m < X_m < upper_m for all m) under the Gaussian copula of `joint_samples`, for B boxes in
     the components' own units through `copula_box_probabilities`; with `given`, conditional on the given values of some
     components as in `conditional_samples`.  A limit that is +-inf or lies at or beyond an end of its distribution's domain is an
@@ -1312,14 +1436,28 @@ def joint_probabilities(distrs, lower, upper, n, seeds, corr=None, factor=None, 
         dropped, the lead of each box is the component with the smallest marginal probability (`lead_components`; ties: the lowest
         index); boxes are grouped by lead with one device call per group, the correlation permuted lead-first and refactored on the
         host.  streams[0] is then the lead's coordinate, streams[i] that of the i-th other constrained component, ascending.  Out of
-        scope: `given` (raises: the conditional family keeps plain mixing) and Genz's full reordering beyond the lead
+        scope: `given` (raises: the conditional family keeps plain mixing); the order BEHIND the lead is the caller's unless
+        order="genz"
+    :param order: "natural" (default): the constrained components are integrated in the caller's order (behind the lead, under
+        mixing="conditioned"), bit for bit what this entry has always returned.  "genz": Genz's variable reordering (`box_order`)
+        of the constrained components of EVERY box, then ONE device call with one factor per box.  The probability needs no
+        un-permuting.  With `given` the conditional covariance F_c F_c^T and the conditional means go to `box_order`.  Under `dof`
+        the ORDER is computed on the NORMAL scores of the limits with the same correlation matrix (the t scores of deep limits are
+        far too large for normal widths to tell the components apart); the chain then runs on the t scores in that order.  Every
+        order is unbiased: this one is a heuristic for the variance.  With mixing="conditioned" the lead of `lead_components` is
+        forced to position 0 and the others are ordered behind it, so the groups by lead collapse into one call.  streams[i]
+        belongs to POSITION i of the order: the lowest Sobol' dimensions go to the components integrated first.  It helps where the
+        limits are heterogeneous and the components correlated; independent components gain nothing (their widths do not depend on
+        the points)
+    :param return_order: also return, last, perm [B, k] int64: the ORIGINAL index (into `distrs`) of the component at each position
+        of the chain of every box, k the number of constrained components
     :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
     return _joint_probabilities("joint_probabilities", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc,
-                                return_integrand, device, dof, mix_stream, mixing)
+                                return_integrand, device, dof, mix_stream, mixing, order, return_order)
 
 
 def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, return_integrand,
-                         device, dof, mix_stream, mixing="plain"):
+                         device, dof, mix_stream, mixing="plain", order="natural", return_order=False):
     """the one body of `joint_probabilities` and `conditional_probabilities` (conditional: the second one, where dof with given
     components goes through `conditional_box_probabilities`); the argument errors come in the order they have always had"""
     distrs = list(distrs)
@@ -1331,6 +1469,8 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
     else:
         dof = _box_dof(what, dof, mix_stream, given)
     lead = _check_mixing(what, mixing, dof, None, given)
+    genz = _check_order(what, order, "a conditional law of the t copula (the _tc_ entries) keeps one shared factor"
+                        if conditional and dof is not None else None)
     if (corr is None) == (factor is None):
         raise ValueError(what + ": exactly one of corr and factor must be given")
     n, seeds, first = _box_call_args(what, n, seeds, first)
@@ -1363,10 +1503,43 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
         streams, mix_stream = _box_t_streams(what, dof, None, streams, mix_stream, max(keep.size - 1, 1 if lead else 0), qmc)
     if keep.size > _lib.BOX_PROB_MAX_M:
         raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
+
+    def with_order(out, perm):
+        if not return_order:
+            return out
+        return out + (perm,) if type(out) is tuple else (out, perm)
+
     if keep.size == 0:
         ones = _joint_probability(np.ones((seeds.size, B)), n, seeds)
-        return (ones, None) if return_integrand else ones
+        return with_order((ones, None) if return_integrand else ones, np.zeros((B, 0), dtype=np.int64))
     finish()
+    comp = free[keep]
+    if genz:
+        # the order of every box from the NORMAL scores of its limits (under dof too: a heuristic, every order is unbiased), then
+        # one device call with one factor per box
+        n_lo, n_hi = z_lo[:, keep], z_hi[:, keep]
+        if observed.size:
+            _, _, _, _, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
+            cov = (fc @ fc.T)[np.ix_(keep, keep)]
+            shift = np.ascontiguousarray(np.broadcast_to(mu[:, keep], (B, keep.size)))
+        else:
+            low = correlation_factor(corr[np.ix_(comp, comp)])[0]
+            cov, shift = low @ low.T, None
+        force = None
+        if dof is not None:
+            t_lo, t_hi = t_scores(n_lo, dof), t_scores(n_hi, dof)
+            if lead:
+                force = lead_components(t_lo, t_hi, dof)[0]
+        ordered = box_order(cov, n_lo, n_hi, shift=shift, first=force)
+        at = ordered.perm.astype(np.int64)
+        if dof is None:
+            b_lo, b_hi = ordered.lower, ordered.upper
+        else:
+            b_lo, b_hi = np.take_along_axis(t_lo, at, axis=1), np.take_along_axis(t_hi, at, axis=1)
+        out = copula_box_probabilities(ordered.factor, b_lo, b_hi, n, [int(s) for s in seeds], shift=ordered.shift, streams=streams,
+                                       first=first, qmc=qmc, return_integrand=return_integrand, device=device, dof=dof,
+                                       mix_stream=mix_stream, mixing=mixing)
+        return with_order(out, comp[at])
     if dof is not None:
         z_lo, z_hi = t_scores(z_lo, dof), t_scores(z_hi, dof)
     if lead:
@@ -1375,9 +1548,11 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
         R = seeds.size
         replicates = np.empty((R, B))
         integrand = None
+        perm = np.empty((B, keep.size), dtype=np.int64)
         for c, boxes in _lead_groups(lead_components(t_lo, t_hi, dof)[0]):
             order = np.concatenate([[c], np.delete(np.arange(keep.size), c)])
             comp = free[keep][order]
+            perm[boxes] = comp
             low = correlation_factor(corr[np.ix_(comp, comp)])[0]
             out = copula_box_probabilities(low, t_lo[np.ix_(boxes, order)], t_hi[np.ix_(boxes, order)], n, [int(s) for s in seeds],
                                            streams=streams, first=first, qmc=qmc, return_integrand=return_integrand, device=device,
@@ -1390,17 +1565,18 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
                 if boxes.size != B:
                     integrand[:, boxes.tolist() if device else boxes, :] = f
         result = _joint_probability(replicates, n, seeds)
-        return (result, integrand) if return_integrand else result
+        return with_order((result, integrand) if return_integrand else result, perm)
+    natural = np.ascontiguousarray(np.broadcast_to(comp, (B, keep.size)))
     if observed.size and dof is not None:
         cond = conditional_factor(corr, observed, return_observed=True)
         _, _, _, _, (_, fc, _), mu, r = _conditioning(what, distrs, given, None, cond, dof)
         cov = fc @ fc.T
         low = np.linalg.cholesky(cov[np.ix_(keep, keep)])
         shift = np.ascontiguousarray(np.broadcast_to(mu[:, keep], (B, keep.size)))
-        return conditional_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], dof,
-                                             dof_mix=dof + observed.size, shift=shift, scale=np.broadcast_to(r, (B,)), streams=streams,
-                                             first=first, qmc=qmc, return_integrand=return_integrand, device=device,
-                                             mix_stream=mix_stream)
+        return with_order(conditional_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], dof,
+                                                        dof_mix=dof + observed.size, shift=shift, scale=np.broadcast_to(r, (B,)),
+                                                        streams=streams, first=first, qmc=qmc, return_integrand=return_integrand,
+                                                        device=device, mix_stream=mix_stream), natural)
     if observed.size:
         _, _, _, _, (_, fc, _), mu, _ = _conditioning(what, distrs, given, corr, None)
         cov = fc @ fc.T
@@ -1409,9 +1585,70 @@ def _joint_probabilities(what, conditional, distrs, lower, upper, n, seeds, corr
     else:
         low = correlation_factor(corr[np.ix_(free[keep], free[keep])])[0]
         shift = None
-    return copula_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], shift=shift, streams=streams,
-                                    first=first, qmc=qmc, return_integrand=return_integrand, device=device, dof=dof,
-                                    mix_stream=mix_stream)
+    return with_order(copula_box_probabilities(low, z_lo[:, keep], z_hi[:, keep], n, [int(s) for s in seeds], shift=shift,
+                                               streams=streams, first=first, qmc=qmc, return_integrand=return_integrand, device=device,
+                                               dof=dof, mix_stream=mix_stream), natural)
+
+
+def joint_probabilities_over_correlations(distrs, lower, upper, n, seeds, corrs, first=0, qmc=True, dof=None, order="natural"):
+    """`joint_probabilities(distrs, lower, upper, n, seeds, corr=corrs[c], dof=dof)` for EVERY correlation matrix of corrs [C, M, M]
+    through ONE device call: the limits map to scores once (they do not depend on the correlation), every matrix is factored on the
+    host, and the C x B (correlation, box) pairs are the boxes of one `copula_box_probabilities` call with one factor per box.  A
+    replicate depends on (factor, box, seed, streams, first, n, qmc) alone, so result c is bit for bit that of the single call.
+    Made for bootstrap replicates of a correlation matrix (Estimate.bootstrap_joint_probability).
+    :param corrs: [C, M, M]; corrs[0] must factor (its error is raised); another matrix whose `correlation_factor` raises is not ok
+    :param order: "natural" or "genz" (`box_order` for every pair, still one chain call), as in `joint_probabilities`
+    :return: (results: a list of C JointProbability, None where not ok; ok [C] bool)"""
+    what = "joint_probabilities_over_correlations"
+    distrs = list(distrs)
+    M = len(distrs)
+    if M == 0:
+        raise ValueError(what + ": no distributions")
+    dof = _box_dof(what, dof, None, None)
+    genz = _check_order(what, order)
+    n, seeds, first = _box_call_args(what, n, seeds, first)
+    _common_quadrature(what, distrs)
+    corrs = np.asarray(corrs, dtype=np.float64)
+    if corrs.ndim != 3 or corrs.shape[0] < 1 or corrs.shape[1:] != (M, M):
+        raise ValueError(what + ": corrs must be [C, M, M] with M = {} distributions, got shape {}".format(M, corrs.shape))
+    lo, hi = _box_limits(what, lower, upper, M)
+    B, C = lo.shape[0], corrs.shape[0]
+    z_lo, z_hi, keep, finish = _limit_scores(what, distrs, lo, hi)
+    streams = _box_streams(what, None, max(keep.size, 1), qmc)
+    mix_stream = None
+    if dof is not None:
+        streams, mix_stream = _box_t_streams(what, dof, None, streams, None, max(keep.size - 1, 0), qmc)
+    if keep.size > _lib.BOX_PROB_MAX_M:
+        raise ValueError(what + ": {} constrained components exceed the cap of {}".format(keep.size, _lib.BOX_PROB_MAX_M))
+    ok = np.ones(C, dtype=bool)
+    if keep.size == 0:
+        return [_joint_probability(np.ones((seeds.size, B)), n, seeds) for _ in range(C)], ok
+    finish()
+    n_lo, n_hi = z_lo[:, keep], z_hi[:, keep]
+    lows = []
+    for c in range(C):
+        try:
+            lows.append(correlation_factor(corrs[c][np.ix_(keep, keep)])[0])
+        except Exception:
+            if c == 0:
+                raise
+            ok[c] = False
+    lows = np.repeat(np.array(lows), B, axis=0)                                     # pair (c, b) at c * B + b
+    b_lo, b_hi = np.tile(n_lo, (int(ok.sum()), 1)), np.tile(n_hi, (int(ok.sum()), 1))
+    if genz:
+        ordered = box_order(lows @ np.swapaxes(lows, 1, 2), b_lo, b_hi)
+        lows, at = ordered.factor, ordered.perm.astype(np.int64)
+        b_lo, b_hi = np.take_along_axis(b_lo, at, axis=1), np.take_along_axis(b_hi, at, axis=1)
+    if dof is not None:
+        b_lo, b_hi = t_scores(b_lo, dof), t_scores(b_hi, dof)
+    reps = copula_box_probabilities(lows, b_lo, b_hi, n, [int(s) for s in seeds], streams=streams, first=first, qmc=qmc, dof=dof,
+                                    mix_stream=mix_stream).replicates
+    # the statistics of a result from an array laid out as the single call has it
+    results, k = [None] * C, 0
+    for c in np.flatnonzero(ok):
+        results[c] = _joint_probability(np.ascontiguousarray(reps[:, k * B:(k + 1) * B]), n, seeds)
+        k += 1
+    return results, ok
 
 
 BoxDraws = collections.namedtuple("BoxDraws", "z u weights prob")
@@ -1569,7 +1806,7 @@ def conditional_box_draws(factor, lower, upper, n, seeds, dof, dof_mix=None, shi
 
 
 def conditional_probabilities(distrs, lower, upper, given, n, seeds, corr=None, factor=None, dof=None, streams=None, first=0, qmc=True,
-                              return_integrand=False, device=False, mix_stream=None):
+                              return_integrand=False, device=False, mix_stream=None, order="natural", return_order=False):
     """Joint box probabilities of the components that are NOT in `given`, conditional on the given values of the others: the
     probability member of the conditional family (`conditional_samples`, `conditional_quantiles`, `conditional_cdfs`).  With dof
     None (or np.inf) this is `joint_probabilities(given=...)`, bit for bit, through the same body.  With dof, a float in [1, 64],
@@ -1582,13 +1819,15 @@ def conditional_probabilities(distrs, lower, upper, given, n, seeds, corr=None, 
     :param given: the mapping of `conditional_samples` (required); arrays [B] pair with the boxes (one box pairs with all sets)
     :param corr, factor: as in `joint_probabilities`; with dof the t copula's correlation matrix
     :param streams, mix_stream: per coordinate of the REDUCED problem, and the mixing stream, as in `joint_probabilities(dof=...)`
+    :param order, return_order: as in `joint_probabilities`.  order="genz" works under the Gaussian copula (dof None); with dof it
+        raises: the conditional t entries keep one shared factor
     :return: JointProbability; a call that constrains nothing returns ones without a device call (and no integrand: None)"""
     return _joint_probabilities("conditional_probabilities", True, distrs, lower, upper, n, seeds, corr, factor, given, streams, first,
-                                qmc, return_integrand, device, dof, mix_stream)
+                                qmc, return_integrand, device, dof, mix_stream, "plain", order, return_order)
 
 
 def conditional_event_samples(distrs, lower, upper, given, n, seeds, corr=None, factor=None, streams=None, first=0, qmc=True,
-                              device=False, dof=None, mix_stream=None):
+                              device=False, dof=None, mix_stream=None, order="natural"):
     """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m AND the given values of some components.  With dof
     None (or np.inf) this is `event_samples(given=...)`, bit for bit, through the same body.  With dof the copula is the Student-t
     copula, as in `conditional_probabilities`: the chain order of `event_samples`, `conditional_box_draws` with shift = mu,
@@ -1597,7 +1836,9 @@ def conditional_event_samples(distrs, lower, upper, given, n, seeds, corr=None, 
     there.
     :param lower, upper: broadcast to [B, M] in the components' own units; a given component must not be constrained
     :param given: the mapping of `conditional_samples` (required)
+    :param order: "natural"; "genz" raises, as in `event_samples`
     :return: EventScenarios"""
+    _check_order("conditional_event_samples", order, _DRAWS_ORDER)
     return _event_samples("conditional_event_samples", True, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc,
                           device, dof, mix_stream)
 
@@ -1662,8 +1903,11 @@ class EventScenarios:
         return out
 
 
+_DRAWS_ORDER = "the draws entries keep one shared factor (`joint_probabilities(order=\"genz\")` reorders the probability)"
+
+
 def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=None, streams=None, first=0, qmc=True, device=False,
-                  dof=None, mix_stream=None, mixing="plain"):
+                  dof=None, mix_stream=None, mixing="plain", order="natural"):
     """Joint scenarios of ALL components GIVEN the event lower_m < X_m < upper_m for all m, under the marginals and the Gaussian
     copula of `joint_samples`, for B events and R seeds through `copula_box_draws` and ONE `quantiles` call: what the system
     looks like when the event of `joint_probabilities` happens.  Every scenario lies in the event and carries a weight; rejection
@@ -1691,7 +1935,10 @@ def event_samples(distrs, lower, upper, n, seeds, corr=None, factor=None, given=
         the front of the chain order above, boxes are grouped by lead with one device call per group, and draws, uniforms and
         weights come back in the components' own order.  `prob` is bit for bit that of `joint_probabilities(mixing="conditioned")`
         where no component is dropped there.  Out of scope: `given` (raises) and reordering beyond the lead
+    :param order: "natural" (the order above); "genz" raises: the draws entries keep one shared factor, so a per-box order cannot be
+        expressed
     :return: EventScenarios"""
+    _check_order("event_samples", order, _DRAWS_ORDER)
     return _event_samples("event_samples", False, distrs, lower, upper, n, seeds, corr, factor, given, streams, first, qmc, device, dof,
                           mix_stream, mixing)
 

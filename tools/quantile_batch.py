@@ -158,10 +158,17 @@ and once with the Gaussian model alone (G = 1), the routes of a shape taking tur
                                columns (the composition is linear in n; the whole of it would take minutes), and that over entry_ms
   torch_ms, torch_over_entry   G = 1 only: torch.special.ndtri + torch.linalg.solve_triangular + the two sums, on the device
   max_abs_difference_from_host / _from_torch   the largest difference of a log density from the composition's
+--boxorder: boxes under equicorrelation 1/2 whose lower limits rise from -2 to 2.5 over the components, each
+box rotated by its index; the routes of a shape taking turns after a warm-up call each:
+  boxorder_kernel   order_ms: box_order alone (upload, the order kernel, download, one wait) for M = 12 / 64 / 128 and B = 1 / 64 / 300
+  boxorder_call     ordered_ms: box_order followed by copula_box_probabilities with one factor per box; natural_ms: the call with one
+                    shared factor in the caller's order; prob / stderr and natural_prob / natural_stderr of box 0
+  boxorder_bands    one_call_ms: joint_probabilities_over_correlations over 301 correlation matrices at M = 12; loop_ms: the loop of 301
+                    joint_probabilities calls that it replaces; bit_identical: every replicate of the two is the same
 Prints one JSON line.  Usage: python tools/quantile_batch.py [--quick | --config B,R1,n | --single]
                                                              [--tails | --divergences | --moments | --samples | --joint | --tcopula | --tconditional | --scores |
                                                               --conditional | --qmc | --boxprob | --boxdraws | --tboxprob | --tcondbox | --tlead | --aggregates |
-                                                              --concordance | --loglik] [--reps K]"""
+                                                              --concordance | --loglik | --boxorder] [--reps K]"""
 import argparse
 import ctypes as C
 import json
@@ -923,6 +930,70 @@ def tlead_shape(M, B, n, reps, t, dof, seeds=tuple(range(1, 9))):
                 plain_prob=float("%.6g" % got["p"].prob[0]), plain_stderr=float("%.3g" % got["p"].stderr[0]), plain_ess_fraction=ess())
 
 
+def _ascending_problem(M, B):
+    """B boxes under equicorrelation 1/2 whose lower limits rise from -2 to 2.5 over the components (no upper limits), each box
+    rotated by its index so that the boxes differ: the case `asc` of DESIGN.md 3.5.28 at any M"""
+    corr = np.full((M, M), 0.5)
+    np.fill_diagonal(corr, 1.0)
+    lo = np.stack([np.roll(np.linspace(-2.0, 2.5, M), b) for b in range(B)])
+    return corr, lo, np.full((B, M), np.inf)
+
+
+def boxorder_kernel_shape(M, B, reps):
+    """box_order alone (upload, the order kernel, download, one wait) for B boxes of M components, one shared covariance"""
+    corr, lo, hi = _ascending_problem(M, B)
+    wall = _turns((lambda: sd.box_order(corr, lo, hi),), reps)
+    return dict(M=M, B=B, order_ms=wall[0])
+
+
+def boxorder_call_shape(M, B, n, reps, seeds=tuple(range(1, 9))):
+    """the reordered chain call (box_order, then copula_box_probabilities with one factor per box) against the natural call of the
+    same shape (one shared factor), the two taking turns in one process, with the probability and standard error of box 0"""
+    corr, lo, hi = _ascending_problem(M, B)
+    low = np.linalg.cholesky(corr)
+    got = {}
+
+    def ordered_route():
+        o = sd.box_order(corr, lo, hi)
+        got["o"] = sd.copula_box_probabilities(o.factor, o.lower, o.upper, n, seeds)
+
+    def natural_route():
+        got["n"] = sd.copula_box_probabilities(low, lo, hi, n, seeds)
+    wall = _turns((ordered_route, natural_route), reps)
+    return dict(M=M, B=B, n=n, R=len(seeds), ordered_ms=wall[0], natural_ms=wall[1],
+                ordered_over_natural_wall=round(wall[0][1] / wall[1][1], 3), prob=float("%.6g" % got["o"].prob[0]),
+                stderr=float("%.3g" % got["o"].stderr[0]), natural_prob=float("%.6g" % got["n"].prob[0]),
+                natural_stderr=float("%.3g" % got["n"].stderr[0]))
+
+
+def boxorder_bands_shape(M, B, n, reps, seeds=tuple(range(1, 9))):
+    """the bands of a joint exceedance over B replicate correlation matrices: ONE call with one factor per box
+    (joint_probabilities_over_correlations) against the loop of B + 1 joint_probabilities calls that it replaces, the two taking
+    turns in one process; the replicates are perturbed equicorrelation matrices, the marginals uniform"""
+    from scipy.special import ndtr
+    from tests import score_cases as sk
+    distrs = [sk.closed_distribution(0.0, (0.0, 1.0)) for _ in range(M)]
+    rng = np.random.default_rng(17)
+    corrs = []
+    for _ in range(B + 1):
+        a = np.linalg.cholesky(_ascending_problem(M, 1)[0]) @ rng.standard_normal((M, 40 * M))
+        c = np.corrcoef(a)
+        corrs.append(0.5 * (c + c.T))
+    corrs = np.array(corrs)
+    x = ndtr(np.linspace(-1.0, 1.5, M))
+    got = {}
+
+    def one_call():
+        got["one"] = sd.joint_probabilities_over_correlations(distrs, x, np.inf, n, seeds, corrs)[0]
+
+    def loop():
+        got["loop"] = [sd.joint_probabilities(distrs, x, np.inf, n, seeds, corr=c) for c in corrs]
+    wall = _turns((one_call, loop), reps)
+    same = all(np.array_equal(a.replicates, b.replicates) for a, b in zip(got["one"], got["loop"]))
+    return dict(M=M, replicates=B, n=n, R=len(seeds), one_call_ms=wall[0], loop_ms=wall[1],
+                loop_over_one_call_wall=round(wall[1][1] / wall[0][1], 2), bit_identical=bool(same))
+
+
 def _tcond_problem(M, B, t):
     """B boxes (t, inf)^M in t-score space under equicorrelation 1/2, each with the conditional location and scale of its own given
     t score of one further component: y_O in (0, 3], mu = y_O / 2, r^2 = (nu + y_O^2) / (nu + 1) with nu filled in by the caller"""
@@ -1305,6 +1376,8 @@ def main():
                     "against the t entries of the same shapes (DESIGN.md section 3.5.26)")
     ap.add_argument("--tlead", action="store_true", help='copula_box_probabilities(dof = 3, 30, mixing="conditioned") against the plain t '
                     "call of the same shapes: time, prob, stderr and ess / n of both (DESIGN.md section 3.5.27)")
+    ap.add_argument("--boxorder", action="store_true", help="box_order alone, the reordered chain call against the natural one, and the "
+                    "one-call bands against the loop of calls (DESIGN.md section 3.5.28)")
     ap.add_argument("--aggregates", action="store_true", help="mlmc_scenario_aggregates against the torch composition on a materialised "
                                                               "scenario matrix (DESIGN.md section 3.5.20)")
     ap.add_argument("--concordance", action="store_true", help="concordance_counts against the torch composition of indicator matrices and "
@@ -1343,6 +1416,15 @@ def main():
             shapes = [(1, 12, 10_000), (3, 5, 1_000)]
         _lib.use_torch_stream()
         out["aggregates"] = [aggregates_shape(S, M, n, a.reps) for S, M, n in shapes]
+    elif a.boxorder:
+        kernel = [(M, B) for M in (12, 64, 128) for B in (1, 64, 300)]
+        calls = [(12, 1, 2 ** 12), (12, 64, 2 ** 12), (12, 300, 2 ** 12), (64, 64, 2 ** 12), (12, 1, 2 ** 16)]
+        bands = [(12, 300, 2 ** 12)]
+        if a.quick:
+            kernel, calls, bands = [(12, 3), (65, 2)], [(12, 3, 2 ** 10)], [(3, 8, 2 ** 10)]
+        out["boxorder_kernel"] = [boxorder_kernel_shape(M, B, a.reps) for M, B in kernel]
+        out["boxorder_call"] = [boxorder_call_shape(M, B, n, a.reps) for M, B, n in calls]
+        out["boxorder_bands"] = [boxorder_bands_shape(M, B, n, a.reps) for M, B, n in bands]
     elif a.tlead:
         t6 = brentq(lambda t: np.log(equicorrelated_exceedance(12, t)) - np.log(1e-6), 0.0, 6.0, xtol=1e-10)
         shapes = [(M, 1, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16, 20)] + [(M, 64, 2 ** k, 0.0) for M in (2, 12, 64) for k in (12, 16)]
